@@ -12,6 +12,7 @@ the timed region), `roofline.pipelined` the rate of the timed region.
 
     python bench.py                      # 1 GPU: cfg2, 32 blocks x 1024 bins resident; also.cfg3, also.cfg5, cpu_baseline
     python bench.py --gpus N             # N GPUs of this node: the program starts its own N ranks (below)
+    python bench.py --dump-outputs DIR   # also write the last timed step's filters and status words as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N         # the same under an external launcher
 
@@ -709,6 +710,30 @@ def dryrun_rank():
                           "local_rank": int(os.environ.get("LOCAL_RANK", "-1"))}), flush=True)
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """arrays: name -> array with the bin as its first axis.  Each is written as <directory>/<name>.npy in float32 (complex
+    values as a trailing (re, im) axis).  Past DUMP_LIMIT bytes in all, the same fixed, seeded sample of bins is kept of every
+    array and its bin indices go to <directory>/bin_index.npy.  Returns {name: shape written}."""
+    os.makedirs(directory, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = (np.stack([a.real, a.imag], axis=-1) if np.iscomplexobj(a) else a).astype(np.float32)
+    n_bins = next(iter(conv.values())).shape[0]
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT:
+        keep = (DUMP_LIMIT - 4096) // (total // n_bins + 8)  # 8: the bin's index in float64; 4096: the .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n_bins, size=keep, replace=False))
+        conv = {k: a[idx] for k, a in conv.items()}
+        conv["bin_index"] = idx.astype(np.float64)
+    for name, a in conv.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in conv.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -728,6 +753,9 @@ def main():
     ap.add_argument("--no-also", action="store_true", help="skip the cfg3 / cfg5 sub-records of the 1-GPU line")
     ap.add_argument("--also-only", default=None, choices=ALSO_RECORDS, help="(internal) compute one sub-record and print it")
     ap.add_argument("--also-device", type=int, default=0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (filters, per-bin status) as DIR/<name>.npy "
+                         "in float32, at most 64 MB in all (rank 0; at N GPUs the gathered filter bank alone)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not os.environ.get("APV_BENCH_FORCE_DIST"):
@@ -863,6 +891,16 @@ def main():
     kern_ms = eng.timer_stop() / args.steps       # waits for the last update kernel(s) only
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path receives from its last step, read outside the timed region: the filters and the
+        # per-bin status words; at N GPUs the gathered filter bank (the ranks' shards in rank order)
+        nr = len(ranks)
+        if multi:
+            dumped = {"w": dw_all.download((world * K, nr, L), np.complex64)}
+        else:
+            dumped = {"w": last_out[0].download((K, nr, L), np.complex64),
+                      "status": (dstatus if (flip[0] - 1) % 2 == 0 else dstatus2).download((K,), np.int32)}
     # roofline leg of a pipelined run: the duration of a launch ALONE (what rocprofv3's kernel trace calls its duration) cannot be
     # read off overlapping launches, so the same launches run once more on ONE stream between the same HIP events, straight
     # behind the timed region (clocks as they are); with --update-streams 1 the timed region itself is that measurement.
@@ -953,6 +991,9 @@ def main():
             out["gather_check"] = gather_check
             out["collective_bytes_per_rank"] = gather_bytes
             out["collective_gbps_per_link"] = gather_bytes / (gather_ms * 1e-3) / 1e9 if gather_ms > 0 else None
+
+    if dumped is not None:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, dumped)
 
     # the headline's buffers go before the sub-records allocate theirs
     for b in [dXB, dXD, dd, dstatus, dstatus2, dw_all] + dws:

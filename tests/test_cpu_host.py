@@ -293,6 +293,28 @@ def test_host_cores_counts_what_the_box_grants():
     assert n <= info.get("affinity_cpus", n) or info.get("override")
 
 
+def test_bench_dump_outputs_float32_within_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: complex arrays as a trailing (re, im) float32 axis; past the size limit, one fixed, seeded
+    sample of bins for every array, the same from call to call, with its bin indices."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    w = (rng.standard_normal((4096, 1, 16)) + 1j * rng.standard_normal((4096, 1, 16))).astype(np.complex64)
+    st = np.arange(4096, dtype=np.int32)
+    shapes = bench.dump_outputs(str(tmp_path / "full"), {"w": w, "status": st})
+    assert shapes == {"w": [4096, 1, 16, 2], "status": [4096]}
+    got = np.load(tmp_path / "full" / "w.npy")
+    assert got.dtype == np.float32 and np.array_equal(got[..., 0] + 1j * got[..., 1], w)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 128 << 10)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"w": w, "status": st})
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_LIMIT
+    idx = np.load(tmp_path / "a" / "bin_index.npy")
+    assert 0 < len(idx) < 4096 and np.array_equal(idx, np.load(tmp_path / "b" / "bin_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "w.npy"), got[idx.astype(np.int64)])
+
+
 def test_bench_and_package_do_not_import_torch():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "import torch" not in src
