@@ -6,8 +6,8 @@
 //            live in registers, one column / one row is broadcast through LDS per step      apvast.py:22-27
 //   stage 2  C = W R_B W^H                         two complex MFMA products                 apvast.py:28-29
 //   stage 3  eigenvectors of C                                                                apvast.py:30
-//            float64: a float32 pre-solve on packed math -- ONE-SIDED Jacobi on the float Cholesky factor of C (column
-//            rotations only, gevd16_common.h) -- then one or two refinement steps of its eigenvector matrix on the f64 MFMA
+//            float64: a float32 pre-solve -- Householder tridiagonal, Sturm multisection and inverse iteration
+//            (tridiag_presolve16) -- then one or two refinement steps of its eigenvector matrix on the f64 MFMA
 //            (four complex products each, Ogita & Aishima 2018); a wave whose spectrum has a gap too narrow for that
 //            orthonormalises exactly, re-forms C on the MFMA and runs register-resident double sweeps (XOR pairing schedule)
 //            float32: the one-sided Jacobi is the solve
@@ -24,6 +24,194 @@
 #include "gevd16_common.h"
 
 namespace {
+
+// ---- float32 pre-solve of the float64 kernel: Householder tridiagonal, Sturm multisection, inverse iteration ----------------
+// (NumPy model with the same steps and counts: tools/probes/tridiag_presolve_model.py)
+// sum over the sixteen lanes that share lane & 3 (lane = 4 i + jq), in all of them
+__device__ __forceinline__ float tp_sum_rows(float v) {
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xf, 0xf, false));      // row_ror:8
+    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x124, 0xf, 0xf, false));      // row_ror:4
+    v += __shfl_xor(v, 16, 64);
+    return v + __shfl_xor(v, 32, 64);
+}
+__device__ __forceinline__ float tp_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+constexpr int kTpSteps = 10;            // multisection steps: the interval shrinks 5x per step, 5^-10 ~ 1e-7 of ||C||
+constexpr int LDQ = 17, LDX = 17;       // row strides of the float Q and X in the pre-solve's LDS scratch
+
+// In: C (float64, LDS row stride LD) scaled by 2^sexp, normS2 = ||2^sexp C||_F^2.  Scratch: fQ (16 x LDQ complex), fX (16 x LDX
+// real), hv / hw (16 complex each).  Out: V32 (eigenvectors of C in float32, the f32 MFMA accumulator layout: v[t] is element
+// (mfma_row<float>(lane, t), lane & 15)), and whether its spectrum is fit for the one-step refinement (finite, spread < 1e3).
+template <typename TS>
+__device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, float normS2, Cx<float>* fQ, float* fX,
+                                                   Cx<float>* hv, Cx<float>* hw, int lane, Cx<float> v32[4]) {
+    using CF = Cx<float>;
+    const int i = lane >> 2, jq = lane & 3;
+    // ---- 1. Q^H C Q = T, real tridiagonal (LAPACK zhetd2 form: H_k = I - tau v v^H with complex tau and real beta; the last
+    // reflector, k = 14, is a pure phase).  Lane (i, jq) holds A[i][jq + 4 t] and Q[i][jq + 4 t].  The rank-2 updates run on
+    // whole rows: rows and columns <= k only collect garbage that is never read again (v is zero there).
+    CF a[4], q[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const Cx<TS> c = sA[i * LD + jq + 4 * t];
+        a[t] = mk<float>(scale_to_f32(c.x, sexp), scale_to_f32(c.y, sexp));
+        q[t] = mk<float>((jq + 4 * t == i) ? 1.f : 0.f, 0.f);
+    }
+    float e[N - 1];                                                        // sub-diagonal (wave-uniform)
+#pragma unroll
+    for (int k = 0; k < N - 1; ++k) {
+        const int tk = k >> 2, jk = k & 3;
+        const CF ak = a[tk];                                               // A[i][k] in the lanes jq == jk
+        const float xn2 = tp_lane(tp_sum_rows((jq == jk && i > k + 1) ? ak.x * ak.x + ak.y * ak.y : 0.f), jk);
+        const float alr = tp_lane(ak.x, 4 * (k + 1) + jk), ali = tp_lane(ak.y, 4 * (k + 1) + jk);
+        if (xn2 == 0.f && ali == 0.f) { e[k] = alr; continue; }            // nothing to annihilate: H_k = I
+        const float nrm = sqrtf(fmaf(alr, alr, fmaf(ali, ali, xn2)));
+        const float beta = uniform_scalar(alr >= 0.f ? -nrm : nrm);
+        const float rb = rcp_full(beta);
+        const float taur = uniform_scalar((beta - alr) * rb), taui = uniform_scalar(-ali * rb);
+        const float dr = alr - beta;
+        const float rdd = rcp_full(fmaf(dr, dr, ali * ali));
+        const float sr = uniform_scalar(dr * rdd), si = uniform_scalar(-ali * rdd);      // 1 / (alpha - beta)
+        e[k] = beta;
+        // v = (0 .. 0, 1, x / (alpha - beta)) to LDS
+        if (jq == jk) hv[i] = (i > k + 1) ? mk<float>(ak.x * sr - ak.y * si, ak.x * si + ak.y * sr) : mk<float>(i == k + 1 ? 1.f : 0.f, 0.f);
+        wsync();
+        const CF vi = hv[i];
+        CF vj[4];
+        float pr = 0.f, pi = 0.f, ur = 0.f, ui = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (4 * t + 3 <= k) continue;                                  // v is zero there
+            vj[t] = hv[jq + 4 * t];
+            pr = fmaf(a[t].x, vj[t].x, fmaf(-a[t].y, vj[t].y, pr));       // (A v)_i
+            pi = fmaf(a[t].x, vj[t].y, fmaf(a[t].y, vj[t].x, pi));
+            ur = fmaf(q[t].x, vj[t].x, fmaf(-q[t].y, vj[t].y, ur));       // (Q v)_i
+            ui = fmaf(q[t].x, vj[t].y, fmaf(q[t].y, vj[t].x, ui));
+        }
+        pr += xcol<1>(pr); pi += xcol<1>(pi); ur += xcol<1>(ur); ui += xcol<1>(ui);
+        pr += xcol<2>(pr); pi += xcol<2>(pi); ur += xcol<2>(ur); ui += xcol<2>(ui);
+        // w = tau A v + kappa v with kappa = -tau/2 (tau A v)^H v = -|tau|^2 / 2 v^H A v (real: A is Hermitian)
+        const float vav = tp_lane(tp_sum_rows(jq == 0 ? fmaf(pr, vi.x, pi * vi.y) : 0.f), 0);
+        const float kap = -0.5f * fmaf(taur, taur, taui * taui) * vav;
+        const CF wi = mk<float>(fmaf(taur, pr, fmaf(-taui, pi, kap * vi.x)), fmaf(taur, pi, fmaf(taui, pr, kap * vi.y)));
+        const CF tu = mk<float>(taur * ur - taui * ui, taur * ui + taui * ur);              // tau (Q v)_i
+        if (jq == 0) hw[i] = wi;
+        wsync();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (4 * t + 3 <= k) continue;
+            const CF wj = hw[jq + 4 * t];
+            // A -= v w^H + w v^H;  Q -= (tau Q v) v^H
+            a[t].x -= fmaf(vi.x, wj.x, fmaf(vi.y, wj.y, fmaf(wi.x, vj[t].x, wi.y * vj[t].y)));
+            a[t].y -= fmaf(vi.y, wj.x, fmaf(-vi.x, wj.y, fmaf(wi.y, vj[t].x, -wi.x * vj[t].y)));
+            q[t].x -= fmaf(tu.x, vj[t].x, tu.y * vj[t].y);
+            q[t].y -= fmaf(tu.y, vj[t].x, -tu.x * vj[t].y);
+        }
+    }
+    float d[N];                                                            // diagonal (wave-uniform)
+#pragma unroll
+    for (int m = 0; m < N; ++m) d[m] = uniform_scalar(tp_lane(a[m >> 2].x, 4 * m + (m & 3)));
+#pragma unroll
+    for (int t = 0; t < 4; ++t) fQ[i * LDQ + jq + 4 * t] = q[t];        // Q to LDS for the back-transform
+
+    // ---- 2. eigenvalue m = i by multisection: lane (i, jq) counts the eigenvalues below lo + (jq + 1) (hi - lo) / 5.  C is positive
+    // semi-definite with ||C|| <= ||C||_F, so the spectrum lies in [-1e-3, 1.001] ||C||_F
+    const float nrmF = sqrtf(normS2);
+    float e2[N - 1];
+#pragma unroll
+    for (int m = 0; m < N - 1; ++m) e2[m] = uniform_scalar(fmaxf(e[m] * e[m], 1e-30f));     // (0 * inf would be NaN)
+    float lo = -1e-3f * nrmF, hi = 1.001f * nrmF;
+    const float frac = 0.2f * (float)(jq + 1);
+#pragma unroll 1
+    for (int st = 0; st < kTpSteps; ++st) {
+        const float x = fmaf(hi - lo, frac, lo);
+        // Sturm count: the negative pivots of T - x I.  A zero pivot gives rcp = inf, the next pivot -inf (counted), rcp(-inf) = -0
+        float qv = d[0] - x;
+        int cnt = qv < 0.f;
+#pragma unroll
+        for (int m = 1; m < N; ++m) {
+            qv = fmaf(-e2[m - 1], __builtin_amdgcn_rcpf(qv), d[m] - x);
+            cnt += qv < 0.f;
+        }
+        // points at or below eigenvalue i raise lo, the others lower hi (monotone in jq: min / max over the quad)
+        float nlo = (cnt <= i) ? x : lo, nhi = (cnt <= i) ? hi : x;
+        nlo = fmaxf(nlo, xcol<1>(nlo)); nhi = fminf(nhi, xcol<1>(nhi));
+        lo = fmaxf(nlo, xcol<2>(nlo)); hi = fminf(nhi, xcol<2>(nhi));
+    }
+    const float lam = 0.5f * (lo + hi);
+
+    // ---- 3. eigenvector i: two inverse-iteration steps on T - lam I, unpivoted L D L^T (pivots kept at least 1e-9 ||C|| away from
+    // zero), start vector ones + e_i, normalised after each step.  No reorthogonalisation: the refinement's E = V^H V - I takes it.
+    float l[N - 1], rdg[N], xv[N];
+    {
+        const float tiny = 1e-9f * nrmF;
+        float piv = d[0] - lam;
+#pragma unroll
+        for (int m = 0; m < N; ++m) {
+            if (m > 0) piv = fmaf(-e[m - 1], l[m - 1], d[m] - lam);
+            piv = copysignf(fmaxf(fabsf(piv), tiny), piv);
+            rdg[m] = rcp_full(piv);
+            if (m < N - 1) l[m] = e[m] * rdg[m];
+        }
+    }
+    float nrm2 = 0.f;
+#pragma unroll
+    for (int m = 0; m < N; ++m) xv[m] = (m == i) ? 2.f : 1.f;         // distinct starts: a double eigenvalue gets two vectors
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        if (it > 0) {
+            const float s = rsq_full(nrm2);
+#pragma unroll
+            for (int m = 0; m < N; ++m) xv[m] *= s;
+        }
+#pragma unroll
+        for (int m = 1; m < N; ++m) xv[m] = fmaf(-l[m - 1], xv[m - 1], xv[m]);      // L y = b
+        xv[N - 1] *= rdg[N - 1];
+#pragma unroll
+        for (int m = N - 2; m >= 0; --m) xv[m] = fmaf(-l[m], xv[m + 1], xv[m] * rdg[m]);   // D L^T x = y
+        nrm2 = 0.f;
+#pragma unroll
+        for (int m = 0; m < N; ++m) nrm2 = fmaf(xv[m], xv[m], nrm2);
+    }
+    const bool finite = nrm2 > 0.f && nrm2 < 3.0e38f;
+    {
+        const float s = rsq_full(nrm2);
+#pragma unroll
+        for (int m = 0; m < N; ++m) xv[m] *= s;
+    }
+    if (jq == 0) {
+#pragma unroll
+        for (int m = 0; m < N; ++m) fX[m * LDX + i] = xv[m];
+    }
+    // eigenvalues closer than 1e-5 ||C|| (none on the bench data) may leave nearly parallel vectors, and the double-sweep fall-back
+    // after the refinement only orthonormalises V32: it cannot restore a direction V32 lacks.  Such a bin is not trusted (double
+    // sweeps on C itself), like a rank-deficient one.
+    const float gap = __shfl_down(lam, 4, 64) - lam;
+    const bool apart = i == N - 1 || gap > 1e-5f * nrmF;
+    // spread of the spectrum, as the one-sided solve's gate (any NaN, a non-finite vector or a close pair fails it)
+    float mn = finite ? lam : __int_as_float(0x7fc00000), mx = mn;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        mn = fminf(mn, __shfl_xor(mn, o, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    }
+    const bool ok = !__any(!(mn >= 1e-3f * mx) || !finite || !apart);
+    wsync();
+
+    // ---- 4. V32 = Q X on the f32 matrix cores (X is real: eight products)
+    f4 re = {0, 0, 0, 0}, im = {0, 0, 0, 0};
+    const int rc = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const CF qa = fQ[rc * LDQ + 4 * s + kq];
+        const float xb = fX[(4 * s + kq) * LDX + rc];
+        re = __builtin_amdgcn_mfma_f32_16x16x4f32(qa.x, xb, re, 0, 0, 0);
+        im = __builtin_amdgcn_mfma_f32_16x16x4f32(qa.y, xb, im, 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v32[t] = mk<float>(re[t], im[t]);
+    return ok;
+}
 
 // XT: element type of the fused input slabs (float2 = c64, double2 = c128: the float64 streaming front-end)
 // DBG: the diagnostic instantiation.  It alone carries the run-time `debug_stop` tests (stage cuts and A/B switches of the
@@ -225,8 +413,8 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
         };
         if constexpr (sizeof(T) == 8) {
             // ---- float32 pre-solve (debug_stop == 4 skips it: double sweeps only, for A/B timing) -------------------
-            // The sweeps are the cost of the kernel and packed-float ones cost a fraction of double ones, so C is first
-            // diagonalised in float32: V32 with V32^H C V32 diagonal to ~1e-7.  V32 is then refined against the exact float64 C on
+            // Double sweeps would be the cost of the kernel, so C is first diagonalised in float32: V32 with V32^H C V32 diagonal
+            // to ~1e-7.  V32 is then refined against the exact float64 C on
             // the matrix cores (below); W waits in registers meanwhile.
             if (dstop != 4) {
                 using CF = Cx<float>;
@@ -236,9 +424,22 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 constexpr float kPresolveTol2 = 1e-6f;
                 CF f0t, f0b, f1t, f1b;
                 bool fconv = false, trust = true;
-                int fs;
+                int fs = 0;
                 int va = a, vb = b;                                                   // (row pair, slot) of this lane's part of V32
-                if (dstop != 11) {
+                CF v32[4];
+                // debug_stop 11-14 and 20-49 (diagnostic instantiation only): the earlier pre-solves, for A/B timing -- 11 the
+                // two-sided float sweeps of round 2a, 14 the one-sided form (12 and 13 stop after its factor and after its sweeps,
+                // 20 + e sets its tolerance 1e-e, 30-49 fine steps of it)
+                const bool legacy = DBG && ((dstop >= 11 && dstop <= 14) || (dstop >= 20 && dstop <= 49));
+                if (!legacy) {
+                    // Householder tridiagonal, multisection and inverse iteration (tridiag_presolve16); its scratch is sB, free until V32
+                    // lands there (W waits in registers), and the spent Cholesky column staging
+                    CF* const fQ = reinterpret_cast<CF*>(&sB[0]);
+                    CF* const hv = reinterpret_cast<CF*>(&scol[0][0]);
+                    trust = tridiag_presolve16<T>(sA, sexp, (float)normS2, fQ, reinterpret_cast<float*>(fQ + N * LDQ), hv, hv + N, lane, v32);
+                    stamp(4);
+                    stamp(5);
+                } else if (dstop != 11) {
                     // one-sided form on the float Cholesky factor of 2^sexp C + delta I (same eigenvectors; the shift keeps the
                     // float pivots positive when C is singular to float precision).  The factor goes through sB, which is free
                     // until V32 lands there (W waits in registers), its column staging through the spent Cholesky staging.
@@ -286,10 +487,15 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 const int mcol = lane & 15;
                 auto cj = [](C w) { return mk<T>(w.x, -w.y); };
                 wsync();
-                sB[(2 * va) * LD + fit] = mk<T>((T)f0t.x, (T)f0t.y);                // V32 takes W's place
-                sB[(2 * va) * LD + fib] = mk<T>((T)f0b.x, (T)f0b.y);
-                sB[(2 * va + 1) * LD + fit] = mk<T>((T)f1t.x, (T)f1t.y);
-                sB[(2 * va + 1) * LD + fib] = mk<T>((T)f1b.x, (T)f1b.y);
+                if (!legacy) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) sB[mfma_row<float>(lane, t) * LD + mcol] = mk<T>((T)v32[t].x, (T)v32[t].y);   // V32 takes W's place
+                } else {
+                    sB[(2 * va) * LD + fit] = mk<T>((T)f0t.x, (T)f0t.y);
+                    sB[(2 * va) * LD + fib] = mk<T>((T)f0b.x, (T)f0b.y);
+                    sB[(2 * va + 1) * LD + fit] = mk<T>((T)f1t.x, (T)f1t.y);
+                    sB[(2 * va + 1) * LD + fib] = mk<T>((T)f1b.x, (T)f1b.y);
+                }
                 wsync();
                 C accT[4], accG[4], accC[4], accV[4];
                 cmm16([&](int r, int kx) { return sA[r * LD + kx]; }, [&](int kx, int c) { return sB[kx * LD + c]; }, lane, accT);       // C V

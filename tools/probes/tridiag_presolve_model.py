@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""NumPy model of the float32 TRIDIAGONAL pre-solve of the float64 order-16 kernel (kernels_gevd16m.hip, stage 3), batched
+over bins and in the kernel's order of operations:
+
+  1. Householder reduction of 2^sexp C to a REAL tridiagonal T = Q^H C Q in float32 (LAPACK zhetd2 form: complex tau,
+     15 reflectors, the last one a pure phase), Q accumulated as Q H_0 H_1 ... H_14;
+  2. eigenvalues by Sturm-count multisection: 4 points per eigenvalue per step (the interval shrinks 5x), NSTEP steps,
+     q_i = (a_i - x) - e_{i-1}^2 rcp(q_{i-1});
+  3. eigenvectors by two inverse-iteration steps on T - lam I, unpivoted L D L^T (the Sturm recurrence at the shift), start
+     vector ones + e_m, normalised after each step;
+     eigenvalues closer than 1e-5 ||C|| (none on the bench data) send the bin to the double sweeps in the kernel;
+  4. V32 = Q X.
+
+It prints the share of bins whose refinement matrix Z_ij = (S_ij - d_j E_ij) / (d_j - d_i), taken in float64 against the
+exact C, meets the kernel's one-step guard |Z| <= 3e-5 and its second-step limit 1e-2, on bench.synth(K, 1234).
+
+    python tools/probes/tridiag_presolve_model.py [K] [NSTEP]
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+
+f32 = np.float32
+N = 16
+
+
+def make_C(K, seed=1234, reg=1e-7):
+    from bench import synth
+    XB, XD, _ = synth(K, seed)
+    XB = XB.astype(np.complex128)
+    XD = XD.astype(np.complex128)
+    RB = XB.conj().transpose(0, 2, 1) @ XB
+    RD = XD.conj().transpose(0, 2, 1) @ XD + reg * np.eye(N)
+    W = np.linalg.inv(np.linalg.cholesky(RD))
+    C = W @ RB @ W.conj().transpose(0, 2, 1)
+    return 0.5 * (C + C.conj().transpose(0, 2, 1))
+
+
+def tridiag(A):
+    """A: [K,16,16] complex64, Hermitian.  Returns a (diag), e (sub-diagonal, real), Q (complex64) with Q^H A Q = T."""
+    K = A.shape[0]
+    A = A.copy()
+    Q = np.broadcast_to(np.eye(N, dtype=np.complex64), A.shape).copy()
+    e = np.zeros((K, N - 1), f32)
+    for k in range(N - 1):
+        alpha = A[:, k + 1, k].copy()
+        x = A[:, k + 2:, k]
+        xn2 = (x.real * x.real + x.imag * x.imag).sum(1, dtype=f32).astype(f32)
+        al2 = (alpha.real * alpha.real + alpha.imag * alpha.imag).astype(f32)
+        trivial = (xn2 == 0) & (alpha.imag == 0)
+        nrm = np.sqrt(al2 + xn2).astype(f32)
+        beta = np.where(alpha.real >= 0, -nrm, nrm).astype(f32)
+        beta = np.where(trivial, alpha.real, beta).astype(f32)
+        rb = np.where(trivial, f32(0), f32(1) / np.where(beta == 0, f32(1), beta)).astype(f32)
+        tau = ((beta - alpha) * rb).astype(np.complex64)                 # (beta - alpha) / beta
+        tau = np.where(trivial, np.complex64(0), tau)
+        d = (alpha - beta).astype(np.complex64)
+        dd = (d.real * d.real + d.imag * d.imag).astype(f32)
+        rdd = np.where(trivial, f32(0), f32(1) / np.where(dd == 0, f32(1), dd)).astype(f32)
+        s = (np.conj(d) * rdd).astype(np.complex64)                      # 1 / (alpha - beta)
+        v = np.zeros((K, N), np.complex64)
+        v[:, k + 1] = 1
+        v[:, k + 2:] = (x * s[:, None]).astype(np.complex64)
+        e[:, k] = beta
+        p = (tau[:, None] * np.einsum("kij,kj->ki", A, v)).astype(np.complex64)
+        kap = (f32(-0.5) * tau * np.einsum("ki,ki->k", p.conj(), v)).astype(np.complex64)
+        w = (p + kap[:, None] * v).astype(np.complex64)
+        A = (A - v[:, :, None] * w.conj()[:, None, :] - w[:, :, None] * v.conj()[:, None, :]).astype(np.complex64)
+        u = np.einsum("kij,kj->ki", Q, v).astype(np.complex64)
+        Q = (Q - (tau[:, None] * u)[:, :, None] * v.conj()[:, None, :]).astype(np.complex64)
+    a = np.einsum("kii->ki", A).real.astype(f32)
+    return a, e, Q
+
+
+def sturm_count(a, e2, x):
+    """number of eigenvalues below x; a [K,16], e2 [K,15], x [K,...]"""
+    q = (a[:, 0, None] - x).astype(f32)
+    cnt = (q < 0).astype(np.int32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for i in range(1, N):
+            r = (f32(1) / q).astype(f32)
+            q = ((a[:, i, None] - x) - e2[:, i - 1, None] * r).astype(f32)
+            cnt += np.signbit(q)
+    return cnt
+
+
+def multisection(a, e, nrm, nstep):
+    K = a.shape[0]
+    e2 = np.maximum(e * e, f32(1e-30)).astype(f32)
+    lo = np.broadcast_to((f32(-1e-3) * nrm)[:, None], (K, N)).astype(f32).copy()
+    hi = np.broadcast_to((f32(1.001) * nrm)[:, None], (K, N)).astype(f32).copy()
+    m = np.arange(N)
+    for _ in range(nstep):
+        h = ((hi - lo) * f32(0.2)).astype(f32)
+        pts = (lo[:, :, None] + h[:, :, None] * np.arange(1, 5, dtype=f32)).astype(f32)     # [K,16,4]
+        c = sturm_count(a, e2, pts.reshape(K, -1)).reshape(K, N, 4)
+        below = c <= m[None, :, None]                                   # eigenvalue m lies above this point
+        nb = below.sum(2)                                               # points at or below lam_m (monotone)
+        new_lo = np.where(nb > 0, np.take_along_axis(pts, np.maximum(nb - 1, 0)[:, :, None], 2)[:, :, 0], lo)
+        new_hi = np.where(nb < 4, np.take_along_axis(pts, np.minimum(nb, 3)[:, :, None], 2)[:, :, 0], hi)
+        lo, hi = new_lo.astype(f32), new_hi.astype(f32)
+    return ((lo + hi) * f32(0.5)).astype(f32)
+
+
+def inverse_iteration(a, e, lam, nrm, steps=2, tiny_rel=1e-9):
+    """X [K,16 (row),16 (eigenvalue)]"""
+    K = a.shape[0]
+    tiny = (f32(tiny_rel) * nrm)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d = np.empty((K, N, N), f32)                                    # [K, i, m]
+        l = np.empty((K, N - 1, N), f32)
+        q = (a[:, 0, None] - lam).astype(f32)
+        for i in range(N):
+            if i > 0:
+                q = ((a[:, i, None] - lam) - e[:, i - 1, None] * l[:, i - 1]).astype(f32)
+            q = np.where(np.abs(q) < tiny, np.where(q < 0, -tiny, tiny), q).astype(f32)
+            d[:, i] = q
+            if i < N - 1:
+                l[:, i] = (e[:, i, None] * (f32(1) / q)).astype(f32)
+        rd = (f32(1) / d).astype(f32)
+        x = (np.ones((N, N), f32) + np.eye(N, dtype=f32))[None].repeat(K, 0)     # ones + e_m: distinct per eigenvalue
+        for _ in range(steps):
+            y = x.copy()
+            for i in range(1, N):
+                y[:, i] = (y[:, i] - l[:, i - 1] * y[:, i - 1]).astype(f32)
+            z = (y * rd).astype(f32)
+            for i in range(N - 2, -1, -1):
+                z[:, i] = (z[:, i] - l[:, i] * z[:, i + 1]).astype(f32)
+            s = (z * z).sum(1, dtype=f32).astype(f32)
+            x = (z / np.sqrt(s)[:, None, :]).astype(f32)
+    return x
+
+
+def presolve(C, nstep):
+    nf2 = (np.abs(C) ** 2).sum((1, 2))
+    sexp = -(np.frexp(nf2)[1] - 1) // 2
+    A = (C * np.ldexp(1.0, sexp)[:, None, None]).astype(np.complex64)
+    nrm = np.sqrt(np.ldexp(nf2, 2 * sexp)).astype(f32)
+    a, e, Q = tridiag(A)
+    lam = multisection(a, e, nrm, nstep)
+    X = inverse_iteration(a, e, lam, nrm)
+    V = (Q @ X.astype(np.complex64)).astype(np.complex64)
+    trust = lam.min(1) >= 1e-3 * lam.max(1)
+    return V, lam, trust, (a, e, Q, A)
+
+
+def zmax(C, V):
+    V = V.astype(np.complex128)
+    S = V.conj().transpose(0, 2, 1) @ C @ V
+    G = V.conj().transpose(0, 2, 1) @ V
+    E = G - np.eye(N)
+    dq = np.einsum("kii->ki", S).real / np.einsum("kii->ki", G).real
+    num = S - dq[:, None, :] * E
+    den = dq[:, None, :] - dq[:, :, None]
+    np.einsum("kii->ki", den)[:] = 1
+    Z = np.abs(num / den)
+    np.einsum("kii->ki", Z)[:] = 0
+    return Z.max((1, 2))
+
+
+def main():
+    K = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
+    nstep = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    C = make_C(K)
+    V, lam, trust, (a, e, Q, A) = presolve(C, nstep)
+    # the reduction itself: Q^H A Q tridiagonal and real
+    T = Q.conj().transpose(0, 2, 1).astype(np.complex128) @ A.astype(np.complex128) @ Q.astype(np.complex128)
+    Tm = np.zeros_like(T)
+    idx = np.arange(N)
+    Tm[:, idx, idx] = a
+    Tm[:, idx[1:], idx[:-1]] = e
+    Tm[:, idx[:-1], idx[1:]] = e
+    nrm = np.sqrt((np.abs(A.astype(np.complex128)) ** 2).sum((1, 2)))
+    print(f"bins {K}, multisection steps {nstep}")
+    print(f"reduction: max |Q^H A Q - T| / ||A|| = {(np.abs(T - Tm).max((1, 2)) / nrm).max():.2e}, "
+          f"max |Q^H Q - I| = {np.abs(Q.conj().transpose(0, 2, 1) @ Q - np.eye(N)).max():.2e}")
+    lref = np.linalg.eigvalsh(C)
+    sc = nrm / np.sqrt((np.abs(C) ** 2).sum((1, 2)))
+    print(f"eigenvalues: max |lam - lam_ref| / ||C|| = {(np.abs(np.sort(lam, 1) / sc[:, None] - lref).max(1) * sc / nrm).max():.2e}")
+    z = zmax(C, V)
+    t = trust
+    print(f"trusted {t.mean() * 100:.2f} %")
+    print(f"|Z| <= 3e-5: {(z[t] <= 3e-5).mean() * 100:.2f} % of trusted bins, <= 1e-2: {(z[t] <= 1e-2).mean() * 100:.3f} %")
+    print(f"max |Z| median / p99 / max: {np.median(z[t]):.2e} / {np.quantile(z[t], 0.99):.2e} / {z[t].max():.2e}")
+
+
+if __name__ == "__main__":
+    main()
