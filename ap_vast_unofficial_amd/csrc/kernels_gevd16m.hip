@@ -27,24 +27,38 @@ namespace {
 
 // ---- float32 pre-solve of the float64 kernel: Householder tridiagonal, Sturm multisection, inverse iteration ----------------
 // (NumPy model with the same steps and counts: tools/probes/tridiag_presolve_model.py)
-// sum over the sixteen lanes that share lane & 3 (lane = 4 i + jq), in all of them
-__device__ __forceinline__ float tp_sum_rows(float v) {
+// sum over the four lanes of a quad (one matrix row), in all of them
+__device__ __forceinline__ float tp_sum_quad(float v) { v += xcol<1>(v); return v + xcol<2>(v); }
+__device__ __forceinline__ float tp_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+// v of lane `src` (ds_bpermute: a crossbar trip, no LDS storage and no barrier)
+__device__ __forceinline__ float tp_from(float v, int src) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v))); }
+// v of lane (lane & ~3) + j of the quad (quad_perm [j,j,j,j]; j a constant once the reflector loop is unrolled)
+__device__ __forceinline__ float tp_quad_bcast(float v, int j) {
+    const int x = __float_as_int(v);
+    return __int_as_float(j == 0 ? __builtin_amdgcn_mov_dpp(x, 0x00, 0xf, 0xf, false) : j == 1 ? __builtin_amdgcn_mov_dpp(x, 0x55, 0xf, 0xf, false)
+                          : j == 2 ? __builtin_amdgcn_mov_dpp(x, 0xAA, 0xf, 0xf, false) : __builtin_amdgcn_mov_dpp(x, 0xFF, 0xf, 0xf, false));
+}
+// sum over the sixteen quads of a value every lane of a quad holds, in all lanes, on the VALU: row_ror 8 and 4 inside a 16-lane
+// row, v_permlane16_swap and v_permlane32_swap across rows
+__device__ __forceinline__ float tp_sum_quads(float v) {
     v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xf, 0xf, false));      // row_ror:8
     v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x124, 0xf, 0xf, false));      // row_ror:4
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
+    const auto r16 = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
+    v = __int_as_float((int)r16[0]) + __int_as_float((int)r16[1]);
+    const auto r32 = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
+    return __int_as_float((int)r32[0]) + __int_as_float((int)r32[1]);
 }
-__device__ __forceinline__ float tp_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
 constexpr int kTpSteps = 10;            // multisection steps: the interval shrinks 5x per step, 5^-10 ~ 1e-7 of ||C||
 constexpr int LDQ = 17, LDX = 17;       // row strides of the float Q and X in the pre-solve's LDS scratch
 
 // In: C (float64, LDS row stride LD) scaled by 2^sexp, normS2 = ||2^sexp C||_F^2.  Scratch: fQ (16 x LDQ complex), fX (16 x LDX
-// real), hv / hw (16 complex each).  Out: V32 (eigenvectors of C in float32, the f32 MFMA accumulator layout: v[t] is element
+// real).  Out: V32 (eigenvectors of C in float32, the f32 MFMA accumulator layout: v[t] is element
 // (mfma_row<float>(lane, t), lane & 15)), and whether its spectrum is fit for the one-step refinement (finite, spread < 1e3).
-template <typename TS>
+// `stamp` (diagnostic instantiation): slots 4 after the reduction, 13 after the multisection, 14 after the inverse iteration, 5 at the end.
+template <typename TS, typename ST = NoStamp>
 __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, float normS2, Cx<float>* fQ, float* fX,
-                                                   Cx<float>* hv, Cx<float>* hw, int lane, Cx<float> v32[4]) {
+                                                   int lane, Cx<float> v32[4], ST stamp = ST()) {
     using CF = Cx<float>;
     const int i = lane >> 2, jq = lane & 3;
     // ---- 1. Q^H C Q = T, real tridiagonal (LAPACK zhetd2 form: H_k = I - tau v v^H with complex tau and real beta; the last
@@ -57,53 +71,67 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
         a[t] = mk<float>(scale_to_f32(c.x, sexp), scale_to_f32(c.y, sexp));
         q[t] = mk<float>((jq + 4 * t == i) ? 1.f : 0.f, 0.f);
     }
+    // The norm of the column below the sub-diagonal and alpha come from row k (its conjugate), which quad k holds: a quad sum and
+    // readlanes.  v and w are formed once per row (quad i) and every lane fetches the entries of its own columns jq + 4 t from quad
+    // jq + 4 t (ds_bpermute: one crossbar trip each, no LDS storage, no barrier); v^H A v is summed over the quads on the VALU.
     float e[N - 1];                                                        // sub-diagonal (wave-uniform)
 #pragma unroll
     for (int k = 0; k < N - 1; ++k) {
-        const int tk = k >> 2, jk = k & 3;
-        const CF ak = a[tk];                                               // A[i][k] in the lanes jq == jk
-        const float xn2 = tp_lane(tp_sum_rows((jq == jk && i > k + 1) ? ak.x * ak.x + ak.y * ak.y : 0.f), jk);
-        const float alr = tp_lane(ak.x, 4 * (k + 1) + jk), ali = tp_lane(ak.y, 4 * (k + 1) + jk);
-        if (xn2 == 0.f && ali == 0.f) { e[k] = alr; continue; }            // nothing to annihilate: H_k = I
+        const int t0 = (k + 1) >> 2;                                       // slots 0 .. t0-1 lie in columns <= k: v is zero there
+        const int k1 = k + 1, tk = k >> 2, jk = k & 3;
+        float xs = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (t >= t0) xs += (jq + 4 * t > k1) ? fmaf(a[t].x, a[t].x, a[t].y * a[t].y) : 0.f;
+        const float xn2 = tp_lane(tp_sum_quad(xs), 4 * k);
+        const float alr = tp_lane(a[k1 >> 2].x, 4 * k + (k1 & 3)), ali = -tp_lane(a[k1 >> 2].y, 4 * k + (k1 & 3));
+        // A[i][k] to every lane of quad i
+        const float akx = tp_quad_bcast(a[tk].x, jk), aky = tp_quad_bcast(a[tk].y, jk);
+        // nothing to annihilate: H_k = I (tau = 0 and v = e_{k+1} make the updates below exact no-ops)
+        const bool triv = xn2 == 0.f && ali == 0.f;
         const float nrm = sqrtf(fmaf(alr, alr, fmaf(ali, ali, xn2)));
-        const float beta = uniform_scalar(alr >= 0.f ? -nrm : nrm);
+        const float beta = uniform_scalar(triv ? alr : alr >= 0.f ? -nrm : nrm);
         const float rb = rcp_full(beta);
-        const float taur = uniform_scalar((beta - alr) * rb), taui = uniform_scalar(-ali * rb);
+        const float taur = uniform_scalar(triv ? 0.f : (beta - alr) * rb), taui = uniform_scalar(triv ? 0.f : -ali * rb);
         const float dr = alr - beta;
         const float rdd = rcp_full(fmaf(dr, dr, ali * ali));
-        const float sr = uniform_scalar(dr * rdd), si = uniform_scalar(-ali * rdd);      // 1 / (alpha - beta)
+        const float sr = uniform_scalar(triv ? 0.f : dr * rdd), si = uniform_scalar(triv ? 0.f : -ali * rdd);      // 1 / (alpha - beta)
         e[k] = beta;
-        // v = (0 .. 0, 1, x / (alpha - beta)) to LDS
-        if (jq == jk) hv[i] = (i > k + 1) ? mk<float>(ak.x * sr - ak.y * si, ak.x * si + ak.y * sr) : mk<float>(i == k + 1 ? 1.f : 0.f, 0.f);
-        wsync();
-        const CF vi = hv[i];
+        // v = (0 .. 0, 1, x / (alpha - beta)): v_i in quad i, then this lane's columns from quads jq + 4 t
+        const CF vi = (i > k1) ? mk<float>(akx * sr - aky * si, akx * si + aky * sr) : mk<float>(i == k1 ? 1.f : 0.f, 0.f);
         CF vj[4];
         float pr = 0.f, pi = 0.f, ur = 0.f, ui = 0.f;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            if (4 * t + 3 <= k) continue;                                  // v is zero there
-            vj[t] = hv[jq + 4 * t];
+            if (t < t0) continue;
+            vj[t] = mk<float>(tp_from(vi.x, 4 * (jq + 4 * t)), tp_from(vi.y, 4 * (jq + 4 * t)));
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (t < t0) continue;
             pr = fmaf(a[t].x, vj[t].x, fmaf(-a[t].y, vj[t].y, pr));       // (A v)_i
             pi = fmaf(a[t].x, vj[t].y, fmaf(a[t].y, vj[t].x, pi));
             ur = fmaf(q[t].x, vj[t].x, fmaf(-q[t].y, vj[t].y, ur));       // (Q v)_i
             ui = fmaf(q[t].x, vj[t].y, fmaf(q[t].y, vj[t].x, ui));
         }
-        pr += xcol<1>(pr); pi += xcol<1>(pi); ur += xcol<1>(ur); ui += xcol<1>(ui);
-        pr += xcol<2>(pr); pi += xcol<2>(pi); ur += xcol<2>(ur); ui += xcol<2>(ui);
+        pr = tp_sum_quad(pr); pi = tp_sum_quad(pi); ur = tp_sum_quad(ur); ui = tp_sum_quad(ui);
         // w = tau A v + kappa v with kappa = -tau/2 (tau A v)^H v = -|tau|^2 / 2 v^H A v (real: A is Hermitian)
-        const float vav = tp_lane(tp_sum_rows(jq == 0 ? fmaf(pr, vi.x, pi * vi.y) : 0.f), 0);
+        const float vav = tp_sum_quads(fmaf(pr, vi.x, pi * vi.y));
         const float kap = -0.5f * fmaf(taur, taur, taui * taui) * vav;
         const CF wi = mk<float>(fmaf(taur, pr, fmaf(-taui, pi, kap * vi.x)), fmaf(taur, pi, fmaf(taui, pr, kap * vi.y)));
         const CF tu = mk<float>(taur * ur - taui * ui, taur * ui + taui * ur);              // tau (Q v)_i
-        if (jq == 0) hw[i] = wi;
-        wsync();
+        CF wj[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            if (4 * t + 3 <= k) continue;
-            const CF wj = hw[jq + 4 * t];
+            if (t < t0) continue;
+            wj[t] = mk<float>(tp_from(wi.x, 4 * (jq + 4 * t)), tp_from(wi.y, 4 * (jq + 4 * t)));
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (t < t0) continue;
             // A -= v w^H + w v^H;  Q -= (tau Q v) v^H
-            a[t].x -= fmaf(vi.x, wj.x, fmaf(vi.y, wj.y, fmaf(wi.x, vj[t].x, wi.y * vj[t].y)));
-            a[t].y -= fmaf(vi.y, wj.x, fmaf(-vi.x, wj.y, fmaf(wi.y, vj[t].x, -wi.x * vj[t].y)));
+            a[t].x -= fmaf(vi.x, wj[t].x, fmaf(vi.y, wj[t].y, fmaf(wi.x, vj[t].x, wi.y * vj[t].y)));
+            a[t].y -= fmaf(vi.y, wj[t].x, fmaf(-vi.x, wj[t].y, fmaf(wi.y, vj[t].x, -wi.x * vj[t].y)));
             q[t].x -= fmaf(tu.x, vj[t].x, tu.y * vj[t].y);
             q[t].y -= fmaf(tu.y, vj[t].x, -tu.x * vj[t].y);
         }
@@ -113,6 +141,7 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
     for (int m = 0; m < N; ++m) d[m] = uniform_scalar(tp_lane(a[m >> 2].x, 4 * m + (m & 3)));
 #pragma unroll
     for (int t = 0; t < 4; ++t) fQ[i * LDQ + jq + 4 * t] = q[t];        // Q to LDS for the back-transform
+    stamp(4);
 
     // ---- 2. eigenvalue m = i by multisection: lane (i, jq) counts the eigenvalues below lo + (jq + 1) (hi - lo) / 5.  C is positive
     // semi-definite with ||C|| <= ||C||_F, so the spectrum lies in [-1e-3, 1.001] ||C||_F
@@ -139,6 +168,7 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
         lo = fmaxf(nlo, xcol<2>(nlo)); hi = fminf(nhi, xcol<2>(nhi));
     }
     const float lam = 0.5f * (lo + hi);
+    stamp(13);
 
     // ---- 3. eigenvector i: two inverse-iteration steps on T - lam I, unpivoted L D L^T (pivots kept at least 1e-9 ||C|| away from
     // zero), start vector ones + e_i, normalised after each step.  No reorthogonalisation: the refinement's E = V^H V - I takes it.
@@ -183,6 +213,7 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
 #pragma unroll
         for (int m = 0; m < N; ++m) fX[m * LDX + i] = xv[m];
     }
+    stamp(14);
     // eigenvalues closer than 1e-5 ||C|| (none on the bench data) may leave nearly parallel vectors, and the double-sweep fall-back
     // after the refinement only orthonormalises V32: it cannot restore a direction V32 lacks.  Such a bin is not trusted (double
     // sweeps on C itself), like a rank-deficient one.
@@ -210,6 +241,7 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) v32[t] = mk<float>(re[t], im[t]);
+    stamp(5);
     return ok;
 }
 
@@ -433,12 +465,9 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 const bool legacy = DBG && ((dstop >= 11 && dstop <= 14) || (dstop >= 20 && dstop <= 49));
                 if (!legacy) {
                     // Householder tridiagonal, multisection and inverse iteration (tridiag_presolve16); its scratch is sB, free until V32
-                    // lands there (W waits in registers), and the spent Cholesky column staging
+                    // lands there (W waits in registers)
                     CF* const fQ = reinterpret_cast<CF*>(&sB[0]);
-                    CF* const hv = reinterpret_cast<CF*>(&scol[0][0]);
-                    trust = tridiag_presolve16<T>(sA, sexp, (float)normS2, fQ, reinterpret_cast<float*>(fQ + N * LDQ), hv, hv + N, lane, v32);
-                    stamp(4);
-                    stamp(5);
+                    trust = tridiag_presolve16<T>(sA, sexp, (float)normS2, fQ, reinterpret_cast<float*>(fQ + N * LDQ), lane, v32, stamp);
                 } else if (dstop != 11) {
                     // one-sided form on the float Cholesky factor of 2^sexp C + delta I (same eigenvectors; the shift keeps the
                     // float pivots positive when C is singular to float precision).  The factor goes through sB, which is free

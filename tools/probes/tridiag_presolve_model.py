@@ -4,8 +4,9 @@ over bins and in the kernel's order of operations:
 
   1. Householder reduction of 2^sexp C to a REAL tridiagonal T = Q^H C Q in float32 (LAPACK zhetd2 form: complex tau,
      15 reflectors, the last one a pure phase), Q accumulated as Q H_0 H_1 ... H_14;
-  2. eigenvalues by Sturm-count multisection: 4 points per eigenvalue per step (the interval shrinks 5x), NSTEP steps,
-     q_i = (a_i - x) - e_{i-1}^2 rcp(q_{i-1});
+  2. eigenvalues by Sturm-count multisection: NPTS points per eigenvalue per step (the interval shrinks NPTS + 1 times),
+     NSTEP steps, q_i = (a_i - x) - e_{i-1}^2 rcp(q_{i-1}); the kernel runs 4 points (four lanes, one count each) and
+     10 steps.  8 points (two interleaved counts per lane) and 7 steps give the same guard pass rates here, 6 steps do not;
   3. eigenvectors by two inverse-iteration steps on T - lam I, unpivoted L D L^T (the Sturm recurrence at the shift), start
      vector ones + e_m, normalised after each step;
      eigenvalues closer than 1e-5 ||C|| (none on the bench data) send the bin to the double sweeps in the kernel;
@@ -14,7 +15,7 @@ over bins and in the kernel's order of operations:
 It prints the share of bins whose refinement matrix Z_ij = (S_ij - d_j E_ij) / (d_j - d_i), taken in float64 against the
 exact C, meets the kernel's one-step guard |Z| <= 3e-5 and its second-step limit 1e-2, on bench.synth(K, 1234).
 
-    python tools/probes/tridiag_presolve_model.py [K] [NSTEP]
+    python tools/probes/tridiag_presolve_model.py [K] [NSTEP] [NPTS]
 """
 import os
 import sys
@@ -87,20 +88,20 @@ def sturm_count(a, e2, x):
     return cnt
 
 
-def multisection(a, e, nrm, nstep):
+def multisection(a, e, nrm, nstep, npts=4):
     K = a.shape[0]
     e2 = np.maximum(e * e, f32(1e-30)).astype(f32)
     lo = np.broadcast_to((f32(-1e-3) * nrm)[:, None], (K, N)).astype(f32).copy()
     hi = np.broadcast_to((f32(1.001) * nrm)[:, None], (K, N)).astype(f32).copy()
     m = np.arange(N)
     for _ in range(nstep):
-        h = ((hi - lo) * f32(0.2)).astype(f32)
-        pts = (lo[:, :, None] + h[:, :, None] * np.arange(1, 5, dtype=f32)).astype(f32)     # [K,16,4]
-        c = sturm_count(a, e2, pts.reshape(K, -1)).reshape(K, N, 4)
+        fr = (np.arange(1, npts + 1) / (npts + 1)).astype(f32)
+        pts = (lo[:, :, None] + (hi - lo)[:, :, None] * fr).astype(f32)                  # [K,16,npts]
+        c = sturm_count(a, e2, pts.reshape(K, -1)).reshape(K, N, npts)
         below = c <= m[None, :, None]                                   # eigenvalue m lies above this point
         nb = below.sum(2)                                               # points at or below lam_m (monotone)
         new_lo = np.where(nb > 0, np.take_along_axis(pts, np.maximum(nb - 1, 0)[:, :, None], 2)[:, :, 0], lo)
-        new_hi = np.where(nb < 4, np.take_along_axis(pts, np.minimum(nb, 3)[:, :, None], 2)[:, :, 0], hi)
+        new_hi = np.where(nb < npts, np.take_along_axis(pts, np.minimum(nb, npts - 1)[:, :, None], 2)[:, :, 0], hi)
         lo, hi = new_lo.astype(f32), new_hi.astype(f32)
     return ((lo + hi) * f32(0.5)).astype(f32)
 
@@ -134,13 +135,13 @@ def inverse_iteration(a, e, lam, nrm, steps=2, tiny_rel=1e-9):
     return x
 
 
-def presolve(C, nstep):
+def presolve(C, nstep, npts=4):
     nf2 = (np.abs(C) ** 2).sum((1, 2))
     sexp = -(np.frexp(nf2)[1] - 1) // 2
     A = (C * np.ldexp(1.0, sexp)[:, None, None]).astype(np.complex64)
     nrm = np.sqrt(np.ldexp(nf2, 2 * sexp)).astype(f32)
     a, e, Q = tridiag(A)
-    lam = multisection(a, e, nrm, nstep)
+    lam = multisection(a, e, nrm, nstep, npts)
     X = inverse_iteration(a, e, lam, nrm)
     V = (Q @ X.astype(np.complex64)).astype(np.complex64)
     trust = lam.min(1) >= 1e-3 * lam.max(1)
@@ -164,8 +165,9 @@ def zmax(C, V):
 def main():
     K = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
     nstep = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    npts = int(sys.argv[3]) if len(sys.argv) > 3 else 4
     C = make_C(K)
-    V, lam, trust, (a, e, Q, A) = presolve(C, nstep)
+    V, lam, trust, (a, e, Q, A) = presolve(C, nstep, npts)
     # the reduction itself: Q^H A Q tridiagonal and real
     T = Q.conj().transpose(0, 2, 1).astype(np.complex128) @ A.astype(np.complex128) @ Q.astype(np.complex128)
     Tm = np.zeros_like(T)
@@ -174,7 +176,7 @@ def main():
     Tm[:, idx[1:], idx[:-1]] = e
     Tm[:, idx[:-1], idx[1:]] = e
     nrm = np.sqrt((np.abs(A.astype(np.complex128)) ** 2).sum((1, 2)))
-    print(f"bins {K}, multisection steps {nstep}")
+    print(f"bins {K}, multisection steps {nstep}, {npts} points per eigenvalue per step")
     print(f"reduction: max |Q^H A Q - T| / ||A|| = {(np.abs(T - Tm).max((1, 2)) / nrm).max():.2e}, "
           f"max |Q^H Q - I| = {np.abs(Q.conj().transpose(0, 2, 1) @ Q - np.eye(N)).max():.2e}")
     lref = np.linalg.eigvalsh(C)
