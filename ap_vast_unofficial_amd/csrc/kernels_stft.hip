@@ -7,13 +7,18 @@
 //              out[c][0:H] = overlap[c][0:H]                          apvast.py:212-225, 265-293, 457-504
 //
 // One workgroup per channel.  A length-N real transform (N even) is an N/2-point complex Stockham FFT in LDS
-// (mixed radix 4/2/3/5/7, so the reference's own N = 1600 works) plus the even/odd split step.  Twiddles and
-// the window come from tables computed once per (device, N, dtype) on the host in double precision.
+// (mixed radix 4/2/3/5/7, so the reference's own N = 1600 works) plus the even/odd split step.  When N/2 has a prime
+// factor above 7 (the MATLAB demo's N = 1020 = 4 * 3 * 5 * 17), the N/2-point transform is a Bluestein (chirp-z)
+// one: a circular convolution of length M = the power of two >= N - 1, done by two M-point radix-4/2 transforms in
+// the same LDS buffer.  Any even N in [4, 4096] works; above 4096 N/2 must be 7-smooth.  Twiddles, chirp, the
+// convolution kernel's spectrum and the window come from tables computed once per (device, N, dtype) on the host in
+// double precision.
 #include "apv_internal.h"
 #include <cstdio>
 #include <cstdlib>
 
 #include <cmath>
+#include <complex>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -23,6 +28,7 @@ namespace {
 
 constexpr int STFT_TPB = 256;
 constexpr int STFT_MAX_N = 8192;
+constexpr int STFT_MAX_BLUESTEIN_N = 4096;    // M <= 4096: one in-place buffer (64 KB of double), M/4 <= INPLACE_MAX_IT * STFT_TPB
 constexpr int MAX_STAGES = 14;
 
 struct FftPlan {
@@ -31,6 +37,9 @@ struct FftPlan {
     int nstages;
     int radix[MAX_STAGES];
     int inplace;           // every stage is radix 4 or 2 and short enough for stockham_stage_inplace: ONE LDS buffer of Nh
+    int bluestein;         // N/2 is not 7-smooth: chirp-z transform; radix[] / nstages are then the stages of the M-point transforms
+    int M;                 // Bluestein convolution length, the power of two >= 2 Nh - 1 (0 for a 7-smooth plan)
+    int buf;               // complex elements of one LDS buffer: Nh, or M for a Bluestein plan (the second buffer starts there)
     int max_it;            // butterflies per thread of the widest in-place stage (kernels are instantiated for 1 and for INPLACE_MAX_IT)
     int debug;             // timing aids of the analysis transforms (APV_STFT_DEBUG; results are wrong): 1 no spectrum stores, 2 no sample loads, 4 no stages
 };
@@ -50,9 +59,83 @@ template <typename T> __device__ __forceinline__ C2<T> cmul(C2<T> a, C2<T> b) {
 
 template <typename T>
 struct Tables {
-    C2<T>* tw = nullptr;   // exp(-2 pi i j / N), j < N (full circle)
+    C2<T>* tw = nullptr;   // exp(-2 pi i j / N), j < N (full circle); a Bluestein plan's tables follow (bluestein_tables)
     T* win = nullptr;      // sin(pi n / N), n < N     (apvast.py:94)
 };
+
+// Stage radices of an L-point transform, 4 first (so that a power of two takes radix 4 and at most one radix 2); false when a
+// prime factor above 7 is left
+bool factor_stages(int L, FftPlan* plan) {
+    plan->nstages = 0;
+    int rem = L;
+    const int radices[] = {4, 2, 3, 5, 7};
+    for (int r : radices)
+        while (rem % r == 0 && rem > 1) {
+            if (plan->nstages >= MAX_STAGES) break;
+            plan->radix[plan->nstages++] = r;
+            rem /= r;
+        }
+    return rem == 1;
+}
+
+// Bluestein length M of a block size, 0 when N/2 is 7-smooth (or N is out of range)
+int bluestein_len(int N) {
+    FftPlan p;
+    if (N < 4 || N > STFT_MAX_BLUESTEIN_N || (N & 1) || factor_stages(N / 2, &p)) return 0;
+    int M = 1;
+    while (M < N - 1) M *= 2;
+    return M;
+}
+
+// In-place radix-2 DFT in double, x[k] <- sum_n x[n] exp(-2 pi i n k / M), M a power of two (Bluestein set-up only)
+void host_fft_pow2(std::vector<std::complex<double>>& x) {
+    const int M = (int)x.size();
+    const double PI = 3.14159265358979323846;
+    for (int i = 1, j = 0; i < M; ++i) {                // bit reversal
+        int bit = M >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) std::swap(x[i], x[j]);
+    }
+    for (int len = 2; len <= M; len <<= 1)
+        for (int k = 0; k < len / 2; ++k) {
+            const std::complex<double> w(std::cos(-2.0 * PI * k / len), std::sin(-2.0 * PI * k / len));
+            for (int i = 0; i < M; i += len) {
+                const std::complex<double> u = x[i + k], v = x[i + k + len / 2] * w;
+                x[i + k] = u + v;
+                x[i + k + len / 2] = u - v;
+            }
+        }
+}
+
+// The tables a Bluestein plan reads behind the N roots (fft_bluestein), all from double precision:
+//   [N, N + M)             exp(-i pi j / M), j < M: the roots of the M-point stages (stockham_stage_inplace reads index 2 k M / (Ns R) < M)
+//   [N + M, N + M + Nh)    the chirp c[n] = exp(-i pi n^2 / Nh), n^2 reduced mod 2 Nh in integers
+//   [N + M + Nh, N + 2M + Nh)  B[k] / M, B the M-point DFT of b: b[n] = b[M - n] = conj(c[n]) for n < Nh, zero elsewhere
+//                              (the 1/M of the inverse transform rides along: M is a power of two, the scaling is exact)
+template <typename T>
+void bluestein_tables(int N, int M, C2<T>* t) {
+    const int Nh = N / 2;
+    const double PI = 3.14159265358979323846;
+    for (int j = 0; j < M; ++j) {
+        t[N + j].x = (T)std::cos(-PI * j / M);
+        t[N + j].y = (T)std::sin(-PI * j / M);
+    }
+    std::vector<std::complex<double>> b(M, 0.0);
+    for (int n = 0; n < Nh; ++n) {
+        const long long q = ((long long)n * n) % (2LL * Nh);
+        const std::complex<double> c(std::cos(-PI * (double)q / Nh), std::sin(-PI * (double)q / Nh));
+        t[N + M + n].x = (T)c.real();
+        t[N + M + n].y = (T)c.imag();
+        b[n] = std::conj(c);
+        if (n > 0) b[M - n] = std::conj(c);
+    }
+    host_fft_pow2(b);
+    for (int k = 0; k < M; ++k) {
+        t[N + M + Nh + k].x = (T)(b[k].real() / M);
+        t[N + M + Nh + k].y = (T)(b[k].imag() / M);
+    }
+}
 
 std::mutex g_tab_mu;
 std::map<std::tuple<int, int, int>, std::pair<void*, void*>> g_tabs;   // (device, N, is_f64) -> (tw, win)
@@ -70,7 +153,9 @@ hipError_t get_tables(int N, Tables<T>* out) {
         out->win = (T*)it->second.second;
         return hipSuccess;
     }
-    std::vector<C2<T>> tw(N);
+    const int M = bluestein_len(N);
+    const size_t ntw = (size_t)N + (M ? 2 * (size_t)M + N / 2 : 0);
+    std::vector<C2<T>> tw(ntw);
     std::vector<T> win(N);
     const double PI = 3.14159265358979323846;
     for (int j = 0; j < N; ++j) {
@@ -78,8 +163,9 @@ hipError_t get_tables(int N, Tables<T>* out) {
         tw[j].y = (T)std::sin(-2.0 * PI * j / N);
         win[j] = (T)std::sin(PI * j / N);
     }
+    if (M) bluestein_tables<T>(N, M, tw.data());
     void *dtw = nullptr, *dwin = nullptr;
-    e = hipMalloc(&dtw, sizeof(C2<T>) * N);
+    e = hipMalloc(&dtw, sizeof(C2<T>) * ntw);
     if (e != hipSuccess) return e;
     e = hipMalloc(&dwin, sizeof(T) * N);
     if (e != hipSuccess) return e;
@@ -88,7 +174,7 @@ hipError_t get_tables(int N, Tables<T>* out) {
     hipStream_t up = nullptr;
     e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
     if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(dtw, tw.data(), sizeof(C2<T>) * N, hipMemcpyHostToDevice, up);
+    e = hipMemcpyAsync(dtw, tw.data(), sizeof(C2<T>) * ntw, hipMemcpyHostToDevice, up);
     if (e == hipSuccess) e = hipMemcpyAsync(dwin, win.data(), sizeof(T) * N, hipMemcpyHostToDevice, up);
     if (e == hipSuccess) e = hipStreamSynchronize(up);
     (void)hipStreamDestroy(up);
@@ -212,10 +298,48 @@ __device__ __forceinline__ void stockham_stage_inplace(C2<T>* __restrict__ buf, 
     __syncthreads();
 }
 
+// Bluestein (chirp-z) form of the Nh-point DFT for an Nh with a prime factor above 7.  With c[n] = exp(-i pi n^2 / Nh) and
+// n k = (n^2 + k^2 - (k - n)^2) / 2,  X[k] = c[k] sum_n (x[n] c[n]) conj(c[k - n]):  a circular convolution of length M >= 2 Nh - 1,
+// i.e. a product of M-point spectra, the kernel's (B / M) from the tables.  The input sits in a[0, Nh) and the workgroup has met; a
+// holds M elements.  The inverse transform is conj(FFT(conj(.))), its 1/M folded into B; the Nh results end in a[0, Nh).
+template <typename T, int MI>
+__device__ __forceinline__ void fft_bluestein(const FftPlan& plan, C2<T>* a, const C2<T>* __restrict__ tw) {
+    const int Nh = plan.Nh, M = plan.M, tid = threadIdx.x;
+    const C2<T>* __restrict__ twm = tw + plan.N;          // exp(-i pi j / M): the M-point stages read it like tw for Nh
+    const C2<T>* __restrict__ chirp = twm + M;
+    const C2<T>* __restrict__ bh = chirp + Nh;
+    for (int n = tid; n < M; n += STFT_TPB) a[n] = n < Nh ? cmul(a[n], chirp[n]) : c2<T>((T)0, (T)0);
+    __syncthreads();
+    for (int pass = 0; pass < 2; ++pass) {
+        int Ns = 1;
+        for (int s = 0; s < plan.nstages; ++s) {          // every stage ends on a barrier
+            if (plan.radix[s] == 4) stockham_stage_inplace<T, 4, MI>(a, M, Ns, twm);
+            else stockham_stage_inplace<T, 2, MI>(a, M, Ns, twm);
+            Ns *= plan.radix[s];
+        }
+        if (pass == 0)
+            for (int n = tid; n < M; n += STFT_TPB) {
+                const C2<T> y = cmul(a[n], bh[n]);
+                a[n] = c2<T>(y.x, -y.y);
+            }
+        else
+            for (int n = tid; n < Nh; n += STFT_TPB) {
+                const C2<T> z = a[n];
+                a[n] = cmul(c2<T>(z.x, -z.y), chirp[n]);
+            }
+        __syncthreads();
+    }
+}
+
 // forward complex FFT of length plan.Nh on natural-order data in `a`; returns the buffer holding the result (`b` is not
-// touched, and need not exist, when plan.inplace is set)
-template <typename T, int MI = INPLACE_MAX_IT>
+// touched, and need not exist, when plan.inplace is set).  BS: the kernel is instantiated for Bluestein plans (fft_bluestein);
+// the 7-smooth instantiations carry none of its code
+template <typename T, int MI = INPLACE_MAX_IT, bool BS = false>
 __device__ __forceinline__ C2<T>* fft_forward(const FftPlan& plan, C2<T>* a, C2<T>* b, const C2<T>* __restrict__ tw) {
+    if constexpr (BS) {
+        fft_bluestein<T, MI>(plan, a, tw);
+        return a;
+    }
     if (plan.inplace) {
         int Ns = 1;
         for (int s = 0; s < plan.nstages; ++s) {
@@ -244,18 +368,18 @@ __device__ __forceinline__ C2<T>* fft_forward(const FftPlan& plan, C2<T>* a, C2<
     return src;
 }
 
-template <typename T, int MI = INPLACE_MAX_IT>
+template <typename T, int MI = INPLACE_MAX_IT, bool BS = false>
 __device__ __forceinline__ void rfft_from_lds(const FftPlan& plan, C2<T>* za, C2<T>* zb, C2<T>* __restrict__ out, long stride_k,
                                               const C2<T>* __restrict__ tw, int kgroup = 1);
 
-template <typename T, int MI = INPLACE_MAX_IT>
+template <typename T, int MI = INPLACE_MAX_IT, bool BS = false>
 __device__ __forceinline__ void stft_analysis_body(const FftPlan& plan, const T* __restrict__ xin, int in_len, int ring_off,
                                                    int use_win, C2<T>* __restrict__ out, long stride_k,
                                                    const C2<T>* __restrict__ tw, const T* __restrict__ win, int kgroup = 1) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     C2<T>* za = reinterpret_cast<C2<T>*>(smem_raw);
     const int N = plan.N, Nh = plan.Nh;
-    C2<T>* zb = za + Nh;
+    C2<T>* zb = za + plan.buf;
     const int tid = threadIdx.x;
     for (int n = tid; n < Nh; n += STFT_TPB) {
         int i0 = 2 * n + ring_off, i1 = i0 + 1;
@@ -276,18 +400,18 @@ __device__ __forceinline__ void stft_analysis_body(const FftPlan& plan, const T*
         za[n] = c2<T>(v0, v1);
     }
     __syncthreads();
-    rfft_from_lds<T, MI>(plan, za, zb, out, stride_k, tw, kgroup);
+    rfft_from_lds<T, MI, BS>(plan, za, zb, out, stride_k, tw, kgroup);
 }
 
 // the real series x[2n], x[2n+1] sits in za[n] (and the workgroup has met): spectrum to out[k * stride_k], k <= N/2
 // kgroup > 1: GROUPED bin-major layout [K / g][C][g] (round 4): bins k .. k + g - 1 of a channel are contiguous (g = 4: one 64-byte
 // line of c128), the groups stride_k * g elements apart; the caller has offset `out` by c * g.  A transform then fills whole
 // lines -- 34.7 million 16-byte pieces per chunk of cfg3, each in another DRAM page, were what its stores cost.
-template <typename T, int MI>
+template <typename T, int MI, bool BS>
 __device__ __forceinline__ void rfft_from_lds(const FftPlan& plan, C2<T>* za, C2<T>* zb, C2<T>* __restrict__ out, long stride_k,
                                               const C2<T>* __restrict__ tw, int kgroup) {
     const int Nh = plan.Nh, tid = threadIdx.x;
-    const C2<T>* z = (plan.debug & 4) ? za : fft_forward<T, MI>(plan, za, zb, tw);
+    const C2<T>* z = (plan.debug & 4) ? za : fft_forward<T, MI, BS>(plan, za, zb, tw);
     // even/odd split: X[k] = E[k] + e^{-2 pi i k/N} O[k]
     // (unrolling this loop and the input loop above so that all of a thread's loads go out together was tried in round 3 after the
     // order-16 kernel's slab loads: 65 -> 97 VGPRs and no change in the kernel's 437 us per chunk -- the transforms of a chunk move
@@ -307,14 +431,14 @@ __device__ __forceinline__ void rfft_from_lds(const FftPlan& plan, C2<T>* za, C2
 
 // x is a ring: logical sample n of channel c lives at x[c*x_stride + (n + ring_off) mod N]; samples
 // n >= in_len read as zero (zero padding, apvast.py:417: rfft(taps, N)); use_win = 0 skips the window
-template <typename T>
+template <typename T, bool BS>
 __global__ void __launch_bounds__(STFT_TPB) stft_analysis_kernel(FftPlan plan, const T* __restrict__ x, long x_stride,
                                                                  int in_len, int ring_off, int use_win,
                                                                  C2<T>* __restrict__ spec, long stride_c, long stride_k,
                                                                  const C2<T>* __restrict__ tw,
                                                                  const T* __restrict__ win) {
     const int c = blockIdx.x;
-    stft_analysis_body<T>(plan, x + (size_t)c * x_stride, in_len, ring_off, use_win, spec + (size_t)c * stride_c, stride_k, tw, win);
+    stft_analysis_body<T, INPLACE_MAX_IT, BS>(plan, x + (size_t)c * x_stride, in_len, ring_off, use_win, spec + (size_t)c * stride_c, stride_k, tw, win);
 }
 
 // several channel sets (full-length, windowed, one shared ring offset) in one launch: the streaming hop has seven
@@ -331,7 +455,7 @@ struct StftJobs {
     long x_stride, x_hop;
     long spec_hop[STFT_MAX_JOBS];
 };
-template <typename T, int MI>
+template <typename T, int MI, bool BS>
 __global__ void __launch_bounds__(STFT_TPB) stft_analysis_jobs_kernel(FftPlan plan, StftJobs<T> jobs, int ring_off,
                                                                       const C2<T>* __restrict__ tw,
                                                                       const T* __restrict__ win) {
@@ -352,7 +476,7 @@ __global__ void __launch_bounds__(STFT_TPB) stft_analysis_jobs_kernel(FftPlan pl
     // a set whose channel stride AND bin stride exceed one is in the grouped layout, the channel stride being the group (see
     // rfft_from_lds): bin-major sets have stride_c = 1, channel-major ones stride_k = 1
     const int kgroup = (jobs.stride_c[j] > 1 && jobs.stride_k[j] > 1) ? (int)jobs.stride_c[j] : 1;
-    stft_analysis_body<T, MI>(plan, jobs.x[j] + (size_t)c * jobs.x_stride + hop * jobs.x_hop, plan.N, ring_off, 1,
+    stft_analysis_body<T, MI, BS>(plan, jobs.x[j] + (size_t)c * jobs.x_stride + hop * jobs.x_hop, plan.N, ring_off, 1,
                           jobs.spec[j] + hop * jobs.spec_hop[j] + (cm ? (size_t)c * (plan.Nh + 1) : (size_t)c * jobs.stride_c[j]),
                           cm ? 1 : jobs.stride_k[j], tw, win, kgroup);
 }
@@ -361,7 +485,7 @@ __global__ void __launch_bounds__(STFT_TPB) stft_analysis_jobs_kernel(FftPlan pl
 // 16-byte pieces, was tried for the chunk launches and lost: 470 us against 440 us per chunk of 16 hops at cfg3.  The transforms are
 // bound by their LDS round trips and barriers, not by the partial-line writes, and sixteen waves in step hide less of them than four
 // independent workgroups.)
-template <typename T, int MI>
+template <typename T, int MI, bool BS>
 __global__ void __launch_bounds__(STFT_TPB) istft_ola_kernel(FftPlan plan, int H, const C2<T>* __restrict__ spec,
                                                              long stride_c, long stride_k, T* __restrict__ overlap,
                                                              T* __restrict__ out, const C2<T>* __restrict__ tw,
@@ -369,7 +493,7 @@ __global__ void __launch_bounds__(STFT_TPB) istft_ola_kernel(FftPlan plan, int H
     extern __shared__ __align__(16) unsigned char smem_raw[];
     C2<T>* za = reinterpret_cast<C2<T>*>(smem_raw);
     const int N = plan.N, Nh = plan.Nh;
-    C2<T>* zb = za + Nh;
+    C2<T>* zb = za + plan.buf;
     const int c = blockIdx.x, tid = threadIdx.x;
     const C2<T>* X = spec + (size_t)c * stride_c;
     // Z[k] = E[k] + i O[k];  inverse transform as conj(FFT(conj(Z))) / Nh
@@ -388,7 +512,7 @@ __global__ void __launch_bounds__(STFT_TPB) istft_ola_kernel(FftPlan plan, int H
         za[k] = c2<T>(e.x - o.y, -(e.y + o.x));                          // conj(E + i O)
     }
     __syncthreads();
-    C2<T>* z = fft_forward<T, MI>(plan, za, zb, tw);
+    C2<T>* z = fft_forward<T, MI, BS>(plan, za, zb, tw);
     const T scale = (T)1 / (T)Nh;
     T* ov = overlap + (size_t)c * N;
     T* zf = reinterpret_cast<T*>(z);
@@ -482,7 +606,7 @@ __global__ void __launch_bounds__(STFT_TPB) fir_chunk_spectra_kernel(FftPlan pla
                                                                      C2<T>* __restrict__ spec, const C2<T>* __restrict__ tw) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     C2<T>* za = reinterpret_cast<C2<T>*>(smem_raw);
-    C2<T>* zb = za + plan.Nh;
+    C2<T>* zb = za + plan.buf;
     const int g = blockIdx.x, hop = blockIdx.y, keep = P - 1, len = keep + H;
     const T* __restrict__ hist = g ? hist1 : hist0;                 // [P - 1 + H]: its last P - 1 samples precede the chunk
     auto sample = [&](int n) -> T {                                   // n-th sample of this hop's history
@@ -507,7 +631,7 @@ __global__ void __launch_bounds__(STFT_TPB) fir_fft_kernel(FftPlan plan, FirFftJ
     using Z = C2<T>;
     Z* za = reinterpret_cast<Z*>(smem_raw);
     const int Fh = plan.Nh;
-    Z* zb = za + Fh;
+    Z* zb = za + plan.buf;
     const int wg = blockIdx.x, tid = threadIdx.x;
     if (wg >= jobs.ch0[jobs.n]) {                                   // the passenger: same work as input_update_kernel
         const int u = wg - jobs.ch0[jobs.n], g = u / jobs.upd_wgs, i = (u - g * jobs.upd_wgs) * STFT_TPB + tid;
@@ -571,27 +695,29 @@ __global__ void __launch_bounds__(STFT_TPB) fir_fft_kernel(FftPlan plan, FirFftJ
 }
 
 bool make_plan(int N, FftPlan* plan, std::string* why) {
+    const char* rule = "STFT block size must be even and in [4, 8192]; above 4096, N/2 must factor into 2, 3, 5 and 7";
     if (N < 4 || N > STFT_MAX_N || (N & 1)) {
-        if (why) *why = "STFT block size must be even and in [4, 8192]";
+        if (why) *why = rule;
         return false;
     }
     plan->N = N;
     plan->Nh = N / 2;
-    plan->nstages = 0;
-    int rem = N / 2;
-    const int radices[] = {4, 2, 3, 5, 7};
-    for (int r : radices)
-        while (rem % r == 0 && rem > 1) {
-            if (plan->nstages >= MAX_STAGES) break;
-            plan->radix[plan->nstages++] = r;
-            rem /= r;
+    plan->buf = N / 2;
+    plan->bluestein = 0;
+    plan->M = 0;
+    if (!factor_stages(N / 2, plan)) {
+        // a prime factor above 7: Bluestein, its M-point stages in place in ONE buffer of M
+        plan->M = bluestein_len(N);
+        if (plan->M == 0) {
+            if (why) *why = rule;
+            return false;
         }
-    if (rem != 1) {
-        if (why) *why = "STFT block size / 2 must factor into 2, 3, 5 and 7";
-        return false;
+        plan->bluestein = 1;
+        plan->buf = plan->M;
+        factor_stages(plan->M, plan);
     }
     static const bool pingpong = getenv("APV_FFT_PINGPONG") != nullptr;      // A/B switch: two-buffer stages everywhere
-    plan->inplace = pingpong ? 0 : 1;
+    plan->inplace = (pingpong && !plan->bluestein) ? 0 : 1;
     plan->max_it = 1;
     // Timing aids of the probes: they make every transform WRONG.  A stray APV_STFT_DEBUG in somebody's environment must not
     // corrupt a stream silently: the bits are honoured only together with APV_STFT_DEBUG_PROBE=1, which the probe
@@ -609,8 +735,8 @@ bool make_plan(int N, FftPlan* plan, std::string* why) {
     }
     for (int s = 0; s < plan->nstages; ++s) {
         const int r = plan->radix[s];
-        if ((r != 2 && r != 4) || plan->Nh / r > INPLACE_MAX_IT * STFT_TPB) plan->inplace = 0;
-        const int it = (plan->Nh / r + STFT_TPB - 1) / STFT_TPB;
+        if ((r != 2 && r != 4) || plan->buf / r > INPLACE_MAX_IT * STFT_TPB) plan->inplace = 0;
+        const int it = (plan->buf / r + STFT_TPB - 1) / STFT_TPB;
         if (it > plan->max_it) plan->max_it = it;
     }
     static const bool mi4 = getenv("APV_FFT_MI4") != nullptr;                // A/B switch: the four-butterfly instantiations everywhere
@@ -620,7 +746,7 @@ bool make_plan(int N, FftPlan* plan, std::string* why) {
 
 // LDS bytes of one transform
 template <typename T>
-size_t plan_lds(const FftPlan& plan) { return sizeof(C2<T>) * (plan.inplace ? 1 : 2) * plan.Nh; }
+size_t plan_lds(const FftPlan& plan) { return sizeof(C2<T>) * (plan.inplace ? 1 : 2) * plan.buf; }
 
 template <typename T>
 hipError_t launch_analysis(int N, int n_ch, const void* x, long x_stride, int in_len, int ring_off, int use_win,
@@ -634,7 +760,7 @@ hipError_t launch_analysis(int N, int n_ch, const void* x, long x_stride, int in
     const size_t lds = plan_lds<T>(plan);
     int off = ring_off % N;
     if (off < 0) off += N;
-    hipLaunchKernelGGL(stft_analysis_kernel<T>, dim3(n_ch), dim3(STFT_TPB), lds, s, plan, (const T*)x, x_stride, in_len,
+    hipLaunchKernelGGL((plan.bluestein ? stft_analysis_kernel<T, true> : stft_analysis_kernel<T, false>), dim3(n_ch), dim3(STFT_TPB), lds, s, plan, (const T*)x, x_stride, in_len,
                        off, use_win, (C2<T>*)spec, stride_c, stride_k, t.tw, t.win);
     return hipGetLastError();
 }
@@ -653,7 +779,9 @@ hipError_t launch_synthesis(int N, int H, int n_ch, const void* spec, long strid
     hipError_t e = get_tables<T>(N, &t);
     if (e != hipSuccess) return e;
     const size_t lds = plan_lds<T>(plan);
-    hipLaunchKernelGGL((plan.max_it == 1 ? istft_ola_kernel<T, 1> : istft_ola_kernel<T, INPLACE_MAX_IT>), dim3(n_ch), dim3(STFT_TPB), lds, s, plan, H, (const C2<T>*)spec, stride_c,
+    const auto kern = plan.bluestein ? (plan.max_it == 1 ? istft_ola_kernel<T, 1, true> : istft_ola_kernel<T, INPLACE_MAX_IT, true>)
+                                     : (plan.max_it == 1 ? istft_ola_kernel<T, 1, false> : istft_ola_kernel<T, INPLACE_MAX_IT, false>);
+    hipLaunchKernelGGL(kern, dim3(n_ch), dim3(STFT_TPB), lds, s, plan, H, (const C2<T>*)spec, stride_c,
                        stride_k, (T*)overlap, (T*)out, t.tw, t.win, (out_group > 0 && n_ch % out_group == 0) ? out_group : 0,
                        out_gstride > 0 ? out_gstride : (long)H * out_group);
     return hipGetLastError();
@@ -687,7 +815,10 @@ hipError_t launch_analysis_jobs(const FftPlan& plan, int n_jobs, const void* con
     if (total <= 0 || n_hops <= 0) return hipSuccess;
     int off = ring_off % plan.N;
     if (off < 0) off += plan.N;
-    hipLaunchKernelGGL((plan.max_it == 1 ? stft_analysis_jobs_kernel<T, 1> : stft_analysis_jobs_kernel<T, INPLACE_MAX_IT>), dim3(total, n_hops), dim3(STFT_TPB), plan_lds<T>(plan), s, plan, jobs, off,
+    const auto kern = plan.bluestein
+                          ? (plan.max_it == 1 ? stft_analysis_jobs_kernel<T, 1, true> : stft_analysis_jobs_kernel<T, INPLACE_MAX_IT, true>)
+                          : (plan.max_it == 1 ? stft_analysis_jobs_kernel<T, 1, false> : stft_analysis_jobs_kernel<T, INPLACE_MAX_IT, false>);
+    hipLaunchKernelGGL(kern, dim3(total, n_hops), dim3(STFT_TPB), plan_lds<T>(plan), s, plan, jobs, off,
                        t.tw, t.win);
     return hipGetLastError();
 }
@@ -774,9 +905,9 @@ int apv_fir_fft_size(int f64, int P, int H) {
 int apv_fir_partitions(int f64, int P, int H) {
     if (apv_fir_fft_size(f64, P, H) != 0 || P < 64 || P - 1 < H) return 0;
     const int F = 2 * H;
-    if (F > (f64 ? 4096 : 8192) || !apv_stft_size_ok(F, nullptr)) return 0;
     FftPlan plan;
-    if (!make_plan(F, &plan, nullptr)) return 0;
+    // 7-smooth segments only: the FIR kernels have no Bluestein instantiations; a long response with another hop takes the direct form
+    if (F > (f64 ? 4096 : 8192) || !make_plan(F, &plan, nullptr) || plan.bluestein) return 0;
     return (P + H - 1) / H;
 }
 
@@ -797,7 +928,7 @@ template <typename T>
 hipError_t launch_fir_input_spectra(int F, const void* x0, const void* x1, int in_len, void* Xf, hipStream_t s, int n_part = 1,
                                     int part_step = 0) {
     FftPlan plan;
-    if (!make_plan(F, &plan, nullptr)) return hipErrorInvalidValue;
+    if (!make_plan(F, &plan, nullptr) || plan.bluestein) return hipErrorInvalidValue;
     Tables<T> t;
     hipError_t e = get_tables<T>(F, &t);
     if (e != hipSuccess) return e;
@@ -810,7 +941,7 @@ template <typename T>
 hipError_t launch_fir_chunk_spectra(int F, int P, int H, int n_hops, const void* hist0, const void* hist1, const void* pin, void* Xf,
                                     hipStream_t s) {
     FftPlan plan;
-    if (!make_plan(F, &plan, nullptr) || P - 1 + H > F || n_hops < 1) return hipErrorInvalidValue;
+    if (!make_plan(F, &plan, nullptr) || plan.bluestein || P - 1 + H > F || n_hops < 1) return hipErrorInvalidValue;
     Tables<T> t;
     hipError_t e = get_tables<T>(F, &t);
     if (e != hipSuccess) return e;
@@ -824,7 +955,7 @@ hipError_t launch_fir_fft_jobs(int F, int n_jobs, const void* const* Hf, const v
                                int P, int H, int N, int ring_off, const ApvInputUpdate* upd, hipStream_t s, int row_stride = 0,
                                int pos0 = 0, long x_hop_stride = 0, int n_hops = 1, int n_part = 1) {
     FftPlan plan;
-    if (!make_plan(F, &plan, nullptr) || n_jobs < 1 || n_jobs > FIR_FFT_JOBS || n_part < 1) return hipErrorInvalidValue;
+    if (!make_plan(F, &plan, nullptr) || plan.bluestein || n_jobs < 1 || n_jobs > FIR_FFT_JOBS || n_part < 1) return hipErrorInvalidValue;
     if (n_part == 1 ? (P - 1 + H > F) : (F != 2 * H || (long)n_part * H < P)) return hipErrorInvalidValue;
     Tables<T> t;
     hipError_t e = get_tables<T>(F, &t);

@@ -88,7 +88,7 @@ typedef struct apv_config {
     double  reg_bright;       /* relative bright loading (apVast.m:552-569); 0 in the Python dialect */
     double  mu;               /* trade-off parameter (apvast.py:49, 410) */
     int32_t max_sweeps;       /* Jacobi sweep cap; 0 = default.  Broadband mode: a value > 0 also selects the complete block-Jacobi solve for every hop (0: the per-hop path computes the leading eigenpairs the filters use, the rest when lambda / U are read) */
-    int32_t block_size;       /* N : STFT length for the streaming entry points (0 = kernel-level use only) */
+    int32_t block_size;       /* N : STFT length for the streaming entry points (0 = kernel-level use only); any even N in [4, 4096], above that up to 8192 with N/2 = 2^a 3^b 5^c 7^d (float32 front end) */
     int32_t hop_size;         /* H */
     int32_t n_zones;          /* streaming: bit mask of zone programs, 1 = A, 2 = B (run_A/run_B, apvast.py:53-54) */
     int32_t debug_stop;       /* profiling aid: stop the fused kernel after stage n (0 = run everything) */
