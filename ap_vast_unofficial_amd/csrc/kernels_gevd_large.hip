@@ -3,17 +3,22 @@
 //
 //   jdiag(A, B)   reference Python/apvast.py:20-36, called at apvast.py:380, 382 with n = J L
 //
-//   1  B + reg I = L L^T               left-looking Cholesky in 32-wide column panels, one launch per panel; the
-//                                      32 x 32 diagonal block is eliminated on [D | I] in LDS, which also yields
-//                                      its inverse                                            apvast.py:22-27
-//      W = L^-1                        forward substitution on 32 x 32 tiles, one launch
-//   2  C = W A W^T                     two tiled GEMMs                                         apvast.py:28-29
-//   3  C = Q diag(lam) Q^T             block cyclic Jacobi: the order is cut into 16-wide blocks, paired round-robin;
-//                                      one launch per block round.  A workgroup owns one 32 x 32 tile (P, Q) of the
-//                                      pair grid, re-derives the rotations of BOTH diagonal tiles it depends on with
-//                                      an in-LDS Jacobi sweep (redundant across the row/column of workgroups, but it
-//                                      removes every dependency inside the launch), and applies V_P^T . V_Q.
-//                                      X = W^T Q is accumulated in place by the same workgroups.    apvast.py:30-35
+//   1  B + reg I = L L^T               left-looking Cholesky in 32-wide column panels, one launch per panel; one wave
+//                                      inverts the factor of the 32 x 32 diagonal block by halving     apvast.py:22-27
+//      W = L^-1                        recursive halving from those diagonal inverses, two products per level on
+//                                      gemm64_kernel
+//   2  C = W A W^T                     two gemm64_kernel products, the second on and below the diagonal only, then
+//                                      mirrored                                                  apvast.py:28-29
+//   3  C = Q diag(lam) Q^T             block cyclic Jacobi: the order is cut into 16-wide blocks, paired round-robin.
+//                                      A block round is the pair solves (one workgroup per pair: an in-LDS Jacobi
+//                                      sweep of its 32 x 32 diagonal tile) and the updates V_P^T C[P,Q] V_Q of every
+//                                      tile; X = W^T Q is accumulated in place by the same workgroups.  From two pairs
+//                                      on, the pair solves of round r + 1 run in the launch that updates round r
+//                                      (look-ahead).  When the caller wants only the leading eigenpairs,
+//                                      kernels_gevd_lead.hip solves for those first, and the sweeps run only if it
+//                                      gives up.                                                 apvast.py:30-35
+//                                      Past an untested stretch, the stop test follows every sweep.  The sweeps are
+//                                      three captured graphs: two sweeps C0 -> C0, one C0 -> C1, one C1 -> C0.
 //   4  rank of every eigenvalue (descending), columns of X gathered in that order               apvast.py:31-35
 //   5  (optional) w_v = sum_{i<v} (x_i^T r)/(lam_i + mu) x_i for v = 1..V                       apvast.py:406-414
 //
@@ -35,11 +40,10 @@ constexpr int BT = 32;   // tile edge: two 16-wide Jacobi blocks, one Cholesky p
 constexpr int BH = 16;
 constexpr int LS = 33;   // LDS row stride in doubles (bank-conflict padding)
 
-// 32 x 32 x 32 product from LDS tiles, 2 x 2 outputs per thread: o = {(ty,tx), (ty,tx+16), (ty+16,tx), (ty+16,tx+16)}
-// of sum_k A(t,k) B(k,u) with A(t,k) = TA ? A[k][t] : A[t][k], B(k,u) = TB ? B[u][k] : B[k][u]
 using d4 = __attribute__((ext_vector_type(4))) double;
 
-// The same product on v_mfma_f64_16x16x4_f64: four waves, wave w owns the 16 x 16 tile (w >> 1, w & 1).
+// 32 x 32 x 32 product from LDS tiles, sum_k A(t,k) B(k,u) with A(t,k) = TA ? A[k][t] : A[t][k], B(k,u) = TB ? B[u][k] : B[k][u],
+// on v_mfma_f64_16x16x4_f64: four waves, wave w owns the 16 x 16 tile (w >> 1, w & 1).
 // acc[t] is element (row0 + (lane >> 4) + 4 t, col0 + (lane & 15)).
 template <bool TA, bool TB = false>
 __device__ __forceinline__ d4 mm32_mfma(const double* A, const double* B, int w, int lane) {
@@ -119,14 +123,13 @@ __device__ __forceinline__ d4 wave_mm16(FA fa, FB fb, int lane) {
 
 // ---- step 1 ---------------------------------------------------------------------------------------
 // Left-looking Cholesky, column panel k (32 wide); workgroup x handles the row tile I = k + x.  Every workgroup
-// forms the updated diagonal block D = B[K,K] - sum_J L[K,J] L[K,J]^T itself and eliminates [D | I] in LDS (unscaled
-// columns of L_D on the left, rows of L_D^-1 up to 1/sqrt(d) on the right), then writes L[I,K] = T L_D^-T.
+// forms the updated diagonal block D = B[K,K] - sum_J L[K,J] L[K,J]^T itself and inverts its Cholesky factor, L_D^-1, in
+// one wave, then writes L[I,K] = T L_D^-T.
 // The strictly lower tiles of B are replaced by L; LiBuf[k] receives L_D^-1 (L_D itself is not kept).
 // diagnostics (APV_LARGE_DEBUG=2): s_memtime of thread 0 of the LAST row tile's workgroup of matrix 0 at the phase boundaries, [panel][4]
 __device__ unsigned long long g_panel_stamps[64 * 4];
 __device__ int g_panel_stamps_on;
 
-template <bool WAVE_ELIM>
 __global__ void __launch_bounds__(256) chol_panel_kernel(int ld, int k, int nbk, double* __restrict__ B,
                                                          double* __restrict__ LiBuf, int* __restrict__ flag,
                                                          size_t mat_stride) {
@@ -192,83 +195,35 @@ __global__ void __launch_bounds__(256) chol_panel_kernel(int ld, int k, int nbk,
         Wp[r * LS + c] = (r == c) ? 1.0 : 0.0;
     }
     __syncthreads();
-    if (WAVE_ELIM) {
-        // L_D^-1 of the 32 x 32 block by halving, all of it in ONE wave (no barrier inside: the wave's own LDS accesses are ordered):
-        //   W11 = inv chol(D11);  L21 = D21 W11^T;  S = D22 - L21 L21^T;  W22 = inv chol(S);  W21 = -W22 (L21 W11)
-        // two 16-step eliminations (wave_inv_chol16) and five 16^3 products on the matrix cores, instead of 32 steps with a
-        // workgroup barrier each (measured per panel launch: see DESIGN 4.8).  The block's memory is overwritten as it goes.
-        if (wq == 0) {
-            double* const D21 = Dm + 16 * LS;            // rows 16.., columns 0..15: D21 -> L21 -> L21 W11
-            double* const D22 = Dm + 16 * LS + 16;
-            double* const W22 = Wp + 16 * LS + 16;
-            const int il = lq & 15, kq = lq >> 4;
-            bool bad = wave_inv_chol16(Dm, Wp, rs, lq);
-            d4 t = wave_mm16([&](int i, int kk) { return D21[i * LS + kk]; }, [&](int kk, int j) { return Wp[j * LS + kk]; }, lq);
+    // L_D^-1 of the 32 x 32 block by halving, all of it in ONE wave (no barrier inside: the wave's own LDS accesses are ordered):
+    //   W11 = inv chol(D11);  L21 = D21 W11^T;  S = D22 - L21 L21^T;  W22 = inv chol(S);  W21 = -W22 (L21 W11)
+    // two 16-step eliminations (wave_inv_chol16) and five 16^3 products on the matrix cores, instead of 32 steps with a
+    // workgroup barrier each (measured per panel launch: see DESIGN 4.8).  The block's memory is overwritten as it goes.
+    if (wq == 0) {
+        double* const D21 = Dm + 16 * LS;            // rows 16.., columns 0..15: D21 -> L21 -> L21 W11
+        double* const D22 = Dm + 16 * LS + 16;
+        double* const W22 = Wp + 16 * LS + 16;
+        const int il = lq & 15, kq = lq >> 4;
+        bool bad = wave_inv_chol16(Dm, Wp, rs, lq);
+        d4 t = wave_mm16([&](int i, int kk) { return D21[i * LS + kk]; }, [&](int kk, int j) { return Wp[j * LS + kk]; }, lq);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) D21[(kq + 4 * u) * LS + il] = t[u];
-            t = wave_mm16([&](int i, int kk) { return D21[i * LS + kk]; }, [&](int kk, int j) { return D21[j * LS + kk]; }, lq);
+        for (int u = 0; u < 4; ++u) D21[(kq + 4 * u) * LS + il] = t[u];
+        t = wave_mm16([&](int i, int kk) { return D21[i * LS + kk]; }, [&](int kk, int j) { return D21[j * LS + kk]; }, lq);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) D22[(kq + 4 * u) * LS + il] -= t[u];
-            bad = wave_inv_chol16(D22, W22, rs, lq) || bad;
-            t = wave_mm16([&](int i, int kk) { return D21[i * LS + kk]; }, [&](int kk, int j) { return Wp[kk * LS + j]; }, lq);
+        for (int u = 0; u < 4; ++u) D22[(kq + 4 * u) * LS + il] -= t[u];
+        bad = wave_inv_chol16(D22, W22, rs, lq) || bad;
+        t = wave_mm16([&](int i, int kk) { return D21[i * LS + kk]; }, [&](int kk, int j) { return Wp[kk * LS + j]; }, lq);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) D21[(kq + 4 * u) * LS + il] = t[u];
-            t = wave_mm16([&](int i, int kk) { return W22[i * LS + kk]; }, [&](int kk, int j) { return D21[kk * LS + j]; }, lq);
+        for (int u = 0; u < 4; ++u) D21[(kq + 4 * u) * LS + il] = t[u];
+        t = wave_mm16([&](int i, int kk) { return W22[i * LS + kk]; }, [&](int kk, int j) { return D21[kk * LS + j]; }, lq);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) Wp[(16 + kq + 4 * u) * LS + il] = -t[u];
-            if (lq == 0) sflag = bad ? 1 : 0;
-        }
-        __syncthreads();
-        if (sflag) {                                   // the same block in every workgroup of the panel: all leave
-            if (tid == 0 && blockIdx.x == 0) flag[z] = 1;
-            return;
-        }
-    } else
-    // [D | I] -> [ . | L_D^-1 ] by elimination with the rows in REGISTERS (round 4): thread (r, cq) holds columns 8 cq .. 8 cq + 7 of
-    // row r of the augmented matrix; a step publishes the pivot row and the pivot column through LDS (two alternating buffers:
-    // one barrier per step), everything else is eight multiply-adds per thread.  Before, every element of both halves went
-    // through LDS in every step (three reads and a write each, 0.45 us a step; 25-36 us of a panel launch were this loop).
-    {
-        const int er = tid >> 3, cq = tid & 7;
-        double a[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] = cq < 4 ? Dm[er * LS + 8 * cq + i] : ((8 * (cq - 4) + i == er) ? 1.0 : 0.0);
-        double* const prow = La;                   // [2][64]   (La holds T only for I != k: parked in registers below)
-        double* const pcol = Lb;                   // [2][32]
-        double tsave[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) tsave[i] = La[((wq >> 1) * 16 + (lq >> 4) + 4 * i) * LS + (wq & 1) * 16 + (lq & 15)];
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < BT; ++j) {
-            const int par = j & 1;
-            if (er == j) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) prow[par * 64 + 8 * cq + i] = a[i];
-            }
-            if (cq == (j >> 3)) pcol[par * 32 + er] = a[j & 7];
-            __syncthreads();
-            const double d = pcol[par * 32 + j];
-            if (!(d > 0.0) || !(d < 1e300)) {          // the same value in every workgroup of the panel: all leave
-                if (tid == 0 && blockIdx.x == 0) flag[z] = 1;
-                return;
-            }
-            if (tid == 0) rs[j] = 1.0 / sqrt(d);
-            if (er > j) {
-                const double f = pcol[par * 32 + er] * (1.0 / d);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) a[i] = __builtin_fma(-f, prow[par * 64 + 8 * cq + i], a[i]);
-            }
-        }
-        __syncthreads();
-        if (cq >= 4) {
-            const double sc = rs[er];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) Wp[er * LS + 8 * (cq - 4) + i] = a[i] * sc;                 // L_D^-1 (lower)
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) La[((wq >> 1) * 16 + (lq >> 4) + 4 * i) * LS + (wq & 1) * 16 + (lq & 15)] = tsave[i];
-        __syncthreads();
+        for (int u = 0; u < 4; ++u) Wp[(16 + kq + 4 * u) * LS + il] = -t[u];
+        if (lq == 0) sflag = bad ? 1 : 0;
+    }
+    __syncthreads();
+    if (sflag) {                                   // the same block in every workgroup of the panel: all leave
+        if (tid == 0 && blockIdx.x == 0) flag[z] = 1;
+        return;
     }
     stamp(2);
     if (I == k) {
@@ -287,68 +242,6 @@ __global__ void __launch_bounds__(256) chol_panel_kernel(int ld, int k, int nbk,
         B[(size_t)(I * BT + r) * ld + k * BT + c] = o[i];
     }
     stamp(3);
-}
-
-// W = L^-1 by forward substitution on tiles: workgroup (K, cq) owns 8 columns of block column K and walks down
-// the block rows; the tiles it wrote are re-read through global memory after a workgroup barrier.
-// The terms L_IJ W_JK of a block row are independent of one another: they are taken FOUR tiles of L per pair of barriers (all
-// sixteen loads of a thread in flight together; one tile per pair of barriers left the walk at ~1.9 us a term, 300 terms for
-// block column 0 at n = 800: 0.58 ms).
-constexpr int TI_CHUNK = 4;
-__global__ void __launch_bounds__(256) tri_inverse_kernel(int ld, int nbk, const double* __restrict__ Lm,
-                                                          const double* __restrict__ LiBuf, double* W,
-                                                          const int* __restrict__ flag, size_t mat_stride) {
-    __shared__ double Lt[TI_CHUNK][BT * LS], Li[BT * LS], Wt[TI_CHUNK][BT * 8], Acc[BT * 8];
-    const int z = blockIdx.z;
-    if (flag[z]) return;
-    Lm += z * mat_stride;
-    W += z * mat_stride;
-    LiBuf += (size_t)z * nbk * BT * BT;
-    const int K = blockIdx.x, cq = blockIdx.y;
-    const int tid = threadIdx.x, t = tid >> 3, u = tid & 7, c = cq * 8 + u;
-    for (int I = K; I < nbk; ++I) {
-#pragma unroll
-        for (int e4 = 0; e4 < BT * BT / 256; ++e4) {
-            const int e = tid + 256 * e4;
-            Li[(e >> 5) * LS + (e & 31)] = LiBuf[(size_t)I * BT * BT + e];
-        }
-        double acc = 0.0;
-        for (int J0 = K; J0 < I; J0 += TI_CHUNK) {
-            const int nj = I - J0 < TI_CHUNK ? I - J0 : TI_CHUNK;
-            __syncthreads();
-#pragma unroll
-            for (int jj = 0; jj < TI_CHUNK; ++jj) {
-                if (jj < nj) {
-                    const int J = J0 + jj;
-#pragma unroll
-                    for (int e4 = 0; e4 < BT * BT / 256; ++e4) {
-                        const int e = tid + 256 * e4;
-                        Lt[jj][(e >> 5) * LS + (e & 31)] = Lm[(size_t)(I * BT + (e >> 5)) * ld + J * BT + (e & 31)];
-                    }
-                    Wt[jj][t * 8 + u] = W[(size_t)(J * BT + t) * ld + K * BT + c];
-                }
-            }
-            __syncthreads();
-            for (int jj = 0; jj < nj; ++jj) {
-#pragma unroll 8
-                for (int m = 0; m < BT; ++m) acc += Lt[jj][t * LS + m] * Wt[jj][m * 8 + u];
-            }
-        }
-        double val;
-        if (I == K) {
-            __syncthreads();
-            val = Li[t * LS + c];
-        } else {
-            Acc[t * 8 + u] = acc;
-            __syncthreads();
-            val = 0.0;
-#pragma unroll 8
-            for (int m = 0; m < BT; ++m) val -= Li[t * LS + m] * Acc[m * 8 + u];
-        }
-        W[(size_t)(I * BT + t) * ld + K * BT + c] = val;
-        __threadfence_block();
-        __syncthreads();
-    }
 }
 
 // Working copies with leading dimension ld >= n: Bw = B + reg I with a unit diagonal on the ghost rows of the padding
@@ -381,54 +274,14 @@ __global__ void __launch_bounds__(TPB) transpose_kernel(int n, int ld, const dou
     for (int j = blockIdx.x * TPB + threadIdx.x; j < n; j += gridDim.x * TPB) X[(size_t)i * ld + j] = W[(size_t)j * ld + i];
 }
 
-// ---- step 2: C = op(A) op(B) on the f64 MFMA: a workgroup owns a 32 x 32 tile of C, the operands pass through LDS in
-// 32-deep slices, each of the four waves accumulates one 16 x 16 quarter ------------------------------------------
-template <bool TA, bool TB>
-__global__ void __launch_bounds__(256) gemm_kernel(int n, int ld, const double* __restrict__ A,
-                                                   const double* __restrict__ Bm, double* __restrict__ C,
-                                                   size_t mat_stride) {
-    __shared__ double sa[BT * LS], sb[BT * LS];          // sa[i][k] = op(A)[row0 + i][k0 + k], sb[k][j] = op(B)[k0 + k][col0 + j]
-    const int z = blockIdx.z;
-    A += z * mat_stride;
-    Bm += z * mat_stride;
-    C += z * mat_stride;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int row0 = blockIdx.y * BT, col0 = blockIdx.x * BT;
-    d4 acc = {0, 0, 0, 0};
-    for (int k0 = 0; k0 < n; k0 += BT) {
-        for (int e = tid; e < BT * BT; e += 256) {
-            const int r = e >> 5, c = e & 31;            // c runs along the contiguous dimension of the source
-            {
-                const int i = TA ? c : r, kk = TA ? r : c;                 // source element (r, c) of A's 32 x 32 window
-                const int gi = row0 + i, gk = k0 + kk;
-                const double v = (gi < n && gk < n) ? (TA ? A[(size_t)gk * ld + gi] : A[(size_t)gi * ld + gk]) : 0.0;
-                sa[i * LS + kk] = v;
-            }
-            {
-                const int kk = TB ? c : r, j = TB ? r : c;
-                const int gk = k0 + kk, gj = col0 + j;
-                const double v = (gk < n && gj < n) ? (TB ? Bm[(size_t)gj * ld + gk] : Bm[(size_t)gk * ld + gj]) : 0.0;
-                sb[kk * LS + j] = v;
-            }
-        }
-        __syncthreads();
-        const d4 part = mm32_mfma<false>(sa, sb, w, lane);
-        for (int t = 0; t < 4; ++t) acc[t] += part[t];
-        __syncthreads();
-    }
-    const int orow = row0 + (w >> 1) * 16 + (lane >> 4), ocol = col0 + (w & 1) * 16 + (lane & 15);
-    for (int t = 0; t < 4; ++t)
-        if (orow + 4 * t < n && ocol < n) C[(size_t)(orow + 4 * t) * ld + ocol] = acc[t];
-}
-
-// ---- round 4: a general product for the factor-and-whiten stage --------------------------------------------------------------
+// ---- W = L^-1 and step 2: a general product for the factor-and-whiten stage --------------------------------------------------
 // C = alpha op(A) op(B), 64 x 64 tile per workgroup, each of the four waves a 32 x 32 quarter (2 x 2 MFMA tiles), operands
 // straight from global memory in the MFMA's own layout (no LDS: the two waves that share an operand strip hit the same lines
 // of the CU's L1), K in chunks of 16 with the next chunk's loads in flight during this chunk's sixteen MFMAs.
 //   A operand, element (i, k): A[i lda + k]  (one 32-byte load per lane and chunk: lane (r, kq) holds k0 + 4 kq .. + 3; MFMA j of
 //                                             the chunk contracts k0 + 4 kq + j -- any order of the contraction index serves)
 //   B operand, element (k, j): TB ? B[j ldb + k] (the same 32-byte pattern) : B[k ldb + j] (four 8-byte loads, coalesced over j)
-// Two levels of batch: blockIdx.z = z * n2 + p, pointer = base + z * s?1 + p * s?2 (p: the pairs of a level of tri_invert).
+// Two levels of batch: blockIdx.z = z * n2 + p, pointer = base + z * s?1 + p * s?2 (p: the pairs of a level of the recursive halving).
 // klim 1: A is lower triangular, k stops at the tile's last row; klim 2: op(B) = W^T with W lower triangular, k stops at the tile's
 // last column.  lower_only: tiles strictly above the diagonal are not computed (the caller mirrors).
 struct Gemm64 {
@@ -524,16 +377,6 @@ __global__ void __launch_bounds__(256) diag_inverse_scatter_kernel(int ld, int n
     for (int e = threadIdx.x; e < BT * BT; e += 256) dst[(size_t)(e >> 5) * ld + (e & 31)] = src[e];
 }
 
-__global__ void __launch_bounds__(TPB) symmetrise_kernel(int n, int ld, double* __restrict__ C, size_t mat_stride) {
-    C += blockIdx.z * mat_stride;
-    const int i = blockIdx.y;
-    for (int j = blockIdx.x * TPB + threadIdx.x; j < i; j += gridDim.x * TPB) {
-        const double m = 0.5 * (C[(size_t)i * ld + j] + C[(size_t)j * ld + i]);
-        C[(size_t)i * ld + j] = m;
-        C[(size_t)j * ld + i] = m;
-    }
-}
-
 // ---- step 3 ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void rr_pair(int ne, int r, int a, int& p, int& q) {
     const int m1 = ne - 1;
@@ -577,21 +420,17 @@ __device__ __forceinline__ void sym_rotation(double alpha, double gamma, double 
 
 __device__ __forceinline__ int tile_index(int I, int J, int t) { return t < BH ? I * BH + t : J * BH + t - BH; }
 
-// One block round.  Tile (P, Q), P <= Q, of the pair grid: rows = the two 16-blocks of pair P, columns = those of
-// pair Q.  The workgroup runs the inner sweep on the diagonal tiles (P, P) and (Q, Q) side by side, one per half of
-// its 512 threads: thread (a, b) of a half owns the 2 x 2 block rows {p_a, q_a} x columns {p_b, q_b} of its tile and
-// rows {2a, 2a+1} of the accumulated rotation V; thread (0, b) derives the rotation of pair b and publishes it (the
-// inner rounds are bound by instruction issue, so the rotations are worked out in one wave per tile only).
-// Then V_P^T C[P,Q] V_Q (and its transpose) goes to the other global buffer and the two tiles of X this workgroup
-// owns are rotated in place.
+// One block round on the tiles (P, Q), P <= Q, of the pair grid: rows = the two 16-blocks of pair P, columns = those of pair Q.
+// MODE 1, one workgroup per pair (P = Q), solves the pair problem.  The first half of its 512 threads runs the inner sweep on
+// the diagonal tile: thread (a, b) owns the 2 x 2 block rows {p_a, q_a} x columns {p_b, q_b} of the tile and rows {2a, 2a+1}
+// of the accumulated rotation V_P; thread (0, b) derives the rotation of pair b and publishes it (the inner rounds are bound
+// by instruction issue, so the rotations are worked out in one wave only).  The rotated tile goes to the other global
+// buffer, V_P to Vbuf, and the pair's X tile is rotated in place.
 // `full`: the inner sweep visits all 496 pairs of the 32 indices (first round of a sweep: that is where the pairs
 // inside one 16-block are annihilated); otherwise only the 256 pairs across the two blocks, in 16 rounds.
-//
-// MODE 0: all of the above in one launch (np (np + 1) / 2 workgroups; rounds 1-2, now the A/B switch APV_LARGE_SPLIT=0).  The
-// redundant inner sweeps cost real time once a launch fills the chip (n = 800: 25 pair problems solved by 650 workgroups), and
-// even below that the off-diagonal workgroups are better off not sweeping.  Round 3 splits the round: MODE 1, np workgroups,
-// solves the pair problems (the diagonal tiles: inner sweep, rotated tile, its X tile) and leaves the rotations V_P in Vbuf;
-// MODE 2, np (np - 1) / 2 workgroups, takes V_P, V_Q from there and applies them to its off-diagonal tile and its two X tiles.
+// MODE 5 (look-ahead, see la_solve_kernel), one workgroup per tile, applies the round's rotations.  A diagonal workgroup
+// copies the rotated tile and V_P that the pair solve left in Dbuf and Vbuf and rotates its X tile; an off-diagonal one
+// writes V_P^T C[P,Q] V_Q (and its transpose) to the other global buffer and rotates its two X tiles.
 template <int MODE>
 __device__ __forceinline__ void block_jacobi_round_body(double* sm, double2 (*rot)[BH], int blk, int ld, int nb, int round, int full,
                                                         const double* __restrict__ Cin, double* __restrict__ Cout,
@@ -605,18 +444,14 @@ __device__ __forceinline__ void block_jacobi_round_body(double* sm, double2 (*ro
     X += z * mat_stride;
     const int np = nb / 2;
     int P = 0, rem = blk;
-    // MODE 5 (look-ahead, see la_solve_kernel): the update half of a round for ALL tiles -- diagonal workgroups copy the rotated
-    // tile from Dbuf and rotate their X tile, the others are MODE 2
     if (MODE == 1) {
         P = blk;
         rem = 0;
     } else {
-        const int skip = (MODE == 2) ? 1 : 0;                 // MODE 2 enumerates the tiles above the diagonal only
-        while (rem >= np - P - skip) {
-            rem -= np - P - skip;
+        while (rem >= np - P) {
+            rem -= np - P;
             ++P;
         }
-        rem += skip;
     }
     const int Q = P + rem;
     const bool diag = P == Q;
@@ -633,7 +468,7 @@ __device__ __forceinline__ void block_jacobi_round_body(double* sm, double2 (*ro
         if (MODE == 5 && diag) {                              // look-ahead: the pair solve has left the rotated tile and V_P behind
             SP[t * LS + u] = Dbuf[((size_t)z * np + P) * TS + t * LS + u];
             VP[t * LS + u] = Vz[(size_t)P * TS + t * LS + u];
-        } else if (MODE != 2 && MODE != 5) {
+        } else if (MODE == 1) {
             SP[t * LS + u] = Cin[gr + tile_index(IP, JP, u)];
             VP[t * LS + u] = (t == u) ? 1.0 : 0.0;
         } else {
@@ -641,18 +476,13 @@ __device__ __forceinline__ void block_jacobi_round_body(double* sm, double2 (*ro
             VQ[t * LS + u] = Vz[(size_t)Q * TS + t * LS + u];
             T[t * LS + u] = Cin[gr + tile_index(IQ, JQ, u)];
         }
-        if (MODE == 0 && !diag) {
-            SQ[t * LS + u] = Cin[(size_t)tile_index(IQ, JQ, t) * ld + tile_index(IQ, JQ, u)];
-            T[t * LS + u] = Cin[gr + tile_index(IQ, JQ, u)];
-            VQ[t * LS + u] = (t == u) ? 1.0 : 0.0;
-        }
     }
     __syncthreads();
-    // ---- inner sweep -------------------------------------------------------------------------------
+    // ---- inner sweep (MODE 1 only; there P = Q, so only the first half is active) --------------------
     const bool active = half == 0 || !diag;
     double* const S = half ? SQ : SP;
     double* const V = half ? VQ : VP;
-    const int inner_rounds = (MODE == 2 || MODE == 5) ? 0 : (full ? BT - 1 : BH);
+    const int inner_rounds = (MODE == 5) ? 0 : (full ? BT - 1 : BH);
     // round-robin positions of pair a / pair b, advanced incrementally (rr_pair without the modulo)
     int ua = (a == 0) ? BT - 1 : a, va = (a == 0) ? 0 : BT - 1 - a;
     int ub = (b == 0) ? BT - 1 : b, vb = (b == 0) ? 0 : BT - 1 - b;
@@ -774,10 +604,8 @@ __global__ void __launch_bounds__(TPB) frob2_kernel(int n, int ld, const double*
     if (threadIdx.x == 0) atomicAdd(out + blockIdx.z, red[0]);
 }
 
-// out[0..count) = 0.  A kernel, not hipMemsetAsync, so that the captured two-sweep hipGraph holds kernel nodes only.  Round 1
-// saw rocprofv3 --kernel-trace segfault at the first replay of this graph and suspected its memset node; in round 2 the crash
-// did not reproduce with or without that node (profiles/r02/rocprof_graph.md: five command lines) -- the likelier causes, a
-// per-thread flag read and an unordered upload, were fixed meanwhile.  The kernel node stays: it traces like any other launch.
+// out[0..count) = 0.  A kernel, not hipMemsetAsync, so that the captured sweep graphs hold kernel nodes only, which a kernel
+// trace records like any other launch.
 __global__ void __launch_bounds__(64) zero_f64_kernel(int count, double* __restrict__ out) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < count) out[i] = 0.0;
@@ -883,8 +711,8 @@ __global__ void __launch_bounds__(512) block_jacobi_round_kernel(int ld, int nb,
 // the blocks (I', I'), (J', J') -- sub-blocks of round r's ROTATED diagonal tiles, which the pair solves of round r leave in Dbuf --
 // and (I', J'), a sub-block of V_a^T C_r[tile (a, b)] V_b for the two round-r pairs a, b that held I' and J' (never the same pair
 // two rounds running).  la_solve_kernel forms that one tile itself (two 32^3 products) and solves, so that the update of round
-// r (la: block_jacobi_round_kernel<5>, the whole chip) runs BESIDE the pair solves of round r + 1 (np workgroups, one long
-// dependent chain each) on a second stream: a round costs the longer of the two instead of their sum.
+// r (block_jacobi_round_body<5>, the whole chip) runs BESIDE the pair solves of round r + 1 (np workgroups, one long
+// dependent chain each) in the same launch (la_fused_kernel): a round costs the longer of the two instead of their sum.
 
 // pair index and position (0: first, 1: second block) of block A in round r of the tournament
 __device__ __forceinline__ void rr_locate(int ne, int r, int A, int& pair, int& half) {
@@ -1153,11 +981,6 @@ int apv_gevd_large(apv_handle* h, int n, int batch, const double* d_A, const dou
     const size_t mb = sizeof(double) * ms * batch;
     const int gx = (ne + TPB - 1) / TPB;
     const int tiles = np * (np + 1) / 2;
-    // the pair solves and the updates of a round as two launches (see the kernel); APV_LARGE_SPLIT=0 is the A/B switch back to one.
-    // Measured (tools/bench_broadband.py): n = 256 two pairs 4.43 -> 4.29 ms per hop, sixteen pairs 1.24 -> 0.95 ms per hop,
-    // n = 800 two pairs 32.6 -> 24.9 ms per hop -- the split wins even where the chip is far from full.
-    static const int split_env = getenv("APV_LARGE_SPLIT") ? atoi(getenv("APV_LARGE_SPLIT")) : -1;
-    const bool split = split_env != 0;
     if (ws.n != n || ws.cap < batch) {
         ws.release();
         ws.n = n;
@@ -1177,27 +1000,29 @@ int apv_gevd_large(apv_handle* h, int n, int batch, const double* d_A, const dou
     }
     GevdLargeGraphs& gs = ws.set_for(batch);
     // two sweeps: 2 (nb - 1) block rounds bring the ping-pong buffers back to where they started
-    static const bool memset_node = getenv("APV_GRAPH_MEMSET") != nullptr;      // A/B switch: a memset node instead (see zero_f64_kernel)
-    // look-ahead (see la_solve_kernel): APV_LARGE_LOOKAHEAD=0 is the A/B switch back to solve-then-update on one stream
-    static const bool la_off = getenv("APV_LARGE_LOOKAHEAD") && atoi(getenv("APV_LARGE_LOOKAHEAD")) == 0;
-    const bool lookahead = split && !la_off && np >= 2;
     // nsweeps = 2: both accumulators, C0 -> C0.  nsweeps = 1: one sweep from C0 (odd = false, accumulator a) or from C1 (odd = true,
     // accumulator b) into the other buffer -- rounds = nb - 1 is odd, so a sweep leaves the matrix in the buffer it did not start in.
-    auto sweeps_la = [&](int nsweeps, bool odd) {
+    // From two pairs on, the pair solves of round r + 1 run in the launch that updates round r (see la_solve_kernel); a single pair
+    // (n <= 32) is solved and rotated by one block_jacobi_round_kernel<1> launch a round.
+    auto sweeps = [&](int nsweeps, bool odd) {
         double* const acc0 = ws.acc + (odd ? (size_t)batch : 0);
         hipLaunchKernelGGL(zero_f64_kernel, dim3((nsweeps * batch + 63) / 64), dim3(64), 0, st, nsweeps * batch, acc0);
         double *Cc = odd ? ws.C1 : ws.C0, *Cn = odd ? ws.C0 : ws.C1;
         const int total = nsweeps * rounds;
         // the pair solves of the very first round read the matrix as it stands
-        hipLaunchKernelGGL(la_solve_kernel<true>, dim3(np, 1, batch), dim3(512), 0, st, ld, nb, 0, 0, 1, Cc, (const double*)ws.Vbuf2,
-                           (const double*)ws.Dbuf2, ws.Vbuf, ws.Dbuf, acc0, ms);
+        if (np >= 2)
+            hipLaunchKernelGGL(la_solve_kernel<true>, dim3(np, 1, batch), dim3(512), 0, st, ld, nb, 0, 0, 1, Cc, (const double*)ws.Vbuf2,
+                               (const double*)ws.Dbuf2, ws.Vbuf, ws.Dbuf, acc0, ms);
         for (int gr = 0; gr < total; ++gr) {
             const int r = gr % rounds;
             double* Vcur = (gr & 1) ? ws.Vbuf2 : ws.Vbuf;
             double* Dcur = (gr & 1) ? ws.Dbuf2 : ws.Dbuf;
             double* Vnext = (gr & 1) ? ws.Vbuf : ws.Vbuf2;
             double* Dnext = (gr & 1) ? ws.Dbuf : ws.Dbuf2;
-            if (gr + 1 < total) {
+            if (np == 1) {
+                hipLaunchKernelGGL(block_jacobi_round_kernel<1>, dim3(np, 1, batch), dim3(512), 0, st, ld, nb, r, r == 0 ? 1 : 0, Cc, Cn,
+                                   ws.X, acc0 + (size_t)(gr / rounds) * batch, ms, ws.Vbuf, (const double*)nullptr);
+            } else if (gr + 1 < total) {
                 const int rn = (gr + 1) % rounds, swn = (gr + 1) / rounds;
                 LaRound q{r, rn == 0 ? 1 : 0, rn, Cc, Cn, Vcur, Dcur, Vnext, Dnext, acc0 + (size_t)swn * batch};
                 hipLaunchKernelGGL(la_fused_kernel, dim3(np + tiles, 1, batch), dim3(512), 0, st, ld, nb, q, ws.X, ms);
@@ -1207,27 +1032,6 @@ int apv_gevd_large(apv_handle* h, int n, int batch, const double* d_A, const dou
             }
             double* t = Cc; Cc = Cn; Cn = t;
         }
-    };
-    auto sweeps = [&](int nsweeps, bool odd) {
-        if (lookahead) return sweeps_la(nsweeps, odd);
-        double* const acc0 = ws.acc + (odd ? (size_t)batch : 0);
-        if (memset_node) (void)hipMemsetAsync(acc0, 0, sizeof(double) * nsweeps * batch, st);
-        else hipLaunchKernelGGL(zero_f64_kernel, dim3((nsweeps * batch + 63) / 64), dim3(64), 0, st, nsweeps * batch, acc0);
-        double *Cc = odd ? ws.C1 : ws.C0, *Cn = odd ? ws.C0 : ws.C1;
-        for (int sw = 0; sw < nsweeps; ++sw)
-            for (int r = 0; r < rounds; ++r) {
-                if (!split) {
-                    hipLaunchKernelGGL(block_jacobi_round_kernel<0>, dim3(tiles, 1, batch), dim3(512), 0, st, ld, nb, r, r == 0 ? 1 : 0,
-                                       Cc, Cn, ws.X, acc0 + (size_t)sw * batch, ms, ws.Vbuf, (const double*)nullptr);
-                } else {
-                    hipLaunchKernelGGL(block_jacobi_round_kernel<1>, dim3(np, 1, batch), dim3(512), 0, st, ld, nb, r, r == 0 ? 1 : 0,
-                                       Cc, Cn, ws.X, acc0 + (size_t)sw * batch, ms, ws.Vbuf, (const double*)nullptr);
-                    if (np > 1)
-                        hipLaunchKernelGGL(block_jacobi_round_kernel<2>, dim3(tiles - np, 1, batch), dim3(512), 0, st, ld, nb, r, 0,
-                                           Cc, Cn, ws.X, acc0 + (size_t)sw * batch, ms, ws.Vbuf, (const double*)nullptr);
-                }
-                double* t = Cc; Cc = Cn; Cn = t;
-            }
     };
     static const bool no_graph = getenv("APV_NO_GRAPH") != nullptr;      // plain launches: rocprofv3 can then trace the rounds
     if (!gs.exec[0] && !no_graph) {
@@ -1254,16 +1058,13 @@ int apv_gevd_large(apv_handle* h, int n, int batch, const double* d_A, const dou
     LCHK(hipMemsetAsync(ws.flag, 0, sizeof(int) * batch, st));
     LCHK(hipMemsetAsync(ws.acc, 0, sizeof(double) * 3 * batch, st));
     hipLaunchKernelGGL(load_pair_kernel, dim3(gx, ne, batch), dim3(TPB), 0, st, n, ne, ld, d_A, d_B, reg, d_reg_scale, ws.C0, ws.Bw, ms);   // C0 holds A for now
-    static const bool old_panel = getenv("APV_LARGE_OLDPANEL") != nullptr;       // A/B switch: the 32-step elimination with a barrier a step
     static const bool panel_dbg = getenv("APV_LARGE_DEBUG") && atoi(getenv("APV_LARGE_DEBUG")) >= 2;
     if (panel_dbg) {
         const int on = 1;
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_panel_stamps_on), &on, sizeof(int));
     }
     for (int k = 0; k < nbk; ++k)
-        hipLaunchKernelGGL((old_panel ? chol_panel_kernel<false> : chol_panel_kernel<true>), dim3(nbk - k, 1, batch), dim3(256), 0, st, ld, k,
-                           nbk, ws.Bw, ws.Li, ws.flag, ms);
-    // APV_LARGE_OLDPRE=1: round 3's tile walk for W = L^-1 and its 32 x 32-tile products (A/B switch)
+        hipLaunchKernelGGL(chol_panel_kernel, dim3(nbk - k, 1, batch), dim3(256), 0, st, ld, k, nbk, ws.Bw, ws.Li, ws.flag, ms);
     if (panel_dbg) {
         (void)hipStreamSynchronize(st);
         unsigned long long hs[64 * 4];
@@ -1272,41 +1073,32 @@ int apv_gevd_large(apv_handle* h, int n, int batch, const double* d_A, const dou
             fprintf(stderr, "[apv gevd_large] panel %d, last row tile, s_memtime ticks: left-looking terms %llu, diagonal block %llu, product + store %llu\n", k,
                     hs[4 * k + 1] - hs[4 * k], hs[4 * k + 2] - hs[4 * k + 1], hs[4 * k + 3] - hs[4 * k + 2]);
     }
-    static const bool old_pre = getenv("APV_LARGE_OLDPRE") != nullptr;
-    if (old_pre) {
-        hipLaunchKernelGGL(tri_inverse_kernel, dim3(nbk, BT / 8, batch), dim3(256), 0, st, ld, nbk, ws.Bw, ws.Li, ws.W, ws.flag, ms);
-        const dim3 gg((n + BT - 1) / BT, (n + BT - 1) / BT, batch);
-        hipLaunchKernelGGL((gemm_kernel<false, false>), gg, dim3(256), 0, st, n, ld, ws.W, ws.C0, ws.T1, ms);     // T1 = W A
-        hipLaunchKernelGGL((gemm_kernel<false, true>), gg, dim3(256), 0, st, n, ld, ws.T1, ws.W, ws.C0, ms);      // C = T1 W^T
-        hipLaunchKernelGGL(symmetrise_kernel, dim3(gx, n, batch), dim3(TPB), 0, st, n, ld, ws.C0, ms);
-    } else {
-        // W = L^-1 by recursive halving: with L = [L11 0; L21 L22], L^-1 = [W11 0; -W22 L21 W11  W22].  The diagonal 32 x 32
-        // blocks are the panel kernel's; every level doubles the block (32 -> 64 -> ...): two products per level over all pairs of
-        // the level at once (T1 is the scratch for L21 W11), ~ 2 log2(n / 32) launches instead of a walk of n / 32 dependent
-        // block rows.  Ghost rows: the padded part of L is the identity, so is W's.
-        hipLaunchKernelGGL(diag_inverse_scatter_kernel, dim3(nbk, 1, batch), dim3(256), 0, st, ld, nbk, ws.Li, ws.W, ms, ws.flag);
-        for (int sz = BT; sz < ne; sz *= 2) {
-            const int span = 2 * sz, full = ne / span, rem = ne - full * span;        // `full` complete pairs, then maybe a ragged one
-            for (int part = 0; part < 2; ++part) {
-                const int np_ = part == 0 ? full : (rem > sz ? 1 : 0);
-                if (np_ == 0) continue;
-                const int o0 = part == 0 ? 0 : full * span;                              // first index of the part's first pair
-                const int m2 = part == 0 ? sz : rem - sz;                                 // rows of the second block
-                const size_t off11 = (size_t)o0 * ld + o0, off21 = (size_t)(o0 + sz) * ld + o0, off22 = (size_t)(o0 + sz) * ld + o0 + sz;
-                const size_t ps = (size_t)span * ld + span;
-                Gemm64 g1{m2, sz, sz, ws.Bw + off21, ld, ms, ps, ws.W + off11, ld, ms, ps, ws.T1 + off21, ld, ms, ps, 1.0, np_, 0, 0, ws.flag};
-                hipLaunchKernelGGL((gemm64_kernel<false>), dim3((sz + 63) / 64, (m2 + 63) / 64, batch * np_), dim3(256), 0, st, g1);   // T = L21 W11
-                Gemm64 g2{m2, sz, m2, ws.W + off22, ld, ms, ps, ws.T1 + off21, ld, ms, ps, ws.W + off21, ld, ms, ps, -1.0, np_, 1, 0, ws.flag};
-                hipLaunchKernelGGL((gemm64_kernel<false>), dim3((sz + 63) / 64, (m2 + 63) / 64, batch * np_), dim3(256), 0, st, g2);   // W21 = -W22 T
-            }
+    // W = L^-1 by recursive halving: with L = [L11 0; L21 L22], L^-1 = [W11 0; -W22 L21 W11  W22].  The diagonal 32 x 32
+    // blocks are the panel kernel's; every level doubles the block (32 -> 64 -> ...): two products per level over all pairs of
+    // the level at once (T1 is the scratch for L21 W11), ~ 2 log2(n / 32) launches instead of a walk of n / 32 dependent
+    // block rows.  Ghost rows: the padded part of L is the identity, so is W's.
+    hipLaunchKernelGGL(diag_inverse_scatter_kernel, dim3(nbk, 1, batch), dim3(256), 0, st, ld, nbk, ws.Li, ws.W, ms, ws.flag);
+    for (int sz = BT; sz < ne; sz *= 2) {
+        const int span = 2 * sz, full = ne / span, rem = ne - full * span;        // `full` complete pairs, then maybe a ragged one
+        for (int part = 0; part < 2; ++part) {
+            const int np_ = part == 0 ? full : (rem > sz ? 1 : 0);
+            if (np_ == 0) continue;
+            const int o0 = part == 0 ? 0 : full * span;                              // first index of the part's first pair
+            const int m2 = part == 0 ? sz : rem - sz;                                 // rows of the second block
+            const size_t off11 = (size_t)o0 * ld + o0, off21 = (size_t)(o0 + sz) * ld + o0, off22 = (size_t)(o0 + sz) * ld + o0 + sz;
+            const size_t ps = (size_t)span * ld + span;
+            Gemm64 g1{m2, sz, sz, ws.Bw + off21, ld, ms, ps, ws.W + off11, ld, ms, ps, ws.T1 + off21, ld, ms, ps, 1.0, np_, 0, 0, ws.flag};
+            hipLaunchKernelGGL((gemm64_kernel<false>), dim3((sz + 63) / 64, (m2 + 63) / 64, batch * np_), dim3(256), 0, st, g1);   // T = L21 W11
+            Gemm64 g2{m2, sz, m2, ws.W + off22, ld, ms, ps, ws.T1 + off21, ld, ms, ps, ws.W + off21, ld, ms, ps, -1.0, np_, 1, 0, ws.flag};
+            hipLaunchKernelGGL((gemm64_kernel<false>), dim3((sz + 63) / 64, (m2 + 63) / 64, batch * np_), dim3(256), 0, st, g2);   // W21 = -W22 T
         }
-        const int gt = (ne + 63) / 64;
-        Gemm64 ga{ne, ne, ne, ws.W, ld, ms, 0, ws.C0, ld, ms, 0, ws.T1, ld, ms, 0, 1.0, 1, 1, 0, ws.flag};
-        hipLaunchKernelGGL((gemm64_kernel<false>), dim3(gt, gt, batch), dim3(256), 0, st, ga);                  // T1 = W A (W lower triangular)
-        Gemm64 gb{ne, ne, ne, ws.T1, ld, ms, 0, ws.W, ld, ms, 0, ws.C0, ld, ms, 0, 1.0, 1, 2, 1, ws.flag};
-        hipLaunchKernelGGL((gemm64_kernel<true>), dim3(gt, gt, batch), dim3(256), 0, st, gb);                   // C = T1 W^T, tiles on and below the diagonal
-        hipLaunchKernelGGL(mirror_lower_kernel, dim3(gx, ne, batch), dim3(TPB), 0, st, ne, ld, ws.C0, ms, ws.flag);
     }
+    const int gt = (ne + 63) / 64;
+    Gemm64 ga{ne, ne, ne, ws.W, ld, ms, 0, ws.C0, ld, ms, 0, ws.T1, ld, ms, 0, 1.0, 1, 1, 0, ws.flag};
+    hipLaunchKernelGGL((gemm64_kernel<false>), dim3(gt, gt, batch), dim3(256), 0, st, ga);                  // T1 = W A (W lower triangular)
+    Gemm64 gb{ne, ne, ne, ws.T1, ld, ms, 0, ws.W, ld, ms, 0, ws.C0, ld, ms, 0, 1.0, 1, 2, 1, ws.flag};
+    hipLaunchKernelGGL((gemm64_kernel<true>), dim3(gt, gt, batch), dim3(256), 0, st, gb);                   // C = T1 W^T, tiles on and below the diagonal
+    hipLaunchKernelGGL(mirror_lower_kernel, dim3(gx, ne, batch), dim3(TPB), 0, st, ne, ld, ws.C0, ms, ws.flag);
     hipLaunchKernelGGL(transpose_kernel, dim3(gx, n, batch), dim3(TPB), 0, st, n, ld, ws.W, ws.X, ms);         // X = W^T Q, Q = I
     std::vector<int> hflag(batch, 0);
     std::vector<double> hacc(3 * batch, 0.0);
@@ -1361,8 +1153,6 @@ int apv_gevd_large(apv_handle* h, int n, int batch, const double* d_A, const dou
     const int max_sweeps = ((h->cfg.max_sweeps > 0 ? h->cfg.max_sweeps : 30) / 2 + 1) * 2;
     // a sweep whose pivots weigh <= tol ||C||^2 leaves ~tol^2 behind (quadratic convergence); APV_LARGE_TOL2 is a tuning aid
     static const double kLargeTol2 = getenv("APV_LARGE_TOL2") ? atof(getenv("APV_LARGE_TOL2")) : 1e-16;   // 1e-20 (round 1) cost two more sweeps for the same G1 errors
-    // APV_LARGE_PAIRS=1: the stop test after every second sweep only, as before round 3's last change (A/B switch)
-    static const bool pairs_only = getenv("APV_LARGE_PAIRS") && atoi(getenv("APV_LARGE_PAIRS")) != 0;
     bool converged = false;
     size_t last_off = 0;          // where in hacc the last tested sweep's pivot weights are
     // The stop test costs a copy and a host synchronisation.  Consecutive calls of a stream solve problems of the same kind: of
@@ -1373,7 +1163,7 @@ int apv_gevd_large(apv_handle* h, int n, int batch, const double* d_A, const dou
     const double tol2 = h->gl_tol2 > 0.0 ? h->gl_tol2 : kLargeTol2;
     while (n_sweeps < max_sweeps && !converged) {
         const bool odd = n_sweeps & 1;
-        const bool pair = !odd && (n_sweeps < untested || pairs_only);
+        const bool pair = !odd && n_sweeps < untested;
         if (gs.exec[0]) LCHK(hipGraphLaunch(gs.exec[pair ? 0 : (odd ? 2 : 1)], st));
         else sweeps(pair ? 2 : 1, odd);
         n_sweeps += pair ? 2 : 1;

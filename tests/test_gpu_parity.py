@@ -288,6 +288,24 @@ def test_jdiag_large_vs_oracle(Engine, n, batch):
         eng2.jdiag_large(np.eye(70)[None], -np.eye(70)[None])
 
 
+@pytest.mark.parametrize("batch", [1, 3])
+@pytest.mark.parametrize("n", [1, 17, 32, 33, 64])      # one pair of blocks (n <= 32: no look-ahead), then two (the smallest look-ahead)
+def test_jdiag_large_small_orders_vs_oracle(Engine, n, batch):
+    rng = np.random.default_rng(n)
+    Y = rng.standard_normal((batch, 3 * n, n))
+    Z = rng.standard_normal((batch, 3 * n, n))
+    A = np.einsum("kmi,kmj->kij", Y, Y)
+    B = np.einsum("kmi,kmj->kij", Z, Z)
+    eng = Engine(1, 4, 4)
+    U, lam = eng.jdiag_large(A, B)
+    eng.close()
+    for k in range(batch):
+        _, lam_ref = gevd.jdiag(A[k], B[k])
+        assert np.abs(lam[k] / lam_ref - 1).max() < 1e-9
+        G = U[k].T @ (B[k] + 1e-7 * np.eye(n)) @ U[k]
+        assert np.abs(G - np.eye(n)).max() < 1e-10
+
+
 def _g8_pair(g):
     XB, XD, d = (g[k].astype(np.complex128) for k in ("XB", "XD", "d"))
     return XB.conj().T @ XB, XD.conj().T @ XD, XB.conj().T @ d
