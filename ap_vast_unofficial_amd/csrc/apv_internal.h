@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -122,7 +123,23 @@ long apv_bb_not_converged(const apv_handle* h);   // stream_bb.hip: hops of the 
 void apv_gevd_large_free(apv_handle* h);  // kernels_gevd_large.hip
 void apv_gevd_lead_free(apv_handle* h);   // kernels_gevd_lead.hip
 int apv_fail(apv_handle* h, int code, const std::string& msg);
+// sink != nullptr: apv_fail on the calling thread writes its message to *sink instead of the handle, until called with nullptr.  A
+// helper thread of a call sets it, so that h->err has one writer: the thread that returns the call's code.
+void apv_fail_redirect(std::string* sink);
 GevdParams apv_base_params(const apv_handle* h);
+
+// hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, bytes) on the current device, once per device: the attribute is the
+// device's.  `done` is the caller's static record for this kernel, bit d for device d (from device 64 on: set at every call).
+inline hipError_t apv_set_max_dynamic_lds(const void* kernel, int bytes, std::atomic<unsigned long long>& done) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = dev < 64 ? 1ull << dev : 0;
+    if (done.load(std::memory_order_relaxed) & bit) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
+    return e;
+}
 
 // kernels_gevd.hip
 hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s, std::string* why);

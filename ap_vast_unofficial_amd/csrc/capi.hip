@@ -16,9 +16,12 @@
 namespace {
 
 thread_local std::string g_create_err;
+thread_local std::string* g_err_sink = nullptr;      // apv_fail_redirect
 
 int fail(apv_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_create_err = msg;
+    if (g_err_sink) *g_err_sink = msg;
+    else if (h) h->err = msg;
+    else g_create_err = msg;
     return code;
 }
 
@@ -39,6 +42,7 @@ size_t lsize(const apv_handle* h) { return h->cfg.out_c128 ? 8 : 4; }
 }  // namespace
 
 int apv_fail(apv_handle* h, int code, const std::string& msg) { return fail(h, code, msg); }
+void apv_fail_redirect(std::string* sink) { g_err_sink = sink; }
 
 GevdParams apv_base_params(const apv_handle* h);
 

@@ -11,9 +11,9 @@
 //             parameters (20 % shared), and a stateless solve keeps a resumed stream bit for bit
 //     pass    Z = C Y                                         one block product (f64 MFMA, the matrix streams from L2 / HBM)
 //             G = Y^T Y, H = Y^T Z                            b x b Gram matrices, K split over slabs of 128 rows
-//             (H, G) -> T, theta                              ONE workgroup: scale to a unit diagonal, eliminate [G | I] (Cholesky
-//                                                             factor and its inverse in one go), M = L^-1 H L^-T, cyclic Jacobi
-//                                                             in LDS, sort, T = D L^-T Q
+//             (H, G) -> T, theta                              ONE workgroup: scale to a unit diagonal, L^-1 with G = L L^T
+//                                                             (blocked in 16 x 16 tiles), M = L^-1 H L^-T, cyclic Jacobi in LDS,
+//                                                             sort, T = D L^-T Q
 //             X = Y T, res_j = ||Z T_j - theta_j X_j||        Ritz vectors, their residuals (partial sums per row tile; the host
 //                                                             adds them up) and step 1 of the next filter (C X = Z T is known)
 //             host: converged?  else degree m of the next filter from the Ritz values
@@ -32,7 +32,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 namespace {
 
@@ -281,14 +280,14 @@ __device__ __forceinline__ void lead_rotation(double alpha, double gamma, double
     s = rotate ? td * cc : 0.0;
 }
 
-// 16 x 16 tile of op(A) op(B) with operands in LDS (row stride ld), K deep: acc[t] = element (row0 + (lane >> 4) + 4 t, col0 + (lane & 15))
-template <bool TA, bool TB, int K>
+// 16 x 16 tile of A op(B) with operands in LDS (row stride ld), K deep: acc[t] = element (row0 + (lane >> 4) + 4 t, col0 + (lane & 15))
+template <bool TB, int K>
 __device__ __forceinline__ d4 lead_tile(const double* A, const double* Bm, int ld, int row0, int col0, int lane) {
     const int il = lane & 15, kq = lane >> 4;
     d4 acc = {0, 0, 0, 0};
 #pragma unroll 4
     for (int k0 = 0; k0 < K; k0 += 4) {
-        const double av = TA ? A[(k0 + kq) * ld + row0 + il] : A[(row0 + il) * ld + k0 + kq];
+        const double av = A[(row0 + il) * ld + k0 + kq];
         const double bv = TB ? Bm[(col0 + il) * ld + k0 + kq] : Bm[(k0 + kq) * ld + col0 + il];
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
     }
@@ -349,7 +348,7 @@ __device__ __forceinline__ d4 lead_mm16(FA fa, FB fb, int lane, d4 acc) {
 
 // The projected problem of one pass: (H, G) of order B -> T [B][B] (X = Y T has orthonormal columns that diagonalise C on
 // span Y), theta [B] descending; hinfo[z] = {theta[B], Gram breakdown, sweeps, Jacobi met its bound, -} is what the host reads.
-template <int B, int NT, bool MOVE>
+template <int B, int NT>
 __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double* __restrict__ Gp, const double* __restrict__ Hp,
                                                         int max_sweeps, double tol2, double* __restrict__ T,
                                                         double* __restrict__ theta, double* __restrict__ hinfo, unsigned active,
@@ -359,13 +358,12 @@ __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double*
     double* S0 = sm;                 // G -> W H -> Q
     double* S1 = S0 + B * LD;        // H -> M
     double* S2 = S1 + B * LD;        // W = L^-1
-    double* S3 = S2 + B * LD;        // MOVE: the second buffer of M's ping-pong (S2 is Q's once W^T has moved into S0)
-    double* dsc = S3 + (MOVE ? B * LD : 0);       // [B] 1/sqrt(diag G)
+    double* S3 = S2 + B * LD;        // the second buffer of M's ping-pong (S2 is Q's once W^T has moved into S0)
+    double* dsc = S3 + B * LD;       // [B] 1/sqrt(diag G)
     double* th = dsc + B;            // [B]
     double* pw = th + B;             // [NP] pivot weights of a sweep
     double2* cs = reinterpret_cast<double2*>(pw + NP + (NP & 1));    // [NP]
-    int* pq = reinterpret_cast<int*>(cs + NP);                       // [B]: p of pair k, then q of pair k
-    int* rk = pq + B;                                                // [B]
+    int* rk = reinterpret_cast<int*>(cs + NP);                       // [B]
     __shared__ int fail;
     __shared__ double scal[2];
     const int z = blockIdx.x;
@@ -434,13 +432,14 @@ __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double*
     }
     __syncthreads();
     stamp(1);
-    if constexpr (MOVE) {
+    {   // (phases c and e are blocks of their own: without the scopes that end their locals, the kernel compiles differently)
         // c: W = L^-1 with G = L L^T, blocked in 16 x 16 tiles as the order-64 kernel's factorisation: the diagonal tile is inverted by
         // ONE wave (lead_wave_inv16, 16 steps without a barrier), the panel L_ik = G_ik W_kk^T and the trailing update
         // G_ij -= L_ik L_jk^T are tile products on the matrix cores, and the off-diagonal tiles of W follow by block forward
         // substitution, W_ba = -W_bb sum_k L_bk W_ka, one block diagonal after the other: 5 B / 16 - 2 barriers instead of B, and
-        // no pass over all of both halves per pivot (the loop below: 28 us of the kernel's 103 at B = 64).  The pivots are those of
-        // the unblocked elimination; one at or below 1e-13 (the Gram matrix has a unit diagonal) is a breakdown.
+        // no pass over all of both halves per pivot (the unblocked elimination of [G | I] that this replaced: 28 us of the kernel's
+        // 103 at B = 64).  The pivots are those of the unblocked elimination; one at or below 1e-13 (the Gram matrix has a unit
+        // diagonal) is a breakdown.
         const int il = lane & 15, kq = lane >> 4;
         for (int kb = 0; kb < NTL; ++kb) {
             const int o = 16 * kb;
@@ -504,53 +503,19 @@ __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double*
             }
             __syncthreads();
         }
-    } else {
-    // c: eliminate [G | I]: G = Lt D Lt^T, the right half becomes Lt^-1; pivots stay on G's diagonal
-    // (a register-resident variant -- rows in registers, pivot row and column published through LDS, the 64 steps unrolled --
-    // was measured: 8 256 instructions, and SLOWER, 178 949 ticks against 66 928 at B = 64; this loop stays)
-    for (int k = 0; k < B - 1; ++k) {
-        const double piv = S0[k * LD + k];
-        if (!(piv > 1e-13)) {                    // uniform: every thread reads the same word
-            if (tid == 0) fail = 1;
-            break;
-        }
-        const double rp = 1.0 / piv;
-        for (int e = tid; e < (B - 1 - k) * B; e += NT) {
-            const int i = k + 1 + e / B, j = e % B;
-            const double f = S0[i * LD + k] * rp;
-            if (j > k) S0[i * LD + j] = __builtin_fma(-f, S0[k * LD + j], S0[i * LD + j]);
-            else S2[i * LD + j] = __builtin_fma(-f, S2[k * LD + j], S2[i * LD + j]);
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    if (!(S0[(B - 1) * LD + B - 1] > 1e-13) && tid == 0) fail = 1;
-    __syncthreads();
-    if (fail) {
-        if (tid == 0) {
-            hinfo[(size_t)z * (B + 4) + B] = 1.0;
-            hinfo[(size_t)z * (B + 4) + B + 1] = 0.0;
-            hinfo[(size_t)z * (B + 4) + B + 2] = 0.0;
-        }
-        return;
-    }
-    if (tid < B) th[tid] = lead_rsq(S0[tid * LD + tid]);
-    __syncthreads();
-    for (int e = tid; e < B * B; e += NT) S2[(e / B) * LD + e % B] *= th[e / B];        // W = D^-1/2 Lt^-1
-    __syncthreads();
     }
     stamp(2);
     // d: M = W H W^T
     for (int tile = wv; tile < NTL * NTL; tile += NW) {
         const int r0 = (tile / NTL) * 16, c0 = (tile % NTL) * 16;
-        const d4 a = lead_tile<false, false, B>(S2, S1, LD, r0, c0, lane);
+        const d4 a = lead_tile<false, B>(S2, S1, LD, r0, c0, lane);
 #pragma unroll
         for (int t = 0; t < 4; ++t) S0[(r0 + (lane >> 4) + 4 * t) * LD + c0 + (lane & 15)] = a[t];
     }
     __syncthreads();
     for (int tile = wv; tile < NTL * NTL; tile += NW) {
         const int r0 = (tile / NTL) * 16, c0 = (tile % NTL) * 16;
-        const d4 a = lead_tile<false, true, B>(S0, S2, LD, r0, c0, lane);
+        const d4 a = lead_tile<true, B>(S0, S2, LD, r0, c0, lane);
 #pragma unroll
         for (int t = 0; t < 4; ++t) S1[(r0 + (lane >> 4) + 4 * t) * LD + c0 + (lane & 15)] = a[t];
     }
@@ -567,8 +532,8 @@ __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double*
             const double m = S1[i * LD + i];
             nrm += m * m;
         }
-        // Q = I (W H is spent); MOVE: the accumulator starts as W^T, so that the sweeps leave W^T Q and W's buffer is free for them
-        S0[i * LD + j] = MOVE ? S2[j * LD + i] : (i == j ? 1.0 : 0.0);
+        // the accumulator starts as W^T (W H is spent), so that the sweeps leave W^T Q and W's buffer is free for them
+        S0[i * LD + j] = S2[j * LD + i];
     }
     // ||M||_F^2 (order of the sum fixed: lanes through DPP-free LDS tree)
     __shared__ double redn[NT];
@@ -585,14 +550,14 @@ __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double*
     // e: cyclic Jacobi, round-robin pairing (player 0 fixed, the others rotate)
     int sweeps = 0, conv = 0;
     double *Mc = S1, *Qc = S0;                 // where M and the accumulator are when the sweeps are done
-    if constexpr (MOVE) {
-        // The same tournament with the ROWS AND COLUMNS MOVING instead of the pairing: pair k is always slots (k, B-1-k), and a
+    {
+        // The tournament with the ROWS AND COLUMNS MOVING instead of the pairing: pair k is always slots (k, B-1-k), and a
         // round writes what it rotated one slot on (slot 0 stays, s -> s + 1, B-1 -> 1: the circle method), M and the accumulator
         // each into a second buffer.  Which elements a thread reads and where it writes them is then the same in every round --
         // no pairing table, no index arithmetic inside the round, the addresses are loop invariants -- and the rotations are
-        // those of the in-place form bit for bit (same pairs, same order of operands).  After B - 1 rounds everything is back in
-        // its own slot.  The round is bound by the instructions the one compute unit issues: the in-place form spent ~150 per
-        // thread and round at B = 64 (pair indices and rotations fetched from LDS, two multiply-adds per address).
+        // those of the in-place form with a pairing table bit for bit (same pairs, same order of operands).  After B - 1 rounds
+        // everything is back in its own slot.  The round is bound by the instructions the one compute unit issues: the in-place
+        // form spent ~150 per thread and round at B = 64 (pair indices and rotations fetched from LDS, two multiply-adds per address).
         auto nx = [](int sl) { return sl == 0 ? 0 : (sl == B - 1 ? 1 : sl + 1); };
         double *Mn = S3, *Qn = S2;
         constexpr int MI = (NP * NP + NT - 1) / NT, QI = (B * NP + NT - 1) / NT;
@@ -660,65 +625,9 @@ __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double*
             }
             __syncthreads();
             ++sweeps;
-            conv = scal[0] <= tol2 * norm2;
+            conv = scal[0] <= tol2 * norm2;         // a sweep whose pivots weigh <= tol2 ||M||^2 leaves ~tol2^2 behind
             __syncthreads();
         }
-    } else {
-    for (int sw = 0; sw < max_sweeps && !conv; ++sw) {
-        double pwk = 0.0;
-        // (Tried: every thread forms the two rotations its 2 x 2 block needs from the pivots it reads itself -- one barrier and no
-        // rotation table per round.  Slower: 1.00 -> 1.63 us a round at B = 64.  The round is bound by the instructions the one
-        // compute unit issues, not by its three LDS round trips, and sixteen waves forming rotations redundantly are ~60 more
-        // vector instructions per thread and round.  The table stays.)
-        for (int r = 0; r < B - 1; ++r) {
-            if (tid < NP) {
-                const int s1 = tid, s2 = B - 1 - tid;
-                int a1 = s1 - 1 - r; a1 %= (B - 1); if (a1 < 0) a1 += B - 1;
-                int a2 = s2 - 1 - r; a2 %= (B - 1); if (a2 < 0) a2 += B - 1;
-                const int p = s1 == 0 ? 0 : 1 + a1, q = 1 + a2;
-                const double al = S1[p * LD + p], ga = S1[q * LD + q], be = S1[p * LD + q];
-                double c, s;
-                lead_rotation(al, ga, be, c, s);
-                pwk = __builtin_fma(be, be, pwk);
-                cs[tid] = double2{c, s};
-                pq[tid] = p;
-                pq[NP + tid] = q;
-            }
-            __syncthreads();
-            for (int e = tid; e < NP * NP; e += NT) {
-                const int k = e / NP, l = e % NP;
-                const int pk = pq[k], qk = pq[NP + k], pl = pq[l], ql = pq[NP + l];
-                const double2 rk2 = cs[k], rl = cs[l];
-                const double a = S1[pk * LD + pl], b_ = S1[pk * LD + ql], c_ = S1[qk * LD + pl], d_ = S1[qk * LD + ql];
-                const double a1 = a * rl.x - b_ * rl.y, b1 = a * rl.y + b_ * rl.x;
-                const double c1 = c_ * rl.x - d_ * rl.y, d1 = c_ * rl.y + d_ * rl.x;
-                S1[pk * LD + pl] = rk2.x * a1 - rk2.y * c1;
-                S1[pk * LD + ql] = rk2.x * b1 - rk2.y * d1;
-                S1[qk * LD + pl] = rk2.y * a1 + rk2.x * c1;
-                S1[qk * LD + ql] = rk2.y * b1 + rk2.x * d1;
-            }
-            for (int e = tid; e < B * NP; e += NT) {
-                const int i = e / NP, l = e % NP;
-                const int pl = pq[l], ql = pq[NP + l];
-                const double2 rl = cs[l];
-                const double x = S0[i * LD + pl], y = S0[i * LD + ql];
-                S0[i * LD + pl] = x * rl.x - y * rl.y;
-                S0[i * LD + ql] = x * rl.y + y * rl.x;
-            }
-            __syncthreads();
-        }
-        if (tid < NP) pw[tid] = pwk;
-        __syncthreads();
-        if (tid == 0) {
-            double t = 0.0;
-            for (int k = 0; k < NP; ++k) t += pw[k];
-            scal[0] = t;
-        }
-        __syncthreads();
-        ++sweeps;
-        conv = scal[0] <= tol2 * norm2;         // a sweep whose pivots weigh <= tol2 ||M||^2 leaves ~tol2^2 behind
-        __syncthreads();
-    }
     }
     // f: descending order, T = D W^T Q with its columns in that order
     stamp(4);
@@ -734,22 +643,10 @@ __global__ void __launch_bounds__(NT) lead_small_kernel(int nslab, const double*
     }
     __syncthreads();
     T += (size_t)z * B * B;
-    if constexpr (MOVE) {
-        // the accumulator started as W^T: it holds W^T Q
-        for (int e = tid; e < B * B; e += NT) {
-            const int i = e / B, j = e - i * B;
-            T[(size_t)i * B + rk[j]] = dsc[i] * Qc[i * LD + j];
-        }
-    } else {
-        for (int tile = wv; tile < NTL * NTL; tile += NW) {
-            const int r0 = (tile / NTL) * 16, c0 = (tile % NTL) * 16;
-            const d4 a = lead_tile<true, false, B>(S2, S0, LD, r0, c0, lane);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int i = r0 + (lane >> 4) + 4 * t, j = c0 + (lane & 15);
-                T[(size_t)i * B + rk[j]] = dsc[i] * a[t];
-            }
-        }
+    // the accumulator started as W^T: it holds W^T Q
+    for (int e = tid; e < B * B; e += NT) {
+        const int i = e / B, j = e - i * B;
+        T[(size_t)i * B + rk[j]] = dsc[i] * Qc[i * LD + j];
     }
     if (tid == 0) {
         hinfo[(size_t)z * (B + 4) + B] = 0.0;
@@ -833,19 +730,15 @@ struct LeadWs {
     }
 };
 
-template <int B, int NT, bool MOVE>
+template <int B, int NT>
 hipError_t launch_small(hipStream_t st, int batch, int nslab, const double* Gp, const double* Hp, int max_sweeps, double tol2,
                         double* T, double* theta, double* hinfo, unsigned active, unsigned long long* stamps) {
     constexpr int LD = B + 1, NP = B / 2;
-    const size_t bytes = sizeof(double) * ((MOVE ? 4 : 3) * (size_t)B * LD + 2 * B + NP + (NP & 1)) + sizeof(double2) * NP + sizeof(int) * 2 * B;
-    static bool once = false;
-    if (!once) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lead_small_kernel<B, NT, MOVE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        once = true;
-    }
-    hipLaunchKernelGGL((lead_small_kernel<B, NT, MOVE>), dim3(batch), dim3(NT), bytes, st, nslab, Gp, Hp, max_sweeps, tol2, T, theta, hinfo,
+    const size_t bytes = sizeof(double) * (4 * (size_t)B * LD + 2 * B + NP + (NP & 1)) + sizeof(double2) * NP + sizeof(int) * B;
+    static std::atomic<unsigned long long> attr_set{0};
+    const hipError_t e = apv_set_max_dynamic_lds(reinterpret_cast<const void*>(&lead_small_kernel<B, NT>), (int)bytes, attr_set);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((lead_small_kernel<B, NT>), dim3(batch), dim3(NT), bytes, st, nslab, Gp, Hp, max_sweeps, tol2, T, theta, hinfo,
                        active, stamps);
     return hipGetLastError();
 }
@@ -862,8 +755,7 @@ void apv_gevd_lead_free(apv_handle* h) {
 
 // Block width for `rank` wanted eigenpairs of an order-n problem, 0 when the leading solver does not apply
 int apv_gevd_lead_block(int n, int rank) {
-    static const int off = getenv("APV_LEAD") ? atoi(getenv("APV_LEAD")) == 0 : 0;
-    if (off || rank <= 0) return 0;
+    if (rank <= 0) return 0;
     int b = (rank + 16 + 15) / 16 * 16;
     if (b < 32) b = 32;
     if (b > 64) b = 64;
@@ -915,48 +807,35 @@ int apv_gevd_lead(apv_handle* h, int n, int ne, int batch, int b, int rank, cons
     one.active = active;
     for (int z = 0; z < batch; ++z) { one.a[z] = 1.0; one.b[z] = 0.0; one.g[z] = 0.0; }
     auto mult = [&](const double* A, const double* Yc, const double* Yp, double* Yo, int rows_out, int ldo, size_t os, const LeadCoef& cf) {
-        // 16 x 16 outputs per workgroup while that fills the chip, 16 x 32 beyond
+        // 16 x 32 outputs and four waves per workgroup beyond 2048 workgroups, else 16 x 16 and eight waves splitting K (measured at
+        // n = 800 / 256, whole solver: 4 -> 1.372 / 0.366 ms, 8 -> 1.339 / 0.358, 16 -> 1.421 / 0.396: the product is not bound
+        // by what one wave has in flight)
         const long wgs = (long)nrt * (b / 16) * batch;
-        static const int kForceNB = getenv("APV_LEAD_NB") ? atoi(getenv("APV_LEAD_NB")) : 0;      // tuning aid
-        // waves that split K in a 16 x 16 workgroup (tuning aid; measured at n = 800 / 256, whole solver: 4 -> 1.372 / 0.366 ms, 8 -> 1.339 /
-        // 0.358, 16 -> 1.421 / 0.396: the product is not bound by what one wave has in flight)
-        static const int kWaves = getenv("APV_LEAD_MULT_WAVES") ? atoi(getenv("APV_LEAD_MULT_WAVES")) : 8;
-        if ((kForceNB == 2 || (kForceNB == 0 && wgs > 2048)) && b % 32 == 0)
+        if (wgs > 2048 && b % 32 == 0)
             hipLaunchKernelGGL((lead_mult_kernel<2>), dim3(nrt * (b / 32), 1, batch), dim3(256), 0, st, ne, ne, ms, A, b, ys, Yc, Yp, Yo, rows_out, ldo, os, cf);
-        else if (kWaves == 8)
-            hipLaunchKernelGGL((lead_mult_kernel<1, 8>), dim3(nrt * (b / 16), 1, batch), dim3(512), 0, st, ne, ne, ms, A, b, ys, Yc, Yp, Yo, rows_out, ldo, os, cf);
-        else if (kWaves == 16)
-            hipLaunchKernelGGL((lead_mult_kernel<1, 16>), dim3(nrt * (b / 16), 1, batch), dim3(1024), 0, st, ne, ne, ms, A, b, ys, Yc, Yp, Yo, rows_out, ldo, os, cf);
         else
-            hipLaunchKernelGGL((lead_mult_kernel<1>), dim3(nrt * (b / 16), 1, batch), dim3(256), 0, st, ne, ne, ms, A, b, ys, Yc, Yp, Yo, rows_out, ldo, os, cf);
+            hipLaunchKernelGGL((lead_mult_kernel<1, 8>), dim3(nrt * (b / 16), 1, batch), dim3(512), 0, st, ne, ne, ms, A, b, ys, Yc, Yp, Yo, rows_out, ldo, os, cf);
     };
-    int ic = 0, ix = 1, iy = 2;
     int final_buf[LEAD_MAXB];
     for (int z = 0; z < batch; ++z) final_buf[z] = -1;
-    hipLaunchKernelGGL(lead_init_kernel, dim3((unsigned)((ys + 255) / 256), 1, batch), dim3(256), 0, st, n, ne, b, ws.P[ic], ys);
-    // the first filter from trace and column-sum bounds (lead_bounds_kernel); APV_LEAD_PREFILTER=0: a Rayleigh-Ritz pass on the
-    // random block instead, as until the middle of round 4 (A/B switch)
-    static const bool prefilter = !(getenv("APV_LEAD_PREFILTER") && atoi(getenv("APV_LEAD_PREFILTER")) == 0);
-    int total_mv = 0;
-    if (prefilter) {
-        hipLaunchKernelGGL(lead_colsum_kernel, dim3((n + 255) / 256, LEAD_BCH, batch), dim3(256), 0, st, n, ne, C, ms, ws.Zb);   // Zb is free here
-        hipLaunchKernelGGL(lead_bounds_kernel, dim3(batch), dim3(1024), 0, st, n, ne, C, ms, (const double*)ws.Zb, ws.coefdev);
+    hipLaunchKernelGGL(lead_init_kernel, dim3((unsigned)((ys + 255) / 256), 1, batch), dim3(256), 0, st, n, ne, b, ws.P[0], ys);
+    // the first filter from trace and column-sum bounds (lead_bounds_kernel): P[0] -> P[1] -> P[2]
+    hipLaunchKernelGGL(lead_colsum_kernel, dim3((n + 255) / 256, LEAD_BCH, batch), dim3(256), 0, st, n, ne, C, ms, ws.Zb);   // Zb is free here
+    hipLaunchKernelGGL(lead_bounds_kernel, dim3(batch), dim3(1024), 0, st, n, ne, C, ms, (const double*)ws.Zb, ws.coefdev);
+    {
         LeadCoef d0 = one, d1 = one;
         d0.dev = d1.dev = ws.coefdev;
         d0.dev_step = 0;
         d1.dev_step = 1;
         mult(C, ws.P[0], nullptr, ws.P[1], ne, b, ys, d0);
         mult(C, ws.P[1], ws.P[0], ws.P[2], ne, b, ys, d1);
-        total_mv += 2;
-        ic = 2; ix = 0; iy = 1;
     }
-    static const double kLimitsRR[3] = {1e6, 1e10, 1e12}, kLimitsPF[3] = {1e10, 1e12, 1e12};
-    const double* const kLimits = prefilter ? kLimitsPF : kLimitsRR;
-    // measured (tools/probes/lead_sweeps_probe.sh, profiles/r04/lead_sweeps_probe.txt): one sweep per non-final pass at b = 64
-    // (n = 800: 1.61 ms for seven passes; two sweeps 1.77 for six, three 2.09, four 2.39), two at b = 32 (n = 256: 0.51 ms, the same
-    // with one or three)
-    static const int kSweepsEnv = getenv("APV_LEAD_SWEEPS") ? atoi(getenv("APV_LEAD_SWEEPS")) : 0;     // tuning aid
-    const int kPartialSweeps = kSweepsEnv > 0 ? kSweepsEnv : (b >= 48 ? 1 : 2);
+    int total_mv = 2;
+    int ic = 2, ix = 0, iy = 1;
+    static const double kLimits[3] = {1e10, 1e12, 1e12};
+    // Jacobi sweeps per pass, measured (profiles/r04/lead_sweeps_probe.txt): one at b = 64 (n = 800: 1.61 ms for seven passes; two
+    // sweeps 1.77 for six, three 2.09, four 2.39), two at b = 32 (n = 256: 0.51 ms, the same with one or three)
+    const int kSweeps = b >= 48 ? 1 : 2;
     int pass = 0;
     bool fallback = false;
     for (;; ++pass) {
@@ -971,31 +850,12 @@ int apv_gevd_lead(apv_handle* h, int n, int ne, int batch, int b, int rank, cons
         // have to keep the columns close to Ritz vectors (the filter's amplification then scales columns instead of making them
         // parallel) and sharpen the Ritz values that set the next filter's bounds; an off-diagonal element left in the leading
         // block shows in the residuals and costs another pass.
-        static const int kSweepEvery = getenv("APV_LEAD_SWEEP_EVERY") ? atoi(getenv("APV_LEAD_SWEEP_EVERY")) : 1;      // tuning aid
-        // APV_LEAD_SWEEP_SCHEDULE="a,b,c,...": sweeps of pass 0, 1, 2, ... (the last entry for all later passes); tuning aid
-        static const std::vector<int> kSchedule = [] {
-            std::vector<int> v;
-            if (const char* e = getenv("APV_LEAD_SWEEP_SCHEDULE"))
-                for (const char* q = e; *q;) {
-                    v.push_back(atoi(q));
-                    while (*q && *q != ',') ++q;
-                    if (*q == ',') ++q;
-                }
-            return v;
-        }();
-        int msw = (kSweepEvery > 1 && pass > 1 && pass % kSweepEvery != 0) ? 0 : kPartialSweeps;
-        if (!kSchedule.empty()) msw = kSchedule[pass < (int)kSchedule.size() ? pass : (int)kSchedule.size() - 1];
         double* const hinfo = ws.out + n_part;
-        // sixteen waves for the one workgroup of a matrix and the sweeps in their moving-slot form (lead_small_kernel, e);
-        // APV_LEAD_WIDE=0: 256 / 256 / 512 threads and the in-place sweeps with their pairing table, as in the middle of round 4
-        static const bool kWide = getenv("APV_LEAD_WIDE") == nullptr || atoi(getenv("APV_LEAD_WIDE")) != 0;
         unsigned long long* const stp = dbg2 ? ws.stamps : nullptr;
-        if (b == 32) se = kWide ? launch_small<32, 512, true>(st, batch, nslab, ws.Gp, ws.Hp, msw, 1e-18, ws.T, ws.theta, hinfo, active, stp)
-                                : launch_small<32, 256, false>(st, batch, nslab, ws.Gp, ws.Hp, msw, 1e-18, ws.T, ws.theta, hinfo, active, stp);
-        else if (b == 48) se = kWide ? launch_small<48, 768, true>(st, batch, nslab, ws.Gp, ws.Hp, msw, 1e-18, ws.T, ws.theta, hinfo, active, stp)
-                                     : launch_small<48, 256, false>(st, batch, nslab, ws.Gp, ws.Hp, msw, 1e-18, ws.T, ws.theta, hinfo, active, stp);
-        else se = kWide ? launch_small<64, 1024, true>(st, batch, nslab, ws.Gp, ws.Hp, msw, 1e-18, ws.T, ws.theta, hinfo, active, stp)
-                        : launch_small<64, 512, false>(st, batch, nslab, ws.Gp, ws.Hp, msw, 1e-18, ws.T, ws.theta, hinfo, active, stp);
+        // sixteen waves for the one workgroup of a matrix (lead_small_kernel)
+        if (b == 32) se = launch_small<32, 512>(st, batch, nslab, ws.Gp, ws.Hp, kSweeps, 1e-18, ws.T, ws.theta, hinfo, active, stp);
+        else if (b == 48) se = launch_small<48, 768>(st, batch, nslab, ws.Gp, ws.Hp, kSweeps, 1e-18, ws.T, ws.theta, hinfo, active, stp);
+        else se = launch_small<64, 1024>(st, batch, nslab, ws.Gp, ws.Hp, kSweeps, 1e-18, ws.T, ws.theta, hinfo, active, stp);
         LCHK(se);
         // Ritz vectors into P[ix], the next filter's first step into P[iy]; the residual partials are summed by the host (row tiles in order)
         hipLaunchKernelGGL(lead_rot_kernel, dim3(nrt, b / 16, batch), dim3(256), 0, st, ne, b, ys, ws.P[ic], ws.Zb, ws.T, ws.theta, ws.P[ix],

@@ -451,28 +451,24 @@ static void syrk_plan(int J, int ncols, int* TC, int* nseg) {
     *TC = tc;
 }
 
-static void launch_syrk(hipStream_t st, int n, int J, int L, int M, int S, int off, int skip, int ncols, int njobs,
-                        const SyrkJobs& jobs) {
-    // the displacement form where its LDS fits (both loudspeakers' sequences of all microphones) and a thread has a lag block;
-    // APV_SYRK_MFMA=1: the dense products on the matrix cores, as until round 4 (A/B switch)
-    static const bool dense = getenv("APV_SYRK_MFMA") != nullptr;
-    {
-        const int Sg = S + 8;
-        const size_t lds = sizeof(double) * ((size_t)2 * M * Sg + (size_t)hc_red_len(J) + 2 * (size_t)J);
-        if (!dense && 2 * J - 1 <= HC_TPB && lds <= 158 * 1024 && ncols + J + 2 <= Sg) {
-            static bool once = false;
-            if (!once) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&hankel_corr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
-                once = true;
-            }
-            hipLaunchKernelGGL(hankel_corr_kernel, dim3(L * (L + 1) / 2, 1, njobs), dim3(HC_TPB), lds, st, n, J, L, M, S, off, skip, ncols, Sg, jobs);
-            return;
-        }
+static hipError_t launch_syrk(hipStream_t st, int n, int J, int L, int M, int S, int off, int skip, int ncols, int njobs,
+                              const SyrkJobs& jobs) {
+    // the displacement form where its LDS fits (both loudspeakers' sequences of all microphones) and a thread has a lag block,
+    // else the dense products on the matrix cores
+    const int Sg = S + 8;
+    const size_t lds = sizeof(double) * ((size_t)2 * M * Sg + (size_t)hc_red_len(J) + 2 * (size_t)J);
+    if (2 * J - 1 <= HC_TPB && lds <= 158 * 1024 && ncols + J + 2 <= Sg) {
+        static std::atomic<unsigned long long> attr_set{0};
+        const hipError_t e = apv_set_max_dynamic_lds(reinterpret_cast<const void*>(&hankel_corr_kernel), 158 * 1024, attr_set);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(hankel_corr_kernel, dim3(L * (L + 1) / 2, 1, njobs), dim3(HC_TPB), lds, st, n, J, L, M, S, off, skip, ncols, Sg, jobs);
+        return hipGetLastError();
     }
     int TC, nseg;
     syrk_plan(J, ncols, &TC, &nseg);
     hipLaunchKernelGGL(syrk_hankel_kernel, dim3((n + 31) / 32, (n + 31) / 32, njobs), dim3(256), sizeof(double) * 2 * SY_BUF, st, n, J,
                        L, M, S, off, skip, ncols, TC, nseg, jobs);
+    return hipGetLastError();
 }
 
 // r[rho] = sum_m sum_ncol Y_m[rho][ncol] d_m[toff + ncol]      (apvast.py:340, 356: toff = J; apVast.m:425: J - 1)
@@ -967,7 +963,7 @@ static int bb_front(apv_handle* h, apv_bb* s, const BbHop& q, double* t_stage, h
             jobs.stats[nj] = s->stats[stat_src[i]];
             jobs.R[nj++] = q.Rq[i];
         }
-        launch_syrk(st, n, J, L, M, S, s->stat_off, s->skip, s->ncols, nj, jobs);
+        BCHK(h, launch_syrk(st, n, J, L, M, S, s->stat_off, s->skip, s->ncols, nj, jobs));
     }
     if (runA) hipLaunchKernelGGL(xcorr_hankel_kernel, dim3(n), dim3(256), 0, st, n, J, L, M, S, s->stat_off, s->skip, s->ncols, s->toff, s->stats[0], s->tstats[0], q.r[0]);
     if (runB) hipLaunchKernelGGL(xcorr_hankel_kernel, dim3(n), dim3(256), 0, st, n, J, L, M, S, s->stat_off, s->skip, s->ncols, s->toff, s->stats[3], s->tstats[1], q.r[1]);
@@ -1140,17 +1136,15 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
     // reached ~3 workgroups per compute unit, which left n = 800 at one hop per group: but a round there is its pair-solve chain,
     // not the chip -- tools/probes/large_batch_scaling.py: 7.5 / 4.9 / 4.1 ms per matrix at batch 2 / 4 / 8 -- and the whole
     // signal went 21.2 -> 15.2 / 13.0 / 11.9 ms per hop with groups of 2 / 4 / 8, under the 16.7 ms a hop of audio lasts.)
-    static const int forced = getenv("APV_BB_GROUP") ? atoi(getenv("APV_BB_GROUP")) : 0;       // A/B switch
     const size_t per_hop_bytes = (size_t)19 * nn * sizeof(double) * nz;
     // sixteen while the group stays within 1 GiB (cfg1: 0.78 / 0.68 / 0.61 / 0.62 / 0.61 ms per hop with 8 / 12 / 16 / 24 / 32 hops
     // a group), eight beyond (n = 800: 11.0 ms per hop with eight, 12.0 with sixteen: 3 GB of matrices no longer sit in the
     // Infinity Cache and the batch sweeps until its slowest member is done), fewer only to stay within 8 GiB
     // (round 4: with the leading-eigenpair solver a batch no longer sweeps until its slowest member is done, and sixteen hops a
-    // group are the better choice at n = 800 too: 4.83 ms per hop against 4.98 with eight, tools/probes/bb_group_sweep.sh)
+    // group are the better choice at n = 800 too: 4.83 ms per hop against 4.98 with eight, profiles/r04/bb_group_sweep.txt)
     const bool lead = h->cfg.max_sweeps <= 0 && apv_gevd_lead_block(n, s->max_rank) > 0;
     int G;
-    if (forced > 0) G = forced;
-    else if (16 * per_hop_bytes <= ((size_t)(lead ? 8 : 1) << 30)) G = 16;
+    if (16 * per_hop_bytes <= ((size_t)(lead ? 8 : 1) << 30)) G = 16;
     else {
         G = (int)(((size_t)8 << 30) / per_hop_bytes);
         G = G < 1 ? 1 : (G > 8 ? 8 : G);
@@ -1187,11 +1181,7 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
             // a copy stream of its own only where a group's outputs are large enough for the next group's solve to notice the
             // transfer (84 MB at the reference's test parameters; 131 KB at cfg1: there the copy rides on the handle's stream --
             // every stream fewer is one fewer to share the runtime's few hardware queues with)
-            {
-                static const int own = getenv("APV_BB_COPY_STREAM") ? atoi(getenv("APV_BB_COPY_STREAM")) : -1;      // A/B: 1 always, 0 never
-                const size_t group_bytes = sizeof(double) * (size_t)G * s->n_out * s->H;
-                if (own == 1 || (own != 0 && group_bytes >= ((size_t)4 << 20))) BCHK(h, hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
-            }
+            if (sizeof(double) * (size_t)G * s->n_out * s->H >= ((size_t)4 << 20)) BCHK(h, hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
             BCHK(h, hipStreamCreateWithFlags(&s->front2, hipStreamNonBlocking));
             BCHK(h, hipEventCreateWithFlags(&s->ev_ring, hipEventDisableTiming));
             BCHK(h, hipEventCreateWithFlags(&s->ev_stat, hipEventDisableTiming));
@@ -1224,16 +1214,14 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
     hipStream_t fs = s->front;
     // every exit below drains both streams first: copies into the caller's h_out may be in flight
     hipStream_t cs = s->copy ? s->copy : st;
-    // the statistics of a hop on a stream of their own beside the next hop's K1 / WOLA chain (bb_front); APV_BB_FRONT2=0: one stream
-    static const bool front2 = getenv("APV_BB_FRONT2") == nullptr || atoi(getenv("APV_BB_FRONT2")) != 0;
-    hipStream_t fs2 = front2 ? s->front2 : nullptr;
     // The front stages of group g + 1 (~18 runtime calls a hop) are enqueued by a helper thread while this one solves group g: the
     // solve's passes block the host, and with the statistics on a stream of their own a group is bound by the host's enqueueing,
-    // not by the device any more (0.6 ms of a group's 1.6 at cfg1).  (Tried earlier in the round, when a group was still bound
-    // by its front stages on the device: no gain then.)  APV_BB_FRONT_THREAD=0: enqueue them from this thread, before the solve.
-    static const bool front_threaded = getenv("APV_BB_FRONT_THREAD") == nullptr || atoi(getenv("APV_BB_FRONT_THREAD")) != 0;
+    // not by the device any more (0.6 ms of a group's 1.6 at cfg1).  Only this thread writes the handle's message: the helper's
+    // apv_fail calls write front_err (apv_fail_redirect), an exception becomes APV_ERR_HIP there, and this thread reports either
+    // after the join.
     std::thread front_thr;
     int front_rc = APV_OK;
+    std::string front_err;
     auto drained = [&](int rc) {
         if (front_thr.joinable()) front_thr.join();
         (void)hipStreamSynchronize(fs); (void)hipStreamSynchronize(s->front2); (void)hipStreamSynchronize(st); (void)hipStreamSynchronize(cs);
@@ -1274,11 +1262,13 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
             q.nrm = s->g_nrm + set * z_nrm + (size_t)i * 4;
             q.nrm_dark = s->g_nrm + set * z_nrm + (size_t)G * 4 + (size_t)i * nz;
             q.inspec = s->g_inspec + set * z_insp + (size_t)i * 2 * K * 2;
-            const int rc = bb_front(h, s, q, nullptr, fs, fs2);
+            // the statistics on a stream of their own, beside the next hop's K1 / WOLA chain
+            const int rc = bb_front(h, s, q, nullptr, fs, s->front2);
             if (rc != APV_OK) return drained(rc);
         }
-        if (fs2) BDCHK(h, hipStreamWaitEvent(fs, s->ev_stat, 0));          // the last hop's statistics belong to the group
+        BDCHK(h, hipStreamWaitEvent(fs, s->ev_stat, 0));          // the last hop's statistics belong to the group
         BDCHK(h, hipEventRecord(s->ev_front[set], fs));
+        BDCHK(h, hipGetLastError());                               // the launches of this thread
         return APV_OK;
     };
     std::vector<int32_t> status((size_t)G * nz, 0);
@@ -1296,13 +1286,18 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
         if (g + 1 < n_groups) {
             // group g + 1 fills the other set, which the back half of group g - 1 has read (its event is on the handle's stream)
             if (g >= 1) BDCHK(h, hipStreamWaitEvent(fs, s->ev_back[set ^ 1], 0));
-            if (front_threaded) {
-                front_rc = APV_OK;
-                front_thr = std::thread([&, g] {
-                    (void)hipSetDevice(h->device);
-                    front_rc = enqueue_front(g + 1);
-                });
-            } else if ((rc = enqueue_front(g + 1)) != APV_OK) return drained(rc);
+            front_thr = std::thread([&, g] {
+                apv_fail_redirect(&front_err);
+                try {
+                    const hipError_t e = hipSetDevice(h->device);
+                    front_rc = e != hipSuccess ? apv_fail(h, APV_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e))
+                                               : enqueue_front(g + 1);
+                } catch (...) {                  // (host memory, most likely: no message is built here, that could throw again)
+                    front_rc = APV_ERR_HIP;
+                    front_err.clear();
+                }
+                apv_fail_redirect(nullptr);
+            });
         }
         BDCHK(h, hipStreamWaitEvent(st, s->ev_front[set], 0));
         double t_b = now_ms(), t_b2 = t_b;
@@ -1366,7 +1361,8 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
         if (!direct && g + 1 == n_groups) collect(g);
         if (front_thr.joinable()) {
             front_thr.join();
-            if (front_rc != APV_OK) return drained(front_rc);
+            if (front_rc != APV_OK)
+                return drained(apv_fail(h, front_rc, front_err.empty() ? "exception while enqueueing the next group's front stages" : front_err));
         }
         if (timing) {
             const double t_e = now_ms();
@@ -1501,8 +1497,8 @@ int apv_vast_static(apv_handle* h, int32_t Nb, int32_t Nd, int32_t P, int32_t L,
         SyrkJobs jb{}, jd{};
         jb.stats[0] = dsb; jb.R[0] = dR;
         jd.stats[0] = dsd; jd.R[0] = dR + (size_t)n * n;
-        launch_syrk(st, n, J, L, Nb, S, 0, 0, S - J, 1, jb);
-        launch_syrk(st, n, J, L, Nd, S, 0, 0, S - J, 1, jd);
+        BCHK(h, launch_syrk(st, n, J, L, Nb, S, 0, 0, S - J, 1, jb));
+        BCHK(h, launch_syrk(st, n, J, L, Nd, S, 0, 0, S - J, 1, jd));
     }
     hipLaunchKernelGGL(xcorr_hankel_kernel, dim3(n), dim3(256), 0, st, n, J, L, Nb, S, 0, 0, S - J, J, dsb, dtd, dr);
     // vast.m:71-73 normalises all three by numberOfMics (of the BRIGHT zone) * (rirLength - filterLength)

@@ -174,10 +174,13 @@ def test_broadband_process_signal_vs_reference_and_hop_loop(golden, zones):
             assert np.abs(np.stack(oa[q]) - np.stack(ob[q])).max() <= 1e-10 * np.abs(np.stack(ob[q])).max()
 
 
-@pytest.mark.parametrize("J,S,L,M", [(24, 1664, 3, 2), (5, 700, 4, 3), (40, 300, 2, 2)])
+# (24, 1664, 3, 8): 2 x 8 x 1672 doubles of sequences, 220 416 bytes of LDS with the work array, more than the 158 KiB that
+# hankel_corr_kernel may take: the statistics fall back to syrk_hankel_kernel
+@pytest.mark.parametrize("J,S,L,M", [(24, 1664, 3, 2), (5, 700, 4, 3), (40, 300, 2, 2), (24, 1664, 3, 8)])
 def test_broadband_statistics_shapes(golden, J, S, L, M):
     """Implicit-Hankel statistics (apvast.py:329-364) where a 32-row tile spans several loudspeakers (J not a
-    multiple of 16, J < 16) and the columns take several LDS chunks (long statistics buffers)."""
+    multiple of 16, J < 16), the columns take several LDS chunks (long statistics buffers), and where the displacement
+    form's LDS does not fit (the dense fall-back)."""
     from ap_vast_unofficial_amd.apvast import apvast
     from oracle.broadband import BroadbandOracle
     rirs = golden("rirs_cfg1")

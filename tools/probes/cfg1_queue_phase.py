@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The broadband whole-signal path (cfg1) after n streams were created in the process (see cfg3_queue_phase.py).
-usage: cfg1_queue_phase.py <streams created and destroyed first> [ref]     (APV_BB_FRONT2 / APV_BB_FRONT_THREAD from the environment;
-`ref`: the reference's test parameters, n = 800, instead of cfg1)"""
+usage: cfg1_queue_phase.py <streams created and destroyed first> [ref]     (`ref`: the reference's test parameters, n = 800, instead of
+cfg1)"""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import bench
@@ -12,6 +12,6 @@ for e in engs:
     e.close()
 ref = len(sys.argv) > 2 and sys.argv[2] == "ref"
 a = bench.also_reftest(0) if ref else bench.also_cfg1(0)
-print(json.dumps({"workload": "n800" if ref else "cfg1", "streams_before": n_pre, "front2": os.environ.get("APV_BB_FRONT2", "1"), "thread": os.environ.get("APV_BB_FRONT_THREAD", "1"),
+print(json.dumps({"workload": "n800" if ref else "cfg1", "streams_before": n_pre,
                   "pib": round(a["process_input_buffers"]["ms_per_hop"], 4), "sig": round(a["process_signal"]["ms_per_hop"], 4),
                   "sig_out": round(a["process_signal_out"]["ms_per_hop"], 4)}), flush=True)
