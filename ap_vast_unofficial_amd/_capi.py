@@ -14,6 +14,7 @@ MAX_N = 64
 
 F32, F64 = 0, 1
 REG_ABS, REG_REL = 0, 1
+NORM2_METHODS = {"auto": 0, "one_wg": 1, "grid": 2}    # APV_NORM2_AUTO / _ONE_WG / _GRID
 
 OK = 0
 ERR_ARG, ERR_HIP, ERR_NOT_PD, ERR_NO_CONVERGE, ERR_RCCL, ERR_STATE = -1, -2, -3, -4, -5, -6
@@ -26,7 +27,7 @@ EXPORTS = (
     "apv_create", "apv_destroy", "apv_last_error", "apv_abi_version",
     "apv_dev_alloc", "apv_dev_free", "apv_memcpy_h2d", "apv_memcpy_d2h", "apv_sync",
     "apv_timer_start", "apv_timer_stop",
-    "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128",
+    "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
     "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_get_state", "apv_bb_set_state",
@@ -118,6 +119,7 @@ def load():
     lib.apv_jdiag_large.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     lib.apv_jdiag_leading.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.apv_jdiag_large_c128.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.apv_norm2.argtypes = [vp, i32, i32, vp, vp, i32]
     lib.apv_stft_analysis_dev.argtypes = [vp, i32, vp, vp]
     lib.apv_istft_ola_dev.argtypes = [vp, i32, vp, vp, vp]
     lib.apv_stream_init.argtypes = [vp, i32, vp, vp, i32, i32, i32]
@@ -401,7 +403,7 @@ class Engine:
         return U, lam
 
     def jdiag_large(self, A, B):
-        """Real symmetric pairs of broadband order (n <= 2048): U (batch, n, n), lam (batch, n), float64."""
+        """Real symmetric pairs of broadband order (n <= 4096): U (batch, n, n), lam (batch, n), float64."""
         A = np.ascontiguousarray(A, dtype=np.float64)
         B = np.ascontiguousarray(B, dtype=np.float64)
         if A.ndim != 3 or A.shape != B.shape or A.shape[1] != A.shape[2]:
@@ -426,6 +428,19 @@ class Engine:
         info = np.empty(batch, dtype=np.int32)
         self._chk(self.lib.apv_jdiag_leading(self.h, n, batch, int(rank), _ptr(A), _ptr(B), _ptr(U), _ptr(lam), _ptr(info)))
         return U, lam, info
+
+    def norm2(self, mats, method="auto"):
+        """||M||_2 of symmetric positive semi-definite matrices (count, n, n) float64, n <= 4096, by the Lanczos kernels of the
+        relative loading (apVast.m:552-569): (count,) float64.  method: "auto" (what a hop runs), "one_wg" (one workgroup per
+        matrix) or "grid" (each step's matrix-vector product over the whole chip)."""
+        M = np.ascontiguousarray(mats, dtype=np.float64)
+        if M.ndim != 3 or M.shape[1] != M.shape[2]:
+            raise ValueError("mats must be (count, n, n)")
+        if method not in NORM2_METHODS:
+            raise ValueError(f"method must be one of {sorted(NORM2_METHODS)}")
+        out = np.empty(M.shape[0])
+        self._chk(self.lib.apv_norm2(self.h, M.shape[1], M.shape[0], _ptr(M), _ptr(out), NORM2_METHODS[method]))
+        return out
 
     def jdiag_large_complex(self, A, B):
         """Complex Hermitian pairs of order 65..1024: U (batch, n, n) complex128, lam (batch, n) float64."""

@@ -55,7 +55,7 @@ _jdiag_engine = None
 
 def jdiag(A, B, device=0):
     """Joint diagonalisation on the GPU: (U, D) with U^H (B + reg I) U = I, U^H A U = D, D descending
-    and returned as a diagonal MATRIX, as apvast.py:20-36 does.  Real symmetric pairs up to n = 2048, complex Hermitian
+    and returned as a diagonal MATRIX, as apvast.py:20-36 does.  Real symmetric pairs up to n = 4096, complex Hermitian
     pairs up to n = 1024 (beyond 64 through the real embedding of order 2n, csrc/kernels_jdiag_cplx.hip).
     Raises numpy.linalg.LinAlgError when the loaded B is not positive definite (apvast.py:21)."""
     global _jdiag_engine
@@ -65,8 +65,8 @@ def jdiag(A, B, device=0):
     if A.shape != (n, n) or B.shape != (n, n):
         raise ValueError("jdiag expects two square matrices of equal size")
     cplx = np.iscomplexobj(A) or np.iscomplexobj(B)
-    if n > _capi.MAX_N and n > (1024 if cplx else 2048):
-        raise NotImplementedError("GPU jdiag: complex Hermitian pairs up to n = 1024; real symmetric pairs up to n = 2048")
+    if n > _capi.MAX_N and n > (1024 if cplx else 4096):
+        raise NotImplementedError("GPU jdiag: complex Hermitian pairs up to n = 1024; real symmetric pairs up to n = 4096")
     mode = _capi.REG_ABS if EXPERIMENTAL_REGULARIZATION else _capi.REG_REL
     key = (device, mode)
     if _jdiag_engine is None or _jdiag_engine[0] != key:

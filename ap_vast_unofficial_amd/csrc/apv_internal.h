@@ -171,8 +171,12 @@ bool apv_host_block_contains(const void* p, size_t bytes);
 int apv_gevd_lead(apv_handle* h, int n, int ne, int batch, int b, int rank, const double* C, const double* WT, double* d_U,
                   double* d_lam, const int* h_pd_flags, int* done);
 
-// stream_bb.hip: d_out[i] = ||mats[i]||_2 (largest eigenvalue of a symmetric PSD n x n matrix, Lanczos), i < count <= 4
-hipError_t apv_launch_norm2(int n, int count, const double* const* d_mats, double* d_out, hipStream_t s);
+// stream_bb.hip: d_out[i] = ||mats[i]||_2 (largest eigenvalue of a symmetric PSD n x n matrix, Lanczos), i < count <= 4,
+// n <= APV_NORM2_MAX_N.  method: APV_NORM2_AUTO (the chip-wide steps above APV_NORM2_GRID_MIN_N, else one workgroup per
+// matrix), APV_NORM2_ONE_WG or APV_NORM2_GRID (include/apvast_hip.h).
+constexpr int APV_NORM2_MAX_N = 4096;
+constexpr int APV_NORM2_GRID_MIN_N = 2048;      // the chip-wide path runs from n = 2049
+hipError_t apv_launch_norm2(int n, int count, const double* const* d_mats, double* d_out, hipStream_t s, int method = APV_NORM2_AUTO);
 
 // kernels_corr.hip
 hipError_t apv_launch_corr(int compute_dtype, int K, int M, int L, const float2* XB, const float2* XD,

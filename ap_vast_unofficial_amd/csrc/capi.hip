@@ -658,7 +658,7 @@ int apv_jdiag_batched(apv_handle* h, int32_t n, int32_t batch, const double* h_A
 int apv_jdiag_large(apv_handle* h, int32_t n, int32_t batch, const double* h_A, const double* h_B, double* h_U,
                     double* h_lam, int32_t* h_status) {
     if (!h || !h_A || !h_B || !h_U || !h_lam) return fail(h, APV_ERR_ARG, "null host pointer");
-    if (n < 1 || n > 2048 || batch < 0) return fail(h, APV_ERR_ARG, "apv_jdiag_large: n must be in 1..2048");
+    if (n < 1 || n > 4096 || batch < 0) return fail(h, APV_ERR_ARG, "apv_jdiag_large: n must be in 1..4096");
     if (batch == 0) return APV_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t mat = (size_t)batch * n * n * sizeof(double);
@@ -701,6 +701,50 @@ int apv_jdiag_large(apv_handle* h, int32_t n, int32_t batch, const double* h_A, 
     return APV_OK;
 }
 
+int apv_norm2(apv_handle* h, int32_t n, int32_t count, const double* h_mats, double* h_out, int32_t method) {
+    if (!h || !h_mats || !h_out) return fail(h, APV_ERR_ARG, "null host pointer");
+    if (n < 1 || n > APV_NORM2_MAX_N || count < 0) return fail(h, APV_ERR_ARG, "apv_norm2: n must be in 1..4096");
+    if (method != APV_NORM2_AUTO && method != APV_NORM2_ONE_WG && method != APV_NORM2_GRID)
+        return fail(h, APV_ERR_ARG, "apv_norm2: unknown method");
+    if (count == 0) return APV_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t nn = (size_t)n * n;
+    struct Tmp {
+        double* p[2] = {nullptr, nullptr};
+        ~Tmp() { for (double* q : p) if (q) (void)hipFree(q); }
+    } t;
+    double*& dM = t.p[0]; double*& dn = t.p[1];
+    HIPCHK(h, hipMalloc((void**)&dM, sizeof(double) * nn * count));
+    HIPCHK(h, hipMalloc((void**)&dn, sizeof(double) * count));
+    HIPCHK(h, hipMemcpyAsync(dM, h_mats, sizeof(double) * nn * count, hipMemcpyHostToDevice, h->stream));
+    // APV_BB_TIMING=1: the device time of the norms alone, between two events (profiling aid, as in stream_bb.hip)
+    static const bool timing = getenv("APV_BB_TIMING") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (timing) {
+        HIPCHK(h, hipEventCreate(&ev[0]));
+        HIPCHK(h, hipEventCreate(&ev[1]));
+        HIPCHK(h, hipEventRecord(ev[0], h->stream));
+    }
+    for (int z0 = 0; z0 < count; z0 += 4) {          // four matrices per call, as a hop has them
+        const double* mats[4];
+        const int cnt = count - z0 < 4 ? count - z0 : 4;
+        for (int q = 0; q < cnt; ++q) mats[q] = dM + (size_t)(z0 + q) * nn;
+        HIPCHK(h, apv_launch_norm2(n, cnt, mats, dn + z0, h->stream, method));
+    }
+    if (timing) {
+        float ms = 0.0f;
+        HIPCHK(h, hipEventRecord(ev[1], h->stream));
+        HIPCHK(h, hipEventSynchronize(ev[1]));
+        HIPCHK(h, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        fprintf(stderr, "[apv norm2] n=%d count=%d method=%d: %.3f ms\n", n, count, method, ms);
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+    }
+    HIPCHK(h, hipMemcpyAsync(h_out, dn, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
 // gathers the leading `rank` columns of U [batch][n][n] into [batch][n][rank]
 __global__ void __launch_bounds__(256) lead_cols_kernel(int n, int rank, const double* __restrict__ U, double* __restrict__ out) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -714,7 +758,7 @@ __global__ void __launch_bounds__(256) lead_cols_kernel(int n, int rank, const d
 int apv_jdiag_leading(apv_handle* h, int32_t n, int32_t batch, int32_t rank, const double* h_A, const double* h_B, double* h_U,
                       double* h_lam, int32_t* h_info) {
     if (!h || !h_A || !h_B || !h_U || !h_lam) return fail(h, APV_ERR_ARG, "null host pointer");
-    if (n < 1 || n > 2048 || batch < 0) return fail(h, APV_ERR_ARG, "apv_jdiag_leading: n must be in 1..2048");
+    if (n < 1 || n > 4096 || batch < 0) return fail(h, APV_ERR_ARG, "apv_jdiag_leading: n must be in 1..4096");
     if (rank < 1 || rank > n) return fail(h, APV_ERR_ARG, "apv_jdiag_leading: rank must be in 1..n");
     if (batch == 0) return APV_OK;
     HIPCHK(h, hipSetDevice(h->device));

@@ -614,9 +614,9 @@ __global__ void __launch_bounds__(64) zero_f64_kernel(int count, double* __restr
 // ---- step 4 ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPB) rank_kernel(int n, int ld, const double* __restrict__ C, double* __restrict__ lam,
                                                    int* __restrict__ order, size_t mat_stride, size_t vec_stride) {
-    // the diagonal goes through LDS once (n <= 2048): read from global memory inside the counting loop, every thread walked n
-    // strided words one dependent load after the other (180 us at n = 800)
-    __shared__ double sdiag[2048];
+    // the diagonal goes through LDS once (n <= 4096, 32 KB): read from global memory inside the counting loop, every thread
+    // walked n strided words one dependent load after the other (180 us at n = 800)
+    __shared__ double sdiag[4096];
     C += blockIdx.z * mat_stride;
     lam += blockIdx.z * (size_t)n;              // dense [batch][n]
     order += blockIdx.z * vec_stride;

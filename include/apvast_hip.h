@@ -172,7 +172,7 @@ int  apv_jdiag_batched(apv_handle* h, int32_t n, int32_t batch, const double* h_
                        double* h_U, double* h_lam, int32_t* h_status);
 
 /* The same for REAL symmetric pairs of broadband order (n = filter_length x loudspeakers: 256 at cfg1, 800 with
- * the parameters of make_python_test.m), n <= 2048: A, B, U are [batch][n][n] f64 row-major, lam [batch][n].
+ * the parameters of make_python_test.m, 4000 with those of main.m), n <= 4096: A, B, U are [batch][n][n] f64 row-major, lam [batch][n].
  * Matrices live in HBM; one launch per elimination step and per Jacobi round.   replaces apvast.py:20-36 at
  * the sizes of its call sites apvast.py:380, 382 */
 int  apv_jdiag_large(apv_handle* h, int32_t n, int32_t batch, const double* h_A, const double* h_B,
@@ -192,6 +192,15 @@ int  apv_jdiag_leading(apv_handle* h, int32_t n, int32_t batch, int32_t rank, co
  *                                                         replaces apvast.py:20-36 */
 int  apv_jdiag_large_c128(apv_handle* h, int32_t n, int32_t batch, const void* h_A, const void* h_B,
                           void* h_U, double* h_lam, int32_t* h_status);
+/* h_out[i] = ||M_i||_2 for `count` symmetric positive semi-definite n x n matrices h_mats [count][n][n] f64 (host), n <= 4096:
+ * the largest Ritz value of 96 Lanczos steps, the norm of the relative loading apVast.m:552-569 (apv_bb_set_rank_list) and
+ * of apv_jdiag_* with APV_REG_REL.  method: APV_NORM2_AUTO is what those paths run -- one workgroup per matrix up to
+ * n = 2048, above that every step's matrix-vector product spread over the chip; APV_NORM2_ONE_WG / APV_NORM2_GRID force one
+ * of the two.                                              replaces norm(R) of apVast.m:559-566 */
+#define APV_NORM2_AUTO   0
+#define APV_NORM2_ONE_WG 1
+#define APV_NORM2_GRID   2
+int  apv_norm2(apv_handle* h, int32_t n, int32_t count, const double* h_mats, double* h_out, int32_t method);
 
 /* ---- STFT stages (K2-K4) ------------------------------------------------ */
 /* spectra[c][k] = rfft(window * x[c][:])  for `n_ch` channels of length N (f32 in, c64 out,
@@ -262,7 +271,7 @@ int  apv_bb_set_rank_list(apv_handle* h, int32_t n_ranks, const int32_t* ranks);
 /* One real (J L) x (J L) pair per zone per hop from `statistics_buffer_length` samples, J-tap filters, every rank
  * 1..V (apvast.py:329-422) or the registered rank list.  The handle needs block_size, hop_size, n_srcs, n_mics,
  * n_zones, mu, dialect, reg_mode and reg_dark (reg_mode = APV_REG_ABS: dark + reg_dark I inside the joint
- * diagonalisation, apvast.py:22-24; APV_REG_REL: see above); n_bins / ranks are not used.  J L <= 2048,
+ * diagonalisation, apvast.py:22-24; APV_REG_REL: see above); n_bins / ranks are not used.  J L <= 4096,
  * block_size <= 4096.  A failed factorisation (APV_ERR_NOT_PD) leaves the input/response/statistics buffers
  * advanced by the hop and the output overlap buffers untouched.
  *                                                         replaces apvast.__init__, apvast.py:40-151 */
