@@ -9,8 +9,9 @@ import sys
 import numpy as np
 
 ABI_VERSION = 2
-MAX_RANKS = 64
-MAX_N = 64
+MAX_RANKS = 64        # ranks the config struct carries (longer lists: Engine.set_rank_list / apv_set_rank_list)
+MAX_N = 64            # largest order of apv_jdiag_batched and of the on-chip per-bin kernels
+MAX_SRCS = 128        # largest n_srcs of a handle (orders 65..128: csrc/kernels_gevd128.hip, float64 arithmetic)
 
 F32, F64 = 0, 1
 REG_ABS, REG_REL = 0, 1
@@ -27,7 +28,7 @@ EXPORTS = (
     "apv_create", "apv_destroy", "apv_last_error", "apv_abi_version",
     "apv_dev_alloc", "apv_dev_free", "apv_memcpy_h2d", "apv_memcpy_d2h", "apv_sync",
     "apv_timer_start", "apv_timer_stop",
-    "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
+    "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
     "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_get_state", "apv_bb_set_state",
@@ -136,6 +137,7 @@ def load():
     lib.apv_set_state.argtypes = [vp, C.c_char_p, vp, sz]
     lib.apv_bb_init.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32]
     lib.apv_bb_set_rank_list.argtypes = [vp, i32, vp]
+    lib.apv_set_rank_list.argtypes = [vp, i32, vp]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -212,14 +214,18 @@ class Engine:
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
-        if not 1 <= len(ranks) <= MAX_RANKS:
+        if int(n_srcs) > MAX_N:
+            # orders 65..128: up to n_srcs ranks, the tail beyond the config struct's MAX_RANKS through apv_set_rank_list
+            if not 1 <= len(ranks) <= int(n_srcs):
+                raise ValueError(f"between 1 and n_srcs = {int(n_srcs)} ranks per launch")
+        elif not 1 <= len(ranks) <= MAX_RANKS:
             raise ValueError(f"between 1 and {MAX_RANKS} ranks per launch")
         cfg = Config()
         cfg.abi_version = ABI_VERSION
         cfg.device = device
         cfg.n_bins, cfg.n_srcs, cfg.n_mics = int(n_bins), int(n_srcs), int(n_mics)
-        cfg.n_ranks = len(ranks)
-        for i, v in enumerate(ranks):
+        cfg.n_ranks = min(len(ranks), MAX_RANKS)
+        for i, v in enumerate(ranks[:MAX_RANKS]):
             cfg.ranks[i] = v
         self.f64 = compute_dtype in ("f64", F64, np.float64)
         cfg.compute_dtype = F64 if self.f64 else F32
@@ -246,6 +252,16 @@ class Engine:
         if rc != OK:
             raise ApvError(rc, self.lib.apv_last_error(None).decode())
         self.h = h
+        if len(ranks) > MAX_RANKS:
+            self.set_rank_list(ranks)
+
+    def set_rank_list(self, ranks):
+        """Replace the handle's rank list (ascending, each 1..n_srcs, at most n_srcs of them) before stream_init: the way to
+        more than MAX_RANKS ranks at orders above 64 (apv_set_rank_list)."""
+        r = np.ascontiguousarray(ranks, dtype=np.int32)
+        self._chk(self.lib.apv_set_rank_list(self.h, int(r.size), _ptr(r) if r.size else None))
+        self.nV = int(r.size)
+        self.cfg.n_ranks = min(self.nV, MAX_RANKS)
 
     # -- plumbing -----------------------------------------------------------
     def _chk(self, rc):

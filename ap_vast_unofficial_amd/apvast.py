@@ -20,6 +20,9 @@ What is different (keyword-only, after ``perceptual``)
     ``statistics_buffer_length`` are accepted and stored, not used).  ``dtype="f64"`` (default) runs every stage in
     float64 like the reference's lfilter / rfft / irfft (apvast.py:171-192, 202-203, 461-496); ``"f32"`` runs every
     stage in float32; ``"mixed"`` keeps the float32 FIR / STFT / overlap-add around a float64 joint diagonalisation.
+    Up to 128 loudspeakers: above 64 the per-bin joint diagonalisation runs in float64 whatever ``dtype`` is
+    (csrc/kernels_gevd128.hip), its filters and eigenvalues handed on in the dtype's format (complex64 / float32 for
+    ``"f32"``); every rank 1..V, V <= number_of_srcs, is emitted.
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).

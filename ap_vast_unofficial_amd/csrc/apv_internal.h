@@ -79,6 +79,7 @@ struct apv_handle {
     unsigned long long* d_stamps;   // apv_debug_set_stamps: stage-stamp buffer of the diagnostic kernel instantiation (caller's)
     struct apv_stream* st;   // streaming state (apv_stream_init), owned
     struct apv_bb* bb;       // broadband streaming state (apv_bb_init), owned
+    std::vector<int32_t> rank_list;  // the subband rank list: cfg.ranks, or apv_set_rank_list's (cfg.n_ranks entries, up to n_srcs)
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -141,13 +142,25 @@ inline hipError_t apv_set_max_dynamic_lds(const void* kernel, int bytes, std::at
     return e;
 }
 
-// kernels_gevd.hip
-hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s, std::string* why);
+// kernels_gevd.hip.  Orders 65..128 go to kernels_gevd128.hip; ranks_all: the whole rank list when p.nV > APV_MAX_RANKS (only
+// that kernel reads more than p.ranks), else nullptr
+hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s, std::string* why,
+                           const int32_t* ranks_all = nullptr);
 int apv_gevd_reads_groups(const GevdParams& p, int compute_dtype, bool x_c128);      // bins per group of the spectra layout that launch reads (1: bin-major)
 // HBM scratch the kernel that WILL run needs for K bins of order n (0 for most configurations): the order-64 kernel's slots when
 // it is eligible, the float64 LDS kernel's parked Cholesky factor at orders 33..64 otherwise.  zones: 1 or 2 zone programs.
 size_t apv_gevd_spill_bytes(int n, int K, int compute_dtype, int reg_mode, double reg_bright, double sweep_tol2, int zones);
 bool apv_gevd64_eligible(int n, int reg_mode, double reg_bright, double sweep_tol2);
+
+// kernels_gevd128.hip: orders 65..128 in float64 arithmetic (packed LDS Cholesky, whitening, Householder tridiagonalisation,
+// implicit QL).  Needs p.Lspill with apv_gevd_spill_bytes() bytes: per (zone program, bin) a slot of apv_gevd128_slot_bytes(n).
+// A fused launch first writes R_B, R_D, r into the slots (corr128_kernel).
+hipError_t apv_launch_gevd128(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s, std::string* why,
+                              const int32_t* ranks_all);
+size_t apv_gevd128_slot_bytes(int n);
+// R_B, R_D [K][L][L] and r [K][L] c128 from bin-major c64 (x_c128 = 0) or c128 slabs, L <= 128
+hipError_t apv_launch_corr128(int K, int M, int L, int x_c128, const void* XB, const void* XD, const void* d, double2* RB,
+                              double2* RD, double2* r, hipStream_t s);
 
 // kernels_gevd16m.hip: order-16 fast path (MFMA correlation / whitening / back-transform + register-resident
 // Jacobi); hipErrorNotSupported when the problem does not qualify

@@ -60,7 +60,9 @@ GevdParams apv_base_params(const apv_handle* h) {
     p.M = c.n_mics;
     p.K = c.n_bins;
     p.nV = c.n_ranks;
-    for (int i = 0; i < c.n_ranks; ++i) p.ranks[i] = c.ranks[i];
+    // (lists longer than APV_MAX_RANKS -- orders above 64 only -- reach kernels_gevd128.hip through apv_launch_gevd's ranks_all)
+    const int nr = c.n_ranks < APV_MAX_RANKS ? c.n_ranks : APV_MAX_RANKS;
+    for (int i = 0; i < nr; ++i) p.ranks[i] = h->rank_list.empty() ? c.ranks[i] : h->rank_list[i];
     p.mu = c.mu;
     p.reg_dark = c.reg_dark;
     p.reg_bright = c.reg_bright;
@@ -195,7 +197,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     if (!cfg || !out) return fail(nullptr, APV_ERR_ARG, "null argument");
     *out = nullptr;
     if (cfg->abi_version != APV_ABI_VERSION) return fail(nullptr, APV_ERR_ARG, "ABI version mismatch");
-    if (cfg->n_srcs < 1 || cfg->n_srcs > APV_MAX_N) return fail(nullptr, APV_ERR_ARG, "n_srcs must be in 1..64");
+    if (cfg->n_srcs < 1 || cfg->n_srcs > APV_MAX_SRCS) return fail(nullptr, APV_ERR_ARG, "n_srcs must be in 1..128");
     if (cfg->n_bins < 0 || cfg->n_mics < 1) return fail(nullptr, APV_ERR_ARG, "n_bins/n_mics out of range");
     if (cfg->n_ranks < 1 || cfg->n_ranks > APV_MAX_RANKS) return fail(nullptr, APV_ERR_ARG, "n_ranks must be in 1..64");
     for (int i = 0; i < cfg->n_ranks; ++i) {
@@ -213,6 +215,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     apv_handle* h = new (std::nothrow) apv_handle();
     if (!h) return fail(nullptr, APV_ERR_HIP, "out of host memory");
     h->cfg = *cfg;
+    h->rank_list.assign(cfg->ranks, cfg->ranks + cfg->n_ranks);
     h->device = cfg->device;
     h->stream = nullptr;
     h->ev0 = h->ev1 = nullptr;
@@ -446,7 +449,7 @@ int apv_update_dev(apv_handle* h, const void* d_XB, const void* d_XD, const void
         p.XB = (const float2*)d_XB;
         p.XD = (const float2*)d_XD;
         p.d = (const float2*)d_d;
-        e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why);
+        e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why, h->rank_list.data());
     }
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
@@ -587,9 +590,35 @@ int apv_gevd_vast_dev(apv_handle* h, const void* d_RB, const void* d_RD, const v
     p.lam = d_lam;
     p.status = d_status;
     std::string why;
-    hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, false, h->stream, &why);
+    hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, false, h->stream, &why, h->rank_list.data());
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
+int apv_set_rank_list(apv_handle* h, int32_t n, const int32_t* ranks) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return fail(h, APV_ERR_STATE, "apv_set_rank_list: the stream is initialised (its buffers are sized by the rank count)");
+    const int L = h->cfg.n_srcs;
+    if (n < 1 || n > L || !ranks) return fail(h, APV_ERR_ARG, "rank list: between 1 and n_srcs ranks");
+    for (int i = 0; i < n; ++i) {
+        if (ranks[i] < 1 || ranks[i] > L) return fail(h, APV_ERR_ARG, "rank V out of 1..L");
+        if (i && ranks[i] <= ranks[i - 1]) return fail(h, APV_ERR_ARG, "ranks must be ascending");
+    }
+    if (n > APV_MAX_RANKS && L <= APV_MAX_N) return fail(h, APV_ERR_ARG, "more than 64 ranks need n_srcs > 64");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_sync(h)) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the host-buffer staging is sized by the rank count: reallocated at the next apv_update
+    void** bufs[] = {&h->d_XB, &h->d_XD, &h->d_d, &h->d_w, &h->d_lam, reinterpret_cast<void**>(&h->d_status)};
+    for (void** b : bufs) {
+        if (*b) HIPCHK(h, hipFree(*b));
+        *b = nullptr;
+    }
+    h->rank_list.assign(ranks, ranks + n);
+    h->cfg.n_ranks = n;
+    const int head = n < APV_MAX_RANKS ? n : APV_MAX_RANKS;
+    for (int i = 0; i < APV_MAX_RANKS; ++i) h->cfg.ranks[i] = i < head ? ranks[i] : 0;
     return APV_OK;
 }
 

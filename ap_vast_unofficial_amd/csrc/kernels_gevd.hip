@@ -647,6 +647,7 @@ size_t apv_gevd_spill_bytes(int n, int K, int compute_dtype, int reg_mode, doubl
     // float32 matrix and r (either arithmetic: the fused order-64 update runs that kernel for both); the float64 LDS kernel of
     // orders 33..64 (SPILL instance) parks its Cholesky factor, n x n c128; every other instance keeps everything in LDS.
     const size_t z = zones > 1 ? 2 : 1;
+    if (n > APV_MAX_N) return z * K * apv_gevd128_slot_bytes(n);       // orders 65..128: kernels_gevd128.hip's slots
     if (apv_gevd64_eligible(n, reg_mode, reg_bright, sweep_tol2)) return z * K * apv_gevd64_slot_bytes();
     if (n > 32 && compute_dtype == APV_F64) return z * K * (size_t)n * n * 16;
     return 0;
@@ -663,9 +664,17 @@ int apv_gevd_reads_groups(const GevdParams& p, int compute_dtype, bool x_c128) {
     return ok ? g : 1;
 }
 
-hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s, std::string* why) {
+hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s, std::string* why,
+                           const int32_t* ranks_all) {
     const int n = p.n;
     static const bool force_generic = (getenv("APV_FORCE_GENERIC") != nullptr);
+    if (n > APV_MAX_N) {
+        if (n > APV_MAX_SRCS) {
+            if (why) *why = "GEVD order n out of range (1..128)";
+            return hipErrorInvalidValue;
+        }
+        return apv_launch_gevd128(p, compute_dtype, fused, s, why, ranks_all);
+    }
     if (p.n_hops > 1 && (force_generic || !apv_gevd16m_takes_hops(p, compute_dtype, fused))) {
         if (why) *why = "several hops per launch (n_hops > 1) are taken by the order-16 kernels on fused slabs only";
         return hipErrorInvalidValue;

@@ -417,7 +417,7 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
             p.XB1 = q.X[3]; p.XD1 = q.X[2]; p.d1 = q.tspec[1];
             p.w1 = wz[1]; p.lam1 = lamz[1]; p.status1 = ostatus[1];
         }
-        hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why);
+        hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why, h->rank_list.data());
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
     }
     {
@@ -1441,7 +1441,8 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         XB = dgb;
         XD = dgd;
     }
-    hipError_t e = s->f64 ? apv_launch_corr_c128(K, M, L, (const double2*)XB, (const double2*)XD, (const double2*)s->tspec[zone],
+    hipError_t e = L > APV_MAX_N ? apv_launch_corr128(K, M, L, s->f64, XB, XD, s->tspec[zone], (double2*)dRB, (double2*)dRD, (double2*)dr, st)
+                 : s->f64 ? apv_launch_corr_c128(K, M, L, (const double2*)XB, (const double2*)XD, (const double2*)s->tspec[zone],
                                                  (double2*)dRB, (double2*)dRD, (double2*)dr, st)
                           : apv_launch_corr(APV_F64, K, M, L, (const float2*)XB, (const float2*)XD, (const float2*)s->tspec[zone], dRB, dRD,
                                             dr, st);

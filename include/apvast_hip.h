@@ -49,7 +49,8 @@ extern "C" {
 
 #define APV_ABI_VERSION 2
 #define APV_MAX_RANKS 64     /* number of simultaneously produced ranks V (nV) */
-#define APV_MAX_N 64         /* largest GEVD order n = L handled on-chip */
+#define APV_MAX_N 64         /* largest GEVD order n = L of apv_jdiag_batched and of the per-bin kernels that hold the pair on-chip */
+#define APV_MAX_SRCS 128     /* largest n_srcs of a handle: subband orders 65..128 take the packed float64 kernel (kernels_gevd128.hip) */
 
 /* status codes */
 #define APV_OK 0
@@ -77,10 +78,11 @@ typedef struct apv_config {
     int32_t abi_version;      /* APV_ABI_VERSION */
     int32_t device;           /* HIP device ordinal */
     int32_t n_bins;           /* K  : bins owned by this handle (its shard) */
-    int32_t n_srcs;           /* L  : loudspeakers = GEVD order n (<= APV_MAX_N) */
+    int32_t n_srcs;           /* L  : loudspeakers = GEVD order n (<= APV_MAX_SRCS; above APV_MAX_N the GEVD runs in float64 whatever
+                                 compute_dtype is, outputs in the format out_c128 asks for) */
     int32_t n_mics;           /* M  : control points per zone */
     int32_t n_ranks;          /* nV : how many ranks V are produced (<= APV_MAX_RANKS; the reference emits every rank 1..V, apvast.py:406-422) */
-    int32_t ranks[APV_MAX_RANKS]; /* the V list, each 1..L, ascending */
+    int32_t ranks[APV_MAX_RANKS]; /* the V list, each 1..L, ascending (longer lists: apv_set_rank_list) */
     int32_t compute_dtype;    /* APV_F32 | APV_F64 */
     int32_t out_c128;         /* 0: w c64 / lam f32;  1: w c128 / lam f64 */
     int32_t reg_mode;         /* APV_REG_ABS | APV_REG_REL */
@@ -112,6 +114,12 @@ int  apv_create(const apv_config* cfg, apv_handle** out);     /* replaces: apvas
 int  apv_destroy(apv_handle* h);
 const char* apv_last_error(const apv_handle* h);               /* h may be NULL: last create() error */
 int  apv_abi_version(void);
+
+/* Replace the subband rank list of cfg (n_ranks / ranks) by n ascending ranks in 1..n_srcs, 1 <= n <= n_srcs: the way to ask
+ * for more than APV_MAX_RANKS ranks (the reference emits every rank 1..V, V <= L, apvast.py:152-154).  Output sizes follow
+ * the new count (w is [K][n][L]).  Refused once apv_stream_init has run: the stream's buffers are sized there.
+ *                                                         replaces apvast.py:152-154 */
+int  apv_set_rank_list(apv_handle* h, int32_t n, const int32_t* ranks);
 
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
