@@ -7,10 +7,11 @@ of the hot path (correlate R_B/R_D/r -> joint diagonalisation -> variable-span f
 resident batch of `--blocks` blocks, i.e. blocks*1024 independent bin-updates in one launch.
 Inputs are resident in HBM before the timed region; PCIe is not in `value`.  On the single-GPU path consecutive steps alternate
 between two streams of the engine's (`--update-streams`, apv_set_update_streams: the last waves of one launch finish beside the
-first of the next; same results) and between two filter / status buffers; `roofline` is the kernel ALONE (one-stream leg behind
-the timed region), `roofline.pipelined` the rate of the timed region.
+first of the next; same results) and between two filter / status buffers; `roofline.pipelined` is the rate of the timed region,
+`roofline.kernel_ms` the kernel ALONE (with --full: a one-stream leg behind the timed region).
 
-    python bench.py                      # 1 GPU: cfg2, 32 blocks x 1024 bins resident; also.cfg3, also.cfg5, cpu_baseline
+    python bench.py                      # 1 GPU: cfg2, 32 blocks x 1024 bins resident; the headline alone
+    python bench.py --full               # the same line with the roofline leg, also.* and cpu_baseline (below)
     python bench.py --gpus N             # N GPUs of this node: the program starts its own N ranks (below)
     python bench.py --dump-outputs DIR   # also write the last timed step's filters and status words as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -28,8 +29,10 @@ environment variables set, rendezvous on 127.0.0.1 and a free port), relays rank
 rank fails.  The parent never initialises HIP and nothing is ever re-exec'd.  Nothing here imports torch: the RCCL id
 is exchanged over a TCP hub (ap_vast_unofficial_amd/rendezvous.py) and barriers are one-word RCCL all-reduces.
 
-Rank 0 prints ONE JSON line.  At N = 1 it also carries (every sub-record computed in a child process of its own
-that has ended before this process touches the GPU: the whole-signal paths are sensitive to the streams a process created before):
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, checks the status words of the last ones and prints
+it.  With --full, the line at N = 1 also carries the duration of a launch alone (`roofline.kernel_ms`: the same launches once more
+on one stream, straight behind the timed region) and (every sub-record computed in a child process of its own that
+has ended before this process touches the GPU: the whole-signal paths are sensitive to the streams a process created before):
   also.cfg3   BASELINE config 3 through the drop-in class: 468 hops of 10 s pink noise, 16 x 32, N = 2048, float64, once
               through apvast.process_input_buffers (one call per hop) and once through apvast.process_signal
   also.cfg5   BASELINE config 5 at kernel level: 64 x 128 x 2048 bins in float64, with its own roofline, and
@@ -39,6 +42,7 @@ that has ended before this process touches the GPU: the whole-signal paths are s
   also.cfg1   BASELINE config 1 in the reference's own broadband formulation through the class (per-hop calls and process_signal)
   also.reference_test_parameters   the same at the reference's own test parameters (make_python_test.m: n = 800)
   cpu_baseline  the oracle's per-bin loop on the host cores (one single-threaded process per core)
+--no-also and --no-cpu-baseline leave those parts out of a --full run.
 """
 import argparse
 import json
@@ -749,8 +753,11 @@ def main():
                          "last waves of one launch finish beside the first of the next; 1: every launch on one stream; 0 (default): "
                          "2 on the single-GPU path, 1 on the sharded path (beside an RCCL gather per step the second stream gains "
                          "nothing: profiles/r04/dist_rehearsal_ab.txt)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the cfg3 / cfg5 sub-records of the 1-GPU line")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the one-stream roofline leg, and on the 1-GPU path the also.* sub-records and the "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the also.* sub-records of the 1-GPU line")
     ap.add_argument("--also-only", default=None, choices=ALSO_RECORDS, help="(internal) compute one sub-record and print it")
     ap.add_argument("--also-device", type=int, default=0)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -775,7 +782,7 @@ def main():
     rehearsal = None
     also_pre = {}
     if (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not os.environ.get("APV_BENCH_FORCE_DIST")
-            and not args.no_also):
+            and args.full and not args.no_also):
         try:
             rehearsal = run_cfg4_rehearsal()          # before anything below loads HIP in this process
         except Exception as ex:
@@ -901,21 +908,22 @@ def main():
         else:
             dumped = {"w": last_out[0].download((K, nr, L), np.complex64),
                       "status": (dstatus if (flip[0] - 1) % 2 == 0 else dstatus2).download((K,), np.int32)}
-    # roofline leg of a pipelined run: the duration of a launch ALONE (what rocprofv3's kernel trace calls its duration) cannot be
-    # read off overlapping launches, so the same launches run once more on ONE stream between the same HIP events, straight
-    # behind the timed region (clocks as they are); with --update-streams 1 the timed region itself is that measurement.
+    # roofline leg of a pipelined run (--full): the duration of a launch ALONE (what a profiler's kernel trace calls its duration)
+    # cannot be read off overlapping launches, so the same launches run once more on ONE stream between the same HIP events,
+    # straight behind the timed region (clocks as they are); with --update-streams 1 the timed region itself is that measurement.
     pipelined_ms = None
     if args.update_streams > 1:
-        pipelined_ms = kern_ms
-        eng.set_update_streams(1)
-        n_alone = min(args.steps, 100)
-        for _ in range(8):
-            eng.update_dev(dXB, dXD, dd, dw, None, dstatus)
-        eng.timer_start()
-        for _ in range(n_alone):
-            eng.update_dev(dXB, dXD, dd, dw, None, dstatus)
-        kern_ms = eng.timer_stop() / n_alone
-        eng.sync()
+        pipelined_ms, kern_ms = kern_ms, None
+        if args.full:
+            eng.set_update_streams(1)
+            n_alone = min(args.steps, 100)
+            for _ in range(8):
+                eng.update_dev(dXB, dXD, dd, dw, None, dstatus)
+            eng.timer_start()
+            for _ in range(n_alone):
+                eng.update_dev(dXB, dXD, dd, dw, None, dstatus)
+            kern_ms = eng.timer_stop() / n_alone
+            eng.sync()
     for buf in (dstatus, dstatus2):                # every launch rewrote one of them: the last steps'
         status = buf.download((K,), np.int32)
         if status.any():
@@ -943,9 +951,19 @@ def main():
         updates = args.steps * K * world
         value = updates / elapsed
         bpu = bytes_per_update(len(ranks))
-        achieved = bpu * K / (kern_ms * 1e-3) / 1e9
         traffic = load_traffic("traffic.json", K, args.dtype)
-        alu = (K / (kern_ms * 1e-3)) * FLOP_PER_UPDATE
+        # the figures of a launch alone: None in a plain pipelined run, which has no one-stream leg
+        achieved = alu = None
+        if kern_ms is not None:
+            achieved = bpu * K / (kern_ms * 1e-3) / 1e9
+            alu = (K / (kern_ms * 1e-3)) * FLOP_PER_UPDATE
+        if pipelined_ms is None:
+            kernel_ms_how = "HIP events around the timed launches (one stream)"
+        elif kern_ms is None:
+            kernel_ms_how = "not measured: the one-stream leg behind the timed region runs with --full; `pipelined` is the timed region"
+        else:
+            kernel_ms_how = ("HIP events around launches on ONE stream, same process, straight behind the timed region "
+                             "(a launch alone: the duration a profiler's kernel trace reports for --update-streams 1)")
         out = {
             "metric": "subband filter-updates/sec (blocks x bins / s), 16-spk/32-mic/1024-bin",
             "value": value, "unit": "updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -960,17 +978,15 @@ def main():
                        "launcher": "self (bench.py started its own ranks)" if os.environ.get("APV_BENCH_CHILD") else
                                    ("external (RANK/WORLD_SIZE from the environment)" if world > 1 else "none")},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": achieved * 1e9 / HBM_PEAK, "traffic": traffic,
+                         "frac": None if achieved is None else achieved * 1e9 / HBM_PEAK, "traffic": traffic,
                          "traffic_source": "profiles/traffic.json (rocprofv3 --pmc passes of this command, committed; not re-measured "
                                            "in this run)" if traffic else None,
                          "kernel": "gevd16m_kernel_f64<fused>" if args.dtype == "f64" else "gevd16m_kernel<float, fused>", "kernel_ms": kern_ms,
-                         "kernel_ms_how": ("HIP events around launches on ONE stream, same process, straight behind the timed region "
-                                           "(a launch alone: the duration rocprofv3's kernel trace reports for --update-streams 1)")
-                                          if pipelined_ms is not None else "HIP events around the timed launches (one stream)",
+                         "kernel_ms_how": kernel_ms_how,
                          "algorithmic_bytes_per_update": bpu, "updates_per_launch": K,
-                         "alu": {"flop_per_update": FLOP_PER_UPDATE, "achieved_tflops": alu / 1e12,
+                         "alu": {"flop_per_update": FLOP_PER_UPDATE, "achieved_tflops": None if alu is None else alu / 1e12,
                                  "peak_tflops": PEAK_FLOPS[args.dtype] / 1e12,
-                                 "frac": alu / PEAK_FLOPS[args.dtype],
+                                 "frac": None if alu is None else alu / PEAK_FLOPS[args.dtype],
                                  "note": "the fused kernel is vector-ALU bound (SURVEY.md 8d); both fractions reported"}},
         }
         if pipelined_ms is not None:
@@ -1004,13 +1020,13 @@ def main():
         rz.close()
 
     if rank == 0:
-        if world == 1 and not multi and not args.no_also:
+        if world == 1 and not multi and args.full and not args.no_also:
             also = dict(also_pre)
             also["how"] = "every sub-record in a child process of its own, run before this process touched the GPU (run_also_child)"
             if rehearsal is not None:
                 also["cfg4_rehearsal"] = rehearsal
             out["also"] = also
-        if not args.no_cpu_baseline and world == 1 and not multi:
+        if args.full and not args.no_cpu_baseline and world == 1 and not multi:
             out["cpu_baseline"] = cpu_baseline(ranks, mu)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -583,3 +583,24 @@ def test_bench_distributed_rehearsal_without_torch():
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["config"]["workload"].startswith("cfg4") and line["collective_us"] > 0
     assert line["collective_bytes_per_rank"] == 32 * 4096 * 16 * 8 and line["value"] > 1e6          # 32 blocks of 4096 bins per rank and step
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """bench.py at one GPU: a plain run prints the headline without the sub-records, the CPU baseline or the one-stream roofline
+    leg; --full adds that leg (here without the sub-records and the CPU baseline, which take tens of seconds)."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "APV_BENCH_FORCE_DIST")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--prespin", "0.05"]
+    lines = []
+    for extra in ([], ["--full", "--no-also", "--no-cpu-baseline"]):
+        r = subprocess.run(cmd + extra, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    plain, full = lines
+    for line in lines:
+        assert line["unit"] == "updates/s" and line["value"] > 1e6 and line["steps"] == 4 and line["ms_per_step"] > 0
+        assert line["config"]["update_streams"] == 2 and line["roofline"]["pipelined"]["ms_per_launch"] > 0
+        assert "also" not in line and "cpu_baseline" not in line
+    assert plain["roofline"]["kernel_ms"] is None and plain["roofline"]["alu"]["frac"] is None
+    assert full["roofline"]["kernel_ms"] > 0 and full["roofline"]["alu"]["frac"] > 0
