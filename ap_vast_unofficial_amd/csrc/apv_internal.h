@@ -230,19 +230,10 @@ hipError_t apv_launch_fir_spectra(int f64, int F, int n_ch, const void* x, int P
 hipError_t apv_launch_fir_input_spectra(int f64, int F, const void* x0, const void* x1, int in_len, void* Xf, hipStream_t s);
 hipError_t apv_launch_fir_chunk_spectra(int f64, int F, int P, int H, int n_hops, const void* hist0, const void* hist1,
                                         const void* pin, void* Xf, hipStream_t s);
-// upd != nullptr: the launch also carries the hop's input update (what apv_launch_input_update does), see FirFftJobs
-struct ApvInputUpdate {
-    const void* old_hist[2];
-    void* new_hist[2];
-    const void* xin;      // pinned host [2][H]
-    void* inblk;          // [2][N] rings
-    int pad;
-};
 // n_part > 1: uniformly partitioned (partitions of H taps, F = 2 H): Hf[j] is [n_part][C_j][F/2 + 1], Xf[j] points at the job's
 // signal inside [n_part][2][F/2 + 1]
 hipError_t apv_launch_fir_fft_jobs(int f64, int F, int n_jobs, const void* const* Hf, const void* const* Xf, void* const* resp,
-                                   const int* n_ch, int P, int H, int N, int ring_off, const ApvInputUpdate* upd, hipStream_t s,
-                                   int n_part = 1);
+                                   const int* n_ch, int P, int H, int N, int ring_off, hipStream_t s, int n_part = 1);
 hipError_t apv_launch_fir_input_spectra_parts(int f64, int F, int n_part, const void* x0, const void* x1, void* Xf, hipStream_t s);
 hipError_t apv_launch_fir_spectra_part(int f64, int F, int n_ch, const void* x, long x_stride, int taps, void* Hf, hipStream_t s,
                                        std::string* why);
@@ -262,10 +253,6 @@ hipError_t apv_launch_chunk_inputs(int f64, int P, int H, int N, int nc, int pad
                                    void* const new_hist[2], const void* pin, void* inL, hipStream_t s);
 
 // kernels_stream.hip
-// y = FIR(rir, x) for one hop, appended to the ring response buffers:
-//   resp[c*N + ((N-H+n + ring_off) & (N-1))] = sum_p rir[p*C + c] * xhist[P-1 + n - p],  n < H, c < C
-hipError_t apv_launch_fir_hop(int C, int P, int H, int N, int ring_off, const float* rir, const float* xhist,
-                              float* resp, hipStream_t s);
 struct FirJob { const float* rir; const float* xh; float* resp; int C; };
 struct FirJobs { FirJob j[6]; int n; };
 // all FIR jobs of a hop in one launch, on the matrix cores (v_mfma_f32_32x32x2_f32, implicit Toeplitz operand)

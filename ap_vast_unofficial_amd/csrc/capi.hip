@@ -474,12 +474,10 @@ int apv_set_update_streams(apv_handle* h, int32_t n) {
         // queues and every stream fewer is one fewer to share them with (with the gather's stream the sharded path then has three
         // streams and the lanes work beside the collective; with a control stream of its own they did not: DESIGN.md 4.9).  Waiting for
         // its own events costs the control stream nothing; a join (copies, timers) holds back lane 0's NEXT launch until lane 1's
-        // latest has ended -- once per copy, not per launch.  APV_LANE0_CONTROL=0: a control stream apart from both lanes (A/B switch).
-        static const bool lane0_ctrl = getenv("APV_LANE0_CONTROL") == nullptr || atoi(getenv("APV_LANE0_CONTROL")) != 0;
+        // latest has ended -- once per copy, not per launch.
         for (auto& ln : h->lane) {
-            if (lane0_ctrl && &ln == &h->lane[0]) ln.s = h->stream;
-            else
-            HIPCHK(h, hipStreamCreateWithFlags(&ln.s, hipStreamNonBlocking));
+            if (&ln == &h->lane[0]) ln.s = h->stream;
+            else HIPCHK(h, hipStreamCreateWithFlags(&ln.s, hipStreamNonBlocking));
             HIPCHK(h, hipEventCreateWithFlags(&ln.ev, hipEventDisableTiming));
             HIPCHK(h, hipEventCreateWithFlags(&ln.ev_prev, hipEventDisableTiming));
         }

@@ -657,11 +657,9 @@ size_t apv_gevd_spill_bytes(int n, int K, int compute_dtype, int reg_mode, doubl
 // grouped branch and of the dispatch below)
 int apv_gevd_reads_groups(const GevdParams& p, int compute_dtype, bool x_c128) {
     static const bool force_generic = (getenv("APV_FORCE_GENERIC") != nullptr);
-    static const int env = getenv("APV_SPECTRA_GROUP") ? atoi(getenv("APV_SPECTRA_GROUP")) : 4;      // A/B switch: 1 = bin-major spectra, 4 | 8 bins a group
-    const int g = (env == 4 || env == 8) ? env : 1;
-    const bool ok = g > 1 && !force_generic && p.n == 16 && p.reg_mode == APV_REG_ABS && p.reg_bright == 0.0 && compute_dtype == APV_F64 && x_c128 &&
+    const bool ok = !force_generic && p.n == 16 && p.reg_mode == APV_REG_ABS && p.reg_bright == 0.0 && compute_dtype == APV_F64 && x_c128 &&
            p.debug_stop == 0 && p.stamps == nullptr;
-    return ok ? g : 1;
+    return ok ? 4 : 1;
 }
 
 hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s, std::string* why,

@@ -880,7 +880,7 @@ __global__ void __launch_bounds__(64) gevd16m_kernel_f32_hops_c64(const GevdPara
 bool apv_gevd16m_takes_hops(const GevdParams& p, int compute_dtype, bool fused) {
     if (!(p.n == 16 && p.reg_mode == APV_REG_ABS && p.reg_bright == 0.0 && fused && p.debug_stop == 0 && p.stamps == nullptr && p.n_hops <= 65535))
         return false;
-    if (p.x_c128) return compute_dtype == APV_F64 && (p.x_group <= 1 || p.x_group == 4 || p.x_group == 8);
+    if (p.x_c128) return compute_dtype == APV_F64 && (p.x_group <= 1 || p.x_group == 4);
     return p.x_group <= 1;          // c64 slabs: either arithmetic, bin-major
 }
 
@@ -898,7 +898,6 @@ hipError_t apv_launch_gevd16m(const GevdParams& p, int compute_dtype, bool fused
             return hipGetLastError();
         }
         if (p.x_group == 4) hipLaunchKernelGGL(gevd16m_kernel_f64_hops<4>, grid3, dim3(64), 0, s, p);
-        else if (p.x_group == 8) hipLaunchKernelGGL(gevd16m_kernel_f64_hops<8>, grid3, dim3(64), 0, s, p);
         else hipLaunchKernelGGL(gevd16m_kernel_f64_hops<1>, grid3, dim3(64), 0, s, p);
         return hipGetLastError();
     }
@@ -906,7 +905,6 @@ hipError_t apv_launch_gevd16m(const GevdParams& p, int compute_dtype, bool fused
         // only the float64 product kernel on c128 slabs reads the grouped layout (apv_gevd16m_reads_groups says when)
         if (!xd || compute_dtype != APV_F64 || p.debug_stop != 0 || p.stamps != nullptr) return hipErrorInvalidValue;
         if (p.x_group == 4) hipLaunchKernelGGL(gevd16m_kernel_f64_grouped<4>, grid, dim3(64), 0, s, p);
-        else if (p.x_group == 8) hipLaunchKernelGGL(gevd16m_kernel_f64_grouped<8>, grid, dim3(64), 0, s, p);
         else return hipErrorInvalidValue;
         return hipGetLastError();
     }

@@ -1106,7 +1106,6 @@ bool apv_gevd64_eligible(int n, int reg_mode, double reg_bright, double sweep_to
 // caller-set sweep tolerance): the LDS kernel of kernels_gevd.hip then takes it
 hipError_t apv_launch_gevd64(const GevdParams& p, int compute_dtype, bool fused, hipStream_t s) {
     static const bool off = (getenv("APV_NO_GEVD64") != nullptr);          // A/B switch: the LDS kernel
-    static const bool single = (getenv("APV_GEVD64_SINGLE") != nullptr);   // A/B switch: one bin per workgroup
     // float32 arithmetic asked for at order 64 gets this kernel too when the inputs are the fused slabs: it is 1.4x as fast
     // as the float LDS kernel and more accurate than asked (explicit float32 statistics still go to the LDS kernel)
     if (off || !apv_gevd64_eligible(p.n, p.reg_mode, p.reg_bright, p.sweep_tol2) || (compute_dtype != APV_F64 && !fused) ||
@@ -1117,7 +1116,7 @@ hipError_t apv_launch_gevd64(const GevdParams& p, int compute_dtype, bool fused,
     const bool xd = fused && p.x_c128;
     // one bin per workgroup while that still gives every CU its own workgroup (the two-bin kernel halves the grid), and for the
     // timing aids of the single-bin kernel (debug_stop 6, 7, 8)
-    if (single || p.K * (p.n_zones > 1 ? 2 : 1) < 512 || p.debug_stop >= 6) {
+    if (p.K * (p.n_zones > 1 ? 2 : 1) < 512 || p.debug_stop >= 6) {
         const dim3 grid(p.K, p.n_zones > 1 ? 2 : 1);
         if (xd) hipLaunchKernelGGL((gevd64_kernel<true, double2>), grid, dim3(1024), 0, s, p);
         else if (fused) hipLaunchKernelGGL((gevd64_kernel<true, float2>), grid, dim3(1024), 0, s, p);

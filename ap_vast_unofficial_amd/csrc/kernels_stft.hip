@@ -574,14 +574,6 @@ struct FirFftJobs {
     // partitioned).  One segment: n_part = 1
     int n_part, skip;
     long h_part_stride[FIR_FFT_JOBS], x_part_stride;
-    // optional passenger (whole-signal path, where the hop's input spectra exist before its input update): the input
-    // update of the hop -- new histories [old[H:], hop, zeros(pad)], hop appended to the input-block rings -- done by
-    // upd_wgs extra workgroups per signal at the end of the grid instead of a launch of its own in front of this one
-    int upd_wgs, pad;
-    const T* old_hist[2];
-    T* new_hist[2];
-    const T* xin;                     // pinned host [2][H]
-    T* inblk;                         // [2][N] rings
 };
 
 // blockIdx.y = partition q (one segment: gridDim.y = 1, part_step = 0): its segment starts part_step samples EARLIER in the history
@@ -625,24 +617,13 @@ __global__ void __launch_bounds__(STFT_TPB) fir_chunk_spectra_kernel(FftPlan pla
 // tried for the chunk launches and lost: 430 us against 300 us per chunk of 16 hops at cfg3 -- sixteen waves meeting at the same
 // barriers hide less than eight independent workgroups of four.)
 template <typename T, int MI>
-__global__ void __launch_bounds__(STFT_TPB) fir_fft_kernel(FftPlan plan, FirFftJobs<T> jobs, int P, int H, int N, int ring_off,
-                                                           const C2<T>* __restrict__ tw) {
+__global__ void __launch_bounds__(STFT_TPB) fir_fft_kernel(FftPlan plan, FirFftJobs<T> jobs, int H, const C2<T>* __restrict__ tw) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     using Z = C2<T>;
     Z* za = reinterpret_cast<Z*>(smem_raw);
     const int Fh = plan.Nh;
     Z* zb = za + plan.buf;
     const int wg = blockIdx.x, tid = threadIdx.x;
-    if (wg >= jobs.ch0[jobs.n]) {                                   // the passenger: same work as input_update_kernel
-        const int u = wg - jobs.ch0[jobs.n], g = u / jobs.upd_wgs, i = (u - g * jobs.upd_wgs) * STFT_TPB + tid;
-        const T* x = jobs.xin + (size_t)g * H;
-        const int keep = P - 1;
-        if (i < keep) jobs.new_hist[g][i] = jobs.old_hist[g][i + H];
-        else if (i < keep + H) jobs.new_hist[g][i] = x[i - keep];
-        else if (i < keep + H + jobs.pad) jobs.new_hist[g][i] = (T)0;
-        if (i < H) jobs.inblk[(size_t)g * N + (N - H + i + ring_off) % N] = x[i];
-        return;
-    }
     int j = 0;
     while (j + 1 < jobs.n && wg >= jobs.ch0[j + 1]) ++j;
     const int c = wg - jobs.ch0[j];
@@ -716,8 +697,7 @@ bool make_plan(int N, FftPlan* plan, std::string* why) {
         plan->buf = plan->M;
         factor_stages(plan->M, plan);
     }
-    static const bool pingpong = getenv("APV_FFT_PINGPONG") != nullptr;      // A/B switch: two-buffer stages everywhere
-    plan->inplace = (pingpong && !plan->bluestein) ? 0 : 1;
+    plan->inplace = 1;
     plan->max_it = 1;
     // Timing aids of the probes: they make every transform WRONG.  A stray APV_STFT_DEBUG in somebody's environment must not
     // corrupt a stream silently: the bits are honoured only together with APV_STFT_DEBUG_PROBE=1, which the probe
@@ -739,8 +719,7 @@ bool make_plan(int N, FftPlan* plan, std::string* why) {
         const int it = (plan->buf / r + STFT_TPB - 1) / STFT_TPB;
         if (it > plan->max_it) plan->max_it = it;
     }
-    static const bool mi4 = getenv("APV_FFT_MI4") != nullptr;                // A/B switch: the four-butterfly instantiations everywhere
-    if (!plan->inplace || mi4) plan->max_it = INPLACE_MAX_IT;
+    if (!plan->inplace) plan->max_it = INPLACE_MAX_IT;
     return true;
 }
 
@@ -952,7 +931,7 @@ hipError_t launch_fir_chunk_spectra(int F, int P, int H, int n_hops, const void*
 
 template <typename T>
 hipError_t launch_fir_fft_jobs(int F, int n_jobs, const void* const* Hf, const void* const* Xf, void* const* resp, const int* n_ch,
-                               int P, int H, int N, int ring_off, const ApvInputUpdate* upd, hipStream_t s, int row_stride = 0,
+                               int P, int H, int N, int ring_off, hipStream_t s, int row_stride = 0,
                                int pos0 = 0, long x_hop_stride = 0, int n_hops = 1, int n_part = 1) {
     FftPlan plan;
     if (!make_plan(F, &plan, nullptr) || plan.bluestein || n_jobs < 1 || n_jobs > FIR_FFT_JOBS || n_part < 1) return hipErrorInvalidValue;
@@ -983,7 +962,7 @@ hipError_t launch_fir_fft_jobs(int F, int n_jobs, const void* const* Hf, const v
         jobs.pos0 = pos0;
         jobs.x_hop_stride = x_hop_stride;
         jobs.n_hops = n_hops;
-        if (upd || n_hops < 1 || n_hops > 65535 || pos0 + (long)n_hops * H > row_stride) return hipErrorInvalidValue;
+        if (n_hops < 1 || n_hops > 65535 || pos0 + (long)n_hops * H > row_stride) return hipErrorInvalidValue;
     } else {
         jobs.row_stride = N;
         jobs.pos0 = (N - H + off) % N;
@@ -991,18 +970,7 @@ hipError_t launch_fir_fft_jobs(int F, int n_jobs, const void* const* Hf, const v
         n_hops = 1;
         jobs.n_hops = 1;
     }
-    if (upd) {
-        jobs.upd_wgs = (P - 1 + H + upd->pad + STFT_TPB - 1) / STFT_TPB;
-        jobs.pad = upd->pad;
-        for (int g = 0; g < 2; ++g) {
-            jobs.old_hist[g] = (const T*)upd->old_hist[g];
-            jobs.new_hist[g] = (T*)upd->new_hist[g];
-        }
-        jobs.xin = (const T*)upd->xin;
-        jobs.inblk = (T*)upd->inblk;
-        total += 2 * jobs.upd_wgs;
-    }
-    hipLaunchKernelGGL((plan.max_it == 1 ? fir_fft_kernel<T, 1> : fir_fft_kernel<T, INPLACE_MAX_IT>), dim3(total, n_hops), dim3(STFT_TPB), plan_lds<T>(plan), s, plan, jobs, P, H, N, off, t.tw);
+    hipLaunchKernelGGL((plan.max_it == 1 ? fir_fft_kernel<T, 1> : fir_fft_kernel<T, INPLACE_MAX_IT>), dim3(total, n_hops), dim3(STFT_TPB), plan_lds<T>(plan), s, plan, jobs, H, t.tw);
     return hipGetLastError();
 }
 }  // namespace
@@ -1012,8 +980,8 @@ hipError_t launch_fir_fft_jobs(int F, int n_jobs, const void* const* Hf, const v
 hipError_t apv_launch_fir_fft_chunk(int f64, int F, int n_jobs, const void* const* Hf, const void* const* Xf, long x_hop_stride,
                                     void* const* resp, const int* n_ch, int P, int H, int row_stride, int pos0, int n_hops,
                                     hipStream_t s) {
-    return f64 ? launch_fir_fft_jobs<double>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, row_stride, 0, nullptr, s, row_stride, pos0, x_hop_stride, n_hops)
-               : launch_fir_fft_jobs<float>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, row_stride, 0, nullptr, s, row_stride, pos0, x_hop_stride, n_hops);
+    return f64 ? launch_fir_fft_jobs<double>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, row_stride, 0, s, row_stride, pos0, x_hop_stride, n_hops)
+               : launch_fir_fft_jobs<float>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, row_stride, 0, s, row_stride, pos0, x_hop_stride, n_hops);
 }
 
 // Xf [2][F/2 + 1] = spectra of the two input histories x0, x1 (in_len = P - 1 + H samples each, zero-padded to F)
@@ -1037,7 +1005,7 @@ hipError_t apv_launch_fir_chunk_spectra(int f64, int F, int P, int H, int n_hops
 }
 
 hipError_t apv_launch_fir_fft_jobs(int f64, int F, int n_jobs, const void* const* Hf, const void* const* Xf, void* const* resp,
-                                   const int* n_ch, int P, int H, int N, int ring_off, const ApvInputUpdate* upd, hipStream_t s, int n_part) {
-    return f64 ? launch_fir_fft_jobs<double>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, N, ring_off, upd, s, 0, 0, 0, 1, n_part)
-               : launch_fir_fft_jobs<float>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, N, ring_off, upd, s, 0, 0, 0, 1, n_part);
+                                   const int* n_ch, int P, int H, int N, int ring_off, hipStream_t s, int n_part) {
+    return f64 ? launch_fir_fft_jobs<double>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, N, ring_off, s, 0, 0, 0, 1, n_part)
+               : launch_fir_fft_jobs<float>(F, n_jobs, Hf, Xf, resp, n_ch, P, H, N, ring_off, s, 0, 0, 0, 1, n_part);
 }

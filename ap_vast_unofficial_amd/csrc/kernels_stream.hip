@@ -1,38 +1,10 @@
 // Streaming glue kernels around the per-bin update.
-//   fir_hop_kernel      K1: RIR convolution of one hop to every control point   reference Python/apvast.py:167-194
 //   apply_filters_kernel K3: output spectra = input spectrum x filter spectra    apvast.py:445-452
 #include "apv_internal.h"
 
 #include <algorithm>
 
 namespace {
-
-constexpr int FIR_TN = 32;     // output samples per thread
-
-// One thread = one control-point channel c, FIR_TN consecutive output samples.  The input history is
-// wave-uniform (scalar loads); the taps are read coalesced across channels ([P][C], channel fastest).
-__global__ void __launch_bounds__(64) fir_hop_kernel(int C, int P, int H, int N, int ring_off,
-                                                     const float* __restrict__ rir, const float* __restrict__ xhist,
-                                                     float* __restrict__ resp) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
-    const int n0 = blockIdx.y * FIR_TN;
-    float acc[FIR_TN];
-#pragma unroll
-    for (int t = 0; t < FIR_TN; ++t) acc[t] = 0.f;
-    const bool live = c < C;
-    const float* xs = xhist + (P - 1) + n0;            // xs[t - p] = x[n0 + t - p]
-    for (int p = 0; p < P; ++p) {
-        const float r = live ? rir[(size_t)p * C + c] : 0.f;
-#pragma unroll
-        for (int t = 0; t < FIR_TN; ++t) acc[t] = __builtin_fmaf(r, xs[t - p], acc[t]);
-    }
-    if (live) {
-        float* dst = resp + (size_t)c * N;
-#pragma unroll
-        for (int t = 0; t < FIR_TN; ++t)
-            if (n0 + t < H) dst[(N - H + n0 + t + ring_off) % N] = acc[t];
-    }
-}
 
 // ---- K1 on the matrix cores -------------------------------------------------------------------
 // Y[n][c] = sum_p x[n-p] R[p][c] is the GEMM  T (H x P, Toeplitz, T[n][p] = x[n-p])  times  R (P x C).
@@ -368,14 +340,6 @@ __global__ void __launch_bounds__(256) apply_filters_kernel(int K, ApplyJobs job
 }
 
 }  // namespace
-
-hipError_t apv_launch_fir_hop(int C, int P, int H, int N, int ring_off, const float* rir, const float* xhist,
-                              float* resp, hipStream_t s) {
-    if (C <= 0 || H <= 0) return hipSuccess;
-    dim3 grid((C + 63) / 64, (H + FIR_TN - 1) / FIR_TN);
-    hipLaunchKernelGGL(fir_hop_kernel, grid, dim3(64), 0, s, C, P, H, N, ring_off % N, rir, xhist, resp);
-    return hipGetLastError();
-}
 
 // f64 = 0: c64 bin-major spectra [K][M] -> float weights [K][M]; f64 = 1: c128 spectra -> double weights
 hipError_t apv_launch_perceptual_weights(int f64, int K, int M, int nch, const void* spec, const double* G2, const double* G2T,

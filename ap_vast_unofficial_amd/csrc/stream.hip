@@ -13,8 +13,6 @@
 #include "apv_internal.h"
 
 #include <algorithm>
-#include <chrono>
-#include <functional>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -259,10 +257,8 @@ static HopSpectra hop_spectra(const apv_stream* s, int set) {
 // Front half of a hop on stream `st`: pinned hop `pin_src` [2][H] -> input histories, response rings (K1), analysis
 // spectra of set `set` (K2, perceptual weighting).  Advances (ring_off, cur) on the host.  Pure enqueue: also used
 // under stream capture.
-// `set_free` (whole-signal path): event to wait for before the first kernel that writes the spectra set; `xspec_ready`: the
-// spectra of this hop's input histories, already formed by apv_launch_fir_chunk_spectra.
-static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin_src, hipEvent_t set_free = nullptr,
-                         const void* xspec_ready = nullptr) {
+// `set_free` (whole-signal path): event to wait for before the first kernel that writes the spectra set.
+static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin_src, hipEvent_t set_free = nullptr) {
     apv_stream* s = h->st;
     const HopSpectra q = hop_spectra(s, set);
     const int N = s->N, H = s->H, K = s->K, L = s->L, M = s->M, C = s->C, P = s->P, f64 = s->f64;
@@ -275,32 +271,28 @@ static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin
     s->ring_off = (s->ring_off + H) % N;
     const void* oh[2] = {s->xhist[s->cur][0], s->xhist[s->cur][1]};
     void* nh[2] = {s->xhist[nxt][0], s->xhist[nxt][1]};
-    // with the hop's input spectra in hand (whole-signal path) K1 does not wait for the input update: it rides in K1's launch
-    const bool ride = xspec_ready != nullptr && s->fir_F > 0 && s->fir_np == 1;
     // (the histories keep s->keep samples in front of the hop: P - 1, more when K1 is partitioned)
-    if (!ride) SCHK(h, apv_launch_input_update(f64, s->keep + 1, H, s->pad, N, s->ring_off, oh, nh, pin_src, s->inblk, st));   // histories + input-block rings
+    SCHK(h, apv_launch_input_update(f64, s->keep + 1, H, s->pad, N, s->ring_off, oh, nh, pin_src, s->inblk, st));   // histories + input-block rings
     s->cur = nxt;
     // K1: RIR convolution into the response rings (one MFMA launch for all six filter banks)
     if (s->fir_F > 0) {
         const size_t spec_bytes = ((size_t)s->fir_F / 2 + 1) * 2 * s->esz;
-        const void* const xs = (xspec_ready && s->fir_np == 1) ? xspec_ready : s->xspec;
         if (s->fir_np > 1)
             SCHK(h, apv_launch_fir_input_spectra_parts(f64, s->fir_F, s->fir_np, s->xhist[s->cur][0], s->xhist[s->cur][1], s->xspec, st));
-        else if (!xspec_ready)
+        else
             SCHK(h, apv_launch_fir_input_spectra(f64, s->fir_F, s->xhist[s->cur][0], s->xhist[s->cur][1], P - 1 + H, s->xspec, st));
         const void *jh[6], *jx[6];
         void* jr[6];
         int jc[6];
         for (int p = 0; p < 4; ++p) {
-            jh[p] = s->rirspec[path_zone(p)]; jx[p] = (const char*)xs + spec_bytes * path_sig(p);
+            jh[p] = s->rirspec[path_zone(p)]; jx[p] = (const char*)s->xspec + spec_bytes * path_sig(p);
             jr[p] = s->resp[p]; jc[p] = C;
         }
         for (int z = 0; z < 2; ++z) {
-            jh[4 + z] = s->trirspec[z]; jx[4 + z] = (const char*)xs + spec_bytes * z;
+            jh[4 + z] = s->trirspec[z]; jx[4 + z] = (const char*)s->xspec + spec_bytes * z;
             jr[4 + z] = s->tresp[z]; jc[4 + z] = M;
         }
-        ApvInputUpdate upd{{oh[0], oh[1]}, {nh[0], nh[1]}, pin_src, s->inblk, s->pad};
-        SCHK(h, apv_launch_fir_fft_jobs(f64, s->fir_F, 6, jh, jx, jr, jc, P, H, N, s->ring_off, ride ? &upd : nullptr, st, s->fir_np));
+        SCHK(h, apv_launch_fir_fft_jobs(f64, s->fir_F, 6, jh, jx, jr, jc, P, H, N, s->ring_off, st, s->fir_np));
     } else if (f64) {
         FirJobsD jobs{};
         for (int p = 0; p < 4; ++p) {
@@ -313,23 +305,13 @@ static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin
         }
         SCHK(h, apv_launch_fir_jobs_f64(jobs, 6, P, H, N, s->ring_off, st));
     } else {
-        static const bool valu_fir = (getenv("APV_FIR_VALU") != nullptr);     // A/B switch: direct-form VALU kernel
-        if (valu_fir) {
-            for (int p = 0; p < 4; ++p)
-                SCHK(h, apv_launch_fir_hop(C, P, H, N, s->ring_off, (const float*)s->rir[path_zone(p)],
-                                           (const float*)s->xhist[s->cur][path_sig(p)], (float*)s->resp[p], st));
-            for (int z = 0; z < 2; ++z)
-                SCHK(h, apv_launch_fir_hop(M, P, H, N, s->ring_off, (const float*)s->trir[z], (const float*)s->xhist[s->cur][z],
-                                           (float*)s->tresp[z], st));
-        } else {
-            FirJobs jobs;
-            jobs.n = 6;
-            for (int p = 0; p < 4; ++p)
-                jobs.j[p] = FirJob{(const float*)s->rir[path_zone(p)], (const float*)s->xhist[s->cur][path_sig(p)], (float*)s->resp[p], C};
-            for (int z = 0; z < 2; ++z)
-                jobs.j[4 + z] = FirJob{(const float*)s->trir[z], (const float*)s->xhist[s->cur][z], (float*)s->tresp[z], M};
-            SCHK(h, apv_launch_fir_jobs(jobs, P, H, N, s->ring_off, st));
-        }
+        FirJobs jobs;
+        jobs.n = 6;
+        for (int p = 0; p < 4; ++p)
+            jobs.j[p] = FirJob{(const float*)s->rir[path_zone(p)], (const float*)s->xhist[s->cur][path_sig(p)], (float*)s->resp[p], C};
+        for (int z = 0; z < 2; ++z)
+            jobs.j[4 + z] = FirJob{(const float*)s->trir[z], (const float*)s->xhist[s->cur][z], (float*)s->tresp[z], M};
+        SCHK(h, apv_launch_fir_jobs(jobs, P, H, N, s->ring_off, st));
     }
     // K2: analysis, bin-major output
     const bool runA = s->zones & 1, runB = s->zones & 2;
@@ -536,33 +518,88 @@ static int scan_hop_status(apv_handle* h, const int32_t* stat, long hop) {
     return APV_OK;
 }
 
+// hops [first, first + n) of the caller's signals into pinned staging `pin` [n][2][H], [A | B] per hop, in the front-end precision
+template <typename TI>
+static void stage_hops(const apv_stream* s, const TI* h_in_A, const TI* h_in_B, int first, int n, void* pin) {
+    const int H = s->H;
+    for (int i = 0; i < n; ++i) {
+        const TI* a = h_in_A + (size_t)(first + i) * H;
+        const TI* b = h_in_B + (size_t)(first + i) * H;
+        if (s->f64) {
+            double* pi = (double*)pin + (size_t)i * 2 * H;
+            for (int t = 0; t < H; ++t) { pi[t] = (double)a[t]; pi[H + t] = (double)b[t]; }
+        } else {
+            float* pi = (float*)pin + (size_t)i * 2 * H;
+            for (int t = 0; t < H; ++t) { pi[t] = (float)a[t]; pi[H + t] = (float)b[t]; }
+        }
+    }
+}
+
+// the samples of hop i of n_hops from its result `res` into h_out.  Channel-major: h_out [n_hops][n_out][H].  Sample-major:
+// h_out [n_out / L][n_hops * H][L], i.e. the hop's group g, a contiguous [H][L] block of the result, lands behind the same group of
+// the hop before it (one straight copy per group)
+template <typename TI>
+static void copy_hop_out(const apv_stream* s, const void* res, int n_hops, int i, TI* h_out) {
+    const size_t nout = (size_t)s->n_out * s->H;
+    const size_t ngrp = s->out_group > 0 ? (size_t)s->n_out / s->out_group : 1, gsz = nout / ngrp;
+    for (size_t g = 0; g < ngrp; ++g) {
+        TI* dst = s->out_group > 0 ? h_out + (g * (size_t)n_hops + (size_t)i) * gsz : h_out + (size_t)i * nout;
+        if (s->f64) {
+            const double* po = (const double*)res + g * gsz;
+            if (sizeof(TI) == sizeof(double)) std::memcpy(dst, po, gsz * sizeof(double));
+            else for (size_t j = 0; j < gsz; ++j) dst[j] = (TI)po[j];
+        } else {
+            const float* po = (const float*)res + g * gsz;
+            if (sizeof(TI) == sizeof(float)) std::memcpy(dst, po, gsz * sizeof(float));
+            else for (size_t j = 0; j < gsz; ++j) dst[j] = (TI)po[j];
+        }
+    }
+}
+
 template <typename TI>
 static int process_block_t(apv_handle* h, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
     if (!h || !h_in_A || !h_in_B || !h_out) return apv_fail(h, APV_ERR_ARG, "null argument");
     apv_stream* s = h->st;
     if (!s) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
     SCHK(h, hipSetDevice(h->device));
-    const int H = s->H;
-    const size_t nout = (size_t)s->n_out * H;
-    if (s->f64) {
-        double* pi = (double*)s->pin_in;
-        for (int i = 0; i < H; ++i) { pi[i] = (double)h_in_A[i]; pi[H + i] = (double)h_in_B[i]; }
-    } else {
-        float* pi = (float*)s->pin_in;
-        for (int i = 0; i < H; ++i) { pi[i] = (float)h_in_A[i]; pi[H + i] = (float)h_in_B[i]; }
-    }
+    stage_hops(s, h_in_A, h_in_B, 0, 1, s->pin_in);
     int rc = run_hop(h);
     if (rc != APV_OK) return rc;
-    if (s->f64) {
-        const double* po = (const double*)s->pin_out;
-        if (sizeof(TI) == sizeof(double)) std::memcpy(h_out, po, nout * sizeof(double));
-        else for (size_t i = 0; i < nout; ++i) h_out[i] = (TI)po[i];
-    } else {
-        const float* po = (const float*)s->pin_out;
-        if (sizeof(TI) == sizeof(float)) std::memcpy(h_out, po, nout * sizeof(float));
-        else for (size_t i = 0; i < nout; ++i) h_out[i] = (TI)po[i];
-    }
+    copy_hop_out(s, s->pin_out, 1, 0, h_out);
     return scan_hop_status(h, hop_status_of(s, s->pin_out), s->hop - 1);
+}
+
+// ---- whole-signal path (apv_process_signal) ----
+
+// hops [base, base + nc) of the call: results (pinned `res`, one every hop_result_bytes) into h_out, and their status words scanned.
+// `worst` keeps the first APV_ERR_NO_CONVERGE, overridden by APV_ERR_NOT_PD, and `worst_msg` its message.
+template <typename TI>
+static void collect_hops(apv_handle* h, const char* res, int n_hops, int base, int nc, long hop_first, TI* h_out, int& worst,
+                         std::string& worst_msg) {
+    const apv_stream* s = h->st;
+    for (int i = 0; i < nc; ++i, res += hop_result_bytes(s)) {
+        copy_hop_out(s, res, n_hops, base + i, h_out);
+        const int r = scan_hop_status(h, hop_status_of(s, res), hop_first + base + i);
+        if (r == APV_ERR_NOT_PD && worst != APV_ERR_NOT_PD) { worst = r; worst_msg = h->err; }
+        if (r == APV_ERR_NO_CONVERGE && worst == APV_OK) { worst = r; worst_msg = h->err; }
+    }
+}
+
+// Every failure after the first enqueue leaves through here: the front stream, the `n_back` back streams and the tail stream are
+// drained (kernels may still be reading the pinned staging and writing the result buffers), and the message says how far the call
+// got -- the rings, histories and the hop counter have advanced by the hops ENQUEUED, of which only the hops DELIVERED reached h_out.
+static int signal_bail(apv_handle* h, const hipStream_t* back, int n_back, int n_hops, long hop_first, long delivered, int code,
+                       const std::string& msg) {
+    apv_stream* s = h->st;
+    (void)hipStreamSynchronize(s->front);
+    for (int b = 0; b < n_back; ++b) (void)hipStreamSynchronize(back[b]);
+    (void)hipStreamSynchronize(s->tail);
+    char buf[192];
+    const long enq = s->hop - hop_first;
+    const long deliv = std::min<long>(delivered, enq);
+    std::snprintf(buf, sizeof(buf), " [apv_process_signal: %ld of %d hops delivered, stream state advanced by %ld hops: restore it "
+                  "with apv_set_state or re-initialise before continuing]", deliv, n_hops, enq);
+    return apv_fail(h, code, msg + buf);
 }
 
 // what the whole-signal path needs beyond the per-hop path; allocated at its first call
@@ -587,13 +624,9 @@ static int signal_prepare(apv_handle* h) {
     // -- but with priority streams the rate of the hop-by-hop schedule depends on how many streams the process created before:
     // 0.069 / 0.102 / 0.092 ms per hop at cfg3 after 0 / 3 / 5 earlier streams, against 0.074 / 0.071 / 0.074 at the default
     // priority (profiles/r04/cfg3_front_prio.txt).  The schedule with one joint-diagonalisation launch per chunk measures the same
-    // either way.  APV_CK_FRONT_PRIO=1 asks for the highest priority again: A/B switch.)
-    int prio_least = 0, prio_greatest = 0;
-    SCHK(h, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    static const bool front_high = getenv("APV_CK_FRONT_PRIO") != nullptr && atoi(getenv("APV_CK_FRONT_PRIO")) == 1;
-    if (!front_high) prio_greatest = 0;
-    if (!s->front) SCHK(h, hipStreamCreateWithPriority(&s->front, hipStreamNonBlocking, prio_greatest));
-    if (!s->tail) SCHK(h, hipStreamCreateWithPriority(&s->tail, hipStreamNonBlocking, prio_greatest));
+    // either way.)
+    if (!s->front) SCHK(h, hipStreamCreateWithPriority(&s->front, hipStreamNonBlocking, 0));
+    if (!s->tail) SCHK(h, hipStreamCreateWithPriority(&s->tail, hipStreamNonBlocking, 0));
     for (int p = 0; p < 2; ++p) {
         if (!s->ev_copied[p]) SCHK(h, hipEventCreateWithFlags(&s->ev_copied[p], hipEventDisableTiming));
         if (!s->ev_front[p]) SCHK(h, hipEventCreateWithFlags(&s->ev_front[p], hipEventDisableTiming));
@@ -626,17 +659,15 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     if (!s) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
     if (n_hops < 0) return apv_fail(h, APV_ERR_ARG, "n_hops must be >= 0");
     if (n_hops == 0) return APV_OK;
-    // responses of 64 taps or more (K1 by fast convolution): a chunk of hops per launch, two back streams (below); short
-    // responses, APV_FIR_DIRECT and APV_SIGNAL_PER_HOP (A/B switch) keep the hop-by-hop pipeline of this function
-    static const bool per_hop = getenv("APV_SIGNAL_PER_HOP") != nullptr;
-    if (s->fir_F > 0 && s->fir_np == 1 && !per_hop) return process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    // K1 as one fast-convolution segment (responses of 64 taps or more): a chunk of hops per launch (below); direct-form K1 (shorter
+    // responses, APV_FIR_DIRECT) and partitioned K1 keep the hop-by-hop pipeline of this function
+    if (s->fir_F > 0 && s->fir_np == 1) return process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
     SCHK(h, hipSetDevice(h->device));
     int rc = signal_prepare(h);
     if (rc != APV_OK) return rc;
     const int H = s->H, K = s->K, chunk = s->sig_chunk;
-    const size_t e1 = s->esz, nout = (size_t)s->n_out * H;
+    const size_t e1 = s->esz;
     hipStream_t back = h->stream;
-    auto drain = [&]() { (void)hipStreamSynchronize(s->front); (void)hipStreamSynchronize(back); (void)hipStreamSynchronize(s->tail); };
     int set = 0, last_set = 0;
     bool released[2] = {true, true};                         // nothing reads either set yet
     bool out_idle[2] = {true, true};                         // no copy of either result buffer pending
@@ -645,84 +676,29 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     const int n_chunks = (n_hops + chunk - 1) / chunk;
     const long hop_first = s->hop;
     // chunk c of the signal lives in half c & 1 of the pinned staging
-    auto stage_in = [&](int c) {
-        const int base = c * chunk, nc = std::min(chunk, n_hops - base);
-        for (int i = 0; i < nc; ++i) {
-            const TI* a = h_in_A + (size_t)(base + i) * H;
-            const TI* b = h_in_B + (size_t)(base + i) * H;
-            const size_t slot = ((size_t)(c & 1) * chunk + i) * 2 * H;
-            if (s->f64) {
-                double* pi = (double*)s->sig_in + slot;
-                for (int t = 0; t < H; ++t) { pi[t] = (double)a[t]; pi[H + t] = (double)b[t]; }
-            } else {
-                float* pi = (float*)s->sig_in + slot;
-                for (int t = 0; t < H; ++t) { pi[t] = (float)a[t]; pi[H + t] = (float)b[t]; }
-            }
-        }
-    };
     auto collect = [&](int c) -> int {
         const int base = c * chunk, nc = std::min(chunk, n_hops - base);
         hipError_t e = hipEventSynchronize(s->ev_chunk[c & 1]);
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e));
-        // channel-major: h_out [n_hops][n_out][H].  Sample-major: h_out [n_out / L][n_hops * H][L], i.e. the hop's group g, a
-        // contiguous [H][L] block of the result, lands behind the same group of the hop before it (one straight copy per group)
-        const size_t ngrp = s->out_group > 0 ? (size_t)s->n_out / s->out_group : 1, gsz = nout / ngrp;
-        for (int i = 0; i < nc; ++i) {
-            const char* res = (const char*)s->sig_out + ((size_t)(c & 1) * chunk + i) * hop_result_bytes(s);
-            for (size_t g = 0; g < ngrp; ++g) {
-                TI* dst = s->out_group > 0 ? h_out + (g * (size_t)n_hops + (size_t)(base + i)) * gsz : h_out + (size_t)(base + i) * nout;
-                if (s->f64) {
-                    const double* po = (const double*)res + g * gsz;
-                    if (sizeof(TI) == sizeof(double)) std::memcpy(dst, po, gsz * sizeof(double));
-                    else for (size_t j = 0; j < gsz; ++j) dst[j] = (TI)po[j];
-                } else {
-                    const float* po = (const float*)res + g * gsz;
-                    if (sizeof(TI) == sizeof(float)) std::memcpy(dst, po, gsz * sizeof(float));
-                    else for (size_t j = 0; j < gsz; ++j) dst[j] = (TI)po[j];
-                }
-            }
-            const int r = scan_hop_status(h, hop_status_of(s, res), hop_first + base + i);
-            if (r == APV_ERR_NOT_PD && worst != APV_ERR_NOT_PD) { worst = r; worst_msg = h->err; }
-            if (r == APV_ERR_NO_CONVERGE && worst == APV_OK) { worst = r; worst_msg = h->err; }
-        }
+        collect_hops(h, (const char*)s->sig_out + (size_t)(c & 1) * chunk * hop_result_bytes(s), n_hops, base, nc, hop_first, h_out,
+                     worst, worst_msg);
         return APV_OK;
     };
     int c_done = 0;                                          // chunks collected
-    // Every failure after the first enqueue leaves through here: all three streams are drained (kernels may still be reading the
-    // pinned staging and writing the result buffers), and the message says how far the call got -- the rings, histories and
-    // the hop counter have advanced by the hops ENQUEUED, of which only the hops DELIVERED reached h_out.
     auto bail = [&](int code, const std::string& msg) {
-        drain();
-        char buf[192];
-        const long enq = s->hop - hop_first;
-        const long deliv = std::min<long>((long)c_done * chunk, enq);
-        std::snprintf(buf, sizeof(buf), " [apv_process_signal: %ld of %d hops delivered, stream state advanced by %ld hops: restore it "
-                      "with apv_set_state or re-initialise before continuing]", deliv, n_hops, enq);
-        return apv_fail(h, code, msg + buf);
+        return signal_bail(h, &back, 1, n_hops, hop_first, (long)c_done * chunk, code, msg);
     };
     auto hipbail = [&](hipError_t e) { return bail(APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e)); };
     for (int c = 0; c < n_chunks && worst != APV_ERR_NOT_PD; ++c) {
         const int base = c * chunk, nc = std::min(chunk, n_hops - base);
-        stage_in(c);                                         // this half was collected when chunk c-2's event came in
-        const size_t xs_bytes = s->fir_F > 0 ? ((size_t)s->fir_F / 2 + 1) * 2 * e1 * 2 : 0;      // one hop's two spectra
-        if (s->fir_F > 0 && s->fir_np == 1) {
-            // the input spectra K1 starts from, for every hop of the chunk at once: they depend on the staged samples and on
-            // the histories as the previous chunk left them, on nothing of this chunk's processing
-            hipError_t e = apv_launch_fir_chunk_spectra(s->f64, s->fir_F, s->P, H, nc, s->xhist[s->cur][0], s->xhist[s->cur][1],
-                                                        (const char*)s->sig_in + (size_t)(c & 1) * chunk * 2 * H * e1, s->xspec_chunk,
-                                                        s->front);
-            if (e != hipSuccess) return hipbail(e);
-        }
+        // this half was collected when chunk c-2's event came in
+        stage_hops(s, h_in_A, h_in_B, base, nc, (char*)s->sig_in + (size_t)(c & 1) * chunk * 2 * H * e1);
         for (int i = 0; i < nc; ++i) {
             const size_t slot = (size_t)(c & 1) * chunk + i;
-            hipError_t e = hipSuccess;
-            {
-                // hop h-2 has to be done with this set before the analysis transforms write it
-                rc = enqueue_front(h, s->front, set, (const char*)s->sig_in + slot * 2 * H * e1, released[set] ? nullptr : s->ev_back[set],
-                                   (s->fir_F > 0 && s->fir_np == 1) ? (const char*)s->xspec_chunk + (size_t)i * xs_bytes : nullptr);
-                if (rc != APV_OK) return bail(rc, h->err);
-                e = hipEventRecord(s->ev_front[set], s->front);
-            }
+            // hop h-2 has to be done with this set before the analysis transforms write it
+            rc = enqueue_front(h, s->front, set, (const char*)s->sig_in + slot * 2 * H * e1, released[set] ? nullptr : s->ev_back[set]);
+            if (rc != APV_OK) return bail(rc, h->err);
+            hipError_t e = hipEventRecord(s->ev_front[set], s->front);
             if (e == hipSuccess) e = hipStreamWaitEvent(back, s->ev_front[set], 0);
             // the output buffers follow the set; hop h-2's synthesis and copy have to be through before this hop writes them
             if (e == hipSuccess && !out_idle[set]) e = hipStreamWaitEvent(back, s->ev_copied[set], 0);
@@ -846,31 +822,22 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     int rc = chunk_prepare(h);
     if (rc != APV_OK) return rc;
     const int N = s->N, H = s->H, K = s->K, L = s->L, M = s->M, C = s->C, P = s->P, f64 = s->f64, chunk = s->sig_chunk, RL = s->ck_RL;
-    const size_t e1 = s->esz, e2 = 2 * s->esz, nout = (size_t)s->n_out * H;
+    const size_t e1 = s->esz, e2 = 2 * s->esz;
     const bool runA = s->zones & 1, runB = s->zones & 2;
     // the chunk's joint diagonalisations as one launch where the kernel that will run takes several hops (order 16, absolute loading,
-    // no diagnostics); APV_SIGNAL_BATCHED=0: hop by hop on the back streams, as before (A/B switch)
+    // no diagnostics); elsewhere hop by hop on the back streams
     bool batched = false;
     {
-        static const bool want = getenv("APV_SIGNAL_BATCHED") == nullptr || atoi(getenv("APV_SIGNAL_BATCHED")) != 0;
         GevdParams probe = apv_base_params(h);
         probe.x_c128 = f64;
         probe.x_group = s->xg;
         probe.n_hops = 2;
         static const bool force_generic = getenv("APV_FORCE_GENERIC") != nullptr;
-        batched = want && !force_generic && apv_gevd16m_takes_hops(probe, h->cfg.compute_dtype, true);
+        batched = !force_generic && apv_gevd16m_takes_hops(probe, h->cfg.compute_dtype, true);
     }
-    if (!batched) {
-        // experiment (APV_CK_BACK_PRIO): -1 lowest stream priority, 1 highest, else the default
-        static const int want = getenv("APV_CK_BACK_PRIO") ? atoi(getenv("APV_CK_BACK_PRIO")) : 0;
-        int lo = 0, hi = 0;
-        SCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        for (int b = 0; b + 1 < CK_NB; ++b) {
-            if (s->ck_back[b]) continue;
-            if (want == 0) SCHK(h, hipStreamCreateWithFlags(&s->ck_back[b], hipStreamNonBlocking));
-            else SCHK(h, hipStreamCreateWithPriority(&s->ck_back[b], hipStreamNonBlocking, want < 0 ? lo : hi));
-        }
-    }
+    if (!batched)
+        for (int b = 0; b + 1 < CK_NB; ++b)
+            if (!s->ck_back[b]) SCHK(h, hipStreamCreateWithFlags(&s->ck_back[b], hipStreamNonBlocking));
     hipStream_t bs[CK_NB];
     void* wset[CK_NB][2];
     void* lset[CK_NB][2];
@@ -881,74 +848,24 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             lset[b][z] = b ? s->ck_lam[b - 1][z] : s->lam[z];
         }
     }
-    auto drain = [&]() {
-        (void)hipStreamSynchronize(s->front);
-        for (int b = 0; b < CK_NB; ++b) (void)hipStreamSynchronize(bs[b]);
-        (void)hipStreamSynchronize(s->tail);
-    };
     const int n_chunks = (n_hops + chunk - 1) / chunk;
     const long hop_first = s->hop;
     const int ring_first = s->ring_off, cur_first = s->cur;
-    static const bool timing = getenv("APV_SIGNAL_TIMING") != nullptr;      // host-side seconds per phase, to stderr
-    double t_stage = 0, t_enq = 0, t_wait = 0, t_copy = 0;
-    std::vector<hipEvent_t> tev;                             // timing aid: [chunk][front start, front end, back0 start, back end 0, back end 1, copied]
-    auto tmark = [&](hipStream_t st) { if (timing) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, st); tev.push_back(e); } };
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     int worst = APV_OK;
     std::string worst_msg;
     int c_done = 0;
     auto bail = [&](int code, const std::string& msg) {
-        drain();
-        char buf[192];
-        const long enq = s->hop - hop_first;
-        const long deliv = std::min<long>((long)c_done * chunk, enq);
-        std::snprintf(buf, sizeof(buf), " [apv_process_signal: %ld of %d hops delivered, stream state advanced by %ld hops: restore it "
-                      "with apv_set_state or re-initialise before continuing]", deliv, n_hops, enq);
-        return apv_fail(h, code, msg + buf);
+        return signal_bail(h, bs, CK_NB, n_hops, hop_first, (long)c_done * chunk, code, msg);
     };
     auto hipbail = [&](hipError_t e) { return bail(APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e)); };
 #define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) return hipbail(_e); } while (0)
-    auto stage_in = [&](int c) {
-        const int base = c * chunk, nc = std::min(chunk, n_hops - base);
-        for (int i = 0; i < nc; ++i) {
-            const TI* a = h_in_A + (size_t)(base + i) * H;
-            const TI* b = h_in_B + (size_t)(base + i) * H;
-            const size_t slot = ((size_t)(c % CK_NS) * chunk + i) * 2 * H;
-            if (s->f64) {
-                double* pi = (double*)s->ck_pin_in + slot;
-                for (int t = 0; t < H; ++t) { pi[t] = (double)a[t]; pi[H + t] = (double)b[t]; }
-            } else {
-                float* pi = (float*)s->ck_pin_in + slot;
-                for (int t = 0; t < H; ++t) { pi[t] = (float)a[t]; pi[H + t] = (float)b[t]; }
-            }
-        }
-    };
+    // staging slot c mod 3 holds chunk c
     auto collect = [&](int c) -> int {
         const int base = c * chunk, nc = std::min(chunk, n_hops - base);
-        double tc0 = now();
         hipError_t e = hipEventSynchronize(s->ck_done[c % CK_NS]);
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e));
-        t_wait += now() - tc0; tc0 = now();
-        struct Acc { double& t; double t0; std::function<double()> f; ~Acc() { t += f() - t0; } } acc{t_copy, tc0, now};
-        const size_t ngrp = s->out_group > 0 ? (size_t)s->n_out / s->out_group : 1, gsz = nout / ngrp;
-        for (int i = 0; i < nc; ++i) {
-            const char* res = (const char*)s->ck_pin_out + ((size_t)(c % CK_NS) * chunk + i) * hop_result_bytes(s);
-            for (size_t g = 0; g < ngrp; ++g) {
-                TI* dst = s->out_group > 0 ? h_out + (g * (size_t)n_hops + (size_t)(base + i)) * gsz : h_out + (size_t)(base + i) * nout;
-                if (s->f64) {
-                    const double* po = (const double*)res + g * gsz;
-                    if (sizeof(TI) == sizeof(double)) std::memcpy(dst, po, gsz * sizeof(double));
-                    else for (size_t j = 0; j < gsz; ++j) dst[j] = (TI)po[j];
-                } else {
-                    const float* po = (const float*)res + g * gsz;
-                    if (sizeof(TI) == sizeof(float)) std::memcpy(dst, po, gsz * sizeof(float));
-                    else for (size_t j = 0; j < gsz; ++j) dst[j] = (TI)po[j];
-                }
-            }
-            const int r = scan_hop_status(h, hop_status_of(s, res), hop_first + base + i);
-            if (r == APV_ERR_NOT_PD && worst != APV_ERR_NOT_PD) { worst = r; worst_msg = h->err; }
-            if (r == APV_ERR_NO_CONVERGE && worst == APV_OK) { worst = r; worst_msg = h->err; }
-        }
+        collect_hops(h, (const char*)s->ck_pin_out + (size_t)(c % CK_NS) * chunk * hop_result_bytes(s), n_hops, base, nc, hop_first,
+                     h_out, worst, worst_msg);
         return APV_OK;
     };
     // the spectra set of hop i of a chunk of parity par
@@ -965,15 +882,12 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     std::string why;
     for (int c = 0; c < n_chunks && worst != APV_ERR_NOT_PD; ++c) {
         const int base = c * chunk, nc = std::min(chunk, n_hops - base), par = c & 1;
-        double t0 = now();
-        stage_in(c);                                         // staging slot c mod 3: chunk c - 3 was collected an iteration ago
-        t_stage += now() - t0; t0 = now();
-        const char* pin = (const char*)s->ck_pin_in + (size_t)(c % CK_NS) * chunk * 2 * H * e1;
+        char* const pin = (char*)s->ck_pin_in + (size_t)(c % CK_NS) * chunk * 2 * H * e1;
+        stage_hops(s, h_in_A, h_in_B, base, nc, pin);        // staging slot c mod 3: chunk c - 3 was collected an iteration ago
         // ---------------- front half of the whole chunk ----------------
         // the spectra sets and linear buffers of this parity were last read by the back halves of chunk c - 2
         if (c >= 2)
             for (int b = 0; b < CK_NB; ++b) CK(hipStreamWaitEvent(s->front, s->ck_backdone[par][b], 0));
-        tmark(s->front);
         CK(apv_launch_fir_chunk_spectra(f64, s->fir_F, P, H, nc, s->xhist[s->cur][0], s->xhist[s->cur][1], pin, s->xspec_chunk, s->front));
         // heads of the linear buffers: the newest N - H samples before the chunk, from the rings (first chunk) or from the tail
         // of the previous chunk's buffers
@@ -1041,7 +955,6 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             }
         }
         CK(hipEventRecord(s->ev_front[par], s->front));
-        tmark(s->front);
         // ---------------- back halves ----------------
         // (a) the joint diagonalisations of the whole chunk as ONE launch (blockIdx.z = hop), then output spectra and synthesis hop
         //     by hop.  A hop's 2050 waves are two per SIMD, all head and tail; every input of the sixteen exists once
@@ -1050,8 +963,6 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             hipStream_t b0 = bs[0];
             CK(hipStreamWaitEvent(b0, s->ev_front[par], 0));
             if (c >= 2) CK(hipStreamWaitEvent(b0, s->ck_done[(c - 2) % CK_NS], 0));        // the result slots of this parity are free
-            tmark(b0);
-            static const bool no_yield = getenv("APV_SIGNAL_NO_YIELD") != nullptr;       // A/B switch
             const size_t hop_w = (size_t)K * s->nV * L * wsz(h), hop_lam = (size_t)K * L * lsz(h);
             {
                 GevdParams p = apv_base_params(h);
@@ -1068,7 +979,7 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
                 p.lam = s->ck_lamall[first];
                 p.status = st0 + (size_t)first * K;
                 p.n_zones = (runA && runB) ? 2 : 1;
-                p.yield_issue = no_yield ? 0 : 1;
+                p.yield_issue = 1;
                 if (p.n_zones == 2) {
                     p.XB1 = q0.X[3]; p.XD1 = q0.X[2]; p.d1 = q0.tspec[1];
                     p.w1 = s->ck_wall[1]; p.lam1 = s->ck_lamall[1]; p.status1 = st0 + K;
@@ -1096,11 +1007,9 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
                 rc = enqueue_back(h, b0, set_of(par, i), wz, lz, nullptr, sch);
                 if (rc != APV_OK) return bail(rc, h->err);
                 if (i + 1 == nc) CK(hipEventRecord(s->ck_backdone[par][0], b0));
-                if (i + 2 >= nc && nc >= 2) tmark(b0);
                 last_par = par; last_nc = nc; last_b = 0;
                 s->hop++;
             }
-            if (nc < 2) { tmark(b0); tmark(b0); }          // (the schedule print expects six marks per chunk)
         }
         // (b) hop by hop, alternating between the back streams (configurations the batched launch does not take)
         for (int i = 0; i < nc && !batched; ++i) {
@@ -1111,7 +1020,6 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
                 // chunks behind)
                 if (c >= 2) CK(hipStreamWaitEvent(bs[b], s->ck_done[(c - 2) % CK_NS], 0));
             }
-            if (i == 0) tmark(bs[b]);
             // Every hop of the two chunks in flight has result and output-spectra slots of its own, so a back stream never waits
             // for the tail stream inside a chunk: its next diagonalisation follows the previous one directly.
             const size_t slot = (size_t)par * chunk + i;
@@ -1121,13 +1029,11 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             sch.result = (char*)s->ck_out + slot * hop_result_bytes(s);
             sch.ospec = (char*)s->ck_ospec + slot * (size_t)s->n_out * K * e2;
             sch.no_copy = true;
-            static const bool no_yield = getenv("APV_SIGNAL_NO_YIELD") != nullptr;       // A/B switch
-            sch.yield_issue = no_yield ? 0 : 1;
+            sch.yield_issue = 1;
             sch.lspill = b > 0 ? s->ck_spill[b - 1] : nullptr;
             rc = enqueue_back(h, bs[b], set_of(par, i), wset[b], lset[b], nullptr, sch);
             if (rc != APV_OK) return bail(rc, h->err);
             if (i + CK_NB >= nc) CK(hipEventRecord(s->ck_backdone[par][b], bs[b]));   // this stream's last hop of the chunk
-            if (i + 2 >= nc && nc >= 2) tmark(bs[b]);
             last_par = par; last_nc = nc; last_b = b;
             s->hop++;
         }
@@ -1136,8 +1042,6 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
                           (char*)s->ck_out + (size_t)par * chunk * hop_result_bytes(s), (size_t)nc * hop_result_bytes(s),
                           hipMemcpyDeviceToHost, s->tail));
         CK(hipEventRecord(s->ck_done[c % CK_NS], s->tail)); // every front and back half of the chunk is upstream of this copy
-        tmark(s->tail);
-        t_enq += now() - t0;
         // the host collects TWO chunks behind: while it waits for chunk c - 2 and copies it out, chunks c - 1 and c are queued on
         // the device, so the front half of chunk c runs beside the back halves of chunk c - 1 whatever the host is doing
         if (c > 1) {
@@ -1194,19 +1098,6 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
         CK(hipStreamSynchronize(st));
     }
 #undef CK
-    if (timing && tev.size() >= 6) {
-        fprintf(stderr, "[apv signal] device schedule, ms from the first chunk's front start: chunk | front start - end | back start - end of two of its streams | copied\n");
-        for (size_t c = 0; c + 1 <= tev.size() / 6; ++c) {
-            float v[6];
-            for (int q = 0; q < 6; ++q) (void)hipEventElapsedTime(&v[q], tev[0], tev[6 * c + q]);
-            if (c < 3 || c + 3 >= tev.size() / 6)
-                fprintf(stderr, "[apv signal]   %2zu | %7.3f - %7.3f | %7.3f - %7.3f, %7.3f | %7.3f\n", c, v[0], v[1], v[2], v[3], v[4], v[5]);
-        }
-    }
-    for (hipEvent_t e : tev) (void)hipEventDestroy(e);
-    if (timing)
-        fprintf(stderr, "[apv signal] %d hops: host stage-in %.3f ms, enqueue %.3f ms, waiting for chunks %.3f ms, copy-out %.3f ms\n", n_hops,
-                t_stage * 1e3, t_enq * 1e3, t_wait * 1e3, t_copy * 1e3);
     if (worst == APV_ERR_NOT_PD) return bail(worst, worst_msg);     // the hops behind the failing one were not run
     if (worst != APV_OK) return apv_fail(h, worst, worst_msg);      // APV_ERR_NO_CONVERGE: every hop ran, every output is written
     return APV_OK;

@@ -124,10 +124,10 @@ _SIGNAL = """
 import sys, numpy as np
 sys.path.insert(0, %r)
 from ap_vast_unofficial_amd.apvast import apvast
-dtype = %r
+dtype, L = %r, %d
 rng = np.random.default_rng(5)
 env = np.exp(-np.arange(200) / (200 / 6.0))[:, None, None]
-rirA, rirB = (rng.standard_normal((200, 16, 32)) * env * 1e-3 for _ in range(2))
+rirA, rirB = (rng.standard_normal((200, 16, 32))[:, :L] * env * 1e-3 for _ in range(2))
 N, H, n_hops = 1020, 510, 19
 mk = lambda: apvast(N, rirA, rirB, 16, 5, 1, 2, 2, 1.0, 4 * N, hop_size=H, seed=3, dtype=dtype, perceptual=False)
 a, b = mk(), mk()
@@ -150,9 +150,11 @@ print("SIGNAL_OK")
 @pytest.mark.parametrize("dtype", ["f64", "mixed"])
 def test_process_signal_equals_hop_loop_1020(dtype, batched):
     """The whole-signal path (chunked analyses, chunk-wide K1 spectra, batched or per-hop diagonalisations) returns the hop
-    loop's samples bit for bit at N = 1020.  The switch is read once per process, so each case runs in a child process."""
-    env = dict(os.environ, APV_SIGNAL_BATCHED=batched)
-    r = subprocess.run([sys.executable, "-c", _SIGNAL % (ROOT, dtype)], env=env, capture_output=True, text=True, timeout=600)
+    loop's samples bit for bit at N = 1020.  batched = "1": 16 loudspeakers, the chunk's joint diagonalisations in one launch;
+    "0": the same responses cut to 8 loudspeakers, an order the batched launch does not take, hop by hop on the back streams.
+    Each case runs in a child process."""
+    L = 16 if batched == "1" else 8
+    r = subprocess.run([sys.executable, "-c", _SIGNAL % (ROOT, dtype, L)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "SIGNAL_OK" in r.stdout, r.stdout + r.stderr
 
 

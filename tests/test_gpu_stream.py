@@ -429,11 +429,12 @@ def test_process_signal_equals_hop_loop_orders_33_to_64(dtype, L):
                                                             ("f32", True, False, False, 70), ("f64", False, True, True, 70),
                                                             ("f64", True, True, False, 20), ("f32", True, True, False, 20)])
 def test_process_signal_equals_hop_loop(dtype, run_A, run_B, perceptual, P):
-    """process_signal pipelines consecutive hops on three streams over two sets of spectra; per hop the kernels and
-    their operands are those of process_input_buffers, so every sample, filter and state array must come out bit
-    for bit: across chunk boundaries (16 hops per half of the pinned staging), ending on either set, and mixed with per-hop
-    calls before and after.  P = 70: K1 by fast convolution (input spectra per chunk, input update inside K1's launch on
-    the whole-signal path); P = 20: K1 in its direct form on the matrix cores."""
+    """process_signal against the hop loop: per hop the kernels and their operands are those of process_input_buffers,
+    so every sample, filter and state array must come out bit for bit: across chunk boundaries (16 hops per chunk of the
+    pinned staging), ending on either set, and mixed with per-hop calls before and after.  P = 70: K1 by fast convolution
+    in one segment, so the chunked driver runs (input spectra, K1 and analysis transforms of a chunk of hops in one launch
+    each); P = 20: K1 in its direct form on the matrix cores, consecutive hops pipelined on three streams over two sets
+    of spectra."""
     from ap_vast_unofficial_amd.apvast import apvast
     rirA, rirB = synth_rirs(P, 4, 8, 11)
     N, H = 128, 64
