@@ -30,8 +30,8 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_state_bytes", "apv_get_state", "apv_set_state",
-    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_get_state", "apv_bb_set_state",
+    "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
     "apv_comm_unique_id", "apv_comm_init", "apv_allgather_filters_dev", "apv_comm_count", "apv_comm_last_gather", "apv_comm_barrier",
@@ -132,6 +132,8 @@ def load():
     lib.apv_stream_is_f64.argtypes = [vp]
     lib.apv_stream_get_statistics.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.apv_stream_not_converged.argtypes = [vp]
+    lib.apv_stream_set_rirs.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.apv_set_mu.argtypes = [vp, C.c_double]
     lib.apv_state_bytes.argtypes = [vp, C.c_char_p, C.POINTER(sz)]
     lib.apv_get_state.argtypes = [vp, C.c_char_p, vp, sz]
     lib.apv_set_state.argtypes = [vp, C.c_char_p, vp, sz]
@@ -141,6 +143,7 @@ def load():
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
+    lib.apv_bb_set_rirs.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.apv_bb_get_state.argtypes = [vp, C.c_char_p, vp, sz]
     lib.apv_host_alloc.argtypes = [C.POINTER(vp), sz]
     lib.apv_host_free.argtypes = [vp]
@@ -507,6 +510,18 @@ class Engine:
         self._chk(self.lib.apv_stream_init(self.h, rir_A.shape[0], _ptr(rir_A), _ptr(rir_B),
                                            int(reference_index_A), int(reference_index_B), int(modeling_delay)))
 
+    def _set_rirs(self, fn, rir_len, rirs):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in rirs]
+        self._chk(fn(self.h, int(rir_len), *[None if a is None else _ptr(a) for a in arrs]))
+
+    def stream_set_rirs(self, rir_len, rir_A=None, rir_B=None, target_rir_A=None, target_rir_B=None):
+        """New responses between two hops (None = unchanged): rir_* (rir_len, L, M), target_rir_* (rir_len, M), float64."""
+        self._set_rirs(self.lib.apv_stream_set_rirs, rir_len, (rir_A, rir_B, target_rir_A, target_rir_B))
+
+    def set_mu(self, mu):
+        """mu of the next hop on (either stream mode)."""
+        self._chk(self.lib.apv_set_mu(self.h, float(mu)))
+
     def stream_set_perceptual(self, tables, normalisation):
         """tables: ap_vast_unofficial_amd.perceptual.PerceptualTables (or None to switch the weighting off)."""
         if tables is None:
@@ -664,6 +679,10 @@ class Engine:
             raise ValueError("out must be a C-contiguous float64 array of shape %r" % (shape,))
         self._chk_stream(self.lib.apv_bb_process_signal(self.h, n_hops, _ptr(in_A), _ptr(in_B), _ptr(out)))
         return out
+
+    def bb_set_rirs(self, rir_len, rir_A=None, rir_B=None, target_rir_A=None, target_rir_B=None):
+        """apv_bb_set_rirs: as stream_set_rirs, for the broadband stream."""
+        self._set_rirs(self.lib.apv_bb_set_rirs, rir_len, (rir_A, rir_B, target_rir_A, target_rir_B))
 
     def bb_get_state(self, name, shape):
         out = np.empty(shape, dtype=np.float64)

@@ -14,6 +14,11 @@ What is the same as the reference
   * readable attributes: hop_size, window, number_of_srcs, number_of_mics, w_A/w_B, lambda_A/lambda_B, U_A/U_B,
     R_A_to_A/R_A_to_B/R_B_to_B/R_B_to_A, r_A/r_B, filter_spectra_A/B/A_t/B_t, input_spectrum_A/B (apvast.py:368-403);
     in subband mode they are per bin (leading axis K)
+  * ``rir_A``, ``rir_B``, ``target_rir_A``, ``target_rir_B`` and ``mu`` may be reassigned between two hops, in both modes, as the
+    reference reads them on every hop (apvast.py:161, 167-193): the samples already in keep ringing out through the response
+    they were filtered with (lfilter's zi), the next hop on goes through the new one.  Targets are readable, built once as
+    apvast.py:100-112 builds them and not re-derived from new rir_*; reference_index_* and modeling_delay are read only at
+    construction, as in the reference
 What is different (keyword-only, after ``perceptual``)
   * ``mode="subband"`` (default): one (R_B, R_D) pair, one GEVD and one filter PER FREQUENCY BIN from the
     current block's control-point spectra -- the fast path (``filter_length`` and
@@ -26,6 +31,9 @@ What is different (keyword-only, after ``perceptual``)
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).
+  * an assigned response must have the constructor's shape and be finite (ValueError otherwise, nothing changed); the class keeps
+    a READ-ONLY float64 copy, so an in-place edit raises where the reference would see it.  Everything assigned since the last
+    hop is applied at the start of the next one
   * outputs are fresh arrays (the reference returns views into its overlap buffers that the next
     call overwrites, apvast.py:500-504).
   * the per-hop attributes (w_*, lambda_*, input_spectrum_*, filter_spectra_*, U_*, R_*, r_*) are fetched from the device
@@ -113,14 +121,12 @@ class apvast:
                  max_sweeps: int = 0,
                  sweep_tol2: float = 0.0):
         self.block_size = block_size
-        self.rir_A = rir_A
-        self.rir_B = rir_B
         self.filter_length = filter_length
         self.modeling_delay = modeling_delay
         self.reference_index_A = reference_index_A
         self.reference_index_B = reference_index_B
         self.number_of_eigenvectors = number_of_eigenvectors
-        self.mu = mu
+        self._mu = float(mu)
         self.sampling_rate = sampling_rate
         self.statistics_buffer_length = statistics_buffer_length
         self.run_A = run_A
@@ -148,6 +154,7 @@ class apvast:
         self.window = np.sin(np.pi / self.block_size * np.arange(self.block_size)).reshape(-1, 1)   # apvast.py:94
         self.rir_length, self.number_of_srcs, self.number_of_mics = rir_A.shape  # apvast.py:97-99
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
+        self._init_responses(rir_A, rir_B)
         if mode == "broadband":
             self._init_broadband(device, seed)
             return
@@ -163,7 +170,7 @@ class apvast:
         else:
             reg_mode, reg_dark, reg_bright = _capi.REG_REL, 5e-3, 1e-8        # apVast.m:552-569
         zones = (1 if run_A else 0) | (2 if run_B else 0)
-        self._eng = _capi.Engine(self._K, L, M, ranks=self._ranks, mu=mu, compute_dtype="f32" if dtype == "f32" else "f64",
+        self._eng = _capi.Engine(self._K, L, M, ranks=self._ranks, mu=self._mu, compute_dtype="f32" if dtype == "f32" else "f64",
                                  reg_mode=reg_mode, reg_dark=reg_dark, reg_bright=reg_bright, device=device,
                                  block_size=N, hop_size=H, n_zones=zones, frontend="f32" if dtype == "mixed" else None,
                                  max_sweeps=self._max_sweeps, sweep_tol2=sweep_tol2,
@@ -192,6 +199,70 @@ class apvast:
         self._hops = 0                      # attributes of apvast.py:368-403 exist once a hop has run
         self._sb_cache = {}
 
+    # ---- responses and mu, reassignable between hops (the reference reads them on every hop, apvast.py:161, 167-193) ----
+    def _init_responses(self, rir_A, rir_B):
+        """Read-only float64 copies of the constructor's responses and the targets built from them (apvast.py:100-112)."""
+        P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
+        d = self.modeling_delay
+        live = {"rir_A": np.array(rir_A, dtype=np.float64), "rir_B": np.array(rir_B, dtype=np.float64),
+                "target_rir_A": np.zeros((P, M)), "target_rir_B": np.zeros((P, M))}
+        for z, ref in (("A", self.reference_index_A), ("B", self.reference_index_B)):
+            if 0 <= d < P and 0 <= ref < L:
+                live["target_rir_" + z][d:] = live["rir_" + z][: P - d, ref, :]
+        for a in live.values():
+            a.flags.writeable = False
+        self._live = live
+        self._live_pending = set()          # names assigned since the last hop, applied together at the next one
+        self._mu_pending = False
+        self._live_applied = False          # some update reached the device: get_state carries the correction tails
+
+    def _set_response(self, name, value):
+        P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
+        shape = (P, L, M) if name.startswith("rir_") else (P, M)
+        a = np.array(value, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{name} must have shape {shape} (the constructor's), got {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"{name} must be finite")
+        if np.array_equal(a, self._live[name]):
+            return
+        a.flags.writeable = False
+        self._live[name] = a
+        self._live_pending.add(name)
+
+    def _apply_live(self):
+        """Everything assigned since the last hop, in one upload and one correction launch (apv_stream_set_rirs / apv_bb_set_rirs)."""
+        if self._live_pending:
+            new = {k: (self._live[k] if k in self._live_pending else None) for k in ("rir_A", "rir_B", "target_rir_A", "target_rir_B")}
+            set_rirs = self._eng.bb_set_rirs if self.mode == "broadband" else self._eng.stream_set_rirs
+            set_rirs(self.rir_length, **new)
+            self._live_pending.clear()
+            self._live_applied = True
+        if self._mu_pending:
+            self._eng.set_mu(self._mu)
+            self._mu_pending = False
+
+    # rir_A / rir_B (rir_length, L, M) and target_rir_A / target_rir_B (rir_length, M): an assignment between two hops takes effect at
+    # the next one as lfilter(..., zi=state) makes it in the reference -- the samples already in take the old response's tail with
+    # them.  Targets are not re-derived from new rir_* (apvast.py:100-112 builds them once).  The arrays held are read-only copies.
+    rir_A = property(lambda self: self._live["rir_A"], lambda self, v: self._set_response("rir_A", v))
+    rir_B = property(lambda self: self._live["rir_B"], lambda self, v: self._set_response("rir_B", v))
+    target_rir_A = property(lambda self: self._live["target_rir_A"], lambda self, v: self._set_response("target_rir_A", v))
+    target_rir_B = property(lambda self: self._live["target_rir_B"], lambda self, v: self._set_response("target_rir_B", v))
+
+    @property
+    def mu(self):
+        return self._mu
+
+    @mu.setter
+    def mu(self, value):
+        m = float(value)
+        if not np.isfinite(m):
+            raise ValueError("mu must be finite")
+        if m != self._mu:
+            self._mu = m
+            self._mu_pending = True
+
     # ---- broadband mode: the reference's own time-domain algorithm, float64 on the device ----------
     def _init_broadband(self, device, seed):
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
@@ -214,7 +285,7 @@ class apvast:
         V = len(self._ranks)
         self._K = N // 2 + 1
         zones = (1 if self.run_A else 0) | (2 if self.run_B else 0)
-        self._eng = _capi.Engine(self._K, L, M, ranks=(1,), mu=self.mu, compute_dtype="f64", device=device, block_size=N,
+        self._eng = _capi.Engine(self._K, L, M, ranks=(1,), mu=self._mu, compute_dtype="f64", device=device, block_size=N,
                                  hop_size=H, n_zones=zones, dialect=self.dialect, max_sweeps=self._max_sweeps,
                                  out_layout=1,     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
                                  **reg)
@@ -278,6 +349,7 @@ class apvast:
         input_B = np.asarray(input_B)
         if input_A.size != self.hop_size or input_B.size != self.hop_size:
             raise RuntimeError("invalid input size")                          # apvast.py:154-155
+        self._apply_live()
         if self.mode == "broadband":
             out = self._eng.bb_process_block(input_A, input_B, self._n_out)      # (groups, H, L), fresh for every hop
             res = self._split_groups(out)
@@ -306,6 +378,7 @@ class apvast:
             raise RuntimeError("invalid input size")
         if input_A.size == 0:
             raise RuntimeError("invalid input size")
+        self._apply_live()
         if self.mode == "broadband":
             # the joint diagonalisations of up to 16 consecutive hops are solved as one batch (apv_bb_process_signal); the library
             # writes (groups, n_samples, L) -- every zone program's and rank's whole signal as the array handed out below
@@ -471,10 +544,27 @@ class apvast:
     _BB_STATE = ("response", "target_response", "stats", "target_stats", "overlap", "target_overlap", "input_block",
                  "input_history", "out_overlap")
     _SB_STATE = ("response", "target_response", "input_block", "input_history", "out_overlap")
+    _LIVE_STATE = ("fir_correction", "target_fir_correction")       # present once a response update has been applied
 
     def get_state(self):
         """Everything the next hop depends on (the reference's instance attributes of apvast.py:115-151), as float64 arrays
-        in the reference's own axis order; ``b.set_state(a.get_state())`` makes b continue exactly as a would."""
+        in the reference's own axis order; ``b.set_state(a.get_state())`` makes b continue exactly as a would.  Once a response
+        update has been applied, also the correction tails it left: ``fir_correction`` (4, rir_length - 1, L, M) and
+        ``target_fir_correction`` (2, rir_length - 1, M).  The responses and mu are not state: an object resumed across an
+        update must first be given the same rir_* / target_rir_* / mu (by construction or assignment) as the one it continues."""
+        st = self._get_state()
+        if self._live_applied:
+            P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
+            Q = max(P - 1, 1)
+            if self.mode == "broadband":
+                g = lambda name, shape: self._eng.bb_get_state(name, shape)
+            else:
+                g = lambda name, shape: self._eng.get_state(name, shape, self._eng.s_dtype).astype(np.float64)
+            st["fir_correction"] = np.stack([g(f"fir_correction{p}", (M, L, Q)) for p in range(4)]).transpose(0, 3, 2, 1)
+            st["target_fir_correction"] = np.stack([g(f"target_fir_correction{z}", (M, Q)) for z in range(2)]).transpose(0, 2, 1)
+        return st
+
+    def _get_state(self):
         e, N, L, M = self._eng, self.block_size, self.number_of_srcs, self.number_of_mics
         if self.mode == "broadband":
             S, P, H = self.statistics_buffer_length, self.rir_length, self.hop_size
@@ -506,10 +596,27 @@ class apvast:
 
     def set_state(self, state):
         e = self._eng
-        known = self._BB_STATE if self.mode == "broadband" else self._SB_STATE
+        known = (self._BB_STATE if self.mode == "broadband" else self._SB_STATE) + self._LIVE_STATE
         unknown = sorted(set(state) - set(known))
         if unknown:
             raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
+        self._set_state(state)
+        if any(k in state for k in self._LIVE_STATE):
+            self._apply_live()             # responses assigned before the resume are in place before their tails are
+            dt = np.float64 if self.mode == "broadband" else e.s_dtype
+            put = e.bb_set_state if self.mode == "broadband" else e.set_state
+            if "fir_correction" in state:
+                r = np.asarray(state["fir_correction"], dtype=dt)                 # (4, P-1, L, M) -> [M][L][P-1]
+                for p in range(4):
+                    put(f"fir_correction{p}", np.ascontiguousarray(r[p].transpose(2, 1, 0)))
+            if "target_fir_correction" in state:
+                t = np.asarray(state["target_fir_correction"], dtype=dt)          # (2, P-1, M) -> [M][P-1]
+                for z in range(2):
+                    put(f"target_fir_correction{z}", np.ascontiguousarray(t[z].T))
+            self._live_applied = True
+
+    def _set_state(self, state):
+        e = self._eng
         if self.mode == "broadband":
             f = lambda a: np.asarray(a, dtype=np.float64)
             per_path = {"response": "response", "stats": "stats", "overlap": "overlap"}

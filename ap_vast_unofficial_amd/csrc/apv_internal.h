@@ -268,6 +268,44 @@ struct FirJobsD {
 };
 hipError_t apv_launch_fir_jobs_f64(FirJobsD jobs, int njobs, int P, int H, int N, int ring_off, hipStream_t s);
 int apv_fir_pad_f64();
+// kernels_live.hip: responses reassigned between hops (apv_stream_set_rirs / apv_bb_set_rirs).  Jobs 0..3 are the paths A->A, A->B,
+// B->A, B->B ([C][P-1] tails), 4..5 the targets ([M][P-1]); all buffers in the stream's front-end precision.
+struct FirLive {
+    int hops_left;                 // hops whose K1 output still takes a tail (0: nothing pending, the stream runs as if never updated)
+    bool live[6];                  // job j has a tail
+    void* corr[6];                 // tails [C_j][P-1], index 0 = the next hop's first sample; allocated at the first update
+    void* stage[4];                // new banks rir A, B, trir A, B in the device layout, on their way in
+};
+struct FirLiveJobs {
+    const void* old[FIR_JOBS_D];   // fir_tail: bank as it was, bank that replaces it, the P - 1 newest input samples
+    const void* nw[FIR_JOBS_D];
+    const void* xh[FIR_JOBS_D];
+    void* corr[FIR_JOBS_D];
+    void* dst[FIR_JOBS_D];         // tail_apply: K1 output rows
+    int C[FIR_JOBS_D];
+    int n;
+};
+struct FirLiveBanks {
+    int P, H, L, M, f64;
+    void* rir[2];                  // [P][C] banks of the stream, rewritten in place
+    void* trir[2];                 // [P][M]
+    const void* hist_tail[2];      // per signal: the P - 1 newest input samples before the update, oldest first
+};
+hipError_t apv_launch_fir_tail(int f64, const FirLiveJobs& jobs, int P, hipStream_t s);
+hipError_t apv_launch_tail_apply(int f64, const FirLiveJobs& jobs, int Q, int n_add, int shift, long row_len, int d0, int dmod,
+                                 hipStream_t s);
+hipError_t apv_launch_bank_transpose(int f64, int P, int C, const void* src, void* dst, hipStream_t s);
+void apv_bank_to_device(const double* src, int P, int L, int M, bool target, std::vector<double>& out);
+// the changed banks (h_new[k] != nullptr: rir A, rir B, target A, target B) uploaded, their tails accumulated, the banks replaced
+int apv_live_update(apv_handle* h, FirLive& fl, const FirLiveBanks& b, const double* const h_new[4], hipStream_t st);
+// after K1: the next n_add samples of every live tail added to dst[j] at (d0 + m) mod dmod (rows row_len apart), tails shifted by `shift`
+int apv_live_apply(apv_handle* h, FirLive& fl, int P, int C, int M, int f64, void* const dst[6], int n_add, int shift, long row_len,
+                   int d0, int dmod, hipStream_t st);
+void apv_live_advance(FirLive& fl, int hops);
+// named state "fir_correction<j>" (j < 4) / "target_fir_correction<j - 4>": get or set tail j, esz bytes per sample
+int apv_live_state(apv_handle* h, FirLive& fl, int j, int P, int H, int C, int M, size_t esz, void* h_buf, size_t bytes, bool get,
+                   hipStream_t st);
+void apv_live_free(FirLive& fl);
 // f64 = 0: c64 spectra / float weights; 1: c128 spectra / double weights (bin-major [K][M])
 hipError_t apv_launch_perceptual_weights(int f64, int K, int M, int nch, const void* spec, const double* G2, const double* G2T,
                                          double Cs, double Ca, double Leff, int N, int norm_mode, void* W, hipStream_t s);

@@ -115,6 +115,10 @@ struct apv_stream {
     // work space of apv_stream_get_statistics (R_B, R_D, r, U, w, lam, spill, status), allocated at its first call and kept
     void* stat_ws[10];
     size_t stat_spill_bytes;
+    // responses reassigned between hops (apv_stream_set_rirs): the tails still to be added to K1's output, and a channel-major
+    // copy of one bank for its fast-convolution spectra; allocated at the first update
+    FirLive live;
+    void* live_cm;
     std::vector<hipGraphExec_t> execs;
     std::vector<int32_t> h_status;
 };
@@ -235,6 +239,8 @@ void apv_stream_free(apv_handle* h) {
     if (s->ck_inspec) (void)hipFree(s->ck_inspec);
     if (s->ck_out) (void)hipFree(s->ck_out);
     if (s->ck_ospec) (void)hipFree(s->ck_ospec);
+    apv_live_free(s->live);
+    if (s->live_cm) (void)hipFree(s->live_cm);
     delete s;
     h->st = nullptr;
 }
@@ -312,6 +318,13 @@ static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin
         for (int z = 0; z < 2; ++z)
             jobs.j[4 + z] = FirJob{(const float*)s->trir[z], (const float*)s->xhist[s->cur][z], (float*)s->tresp[z], M};
         SCHK(h, apv_launch_fir_jobs(jobs, P, H, N, s->ring_off, st));
+    }
+    if (s->live.hops_left > 0) {
+        // responses replaced within the last P - 1 samples: the samples before the update still ring out through the old ones
+        void* dst[6] = {s->resp[0], s->resp[1], s->resp[2], s->resp[3], s->tresp[0], s->tresp[1]};
+        int rc = apv_live_apply(h, s->live, P, C, M, f64, dst, H, H, N, N - H + s->ring_off, N, st);
+        if (rc != APV_OK) return rc;
+        apv_live_advance(s->live, 1);
     }
     // K2: analysis, bin-major output
     const bool runA = s->zones & 1, runB = s->zones & 2;
@@ -454,8 +467,9 @@ static int run_hop(apv_handle* h) {
     apv_stream* s = h->st;
     hipStream_t st = h->stream;
     const int H = s->H;
-    if (s->period > 0) {
-        // replay the captured launch sequence of this phase; capture it the first time the phase comes up
+    if (s->period > 0 && s->live.hops_left == 0) {
+        // replay the captured launch sequence of this phase; capture it the first time the phase comes up (a hop that adds a
+        // correction tail runs the launches eagerly: the graphs stay those of a stream that was never updated)
         const int phase = (int)(s->hop % s->period);
         const int ring_before = s->ring_off, cur_before = s->cur;
         if (!s->execs[phase]) {
@@ -922,6 +936,13 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             }
             CK(apv_launch_fir_fft_chunk(f64, s->fir_F, 6, jh, jx, (long)(2 * (s->fir_F / 2 + 1)), jr, jc, P, H, RL, N - H, nc, s->front));
         }
+        if (s->live.hops_left > 0) {
+            // the chunk's share of the pending correction tails, on the samples the per-hop path would add them to
+            void* dst[6] = {s->ck_resp[par][0], s->ck_resp[par][1], s->ck_resp[par][2], s->ck_resp[par][3], s->ck_tresp[par][0],
+                            s->ck_tresp[par][1]};
+            if ((rc = apv_live_apply(h, s->live, P, C, M, f64, dst, nc * H, nc * H, RL, N - H, RL, s->front)) != APV_OK) return bail(rc, h->err);
+            apv_live_advance(s->live, nc);
+        }
         {
             // K2: every analysis transform of the chunk in one launch; hop i's block starts i H samples into the rows
             const HopSpectra q0 = set_of(par, 0);
@@ -1103,6 +1124,23 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     return APV_OK;
 }
 
+// spectra of one bank for the fast-convolution K1: cm [n_ch][P] channel-major -> spec [fir_np][n_ch][fir_F/2 + 1] (one segment: the
+// whole response; partitioned: taps [q H, (q + 1) H) of every channel, partition-major)
+static int bank_spectra(apv_handle* h, const void* cm, int n_ch, void* spec) {
+    const apv_stream* s = h->st;
+    const int np = s->fir_np, P = s->P, H = s->H;
+    const size_t Kf = (size_t)s->fir_F / 2 + 1;
+    std::string why;
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < np && e == hipSuccess; ++q) {
+        const int taps = np == 1 ? P : std::min(H, P - q * H);
+        e = apv_launch_fir_spectra_part(s->f64, s->fir_F, n_ch, (const char*)cm + (size_t)q * (np == 1 ? 0 : H) * s->esz, P, taps,
+                                        (char*)spec + (size_t)q * Kf * n_ch * 2 * s->esz, h->stream, &why);
+    }
+    if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
 extern "C" {
 
 int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const double* h_rir_B,
@@ -1179,7 +1217,6 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         void* cm = nullptr;                                  // [C][P] channel-major copy of one bank, set-up only
         if ((rc = dalloc(h, &cm, (size_t)C * P, e1))) return rc;
         std::vector<double> tr((size_t)C * P);
-        std::string why;
         for (int z = 0; z < 2; ++z) {
             const double* src = z ? h_rir_B : h_rir_A;
             const int ref = z ? reference_index_B : reference_index_A;
@@ -1189,26 +1226,13 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
                 for (int l = 0; l < L; ++l)
                     for (int m = 0; m < M; ++m) tr[(size_t)(m * L + l) * P + p] = src[((size_t)p * L + l) * M + m];
             if ((rc = upload(h, f64, cm, tr))) return rc;
-            hipError_t e = hipSuccess;
-            // (one segment: the whole response; partitioned: taps [q H, (q + 1) H) of every channel, partition-major)
-            for (int q = 0; q < np && e == hipSuccess; ++q) {
-                const int taps = np == 1 ? P : std::min(H, P - q * H);
-                e = apv_launch_fir_spectra_part(f64, F, C, (const char*)cm + (size_t)q * (np == 1 ? 0 : H) * e1, P, taps,
-                                                (char*)s->rirspec[z] + (size_t)q * Kf * C * e2, h->stream, &why);
-            }
-            if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+            if ((rc = bank_spectra(h, cm, C, s->rirspec[z]))) return rc;
             SCHK(h, hipStreamSynchronize(h->stream));
             std::fill(tr.begin(), tr.end(), 0.0);
             for (int p = modeling_delay; p < P; ++p)
                 for (int m = 0; m < M; ++m) tr[(size_t)m * P + p] = src[((size_t)(p - modeling_delay) * L + ref) * M + m];
             if ((rc = upload(h, f64, cm, tr))) return rc;
-            e = hipSuccess;
-            for (int q = 0; q < np && e == hipSuccess; ++q) {
-                const int taps = np == 1 ? P : std::min(H, P - q * H);
-                e = apv_launch_fir_spectra_part(f64, F, M, (const char*)cm + (size_t)q * (np == 1 ? 0 : H) * e1, P, taps,
-                                                (char*)s->trirspec[z] + (size_t)q * Kf * M * e2, h->stream, &why);
-            }
-            if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+            if ((rc = bank_spectra(h, cm, M, s->trirspec[z]))) return rc;
             SCHK(h, hipStreamSynchronize(h->stream));
         }
         (void)hipFree(cm);
@@ -1409,6 +1433,59 @@ int apv_stream_set_perceptual(apv_handle* h, int32_t n_channels, const double* h
     return APV_OK;
 }
 
+// New responses between two hops.  NULL = that response is unchanged; targets are (P, M).  Every tail is formed from the banks as
+// they are before this call; the next hops add them to K1's output (kernels_live.hip).     replaces `ap.rir_A = ...` between two
+// calls of process_input_buffers, read by lfilter(..., zi=state) at apvast.py:167-193
+int apv_stream_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, const double* h_rir_B, const double* h_trir_A,
+                        const double* h_trir_B) {
+    if (!h || !h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
+    apv_stream* s = h->st;
+    if (rir_len != s->P) return apv_fail(h, APV_ERR_ARG, "rir_len must equal the stream's response length");
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    const double* nw[4] = {h_rir_A, h_rir_B, h_trir_A, h_trir_B};
+    if (!nw[0] && !nw[1] && !nw[2] && !nw[3]) return APV_OK;
+    FirLiveBanks b{};
+    b.P = s->P; b.H = s->H; b.L = s->L; b.M = s->M; b.f64 = s->f64;
+    for (int z = 0; z < 2; ++z) {
+        b.rir[z] = s->rir[z];
+        b.trir[z] = s->trir[z];
+        // the current history ends with the newest sample: [keep samples before the last hop | the last hop]
+        b.hist_tail[z] = (const char*)s->xhist[s->cur][z] + (size_t)(s->keep + s->H - (s->P - 1)) * s->esz;
+    }
+    int rc = apv_live_update(h, s->live, b, nw, h->stream);
+    if (rc != APV_OK) return rc;
+    if (s->fir_F > 0) {
+        // the fast-convolution K1 reads spectra of the banks: recomputed in place from the new ones
+        if (!s->live_cm) SCHK(h, hipMalloc(&s->live_cm, s->esz * (size_t)s->P * s->C));
+        for (int k = 0; k < 4; ++k) {
+            if (!nw[k]) continue;
+            const int n_ch = k < 2 ? s->C : s->M;
+            SCHK(h, apv_launch_bank_transpose(s->f64, s->P, n_ch, k < 2 ? s->rir[k] : s->trir[k - 2], s->live_cm, h->stream));
+            if ((rc = bank_spectra(h, s->live_cm, n_ch, k < 2 ? s->rirspec[k] : s->trirspec[k - 2]))) return rc;
+        }
+    }
+    SCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
+// mu of the next hop on (either stream mode).  The per-hop graphs of the subband stream hold it by value: they are captured again.
+//                                                         replaces `ap.mu = ...`, read at apvast.py:161, 406-414
+int apv_set_mu(apv_handle* h, double mu) {
+    if (!h) return apv_fail(h, APV_ERR_ARG, "null handle");
+    if (!std::isfinite(mu)) return apv_fail(h, APV_ERR_ARG, "mu must be finite");
+    if (h->st) {
+        SCHK(h, hipSetDevice(h->device));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        for (hipGraphExec_t& e : h->st->execs) {
+            if (e) (void)hipGraphExecDestroy(e);
+            e = nullptr;
+        }
+    }
+    h->cfg.mu = mu;
+    return APV_OK;
+}
+
 // Named state arrays, as stored on the device: real samples are float32 (float64 with the float64 front-end),
 // spectra the matching complex type; rings are returned in LOGICAL order:
 //   "response<p>"     [C][N]           "target_response<z>" [M][N]       "input_block" [2][N]
@@ -1416,6 +1493,15 @@ int apv_stream_set_perceptual(apv_handle* h, int32_t n_channels, const double* h
 //   "spectra<p>"      [K][C] complex   "target_spectra<z>"  [K][M] complex   "input_spectrum" [2][K] complex
 //   "weights<z>"      [K][M]
 //   "w_A" / "w_B"     [K][nV][L] c64|c128        "lambda_A" / "lambda_B" [K][L] f32|f64   (cfg.out_c128)
+//   "fir_correction<p>" [C][P-1]   "target_fir_correction<z>" [M][P-1]   pending correction tails (apv_stream_set_rirs): zeros in a
+//                                  stream that was never updated; handled by apv_live_state
+static int live_index(const char* name) {
+    const std::string n(name);
+    if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
+    if (n.size() == 22 && n.rfind("target_fir_correction", 0) == 0 && (n[21] == '0' || n[21] == '1')) return 4 + n[21] - '0';
+    return -1;
+}
+
 static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* bytes, int* ring_rows) {
     apv_stream* s = h->st;
     *ring_rows = 0;
@@ -1441,12 +1527,22 @@ static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* by
 
 int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
     if (!h || !h->st || !name || !bytes) return apv_fail(h, APV_ERR_ARG, "null argument / no stream");
+    const int j = live_index(name);
+    if (j >= 0) {
+        *bytes = h->st->esz * (size_t)(j < 4 ? h->st->C : h->st->M) * (size_t)std::max(h->st->P - 1, 1);
+        return APV_OK;
+    }
     void* d; int rr;
     return state_lookup(h, name, &d, bytes, &rr);
 }
 
 int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
     if (!h || !h->st || !name || !h_dst) return apv_fail(h, APV_ERR_ARG, "null argument / no stream");
+    if (live_index(name) >= 0) {
+        apv_stream* s = h->st;
+        SCHK(h, hipSetDevice(h->device));
+        return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, h_dst, bytes, true, h->stream);
+    }
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;
@@ -1486,6 +1582,13 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
 
 int apv_set_state(apv_handle* h, const char* name, const void* h_src, size_t bytes) {
     if (!h || !h->st || !name || !h_src) return apv_fail(h, APV_ERR_ARG, "null argument / no stream");
+    if (live_index(name) >= 0) {
+        apv_stream* s = h->st;
+        SCHK(h, hipSetDevice(h->device));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, const_cast<void*>(h_src), bytes, false,
+                              h->stream);
+    }
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;

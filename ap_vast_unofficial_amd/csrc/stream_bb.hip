@@ -99,6 +99,7 @@ struct apv_bb {
     hipEvent_t ev_ring, ev_stat;             // hop's statistics rings written / read
     hipEvent_t ev_front[2], ev_back[2];      // group set filled / group set read for the last time
     hipEvent_t ev_out[2];                    // a group's outputs have reached g_pin
+    FirLive live;          // responses reassigned between hops (apv_bb_set_rirs): the correction tails still to be added to K1's output
 };
 
 namespace {
@@ -865,6 +866,7 @@ void apv_bb_free(apv_handle* h) {
         if (s->ev_back[i]) (void)hipEventDestroy(s->ev_back[i]);
         if (s->ev_out[i]) (void)hipEventDestroy(s->ev_out[i]);
     }
+    apv_live_free(s->live);
     delete s;
     h->bb = nullptr;
 }
@@ -1072,6 +1074,13 @@ static int bb_front(apv_handle* h, apv_bb* s, const BbHop& q, double* t_stage, h
             jobs.C[nj++] = M;
         }
         BCHK(h, apv_launch_fir_jobs_f64(jobs, nj, P, H, N, s->ring_off, st));
+        if (s->live.hops_left > 0) {
+            // responses replaced within the last P - 1 samples: the samples before the update ring out through the old ones
+            double* dst[6] = {s->resp[0], s->resp[1], s->resp[2], s->resp[3], s->tresp[0], s->tresp[1]};
+            const int rc = apv_live_apply(h, s->live, P, C, M, 1, (void* const*)dst, H, H, N, N - H + s->ring_off, N, st);
+            if (rc != APV_OK) return rc;
+            apv_live_advance(s->live, 1);
+        }
     }
     stage_done();
     // 2: WOLA (unit weights, apvast.py:326-327, or the perceptual curves) and append the finished hop to the statistics rings:
@@ -1672,6 +1681,37 @@ int apv_vast_static(apv_handle* h, int32_t Nb, int32_t Nd, int32_t P, int32_t L,
     return rc;
 }
 
+// New responses between two hops of the broadband stream; arguments and semantics as apv_stream_set_rirs (stream.hip).
+//                                    replaces `ap.rir_A = ...` between two hops, read by lfilter(..., zi=state) at apvast.py:167-193
+int apv_bb_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, const double* h_rir_B, const double* h_trir_A,
+                    const double* h_trir_B) {
+    if (!h || !h->bb) return apv_fail(h, APV_ERR_ARG, "null argument / broadband stream not initialised");
+    apv_bb* s = h->bb;
+    if (rir_len != s->P) return apv_fail(h, APV_ERR_ARG, "rir_len must equal the stream's response length");
+    BCHK(h, hipSetDevice(h->device));
+    BCHK(h, hipStreamSynchronize(h->stream));
+    const double* nw[4] = {h_rir_A, h_rir_B, h_trir_A, h_trir_B};
+    FirLiveBanks b{};
+    b.P = s->P; b.H = s->H; b.L = s->L; b.M = s->M; b.f64 = 1;
+    for (int z = 0; z < 2; ++z) {
+        b.rir[z] = s->rir[z];
+        b.trir[z] = s->trir[z];
+        b.hist_tail[z] = s->xhist[s->cur][z] + s->H;          // [P - 1 samples before the last hop | the last hop]: its last P - 1
+    }
+    const int rc = apv_live_update(h, s->live, b, nw, h->stream);
+    if (rc != APV_OK) return rc;
+    BCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
+static int bb_live_index(const char* name) {
+    const std::string n(name);
+    if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
+    if (n.size() == 22 && n.rfind("target_fir_correction", 0) == 0 && (n[21] == '0' || n[21] == '1')) return 4 + n[21] - '0';
+    return -1;
+}
+
+
 // state: "response<p>" [C][N], "target_response<z>" [M][N], "input_block" [2][N] (rings, logical order); "R<q>" [n][n]
 // (AA, BB, AB, BA), "r" [2][n], "lambda" [2][n], "w" [2][V][n], "U<z>" [n][n] (columns = eigenvectors, descending),
 // "stats<p>" [C][S], "target_stats<z>" [M][S] (rings, logical order); and what a bit-for-bit resume also needs:
@@ -1732,6 +1772,12 @@ static int bb_complete_eigenpairs(apv_handle* h) {
 
 int apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t count) {
     if (!h || !h->bb || !name || !h_dst) return apv_fail(h, APV_ERR_ARG, "null argument / broadband stream not initialised");
+    if (bb_live_index(name) >= 0) {
+        apv_bb* s = h->bb;
+        BCHK(h, hipSetDevice(h->device));
+        return apv_live_state(h, s->live, bb_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), h_dst, sizeof(double) * count,
+                              true, h->stream);
+    }
     double* d; size_t need; int rows, len, off;
     int rc = bb_lookup(h, name, &d, &need, &rows, &len, &off);
     if (rc != APV_OK) return rc;
@@ -1755,6 +1801,13 @@ int apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t coun
 
 int apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size_t count) {
     if (!h || !h->bb || !name || !h_src) return apv_fail(h, APV_ERR_ARG, "null argument / broadband stream not initialised");
+    if (bb_live_index(name) >= 0) {
+        apv_bb* s = h->bb;
+        BCHK(h, hipSetDevice(h->device));
+        BCHK(h, hipStreamSynchronize(h->stream));
+        return apv_live_state(h, s->live, bb_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), const_cast<double*>(h_src),
+                              sizeof(double) * count, false, h->stream);
+    }
     double* d; size_t need; int rows, len, off;
     int rc = bb_lookup(h, name, &d, &need, &rows, &len, &off);
     if (rc != APV_OK) return rc;

@@ -262,6 +262,18 @@ long apv_stream_not_converged(apv_handle* h);
  *                         replaces update_perceptual_weighting, apvast.py:313-324 / apVast.m:386-408 */
 int  apv_stream_set_perceptual(apv_handle* h, int32_t n_channels, const double* h_G2, double Cs, double Ca,
                                double Leff, int32_t normalisation);
+/* New room responses between two hops, without tearing the stream down.  h_rir_A / h_rir_B: (rir_len, L, M), h_trir_A /
+ * h_trir_B: (rir_len, M) target responses, all float64 C order; NULL = that response is unchanged (targets are not re-derived from
+ * new rir_*: the reference builds them once, apvast.py:100-112).  rir_len must equal the stream's (else APV_ERR_ARG, nothing
+ * changed).  Every sample that arrived before the call keeps ringing out through the response it was filtered with, the samples
+ * of the next hop on go through the new one: the difference is added to the next ceil((rir_len - 1) / H) hops as a correction tail
+ * (state "fir_correction<p>" [C][rir_len-1], "target_fir_correction<z>" [M][rir_len-1]).  Several calls compose.
+ *                        replaces `ap.rir_A = ...` etc. between two hops, read by lfilter(..., zi=state) at apvast.py:167-193 */
+int  apv_stream_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, const double* h_rir_B, const double* h_trir_A,
+                         const double* h_trir_B);
+/* mu of the next hop on, either stream mode (the subband stream's captured per-hop graphs are captured again).
+ *                        replaces `ap.mu = ...` between two hops, read at apvast.py:161, 406-414 */
+int  apv_set_mu(apv_handle* h, double mu);
 /* Named state arrays for fixtures / checkpoint-resume (names: see stream.hip), in the front-end precision:
  * float32 / complex64, or float64 / complex128 with the float64 front-end.          apvast.py:115-151 */
 int  apv_state_bytes(apv_handle* h, const char* name, size_t* bytes);
@@ -306,6 +318,10 @@ int  apv_host_free(void* p);
 /* perceptual weighting for the broadband stream; arguments as for apv_stream_set_perceptual */
 int  apv_bb_set_perceptual(apv_handle* h, int32_t n_channels, const double* h_G2, double Cs, double Ca, double Leff,
                            int32_t normalisation);
+/* apv_stream_set_rirs for the broadband stream (same arguments and semantics).
+ *                        replaces `ap.rir_A = ...` etc. between two hops, read by lfilter(..., zi=state) at apvast.py:167-193 */
+int  apv_bb_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, const double* h_rir_B, const double* h_trir_A,
+                     const double* h_trir_B);
 /* float64 state arrays by name (stream_bb.hip); `count` = number of doubles */
 int  apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t count);
 int  apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size_t count);
