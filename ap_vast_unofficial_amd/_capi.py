@@ -11,6 +11,7 @@ import numpy as np
 ABI_VERSION = 2
 MAX_RANKS = 64        # ranks the config struct carries (longer lists: Engine.set_rank_list / apv_set_rank_list)
 MAX_N = 64            # largest order of apv_jdiag_batched and of the on-chip per-bin kernels
+MAX_STAT_HOPS = 64    # longest statistics window of the subband stream, in hops (apv_stream_set_stat_hops)
 MAX_SRCS = 128        # largest n_srcs of a handle (orders 65..128: csrc/kernels_gevd128.hip, float64 arithmetic)
 
 F32, F64 = 0, 1
@@ -30,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -140,6 +141,7 @@ def load():
     lib.apv_bb_init.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32]
     lib.apv_bb_set_rank_list.argtypes = [vp, i32, vp]
     lib.apv_set_rank_list.argtypes = [vp, i32, vp]
+    lib.apv_stream_set_stat_hops.argtypes = [vp, i32]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -213,7 +215,7 @@ class Engine:
     def __init__(self, n_bins, n_srcs, n_mics, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=None,
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
-                 out_layout=0):
+                 out_layout=0, stat_hops=1):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -257,6 +259,14 @@ class Engine:
         self.h = h
         if len(ranks) > MAX_RANKS:
             self.set_rank_list(ranks)
+        self.stat_hops = 1
+        if int(stat_hops) != 1:
+            self.set_stat_hops(stat_hops)
+
+    def set_stat_hops(self, n_hops):
+        """Statistics window of the subband stream, in hops (1..MAX_STAT_HOPS), before stream_init (apv_stream_set_stat_hops)."""
+        self._chk(self.lib.apv_stream_set_stat_hops(self.h, int(n_hops)))
+        self.stat_hops = int(n_hops)
 
     def set_rank_list(self, ranks):
         """Replace the handle's rank list (ascending, each 1..n_srcs, at most n_srcs of them) before stream_init: the way to
@@ -573,6 +583,11 @@ class Engine:
         lam = np.empty((K, L)) if want_U else None
         self._chk(self.lib.apv_stream_get_statistics(self.h, int(zone), _ptr(RB), _ptr(RD), _ptr(r), _ptr(U), _ptr(lam)))
         return RB, RD, r, U, lam
+
+    @property
+    def stat_dtype(self):
+        """dtype of the statistics window's ring (states "stat_window<z>"): that of the joint diagonalisation's arithmetic."""
+        return np.complex128 if (self.f64 or self.L > MAX_N) else np.complex64
 
     @property
     def s_dtype(self):

@@ -21,8 +21,12 @@ What is the same as the reference
     construction, as in the reference
 What is different (keyword-only, after ``perceptual``)
   * ``mode="subband"`` (default): one (R_B, R_D) pair, one GEVD and one filter PER FREQUENCY BIN from the
-    current block's control-point spectra -- the fast path (``filter_length`` and
-    ``statistics_buffer_length`` are accepted and stored, not used).  ``dtype="f64"`` (default) runs every stage in
+    current block's control-point spectra -- the fast path -- or, with ``statistics_hops=T``, from the spectra of the
+    last T hops: R_B[k] = sum_t X_B^(h-t)[k]^H X_B^(h-t)[k], likewise R_D and r, the per-bin form of the reference's
+    statistics buffer of several blocks (apvast.py:329-364).  ``statistics_hops="auto"`` takes T from
+    ``statistics_buffer_length``: the whole blocks that many samples span, max(1, 1 + (S - N) // hop_size); the default 1
+    keeps the single-block update (``filter_length`` is accepted and stored, not used; ``statistics_buffer_length`` is
+    used by ``"auto"`` only).  With T > 1 the attributes R_*, r_*, U_*, lambda_* are those of the window.  ``dtype="f64"`` (default) runs every stage in
     float64 like the reference's lfilter / rfft / irfft (apvast.py:171-192, 202-203, 461-496); ``"f32"`` runs every
     stage in float32; ``"mixed"`` keeps the float32 FIR / STFT / overlap-add around a float64 joint diagonalisation.
     Up to 128 loudspeakers: above 64 the per-bin joint diagonalisation runs in float64 whatever ``dtype`` is
@@ -119,7 +123,8 @@ class apvast:
                  seed=None,
                  fullscale_db_spl: float = 94.0,
                  max_sweeps: int = 0,
-                 sweep_tol2: float = 0.0):
+                 sweep_tol2: float = 0.0,
+                 statistics_hops=1):
         self.block_size = block_size
         self.filter_length = filter_length
         self.modeling_delay = modeling_delay
@@ -151,6 +156,8 @@ class apvast:
             raise ValueError("at least one of run_A / run_B must be True")
 
         self.hop_size = hop_size if hop_size else self.block_size // 2        # apvast.py:93
+        self.statistics_hops = self._resolve_statistics_hops(statistics_hops, statistics_buffer_length, block_size,
+                                                             self.hop_size, mode)
         self.window = np.sin(np.pi / self.block_size * np.arange(self.block_size)).reshape(-1, 1)   # apvast.py:94
         self.rir_length, self.number_of_srcs, self.number_of_mics = rir_A.shape  # apvast.py:97-99
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
@@ -174,7 +181,8 @@ class apvast:
                                  reg_mode=reg_mode, reg_dark=reg_dark, reg_bright=reg_bright, device=device,
                                  block_size=N, hop_size=H, n_zones=zones, frontend="f32" if dtype == "mixed" else None,
                                  max_sweeps=self._max_sweeps, sweep_tol2=sweep_tol2,
-                                 out_layout=1)     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
+                                 out_layout=1,     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
+                                 stat_hops=self.statistics_hops)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -198,6 +206,24 @@ class apvast:
             self.set_state({"response": np.stack(resp), "target_response": np.stack(tresp)})
         self._hops = 0                      # attributes of apvast.py:368-403 exist once a hop has run
         self._sb_cache = {}
+
+    @staticmethod
+    def _resolve_statistics_hops(value, statistics_buffer_length, block_size, hop_size, mode):
+        """statistics_hops as an int in 1.._capi.MAX_STAT_HOPS.  "auto": the whole blocks that statistics_buffer_length samples
+        span, max(1, 1 + (S - N) // H) (the reference's example: S = 512, N = 256, H = 128 -> 3), capped at the largest window.
+        Broadband mode has its own statistics buffer: only 1 and "auto" (which mean nothing there) are accepted."""
+        if isinstance(value, str):
+            if value != "auto":
+                raise ValueError("statistics_hops must be an int in 1..%d or 'auto'" % _capi.MAX_STAT_HOPS)
+            if mode == "broadband":
+                return 1
+            T = max(1, 1 + (int(statistics_buffer_length) - int(block_size)) // int(hop_size))
+            return min(T, _capi.MAX_STAT_HOPS)
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= _capi.MAX_STAT_HOPS:
+            raise ValueError("statistics_hops must be an int in 1..%d or 'auto'" % _capi.MAX_STAT_HOPS)
+        if mode == "broadband" and int(value) > 1:
+            raise ValueError("statistics_hops > 1 is a subband keyword: broadband mode averages over statistics_buffer_length samples")
+        return int(value)
 
     # ---- responses and mu, reassignable between hops (the reference reads them on every hop, apvast.py:161, 167-193) ----
     def _init_responses(self, rir_A, rir_B):
@@ -545,14 +571,26 @@ class apvast:
                  "input_history", "out_overlap")
     _SB_STATE = ("response", "target_response", "input_block", "input_history", "out_overlap")
     _LIVE_STATE = ("fir_correction", "target_fir_correction")       # present once a response update has been applied
+    _WIN_STATE = ("statistics_window", "statistics_window_fill")    # present with statistics_hops > 1
 
     def get_state(self):
         """Everything the next hop depends on (the reference's instance attributes of apvast.py:115-151), as float64 arrays
         in the reference's own axis order; ``b.set_state(a.get_state())`` makes b continue exactly as a would.  Once a response
         update has been applied, also the correction tails it left: ``fir_correction`` (4, rir_length - 1, L, M) and
         ``target_fir_correction`` (2, rir_length - 1, M).  The responses and mu are not state: an object resumed across an
-        update must first be given the same rir_* / target_rir_* / mu (by construction or assignment) as the one it continues."""
+        update must first be given the same rir_* / target_rir_* / mu (by construction or assignment) as the one it continues.
+        With ``statistics_hops = T > 1`` also the window: ``statistics_window`` (zone programs that run, T, K, 2 L^2 + L) complex128
+        -- per hop and bin [R_B (lower triangle) | R_D (lower triangle) | r] of that hop alone, hops oldest first, zeros beyond the
+        fill level -- and ``statistics_window_fill``, the number of hops it holds (it fills during the first T - 1 hops).  Both are
+        absent when T = 1.  R_*, r_*, U_*, lambda_* are what the last hop of THIS object left on the device: they follow a restored
+        window from the next hop on, not from set_state."""
         st = self._get_state()
+        if self.mode == "subband" and self.statistics_hops > 1:
+            e, T, L = self._eng, self.statistics_hops, self.number_of_srcs
+            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
+            st["statistics_window"] = np.stack([e.get_state(f"stat_window{z}", (T, self._K, 2 * L * L + L), e.stat_dtype)
+                                                for z in zs]).astype(np.complex128)
+            st["statistics_window_fill"] = int(e.get_state("stat_window_fill", (1,), np.int32)[0])
         if self._live_applied:
             P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
             Q = max(P - 1, 1)
@@ -597,10 +635,22 @@ class apvast:
     def set_state(self, state):
         e = self._eng
         known = (self._BB_STATE if self.mode == "broadband" else self._SB_STATE) + self._LIVE_STATE
+        if self.mode == "subband" and self.statistics_hops > 1:
+            known = known + self._WIN_STATE
         unknown = sorted(set(state) - set(known))
         if unknown:
             raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
         self._set_state(state)
+        if "statistics_window" in state:
+            T, L = self.statistics_hops, self.number_of_srcs
+            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
+            win = np.asarray(state["statistics_window"])
+            if win.shape != (len(zs), T, self._K, 2 * L * L + L):
+                raise ValueError(f"statistics_window must have shape {(len(zs), T, self._K, 2 * L * L + L)}, got {win.shape}")
+            for i, z in enumerate(zs):
+                e.set_state(f"stat_window{z}", np.ascontiguousarray(win[i], dtype=e.stat_dtype))
+        if "statistics_window_fill" in state:
+            e.set_state("stat_window_fill", np.array([int(state["statistics_window_fill"])], dtype=np.int32))
         if any(k in state for k in self._LIVE_STATE):
             self._apply_live()             # responses assigned before the resume are in place before their tails are
             dt = np.float64 if self.mode == "broadband" else e.s_dtype

@@ -58,6 +58,11 @@ struct GevdParams {
     // the order-16 kernels on fused slabs take it (apv_gevd16m_takes_hops); 0 or 1: a single hop, strides unused
     int n_hops;
     size_t hop_X, hop_d, hop_w, hop_lam, hop_status;
+    // 1: an order-64 launch goes to the LDS kernel of kernels_gevd.hip, not to kernels_gevd64.hip.  For float64 pencils of rank
+    // below n (a statistics window that holds fewer than n rows): loaded with 1e-7 alone, the whitened matrix spans more decades
+    // than the float32 sweeps of the order-64 kernel resolve; the LDS kernel's float64 instance sweeps in float64, and its parked
+    // factor fits the same scratch slots.  (Explicit float32 statistics never reach kernels_gevd64.hip: nothing to reroute there.)
+    int no_gevd64;
 };
 
 struct apv_handle {
@@ -80,6 +85,7 @@ struct apv_handle {
     struct apv_stream* st;   // streaming state (apv_stream_init), owned
     struct apv_bb* bb;       // broadband streaming state (apv_bb_init), owned
     std::vector<int32_t> rank_list;  // the subband rank list: cfg.ranks, or apv_set_rank_list's (cfg.n_ranks entries, up to n_srcs)
+    int stat_hops;                   // apv_stream_set_stat_hops: statistics window of the next apv_stream_init, in hops (<= 1: one block)
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -202,6 +208,15 @@ hipError_t apv_launch_corr_c128(int K, int M, int L, const double2* XB, const do
 hipError_t apv_launch_corr_bf16(int K, int M, int L, const uint32_t* XB, const uint32_t* XD, const uint32_t* d,
                                 float2* RB, float2* RD, float2* r, hipStream_t s);
 hipError_t apv_launch_to_bf16(size_t count, const float2* in, uint32_t* out, hipStream_t s);
+
+// kernels_statwin.hip: statistics of the subband stream over a window of T hops (see the file header).  One launch per hop for
+// `zones` zone programs: the hop's Gram matrices into slot ctr[0] of the rings, the window sums (oldest slot first) into RB / RD /
+// r, then the counters ctr = {head, fill} advanced by a second, one-thread launch.
+size_t apv_statwin_slot_elems(int L);         // complex elements of one bin's ring slot: 2 L^2 + L
+hipError_t apv_launch_statwin(int x_c128, int acc_f64, int K, int M, int L, int T, int zones, const void* const* XB,
+                              const void* const* XD, const void* const* d, void* const* ring, void* const* RB, void* const* RD,
+                              void* const* r, int32_t* ctr, hipStream_t s);
+hipError_t apv_launch_widen_c64(size_t count, const void* in, void* out, hipStream_t s);     // c64 -> c128
 
 // kernels_stft.hip
 hipError_t apv_launch_stft_analysis(int N, int n_ch, const float* x, float2* spec, hipStream_t s, std::string* why);

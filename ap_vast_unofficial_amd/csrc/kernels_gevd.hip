@@ -680,7 +680,7 @@ hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, h
     if (!force_generic) {
         const hipError_t e16 = apv_launch_gevd16m(p, compute_dtype, fused, s);
         if (e16 != hipErrorNotSupported) return e16;
-        const hipError_t e64 = apv_launch_gevd64(p, compute_dtype, fused, s);
+        const hipError_t e64 = p.no_gevd64 ? hipErrorNotSupported : apv_launch_gevd64(p, compute_dtype, fused, s);
         if (e64 != hipErrorNotSupported) return e64;
     }
     if (n < 1 || n > APV_MAX_N) {

@@ -119,6 +119,19 @@ struct apv_stream {
     // copy of one bank for its fast-convolution spectra; allocated at the first update
     FirLive live;
     void* live_cm;
+    // statistics window (apv_stream_set_stat_hops, kernels_statwin.hip); win_T = 1: off, the fused single-block update runs
+    int win_T;                    // hops in the window
+    int win_c128;                 // ring and window sums are c128 (float64 joint diagonalisation), else c64
+    void* win_ring[2];            // per zone program: [win_T][K][2 L^2 + L] Gram matrices of the last hops
+    void* win_RB[2];              // per zone program: the window sums the joint diagonalisation reads, [K][L][L], [K][L][L], [K][L]
+    void* win_RD[2];
+    void* win_r[2];
+    int32_t* win_ctr;             // device words {head, fill}: read by the hop's statistics kernel, advanced behind it
+    int win_fill_host;            // the host's copy of fill (hops in the window before the next one), kept in step by run_hop and by
+                                  // the state "stat_window_fill".  Only win_low_rank reads it (which KERNEL solves an order-64 hop):
+                                  // the ring position itself never enters a launch from the host
+    hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
+    double win_ms[2];             // ... and {sum of its times in ms, hops timed}
     std::vector<hipGraphExec_t> execs;
     std::vector<int32_t> h_status;
 };
@@ -241,6 +254,13 @@ void apv_stream_free(apv_handle* h) {
     if (s->ck_ospec) (void)hipFree(s->ck_ospec);
     apv_live_free(s->live);
     if (s->live_cm) (void)hipFree(s->live_cm);
+    for (int z = 0; z < 2; ++z) {
+        void* wb[] = {s->win_ring[z], s->win_RB[z], s->win_RD[z], s->win_r[z]};
+        for (void* b : wb)
+            if (b) (void)hipFree(b);
+        if (s->win_ev[z]) (void)hipEventDestroy(s->win_ev[z]);
+    }
+    if (s->win_ctr) (void)hipFree(s->win_ctr);
     delete s;
     h->st = nullptr;
 }
@@ -258,6 +278,18 @@ static HopSpectra hop_spectra(const apv_stream* s, int set) {
     for (int z = 0; z < 2; ++z) q.tspec[z] = set ? s->tspec1[z] : s->tspec[z];
     q.inspec = set ? s->inspec1 : s->inspec;
     return q;
+}
+
+// Will the next hop's window hold fewer rows than the order of its pencils (fill phase of a stream with M < L, or T M < L
+// throughout) AND would its solve go to kernels_gevd64.hip (order 64, float64 statistics)?  R_B and R_D then have rank below L,
+// which that kernel does not solve (GevdParams::no_gevd64): such a hop takes the LDS kernel, and the un-captured launch sequence,
+// so that the graphs stay those of the full window.  Every other order runs the same kernel whatever the rank, graphs included.
+static bool win_low_rank(const apv_handle* h) {
+    const apv_stream* s = h->st;
+    const apv_config& c = h->cfg;
+    if (s->win_T <= 1 || !s->win_c128 || !apv_gevd64_eligible(s->L, c.reg_mode, c.reg_bright, c.sweep_tol2)) return false;
+    const long hops = s->win_fill_host + 1 < s->win_T ? s->win_fill_host + 1 : s->win_T;
+    return hops * s->M < s->L;
 }
 
 // Front half of a hop on stream `st`: pinned hop `pin_src` [2][H] -> input histories, response rings (K1), analysis
@@ -393,7 +425,33 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
     std::string why;
     // per-bin update per zone program: A: bright A->A, dark A->B, target A;  B: bright B->B, dark B->A, target B
     int oc = 0;     // output channel cursor
-    if (!sch.skip_gevd) {
+    if (s->win_T > 1) {
+        // statistics over the last win_T hops: this hop's Gram matrices into the ring and the window sums in one launch for both
+        // zone programs, then the joint diagonalisation from explicit R_B, R_D, r (the launch apv_gevd_vast_dev makes), per zone
+        const void *xb[2], *xd[2], *dd[2];
+        void *ring[2], *RB[2], *RD[2], *rr[2];
+        int zlist[2], nz = 0;
+        for (int z = 0; z < 2; ++z) {
+            if (!(z ? runB : runA)) continue;
+            xb[nz] = z ? q.X[3] : q.X[0]; xd[nz] = z ? q.X[2] : q.X[1]; dd[nz] = q.tspec[z];
+            ring[nz] = s->win_ring[z]; RB[nz] = s->win_RB[z]; RD[nz] = s->win_RD[z]; rr[nz] = s->win_r[z];
+            zlist[nz++] = z;
+        }
+        if (s->win_ev[0]) SCHK(h, hipEventRecord(s->win_ev[0], st));
+        SCHK(h, apv_launch_statwin(f64, s->win_c128, K, s->M, L, s->win_T, nz, xb, xd, dd, ring, RB, RD, rr, s->win_ctr, st));
+        if (s->win_ev[1]) SCHK(h, hipEventRecord(s->win_ev[1], st));
+        for (int i = 0; i < nz; ++i) {
+            const int z = zlist[i];
+            GevdParams p = apv_base_params(h);
+            p.RB = s->win_RB[z]; p.RD = s->win_RD[z]; p.r = s->win_r[z];
+            p.w = wz[z]; p.lam = lamz[z]; p.status = ostatus[z];
+            p.n_zones = 1;
+            p.no_gevd64 = win_low_rank(h);
+            if (sch.lspill) p.Lspill = sch.lspill;
+            hipError_t e = apv_launch_gevd(p, s->win_c128 ? APV_F64 : APV_F32, false, st, &why, h->rank_list.data());
+            if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+        }
+    } else if (!sch.skip_gevd) {
         // both zone programs go out in ONE launch (blockIdx.y = zone): K = N/2+1 bins alone cannot fill the chip
         GevdParams p = apv_base_params(h);
         const int first = runA ? 0 : 1;
@@ -467,7 +525,7 @@ static int run_hop(apv_handle* h) {
     apv_stream* s = h->st;
     hipStream_t st = h->stream;
     const int H = s->H;
-    if (s->period > 0 && s->live.hops_left == 0) {
+    if (s->period > 0 && s->live.hops_left == 0 && !win_low_rank(h)) {
         // replay the captured launch sequence of this phase; capture it the first time the phase comes up (a hop that adds a
         // correction tail runs the launches eagerly: the graphs stay those of a stream that was never updated)
         const int phase = (int)(s->hop % s->period);
@@ -500,7 +558,14 @@ static int run_hop(apv_handle* h) {
         if (rc != APV_OK) return rc;
     }
     s->hop++;
+    if (s->win_fill_host < s->win_T) s->win_fill_host++;
     SCHK(h, hipStreamSynchronize(st));
+    if (s->win_ev[0]) {
+        float ms = 0.f;
+        SCHK(h, hipEventElapsedTime(&ms, s->win_ev[0], s->win_ev[1]));
+        s->win_ms[0] += ms;
+        s->win_ms[1] += 1.0;
+    }
     return APV_OK;
 }
 
@@ -666,6 +731,31 @@ static int signal_prepare(apv_handle* h) {
 template <typename TI>
 static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out);
 
+// The whole-signal call of a stream with a statistics window: the hops one after the other through the per-hop path (its graphs
+// included), so the samples are those of n_hops per-hop calls by construction.  (One statistics launch per chunk of hops is the
+// follow-up named in DESIGN.md section 4.13.)
+template <typename TI>
+static int process_signal_hops_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
+    apv_stream* s = h->st;
+    SCHK(h, hipSetDevice(h->device));
+    int worst = APV_OK;                                      // first APV_ERR_NO_CONVERGE: every hop still runs
+    std::string worst_msg;
+    for (int i = 0; i < n_hops; ++i) {
+        stage_hops(s, h_in_A, h_in_B, i, 1, s->pin_in);
+        int rc = run_hop(h);
+        if (rc != APV_OK) return rc;
+        copy_hop_out(s, s->pin_out, n_hops, i, h_out);
+        rc = scan_hop_status(h, hop_status_of(s, s->pin_out), s->hop - 1);
+        if (rc == APV_ERR_NO_CONVERGE) {
+            if (worst == APV_OK) { worst = rc; worst_msg = h->err; }
+        } else if (rc != APV_OK) {
+            return rc;
+        }
+    }
+    if (worst != APV_OK) return apv_fail(h, worst, worst_msg);
+    return APV_OK;
+}
+
 template <typename TI>
 static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
     if (!h || !h_in_A || !h_in_B || !h_out) return apv_fail(h, APV_ERR_ARG, "null argument");
@@ -673,6 +763,7 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     if (!s) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
     if (n_hops < 0) return apv_fail(h, APV_ERR_ARG, "n_hops must be >= 0");
     if (n_hops == 0) return APV_OK;
+    if (s->win_T > 1) return process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
     // K1 as one fast-convolution segment (responses of 64 taps or more): a chunk of hops per launch (below); direct-form K1 (shorter
     // responses, APV_FIR_DIRECT) and partitioned K1 keep the hop-by-hop pipeline of this function
     if (s->fir_F > 0 && s->fir_np == 1) return process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
@@ -1175,7 +1266,9 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     s->n_out = nz * s->nV * s->L + 2 * s->L;
     s->out_group = c.out_layout == 1 ? s->L : 0;
     s->Kp = (s->K + 7) / 8 * 8;
-    s->xg_default = apv_gevd_reads_groups(apv_base_params(h), h->cfg.compute_dtype, f64 != 0);
+    s->win_T = h->stat_hops > 1 ? h->stat_hops : 1;
+    // (a windowed stream does not launch the fused kernel that reads grouped spectra: its slabs stay bin-major)
+    s->xg_default = s->win_T > 1 ? 1 : apv_gevd_reads_groups(apv_base_params(h), h->cfg.compute_dtype, f64 != 0);
     s->xg = s->xg_default;
     const int L = s->L, M = s->M, C = s->C, P = s->P, K = s->K;
     const size_t e1 = s->esz, e2 = 2 * s->esz;
@@ -1265,6 +1358,31 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         s->status[0] = reinterpret_cast<int32_t*>(outbuf + hop_out_bytes(s));
         s->status[1] = s->status[0] + K;
     }
+    if (s->win_T > 1) {
+        // the ring of per-hop Gram matrices and the window sums, in the precision the joint diagonalisation runs in (orders above
+        // 64: float64 whatever compute_dtype is)
+        s->win_c128 = (c.compute_dtype == APV_F64 || L > APV_MAX_N) ? 1 : 0;
+        const size_t ce = s->win_c128 ? 16 : 8, E = apv_statwin_slot_elems(L);
+        const size_t ring_bytes = (size_t)s->win_T * K * E * ce;
+        for (int z = 0; z < 2; ++z) {
+            if (!(s->zones & (1 << z))) continue;
+            hipError_t e = hipMalloc(&s->win_ring[z], ring_bytes);
+            if (e != hipSuccess) {
+                char buf[192];
+                std::snprintf(buf, sizeof(buf), "statistics window: the ring of %d hops needs %zu bytes per zone program (%d of them): %s",
+                              s->win_T, ring_bytes, nz, hipGetErrorString(e));
+                s->win_ring[z] = nullptr;
+                return apv_fail(h, APV_ERR_HIP, buf);
+            }
+            SCHK(h, hipMemsetAsync(s->win_ring[z], 0, ring_bytes, h->stream));
+            if ((rc = dalloc(h, &s->win_RB[z], (size_t)K * L * L, ce))) return rc;
+            if ((rc = dalloc(h, &s->win_RD[z], (size_t)K * L * L, ce))) return rc;
+            if ((rc = dalloc(h, &s->win_r[z], (size_t)K * L, ce))) return rc;
+        }
+        if ((rc = dalloc(h, &s->win_ctr, 2))) return rc;
+        if (getenv("APV_STAT_WINDOW_TIMING") != nullptr)
+            for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->win_ev[i]));
+    }
     // target filter spectra: rfft of a unit impulse at tap modeling_delay of the A reference loudspeaker
     // (apvast.py:389-390, 418, 422: the same filter serves A_t and B_t)
     std::vector<double> tg((size_t)L * K * 2, 0.0);
@@ -1292,12 +1410,22 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         while (b) { const int t = a % b; a = b; b = t; }
         int per = N / a;
         if (per % 2) per *= 2;
-        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr) ? per : 0;
+        // (the statistics window adds no phase: its ring position is two device words that a kernel of the hop advances.  Timed
+        // statistics launches -- a measuring aid -- run eagerly: their events are read after every hop)
+        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr && !s->win_ev[0]) ? per : 0;
         s->execs.assign(s->period > 0 ? s->period : 0, nullptr);
     }
     s->hop = 0;
     SCHK(h, apv_stft_prepare(N, f64));
     SCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
+int apv_stream_set_stat_hops(apv_handle* h, int32_t n_hops) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_stat_hops: the stream is initialised (the ring of hops is sized there)");
+    if (n_hops < 1 || n_hops > APV_MAX_STAT_HOPS) return apv_fail(h, APV_ERR_ARG, "statistics window: between 1 and 64 hops");
+    h->stat_hops = n_hops;
     return APV_OK;
 }
 
@@ -1343,9 +1471,23 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
     if (!dRB) SCHK(h, hipMalloc(&dRB, mat));
     if (!dRD) SCHK(h, hipMalloc(&dRD, mat));
     if (!dr) SCHK(h, hipMalloc(&dr, vec));
+    if (s->win_T > 1) {
+        // the windowed statistics of the last hop are in device memory: handed out as they are (c64 widened first)
+        const size_t nm = (size_t)K * L * L, nv = (size_t)K * L;
+        hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+        if (s->win_c128) {
+            SCHK(h, hipMemcpyAsync(dRB, s->win_RB[zone], mat, dd, st));
+            SCHK(h, hipMemcpyAsync(dRD, s->win_RD[zone], mat, dd, st));
+            SCHK(h, hipMemcpyAsync(dr, s->win_r[zone], vec, dd, st));
+        } else {
+            SCHK(h, apv_launch_widen_c64(nm, s->win_RB[zone], dRB, st));
+            SCHK(h, apv_launch_widen_c64(nm, s->win_RD[zone], dRD, st));
+            SCHK(h, apv_launch_widen_c64(nv, s->win_r[zone], dr, st));
+        }
+    }
     const void* XB = zone ? s->X[3] : s->X[0];
     const void* XD = zone ? s->X[2] : s->X[1];
-    if (s->xg > 1) {
+    if (s->win_T == 1 && s->xg > 1) {
         // grouped spectra: the correlation kernel reads bin-major slabs, so the two sets are regrouped into scratch first
         void*& dgb = s->stat_ws[8]; void*& dgd = s->stat_ws[9];
         const size_t sb = (size_t)K * s->C * 2 * s->esz;
@@ -1356,7 +1498,8 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         XB = dgb;
         XD = dgd;
     }
-    hipError_t e = L > APV_MAX_N ? apv_launch_corr128(K, M, L, s->f64, XB, XD, s->tspec[zone], (double2*)dRB, (double2*)dRD, (double2*)dr, st)
+    hipError_t e = s->win_T > 1 ? hipSuccess
+                 : L > APV_MAX_N ? apv_launch_corr128(K, M, L, s->f64, XB, XD, s->tspec[zone], (double2*)dRB, (double2*)dRD, (double2*)dr, st)
                  : s->f64 ? apv_launch_corr_c128(K, M, L, (const double2*)XB, (const double2*)XD, (const double2*)s->tspec[zone],
                                                  (double2*)dRB, (double2*)dRD, (double2*)dr, st)
                           : apv_launch_corr(APV_F64, K, M, L, (const float2*)XB, (const float2*)XD, (const float2*)s->tspec[zone], dRB, dRD,
@@ -1377,6 +1520,8 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
             s->stat_spill_bytes = sb;
         }
         p.nV = 1; p.ranks[0] = 1; p.out_c128 = 1; p.n_zones = 1;
+        // a window of fewer than L rows (win_fill_host hops are in it now): not for kernels_gevd64.hip, see win_low_rank
+        p.no_gevd64 = s->win_T > 1 && (long)s->win_fill_host * M < L;
         p.RB = dRB; p.RD = dRD; p.r = dr; p.w = dw; p.lam = dl; p.status = (int32_t*)dst; p.U = dU; p.Lspill = dspill;
         std::string why;
         e = apv_launch_gevd(p, APV_F64, false, st, &why);
@@ -1495,11 +1640,77 @@ int apv_set_mu(apv_handle* h, double mu) {
 //   "w_A" / "w_B"     [K][nV][L] c64|c128        "lambda_A" / "lambda_B" [K][L] f32|f64   (cfg.out_c128)
 //   "fir_correction<p>" [C][P-1]   "target_fir_correction<z>" [M][P-1]   pending correction tails (apv_stream_set_rirs): zeros in a
 //                                  stream that was never updated; handled by apv_live_state
+//   "stat_window<z>" [T][K][2 L^2 + L] complex, "stat_window_fill" int32   the statistics window (apv_stream_set_stat_hops), see win_index
 static int live_index(const char* name) {
     const std::string n(name);
     if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
     if (n.size() == 22 && n.rfind("target_fir_correction", 0) == 0 && (n[21] == '0' || n[21] == '1')) return 4 + n[21] - '0';
     return -1;
+}
+
+// "stat_window<z>" [win_T][K][2 L^2 + L] complex of the ring's precision, slots in the order of age (oldest first, zeros beyond the fill
+// level): 0 / 1; "stat_window_fill" one int32: 2; "stat_window_kernel_ms" {sum, count} of the timed statistics launches
+// (APV_STAT_WINDOW_TIMING, read-only): 3.  Only a stream with a statistics window has them.
+static int win_index(const apv_stream* s, const char* name) {
+    if (s->win_T <= 1) return -1;
+    const std::string n(name);
+    if ((n == "stat_window0" || n == "stat_window1") && s->win_ring[n.back() - '0']) return n.back() - '0';
+    if (n == "stat_window_fill") return 2;
+    if (n == "stat_window_kernel_ms") return 3;
+    return -1;
+}
+
+static size_t win_state_bytes(const apv_stream* s, int j) {
+    if (j == 2) return sizeof(int32_t);
+    if (j == 3) return 2 * sizeof(double);
+    return (size_t)s->win_T * s->K * apv_statwin_slot_elems(s->L) * (s->win_c128 ? 16 : 8);
+}
+
+static int win_state(apv_handle* h, int j, void* h_buf, size_t bytes, bool get) {
+    apv_stream* s = h->st;
+    if (bytes != win_state_bytes(s, j)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+    SCHK(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    SCHK(h, hipStreamSynchronize(st));
+    const int T = s->win_T;
+    if (j == 3) {
+        if (!get) return apv_fail(h, APV_ERR_STATE, "stat_window_kernel_ms is read-only");
+        std::memcpy(h_buf, s->win_ms, sizeof(s->win_ms));
+        return APV_OK;
+    }
+    int32_t ctr[2];
+    SCHK(h, hipMemcpyAsync(ctr, s->win_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
+    SCHK(h, hipStreamSynchronize(st));
+    if (j == 2) {
+        if (get) {
+            *static_cast<int32_t*>(h_buf) = ctr[1];
+            return APV_OK;
+        }
+        // a restored window lies in slots 0 .. fill - 1 (see below): the next hop goes to slot fill mod T
+        const int32_t fill = *static_cast<const int32_t*>(h_buf);
+        if (fill < 0 || fill > T) return apv_fail(h, APV_ERR_STATE, "stat_window_fill out of 0..statistics hops");
+        const int32_t nw[2] = {fill % T, fill};
+        SCHK(h, hipMemcpyAsync(s->win_ctr, nw, sizeof(nw), hipMemcpyHostToDevice, st));
+        SCHK(h, hipStreamSynchronize(st));
+        s->win_fill_host = fill;
+        return APV_OK;
+    }
+    const size_t slot = bytes / T;
+    char* ring = static_cast<char*>(s->win_ring[j]);
+    if (!get) {
+        // slots in the order of age into slots 0, 1, ...: where a ring stands does not enter the window sum
+        SCHK(h, hipMemcpyAsync(ring, h_buf, bytes, hipMemcpyHostToDevice, st));
+        SCHK(h, hipStreamSynchronize(st));
+        return APV_OK;
+    }
+    const int head = ctr[0], fill = ctr[1];
+    std::memset(h_buf, 0, bytes);
+    for (int a = 0; a < fill; ++a) {
+        const int from = ((head - fill + a) % T + T) % T;
+        SCHK(h, hipMemcpyAsync(static_cast<char*>(h_buf) + (size_t)a * slot, ring + (size_t)from * slot, slot, hipMemcpyDeviceToHost, st));
+    }
+    SCHK(h, hipStreamSynchronize(st));
+    return APV_OK;
 }
 
 static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* bytes, int* ring_rows) {
@@ -1532,6 +1743,11 @@ int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
         *bytes = h->st->esz * (size_t)(j < 4 ? h->st->C : h->st->M) * (size_t)std::max(h->st->P - 1, 1);
         return APV_OK;
     }
+    const int wj = win_index(h->st, name);
+    if (wj >= 0) {
+        *bytes = win_state_bytes(h->st, wj);
+        return APV_OK;
+    }
     void* d; int rr;
     return state_lookup(h, name, &d, bytes, &rr);
 }
@@ -1543,6 +1759,7 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
         SCHK(h, hipSetDevice(h->device));
         return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, h_dst, bytes, true, h->stream);
     }
+    if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), h_dst, bytes, true);
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;
@@ -1589,6 +1806,7 @@ int apv_set_state(apv_handle* h, const char* name, const void* h_src, size_t byt
         return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, const_cast<void*>(h_src), bytes, false,
                               h->stream);
     }
+    if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), const_cast<void*>(h_src), bytes, false);
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;

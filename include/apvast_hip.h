@@ -51,6 +51,7 @@ extern "C" {
 #define APV_MAX_RANKS 64     /* number of simultaneously produced ranks V (nV) */
 #define APV_MAX_N 64         /* largest GEVD order n = L of apv_jdiag_batched and of the per-bin kernels that hold the pair on-chip */
 #define APV_MAX_SRCS 128     /* largest n_srcs of a handle: subband orders 65..128 take the packed float64 kernel (kernels_gevd128.hip) */
+#define APV_MAX_STAT_HOPS 64 /* longest statistics window of the subband stream, in hops (apv_stream_set_stat_hops) */
 
 /* status codes */
 #define APV_OK 0
@@ -120,6 +121,19 @@ int  apv_abi_version(void);
  * the new count (w is [K][n][L]).  Refused once apv_stream_init has run: the stream's buffers are sized there.
  *                                                         replaces apvast.py:152-154 */
 int  apv_set_rank_list(apv_handle* h, int32_t n, const int32_t* ranks);
+
+/* Statistics window of the subband stream: every bin's R_B, R_D, r are accumulated over the last n_hops hops,
+ *   R_B[k] = sum_{t < n_hops} X_B^(h-t)[k]^H X_B^(h-t)[k]  (R_D likewise),  r[k] = sum_{t < n_hops} X_B^(h-t)[k]^H d^(h-t)[k],
+ * the per-bin form of the reference's statistics buffer, which spans several blocks (512 samples against a block of 256 with
+ * its example parameters); hops before the first contribute nothing.  n_hops in 1..APV_MAX_STAT_HOPS; 1 (the default) is the
+ * single-block update that never writes R to HBM.  Above 1 every hop's Gram matrices go to a ring of n_hops slots sized by
+ * apv_stream_init (n_hops x zone programs x K x (2 L^2 + L) complex of the compute precision; APV_ERR_HIP with the size in the
+ * message if that cannot be allocated), the window sum feeds the explicit joint diagonalisation of apv_gevd_vast_dev,
+ * apv_stream_get_statistics returns the windowed statistics, and the states "stat_window<z>" [n_hops][K][2 L^2 + L] (slots oldest
+ * first, zero beyond the fill level) and "stat_window_fill" (one int32) carry the window for a resume.  Called between apv_create
+ * and apv_stream_init; refused (APV_ERR_ARG, nothing changed) once the stream is initialised: the ring is sized there.
+ *                                                         replaces: update_statistics' buffer of several blocks, apvast.py:329-364 */
+int  apv_stream_set_stat_hops(apv_handle* h, int32_t n_hops);
 
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
