@@ -27,8 +27,6 @@ namespace {
 
 // ---- float32 pre-solve of the float64 kernel: Householder tridiagonal, Sturm multisection, inverse iteration ----------------
 // (NumPy model with the same steps and counts: tools/probes/tridiag_presolve_model.py)
-// sum over the four lanes of a quad (one matrix row), in all of them
-__device__ __forceinline__ float tp_sum_quad(float v) { v += xcol<1>(v); return v + xcol<2>(v); }
 __device__ __forceinline__ float tp_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 // v of lane `src` (ds_bpermute: a crossbar trip, no LDS storage and no barrier)
 __device__ __forceinline__ float tp_from(float v, int src) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v))); }
@@ -38,11 +36,20 @@ __device__ __forceinline__ float tp_quad_bcast(float v, int j) {
     return __int_as_float(j == 0 ? __builtin_amdgcn_mov_dpp(x, 0x00, 0xf, 0xf, false) : j == 1 ? __builtin_amdgcn_mov_dpp(x, 0x55, 0xf, 0xf, false)
                           : j == 2 ? __builtin_amdgcn_mov_dpp(x, 0xAA, 0xf, 0xf, false) : __builtin_amdgcn_mov_dpp(x, 0xFF, 0xf, 0xf, false));
 }
+// One stage of a cross-lane sum as ONE v_add_f32_dpp (update_dpp with a zero `old` and bound_ctrl is the form the DPP combiner folds
+// into the add; a v_mov_b32_dpp and an add otherwise).  The empty asm statement pins the order and keeps the vectoriser from pairing
+// two chains into a v_pk_add_f32 fed by moves: chains called alternately fill each other's DPP wait states.
+template <int CTRL> __device__ __forceinline__ void tp_dpp_add(float& v) {
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+    asm volatile("" : "+v"(v));
+}
+// sum over the four lanes of a quad (one matrix row), in all of them: quad_perm [1,0,3,2] and [2,3,0,1]
+__device__ __forceinline__ float tp_sum_quad(float v) { tp_dpp_add<0xB1>(v); tp_dpp_add<0x4E>(v); return v; }
 // sum over the sixteen quads of a value every lane of a quad holds, in all lanes, on the VALU: row_ror 8 and 4 inside a 16-lane
 // row, v_permlane16_swap and v_permlane32_swap across rows
 __device__ __forceinline__ float tp_sum_quads(float v) {
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xf, 0xf, false));      // row_ror:8
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x124, 0xf, 0xf, false));      // row_ror:4
+    tp_dpp_add<0x128>(v);                                                                          // row_ror:8
+    tp_dpp_add<0x124>(v);                                                                          // row_ror:4
     const auto r16 = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
     v = __int_as_float((int)r16[0]) + __int_as_float((int)r16[1]);
     const auto r32 = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
@@ -61,107 +68,137 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
                                                    int lane, Cx<float> v32[4], ST stamp = ST()) {
     using CF = Cx<float>;
     const int i = lane >> 2, jq = lane & 3;
-    // ---- 1. Q^H C Q = T, real tridiagonal (LAPACK zhetd2 form: H_k = I - tau v v^H with complex tau and real beta; the last
-    // reflector, k = 14, is a pure phase).  Lane (i, jq) holds A[i][jq + 4 t] and Q[i][jq + 4 t].  The rank-2 updates run on
-    // whole rows: rows and columns <= k only collect garbage that is never read again (v is zero there).
-    CF a[4], q[4];
+    // ---- 1. Q^H C Q = T, Hermitian tridiagonal, by Hermitian reflectors H_k = I - gamma u u^H with a REAL gamma: for the column
+    // x below the diagonal, alpha = x_0, n^2 = ||x||^2, phi = alpha / |alpha| (1 if alpha = 0), u = x but u_0 = alpha + phi ||x||,
+    // gamma = 1 / (n^2 + ||x|| |alpha|) = 2 / ||u||^2.  H_k x = -phi ||x|| e_0: the sub-diagonal of T is complex, and only its
+    // modulus ||x|| goes on (e[k], and e2[k] = n^2 for the Sturm recurrence).  The phases are put back at the end:
+    // diag(delta)^H T diag(delta) is real with delta_0 = 1, delta_{k+1} = -delta_k phi_k, and Q's column m is scaled by delta_m.
+    // u needs no scaling (rows beyond k+1 take the raw column entry) and a column with nothing below alpha no special case
+    // (u_0 = 2 alpha, H_k a sign flip); a zero column gets gamma = 0.
+    // Lane (i, jq) holds A[i][jq + 4 t] and Q[i][jq + 4 t].  The rank-2 updates run on whole rows: rows and columns <= k only
+    // collect garbage that is never read again (u is zero there).
+    f2v a[4], q[4], dq[4];                                                 // dq[t]: delta of column jq + 4 t
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const Cx<TS> c = sA[i * LD + jq + 4 * t];
-        a[t] = mk<float>(scale_to_f32(c.x, sexp), scale_to_f32(c.y, sexp));
-        q[t] = mk<float>((jq + 4 * t == i) ? 1.f : 0.f, 0.f);
+        a[t] = (f2v){scale_to_f32(c.x, sexp), scale_to_f32(c.y, sexp)};
+        q[t] = (f2v){(jq + 4 * t == i) ? 1.f : 0.f, 0.f};
+        dq[t] = (f2v){1.f, 0.f};
     }
-    // The norm of the column below the sub-diagonal and alpha come from row k (its conjugate), which quad k holds: a quad sum and
-    // readlanes.  v and w are formed once per row (quad i) and every lane fetches the entries of its own columns jq + 4 t from quad
-    // jq + 4 t (ds_bpermute: one crossbar trip each, no LDS storage, no barrier); v^H A v is summed over the quads on the VALU.
-    float e[N - 1];                                                        // sub-diagonal (wave-uniform)
+    // u and w are formed once per row (quad i: A[i][k] by a quad broadcast) and every lane fetches the entries of its own columns
+    // jq + 4 t from quad jq + 4 t (ds_bpermute: one crossbar trip each, no LDS storage, no barrier); ||x||^2 and u^H A u are summed
+    // over the quads on the VALU.
+    float e[N - 1], e2[N - 1];                                             // |sub-diagonal| and its square (wave-uniform)
+    float dlr = 1.f, dli = 0.f;                                            // delta_k (the same in every lane)
 #pragma unroll
     for (int k = 0; k < N - 1; ++k) {
-        const int t0 = (k + 1) >> 2;                                       // slots 0 .. t0-1 lie in columns <= k: v is zero there
+        const int t0 = (k + 1) >> 2;                                       // slots 0 .. t0-1 lie in columns <= k: u is zero there
         const int k1 = k + 1, tk = k >> 2, jk = k & 3;
-        float xs = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (t >= t0) xs += (jq + 4 * t > k1) ? fmaf(a[t].x, a[t].x, a[t].y * a[t].y) : 0.f;
-        const float xn2 = tp_lane(tp_sum_quad(xs), 4 * k);
-        const float alr = tp_lane(a[k1 >> 2].x, 4 * k + (k1 & 3)), ali = -tp_lane(a[k1 >> 2].y, 4 * k + (k1 & 3));
         // A[i][k] to every lane of quad i
         const float akx = tp_quad_bcast(a[tk].x, jk), aky = tp_quad_bcast(a[tk].y, jk);
-        // nothing to annihilate: H_k = I (tau = 0 and v = e_{k+1} make the updates below exact no-ops)
-        const bool triv = xn2 == 0.f && ali == 0.f;
-        const float nrm = sqrtf(fmaf(alr, alr, fmaf(ali, ali, xn2)));
-        const float beta = uniform_scalar(triv ? alr : alr >= 0.f ? -nrm : nrm);
-        const float rb = rcp_full(beta);
-        const float taur = uniform_scalar(triv ? 0.f : (beta - alr) * rb), taui = uniform_scalar(triv ? 0.f : -ali * rb);
-        const float dr = alr - beta;
-        const float rdd = rcp_full(fmaf(dr, dr, ali * ali));
-        const float sr = uniform_scalar(triv ? 0.f : dr * rdd), si = uniform_scalar(triv ? 0.f : -ali * rdd);      // 1 / (alpha - beta)
-        e[k] = beta;
-        // v = (0 .. 0, 1, x / (alpha - beta)): v_i in quad i, then this lane's columns from quads jq + 4 t
-        const CF vi = (i > k1) ? mk<float>(akx * sr - aky * si, akx * si + aky * sr) : mk<float>(i == k1 ? 1.f : 0.f, 0.f);
-        CF vj[4];
-        float pr = 0.f, pi = 0.f, ur = 0.f, ui = 0.f;
+        // n^2 and alpha from the very column entries u is made of (row k is their conjugate only up to the rounding of the
+        // updates, and 1e-7 ||A|| is 1e-5 of a small column: H_k would be that far from unitary).  The quads of the rows <= k
+        // add 1e-31 each: e2 is never zero (0 * inf in the Sturm recurrence would be NaN), at no instruction.
+        const float n2 = uniform_scalar(tp_sum_quads((i > k) ? fmaf(akx, akx, aky * aky) : 1e-31f));
+        const float alr = tp_lane(akx, 4 * k1), ali = tp_lane(aky, 4 * k1);
+        // the scalar chain: two v_rsq_f32 and one reciprocal.  1/|alpha| and gamma take a Newton step: errors of 1 ulp in all
+        // three scalars leave H_k unitary to 1e-7 still, but coherently over the whole matrix, and cost 0.2 % of the bench bins
+        // their one-step guard (tridiag_presolve_model.py).  H_k annihilates x exactly whatever ||x|| is taken to be.
+        const float a2 = fmaf(alr, alr, ali * ali);
+        const float nrm = n2 * __builtin_amdgcn_rsqf(n2);
+        const float ra = rsq_full(fmaxf(a2, 1e-36f));
+        const bool pha = a2 > 1e-36f;
+        const float phr = pha ? alr * ra : 1.f, phi = pha ? ali * ra : 0.f;
+        const float gam = n2 > 4e-30f ? rcp_full(fmaf(nrm, a2 * ra, n2)) : 0.f;
+        const float u0r = fmaf(phr, nrm, alr), u0i = fmaf(phi, nrm, ali);
+        e[k] = uniform_scalar(nrm);
+        e2[k] = n2;
+        // u_i in quad i, then this lane's columns from quads jq + 4 t
+        const CF vi = (i > k1) ? mk<float>(akx, aky) : (i == k1) ? mk<float>(u0r, u0i) : mk<float>(0.f, 0.f);
+        f2v vj[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (t < t0) continue;
-            vj[t] = mk<float>(tp_from(vi.x, 4 * (jq + 4 * t)), tp_from(vi.y, 4 * (jq + 4 * t)));
+            vj[t] = (f2v){tp_from(vi.x, 4 * (jq + 4 * t)), tp_from(vi.y, 4 * (jq + 4 * t))};
         }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (t < t0) continue;
-            pr = fmaf(a[t].x, vj[t].x, fmaf(-a[t].y, vj[t].y, pr));       // (A v)_i
-            pi = fmaf(a[t].x, vj[t].y, fmaf(a[t].y, vj[t].x, pi));
-            ur = fmaf(q[t].x, vj[t].x, fmaf(-q[t].y, vj[t].y, ur));       // (Q v)_i
-            ui = fmaf(q[t].x, vj[t].y, fmaf(q[t].y, vj[t].x, ui));
+        // delta_{k+1} = -delta_k phi_k, kept by the lanes that hold column k+1 (off the chain: it fills the permutes' wait)
+        {
+            const float ndr = fmaf(dli, phi, -dlr * phr), ndi = -fmaf(dlr, phi, dli * phr);
+            dlr = ndr; dli = ndi;
+            if (jq == (k1 & 3)) dq[k1 >> 2] = (f2v){dlr, dli};
         }
-        pr = tp_sum_quad(pr); pi = tp_sum_quad(pi); ur = tp_sum_quad(ur); ui = tp_sum_quad(ui);
-        // w = tau A v + kappa v with kappa = -tau/2 (tau A v)^H v = -|tau|^2 / 2 v^H A v (real: A is Hermitian)
-        const float vav = tp_sum_quads(fmaf(pr, vi.x, pi * vi.y));
-        const float kap = -0.5f * fmaf(taur, taur, taui * taui) * vav;
-        const CF wi = mk<float>(fmaf(taur, pr, fmaf(-taui, pi, kap * vi.x)), fmaf(taur, pi, fmaf(taui, pr, kap * vi.y)));
-        const CF tu = mk<float>(taur * ur - taui * ui, taur * ui + taui * ur);              // tau (Q v)_i
-        CF wj[4];
+        // A u and Q u as sums of a[t] u.x and of a[t] u.y (packed, no swap and no negation per slot), put together once
+        f2v px = {0.f, 0.f}, py = {0.f, 0.f}, ux = {0.f, 0.f}, uy = {0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (t < t0) continue;
-            wj[t] = mk<float>(tp_from(wi.x, 4 * (jq + 4 * t)), tp_from(wi.y, 4 * (jq + 4 * t)));
+            const f2v vx = {vj[t].x, vj[t].x}, vy = {vj[t].y, vj[t].y};
+            px = __builtin_elementwise_fma(a[t], vx, px);
+            py = __builtin_elementwise_fma(a[t], vy, py);
+            ux = __builtin_elementwise_fma(q[t], vx, ux);
+            uy = __builtin_elementwise_fma(q[t], vy, uy);
         }
+        float pr = px.x - py.y, pi = px.y + py.x, ur = ux.x - uy.y, ui = ux.y + uy.x;      // (A u)_i, (Q u)_i
+        // four chains, stage by stage
+        tp_dpp_add<0xB1>(pr); tp_dpp_add<0xB1>(pi); tp_dpp_add<0xB1>(ur); tp_dpp_add<0xB1>(ui);
+        tp_dpp_add<0x4E>(pr); tp_dpp_add<0x4E>(pi); tp_dpp_add<0x4E>(ur); tp_dpp_add<0x4E>(ui);
+        // w = p + kappa u with p = gamma A u and kappa = -gamma/2 u^H p (real: A is Hermitian)
+        const float uau = tp_sum_quads(fmaf(pr, vi.x, pi * vi.y));
+        const float kap = -0.5f * gam * gam * uau;
+        const CF wi = mk<float>(fmaf(gam, pr, kap * vi.x), fmaf(gam, pi, kap * vi.y));
+        const f2v tu = {gam * ur, gam * ui};                                                // gamma (Q u)_i
+        f2v wj[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (t < t0) continue;
-            // A -= v w^H + w v^H;  Q -= (tau Q v) v^H
-            a[t].x -= fmaf(vi.x, wj[t].x, fmaf(vi.y, wj[t].y, fmaf(wi.x, vj[t].x, wi.y * vj[t].y)));
-            a[t].y -= fmaf(vi.y, wj[t].x, fmaf(-vi.x, wj[t].y, fmaf(wi.y, vj[t].x, -wi.x * vj[t].y)));
-            q[t].x -= fmaf(tu.x, vj[t].x, tu.y * vj[t].y);
-            q[t].y -= fmaf(tu.y, vj[t].x, -tu.x * vj[t].y);
+            wj[t] = (f2v){tp_from(wi.x, 4 * (jq + 4 * t)), tp_from(wi.y, 4 * (jq + 4 * t))};
+        }
+        const f2v nu = {-vi.x, -vi.y}, nus = {-vi.y, vi.x}, nw = {-wi.x, -wi.y}, nws = {-wi.y, wi.x};
+        const f2v ntu = {-tu.x, -tu.y}, ntus = {-tu.y, tu.x};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (t < t0) continue;
+            // A -= u w^H + w u^H;  Q -= (gamma Q u) u^H
+            const f2v vx = {vj[t].x, vj[t].x}, vy = {vj[t].y, vj[t].y}, wx = {wj[t].x, wj[t].x}, wy = {wj[t].y, wj[t].y};
+            a[t] = __builtin_elementwise_fma(nu, wx, a[t]);
+            a[t] = __builtin_elementwise_fma(nus, wy, a[t]);
+            a[t] = __builtin_elementwise_fma(nw, vx, a[t]);
+            a[t] = __builtin_elementwise_fma(nws, vy, a[t]);
+            q[t] = __builtin_elementwise_fma(ntu, vx, q[t]);
+            q[t] = __builtin_elementwise_fma(ntus, vy, q[t]);
         }
     }
     float d[N];                                                            // diagonal (wave-uniform)
 #pragma unroll
     for (int m = 0; m < N; ++m) d[m] = uniform_scalar(tp_lane(a[m >> 2].x, 4 * m + (m & 3)));
 #pragma unroll
-    for (int t = 0; t < 4; ++t) fQ[i * LDQ + jq + 4 * t] = q[t];        // Q to LDS for the back-transform
+    for (int t = 0; t < 4; ++t) {                                          // Q diag(delta) to LDS for the back-transform
+        const f2v s = __builtin_elementwise_fma((f2v){-q[t].y, q[t].x}, (f2v){dq[t].y, dq[t].y}, q[t] * (f2v){dq[t].x, dq[t].x});
+        fQ[i * LDQ + jq + 4 * t] = mk<float>(s.x, s.y);
+    }
     stamp(4);
 
     // ---- 2. eigenvalue m = i by multisection: lane (i, jq) counts the eigenvalues below lo + (jq + 1) (hi - lo) / 5.  C is positive
     // semi-definite with ||C|| <= ||C||_F, so the spectrum lies in [-1e-3, 1.001] ||C||_F
     const float nrmF = sqrtf(normS2);
-    float e2[N - 1];
-#pragma unroll
-    for (int m = 0; m < N - 1; ++m) e2[m] = uniform_scalar(fmaxf(e[m] * e[m], 1e-30f));     // (0 * inf would be NaN)
     float lo = -1e-3f * nrmF, hi = 1.001f * nrmF;
     const float frac = 0.2f * (float)(jq + 1);
 #pragma unroll 1
     for (int st = 0; st < kTpSteps; ++st) {
         const float x = fmaf(hi - lo, frac, lo);
-        // Sturm count: the negative pivots of T - x I.  A zero pivot gives rcp = inf, the next pivot -inf (counted), rcp(-inf) = -0
+        // Sturm count: the negative pivots of T - x I.  A zero pivot gives rcp = inf, the next pivot -inf (counted), rcp(-inf) = -0.
+        // The sign bit of every pivot is shifted into one word (v_alignbit_b32: one instruction per pivot) and counted once.  It
+        // differs from `qv < 0` on a pivot of -0 only, and a fused -e2 r + (d - x) rounds to -0 only from a negative value that
+        // underflowed (e2 > 0, and d - x is -0 for d = -0, x = +0 alone): the sign bit is the sign of the pivot.  (The NumPy
+        // model has counted sign bits all along.)
         float qv = d[0] - x;
-        int cnt = qv < 0.f;
+        unsigned sg = __float_as_uint(qv) >> 31;
 #pragma unroll
         for (int m = 1; m < N; ++m) {
             qv = fmaf(-e2[m - 1], __builtin_amdgcn_rcpf(qv), d[m] - x);
-            cnt += qv < 0.f;
+            sg = __builtin_amdgcn_alignbit(sg, __float_as_uint(qv), 31);
         }
+        const int cnt = __builtin_popcount(sg);
         // points at or below eigenvalue i raise lo, the others lower hi (monotone in jq: min / max over the quad)
         float nlo = (cnt <= i) ? x : lo, nhi = (cnt <= i) ? hi : x;
         nlo = fmaxf(nlo, xcol<1>(nlo)); nhi = fminf(nhi, xcol<1>(nhi));
