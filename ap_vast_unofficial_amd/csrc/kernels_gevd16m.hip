@@ -56,12 +56,28 @@ __device__ __forceinline__ float tp_sum_quads(float v) {
     return __int_as_float((int)r32[0]) + __int_as_float((int)r32[1]);
 }
 
-constexpr int kTpSteps = 10;            // multisection steps: the interval shrinks 5x per step, 5^-10 ~ 1e-7 of ||C||
+// Multisection steps: the interval [-1e-3, 1.001] ||C|| shrinks 5x per step, to 1.002 * 5^-kTpSteps of ||C||, and the eigenvalue
+// is its midpoint.  The refinement certifies the result whatever the pre-solve delivers, so the multisection stops where the
+// refinement's own guards stop gaining (tools/probes/tridiag_presolve_model.py, 32 768 bench bins; DESIGN 4.1 has the table).
+constexpr int kTpSteps = 9;
+constexpr float tp_pow5_inv(int n) { return n == 0 ? 1.f : 0.2f * tp_pow5_inv(n - 1); }
+// Largest error of a multisection eigenvalue, in units of ||C||: half the final interval plus the float32 floor of the Sturm count
+// and of the interval's re-formed ends.  The floor is taken as 1e-6: over 32 768 bench bins the model's largest error is 7.2e-7 at
+// ten steps, where the interval (half of it 5e-8) no longer matters.  Nine steps: 2.6e-7 + 1e-6 = 1.26e-6 (model: 7.5e-7);
+// eight: 1.28e-6 + 1e-6 = 2.3e-6 (model: 1.7e-6).
+constexpr float kTpLamErr = 0.5f * 1.002f * tp_pow5_inv(kTpSteps) + 1e-6f;
+// Two eigenvalues whose TRUE gap is below 1e-5 ||C|| must not be trusted (see the gate).  Each measured eigenvalue is off by at most
+// kTpLamErr, so a true gap g reads as at most g + 2 kTpLamErr: the measured gap has to exceed 1e-5 + 2 kTpLamErr (nine steps:
+// 1.25e-5, eight: 1.46e-5) before the pair counts as apart.
+constexpr float kTpApart = 1e-5f + 2.f * kTpLamErr;
 constexpr int LDQ = 17, LDX = 17;       // row strides of the float Q and X in the pre-solve's LDS scratch
 
 // In: C (float64, LDS row stride LD) scaled by 2^sexp, normS2 = ||2^sexp C||_F^2.  Scratch: fQ (16 x LDQ complex), fX (16 x LDX
 // real).  Out: V32 (eigenvectors of C in float32, the f32 MFMA accumulator layout: v[t] is element
-// (mfma_row<float>(lane, t), lane & 15)), and whether its spectrum is fit for the one-step refinement (finite, spread < 1e3).
+// (mfma_row<float>(lane, t), lane & 15)), and whether its spectrum is fit for the refinement (finite, spread < 1e3, no two
+// eigenvalues closer than 1e-5 ||C||).  The eigenvalues are good to kTpLamErr ||C|| only: the multisection stops where two
+// inverse-iteration steps and the refinement's guards (|Z| <= 3e-5 for one step, 1e-2 for two) no longer gain from a finer
+// shift.  They come out in ascending order, quad i holding eigenvalue i, which the gate at the end relies on.
 // `stamp` (diagnostic instantiation): slots 4 after the reduction, 13 after the multisection, 14 after the inverse iteration, 5 at the end.
 template <typename TS, typename ST = NoStamp>
 __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, float normS2, Cx<float>* fQ, float* fX,
@@ -185,7 +201,8 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
     const float frac = 0.2f * (float)(jq + 1);
 #pragma unroll 1
     for (int st = 0; st < kTpSteps; ++st) {
-        const float x = fmaf(hi - lo, frac, lo);
+        const float wd = hi - lo;
+        const float x = fmaf(wd, frac, lo);
         // Sturm count: the negative pivots of T - x I.  A zero pivot gives rcp = inf, the next pivot -inf (counted), rcp(-inf) = -0.
         // The sign bit of every pivot is shifted into one word (v_alignbit_b32: one instruction per pivot) and counted once.  It
         // differs from `qv < 0` on a pivot of -0 only, and a fused -e2 r + (d - x) rounds to -0 only from a negative value that
@@ -199,10 +216,14 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
             sg = __builtin_amdgcn_alignbit(sg, __float_as_uint(qv), 31);
         }
         const int cnt = __builtin_popcount(sg);
-        // points at or below eigenvalue i raise lo, the others lower hi (monotone in jq: min / max over the quad)
-        float nlo = (cnt <= i) ? x : lo, nhi = (cnt <= i) ? hi : x;
-        nlo = fmaxf(nlo, xcol<1>(nlo)); nhi = fminf(nhi, xcol<1>(nhi));
-        lo = fmaxf(nlo, xcol<2>(nlo)); hi = fminf(nhi, xcol<2>(nhi));
+        // The points are monotone in jq, so the number nb of the quad's points at or below eigenvalue i places it: the new interval
+        // is the nb-th fifth of the old one.  A quad sum (two v_add_f32_dpp) and three operations; the min / max over the quad of
+        // the points themselves was sixteen instructions (a v_mov_b32_dpp and the canonicalising v_max_f32 of every operand).
+        // The ends are re-formed from lo, to rounding: a fraction of the Sturm count's own error (kTpLamErr's floor).
+        const float nb = tp_sum_quad((cnt <= i) ? 1.f : 0.f);
+        const float w5 = 0.2f * wd;
+        lo = fmaf(nb, w5, lo);
+        hi = lo + w5;
     }
     const float lam = 0.5f * (lo + hi);
     stamp(13);
@@ -253,17 +274,16 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
     stamp(14);
     // eigenvalues closer than 1e-5 ||C|| (none on the bench data) may leave nearly parallel vectors, and the double-sweep fall-back
     // after the refinement only orthonormalises V32: it cannot restore a direction V32 lacks.  Such a bin is not trusted (double
-    // sweeps on C itself), like a rank-deficient one.
-    const float gap = __shfl_down(lam, 4, 64) - lam;
-    const bool apart = i == N - 1 || gap > 1e-5f * nrmF;
-    // spread of the spectrum, as the one-sided solve's gate (any NaN, a non-finite vector or a close pair fails it)
-    float mn = finite ? lam : __int_as_float(0x7fc00000), mx = mn;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        mn = fminf(mn, __shfl_xor(mn, o, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    }
-    const bool ok = !__any(!(mn >= 1e-3f * mx) || !finite || !apart);
+    // sweeps on C itself), like a rank-deficient one.  kTpApart is 1e-5 widened by the multisection's own error.  The gap to the
+    // next eigenvalue is one crossbar trip from quad i + 1 (quad 15 reads quad 0 and does not use it).
+    const float gap = tp_from(lam, (lane + 4) & 63) - lam;
+    const bool apart = i == N - 1 || gap > kTpApart * nrmF;
+    // spread of the spectrum, as the one-sided solve's gate.  Quad i holds eigenvalue i and the multisection delivers them in
+    // ascending order (the Sturm count is one function of x for all quads), so the smallest is quad 0's and the largest quad 15's:
+    // two readlanes, no reduction.  Any NaN, a non-finite vector or a close pair fails the gate: a NaN in quad 0 or 15 fails the
+    // comparison, one anywhere fails `lam == lam` (and leaves its own vector non-finite and its neighbour's gap NaN).
+    const float mn = tp_lane(lam, 0), mx = tp_lane(lam, 63);
+    const bool ok = (mn >= 1e-3f * mx) && !__any(!finite || !apart || !(lam == lam));
     wsync();
 
     // ---- 4. V32 = Q X on the f32 matrix cores (X is real: eight products)

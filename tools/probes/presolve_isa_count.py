@@ -5,7 +5,7 @@ and splits the common path of the function into the three regions of DESIGN 4.1:
 
   Householder reduction       from the first v_sqrt_f32 / v_rsq_f32 after the last f64 MFMA in front of the Sturm loop
                               (the scalar chain of reflector 0) to the head of the Sturm loop
-  Sturm multisection          the body of the one loop that holds the 15 v_rcp_f32 of the recurrence, times its 10 steps
+  Sturm multisection          the body of the one loop that holds the 15 v_rcp_f32 of the recurrence, times its 9 steps
   inverse iteration, gate, QX from the loop's end to the last v_mfma_f32
 
 and prints VGPRs, spills, scratch, LDS and, per region, the VALU count (every v_* but the MFMAs), s_nop, other SALU, ds_bpermute
@@ -24,7 +24,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(ROOT, "ap_vast_unofficial_amd", "csrc", "kernels_gevd16m.hip")
 KERNEL = "gevd16m_kernel_f64ILb1E15HIP_vector_typeIfLj2EELb0EE"      # <true, float2, false>
-STEPS = 10                                                              # kTpSteps
+STEPS = 9                                                               # kTpSteps
 
 
 def compile_asm(path):

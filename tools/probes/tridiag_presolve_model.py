@@ -11,10 +11,12 @@ over bins and in the kernel's order of operations:
      bins inside the one-step guard falls from 99.70 % to 99.53 %;
   2. eigenvalues by Sturm-count multisection: NPTS points per eigenvalue per step (the interval shrinks NPTS + 1 times),
      NSTEP steps, q_i = (a_i - x) - e_{i-1}^2 rcp(q_{i-1}); the kernel runs 4 points (four lanes, one count each) and
-     10 steps.  8 points (two interleaved counts per lane) and 7 steps give the same guard pass rates here, 6 steps do not;
+     NSTEP_KERNEL steps (the refinement that follows certifies the result: DESIGN 4.1 has the pass rates of 6 to 10 steps);
   3. eigenvectors by two inverse-iteration steps on T - lam I, unpivoted L D L^T (the Sturm recurrence at the shift), start
      vector ones + e_m, normalised after each step;
-     eigenvalues closer than 1e-5 ||C|| (none on the bench data) send the bin to the double sweeps in the kernel;
+     two neighbouring eigenvalues whose MEASURED gap is not above apart_threshold(NSTEP) ||C|| send the bin to the double
+     sweeps in the kernel (none on the bench data): 1e-5 widened by twice the multisection's own error, so that every pair
+     whose true gap is under 1e-5 ||C|| goes there.  `trust` below carries this gate and the spread gate;
   4. V32 = Q X.
 
 It prints the share of bins whose refinement matrix Z_ij = (S_ij - d_j E_ij) / (d_j - d_i), taken in float64 against the
@@ -31,6 +33,18 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 f32 = np.float32
 N = 16
+NSTEP_KERNEL = 9                    # kTpSteps of kernels_gevd16m.hip
+
+
+def lam_err(nstep):
+    """kTpLamErr: half the final interval of the multisection (1.002 * 5^-nstep) plus the float32 floor of the Sturm count, taken as 1e-6
+    (the largest error at ten steps, where the interval no longer matters, is 7.2e-7 on the bench bins)."""
+    return 0.5 * 1.002 * 5.0 ** -nstep + 1e-6
+
+
+def apart_threshold(nstep):
+    """kTpApart, in units of ||C||"""
+    return 1e-5 + 2 * lam_err(nstep)
 
 
 def make_C(K, seed=1234, reg=1e-7):
@@ -115,9 +129,10 @@ def multisection(a, e2, nrm, nstep, npts=4):
         c = sturm_count(a, e2, pts.reshape(K, -1)).reshape(K, N, npts)
         below = c <= m[None, :, None]                                   # eigenvalue m lies above this point
         nb = below.sum(2)                                               # points at or below lam_m (monotone)
-        new_lo = np.where(nb > 0, np.take_along_axis(pts, np.maximum(nb - 1, 0)[:, :, None], 2)[:, :, 0], lo)
-        new_hi = np.where(nb < npts, np.take_along_axis(pts, np.minimum(nb, npts - 1)[:, :, None], 2)[:, :, 0], hi)
-        lo, hi = new_lo.astype(f32), new_hi.astype(f32)
+        # the kernel's form: the nb-th of the npts + 1 parts of the old interval, its ends re-formed from lo
+        wp = (f32(1 / (npts + 1)) * (hi - lo)).astype(f32)
+        lo = (lo + nb.astype(f32) * wp).astype(f32)
+        hi = (lo + wp).astype(f32)
     return ((lo + hi) * f32(0.5)).astype(f32)
 
 
@@ -160,7 +175,11 @@ def presolve(C, nstep, npts=4, rng=None):
     X = inverse_iteration(a, e, lam, nrm)
     Q = (Q * delta[:, None, :]).astype(np.complex64)                    # the phases go back into Q's columns
     V = (Q @ X.astype(np.complex64)).astype(np.complex64)
-    trust = lam.min(1) >= 1e-3 * lam.max(1)
+    # the kernel's gate: spread under 1e3 (smallest and largest are eigenvalue 0 and 15: they come out sorted), every
+    # neighbouring pair apart, nothing NaN
+    with np.errstate(invalid="ignore"):
+        apart = (np.diff(lam, axis=1) > f32(apart_threshold(nstep)) * nrm[:, None]).all(1)
+        trust = (lam[:, 0] >= f32(1e-3) * lam[:, -1]) & apart & np.isfinite(X).all((1, 2)) & ~np.isnan(lam).any(1)
     return V, lam, trust, (a, e, Q, A)
 
 
@@ -180,7 +199,7 @@ def zmax(C, V):
 
 def main():
     K = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
-    nstep = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    nstep = int(sys.argv[2]) if len(sys.argv) > 2 else NSTEP_KERNEL
     npts = int(sys.argv[3]) if len(sys.argv) > 3 else 4
     C = make_C(K)
     V, lam, trust, (a, e, Q, A) = presolve(C, nstep, npts, np.random.default_rng(7) if os.environ.get("ULP_NOISE", "1") != "0" else None)
@@ -200,7 +219,9 @@ def main():
     print(f"eigenvalues: max |lam - lam_ref| / ||C|| = {(np.abs(np.sort(lam, 1) / sc[:, None] - lref).max(1) * sc / nrm).max():.2e}")
     z = zmax(C, V)
     t = trust
-    print(f"trusted {t.mean() * 100:.2f} %")
+    gaps = np.diff(lref, axis=1).min(1) / np.sqrt((np.abs(C) ** 2).sum((1, 2)))
+    print(f"trusted {t.mean() * 100:.2f} % (spread < 1e3 and measured gaps > {apart_threshold(nstep):.3g} ||C||; smallest true gap {gaps.min():.2e} ||C||, "
+          f"{(gaps < 1e-5).sum()} bins under 1e-5, {(~t & (gaps >= 1e-5)).sum()} untrusted above it)")
     print(f"|Z| <= 3e-5: {(z[t] <= 3e-5).mean() * 100:.2f} % of trusted bins, <= 1e-2: {(z[t] <= 1e-2).mean() * 100:.3f} %")
     print(f"max |Z| median / p99 / max: {np.median(z[t]):.2e} / {np.quantile(z[t], 0.99):.2e} / {z[t].max():.2e}")
 
