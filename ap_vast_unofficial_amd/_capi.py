@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -142,6 +142,7 @@ def load():
     lib.apv_bb_set_rank_list.argtypes = [vp, i32, vp]
     lib.apv_set_rank_list.argtypes = [vp, i32, vp]
     lib.apv_stream_set_stat_hops.argtypes = [vp, i32]
+    lib.apv_stream_set_stat_forgetting.argtypes = [vp, C.c_double]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -215,7 +216,7 @@ class Engine:
     def __init__(self, n_bins, n_srcs, n_mics, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=None,
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
-                 out_layout=0, stat_hops=1):
+                 out_layout=0, stat_hops=1, stat_forgetting=None):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -262,11 +263,19 @@ class Engine:
         self.stat_hops = 1
         if int(stat_hops) != 1:
             self.set_stat_hops(stat_hops)
+        self.stat_forgetting = None
+        if stat_forgetting is not None:
+            self.set_stat_forgetting(stat_forgetting)
 
     def set_stat_hops(self, n_hops):
         """Statistics window of the subband stream, in hops (1..MAX_STAT_HOPS), before stream_init (apv_stream_set_stat_hops)."""
         self._chk(self.lib.apv_stream_set_stat_hops(self.h, int(n_hops)))
         self.stat_hops = int(n_hops)
+
+    def set_stat_forgetting(self, beta):
+        """Forgetting factor in (0, 1] of the subband stream's statistics, before stream_init (apv_stream_set_stat_forgetting)."""
+        self._chk(self.lib.apv_stream_set_stat_forgetting(self.h, float(beta)))
+        self.stat_forgetting = float(beta)
 
     def set_rank_list(self, ranks):
         """Replace the handle's rank list (ascending, each 1..n_srcs, at most n_srcs of them) before stream_init: the way to

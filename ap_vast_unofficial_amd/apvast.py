@@ -26,7 +26,11 @@ What is different (keyword-only, after ``perceptual``)
     statistics buffer of several blocks (apvast.py:329-364).  ``statistics_hops="auto"`` takes T from
     ``statistics_buffer_length``: the whole blocks that many samples span, max(1, 1 + (S - N) // hop_size); the default 1
     keeps the single-block update (``filter_length`` is accepted and stored, not used; ``statistics_buffer_length`` is
-    used by ``"auto"`` only).  With T > 1 the attributes R_*, r_*, U_*, lambda_* are those of the window.  ``dtype="f64"`` (default) runs every stage in
+    used by ``"auto"`` only).  With T > 1 the attributes R_*, r_*, U_*, lambda_* are those of the window.
+    ``statistics_forgetting=beta``, a float in (0, 1], is the recursive estimate instead: R_B[k] <- beta R_B[k] + X_B[k]^H X_B[k]
+    per hop, likewise R_D and r, from zero before the first hop (1.0 accumulates every hop); one smoothing constant, no hard
+    edge when a hop leaves, and memory that does not grow with the averaging time.  Fixed at construction; ``None`` (default)
+    is off; it excludes ``statistics_hops > 1``, and R_*, r_*, U_*, lambda_* are then the running sums'.  ``dtype="f64"`` (default) runs every stage in
     float64 like the reference's lfilter / rfft / irfft (apvast.py:171-192, 202-203, 461-496); ``"f32"`` runs every
     stage in float32; ``"mixed"`` keeps the float32 FIR / STFT / overlap-add around a float64 joint diagonalisation.
     Up to 128 loudspeakers: above 64 the per-bin joint diagonalisation runs in float64 whatever ``dtype`` is
@@ -124,6 +128,7 @@ class apvast:
                  fullscale_db_spl: float = 94.0,
                  max_sweeps: int = 0,
                  sweep_tol2: float = 0.0,
+                 statistics_forgetting=None,
                  statistics_hops=1):
         self.block_size = block_size
         self.filter_length = filter_length
@@ -158,6 +163,7 @@ class apvast:
         self.hop_size = hop_size if hop_size else self.block_size // 2        # apvast.py:93
         self.statistics_hops = self._resolve_statistics_hops(statistics_hops, statistics_buffer_length, block_size,
                                                              self.hop_size, mode)
+        self.statistics_forgetting = self._check_statistics_forgetting(statistics_forgetting, self.statistics_hops, mode)
         self.window = np.sin(np.pi / self.block_size * np.arange(self.block_size)).reshape(-1, 1)   # apvast.py:94
         self.rir_length, self.number_of_srcs, self.number_of_mics = rir_A.shape  # apvast.py:97-99
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
@@ -182,7 +188,7 @@ class apvast:
                                  block_size=N, hop_size=H, n_zones=zones, frontend="f32" if dtype == "mixed" else None,
                                  max_sweeps=self._max_sweeps, sweep_tol2=sweep_tol2,
                                  out_layout=1,     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
-                                 stat_hops=self.statistics_hops)
+                                 stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -224,6 +230,19 @@ class apvast:
         if mode == "broadband" and int(value) > 1:
             raise ValueError("statistics_hops > 1 is a subband keyword: broadband mode averages over statistics_buffer_length samples")
         return int(value)
+
+    @staticmethod
+    def _check_statistics_forgetting(value, statistics_hops, mode):
+        """statistics_forgetting as None (off) or a float in (0, 1]."""
+        if value is None:
+            return None
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not 0.0 < float(value) <= 1.0:
+            raise ValueError("statistics_forgetting must be None or a number in (0, 1]")       # (NaN fails the comparison)
+        if mode == "broadband":
+            raise ValueError("statistics_forgetting is a subband keyword: broadband mode averages over statistics_buffer_length samples")
+        if statistics_hops > 1:
+            raise ValueError("statistics_forgetting and statistics_hops > 1 exclude each other: one estimator per stream")
+        return float(value)
 
     # ---- responses and mu, reassignable between hops (the reference reads them on every hop, apvast.py:161, 167-193) ----
     def _init_responses(self, rir_A, rir_B):
@@ -572,6 +591,7 @@ class apvast:
     _SB_STATE = ("response", "target_response", "input_block", "input_history", "out_overlap")
     _LIVE_STATE = ("fir_correction", "target_fir_correction")       # present once a response update has been applied
     _WIN_STATE = ("statistics_window", "statistics_window_fill")    # present with statistics_hops > 1
+    _FORGET_STATE = ("statistics_forgetting_sums",)                  # present with statistics_forgetting set
 
     def get_state(self):
         """Everything the next hop depends on (the reference's instance attributes of apvast.py:115-151), as float64 arrays
@@ -582,7 +602,9 @@ class apvast:
         With ``statistics_hops = T > 1`` also the window: ``statistics_window`` (zone programs that run, T, K, 2 L^2 + L) complex128
         -- per hop and bin [R_B (lower triangle) | R_D (lower triangle) | r] of that hop alone, hops oldest first, zeros beyond the
         fill level -- and ``statistics_window_fill``, the number of hops it holds (it fills during the first T - 1 hops).  Both are
-        absent when T = 1.  R_*, r_*, U_*, lambda_* are what the last hop of THIS object left on the device: they follow a restored
+        absent when T = 1.  With ``statistics_forgetting`` set, the running sums instead: ``statistics_forgetting_sums`` (zone
+        programs that run, K, 2 L^2 + L), per bin [R_B (lower triangle) | R_D (lower triangle) | r], complex128 (complex64 with
+        ``dtype="f32"`` up to 64 loudspeakers: the precision they are kept in); absent otherwise.  R_*, r_*, U_*, lambda_* are what the last hop of THIS object left on the device: they follow a restored
         window from the next hop on, not from set_state."""
         st = self._get_state()
         if self.mode == "subband" and self.statistics_hops > 1:
@@ -591,6 +613,10 @@ class apvast:
             st["statistics_window"] = np.stack([e.get_state(f"stat_window{z}", (T, self._K, 2 * L * L + L), e.stat_dtype)
                                                 for z in zs]).astype(np.complex128)
             st["statistics_window_fill"] = int(e.get_state("stat_window_fill", (1,), np.int32)[0])
+        if self.mode == "subband" and self.statistics_forgetting is not None:
+            e, L = self._eng, self.number_of_srcs
+            st["statistics_forgetting_sums"] = np.stack([e.get_state(f"stat_forget{z}", (self._K, 2 * L * L + L), e.stat_dtype)
+                                                         for z, run in enumerate((self.run_A, self.run_B)) if run])
         if self._live_applied:
             P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
             Q = max(P - 1, 1)
@@ -637,6 +663,8 @@ class apvast:
         known = (self._BB_STATE if self.mode == "broadband" else self._SB_STATE) + self._LIVE_STATE
         if self.mode == "subband" and self.statistics_hops > 1:
             known = known + self._WIN_STATE
+        if self.mode == "subband" and self.statistics_forgetting is not None:
+            known = known + self._FORGET_STATE
         unknown = sorted(set(state) - set(known))
         if unknown:
             raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
@@ -649,6 +677,14 @@ class apvast:
                 raise ValueError(f"statistics_window must have shape {(len(zs), T, self._K, 2 * L * L + L)}, got {win.shape}")
             for i, z in enumerate(zs):
                 e.set_state(f"stat_window{z}", np.ascontiguousarray(win[i], dtype=e.stat_dtype))
+        if "statistics_forgetting_sums" in state:
+            L = self.number_of_srcs
+            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
+            sums = np.asarray(state["statistics_forgetting_sums"])
+            if sums.shape != (len(zs), self._K, 2 * L * L + L):
+                raise ValueError(f"statistics_forgetting_sums must have shape {(len(zs), self._K, 2 * L * L + L)}, got {sums.shape}")
+            for i, z in enumerate(zs):
+                e.set_state(f"stat_forget{z}", np.ascontiguousarray(sums[i], dtype=e.stat_dtype))
         if "statistics_window_fill" in state:
             e.set_state("stat_window_fill", np.array([int(state["statistics_window_fill"])], dtype=np.int32))
         if any(k in state for k in self._LIVE_STATE):

@@ -86,6 +86,7 @@ struct apv_handle {
     struct apv_bb* bb;       // broadband streaming state (apv_bb_init), owned
     std::vector<int32_t> rank_list;  // the subband rank list: cfg.ranks, or apv_set_rank_list's (cfg.n_ranks entries, up to n_srcs)
     int stat_hops;                   // apv_stream_set_stat_hops: statistics window of the next apv_stream_init, in hops (<= 1: one block)
+    double stat_forgetting;          // apv_stream_set_stat_forgetting: forgetting factor of the next apv_stream_init in (0, 1]; 0: off
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -216,6 +217,11 @@ size_t apv_statwin_slot_elems(int L);         // complex elements of one bin's r
 hipError_t apv_launch_statwin(int x_c128, int acc_f64, int K, int M, int L, int T, int zones, const void* const* XB,
                               const void* const* XD, const void* const* d, void* const* ring, void* const* RB, void* const* RD,
                               void* const* r, int32_t* ctr, hipStream_t s);
+// ... and with exponential forgetting: acc <- beta acc + (the hop's Gram matrices) in ONE slot per zone program, the new sums
+// into RB / RD / r.  One launch, no counters.
+hipError_t apv_launch_statforget(int x_c128, int acc_f64, int K, int M, int L, double beta, int zones, const void* const* XB,
+                                 const void* const* XD, const void* const* d, void* const* acc, void* const* RB, void* const* RD,
+                                 void* const* r, hipStream_t s);
 hipError_t apv_launch_widen_c64(size_t count, const void* in, void* out, hipStream_t s);     // c64 -> c128
 
 // kernels_stft.hip

@@ -229,6 +229,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     h->st = nullptr;
     h->bb = nullptr;
     h->stat_hops = 1;
+    h->stat_forgetting = 0.0;
     h->gl_ws = nullptr;
     h->gl_tol2 = 0.0;
     h->gl_lead_rank = 0;

@@ -9,6 +9,10 @@
 //   statwin_advance  one thread: head <- (head + 1) mod T, fill <- min(fill + 1, T).  The two words live in device memory, so a
 //                    captured hop graph replays unchanged whatever the ring's phase is.
 //
+//   statforget_kernel  the same Gram matrices, added to ONE slot that forgets exponentially (apv_stream_set_stat_forgetting):
+//                    R <- beta R + G, r <- beta r + g, one fma per real and per imaginary part by the lane that owns the
+//                    element; the new sums go back to the slot and, full, to the explicit-statistics arrays.  No counters.
+//
 // Ring slot of one bin: [R_B: L x L][R_D: L x L][r: L] complex of the compute precision; a zone program's ring is [T][K][slot].
 // Only the lower triangle of a matrix is kept in the ring (tiles on and below the diagonal; inside a diagonal tile the elements
 // with j <= i); the sums are written out full, the upper triangle as the conjugate of the lower, the diagonal real.
@@ -69,21 +73,45 @@ __device__ __forceinline__ C window_sum(C* __restrict__ ring, size_t slot_stride
     return s;
 }
 
-// grid (K, 2 matrices, zone programs); every wave of the workgroup takes tiles wave, wave + n_waves, ... of the lower triangle
-template <typename XT, typename T>
-__global__ void __launch_bounds__(256) statwin_kernel(const StatWinArgs a) {
+// what statwin_kernel does with an element of the hop's Gram matrices: the window sum over the ring, see window_sum
+template <typename C, typename T>
+struct WindowUpdate {
+    C* __restrict__ ring;
+    size_t slot_stride;
+    int head, nold, Tn;
+    __device__ __forceinline__ C operator()(size_t idx, T gx, T gy) const {
+        return window_sum<C, T>(ring, slot_stride, idx, head, nold, Tn, gx, gy);
+    }
+};
+
+// ... and what statforget_kernel does: acc <- beta acc + g, real and imaginary part each one fma
+template <typename C, typename T>
+struct ForgetUpdate {
+    C* __restrict__ acc;
+    T beta;
+    __device__ __forceinline__ C operator()(size_t idx, T gx, T gy) const {
+        const C old = acc[idx];
+        C s;
+        s.x = fma(beta, old.x, gx); s.y = fma(beta, old.y, gy);
+        acc[idx] = s;
+        return s;
+    }
+};
+
+// The hop's Gram matrix of block (k = blockIdx.x, which = blockIdx.y, z = blockIdx.z) in 16 x 16 tiles on the matrix cores; every
+// wave of the workgroup takes tiles wave, wave + n_waves, ... of the lower triangle.  Each element (and each entry of g = X_B^H d,
+// from the tiles of column 0) goes through `upd` (index inside the zone program's slot, value) -> the statistic to write out.
+template <typename XT, typename T, typename Upd>
+__device__ __forceinline__ void gram_tiles(const StatWinArgs& a, const Upd& upd) {
     using MM = Mma<T>;
     using C = typename MM::cplx;
     const int k = blockIdx.x, which = blockIdx.y, z = blockIdx.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
     const int c = lane & 15, h = lane >> 4;
-    const int L = a.L, M = a.M, Tn = a.T;
-    const int head = a.ctr[0], fill = a.ctr[1];
-    const int nold = fill < Tn - 1 ? fill : Tn - 1;         // a full ring: the slot at `head` is the oldest and leaves the window
-    const size_t E = 2 * (size_t)L * L + L, slot_stride = (size_t)a.K * E;
+    const int L = a.L, M = a.M;
+    const size_t E = 2 * (size_t)L * L + L;
     const XT* __restrict__ X = reinterpret_cast<const XT*>(which ? a.XD[z] : a.XB[z]) + (size_t)k * M * L;
     const XT* __restrict__ dv = reinterpret_cast<const XT*>(a.d[z]) + (size_t)k * M;
-    C* __restrict__ ring = reinterpret_cast<C*>(a.ring[z]);
     C* __restrict__ R = reinterpret_cast<C*>(which ? a.RD[z] : a.RB[z]) + (size_t)k * L * L;
     C* __restrict__ rr = reinterpret_cast<C*>(a.r[z]) + (size_t)k * L;
     const size_t mat0 = (size_t)k * E + (which ? (size_t)L * L : 0), vec0 = (size_t)k * E + 2 * (size_t)L * L;
@@ -114,7 +142,7 @@ __global__ void __launch_bounds__(256) statwin_kernel(const StatWinArgs a) {
         auto emit = [&](int t, T gx, T gy) {
             const int i = 16 * ta + MM::row(h, t), j = ib;
             if (i >= L || j >= L || j > i) return;            // (j > i: upper part of a diagonal tile, mirrored from the lower)
-            const C s = window_sum<C, T>(ring, slot_stride, mat0 + (size_t)i * L + j, head, nold, Tn, gx, i == j ? (T)0 : gy);
+            const C s = upd(mat0 + (size_t)i * L + j, gx, i == j ? (T)0 : gy);
             R[(size_t)i * L + j] = s;
             if (i != j) R[(size_t)j * L + i] = MM::make(s.x, -s.y);
         };
@@ -125,9 +153,26 @@ __global__ void __launch_bounds__(256) statwin_kernel(const StatWinArgs a) {
         if (want_r) {
             rx += __shfl_xor(rx, 16, 64); ry += __shfl_xor(ry, 16, 64);
             rx += __shfl_xor(rx, 32, 64); ry += __shfl_xor(ry, 32, 64);
-            if (h == 0 && oka) rr[ia] = window_sum<C, T>(ring, slot_stride, vec0 + ia, head, nold, Tn, rx, ry);
+            if (h == 0 && oka) rr[ia] = upd(vec0 + ia, rx, ry);
         }
     }
+}
+
+// grid (K, 2 matrices, zone programs)
+template <typename XT, typename T>
+__global__ void __launch_bounds__(256) statwin_kernel(const StatWinArgs a) {
+    using C = typename Mma<T>::cplx;
+    const int Tn = a.T, head = a.ctr[0], fill = a.ctr[1];
+    const int nold = fill < Tn - 1 ? fill : Tn - 1;         // a full ring: the slot at `head` is the oldest and leaves the window
+    const size_t slot_stride = (size_t)a.K * (2 * (size_t)a.L * a.L + a.L);
+    gram_tiles<XT, T>(a, WindowUpdate<C, T>{reinterpret_cast<C*>(a.ring[blockIdx.z]), slot_stride, head, nold, Tn});
+}
+
+// the same grid; a.ring[z] is the one accumulator slot [K][2 L L + L], a.T and a.ctr are not read
+template <typename XT, typename T>
+__global__ void __launch_bounds__(256) statforget_kernel(const StatWinArgs a, const T beta) {
+    using C = typename Mma<T>::cplx;
+    gram_tiles<XT, T>(a, ForgetUpdate<C, T>{reinterpret_cast<C*>(a.ring[blockIdx.z]), beta});
 }
 
 __global__ void statwin_advance_kernel(int32_t* __restrict__ ctr, int Tn) {
@@ -173,6 +218,31 @@ hipError_t apv_launch_statwin(int x_c128, int acc_f64, int K, int M, int L, int 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(statwin_advance_kernel, dim3(1), dim3(64), 0, s, ctr, T);
+    return hipGetLastError();
+}
+
+// One hop of an exponentially forgetting stream: R <- beta R + G in the accumulators `acc` [K][2 L L + L], the new sums into
+// RB / RD / r.  The arguments are apv_launch_statwin's, without a window length and without counters.
+hipError_t apv_launch_statforget(int x_c128, int acc_f64, int K, int M, int L, double beta, int zones, const void* const* XB,
+                                 const void* const* XD, const void* const* d, void* const* acc, void* const* RB, void* const* RD,
+                                 void* const* r, hipStream_t s) {
+    if (K <= 0) return hipSuccess;
+    if (L < 1 || L > APV_MAX_SRCS || M < 1 || !(beta > 0.0 && beta <= 1.0) || zones < 1 || zones > 2) return hipErrorInvalidValue;
+    StatWinArgs a{};
+    a.K = K; a.M = M; a.L = L; a.T = 1; a.NT = (L + 15) / 16;
+    for (int z = 0; z < zones; ++z) {
+        a.XB[z] = XB[z]; a.XD[z] = XD[z]; a.d[z] = d[z];
+        a.ring[z] = acc[z]; a.RB[z] = RB[z]; a.RD[z] = RD[z]; a.r[z] = r[z];
+    }
+    const int n_tiles = a.NT * (a.NT + 1) / 2;
+    const dim3 grid(K, 2, zones), block(64 * (n_tiles < 4 ? n_tiles : 4));
+    if (acc_f64) {
+        if (x_c128) hipLaunchKernelGGL((statforget_kernel<double2, double>), grid, block, 0, s, a, beta);
+        else hipLaunchKernelGGL((statforget_kernel<float2, double>), grid, block, 0, s, a, beta);
+    } else {
+        if (x_c128) hipLaunchKernelGGL((statforget_kernel<double2, float>), grid, block, 0, s, a, (float)beta);
+        else hipLaunchKernelGGL((statforget_kernel<float2, float>), grid, block, 0, s, a, (float)beta);
+    }
     return hipGetLastError();
 }
 

@@ -130,6 +130,10 @@ struct apv_stream {
     int win_fill_host;            // the host's copy of fill (hops in the window before the next one), kept in step by run_hop and by
                                   // the state "stat_window_fill".  Only win_low_rank reads it (which KERNEL solves an order-64 hop):
                                   // the ring position itself never enters a launch from the host
+    // exponentially forgetting statistics (apv_stream_set_stat_forgetting): R <- fg_beta R + G per hop.  win_T stays 1; the
+    // accumulator is the one slot win_ring[z] [K][2 L^2 + L], and win_c128, win_RB / win_RD / win_r, win_ev / win_ms serve as above
+    double fg_beta;               // 0: off
+    int fg_no_gevd64;             // GevdParams::no_gevd64 of every hop and of apv_stream_get_statistics: see apv_stream_init
     hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
     double win_ms[2];             // ... and {sum of its times in ms, hops timed}
     std::vector<hipGraphExec_t> execs;
@@ -280,6 +284,9 @@ static HopSpectra hop_spectra(const apv_stream* s, int set) {
     return q;
 }
 
+// the hop forms R_B, R_D, r explicitly (window or forgetting) and the joint diagonalisation reads them: not the fused update
+static inline bool explicit_stats(const apv_stream* s) { return s->win_T > 1 || s->fg_beta > 0.0; }
+
 // Will the next hop's window hold fewer rows than the order of its pencils (fill phase of a stream with M < L, or T M < L
 // throughout) AND would its solve go to kernels_gevd64.hip (order 64, float64 statistics)?  R_B and R_D then have rank below L,
 // which that kernel does not solve (GevdParams::no_gevd64): such a hop takes the LDS kernel, and the un-captured launch sequence,
@@ -425,9 +432,10 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
     std::string why;
     // per-bin update per zone program: A: bright A->A, dark A->B, target A;  B: bright B->B, dark B->A, target B
     int oc = 0;     // output channel cursor
-    if (s->win_T > 1) {
+    if (explicit_stats(s)) {
         // statistics over the last win_T hops: this hop's Gram matrices into the ring and the window sums in one launch for both
-        // zone programs, then the joint diagonalisation from explicit R_B, R_D, r (the launch apv_gevd_vast_dev makes), per zone
+        // zone programs (forgetting: beta x accumulator + Gram matrices, likewise one launch), then the joint diagonalisation from
+        // explicit R_B, R_D, r (the launch apv_gevd_vast_dev makes), per zone
         const void *xb[2], *xd[2], *dd[2];
         void *ring[2], *RB[2], *RD[2], *rr[2];
         int zlist[2], nz = 0;
@@ -438,7 +446,8 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
             zlist[nz++] = z;
         }
         if (s->win_ev[0]) SCHK(h, hipEventRecord(s->win_ev[0], st));
-        SCHK(h, apv_launch_statwin(f64, s->win_c128, K, s->M, L, s->win_T, nz, xb, xd, dd, ring, RB, RD, rr, s->win_ctr, st));
+        if (s->fg_beta > 0.0) SCHK(h, apv_launch_statforget(f64, s->win_c128, K, s->M, L, s->fg_beta, nz, xb, xd, dd, ring, RB, RD, rr, st));
+        else SCHK(h, apv_launch_statwin(f64, s->win_c128, K, s->M, L, s->win_T, nz, xb, xd, dd, ring, RB, RD, rr, s->win_ctr, st));
         if (s->win_ev[1]) SCHK(h, hipEventRecord(s->win_ev[1], st));
         for (int i = 0; i < nz; ++i) {
             const int z = zlist[i];
@@ -446,7 +455,7 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
             p.RB = s->win_RB[z]; p.RD = s->win_RD[z]; p.r = s->win_r[z];
             p.w = wz[z]; p.lam = lamz[z]; p.status = ostatus[z];
             p.n_zones = 1;
-            p.no_gevd64 = win_low_rank(h);
+            p.no_gevd64 = s->fg_beta > 0.0 ? s->fg_no_gevd64 : win_low_rank(h);
             if (sch.lspill) p.Lspill = sch.lspill;
             hipError_t e = apv_launch_gevd(p, s->win_c128 ? APV_F64 : APV_F32, false, st, &why, h->rank_list.data());
             if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
@@ -763,7 +772,7 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     if (!s) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
     if (n_hops < 0) return apv_fail(h, APV_ERR_ARG, "n_hops must be >= 0");
     if (n_hops == 0) return APV_OK;
-    if (s->win_T > 1) return process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    if (explicit_stats(s)) return process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
     // K1 as one fast-convolution segment (responses of 64 taps or more): a chunk of hops per launch (below); direct-form K1 (shorter
     // responses, APV_FIR_DIRECT) and partitioned K1 keep the hop-by-hop pipeline of this function
     if (s->fir_F > 0 && s->fir_np == 1) return process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
@@ -1267,8 +1276,9 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     s->out_group = c.out_layout == 1 ? s->L : 0;
     s->Kp = (s->K + 7) / 8 * 8;
     s->win_T = h->stat_hops > 1 ? h->stat_hops : 1;
-    // (a windowed stream does not launch the fused kernel that reads grouped spectra: its slabs stay bin-major)
-    s->xg_default = s->win_T > 1 ? 1 : apv_gevd_reads_groups(apv_base_params(h), h->cfg.compute_dtype, f64 != 0);
+    s->fg_beta = h->stat_forgetting;
+    // (a windowed or forgetting stream does not launch the fused kernel that reads grouped spectra: its slabs stay bin-major)
+    s->xg_default = explicit_stats(s) ? 1 : apv_gevd_reads_groups(apv_base_params(h), h->cfg.compute_dtype, f64 != 0);
     s->xg = s->xg_default;
     const int L = s->L, M = s->M, C = s->C, P = s->P, K = s->K;
     const size_t e1 = s->esz, e2 = 2 * s->esz;
@@ -1358,9 +1368,9 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         s->status[0] = reinterpret_cast<int32_t*>(outbuf + hop_out_bytes(s));
         s->status[1] = s->status[0] + K;
     }
-    if (s->win_T > 1) {
-        // the ring of per-hop Gram matrices and the window sums, in the precision the joint diagonalisation runs in (orders above
-        // 64: float64 whatever compute_dtype is)
+    if (explicit_stats(s)) {
+        // the ring of per-hop Gram matrices (forgetting: the one accumulator slot) and the sums the joint diagonalisation reads,
+        // in the precision it runs in (orders above 64: float64 whatever compute_dtype is)
         s->win_c128 = (c.compute_dtype == APV_F64 || L > APV_MAX_N) ? 1 : 0;
         const size_t ce = s->win_c128 ? 16 : 8, E = apv_statwin_slot_elems(L);
         const size_t ring_bytes = (size_t)s->win_T * K * E * ce;
@@ -1369,8 +1379,8 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
             hipError_t e = hipMalloc(&s->win_ring[z], ring_bytes);
             if (e != hipSuccess) {
                 char buf[192];
-                std::snprintf(buf, sizeof(buf), "statistics window: the ring of %d hops needs %zu bytes per zone program (%d of them): %s",
-                              s->win_T, ring_bytes, nz, hipGetErrorString(e));
+                std::snprintf(buf, sizeof(buf), "statistics %s: the ring of %d hop(s) needs %zu bytes per zone program (%d of them): %s",
+                              s->fg_beta > 0.0 ? "accumulator" : "window", s->win_T, ring_bytes, nz, hipGetErrorString(e));
                 s->win_ring[z] = nullptr;
                 return apv_fail(h, APV_ERR_HIP, buf);
             }
@@ -1379,7 +1389,11 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
             if ((rc = dalloc(h, &s->win_RD[z], (size_t)K * L * L, ce))) return rc;
             if ((rc = dalloc(h, &s->win_r[z], (size_t)K * L, ce))) return rc;
         }
-        if ((rc = dalloc(h, &s->win_ctr, 2))) return rc;
+        if (s->fg_beta == 0.0 && (rc = dalloc(h, &s->win_ctr, 2))) return rc;
+        // Forgetting at order 64 with M < L: the first hops hold fewer than L rows and the later ones geometrically weighted rows,
+        // neither of which the float32 sweeps of kernels_gevd64.hip resolve (see win_low_rank).  No threshold in beta or in the
+        // hop count separates the two: such a stream keeps every solve off that kernel, so its launch sequence is one and captured.
+        s->fg_no_gevd64 = s->fg_beta > 0.0 && s->win_c128 && M < L && apv_gevd64_eligible(L, c.reg_mode, c.reg_bright, c.sweep_tol2);
         if (getenv("APV_STAT_WINDOW_TIMING") != nullptr)
             for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->win_ev[i]));
     }
@@ -1425,7 +1439,19 @@ int apv_stream_set_stat_hops(apv_handle* h, int32_t n_hops) {
     if (!h) return APV_ERR_ARG;
     if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_stat_hops: the stream is initialised (the ring of hops is sized there)");
     if (n_hops < 1 || n_hops > APV_MAX_STAT_HOPS) return apv_fail(h, APV_ERR_ARG, "statistics window: between 1 and 64 hops");
+    if (n_hops > 1 && h->stat_forgetting > 0.0)
+        return apv_fail(h, APV_ERR_ARG, "apv_stream_set_stat_hops: exponential forgetting is set (a window and forgetting exclude each other)");
     h->stat_hops = n_hops;
+    return APV_OK;
+}
+
+int apv_stream_set_stat_forgetting(apv_handle* h, double beta) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_stat_forgetting: the stream is initialised (the accumulator is allocated there)");
+    if (!(beta > 0.0 && beta <= 1.0)) return apv_fail(h, APV_ERR_ARG, "statistics forgetting factor: in (0, 1]");
+    if (h->stat_hops > 1)
+        return apv_fail(h, APV_ERR_ARG, "apv_stream_set_stat_forgetting: a statistics window is set (a window and forgetting exclude each other)");
+    h->stat_forgetting = beta;
     return APV_OK;
 }
 
@@ -1471,8 +1497,8 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
     if (!dRB) SCHK(h, hipMalloc(&dRB, mat));
     if (!dRD) SCHK(h, hipMalloc(&dRD, mat));
     if (!dr) SCHK(h, hipMalloc(&dr, vec));
-    if (s->win_T > 1) {
-        // the windowed statistics of the last hop are in device memory: handed out as they are (c64 widened first)
+    if (explicit_stats(s)) {
+        // the windowed (or forgetting) statistics of the last hop are in device memory: handed out as they are (c64 widened first)
         const size_t nm = (size_t)K * L * L, nv = (size_t)K * L;
         hipMemcpyKind dd = hipMemcpyDeviceToDevice;
         if (s->win_c128) {
@@ -1487,7 +1513,7 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
     }
     const void* XB = zone ? s->X[3] : s->X[0];
     const void* XD = zone ? s->X[2] : s->X[1];
-    if (s->win_T == 1 && s->xg > 1) {
+    if (!explicit_stats(s) && s->xg > 1) {
         // grouped spectra: the correlation kernel reads bin-major slabs, so the two sets are regrouped into scratch first
         void*& dgb = s->stat_ws[8]; void*& dgd = s->stat_ws[9];
         const size_t sb = (size_t)K * s->C * 2 * s->esz;
@@ -1498,7 +1524,7 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         XB = dgb;
         XD = dgd;
     }
-    hipError_t e = s->win_T > 1 ? hipSuccess
+    hipError_t e = explicit_stats(s) ? hipSuccess
                  : L > APV_MAX_N ? apv_launch_corr128(K, M, L, s->f64, XB, XD, s->tspec[zone], (double2*)dRB, (double2*)dRD, (double2*)dr, st)
                  : s->f64 ? apv_launch_corr_c128(K, M, L, (const double2*)XB, (const double2*)XD, (const double2*)s->tspec[zone],
                                                  (double2*)dRB, (double2*)dRD, (double2*)dr, st)
@@ -1521,7 +1547,7 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         }
         p.nV = 1; p.ranks[0] = 1; p.out_c128 = 1; p.n_zones = 1;
         // a window of fewer than L rows (win_fill_host hops are in it now): not for kernels_gevd64.hip, see win_low_rank
-        p.no_gevd64 = s->win_T > 1 && (long)s->win_fill_host * M < L;
+        p.no_gevd64 = s->fg_beta > 0.0 ? s->fg_no_gevd64 : (s->win_T > 1 && (long)s->win_fill_host * M < L);
         p.RB = dRB; p.RD = dRD; p.r = dr; p.w = dw; p.lam = dl; p.status = (int32_t*)dst; p.U = dU; p.Lspill = dspill;
         std::string why;
         e = apv_launch_gevd(p, APV_F64, false, st, &why);
@@ -1641,6 +1667,7 @@ int apv_set_mu(apv_handle* h, double mu) {
 //   "fir_correction<p>" [C][P-1]   "target_fir_correction<z>" [M][P-1]   pending correction tails (apv_stream_set_rirs): zeros in a
 //                                  stream that was never updated; handled by apv_live_state
 //   "stat_window<z>" [T][K][2 L^2 + L] complex, "stat_window_fill" int32   the statistics window (apv_stream_set_stat_hops), see win_index
+//   "stat_forget<z>" [K][2 L^2 + L] complex   the forgetting accumulator (apv_stream_set_stat_forgetting), see win_index
 static int live_index(const char* name) {
     const std::string n(name);
     if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
@@ -1650,10 +1677,15 @@ static int live_index(const char* name) {
 
 // "stat_window<z>" [win_T][K][2 L^2 + L] complex of the ring's precision, slots in the order of age (oldest first, zeros beyond the fill
 // level): 0 / 1; "stat_window_fill" one int32: 2; "stat_window_kernel_ms" {sum, count} of the timed statistics launches
-// (APV_STAT_WINDOW_TIMING, read-only): 3.  Only a stream with a statistics window has them.
+// (APV_STAT_WINDOW_TIMING, read-only): 3.  Only a stream with a statistics window has them.  A forgetting stream has
+// "stat_forget<z>" [K][2 L^2 + L], its accumulator: 4 / 5, and "stat_window_kernel_ms" for its own statistics launch.
 static int win_index(const apv_stream* s, const char* name) {
-    if (s->win_T <= 1) return -1;
     const std::string n(name);
+    if (s->fg_beta > 0.0) {
+        if ((n == "stat_forget0" || n == "stat_forget1") && s->win_ring[n.back() - '0']) return 4 + (n.back() - '0');
+        return n == "stat_window_kernel_ms" ? 3 : -1;
+    }
+    if (s->win_T <= 1) return -1;
     if ((n == "stat_window0" || n == "stat_window1") && s->win_ring[n.back() - '0']) return n.back() - '0';
     if (n == "stat_window_fill") return 2;
     if (n == "stat_window_kernel_ms") return 3;
@@ -1663,6 +1695,7 @@ static int win_index(const apv_stream* s, const char* name) {
 static size_t win_state_bytes(const apv_stream* s, int j) {
     if (j == 2) return sizeof(int32_t);
     if (j == 3) return 2 * sizeof(double);
+    if (j >= 4) return (size_t)s->K * apv_statwin_slot_elems(s->L) * (s->win_c128 ? 16 : 8);
     return (size_t)s->win_T * s->K * apv_statwin_slot_elems(s->L) * (s->win_c128 ? 16 : 8);
 }
 
@@ -1676,6 +1709,12 @@ static int win_state(apv_handle* h, int j, void* h_buf, size_t bytes, bool get) 
     if (j == 3) {
         if (!get) return apv_fail(h, APV_ERR_STATE, "stat_window_kernel_ms is read-only");
         std::memcpy(h_buf, s->win_ms, sizeof(s->win_ms));
+        return APV_OK;
+    }
+    if (j >= 4) {
+        if (get) SCHK(h, hipMemcpyAsync(h_buf, s->win_ring[j - 4], bytes, hipMemcpyDeviceToHost, st));
+        else SCHK(h, hipMemcpyAsync(s->win_ring[j - 4], h_buf, bytes, hipMemcpyHostToDevice, st));
+        SCHK(h, hipStreamSynchronize(st));
         return APV_OK;
     }
     int32_t ctr[2];

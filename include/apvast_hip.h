@@ -135,6 +135,19 @@ int  apv_set_rank_list(apv_handle* h, int32_t n, const int32_t* ranks);
  *                                                         replaces: update_statistics' buffer of several blocks, apvast.py:329-364 */
 int  apv_stream_set_stat_hops(apv_handle* h, int32_t n_hops);
 
+/* Exponentially forgetting statistics of the subband stream: after hop h every bin holds
+ *   R_B^(h)[k] = beta R_B^(h-1)[k] + X_B^(h)[k]^H X_B^(h)[k]  (R_D likewise),  r^(h)[k] = beta r^(h-1)[k] + X_B^(h)[k]^H d^(h)[k],
+ * from R = 0, r = 0 before the first hop: the recursive form of the reference's statistics buffer, with one smoothing constant
+ * in place of a window length and no ring.  beta in (0, 1]; 1 accumulates everything since the first hop.  apv_stream_init
+ * allocates ONE slot per zone program (K x (2 L^2 + L) complex of the compute precision, zero-filled); every hop reads and
+ * writes it once (one fma per real and imaginary part) and feeds the explicit joint diagonalisation of apv_gevd_vast_dev,
+ * apv_stream_get_statistics returns the running sums, and the state "stat_forget<z>" [K][2 L^2 + L] carries them for a resume.
+ * beta is fixed for the life of the stream.  Called between apv_create and apv_stream_init; refused (APV_ERR_ARG, nothing
+ * changed) if beta is not a finite number in (0, 1], once the stream is initialised, or when a window of more than one hop is
+ * set -- as apv_stream_set_stat_hops(h, n > 1) is once forgetting is set: the two exclude each other.
+ *                                                         replaces: update_statistics' buffer of several blocks, apvast.py:329-364 */
+int  apv_stream_set_stat_forgetting(apv_handle* h, double beta);
+
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
 int  apv_dev_free(apv_handle* h, void* d_ptr);

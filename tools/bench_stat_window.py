@@ -6,10 +6,11 @@ T in {1, 2, 4, 8, 16} and at one shape with more loudspeakers than control point
 also the statistics launch's own time from HIP events around it (a second object with APV_STAT_WINDOW_TIMING set, which runs the
 hop's launches uncaptured), the bytes it moves by the traffic model -- one slot written, T read:
 (T + 1) Z K (2 L^2 + L) 16 B -- and the fraction of the HBM roof that makes.  A hop of audio at 48 kHz lasts H / 48 ms.
+`--forgetting BETA` adds, per shape, a leg with statistics_forgetting=BETA (one slot read and written: the model's T = 1).
 
 Every (shape, T) is one child process under its own time limit; the first that fails or overruns ends the run.  One JSON line
 per leg.  `--leg SHAPE T` runs one leg in this process (also the way to time T = 1 on another checkout: the keyword is left out
-there).
+there); with `--forgetting BETA` (and T = 1) that leg is the forgetting one.
 """
 import argparse
 import json
@@ -44,12 +45,14 @@ def hop_times(obj, H, warm, n):
     return np.array(ts[warm:]) * 1e3
 
 
-def leg(shape, T, hops):
+def leg(shape, T, hops, beta=None):
     from ap_vast_unofficial_amd.apvast import apvast
     s = SHAPES[shape]
     L, M, N, H, P = s["L"], s["M"], s["N"], s["H"], s["P"]
     a0, b0 = rirs(P, L, M, 99)
     kw = {} if T == 1 else dict(statistics_hops=T)          # T = 1 without the keyword: runs on a checkout that lacks it
+    if beta is not None:
+        kw = dict(statistics_forgetting=beta)
     mk = lambda: apvast(N, a0, b0, 100, 20, 0, 0, 1, 1.0, 4 * N, hop_size=H, perceptual=False, dtype="f64", seed=0, **kw)
     warm = max(8, 2 * T)
     obj = mk()
@@ -57,7 +60,9 @@ def leg(shape, T, hops):
     obj.close()
     res = dict(shape=shape, L=L, M=M, N=N, H=H, rir_len=P, dtype="f64", statistics_hops=T, hops=hops,
                hop_ms_median=float(np.median(ts)), hop_ms_p90=float(np.percentile(ts, 90)), audio_hop_ms=H / 48.0)
-    if T > 1:
+    if beta is not None:
+        res["statistics_forgetting"] = beta
+    if T > 1 or beta is not None:
         os.environ["APV_STAT_WINDOW_TIMING"] = "1"
         obj = mk()
         hop_times(obj, H, warm, hops)
@@ -75,19 +80,25 @@ def leg(shape, T, hops):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", nargs=2, metavar=("SHAPE", "T"))
+    ap.add_argument("--forgetting", type=float, default=None, metavar="BETA")
     ap.add_argument("--hops", type=int, default=100)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per leg")
     args = ap.parse_args()
     if args.leg:
-        leg(args.leg[0], int(args.leg[1]), args.hops)
+        if args.forgetting is not None and int(args.leg[1]) != 1:
+            ap.error("--forgetting goes with T = 1: a window and forgetting exclude each other")
+        leg(args.leg[0], int(args.leg[1]), args.hops, args.forgetting)
         return 0
     for shape, s in SHAPES.items():
-        for T in s["Ts"]:
+        legs = [(T, []) for T in s["Ts"]]
+        if args.forgetting is not None:
+            legs.append((1, ["--forgetting", str(args.forgetting)]))
+        for T, extra in legs:
             # one child per leg, under its own time limit; nothing more is started after a leg that fails or overruns
             r = subprocess.run(["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--leg", shape,
-                                str(T), "--hops", str(args.hops if shape == "cfg3" else max(args.hops // 4, 10))])
+                                str(T), "--hops", str(args.hops if shape == "cfg3" else max(args.hops // 4, 10))] + extra)
             if r.returncode != 0:
-                print(json.dumps(dict(shape=shape, statistics_hops=T, failed=r.returncode)), flush=True)
+                print(json.dumps(dict(shape=shape, statistics_hops=T, forgetting=bool(extra), failed=r.returncode)), flush=True)
                 return r.returncode
     return 0
 
