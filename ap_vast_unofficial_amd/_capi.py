@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -143,6 +143,8 @@ def load():
     lib.apv_set_rank_list.argtypes = [vp, i32, vp]
     lib.apv_stream_set_stat_hops.argtypes = [vp, i32]
     lib.apv_stream_set_stat_forgetting.argtypes = [vp, C.c_double]
+    lib.apv_stream_set_filter_taps.argtypes = [vp, i32]
+    lib.apv_constrain_filters.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -216,7 +218,7 @@ class Engine:
     def __init__(self, n_bins, n_srcs, n_mics, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=None,
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
-                 out_layout=0, stat_hops=1, stat_forgetting=None):
+                 out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -266,6 +268,31 @@ class Engine:
         self.stat_forgetting = None
         if stat_forgetting is not None:
             self.set_stat_forgetting(stat_forgetting)
+        self.filter_taps = 0
+        if int(filter_taps) != 0:
+            self.set_filter_taps(filter_taps)
+
+    def set_filter_taps(self, J):
+        """Filter-length constraint of the subband stream: J taps (1..block_size; 0 = off), before stream_init
+        (apv_stream_set_filter_taps)."""
+        self._chk(self.lib.apv_stream_set_filter_taps(self.h, int(J)))
+        self.filter_taps = int(J)
+
+    def constrain_filters(self, w, N, J):
+        """The projection alone (apv_constrain_filters): w (N/2 + 1, nV, L) complex -> (w', taps), w' = rfft(g, N) with
+        g = irfft(w, N) cut to J taps along axis 0, in the handle's filter dtype (w_dtype); taps = g[:J] as (nV, J, L) of lam_dtype."""
+        w = np.ascontiguousarray(w, dtype=self.w_dtype)
+        if w.ndim != 3 or w.shape[0] != int(N) // 2 + 1:
+            raise ValueError("w must be (N / 2 + 1, nV, L)")
+        K, nV, L = w.shape
+        dw = self.to_device(w)
+        dt = self.alloc(nV * int(J) * L * np.dtype(self.lam_dtype).itemsize)
+        try:
+            self._chk(self.lib.apv_constrain_filters(self.h, dw.ptr, K, nV, L, int(N), int(J), dt.ptr))
+            return dw.download((K, nV, L), self.w_dtype), dt.download((nV, int(J), L), self.lam_dtype)
+        finally:
+            dw.free()
+            dt.free()
 
     def set_stat_hops(self, n_hops):
         """Statistics window of the subband stream, in hops (1..MAX_STAT_HOPS), before stream_init (apv_stream_set_stat_hops)."""

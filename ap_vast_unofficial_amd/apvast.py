@@ -25,8 +25,8 @@ What is different (keyword-only, after ``perceptual``)
     last T hops: R_B[k] = sum_t X_B^(h-t)[k]^H X_B^(h-t)[k], likewise R_D and r, the per-bin form of the reference's
     statistics buffer of several blocks (apvast.py:329-364).  ``statistics_hops="auto"`` takes T from
     ``statistics_buffer_length``: the whole blocks that many samples span, max(1, 1 + (S - N) // hop_size); the default 1
-    keeps the single-block update (``filter_length`` is accepted and stored, not used; ``statistics_buffer_length`` is
-    used by ``"auto"`` only).  With T > 1 the attributes R_*, r_*, U_*, lambda_* are those of the window.
+    keeps the single-block update (``statistics_buffer_length`` is used by ``"auto"`` only; ``filter_length`` is used by
+    ``constrain_filter_length=True`` only, see below).  With T > 1 the attributes R_*, r_*, U_*, lambda_* are those of the window.
     ``statistics_forgetting=beta``, a float in (0, 1], is the recursive estimate instead: R_B[k] <- beta R_B[k] + X_B[k]^H X_B[k]
     per hop, likewise R_D and r, from zero before the first hop (1.0 accumulates every hop); one smoothing constant, no hard
     edge when a hop leaves, and memory that does not grow with the averaging time.  Fixed at construction; ``None`` (default)
@@ -36,6 +36,17 @@ What is different (keyword-only, after ``perceptual``)
     Up to 128 loudspeakers: above 64 the per-bin joint diagonalisation runs in float64 whatever ``dtype`` is
     (csrc/kernels_gevd128.hip), its filters and eigenvalues handed on in the dtype's format (complex64 / float32 for
     ``"f32"``); every rank 1..V, V <= number_of_srcs, is emitted.
+  * ``constrain_filter_length=True`` (subband mode; default False): ``filter_length`` = J is honoured.  After the joint
+    diagonalisation of a hop and before the output spectra, every filter -- zone programs that run, rank index v, loudspeaker l --
+    is projected onto the spectra of causal J-tap responses: g = irfft(W[:, v, l], N) (numpy's convention: the imaginary parts of
+    bins 0 and N/2 are discarded), g[J:] = 0, W'[:, v, l] = rfft(g, N), the constraint step of frequency-domain adaptive filters.
+    W' is what the synthesis uses and what w_* / filter_spectra_* return; ``w_time_A`` / ``w_time_B`` return the taps g[:J] as
+    float64 (V, J, L) -- the subband counterpart of the reference's J-tap w_A / w_B, loadable into a convolver -- and None before
+    the first hop or for a zone that does not run.  Needs 1 <= filter_length <= block_size and modeling_delay < filter_length (the
+    reference puts its target tap at J ref + delay); the target paths, a delta already, are untouched.  Combines with every dtype,
+    statistics_hops, statistics_forgetting, perceptual, reassigned rir_* / mu, up to 128 loudspeakers and every block size.
+    process_signal on such a stream runs its hops one after the other through the per-hop path (the same bits as the hop loop).
+    Without the keyword the stream launches exactly what it launched before, and ``filter_length`` is stored and not used.
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).
@@ -128,6 +139,7 @@ class apvast:
                  fullscale_db_spl: float = 94.0,
                  max_sweeps: int = 0,
                  sweep_tol2: float = 0.0,
+                 constrain_filter_length=False,
                  statistics_forgetting=None,
                  statistics_hops=1):
         self.block_size = block_size
@@ -164,6 +176,8 @@ class apvast:
         self.statistics_hops = self._resolve_statistics_hops(statistics_hops, statistics_buffer_length, block_size,
                                                              self.hop_size, mode)
         self.statistics_forgetting = self._check_statistics_forgetting(statistics_forgetting, self.statistics_hops, mode)
+        self.constrain_filter_length = self._check_constrain_filter_length(constrain_filter_length, filter_length, block_size,
+                                                                           modeling_delay, mode)
         self.window = np.sin(np.pi / self.block_size * np.arange(self.block_size)).reshape(-1, 1)   # apvast.py:94
         self.rir_length, self.number_of_srcs, self.number_of_mics = rir_A.shape  # apvast.py:97-99
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
@@ -188,7 +202,8 @@ class apvast:
                                  block_size=N, hop_size=H, n_zones=zones, frontend="f32" if dtype == "mixed" else None,
                                  max_sweeps=self._max_sweeps, sweep_tol2=sweep_tol2,
                                  out_layout=1,     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
-                                 stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting)
+                                 stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting,
+                                 filter_taps=int(filter_length) if self.constrain_filter_length else 0)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -243,6 +258,23 @@ class apvast:
         if statistics_hops > 1:
             raise ValueError("statistics_forgetting and statistics_hops > 1 exclude each other: one estimator per stream")
         return float(value)
+
+    @staticmethod
+    def _check_constrain_filter_length(value, filter_length, block_size, modeling_delay, mode):
+        """constrain_filter_length as a bool; True needs subband mode, 1 <= filter_length <= block_size and
+        modeling_delay < filter_length."""
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError("constrain_filter_length must be a bool")
+        if not value:
+            return False
+        if mode == "broadband":
+            raise ValueError("constrain_filter_length is a subband keyword: broadband mode designs filter_length-tap filters by construction")
+        if isinstance(filter_length, bool) or not isinstance(filter_length, (int, np.integer)) or not 1 <= int(filter_length) <= int(block_size):
+            raise ValueError("constrain_filter_length: filter_length must be an int in 1..block_size")
+        if not int(modeling_delay) < int(filter_length):
+            raise ValueError("constrain_filter_length: modeling_delay must be below filter_length (the target tap has to lie inside "
+                             "the filter)")
+        return True
 
     # ---- responses and mu, reassignable between hops (the reference reads them on every hop, apvast.py:161, 167-193) ----
     def _init_responses(self, rir_A, rir_B):
@@ -501,10 +533,14 @@ class apvast:
             return c[name]
         if not (self.run_A if z == "A" else self.run_B):
             return None
-        if name.startswith("w_") or name.startswith("filter_spectra_"):
+        if (name.startswith("w_") and not name.startswith("w_time_")) or name.startswith("filter_spectra_"):
             w = e.get_state("w_" + z, (K, V, L), e.w_dtype).astype(np.complex128)
             c["w_" + z] = np.ascontiguousarray(w.transpose(1, 0, 2))               # (V, K, L)
             c["filter_spectra_" + z] = [c["w_" + z][i] for i in range(V)]          # V x (K, L): the filters ARE the spectra
+        elif name.startswith("w_time_"):
+            if not self.constrain_filter_length:
+                return None
+            c[name] = e.get_state(name, (V, int(self.filter_length), L), e.lam_dtype).astype(np.float64)
         elif name.startswith("lambda_"):
             c[name] = e.get_state(name, (K, L), e.lam_dtype).astype(np.float64)
         else:
@@ -562,7 +598,7 @@ class apvast:
     U_B = property(lambda self: self._zone_attr("B", "U"))
 
     _LAZY = ("w_A", "w_B", "lambda_A", "lambda_B", "input_spectrum_A", "input_spectrum_B", "filter_spectra_A", "filter_spectra_B",
-             "R_A_to_A", "R_A_to_B", "R_B_to_B", "R_B_to_A", "r_A", "r_B")
+             "R_A_to_A", "R_A_to_B", "R_B_to_B", "R_B_to_A", "r_A", "r_B", "w_time_A", "w_time_B")
 
     def __getattr__(self, name):
         # the attributes the reference assigns in every hop (apvast.py:368-403): read from the device on demand, cached until
@@ -570,6 +606,8 @@ class apvast:
         d = self.__dict__
         if name in apvast._LAZY and "_eng" in d and "_hops" in d:
             if d.get("mode") == "broadband":
+                if name.startswith("w_time_"):
+                    return None                                                   # broadband w_* are the J-tap filters themselves
                 if name.startswith("filter_spectra_"):
                     if d["_hops"] == 0:
                         return None

@@ -87,6 +87,7 @@ struct apv_handle {
     std::vector<int32_t> rank_list;  // the subband rank list: cfg.ranks, or apv_set_rank_list's (cfg.n_ranks entries, up to n_srcs)
     int stat_hops;                   // apv_stream_set_stat_hops: statistics window of the next apv_stream_init, in hops (<= 1: one block)
     double stat_forgetting;          // apv_stream_set_stat_forgetting: forgetting factor of the next apv_stream_init in (0, 1]; 0: off
+    int filter_taps;                 // apv_stream_set_filter_taps: J of the next apv_stream_init's filter-length constraint; 0: off
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -260,6 +261,13 @@ hipError_t apv_launch_fir_spectra_part(int f64, int F, int n_ch, const void* x, 
                                        std::string* why);
 // uniformly partitioned K1 for (P, H): number of partitions (segments of 2 H samples), 0 when it does not apply
 int apv_fir_partitions(int f64, int P, int H);
+
+// kernels_constrain.hip: the filter-length constraint.  w[z] [N/2 + 1][nV][L] complex (c128: double, else float) of `zones` zone
+// programs projected in place onto the spectra of J-tap responses, the taps to taps[z] [nV][J][L] real of the same precision
+// (taps, or an entry of it, may be null).  One launch; the tables of (N, precision) must exist when it is captured (apv_stft_prepare)
+bool apv_constrain_size_ok(int c128, int N, std::string* why);
+hipError_t apv_launch_constrain_filters(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
+                                        hipStream_t s, std::string* why);
 
 // whole-signal path, a chunk of hops per launch (kernels_stft.hip / kernels_stream.hip; see process_signal_chunked_t in stream.hip)
 hipError_t apv_launch_stft_analysis_chunk(int f64, int N, int n_jobs, const void* const* x, const int* n_ch, void* const* spec,

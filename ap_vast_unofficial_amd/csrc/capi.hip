@@ -230,6 +230,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     h->bb = nullptr;
     h->stat_hops = 1;
     h->stat_forgetting = 0.0;
+    h->filter_taps = 0;
     h->gl_ws = nullptr;
     h->gl_tol2 = 0.0;
     h->gl_lead_rank = 0;
@@ -851,6 +852,20 @@ int apv_istft_ola_dev(apv_handle* h, int32_t n_ch, const void* d_spec, float* d_
     std::string why;
     hipError_t e = apv_launch_istft_ola(h->cfg.block_size, h->cfg.hop_size, n_ch, (const float2*)d_spec, d_overlap,
                                         d_out, h->stream, &why);
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
+int apv_constrain_filters(apv_handle* h, void* d_w, int32_t n_bins, int32_t nV, int32_t L, int32_t N, int32_t J, void* d_taps) {
+    if (!h || !d_w) return fail(h, APV_ERR_ARG, "null device pointer");
+    if (N < 4 || (N & 1) || n_bins != N / 2 + 1) return fail(h, APV_ERR_ARG, "apv_constrain_filters: n_bins must be N / 2 + 1, N even");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    std::string why;
+    void* w[1] = {d_w};
+    void* taps[1] = {d_taps};
+    hipError_t e = apv_launch_constrain_filters(h->cfg.out_c128, N, J, nV, L, 1, w, taps, h->stream, &why);
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
     return APV_OK;

@@ -134,6 +134,11 @@ struct apv_stream {
     // accumulator is the one slot win_ring[z] [K][2 L^2 + L], and win_c128, win_RB / win_RD / win_r, win_ev / win_ms serve as above
     double fg_beta;               // 0: off
     int fg_no_gevd64;             // GevdParams::no_gevd64 of every hop and of apv_stream_get_statistics: see apv_stream_init
+    // filter-length constraint (apv_stream_set_filter_taps, kernels_constrain.hip); taps = 0: off, nothing below exists
+    int taps;                     // J
+    void* wtaps[2];               // per zone program: [nV][J][L] real, the J taps of the hop's projected filters (precision of w)
+    hipEvent_t cf_ev[2];          // APV_FILTER_CONSTRAINT_TIMING (tools/bench_filter_constraint.py): events around the projection
+    double cf_ms[2];              // ... and {sum of its times in ms, hops timed}
     hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
     double win_ms[2];             // ... and {sum of its times in ms, hops timed}
     std::vector<hipGraphExec_t> execs;
@@ -263,6 +268,8 @@ void apv_stream_free(apv_handle* h) {
         for (void* b : wb)
             if (b) (void)hipFree(b);
         if (s->win_ev[z]) (void)hipEventDestroy(s->win_ev[z]);
+        if (s->wtaps[z]) (void)hipFree(s->wtaps[z]);
+        if (s->cf_ev[z]) (void)hipEventDestroy(s->cf_ev[z]);
     }
     if (s->win_ctr) (void)hipFree(s->win_ctr);
     delete s;
@@ -482,6 +489,20 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
         hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why, h->rank_list.data());
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
     }
+    if (s->taps > 0) {
+        // the hop's filters projected onto J-tap responses, in place, both zone programs in one launch: K3, the attributes and the
+        // states read the projected filters
+        void *cw[2], *ct[2];
+        int nz = 0;
+        for (int z = 0; z < 2; ++z) {
+            if (!(z ? runB : runA)) continue;
+            cw[nz] = wz[z]; ct[nz] = s->wtaps[z]; ++nz;
+        }
+        if (s->cf_ev[0]) SCHK(h, hipEventRecord(s->cf_ev[0], st));
+        hipError_t e = apv_launch_constrain_filters(h->cfg.out_c128, N, s->taps, s->nV, L, nz, cw, ct, st, &why);
+        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+        if (s->cf_ev[1]) SCHK(h, hipEventRecord(s->cf_ev[1], st));
+    }
     {
         // K3: output spectra in one launch: each live zone's nV*L filtered channels, then the target paths A_t, B_t
         const void* jin[4];
@@ -574,6 +595,12 @@ static int run_hop(apv_handle* h) {
         SCHK(h, hipEventElapsedTime(&ms, s->win_ev[0], s->win_ev[1]));
         s->win_ms[0] += ms;
         s->win_ms[1] += 1.0;
+    }
+    if (s->cf_ev[0]) {
+        float ms = 0.f;
+        SCHK(h, hipEventElapsedTime(&ms, s->cf_ev[0], s->cf_ev[1]));
+        s->cf_ms[0] += ms;
+        s->cf_ms[1] += 1.0;
     }
     return APV_OK;
 }
@@ -742,7 +769,8 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
 
 // The whole-signal call of a stream with a statistics window: the hops one after the other through the per-hop path (its graphs
 // included), so the samples are those of n_hops per-hop calls by construction.  (One statistics launch per chunk of hops is the
-// follow-up named in DESIGN.md section 4.13.)
+// follow-up named in DESIGN.md section 4.13.)  A stream with the filter-length constraint takes it too: the chunked and batched
+// schedules do not launch the projection (the follow-up named in DESIGN.md section 4.15).
 template <typename TI>
 static int process_signal_hops_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
     apv_stream* s = h->st;
@@ -772,7 +800,7 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     if (!s) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
     if (n_hops < 0) return apv_fail(h, APV_ERR_ARG, "n_hops must be >= 0");
     if (n_hops == 0) return APV_OK;
-    if (explicit_stats(s)) return process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    if (explicit_stats(s) || s->taps > 0) return process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
     // K1 as one fast-convolution segment (responses of 64 taps or more): a chunk of hops per launch (below); direct-form K1 (shorter
     // responses, APV_FIR_DIRECT) and partitioned K1 keep the hop-by-hop pipeline of this function
     if (s->fir_F > 0 && s->fir_np == 1) return process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
@@ -1262,6 +1290,12 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     if (reference_index_A < 0 || reference_index_A >= c.n_srcs || reference_index_B < 0 || reference_index_B >= c.n_srcs)
         return apv_fail(h, APV_ERR_ARG, "reference index out of range");
     if (c.n_zones < 1 || c.n_zones > 3) return apv_fail(h, APV_ERR_ARG, "n_zones is a bit mask: 1 = A, 2 = B, 3 = both");
+    if (h->filter_taps > 0) {
+        std::string why;
+        if (h->filter_taps > N) return apv_fail(h, APV_ERR_ARG, "filter taps (apv_stream_set_filter_taps) must not exceed block_size");
+        if (modeling_delay >= h->filter_taps) return apv_fail(h, APV_ERR_ARG, "modeling_delay must be below the filter taps (apv_stream_set_filter_taps)");
+        if (!apv_constrain_size_ok(c.out_c128, N, &why)) return apv_fail(h, APV_ERR_ARG, why);
+    }
     SCHK(h, hipSetDevice(h->device));
     apv_stream_free(h);
     apv_stream* s = new apv_stream();
@@ -1277,6 +1311,7 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     s->Kp = (s->K + 7) / 8 * 8;
     s->win_T = h->stat_hops > 1 ? h->stat_hops : 1;
     s->fg_beta = h->stat_forgetting;
+    s->taps = h->filter_taps;
     // (a windowed or forgetting stream does not launch the fused kernel that reads grouped spectra: its slabs stay bin-major)
     s->xg_default = explicit_stats(s) ? 1 : apv_gevd_reads_groups(apv_base_params(h), h->cfg.compute_dtype, f64 != 0);
     s->xg = s->xg_default;
@@ -1397,6 +1432,13 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (getenv("APV_STAT_WINDOW_TIMING") != nullptr)
             for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->win_ev[i]));
     }
+    if (s->taps > 0) {
+        for (int z = 0; z < 2; ++z)
+            if ((s->zones & (1 << z)) && (rc = dalloc(h, &s->wtaps[z], (size_t)s->nV * s->taps * L, lsz(h)))) return rc;
+        SCHK(h, apv_stft_prepare(N, c.out_c128));           // the projection runs in the filters' precision
+        if (getenv("APV_FILTER_CONSTRAINT_TIMING") != nullptr)
+            for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->cf_ev[i]));
+    }
     // target filter spectra: rfft of a unit impulse at tap modeling_delay of the A reference loudspeaker
     // (apvast.py:389-390, 418, 422: the same filter serves A_t and B_t)
     std::vector<double> tg((size_t)L * K * 2, 0.0);
@@ -1426,7 +1468,7 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (per % 2) per *= 2;
         // (the statistics window adds no phase: its ring position is two device words that a kernel of the hop advances.  Timed
         // statistics launches -- a measuring aid -- run eagerly: their events are read after every hop)
-        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr && !s->win_ev[0]) ? per : 0;
+        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr && !s->win_ev[0] && !s->cf_ev[0]) ? per : 0;
         s->execs.assign(s->period > 0 ? s->period : 0, nullptr);
     }
     s->hop = 0;
@@ -1442,6 +1484,15 @@ int apv_stream_set_stat_hops(apv_handle* h, int32_t n_hops) {
     if (n_hops > 1 && h->stat_forgetting > 0.0)
         return apv_fail(h, APV_ERR_ARG, "apv_stream_set_stat_hops: exponential forgetting is set (a window and forgetting exclude each other)");
     h->stat_hops = n_hops;
+    return APV_OK;
+}
+
+int apv_stream_set_filter_taps(apv_handle* h, int32_t J) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_filter_taps: the stream is initialised (the taps buffer is allocated there)");
+    if (J < 0 || (h->cfg.block_size > 0 && J > h->cfg.block_size))
+        return apv_fail(h, APV_ERR_ARG, "filter taps: 0 (off) or between 1 and block_size");
+    h->filter_taps = J;
     return APV_OK;
 }
 
@@ -1668,6 +1719,9 @@ int apv_set_mu(apv_handle* h, double mu) {
 //                                  stream that was never updated; handled by apv_live_state
 //   "stat_window<z>" [T][K][2 L^2 + L] complex, "stat_window_fill" int32   the statistics window (apv_stream_set_stat_hops), see win_index
 //   "stat_forget<z>" [K][2 L^2 + L] complex   the forgetting accumulator (apv_stream_set_stat_forgetting), see win_index
+//   "w_time_A" / "w_time_B" [nV][J][L] f32|f64 (cfg.out_c128)   the J taps of the last hop's projected filters; only a stream with
+//                                  the filter-length constraint (apv_stream_set_filter_taps) and only zone programs that run have them
+//   "filter_constraint_kernel_ms" {sum, count} of the timed projections (APV_FILTER_CONSTRAINT_TIMING), read-only
 static int live_index(const char* name) {
     const std::string n(name);
     if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
@@ -1772,6 +1826,8 @@ static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* by
     if ((n == "weights0" || n == "weights1") && s->nch > 0) { *dptr = s->Wgt[n.back() - '0']; *bytes = K * M * e1; return APV_OK; }
     if (n == "w_A" || n == "w_B") { *dptr = s->w[n == "w_B"]; *bytes = K * s->nV * L * wsz(h); return APV_OK; }
     if (n == "lambda_A" || n == "lambda_B") { *dptr = s->lam[n == "lambda_B"]; *bytes = K * L * lsz(h); return APV_OK; }
+    if ((n == "w_time_A" || n == "w_time_B") && s->wtaps[n == "w_time_B"]) {
+        *dptr = s->wtaps[n == "w_time_B"]; *bytes = (size_t)s->nV * s->taps * L * lsz(h); return APV_OK; }
     return apv_fail(h, APV_ERR_STATE, std::string("unknown state name: ") + name);
 }
 
@@ -1787,6 +1843,10 @@ int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
         *bytes = win_state_bytes(h->st, wj);
         return APV_OK;
     }
+    if (h->st->taps > 0 && std::string(name) == "filter_constraint_kernel_ms") {
+        *bytes = sizeof(h->st->cf_ms);
+        return APV_OK;
+    }
     void* d; int rr;
     return state_lookup(h, name, &d, bytes, &rr);
 }
@@ -1799,6 +1859,11 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
         return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, h_dst, bytes, true, h->stream);
     }
     if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), h_dst, bytes, true);
+    if (h->st->taps > 0 && std::string(name) == "filter_constraint_kernel_ms") {
+        if (bytes != sizeof(h->st->cf_ms)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+        std::memcpy(h_dst, h->st->cf_ms, sizeof(h->st->cf_ms));
+        return APV_OK;
+    }
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;

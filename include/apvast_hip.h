@@ -148,6 +148,29 @@ int  apv_stream_set_stat_hops(apv_handle* h, int32_t n_hops);
  *                                                         replaces: update_statistics' buffer of several blocks, apvast.py:329-364 */
 int  apv_stream_set_stat_forgetting(apv_handle* h, double beta);
 
+/* Filter-length constraint of the subband stream: with J > 0 every hop projects its per-bin filters, between the joint
+ * diagonalisation and the output spectra, onto the spectra of causal J-tap impulse responses -- for every zone program that runs,
+ * every rank index v and every loudspeaker l
+ *   g = irfft(W[:, v, l], N)     (numpy's convention: the imaginary parts of bins 0 and N/2 are discarded)
+ *   g[J:] = 0
+ *   W'[:, v, l] = rfft(g, N)
+ * and W' replaces W everywhere downstream: the output spectra and the synthesis use it, the states "w_A" / "w_B" hold it, and the
+ * states "w_time_A" / "w_time_B" [nV][J][L] (float64 with cfg.out_c128, else float32) hold the taps g[:J] of the last hop: the
+ * subband counterpart of the reference's J-tap w_A / w_B.  The target paths are a delta already and are not touched.  One more
+ * kernel per hop (csrc/kernels_constrain.hip), part of the captured hop graphs; the taps buffers are allocated by apv_stream_init
+ * only when J > 0.  apv_process_signal* on such a stream runs its hops through the per-hop path.  J = 0 (the default) switches the
+ * constraint off: the stream launches what it launches without this call, and has no "w_time_*" states.  Called between apv_create
+ * and apv_stream_init; APV_ERR_ARG (nothing changed) once the stream is initialised or for J outside 0..block_size;
+ * apv_stream_init refuses modeling_delay >= J (the reference puts its target tap at J ref + delay).
+ *                                                         replaces: the J-tap filters of apvast.py:389-422 (filter_length) */
+int  apv_stream_set_filter_taps(apv_handle* h, int32_t J);
+
+/* The projection alone, without a stream: d_w [n_bins][nV][L] complex (c128 with cfg.out_c128, else c64), n_bins = N / 2 + 1,
+ * projected in place onto J-tap responses as defined above, 1 <= J <= N; d_taps [nV][J][L] real of the same precision receives
+ * g[:J] (NULL: not wanted).  Any even N the STFT accepts whose transform fits LDS in that precision.  On the handle's stream.
+ *                                                         replaces: nothing in the reference (see apv_stream_set_filter_taps) */
+int  apv_constrain_filters(apv_handle* h, void* d_w, int32_t n_bins, int32_t nV, int32_t L, int32_t N, int32_t J, void* d_taps);
+
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
 int  apv_dev_free(apv_handle* h, void* d_ptr);
