@@ -55,20 +55,34 @@ __device__ __forceinline__ float tp_sum_quads(float v) {
     const auto r32 = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
     return __int_as_float((int)r32[0]) + __int_as_float((int)r32[1]);
 }
+// The wide multisection step's votes: nb_m = the number of lanes whose Sturm count is <= m (one v_cmp into a scalar pair and a
+// scalar population count) goes into lane m of nbv, m = M .. 15 (v_writelane_b32 with the lane as an immediate; the compiler has
+// no builtin for it)
+template <int M> __device__ __forceinline__ void tp_vote(int cnt, int& nbv) {
+    const int nb = __builtin_popcountll(__builtin_amdgcn_ballot_w64(cnt <= M));
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(nbv) : "s"(nb), "n"(M));
+    if constexpr (M + 1 < 16) tp_vote<M + 1>(cnt, nbv);
+}
 
-// Multisection steps: the interval [-1e-3, 1.001] ||C|| shrinks 5x per step, to 1.002 * 5^-kTpSteps of ||C||, and the eigenvalue
-// is its midpoint.  The refinement certifies the result whatever the pre-solve delivers, so the multisection stops where the
-// refinement's own guards stop gaining (tools/probes/tridiag_presolve_model.py, 32 768 bench bins; DESIGN 4.1 has the table).
-constexpr int kTpSteps = 9;
+// Multisection: the interval [-1e-3, 1.001] ||C|| (width 1.002 ||C||) shrinks 65x in the wave-wide first step, where all
+// sixteen quads still search the same interval and the 64 lanes evaluate 64 distinct points, and 5x in each of the kTpQuadSteps
+// quad steps that follow (four points per eigenvalue): 1 + kTpQuadSteps Sturm evaluations per lane.  The refinement certifies the
+// result whatever the pre-solve delivers, so the multisection stops where the refinement's own guards stop gaining
+// (tools/probes/tridiag_presolve_model.py on the bench bins; DESIGN 4.1 has the table: six quad steps keep the share of bins
+// inside the one-step guard, five lose 0.2 %).
+constexpr int kTpQuadSteps = 6;
 constexpr float tp_pow5_inv(int n) { return n == 0 ? 1.f : 0.2f * tp_pow5_inv(n - 1); }
-// Largest error of a multisection eigenvalue, in units of ||C||: half the final interval plus the float32 floor of the Sturm count
-// and of the interval's re-formed ends.  The floor is taken as 1e-6: over 32 768 bench bins the model's largest error is 7.2e-7 at
-// ten steps, where the interval (half of it 5e-8) no longer matters.  Nine steps: 2.6e-7 + 1e-6 = 1.26e-6 (model: 7.5e-7);
-// eight: 1.28e-6 + 1e-6 = 2.3e-6 (model: 1.7e-6).
-constexpr float kTpLamErr = 0.5f * 1.002f * tp_pow5_inv(kTpSteps) + 1e-6f;
+// width of the final interval in units of ||C||: 1.002 / (65 * 5^kTpQuadSteps) = 9.9e-7
+constexpr float kTpFinal = 1.002f / 65.f * tp_pow5_inv(kTpQuadSteps);
+// Largest error of the eigenvalue a quad reports, in units of ||C||.  The four lanes of a quad shift by the points 1/8, 3/8, 5/8
+// and 7/8 of the final interval and the best one is the quad's eigenvalue, so an eigenvalue inside the interval is at most an
+// eighth of the interval from the nearest shift: 0.125 kTpFinal = 1.2e-7.  To that comes the float32 floor of the Sturm count
+// and of the interval's re-formed ends, taken as 1e-6: the model's largest error over 32 768 bench bins is 7.2e-7 where the
+// interval no longer matters (with this scheme: 6.2e-7 over 32 768, 6.4e-7 with 1-ulp noise on the pivots' reciprocals).
+constexpr float kTpLamErr = 0.125f * kTpFinal + 1e-6f;
 // Two eigenvalues whose TRUE gap is below 1e-5 ||C|| must not be trusted (see the gate).  Each measured eigenvalue is off by at most
-// kTpLamErr, so a true gap g reads as at most g + 2 kTpLamErr: the measured gap has to exceed 1e-5 + 2 kTpLamErr (nine steps:
-// 1.25e-5, eight: 1.46e-5) before the pair counts as apart.
+// kTpLamErr, so a true gap g reads as at most g + 2 kTpLamErr: the measured gap has to exceed 1e-5 + 2 kTpLamErr = 1.22e-5 before
+// the pair counts as apart.
 constexpr float kTpApart = 1e-5f + 2.f * kTpLamErr;
 constexpr int LDQ = 17, LDX = 17;       // row strides of the float Q and X in the pre-solve's LDS scratch
 
@@ -77,7 +91,7 @@ constexpr int LDQ = 17, LDX = 17;       // row strides of the float Q and X in t
 // (mfma_row<float>(lane, t), lane & 15)), and whether its spectrum is fit for the refinement (finite, spread < 1e3, no two
 // eigenvalues closer than 1e-5 ||C||).  The eigenvalues are good to kTpLamErr ||C|| only: the multisection stops where two
 // inverse-iteration steps and the refinement's guards (|Z| <= 3e-5 for one step, 1e-2 for two) no longer gain from a finer
-// shift.  They come out in ascending order, quad i holding eigenvalue i, which the gate at the end relies on.
+// shift.  Their intervals come out in ascending order, quad i holding eigenvalue i, which the gate at the end relies on.
 // `stamp` (diagnostic instantiation): slots 4 after the reduction, 13 after the multisection, 14 after the inverse iteration, 5 at the end.
 template <typename TS, typename ST = NoStamp>
 __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, float normS2, Cx<float>* fQ, float* fX,
@@ -194,20 +208,15 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
     }
     stamp(4);
 
-    // ---- 2. eigenvalue m = i by multisection: lane (i, jq) counts the eigenvalues below lo + (jq + 1) (hi - lo) / 5.  C is positive
-    // semi-definite with ||C|| <= ||C||_F, so the spectrum lies in [-1e-3, 1.001] ||C||_F
+    // ---- 2. eigenvalue m = i by multisection.  C is positive semi-definite with ||C|| <= ||C||_F, so the spectrum lies in
+    // [-1e-3, 1.001] ||C||_F
     const float nrmF = sqrtf(normS2);
-    float lo = -1e-3f * nrmF, hi = 1.001f * nrmF;
-    const float frac = 0.2f * (float)(jq + 1);
-#pragma unroll 1
-    for (int st = 0; st < kTpSteps; ++st) {
-        const float wd = hi - lo;
-        const float x = fmaf(wd, frac, lo);
-        // Sturm count: the negative pivots of T - x I.  A zero pivot gives rcp = inf, the next pivot -inf (counted), rcp(-inf) = -0.
-        // The sign bit of every pivot is shifted into one word (v_alignbit_b32: one instruction per pivot) and counted once.  It
-        // differs from `qv < 0` on a pivot of -0 only, and a fused -e2 r + (d - x) rounds to -0 only from a negative value that
-        // underflowed (e2 > 0, and d - x is -0 for d = -0, x = +0 alone): the sign bit is the sign of the pivot.  (The NumPy
-        // model has counted sign bits all along.)
+    // Sturm count: the negative pivots of T - x I.  A zero pivot gives rcp = inf, the next pivot -inf (counted), rcp(-inf) = -0.
+    // The sign bit of every pivot is shifted into one word (v_alignbit_b32: one instruction per pivot) and counted once.  It
+    // differs from `qv < 0` on a pivot of -0 only, and a fused -e2 r + (d - x) rounds to -0 only from a negative value that
+    // underflowed (e2 > 0, and d - x is -0 for d = -0, x = +0 alone): the sign bit is the sign of the pivot.  (The NumPy
+    // model has counted sign bits all along.)
+    auto sturm = [&](float x) {
         float qv = d[0] - x;
         unsigned sg = __float_as_uint(qv) >> 31;
 #pragma unroll
@@ -215,7 +224,29 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
             qv = fmaf(-e2[m - 1], __builtin_amdgcn_rcpf(qv), d[m] - x);
             sg = __builtin_amdgcn_alignbit(sg, __float_as_uint(qv), 31);
         }
-        const int cnt = __builtin_popcount(sg);
+        return __builtin_popcount(sg);
+    };
+    float lo = -1e-3f * nrmF, hi;
+    {
+        // The wide first step: every quad still searches the same interval, so lane l counts the eigenvalues below
+        // lo + (l + 1) (hi - lo) / 65, 64 distinct points.  The counts are monotone in the lane, and nb_m, the number of lanes whose
+        // count is <= m, places eigenvalue m in the nb_m-th 65th of the interval.  One wave vote and a scalar population count per
+        // eigenvalue; v_writelane puts nb_m into lane m of one register and a single crossbar trip hands quad i its own.
+        const float wd = 1.002f * nrmF;
+        const int cnt = sturm(fmaf(wd, (float)(lane + 1) * (1.f / 65.f), lo));
+        int nbv = 0;
+        tp_vote<0>(cnt, nbv);
+        const float nb = (float)__builtin_amdgcn_ds_bpermute(i << 2, nbv);
+        const float w65 = (1.f / 65.f) * wd;
+        lo = fmaf(nb, w65, lo);
+        hi = lo + w65;
+    }
+    // The quad steps: lane (i, jq) counts the eigenvalues below lo + (jq + 1) (hi - lo) / 5
+    const float frac = 0.2f * (float)(jq + 1);
+#pragma unroll 1
+    for (int st = 0; st < kTpQuadSteps; ++st) {
+        const float wd = hi - lo;
+        const int cnt = sturm(fmaf(wd, frac, lo));
         // The points are monotone in jq, so the number nb of the quad's points at or below eigenvalue i places it: the new interval
         // is the nb-th fifth of the old one.  A quad sum (two v_add_f32_dpp) and three operations; the min / max over the quad of
         // the points themselves was sixteen instructions (a v_mov_b32_dpp and the canonicalising v_max_f32 of every operand).
@@ -225,20 +256,26 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
         lo = fmaf(nb, w5, lo);
         hi = lo + w5;
     }
-    const float lam = 0.5f * (lo + hi);
+    // The inverse iteration below is one lane's work, and a quad would run it four times over.  Instead each lane of the quad takes
+    // a shift of its own, the points 1/8, 3/8, 5/8 and 7/8 of the final interval, and the best of the four is kept: two more bits
+    // of the eigenvalue at no instruction.
+    const float lsh = fmaf(hi - lo, 0.125f + 0.25f * (float)jq, lo);
     stamp(13);
 
-    // ---- 3. eigenvector i: two inverse-iteration steps on T - lam I, unpivoted L D L^T (pivots kept at least 1e-9 ||C|| away from
+    // ---- 3. eigenvector i: two inverse-iteration steps on T - lsh I, unpivoted L D L^T (pivots kept at least 1e-9 ||C|| away from
     // zero), start vector ones + e_i, normalised after each step.  No reorthogonalisation: the refinement's E = V^H V - I takes it.
+    // The pivots' reciprocals are the bare v_rcp_f32 (1 ulp): the factorisation only has to serve an iteration whose result the
+    // refinement certifies, and 1-ulp noise on them leaves the model's one-step share where it is (99.67 % against 99.69 % over 32 768
+    // bench bins, 99.66 % against 99.62 % over 8 192: inside the sampling error of either).
     float l[N - 1], rdg[N], xv[N];
     {
         const float tiny = 1e-9f * nrmF;
-        float piv = d[0] - lam;
+        float piv = d[0] - lsh;
 #pragma unroll
         for (int m = 0; m < N; ++m) {
-            if (m > 0) piv = fmaf(-e[m - 1], l[m - 1], d[m] - lam);
+            if (m > 0) piv = fmaf(-e[m - 1], l[m - 1], d[m] - lsh);
             piv = copysignf(fmaxf(fabsf(piv), tiny), piv);
-            rdg[m] = rcp_full(piv);
+            rdg[m] = __builtin_amdgcn_rcpf(piv);
             if (m < N - 1) l[m] = e[m] * rdg[m];
         }
     }
@@ -261,29 +298,43 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
 #pragma unroll
         for (int m = 0; m < N; ++m) nrm2 = fmaf(xv[m], xv[m], nrm2);
     }
+    // The lane whose second step grew the normalised vector most has the shift nearest the eigenvalue: it wins.  nrm2 is a sum of
+    // squares, and non-negative floats order as their bit patterns do, so the quad maximum is two integer DPP stages (no
+    // canonicalising moves).  3 - jq in the two lowest bits makes the four keys distinct, so exactly one lane wins and a tie goes
+    // to the lowest jq; the comparison is unsigned, so a NaN of either sign wins and fails the gate below.
+    const unsigned key = (__float_as_uint(nrm2) & ~3u) | (unsigned)(3 - jq);
+    unsigned kmx = key;
+    kmx = max(kmx, (unsigned)__builtin_amdgcn_update_dpp(0, (int)kmx, 0xB1, 0xf, 0xf, true));
+    kmx = max(kmx, (unsigned)__builtin_amdgcn_update_dpp(0, (int)kmx, 0x4E, 0xf, 0xf, true));
+    const bool win = key == kmx;
     const bool finite = nrm2 > 0.f && nrm2 < 3.0e38f;
     {
         const float s = rsq_full(nrm2);
 #pragma unroll
         for (int m = 0; m < N; ++m) xv[m] *= s;
     }
-    if (jq == 0) {
+    if (win) {
 #pragma unroll
         for (int m = 0; m < N; ++m) fX[m * LDX + i] = xv[m];
     }
+    // the winner's shift is the quad's eigenvalue: a quad sum of it and three zeros (exact; a NaN stays a NaN)
+    const float lam = tp_sum_quad(win ? lsh : 0.f);
     stamp(14);
     // eigenvalues closer than 1e-5 ||C|| (none on the bench data) may leave nearly parallel vectors, and the double-sweep fall-back
     // after the refinement only orthonormalises V32: it cannot restore a direction V32 lacks.  Such a bin is not trusted (double
-    // sweeps on C itself), like a rank-deficient one.  kTpApart is 1e-5 widened by the multisection's own error.  The gap to the
-    // next eigenvalue is one crossbar trip from quad i + 1 (quad 15 reads quad 0 and does not use it).
+    // sweeps on C itself), like a rank-deficient one.  kTpApart is 1e-5 widened by the multisection's own error.  Two eigenvalues
+    // that share a final interval may win with the same shift: their gap reads <= 0 and the bin goes the same way, rightly, their
+    // true gap being under kTpFinal.  The gap to the next eigenvalue is one crossbar trip from quad i + 1 (quad 15 reads quad 0
+    // and does not use it).
     const float gap = tp_from(lam, (lane + 4) & 63) - lam;
     const bool apart = i == N - 1 || gap > kTpApart * nrmF;
     // spread of the spectrum, as the one-sided solve's gate.  Quad i holds eigenvalue i and the multisection delivers them in
-    // ascending order (the Sturm count is one function of x for all quads), so the smallest is quad 0's and the largest quad 15's:
-    // two readlanes, no reduction.  Any NaN, a non-finite vector or a close pair fails the gate: a NaN in quad 0 or 15 fails the
-    // comparison, one anywhere fails `lam == lam` (and leaves its own vector non-finite and its neighbour's gap NaN).
+    // ascending order (the Sturm count is one function of x for all quads, and the shifts lie inside the intervals), so the smallest
+    // is quad 0's and the largest quad 15's: two readlanes, no reduction.  Any NaN, a non-finite winning vector or a close pair fails
+    // the gate: a NaN in quad 0 or 15 fails the comparison, one anywhere fails `lam == lam` (and leaves its own vector non-finite
+    // and its neighbour's gap NaN).
     const float mn = tp_lane(lam, 0), mx = tp_lane(lam, 63);
-    const bool ok = (mn >= 1e-3f * mx) && !__any(!finite || !apart || !(lam == lam));
+    const bool ok = (mn >= 1e-3f * mx) && !__any((win && !finite) || !apart || !(lam == lam));
     wsync();
 
     // ---- 4. V32 = Q X on the f32 matrix cores (X is real: eight products)

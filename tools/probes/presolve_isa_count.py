@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Static instruction counts of the float32 pre-solve (tridiag_presolve16) in the product instantiation of the order-16 float64
 kernel, gevd16m_kernel_f64<true, float2, false>.  Compiles kernels_gevd16m.hip to gfx950 assembly with hipcc (no GPU needed)
-and splits the common path of the function into the three regions of DESIGN 4.1:
+and splits the common path of the function into the regions of DESIGN 4.1:
 
   Householder reduction       from the first v_sqrt_f32 / v_rsq_f32 after the last f64 MFMA in front of the Sturm loop
-                              (the scalar chain of reflector 0) to the head of the Sturm loop
-  Sturm multisection          the body of the one loop that holds the 15 v_rcp_f32 of the recurrence, times its 9 steps
+                              (the scalar chain of reflector 0) to the wide step
+  wide multisection step      from the first of the last 15 v_rcp_f32 in front of the Sturm loop (the recurrence of the
+                              wave-wide first step, straight-line code) to the head of the loop: the recurrence, the sixteen
+                              votes and v_writelane_b32, the interval update (the scheduler moves a few instructions of the
+                              reduction's end in here and the step's point out: the split is good to about five)
+  quad steps                  the body of the one loop that holds the 15 v_rcp_f32 of the recurrence, times its 6 steps
   inverse iteration, gate, QX from the loop's end to the last v_mfma_f32
 
 and prints VGPRs, spills, scratch, LDS and, per region, the VALU count (every v_* but the MFMAs), s_nop, other SALU, ds_bpermute
@@ -24,7 +28,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(ROOT, "ap_vast_unofficial_amd", "csrc", "kernels_gevd16m.hip")
 KERNEL = "gevd16m_kernel_f64ILb1E15HIP_vector_typeIfLj2EELb0EE"      # <true, float2, false>
-STEPS = 9                                                               # kTpSteps
+STEPS = 6                                                               # kTpQuadSteps
 
 
 def compile_asm(path):
@@ -100,7 +104,10 @@ def main():
     last_f64 = max(i for i in range(loop[0]) if body[i].strip().startswith("v_mfma_f64"))
     red0 = next(i for i in range(last_f64, loop[0]) if body[i].strip().startswith(("v_sqrt_f32", "v_rsq_f32")))
     last_f32 = max(i for i, l in enumerate(body) if l.strip().startswith("v_mfma_f32"))
-    regions = [("Householder reduction", body[red0:loop[0]], 1), (f"Sturm multisection, loop body x {STEPS}", body[loop[0]:loop[1]], STEPS),
+    rcps = [i for i in range(red0, loop[0]) if body[i].strip().startswith("v_rcp_f32")]
+    wide0 = rcps[-15]
+    regions = [("Householder reduction", body[red0:wide0], 1), ("wide multisection step", body[wide0:loop[0]], 1),
+               (f"quad steps, loop body x {STEPS}", body[loop[0]:loop[1]], STEPS),
                ("inverse iteration, gate, Q X", body[loop[1]:last_f32 + 1], 1)]
     print(f"gevd16m_kernel_f64<true, float2, false>: {meta.get('NumVgprs')} VGPRs, {spills} spill stores / {reloads} reloads, "
           f"{meta.get('ScratchSize')} B scratch, {meta.get('LDSByteSize')} B LDS")
@@ -111,7 +118,7 @@ def main():
         total += c["valu"] * mult
         f = (lambda v: f"{v} x {mult}") if mult > 1 else str
         print(f"| {name} | {f(c['valu'])} | {f(c['s_nop'])} | {f(c['salu'])} | {c['ds_bpermute']} | {c['ds_other']} | {c['mfma']} |")
-    print(f"| the three together | {total} | | | | | |")
+    print(f"| together | {total} | | | | | |")
     top = collections.Counter(re.sub(r"_e(32|64)$", "", x) for x in map(mnemonic, regions[0][1]) if x and x.startswith("v_"))
     print("\nreduction, VALU by mnemonic: " + ", ".join(f"{k} {v}" for k, v in top.most_common(args.top)))
 

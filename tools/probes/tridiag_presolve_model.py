@@ -9,11 +9,17 @@ over bins and in the kernel's order of operations:
      ||x|| = n^2 rsq(n^2) carries a random error of up to 1 ulp, as the bare v_rsq_f32 does (ULP_NOISE=0: correctly
      rounded); 1/|alpha| and gamma take a Newton step in the kernel.  With bare instructions for all three the share of
      bins inside the one-step guard falls from 99.70 % to 99.53 %;
-  2. eigenvalues by Sturm-count multisection: NPTS points per eigenvalue per step (the interval shrinks NPTS + 1 times),
-     NSTEP steps, q_i = (a_i - x) - e_{i-1}^2 rcp(q_{i-1}); the kernel runs 4 points (four lanes, one count each) and
-     NSTEP_KERNEL steps (the refinement that follows certifies the result: DESIGN 4.1 has the pass rates of 6 to 10 steps);
+  2. eigenvalues by Sturm-count multisection, q_i = (a_i - x) - e_{i-1}^2 rcp(q_{i-1}), NSTEP Sturm evaluations per lane:
+     a WIDE first step (all sixteen quads search the same interval, so the 64 lanes count at lo + (l + 1) (hi - lo) / 65 and
+     eigenvalue m takes the 65th that holds it: nb_m = number of lanes whose count is <= m), then NSTEP - 1 quad steps of
+     NPTS points per eigenvalue (the interval shrinks NPTS + 1 times; the kernel runs 4 points, four lanes with one count
+     each).  The kernel runs NSTEP_KERNEL evaluations (the refinement that follows certifies the result: DESIGN 4.1 has the
+     pass rates).  SCHEME without "wide" runs NSTEP quad steps, the scheme before the wide step;
   3. eigenvectors by two inverse-iteration steps on T - lam I, unpivoted L D L^T (the Sturm recurrence at the shift), start
-     vector ones + e_m, normalised after each step;
+     vector ones + e_m, normalised after each step.  BEST OF FOUR: lane jq of the quad takes the shift
+     lo + (1/8 + jq/4) (hi - lo) of the final interval, and the lane whose second step grew the normalised vector most
+     (the largest squared norm before the last normalisation, compared as an integer with 3 - jq in its two lowest bits: a
+     tie goes to the lowest jq) delivers the vector and the quad's eigenvalue.  SCHEME without "best4" takes the midpoint;
      two neighbouring eigenvalues whose MEASURED gap is not above apart_threshold(NSTEP) ||C|| send the bin to the double
      sweeps in the kernel (none on the bench data): 1e-5 widened by twice the multisection's own error, so that every pair
      whose true gap is under 1e-5 ||C|| goes there.  `trust` below carries this gate and the spread gate;
@@ -22,7 +28,11 @@ over bins and in the kernel's order of operations:
 It prints the share of bins whose refinement matrix Z_ij = (S_ij - d_j E_ij) / (d_j - d_i), taken in float64 against the
 exact C, meets the kernel's one-step guard |Z| <= 3e-5 and its second-step limit 1e-2, on bench.synth(K, 1234).
 
-    python tools/probes/tridiag_presolve_model.py [K] [NSTEP] [NPTS]
+    python tools/probes/tridiag_presolve_model.py [K] [NSTEP] [NPTS] [SCHEME]
+
+SCHEME: "wide+best4" (the kernel's), "wide", "best4" or "quad".  The reciprocals of the L D L^T pivots carry 1-ulp noise too,
+as the bare v_rcp_f32 of the kernel does, whenever the reflector scalars do (ULP_NOISE, or `rng` of presolve); RCP_NOISE=0
+takes them correctly rounded (the kernel's earlier Newton step).
 """
 import os
 import sys
@@ -33,18 +43,27 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 f32 = np.float32
 N = 16
-NSTEP_KERNEL = 9                    # kTpSteps of kernels_gevd16m.hip
+NWIDE = 64                          # points of the wide first step: one per lane
+NQUAD_KERNEL = 6                    # kTpQuadSteps of kernels_gevd16m.hip
+NSTEP_KERNEL = 1 + NQUAD_KERNEL     # Sturm evaluations per lane: the wide step and the quad steps
+SCHEME_KERNEL = "wide+best4"
 
 
-def lam_err(nstep):
-    """kTpLamErr: half the final interval of the multisection (1.002 * 5^-nstep) plus the float32 floor of the Sturm count, taken as 1e-6
-    (the largest error at ten steps, where the interval no longer matters, is 7.2e-7 on the bench bins)."""
-    return 0.5 * 1.002 * 5.0 ** -nstep + 1e-6
+def final_interval(nstep, scheme=SCHEME_KERNEL):
+    """width of the multisection's last interval in units of ||C||: 1.002 / (65 * 5^(nstep-1)) with the wide step, 1.002 * 5^-nstep without"""
+    return 1.002 / (NWIDE + 1) * 5.0 ** -(nstep - 1) if "wide" in scheme else 1.002 * 5.0 ** -nstep
 
 
-def apart_threshold(nstep):
+def lam_err(nstep, scheme=SCHEME_KERNEL):
+    """kTpLamErr: the distance from an eigenvalue to the nearest shift (an eighth of the final interval with the best of four
+    shifts, half of it with the midpoint) plus the float32 floor of the Sturm count, taken as 1e-6 (the largest error where
+    the interval no longer matters is 7.2e-7 on the bench bins)."""
+    return (0.125 if "best4" in scheme else 0.5) * final_interval(nstep, scheme) + 1e-6
+
+
+def apart_threshold(nstep, scheme=SCHEME_KERNEL):
     """kTpApart, in units of ||C||"""
-    return 1e-5 + 2 * lam_err(nstep)
+    return 1e-5 + 2 * lam_err(nstep, scheme)
 
 
 def make_C(K, seed=1234, reg=1e-7):
@@ -118,12 +137,25 @@ def sturm_count(a, e2, x):
     return cnt
 
 
-def multisection(a, e2, nrm, nstep, npts=4):
+def multisection(a, e2, nrm, nstep, npts=4, scheme=SCHEME_KERNEL, interval=False):
+    """eigenvalue m of every bin after nstep Sturm evaluations: the midpoint of its last interval, or (lo, hi) if `interval`"""
     K = a.shape[0]
     lo = np.broadcast_to((f32(-1e-3) * nrm)[:, None], (K, N)).astype(f32).copy()
     hi = np.broadcast_to((f32(1.001) * nrm)[:, None], (K, N)).astype(f32).copy()
     m = np.arange(N)
-    for _ in range(nstep):
+    nquad = nstep
+    if "wide" in scheme and nstep > 0:
+        # all quads hold the same interval: 64 points, one per lane, and nb_m = number of lanes whose count is <= m
+        nquad = nstep - 1
+        wd = (f32(1.002) * nrm).astype(f32)                                             # hi - lo, as the kernel forms it
+        fr = (np.arange(1, NWIDE + 1).astype(f32) * f32(1 / (NWIDE + 1))).astype(f32)
+        pts = (lo[:, :1] + wd[:, None] * fr).astype(f32)                                # [K,64]
+        c = sturm_count(a, e2, pts)
+        nb = (c[:, None, :] <= m[None, :, None]).sum(2)                                 # [K,16]
+        wp = (f32(1 / (NWIDE + 1)) * wd).astype(f32)[:, None]
+        lo = (lo + nb.astype(f32) * wp).astype(f32)
+        hi = (lo + wp).astype(f32)
+    for _ in range(nquad):
         fr = (np.arange(1, npts + 1) / (npts + 1)).astype(f32)
         pts = (lo[:, :, None] + (hi - lo)[:, :, None] * fr).astype(f32)                  # [K,16,npts]
         c = sturm_count(a, e2, pts.reshape(K, -1)).reshape(K, N, npts)
@@ -133,26 +165,32 @@ def multisection(a, e2, nrm, nstep, npts=4):
         wp = (f32(1 / (npts + 1)) * (hi - lo)).astype(f32)
         lo = (lo + nb.astype(f32) * wp).astype(f32)
         hi = (lo + wp).astype(f32)
+    if interval:
+        return lo, hi
     return ((lo + hi) * f32(0.5)).astype(f32)
 
 
-def inverse_iteration(a, e, lam, nrm, steps=2, tiny_rel=1e-9):
-    """X [K,16 (row),16 (eigenvalue)]"""
-    K = a.shape[0]
+def inverse_iteration(a, e, lam, nrm, steps=2, tiny_rel=1e-9, rng=None, growth=False):
+    """X [K,16 (row),S*16 (shift)] for lam [K, S*16]: S shifts per eigenvalue, shift c belongs to eigenvalue c // S and starts from
+    ones + e_(c // S).  `growth`: also the squared norm of the last step's vector before its normalisation.  `rng`: 1-ulp noise
+    on the pivots' reciprocals."""
+    K, NS = lam.shape
+    S = NS // N
     tiny = (f32(tiny_rel) * nrm)[:, None]
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        d = np.empty((K, N, N), f32)                                    # [K, i, m]
-        l = np.empty((K, N - 1, N), f32)
+        d = np.empty((K, N, NS), f32)                                   # [K, i, c]
+        l = np.empty((K, N - 1, NS), f32)
+        rd = np.empty((K, N, NS), f32)
         q = (a[:, 0, None] - lam).astype(f32)
         for i in range(N):
             if i > 0:
                 q = ((a[:, i, None] - lam) - e[:, i - 1, None] * l[:, i - 1]).astype(f32)
             q = np.where(np.abs(q) < tiny, np.where(q < 0, -tiny, tiny), q).astype(f32)
             d[:, i] = q
+            rd[:, i] = ulp_noise(f32(1) / q, rng)
             if i < N - 1:
-                l[:, i] = (e[:, i, None] * (f32(1) / q)).astype(f32)
-        rd = (f32(1) / d).astype(f32)
-        x = (np.ones((N, N), f32) + np.eye(N, dtype=f32))[None].repeat(K, 0)     # ones + e_m: distinct per eigenvalue
+                l[:, i] = (e[:, i, None] * rd[:, i]).astype(f32)
+        x = (np.ones((N, NS), f32) + (np.arange(N)[:, None] == np.arange(NS)[None, :] // S).astype(f32))[None].repeat(K, 0)
         for _ in range(steps):
             y = x.copy()
             for i in range(1, N):
@@ -162,23 +200,47 @@ def inverse_iteration(a, e, lam, nrm, steps=2, tiny_rel=1e-9):
                 z[:, i] = (z[:, i] - l[:, i] * z[:, i + 1]).astype(f32)
             s = (z * z).sum(1, dtype=f32).astype(f32)
             x = (z / np.sqrt(s)[:, None, :]).astype(f32)
-    return x
+    return (x, s) if growth else x
 
 
-def presolve(C, nstep, npts=4, rng=None):
+def best_of_four(a, e, lo, hi, nrm, rng=None):
+    """(X [K,16,16], lam [K,16], winner [K,16]): lane jq of quad m shifts by lo + (1/8 + jq/4) (hi - lo); the lane with the
+    largest key wins, key = the bits of the squared norm of the second step with 3 - jq in the two lowest (unsigned: a NaN wins
+    and fails the gate)."""
+    K = a.shape[0]
+    fr = (f32(0.125) + f32(0.25) * np.arange(4).astype(f32)).astype(f32)
+    lam4 = (lo[:, :, None] + (hi - lo).astype(f32)[:, :, None] * fr).astype(f32)         # [K,16,4]
+    X4, s = inverse_iteration(a, e, lam4.reshape(K, 4 * N), nrm, rng=rng, growth=True)
+    key = (s.reshape(K, N, 4).view(np.uint32) & np.uint32(0xFFFFFFFC)) | (np.uint32(3) - np.arange(4).astype(np.uint32))
+    win = key.argmax(2)                                                                  # keys are distinct within a quad
+    X = np.take_along_axis(X4.reshape(K, N, N, 4), win[:, None, :, None], 3)[..., 0]
+    lam = np.take_along_axis(lam4, win[:, :, None], 2)[..., 0]
+    return X, lam, win
+
+
+def presolve(C, nstep, npts=4, rng=None, scheme=SCHEME_KERNEL, rcp_rng="as rng"):
+    """`rng`: 1-ulp noise on rsq(n^2) of the reflectors.  `rcp_rng`: 1-ulp noise on the pivots' reciprocals of the L D L^T (the
+    kernel's bare v_rcp_f32); by default a generator of its own whenever `rng` is given, None for correctly rounded ones."""
+    if isinstance(rcp_rng, str):
+        rcp_rng = np.random.default_rng(11) if rng is not None else None
     nf2 = (np.abs(C) ** 2).sum((1, 2))
     sexp = -(np.frexp(nf2)[1] - 1) // 2
     A = (C * np.ldexp(1.0, sexp)[:, None, None]).astype(np.complex64)
     nrm = np.sqrt(np.ldexp(nf2, 2 * sexp)).astype(f32)
     a, e, e2, Q, delta = tridiag(A, rng)
-    lam = multisection(a, e2, nrm, nstep, npts)
-    X = inverse_iteration(a, e, lam, nrm)
+    if "best4" in scheme:
+        lo, hi = multisection(a, e2, nrm, nstep, npts, scheme, interval=True)
+        X, lam, _ = best_of_four(a, e, lo, hi, nrm, rcp_rng)
+    else:
+        lam = multisection(a, e2, nrm, nstep, npts, scheme)
+        X = inverse_iteration(a, e, lam, nrm, rng=rcp_rng)
     Q = (Q * delta[:, None, :]).astype(np.complex64)                    # the phases go back into Q's columns
     V = (Q @ X.astype(np.complex64)).astype(np.complex64)
     # the kernel's gate: spread under 1e3 (smallest and largest are eigenvalue 0 and 15: they come out sorted), every
-    # neighbouring pair apart, nothing NaN
+    # neighbouring pair apart (two eigenvalues that share a final interval may win with the same shift: their gap reads <= 0),
+    # nothing NaN
     with np.errstate(invalid="ignore"):
-        apart = (np.diff(lam, axis=1) > f32(apart_threshold(nstep)) * nrm[:, None]).all(1)
+        apart = (np.diff(lam, axis=1) > f32(apart_threshold(nstep, scheme)) * nrm[:, None]).all(1)
         trust = (lam[:, 0] >= f32(1e-3) * lam[:, -1]) & apart & np.isfinite(X).all((1, 2)) & ~np.isnan(lam).any(1)
     return V, lam, trust, (a, e, Q, A)
 
@@ -201,8 +263,11 @@ def main():
     K = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
     nstep = int(sys.argv[2]) if len(sys.argv) > 2 else NSTEP_KERNEL
     npts = int(sys.argv[3]) if len(sys.argv) > 3 else 4
+    scheme = sys.argv[4] if len(sys.argv) > 4 else SCHEME_KERNEL
     C = make_C(K)
-    V, lam, trust, (a, e, Q, A) = presolve(C, nstep, npts, np.random.default_rng(7) if os.environ.get("ULP_NOISE", "1") != "0" else None)
+    noise = os.environ.get("ULP_NOISE", "1") != "0"
+    V, lam, trust, (a, e, Q, A) = presolve(C, nstep, npts, np.random.default_rng(7) if noise else None, scheme,
+                                           np.random.default_rng(11) if noise and os.environ.get("RCP_NOISE", "1") != "0" else None)
     # the reduction itself: (Q diag(delta))^H A (Q diag(delta)) tridiagonal and real
     T = Q.conj().transpose(0, 2, 1).astype(np.complex128) @ A.astype(np.complex128) @ Q.astype(np.complex128)
     Tm = np.zeros_like(T)
@@ -211,7 +276,7 @@ def main():
     Tm[:, idx[1:], idx[:-1]] = e
     Tm[:, idx[:-1], idx[1:]] = e
     nrm = np.sqrt((np.abs(A.astype(np.complex128)) ** 2).sum((1, 2)))
-    print(f"bins {K}, multisection steps {nstep}, {npts} points per eigenvalue per step")
+    print(f"bins {K}, scheme {scheme}: {nstep} Sturm evaluations, {npts} points per eigenvalue per quad step")
     print(f"reduction: max |Q^H A Q - T| / ||A|| = {(np.abs(T - Tm).max((1, 2)) / nrm).max():.2e}, "
           f"max |Q^H Q - I| = {np.abs(Q.conj().transpose(0, 2, 1) @ Q - np.eye(N)).max():.2e}")
     lref = np.linalg.eigvalsh(C)
@@ -220,7 +285,7 @@ def main():
     z = zmax(C, V)
     t = trust
     gaps = np.diff(lref, axis=1).min(1) / np.sqrt((np.abs(C) ** 2).sum((1, 2)))
-    print(f"trusted {t.mean() * 100:.2f} % (spread < 1e3 and measured gaps > {apart_threshold(nstep):.3g} ||C||; smallest true gap {gaps.min():.2e} ||C||, "
+    print(f"trusted {t.mean() * 100:.2f} % (spread < 1e3 and measured gaps > {apart_threshold(nstep, scheme):.3g} ||C||; smallest true gap {gaps.min():.2e} ||C||, "
           f"{(gaps < 1e-5).sum()} bins under 1e-5, {(~t & (gaps >= 1e-5)).sum()} untrusted above it)")
     print(f"|Z| <= 3e-5: {(z[t] <= 3e-5).mean() * 100:.2f} % of trusted bins, <= 1e-2: {(z[t] <= 1e-2).mean() * 100:.3f} %")
     print(f"max |Z| median / p99 / max: {np.median(z[t]):.2e} / {np.quantile(z[t], 0.99):.2e} / {z[t].max():.2e}")
