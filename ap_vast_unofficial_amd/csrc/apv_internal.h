@@ -19,7 +19,8 @@ struct GevdParams {
     double reg_bright;
     int reg_mode;
     int max_sweeps;
-    int debug_stop;    // profiling aid: return after stage N (1 = correlate, 2 = Cholesky, 3 = whitening); 0 = run everything
+    int debug_stop;    // profiling aid: return after stage N (1 = correlate, 2 = Cholesky, 3 = whitening); 0 = run everything.  Values above 3:
+                       // A/B switches of the diagnostic order-16 (4, 5, 9, 10: kernels_gevd16m.hip) and order-64 (4..8) kernels
     double sweep_tol2; // Jacobi stop threshold on off^2/||C||_F^2 seen during a sweep; 0 = per-dtype default
     int out_c128;
     // fused input: c64, or c128 when x_c128 is set (the float64 streaming front-end)

@@ -576,7 +576,7 @@ __device__ __forceinline__ void jacobi16_sweep0(Cx<TT>& tt_, Cx<TT>& tb_, Cx<TT>
     tt_ = tt; tb_ = tb; bt_ = bt; bb_ = bb; v0t_ = v0t; v0b_ = v0b; v1t_ = v1t; v1b_ = v1b;
 }
 
-// ---- float32 ONE-SIDED Jacobi (Hestenes) for the pre-solve of the float64 order-16 kernel -------------------------------
+// ---- float32 ONE-SIDED Jacobi (Hestenes): the solve of the float32 order-16 kernel ----------------------------------------
 // With G G^H = C, column rotations G <- G J leave G G^H alone and end with orthogonal columns G J = U Sigma, so the
 // normalised columns ARE the eigenvectors of C: no accumulation of V, no two-sided update of C.  A round rotates one
 // 16 x 16 array once (12 packed operations per lane) where the two-sided form rotates three (36), the pivots
@@ -596,19 +596,14 @@ __device__ __forceinline__ float colsum8(float v) {
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true));
     return v;
 }
-__device__ __forceinline__ void xchg_f(float& top, float& bot, bool bit, int peer) {
-    const float send = bit ? top : bot;
-    const float recv = __shfl(send, peer, 64);
-    if (bit) top = recv; else bot = recv;
-}
 
 // float32 Cholesky factor of (2^sexp C + delta I) from the matrix in sA, left in fG [16][LDF].  The elimination runs from
 // the LAST index to the first (the indices are reversed on the way in and on the way out), i.e. fG is the UPPER factor U with
 // U U^H = C: on the whitened matrices of this path the one-sided sweeps that follow need 0.7 sweeps fewer from it than from
 // the lower factor (5.5 -> 4.8 on the bench workload; a diagonally pivoted factor would save 0.9 and cost a wave-wide argmax
 // per step).  Lane (i = lane >> 2, jq = lane & 3) owns row i, columns jq + 4t; one column goes through LDS per step.
-// A pivot that is not positive is clamped: the factor only seeds the pre-solve, whose result the float64 refinement
-// certifies against the exact C.
+// A pivot that is not positive is clamped: the caller trusts the sweeps' result only if they converged on a spectrum that
+// spans less than 1e3, and runs the two-sided sweeps on C itself otherwise.
 __device__ __forceinline__ float scale_to_f32(double v, int e) { return (float)ldexp(v, e); }
 __device__ __forceinline__ float scale_to_f32(float v, int e) { return ldexpf(v, e); }
 template <typename TS, int LDA, int LDF>

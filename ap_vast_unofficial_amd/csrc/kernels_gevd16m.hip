@@ -354,9 +354,11 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
 }
 
 // XT: element type of the fused input slabs (float2 = c64, double2 = c128: the float64 streaming front-end)
-// DBG: the diagnostic instantiation.  It alone carries the run-time `debug_stop` tests (stage cuts and A/B switches of the
-// probes under tools/probes/) and the in-kernel stage stamps (p.stamps); in the product instantiation `dstop` is the constant 0
-// and all of it folds away, the round-2a two-sided pre-solve included.
+// DBG: the diagnostic instantiation.  It alone carries the run-time `debug_stop` tests and the in-kernel stage stamps (p.stamps);
+// in the product instantiation `dstop` is the constant 0 and all of it folds away.  debug_stop: 1, 2, 3 return after stage 0, 1,
+// 2; 4 skips the float32 pre-solve (double sweeps only); 5 always takes the guarded path (double sweeps after the pre-solve);
+// 9 marks the bins by the refinement step they miss (status 8 / 16); 10 switches the refinement's guard off (results invalid).
+// Any other value runs the whole kernel.
 // HOPS: the launch covers several hops of a chunk (blockIdx.z = hop): every operand moves on by its byte stride per hop (scalar
 // arithmetic on the argument block; the instantiations without it are untouched)
 template <typename T, bool FUSED, typename XT, bool DBG, int GS = 1, bool HOPS = false>
@@ -558,81 +560,22 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
             // the matrix cores (below); W waits in registers meanwhile.
             if (dstop != 4) {
                 using CF = Cx<float>;
-                // looser than the float kernel's own 1e-8: the refinement follows anyway, so the float sweep that would only confirm
-                // convergence is not run (1e-6 measured best: at 1e-5 so many more bins need a second refinement step that the launch
-                // is 5 % slower, tools/probes/presolve_tol.py; debug_stop = 20 + e sets 1e-e)
-                constexpr float kPresolveTol2 = 1e-6f;
-                CF f0t, f0b, f1t, f1b;
-                bool fconv = false, trust = true;
-                int fs = 0;
-                int va = a, vb = b;                                                   // (row pair, slot) of this lane's part of V32
                 CF v32[4];
-                // debug_stop 11-14 and 20-49 (diagnostic instantiation only): the earlier pre-solves, for A/B timing -- 11 the
-                // two-sided float sweeps of round 2a, 14 the one-sided form (12 and 13 stop after its factor and after its sweeps,
-                // 20 + e sets its tolerance 1e-e, 30-49 fine steps of it)
-                const bool legacy = DBG && ((dstop >= 11 && dstop <= 14) || (dstop >= 20 && dstop <= 49));
-                if (!legacy) {
-                    // Householder tridiagonal, multisection and inverse iteration (tridiag_presolve16); its scratch is sB, free until V32
-                    // lands there (W waits in registers)
-                    CF* const fQ = reinterpret_cast<CF*>(&sB[0]);
-                    trust = tridiag_presolve16<T>(sA, sexp, (float)normS2, fQ, reinterpret_cast<float*>(fQ + N * LDQ), lane, v32, stamp);
-                } else if (dstop != 11) {
-                    // one-sided form on the float Cholesky factor of 2^sexp C + delta I (same eigenvectors; the shift keeps the
-                    // float pivots positive when C is singular to float precision).  The factor goes through sB, which is free
-                    // until V32 lands there (W waits in registers), its column staging through the spent Cholesky staging.
-                    constexpr int LDF = 17;
-                    constexpr float kShift = 8e-6f;                                   // x ||C||_F (scaled to ~1)
-                    CF* const fG = reinterpret_cast<CF*>(&sB[0]);
-                    CF (*const fcol)[16] = reinterpret_cast<CF(*)[16]>(&scol[0][0]);
-                    chol16_f32<T, LD, LDF>(sA, sexp, kShift * sqrtf((float)normS2), fG, fcol, lane);
-                    stamp(4);
-                    if (dstop == 12) return;                                   // timing aids: 12 after the float factor, 13 after the sweeps
-                    va = lane & 7; vb = lane >> 3;                                   // the one-sided solve's layout: lane = a + 8 b
-                    f0t = fG[(2 * va) * LDF + vb]; f0b = fG[(2 * va) * LDF + 8 + vb];
-                    f1t = fG[(2 * va + 1) * LDF + vb]; f1b = fG[(2 * va + 1) * LDF + 8 + vb];
-                    float n2t, n2b;
-                    fs = jacobi16_onesided<LDF>(f0t, f0b, f1t, f1b, lane, (dstop >= 20 && dstop <= 27) ? __builtin_powif(10.f, 20 - dstop) : (dstop >= 30 && dstop <= 49) ? 0.5e-6f * (float)(dstop - 29) : kPresolveTol2, (float)normS2, Prec<float>::max_sweeps, fconv, n2t, n2b, fG);
-                    trust = fconv && spectrum_ok(n2t, n2b);
-                    stamp(5);
-                    if (dstop == 13) {
-                        if (lane == 0 && pstatus != nullptr) pstatus[k] = fs;        // sweeps of the pre-solve
-                        return;
-                    }
-                } else {
-                    // debug_stop == 11: round 2a's two-sided pre-solve (A/B timing)
-                    auto ldf = [&](int r, int c) {
-                        const C v = sA[r * LD + c];
-                        return mk<float>((float)ldexp((double)v.x, sexp), (float)ldexp((double)v.y, sexp));
-                    };
-                    CF ftt = ldf(a, b), ftb = ldf(a, 8 + b), fbt = ldf(8 + a, b), fbb = ldf(8 + a, 8 + b);
-                    f0t = mk<float>((2 * a == b) ? 1.f : 0.f, 0.f); f0b = mk<float>((2 * a == 8 + b) ? 1.f : 0.f, 0.f);
-                    f1t = mk<float>((2 * a + 1 == b) ? 1.f : 0.f, 0.f); f1b = mk<float>((2 * a + 1 == 8 + b) ? 1.f : 0.f, 0.f);
-                    fs = jacobi16_sweeps<float>(ftt, ftb, fbt, fbb, f0t, f0b, f1t, f1b, (float (*)[4]) nullptr, lane,
-                                                kPresolveTol2, (float)normS2, Prec<float>::max_sweeps, fconv);
-                }
+                // Householder tridiagonal, multisection and inverse iteration (tridiag_presolve16); its scratch is sB, free until V32
+                // lands there (W waits in registers)
+                CF* const fQ = reinterpret_cast<CF*>(&sB[0]);
+                const bool trust = tridiag_presolve16<T>(sA, sexp, (float)normS2, fQ, reinterpret_cast<float*>(fQ + N * LDQ), lane, v32, stamp);
                 if (!trust) {
                     wsync();
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) sB[i * LD + jq + 4 * t] = wrow[t];      // the float factor went through sB: W back in place
+                    for (int t = 0; t < 4; ++t) sB[i * LD + jq + 4 * t] = wrow[t];      // the pre-solve's scratch went through sB: W back in place
                     wsync();
                 } else {
-                // columns of V32 held by this lane: where the one-sided schedule leaves them, or (debug_stop == 11) the two-sided
-                // schedules' layout after an odd / even number of sweeps
-                const bool fnat = fs & 1;
-                const int fit = (dstop != 11) ? os_top_end(vb) : (fnat ? 2 * vb : vb);
-                const int fib = (dstop != 11) ? os_bot_end(vb) : (fnat ? 2 * vb + 1 : 8 + vb);
                 const int mcol = lane & 15;
                 auto cj = [](C w) { return mk<T>(w.x, -w.y); };
                 wsync();
-                if (!legacy) {
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) sB[mfma_row<float>(lane, t) * LD + mcol] = mk<T>((T)v32[t].x, (T)v32[t].y);   // V32 takes W's place
-                } else {
-                    sB[(2 * va) * LD + fit] = mk<T>((T)f0t.x, (T)f0t.y);
-                    sB[(2 * va) * LD + fib] = mk<T>((T)f0b.x, (T)f0b.y);
-                    sB[(2 * va + 1) * LD + fit] = mk<T>((T)f1t.x, (T)f1t.y);
-                    sB[(2 * va + 1) * LD + fib] = mk<T>((T)f1b.x, (T)f1b.y);
-                }
+                for (int t = 0; t < 4; ++t) sB[mfma_row<float>(lane, t) * LD + mcol] = mk<T>((T)v32[t].x, (T)v32[t].y);   // V32 takes W's place
                 wsync();
                 C accT[4], accG[4], accC[4], accV[4];
                 cmm16([&](int r, int kx) { return sA[r * LD + kx]; }, [&](int kx, int c) { return sB[kx * LD + c]; }, lane, accT);       // C V
@@ -647,7 +590,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 //   V'' = V (I + Z),  Z_ij = (S_ij - d_j E_ij) / (d_j - d_i)  (i != j),  Z_ii = -E_ii / 2
                 // removes the float solve's error to second order: what is left is |Z|^2, the same order a double Jacobi sweep
                 // from (C', V') leaves.  |Z_ij| <= kRefineGuard on every pair keeps that below 1e-9; a wave that meets a
-                // narrower spectral gap (or a pair the float sweeps did not finish) takes the double sweeps instead.
+                // narrower spectral gap (or a pair the pre-solve did not resolve) takes the double sweeps instead.
                 constexpr double kRefineGuard2 = 9e-10;        // |Z_ij|^2 <= (3e-5)^2
                 // A step that misses the guard by less than |Z_ij| <= 1e-2 is applied all the same and followed by a second one
                 // in the rotated basis: S'' = (I+Z)^H S (I+Z) needs no C (the accumulator of S is itself an MFMA operand),
@@ -700,7 +643,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                             hopeless = hopeless || !(zz <= (T)kSecondStep2);
                             z = mk<T>(zx, zy);
                             // second-order term of the eigenvalue of the pencil (S, Gram) next to d_i: -|S_ij - d_i E_ij|^2 / (d_j - d_i).
-                            // (Exact to third order in Z AND E: the one-sided pre-solve leaves E ~ 1e-5 between the columns of small
+                            // (Exact to third order in Z AND E: a float32 pre-solve can leave E ~ 1e-5 between the columns of small
                             // eigenvalues, where a formula that orthonormalises to first order only is off by E^2.)
                             const T nx = __builtin_fma(-di, accG[t].x, accC[t].x), ny = __builtin_fma(-di, accG[t].y, accC[t].y);
                             l2 = -(nx * nx + ny * ny) * inv;
@@ -795,26 +738,25 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
             }
         }
         if constexpr (sizeof(T) == 4) {
-            // float kernel: the one-sided form IS the solve (debug_stop == 11: the two-sided sweeps below, for A/B timing).
-            // Eigenvalues are the squared column norms less the shift, eigenvectors the normalised columns.
-            if (dstop != 11) {
-                constexpr int LDF = 17;
-                constexpr float kShift = 8e-6f;
-                const float delta = kShift * sqrtf((float)normS2);
-                Cx<float>* const fG = reinterpret_cast<Cx<float>*>(&sB[0]);
-                Cx<float> (*const fcol)[16] = reinterpret_cast<Cx<float>(*)[16]>(&scol[0][0]);
-                chol16_f32<T, LD, LDF>(sA, sexp, delta, fG, fcol, lane);
-                const int oa = lane & 7, ob = lane >> 3;                        // the one-sided solve's layout: lane = a + 8 b
-                Cx<float> g0t = fG[(2 * oa) * LDF + ob], g0b = fG[(2 * oa) * LDF + 8 + ob];
-                Cx<float> g1t = fG[(2 * oa + 1) * LDF + ob], g1b = fG[(2 * oa + 1) * LDF + 8 + ob];
-                float n2t, n2b;
-                (void)jacobi16_onesided<LDF>(g0t, g0b, g1t, g1b, lane, (float)tol2, (float)normS2, max_sweeps, converged, n2t, n2b, fG);
-                const bool trust = converged && spectrum_ok(n2t, n2b);
-                converged = false;
-                wsync();
+            // float kernel: the one-sided form IS the solve.  Eigenvalues are the squared column norms less the shift, eigenvectors
+            // the normalised columns.
+            constexpr int LDF = 17;
+            constexpr float kShift = 8e-6f;
+            const float delta = kShift * sqrtf((float)normS2);
+            Cx<float>* const fG = reinterpret_cast<Cx<float>*>(&sB[0]);
+            Cx<float> (*const fcol)[16] = reinterpret_cast<Cx<float>(*)[16]>(&scol[0][0]);
+            chol16_f32<T, LD, LDF>(sA, sexp, delta, fG, fcol, lane);
+            const int oa = lane & 7, ob = lane >> 3;                        // the one-sided solve's layout: lane = a + 8 b
+            Cx<float> g0t = fG[(2 * oa) * LDF + ob], g0b = fG[(2 * oa) * LDF + 8 + ob];
+            Cx<float> g1t = fG[(2 * oa + 1) * LDF + ob], g1b = fG[(2 * oa + 1) * LDF + 8 + ob];
+            float n2t, n2b;
+            (void)jacobi16_onesided<LDF>(g0t, g0b, g1t, g1b, lane, (float)tol2, (float)normS2, max_sweeps, converged, n2t, n2b, fG);
+            const bool trust = converged && spectrum_ok(n2t, n2b);
+            converged = false;
+            wsync();
 #pragma unroll
-                for (int t = 0; t < 4; ++t) sB[i * LD + jq + 4 * t] = wrow[t];          // W back in place (stage 5, or the sweeps below)
-                if (trust) {
+            for (int t = 0; t < 4; ++t) sB[i * LD + jq + 4 * t] = wrow[t];          // W back in place (stage 5, or the sweeps below)
+            if (trust) {
                 const int it_b = os_top_end(ob), ib_b = os_bot_end(ob);
                 wsync();
                 sA[(2 * oa) * LD + it_b] = mk<T>(g0t.x, g0t.y);
@@ -826,9 +768,8 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                     sLam[ib_b] = (T)ldexpf(n2b - delta, -sexp);
                 }
                 refined = true;
-                }
-                wsync();
             }
+            wsync();
         }
         if (!refined) {
             C tt = sA[a * LD + b], tb = sA[a * LD + 8 + b], bt = sA[(8 + a) * LD + b], bb = sA[(8 + a) * LD + 8 + b];

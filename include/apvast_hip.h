@@ -94,7 +94,7 @@ typedef struct apv_config {
     int32_t block_size;       /* N : STFT length for the streaming entry points (0 = kernel-level use only); any even N in [4, 4096], above that up to 8192 with N/2 = 2^a 3^b 5^c 7^d (float32 front end) */
     int32_t hop_size;         /* H */
     int32_t n_zones;          /* streaming: bit mask of zone programs, 1 = A, 2 = B (run_A/run_B, apvast.py:53-54) */
-    int32_t debug_stop;       /* profiling aid: stop the fused kernel after stage n (0 = run everything) */
+    int32_t debug_stop;       /* profiling aid (0 = run everything): 1, 2, 3 stop the update kernels after stage n; the order-16 kernel also takes 4 (double sweeps only), 5 (guarded path always), 9 (mark bins by the refinement step they miss), 10 (guard off, results invalid); the order-64 kernel gives 4..8 its own meanings */
     int32_t dialect;          /* APV_DIALECT_PYTHON | APV_DIALECT_MATLAB: the broadband stream's statistics/loading/rank conventions */
     int32_t frontend;         /* streaming (subband) front-end precision -- RIRs, FIR, rings, STFT, spectra, overlap-add:
                                  0 = follow compute_dtype (APV_F64: everything float64, as the reference's lfilter / rfft /

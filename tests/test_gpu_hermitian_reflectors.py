@@ -15,26 +15,16 @@ if ROOT not in sys.path:
 pytestmark = pytest.mark.gpu
 
 from oracle import subband  # noqa: E402  (checker only)
+from presolve_cases import cn, refinement_marks, rel_w, unitary  # noqa: E402
 
 K, L, M = 32, 16, 32
 CASES = ["zero_column_0", "zero_column_7", "zero_column_14", "real", "imaginary_first_column"]
-
-
-def rel_w(w, ref):
-    return (np.linalg.norm(w - ref, axis=-1) / np.linalg.norm(ref, axis=-1)).max()
 
 
 @pytest.fixture(scope="module")
 def Engine():
     from ap_vast_unofficial_amd import Engine
     return Engine
-
-
-def unitary(rng, n, real=False):
-    g = rng.standard_normal((n, n))
-    if not real:
-        g = g + 1j * rng.standard_normal((n, n))
-    return np.linalg.qr(g)[0]
 
 
 def bins(case, rng):
@@ -88,7 +78,7 @@ def test_inputs_have_the_structure():
 def test_special_columns_against_oracle(Engine, case):
     rng = np.random.default_rng(43)
     XB, XD = bins(case, rng)
-    d = ((rng.standard_normal((K, M)) + 1j * rng.standard_normal((K, M))) * np.sqrt(0.5)).astype(np.complex64)
+    d = cn(rng, K, M)
     ranks = (1, 16)
     eng = Engine(K, L, M, ranks=ranks, mu=0.1, compute_dtype="f64", out_c128=True)
     w, lam_gpu, status = eng.update(XB, XD, d)
@@ -109,11 +99,6 @@ def test_special_columns_stay_on_the_refinement(Engine):
     rng = np.random.default_rng(43)
     parts = [bins(case, rng) for case in CASES]
     XB, XD = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
-    Kt = XB.shape[0]
-    d = ((rng.standard_normal((Kt, M)) + 1j * rng.standard_normal((Kt, M))) * np.sqrt(0.5)).astype(np.complex64)
-    eng = Engine(Kt, L, M, ranks=(1,), mu=0.1, compute_dtype="f64", out_c128=True, debug_stop=9)
-    _, _, status = eng.update(XB, XD, d, raise_on_status=False)
-    eng.close()
-    print("status words:", dict(zip(*np.unique(status, return_counts=True))))
-    assert set(np.unique(status)) <= {0, 8, 16}
+    d = cn(rng, XB.shape[0], M)
+    status = refinement_marks(Engine, XB, XD, d, mu=0.1)
     assert np.count_nonzero(status == 16) == 0

@@ -1,10 +1,11 @@
-"""The shortened Sturm multisection of the float32 pre-solve (kernels_gevd16m.hip: kTpSteps, the `apart` gate widened by the
+"""The shortened Sturm multisection of the float32 pre-solve (kernels_gevd16m.hip: kTpQuadSteps, the `apart` gate widened by the
 multisection's own error, the spread gate read from quads 0 and 15) where it can go wrong: pairs of eigenvalues whose gap straddles
-the gate's threshold, eigenvalues that sit on the multisection's grid points, the share of bench bins that need a second refinement
-step against the NumPy model of the kernel's steps, and a NaN that must fail the gate.  L = 16, explicit R_B / R_D (R_D = I, so the
+the gate's threshold, eigenvalues that sit on the grid points of a multisection in fifths (the kernel's first step was one when
+these cases were chosen; it is a wave-wide step of a 65th now, whose own points tests/test_gpu_presolve_wide_step.py covers, and the
+old points stay as inputs like any other), the share of bench bins that need a second refinement step against the NumPy model of
+the kernel's steps, and a NaN that must fail the gate.  L = 16, explicit R_B / R_D (R_D = I, so the
 whitened C is R_B / (1 + reg)), bounds as tests/test_gpu_tridiag_presolve.py applies them to its structured spectra.
 Run on the MI355X box with `-m gpu`; the model's own share is checked without a GPU."""
-import importlib.util
 import os
 import sys
 
@@ -16,6 +17,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle import subband  # noqa: E402  (checker only)
+from presolve_cases import (binomial_bound, check_nan_bin, refinement_marks, rel_w, with_spectrum,  # noqa: E402
+                            model_second_step_share as model_share)
 
 L, M = 16, 32
 REG = 1e-7                                    # the engine's and the oracle's loading of R_D
@@ -24,20 +27,6 @@ GAPS = [1e-6, 3e-6, 7e-6, 1.2e-5, 3e-5, 1e-4, 1e-3]          # x ||C||_F
 PLACES = {"bottom": 14, "middle": 7, "top": 0}               # index of the pair's larger eigenvalue, descending order
 BINS_PER_CASE = 4
 STEP_BINS = 1024
-
-
-def rel_w(w, ref):
-    return (np.linalg.norm(w - ref, axis=-1) / np.linalg.norm(ref, axis=-1)).max()
-
-
-def unitary(rng):
-    return np.linalg.qr(rng.standard_normal((L, L)) + 1j * rng.standard_normal((L, L)))[0]
-
-
-def with_spectrum(rng, lam):
-    U = unitary(rng)
-    C = (U * lam) @ U.conj().T
-    return 0.5 * (C + C.conj().T)
 
 
 def pair_spectrum(gap, at):
@@ -49,8 +38,9 @@ def pair_spectrum(gap, at):
 
 
 def grid_spectra():
-    """Spectra with ||lam||_2 = 1 whose eigenvalues sit on points of the first multisection steps, lo + j (hi - lo) / 5 with
-    [lo, hi] = [-1e-3, 1.001] ||C||_F, and at 0.  (Not all four first-step points at once: their squares sum to 1.2.)"""
+    """Spectra with ||lam||_2 = 1 whose eigenvalues sit on points of the first two steps of a multisection in fifths,
+    lo + j (hi - lo) / 5 with [lo, hi] = [-1e-3, 1.001] ||C||_F, and at 0.  (Not all four first-step points at once: their squares
+    sum to 1.2.)"""
     lo, w = -1e-3, 1.002
     g = [lo + j * w / 5 for j in range(1, 5)]
     g2 = [g[0] + j * w / 25 for j in range(1, 5)]            # second step, inside [g_1, g_2]
@@ -138,8 +128,9 @@ def grid_points(Engine):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(grid_spectra()))
 def test_eigenvalue_at_a_multisection_point(grid_points, name):
-    """Eigenvalues on the points the first two multisection steps evaluate (a pivot of the Sturm recurrence at or next to zero) and
-    an eigenvalue 0 (a singular C: the spread gate sends it to the double sweeps)."""
+    """Eigenvalues on the points the first two steps of a multisection in fifths evaluate (where the kernel evaluated these very
+    points, a pivot of the Sturm recurrence was at or next to zero) and an eigenvalue 0 (a singular C: the spread gate sends it to
+    the double sweeps)."""
     cases, RB, res = grid_points
     check(res, cases[name], RB, simple_top=True)
 
@@ -147,14 +138,7 @@ def test_eigenvalue_at_a_multisection_point(grid_points, name):
 @pytest.fixture(scope="module")
 def model_second_step_share():
     """share of the first STEP_BINS bench-distribution bins outside the one-step guard |Z| <= 3e-5 in the NumPy model"""
-    spec = importlib.util.spec_from_file_location("tridiag_presolve_model", os.path.join(ROOT, "tools", "probes", "tridiag_presolve_model.py"))
-    model = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(model)
-    C = model.make_C(STEP_BINS)                                          # bench.synth(STEP_BINS, 1234), whitened in float64
-    V, _, trust, _ = model.presolve(C, model.NSTEP_KERNEL, 4, np.random.default_rng(7))
-    z = model.zmax(C, V)
-    assert trust.all() and (z <= 1e-2).all()
-    return float((z > 3e-5).mean())
+    return model_share(STEP_BINS)
 
 
 def test_model_second_step_share(model_second_step_share):
@@ -164,18 +148,16 @@ def test_model_second_step_share(model_second_step_share):
 @pytest.mark.gpu
 def test_step_marks(Engine, model_second_step_share):
     """debug_stop = 9 marks a bin 8 if it missed the first refinement step's guard and 16 if it missed the second step's too.
-    No bench bin may be left to the double sweeps, and the share that needs the second step may exceed the model's by at most
-    three standard deviations of a binomial count over STEP_BINS draws."""
+    No bench bin may be left to the double sweeps, and the share that needs the second step may exceed the model's (wide step,
+    NQUAD_KERNEL quad steps, best of four, 1-ulp noise on the pivots' reciprocals) by at most three standard deviations of a
+    binomial count over STEP_BINS draws."""
     import bench
     XB, XD, d = bench.synth(STEP_BINS, 1234)
-    eng = Engine(STEP_BINS, L, M, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=True, debug_stop=9)
-    _, _, status = eng.update(XB, XD, d, raise_on_status=False)
-    eng.close()
+    status = refinement_marks(Engine, XB, XD, d, mu=1.0)
     p = model_second_step_share
     share = np.count_nonzero(status == 8) / STEP_BINS
-    bound = p + 3 * np.sqrt(p * (1 - p) / STEP_BINS)
-    print(f"marks {dict(zip(*np.unique(status, return_counts=True)))}: second step {share:.4f}, model {p:.4f}, bound {bound:.4f}")
-    assert set(np.unique(status)) <= {0, 8, 16}
+    bound = binomial_bound(p, STEP_BINS)
+    print(f"second step {share:.4f}, model {p:.4f}, bound {bound:.4f}")
     assert np.count_nonzero(status == 16) == 0
     assert share <= bound, (share, p, bound)
 
@@ -183,19 +165,5 @@ def test_step_marks(Engine, model_second_step_share):
 @pytest.mark.gpu
 def test_nan_fails_the_gate(Engine):
     """A NaN in one bin's R_B (through its X_B) gives that bin a non-zero status and leaves its neighbours' results as they are
-    without it."""
-    import bench
-    K, k0 = 64, 29
-    XB, XD, d = bench.synth(K, 77)
-    eng = Engine(K, L, M, ranks=RANKS, mu=1.0, compute_dtype="f64", out_c128=True)
-    w0, lam0, st0 = eng.update(XB, XD, d, raise_on_status=False)
-    XB = XB.copy()
-    XB[k0, 3, 5] = np.nan
-    w1, lam1, st1 = eng.update(XB, XD, d, raise_on_status=False)
-    eng.close()
-    print("status of the NaN bin:", st1[k0])
-    assert not st0.any()
-    assert st1[k0] != 0
-    others = np.arange(K) != k0
-    assert not st1[others].any()
-    assert np.array_equal(w1[others], w0[others]) and np.array_equal(lam1[others], lam0[others])
+    without it: bin 29 of 64, ranks (1, 16)."""
+    check_nan_bin(Engine, K=64, k0=29, ranks=RANKS)

@@ -82,8 +82,8 @@ def test_update_vs_oracle(Engine, K, L, M, ranks, dtype):
     # (tools/probes/parity_margins.py, profiles/r04/parity_margins.md): float64 lambda <= 5.0e-11 relative (order 64; <= 7.5e-14
     # below it), w <= 4.8e-8 (order 64; 1.0e-10 at 16 x 32); float32 lambda <= 7.4e-6, w <= 4.3e-6.  The exception is float32 with
     # M < L: the dark matrix is singular and loaded to cond ~ 3e3, and the float32 whitening of it leaves 7.1e-5 on the
-    # eigenvalues and 0.8-1.8e-3 on the filters whichever eigensolver follows (tools/probes/rankdef_f32_probe.py; float64: 8e-14
-    # and 6e-12, inside the plain bounds).
+    # eigenvalues and 0.8-1.8e-3 on the filters (tools/probes/rankdef_f32_probe.py; the two-sided sweeps the probe could select
+    # before that switch was removed gave the same; float64: 8e-14 and 6e-12, inside the plain bounds).
     loose = dtype == "f32" and M < L
     assert (np.abs(lam[:, :nz] - lam_ref[:, :nz]) / scale).max() < TOL[dtype]["lam"] * (10 if loose else 1)
     if M >= L:

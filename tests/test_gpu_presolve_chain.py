@@ -15,10 +15,7 @@ if ROOT not in sys.path:
 pytestmark = pytest.mark.gpu
 
 from oracle import subband  # noqa: E402  (checker only)
-
-
-def rel_w(w, ref):
-    return (np.linalg.norm(w - ref, axis=-1) / np.linalg.norm(ref, axis=-1)).max()
+from presolve_cases import cn, refinement_marks, rel_w, unitary  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -51,23 +48,19 @@ def test_guard_pass_rates(Engine, bench_bins):
     """debug_stop = 9 marks a bin by the last refinement step whose guard it missed: at least 99.6 % of the bench bins pass the
     one-step guard (the NumPy model of the kernel's steps gives 99.68 %) and every bin passes the second step's limit."""
     XB, XD, d = bench_bins
-    K, M, L = XB.shape
-    eng = Engine(K, L, M, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=True, debug_stop=9)
-    _, _, status = eng.update(XB, XD, d, raise_on_status=False)
-    eng.close()
-    assert set(np.unique(status)) <= {0, 8, 16}
+    K = XB.shape[0]
+    status = refinement_marks(Engine, XB, XD, d, mu=1.0)
     assert np.count_nonzero(status == 0) / K >= 0.996, np.count_nonzero(status) / K
     assert np.count_nonzero(status == 16) == 0
 
 
 def pencil(rng, lam, K, M):
-    """K bins whose whitened C has the spectrum `lam` (orthonormal X_D columns: R_D = I); identity eigenvectors if `diag`."""
+    """K bins whose whitened C has the spectrum `lam` (orthonormal X_D columns: R_D = I)"""
     L = len(lam)
     XB = np.zeros((K, M, L), np.complex128)
     XD = np.zeros((K, M, L), np.complex128)
     for k in range(K):
-        U = np.linalg.qr(rng.standard_normal((L, L)) + 1j * rng.standard_normal((L, L)))[0]
-        XB[k, :L] = np.sqrt(lam)[:, None] * U.conj().T
+        XB[k, :L] = np.sqrt(lam)[:, None] * unitary(rng, L).conj().T
         XD[k] = np.linalg.qr(rng.standard_normal((M, L)) + 1j * rng.standard_normal((M, L)))[0]
     return XB.astype(np.complex64), XD.astype(np.complex64)
 
@@ -92,7 +85,7 @@ def test_structured_spectra(Engine, spectrum):
         XD[:, :L] = np.eye(L, dtype=np.complex64)
     else:
         XB, XD = pencil(rng, lam, K, M)
-    d = ((rng.standard_normal((K, M)) + 1j * rng.standard_normal((K, M))) * np.sqrt(0.5)).astype(np.complex64)
+    d = cn(rng, K, M)
     ranks = (1, 16)
     eng = Engine(K, L, M, ranks=ranks, mu=0.1, compute_dtype="f64", out_c128=True)
     w, lam_gpu, status = eng.update(XB, XD, d)

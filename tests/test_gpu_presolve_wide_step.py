@@ -1,12 +1,12 @@
 """The wave-wide first multisection step and the best-of-four shifts of the float32 pre-solve (kernels_gevd16m.hip,
 tridiag_presolve16) where they can go wrong: eigenvalues on and between the 64 points of the wide step (the vote crosses 16-lane
 rows and 32-lane halves), many eigenvalues inside one of its 65 brackets, close pairs on either side of a quad point and of the
-boundary between two shifts, eigenvalues placed so that the first, the last or no single lane of the quad has the best shift, the
-debug_stop = 9 marks against the NumPy model, and a NaN bin between healthy ones.  L = 16, explicit R_B / R_D (R_D = I, so the
+boundary between two shifts, eigenvalues placed so that the first, the last or no single lane of the quad has the best shift, and
+a NaN bin between healthy ones (the debug_stop = 9 marks against the NumPy model of this scheme: test_step_marks of
+tests/test_gpu_multisection_steps.py).  L = 16, explicit R_B / R_D (R_D = I, so the
 whitened C is R_B / (1 + reg)); spectra have ||lam||_2 = 1 = ||C||_F (1 + reg), so a value x is the point x ||C||_F of the kernel's
 interval [-1e-3, 1.001] ||C||_F.  Bounds as tests/test_gpu_multisection_steps.py.  Every bin is solved twice: by the engine with
 ranks (1,), and by one with ranks (1, 16), because only the full-rank filter sees every eigenvector."""
-import importlib.util
 import os
 import sys
 
@@ -18,16 +18,14 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle import subband  # noqa: E402  (checker only)
+from presolve_cases import check_nan_bin, presolve_model, rel_w, with_spectrum  # noqa: E402
 
-_spec = importlib.util.spec_from_file_location("tridiag_presolve_model", os.path.join(ROOT, "tools", "probes", "tridiag_presolve_model.py"))
-model = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(model)
+model = presolve_model()
 
 L, M = 16, 32
 REG = 1e-7                                    # the engine's and the oracle's loading of R_D
 MU = 0.1
 BINS_PER_CASE = 4
-STEP_BINS = 1024
 LO, W = -1e-3, 1.002                          # the multisection's first interval, in units of ||C||_F
 NW = model.NWIDE + 1                          # 65 brackets
 WB = W / NW                                   # one bracket of the wide step
@@ -41,16 +39,6 @@ def point(l):
 
 
 Q0 = point(15) + 2 * WB / 5                   # a point of the first quad step inside bracket 16 (and an end of final intervals)
-
-
-def rel_w(w, ref):
-    return (np.linalg.norm(w - ref, axis=-1) / np.linalg.norm(ref, axis=-1)).max()
-
-
-def with_spectrum(rng, lam):
-    U = np.linalg.qr(rng.standard_normal((L, L)) + 1j * rng.standard_normal((L, L)))[0]
-    C = (U * lam) @ U.conj().T
-    return 0.5 * (C + C.conj().T)
 
 
 def filled(fixed, hi=0.15, lo=0.02, min_gap=1e-4):
@@ -234,53 +222,8 @@ def test_model_winning_lane(name, lanes):
         assert counts[list(lanes)].sum() == win.size and all(counts[j] > 0 for j in lanes), counts
 
 
-@pytest.fixture(scope="module")
-def model_second_step_share():
-    """share of the first STEP_BINS bench-distribution bins outside the one-step guard |Z| <= 3e-5 in the NumPy model"""
-    C = model.make_C(STEP_BINS)                                          # bench.synth(STEP_BINS, 1234), whitened in float64
-    V, _, trust, _ = model.presolve(C, model.NSTEP_KERNEL, 4, np.random.default_rng(7))
-    z = model.zmax(C, V)
-    assert trust.all() and (z <= 1e-2).all()
-    return float((z > 3e-5).mean())
-
-
-@pytest.mark.gpu
-def test_step_marks_against_the_model(Engine, model_second_step_share):
-    """debug_stop = 9 marks a bin 8 if it missed the first refinement step's guard and 16 if it missed the second step's too.
-    No bench bin may be left to the double sweeps, and the share that needs the second step may exceed the model's (wide step,
-    NQUAD_KERNEL quad steps, best of four, 1-ulp noise on the pivots' reciprocals) by at most three standard deviations of a
-    binomial count over STEP_BINS draws.  This is test_step_marks of test_gpu_multisection_steps.py over again (the same bins, the
-    same model call, the same bound), kept here so that this file alone covers the scheme; it adds no case of its own."""
-    import bench
-    XB, XD, d = bench.synth(STEP_BINS, 1234)
-    eng = Engine(STEP_BINS, L, M, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=True, debug_stop=9)
-    _, _, status = eng.update(XB, XD, d, raise_on_status=False)
-    eng.close()
-    p = model_second_step_share
-    share = np.count_nonzero(status == 8) / STEP_BINS
-    bound = p + 3 * np.sqrt(p * (1 - p) / STEP_BINS)
-    print(f"marks {dict(zip(*np.unique(status, return_counts=True)))}: second step {share:.4f}, model {p:.4f}, bound {bound:.4f}")
-    assert set(np.unique(status)) <= {0, 8, 16}
-    assert np.count_nonzero(status == 16) == 0
-    assert share <= bound, (share, p, bound)
-
-
 @pytest.mark.gpu
 def test_nan_bin_between_healthy_bins(Engine):
     """A NaN in one bin (every lane's Sturm count and every shift of that wave is NaN: a NaN key wins the quad and fails the gate)
-    gives that bin a non-zero status and leaves its neighbours' results bit for bit as they are without it."""
-    import bench
-    K, k0 = 16, 7
-    XB, XD, d = bench.synth(K, 77)
-    eng = Engine(K, L, M, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=True)
-    w0, lam0, st0 = eng.update(XB, XD, d, raise_on_status=False)
-    XB = XB.copy()
-    XB[k0, 3, 5] = np.nan
-    w1, lam1, st1 = eng.update(XB, XD, d, raise_on_status=False)
-    eng.close()
-    print("status of the NaN bin:", st1[k0])
-    assert not st0.any()
-    assert st1[k0] != 0
-    others = np.arange(K) != k0
-    assert not st1[others].any()
-    assert np.array_equal(w1[others], w0[others]) and np.array_equal(lam1[others], lam0[others])
+    gives that bin a non-zero status and leaves its neighbours' results bit for bit as they are without it: bin 7 of 16, ranks (1,)."""
+    check_nan_bin(Engine, K=16, k0=7, ranks=(1,))

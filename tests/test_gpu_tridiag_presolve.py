@@ -13,14 +13,7 @@ if ROOT not in sys.path:
 pytestmark = pytest.mark.gpu
 
 from oracle import subband  # noqa: E402  (checker only)
-
-
-def cn(rng, *s):
-    return ((rng.standard_normal(s) + 1j * rng.standard_normal(s)) * np.sqrt(0.5)).astype(np.complex64)
-
-
-def rel_w(w, ref):
-    return (np.linalg.norm(w - ref, axis=-1) / np.linalg.norm(ref, axis=-1)).max()
+from presolve_cases import cn, refinement_marks, rel_w, unitary  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -54,11 +47,8 @@ def test_second_refinement_step_is_rare(Engine, bench_bins):
     """debug_stop = 9 marks a bin by the last refinement step whose guard it missed (8: the first only, 16: the second): at most
     1 % of the bench bins need the second step, and none is left to the double sweeps by the second guard."""
     XB, XD, d = bench_bins
-    K, M, L = XB.shape
-    eng = Engine(K, L, M, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=True, debug_stop=9)
-    _, _, status = eng.update(XB, XD, d, raise_on_status=False)
-    eng.close()
-    assert set(np.unique(status)) <= {0, 8, 16}
+    K = XB.shape[0]
+    status = refinement_marks(Engine, XB, XD, d, mu=1.0)
     second = np.count_nonzero(status) / K
     assert second <= 0.01, second
     assert np.count_nonzero(status == 16) <= K * 1e-3
@@ -76,8 +66,7 @@ def test_close_eigenvalues(Engine, spectrum):
            "double": np.repeat(base[::2], 2)}[spectrum]
     XB = np.zeros((K, M, L), np.complex128)
     for k in range(K):
-        U = np.linalg.qr(rng.standard_normal((L, L)) + 1j * rng.standard_normal((L, L)))[0]
-        XB[k, :L] = np.sqrt(lam)[:, None] * U.conj().T
+        XB[k, :L] = np.sqrt(lam)[:, None] * unitary(rng, L).conj().T
     XD = np.zeros((K, M, L), np.complex128)
     for k in range(K):
         XD[k] = np.linalg.qr(rng.standard_normal((M, L)) + 1j * rng.standard_normal((M, L)))[0]

@@ -8,12 +8,12 @@ python3 - <<'PY'
 import csv, glob, collections
 f = glob.glob('/tmp/pmc_st/*/*counter_collection.csv')[0]
 rows = list(csv.DictReader(open(f)))
-# dispatches come in six groups of 120 launches (20 warm-up + 100 timed) in the order of the probe's stage list
+# dispatches come in four groups of 120 launches (20 warm-up + 100 timed) in the order of the probe's stage list
 by = collections.OrderedDict()
 for r in rows:
     by.setdefault(int(r['Dispatch_Id']), {})[r['Counter_Name']] = float(r['Counter_Value'])
 ids = sorted(by)
-names = ["correlate", "cholesky + inverse", "whitening", "float cholesky", "one-sided sweeps", "refinement + tail"]
+names = ["correlate", "cholesky + inverse", "whitening", "pre-solve + refinement + tail"]
 per = len(ids) // len(names)
 prev = collections.Counter()
 print("| stage (cumulative kernel cut at its end) | VALU / wave | LDS / wave | MFMA / wave | SALU / wave | stage VALU | stage LDS | stage MFMA |")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Eigenvalue error of the fused order-16 update on fixture G3 per pre-solve variant (debug_stop 0 / 11) and which bins
+"""Eigenvalue error of the fused order-16 update on fixture G3 (debug_stop 0, and 5: the guarded path always) and which bins
 took a second refinement step (debug_stop 9)."""
 import os, sys
 import numpy as np
@@ -10,7 +10,7 @@ XB, XD, d = g["XB"], g["XD"], g["d"]
 K, M, L = XB.shape
 ranks = [int(v) for v in g["ranks"]]
 res = {}
-for stop in (0, 11, 9, 5):
+for stop in (0, 9, 5):
     eng = Engine(K, L, M, ranks=ranks, mu=float(g["mu"]), compute_dtype="f64", reg_dark=float(g["reg"]), debug_stop=stop)
     w, lam, status = eng.update(XB, XD, d)
     eng.close()
