@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -68,6 +68,9 @@ class Config(C.Structure):
         ("reserved", C.c_int32 * 4),
         ("sweep_tol2", C.c_double),
     ]
+
+
+SYNTHESIS = {"wola": 0, "fir": 1}     # APV_SYNTH_WOLA, APV_SYNTH_FIR
 
 
 class ApvError(RuntimeError):
@@ -145,6 +148,8 @@ def load():
     lib.apv_stream_set_stat_forgetting.argtypes = [vp, C.c_double]
     lib.apv_stream_set_filter_taps.argtypes = [vp, i32]
     lib.apv_constrain_filters.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.apv_stream_set_synthesis.argtypes = [vp, i32]
+    lib.apv_fir_synthesis.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -218,7 +223,7 @@ class Engine:
     def __init__(self, n_bins, n_srcs, n_mics, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=None,
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
-                 out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0):
+                 out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola"):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -271,6 +276,43 @@ class Engine:
         self.filter_taps = 0
         if int(filter_taps) != 0:
             self.set_filter_taps(filter_taps)
+        self.synthesis = "wola"
+        if synthesis != "wola":
+            self.set_synthesis(synthesis)
+
+    def set_synthesis(self, mode):
+        """Synthesis of the subband stream, before stream_init (apv_stream_set_synthesis): "wola" (the reference's overlap-add)
+        or "fir" (the constrained stream's taps as zero-latency time-domain FIR filters; needs filter_taps)."""
+        if mode not in SYNTHESIS:
+            raise ValueError("synthesis must be 'wola' or 'fir'")
+        self._chk(self.lib.apv_stream_set_synthesis(self.h, SYNTHESIS[mode]))
+        self.synthesis = mode
+
+    def fir_synthesis(self, x, taps_prev, taps_cur, H):
+        """The FIR synthesis kernel alone (apv_fir_synthesis): x (J - 1 + H,) samples of one signal -- the J - 1 in front of the
+        hop, then the hop -- in s_dtype, taps_prev / taps_cur (nV, J, L) in lam_dtype -> (nV, H, L) of s_dtype: sample t takes
+        (1 - a) * (taps_prev applied) + a * (taps_cur applied), a = (t + 1) / H."""
+        taps_prev = np.ascontiguousarray(taps_prev, dtype=self.lam_dtype)
+        taps_cur = np.ascontiguousarray(taps_cur, dtype=self.lam_dtype)
+        if taps_prev.ndim != 3 or taps_prev.shape != taps_cur.shape:
+            raise ValueError("taps_prev and taps_cur must both be (nV, J, L)")
+        nV, J, L = taps_prev.shape
+        H = int(H)
+        x = np.ascontiguousarray(x, dtype=self.s_dtype).ravel()
+        if J >= 1 and H >= 1 and x.size != J - 1 + H:
+            raise ValueError("x must hold J - 1 + H samples")
+        isz = np.dtype(self.s_dtype).itemsize
+        dx, dp, dc = self.to_device(x) if x.size else self.alloc(isz), self.alloc(max(taps_prev.nbytes, 8)), self.alloc(max(taps_cur.nbytes, 8))
+        dout = self.alloc(max(nV * H * L, 1) * isz)
+        try:
+            if taps_prev.size:
+                dp.upload(taps_prev)
+                dc.upload(taps_cur)
+            self._chk(self.lib.apv_fir_synthesis(self.h, dx.ptr, dp.ptr, dc.ptr, nV, L, J, H, dout.ptr))
+            return dout.download((nV, H, L), self.s_dtype)
+        finally:
+            for b in (dx, dp, dc, dout):
+                b.free()
 
     def set_filter_taps(self, J):
         """Filter-length constraint of the subband stream: J taps (1..block_size; 0 = off), before stream_init

@@ -47,6 +47,13 @@ What is different (keyword-only, after ``perceptual``)
     statistics_hops, statistics_forgetting, perceptual, reassigned rir_* / mu, up to 128 loudspeakers and every block size.
     process_signal on such a stream runs its hops one after the other through the per-hop path (the same bits as the hop loop).
     Without the keyword the stream launches exactly what it launched before, and ``filter_length`` is stored and not used.
+  * ``synthesis="fir"`` (with ``constrain_filter_length=True``; default ``"wola"``, the reference's weighted overlap-add): the J
+    taps are applied to the inputs as time-domain FIR filters with no latency.  With x_z the input of zone program z (zero before
+    the first hop), g_h the taps w_time_* return after hop h, g_-1 = 0, and for hop h, t = 0..H-1, n = h H + t, a = (t + 1) / H:
+    y[z, v][n, l] = (1 - a) sum_j g_{h-1}[z, v, j, l] x_z[n - j] + a sum_j g_h[z, v, j, l] x_z[n - j], a linear cross-fade over
+    the hop; the target outputs are the inputs delayed by modeling_delay in column reference_index_A.  Return shapes, w_*,
+    lambda_*, w_time_* and everything else the design half leaves are unchanged; get_state() gains ``fir_synthesis_taps`` (zone
+    programs that run, V, J, L) and ``fir_synthesis_history`` (2, J - 1), and ``out_overlap`` stays, untouched by the hops.
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).
@@ -140,6 +147,7 @@ class apvast:
                  max_sweeps: int = 0,
                  sweep_tol2: float = 0.0,
                  constrain_filter_length=False,
+                 synthesis="wola",
                  statistics_forgetting=None,
                  statistics_hops=1):
         self.block_size = block_size
@@ -178,6 +186,7 @@ class apvast:
         self.statistics_forgetting = self._check_statistics_forgetting(statistics_forgetting, self.statistics_hops, mode)
         self.constrain_filter_length = self._check_constrain_filter_length(constrain_filter_length, filter_length, block_size,
                                                                            modeling_delay, mode)
+        self.synthesis = self._check_synthesis(synthesis, self.constrain_filter_length, mode)
         self.window = np.sin(np.pi / self.block_size * np.arange(self.block_size)).reshape(-1, 1)   # apvast.py:94
         self.rir_length, self.number_of_srcs, self.number_of_mics = rir_A.shape  # apvast.py:97-99
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
@@ -203,7 +212,8 @@ class apvast:
                                  max_sweeps=self._max_sweeps, sweep_tol2=sweep_tol2,
                                  out_layout=1,     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
                                  stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting,
-                                 filter_taps=int(filter_length) if self.constrain_filter_length else 0)
+                                 filter_taps=int(filter_length) if self.constrain_filter_length else 0,
+                                 synthesis=self.synthesis)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -275,6 +285,20 @@ class apvast:
             raise ValueError("constrain_filter_length: modeling_delay must be below filter_length (the target tap has to lie inside "
                              "the filter)")
         return True
+
+    @staticmethod
+    def _check_synthesis(value, constrain_filter_length, mode):
+        """synthesis as "wola" or "fir"; "fir" needs subband mode and constrain_filter_length=True (it applies the J taps)."""
+        if not isinstance(value, str) or value not in ("wola", "fir"):
+            raise ValueError("synthesis must be 'wola' (weighted overlap-add, the reference's) or 'fir' (the constrained filters "
+                             "as time-domain FIR filters)")
+        if value == "wola":
+            return value
+        if mode == "broadband":
+            raise ValueError("synthesis='fir' is a subband keyword: broadband mode has its own time-domain filters")
+        if not constrain_filter_length:
+            raise ValueError("synthesis='fir' needs constrain_filter_length=True: it applies the filter_length taps of w_time_*")
+        return value
 
     # ---- responses and mu, reassignable between hops (the reference reads them on every hop, apvast.py:161, 167-193) ----
     def _init_responses(self, rir_A, rir_B):
@@ -630,6 +654,7 @@ class apvast:
     _LIVE_STATE = ("fir_correction", "target_fir_correction")       # present once a response update has been applied
     _WIN_STATE = ("statistics_window", "statistics_window_fill")    # present with statistics_hops > 1
     _FORGET_STATE = ("statistics_forgetting_sums",)                  # present with statistics_forgetting set
+    _FIR_STATE = ("fir_synthesis_taps", "fir_synthesis_history")    # present with synthesis="fir"
 
     def get_state(self):
         """Everything the next hop depends on (the reference's instance attributes of apvast.py:115-151), as float64 arrays
@@ -655,6 +680,12 @@ class apvast:
             e, L = self._eng, self.number_of_srcs
             st["statistics_forgetting_sums"] = np.stack([e.get_state(f"stat_forget{z}", (self._K, 2 * L * L + L), e.stat_dtype)
                                                          for z, run in enumerate((self.run_A, self.run_B)) if run])
+        if self.mode == "subband" and self.synthesis == "fir":
+            e, L, V, J = self._eng, self.number_of_srcs, len(self._ranks), int(self.filter_length)
+            st["fir_synthesis_taps"] = np.stack([e.get_state(f"fir_synth_taps_{'AB'[z]}", (V, J, L), e.lam_dtype)
+                                                 for z, run in enumerate((self.run_A, self.run_B)) if run]).astype(np.float64)
+            st["fir_synthesis_history"] = np.stack([e.get_state(f"fir_synth_history{g}", (J - 1,), e.s_dtype) if J > 1 else np.zeros(0)
+                                                    for g in range(2)]).astype(np.float64)
         if self._live_applied:
             P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
             Q = max(P - 1, 1)
@@ -703,6 +734,8 @@ class apvast:
             known = known + self._WIN_STATE
         if self.mode == "subband" and self.statistics_forgetting is not None:
             known = known + self._FORGET_STATE
+        if self.mode == "subband" and self.synthesis == "fir":
+            known = known + self._FIR_STATE
         unknown = sorted(set(state) - set(known))
         if unknown:
             raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
@@ -723,6 +756,21 @@ class apvast:
                 raise ValueError(f"statistics_forgetting_sums must have shape {(len(zs), self._K, 2 * L * L + L)}, got {sums.shape}")
             for i, z in enumerate(zs):
                 e.set_state(f"stat_forget{z}", np.ascontiguousarray(sums[i], dtype=e.stat_dtype))
+        if "fir_synthesis_taps" in state:
+            L, V, J = self.number_of_srcs, len(self._ranks), int(self.filter_length)
+            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
+            taps = np.asarray(state["fir_synthesis_taps"])
+            if taps.shape != (len(zs), V, J, L):
+                raise ValueError(f"fir_synthesis_taps must have shape {(len(zs), V, J, L)}, got {taps.shape}")
+            for i, z in enumerate(zs):
+                e.set_state(f"fir_synth_taps_{'AB'[z]}", np.ascontiguousarray(taps[i], dtype=e.lam_dtype))
+        if "fir_synthesis_history" in state:
+            J = int(self.filter_length)
+            hst = np.asarray(state["fir_synthesis_history"])
+            if hst.shape != (2, J - 1):
+                raise ValueError(f"fir_synthesis_history must have shape {(2, J - 1)}, got {hst.shape}")
+            for g in range(2 if J > 1 else 0):
+                e.set_state(f"fir_synth_history{g}", np.ascontiguousarray(hst[g], dtype=e.s_dtype))
         if "statistics_window_fill" in state:
             e.set_state("stat_window_fill", np.array([int(state["statistics_window_fill"])], dtype=np.int32))
         if any(k in state for k in self._LIVE_STATE):

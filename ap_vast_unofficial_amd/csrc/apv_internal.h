@@ -89,6 +89,7 @@ struct apv_handle {
     int stat_hops;                   // apv_stream_set_stat_hops: statistics window of the next apv_stream_init, in hops (<= 1: one block)
     double stat_forgetting;          // apv_stream_set_stat_forgetting: forgetting factor of the next apv_stream_init in (0, 1]; 0: off
     int filter_taps;                 // apv_stream_set_filter_taps: J of the next apv_stream_init's filter-length constraint; 0: off
+    int synthesis;                   // apv_stream_set_synthesis: APV_SYNTH_WOLA (0) or APV_SYNTH_FIR of the next apv_stream_init
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -269,6 +270,33 @@ int apv_fir_partitions(int f64, int P, int H);
 bool apv_constrain_size_ok(int c128, int N, std::string* why);
 hipError_t apv_launch_constrain_filters(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
                                         hipStream_t s, std::string* why);
+
+// kernels_firsynth.hip: the FIR synthesis of a constrained stream (see the file header).  One launch writes the groups
+// [program 0: nV][program 1: nV][target A][target B] (n_tgt = 0: no target groups) of H samples x L loudspeakers each; element
+// (g, n, l) of the result goes to out[g H L + n sn + l sl].  Taps are float or double (taps_f64), samples and results likewise (x_f64).
+struct FirSynthArgs {
+    const void* prev[2];           // per zone program of the launch: the taps the hop fades from, [nV][J][L]
+    const void* cur[2];            // ... and the hop's own
+    int sig[2];                    // the input signal each program filters
+    const void* xhist[2];          // per input signal: the J - 1 samples in front of the hop, oldest first (not read when J = 1)
+    const void* xhop[2];           // ... and the hop's H samples
+    int nz, nV, L, J, H;
+    int n_tgt, ref, delay;         // target groups: x[n - delay] in column ref, zeros elsewhere
+    void* out;
+    long sn, sl;
+};
+hipError_t apv_launch_fir_synthesis(int taps_f64, int x_f64, const FirSynthArgs& a, hipStream_t s, std::string* why);
+// behind it: prev[z] <- cur[z] (n_taps elements each), new_hist[g] <- the J - 1 newest samples of [old_hist[g] | xhop[g]], g < 2
+struct FirSynthAdvance {
+    const void* cur[2];
+    void* prev[2];
+    size_t n_taps;
+    const void* old_hist[2];
+    const void* xhop[2];
+    void* new_hist[2];
+    int nz, J, H;
+};
+hipError_t apv_launch_fir_synth_advance(int taps_f64, int x_f64, const FirSynthAdvance& a, hipStream_t s);
 
 // whole-signal path, a chunk of hops per launch (kernels_stft.hip / kernels_stream.hip; see process_signal_chunked_t in stream.hip)
 hipError_t apv_launch_stft_analysis_chunk(int f64, int N, int n_jobs, const void* const* x, const int* n_ch, void* const* spec,

@@ -231,6 +231,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     h->stat_hops = 1;
     h->stat_forgetting = 0.0;
     h->filter_taps = 0;
+    h->synthesis = APV_SYNTH_WOLA;
     h->gl_ws = nullptr;
     h->gl_tol2 = 0.0;
     h->gl_lead_rank = 0;
@@ -866,6 +867,28 @@ int apv_constrain_filters(apv_handle* h, void* d_w, int32_t n_bins, int32_t nV, 
     void* w[1] = {d_w};
     void* taps[1] = {d_taps};
     hipError_t e = apv_launch_constrain_filters(h->cfg.out_c128, N, J, nV, L, 1, w, taps, h->stream, &why);
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
+int apv_fir_synthesis(apv_handle* h, const void* d_x, const void* d_taps_prev, const void* d_taps_cur, int32_t nV, int32_t L,
+                      int32_t J, int32_t H, void* d_out) {
+    if (!h || !d_x || !d_taps_prev || !d_taps_cur || !d_out) return fail(h, APV_ERR_ARG, "null device pointer");
+    if (J < 1 || H < 1 || nV < 1 || L < 1) return fail(h, APV_ERR_ARG, "apv_fir_synthesis: J, H, nV and L must be at least 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    const apv_config& c = h->cfg;
+    const int x_f64 = c.frontend == 1 ? 0 : c.frontend == 2 ? 1 : c.compute_dtype == APV_F64;
+    const size_t esz = x_f64 ? 8 : 4;
+    FirSynthArgs a{};
+    a.prev[0] = d_taps_prev; a.cur[0] = d_taps_cur; a.sig[0] = 0;
+    a.xhist[0] = d_x; a.xhop[0] = static_cast<const char*>(d_x) + (size_t)(J - 1) * esz;
+    a.nz = 1; a.nV = nV; a.L = L; a.J = J; a.H = H;
+    a.n_tgt = 0;
+    a.out = d_out; a.sn = L; a.sl = 1;
+    std::string why;
+    hipError_t e = apv_launch_fir_synthesis(c.out_c128, x_f64, a, h->stream, &why);
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
     return APV_OK;

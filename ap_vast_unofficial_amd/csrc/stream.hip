@@ -139,6 +139,13 @@ struct apv_stream {
     void* wtaps[2];               // per zone program: [nV][J][L] real, the J taps of the hop's projected filters (precision of w)
     hipEvent_t cf_ev[2];          // APV_FILTER_CONSTRAINT_TIMING (tools/bench_filter_constraint.py): events around the projection
     double cf_ms[2];              // ... and {sum of its times in ms, hops timed}
+    // FIR synthesis (apv_stream_set_synthesis, kernels_firsynth.hip); fir_synth = 0: off, nothing below exists
+    int fir_synth;
+    int fs_ref, fs_delay;         // the target paths: column reference_index_A, modeling_delay samples late
+    void* fs_taps[2];             // per zone program that runs: [nV][J][L], the taps the next hop fades from (precision of w)
+    void* fs_hist[2][2];          // [buf][signal][J - 1]: the newest input samples; buf = cur, like the input histories of K1
+    hipEvent_t fs_ev[2];          // APV_FIR_SYNTHESIS_TIMING (tools/bench_fir_synthesis.py): events around the synthesis launch
+    double fs_ms[2];              // ... and {sum of its times in ms, hops timed}
     hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
     double win_ms[2];             // ... and {sum of its times in ms, hops timed}
     std::vector<hipGraphExec_t> execs;
@@ -270,6 +277,10 @@ void apv_stream_free(apv_handle* h) {
         if (s->win_ev[z]) (void)hipEventDestroy(s->win_ev[z]);
         if (s->wtaps[z]) (void)hipFree(s->wtaps[z]);
         if (s->cf_ev[z]) (void)hipEventDestroy(s->cf_ev[z]);
+        if (s->fs_taps[z]) (void)hipFree(s->fs_taps[z]);
+        for (int b = 0; b < 2; ++b)
+            if (s->fs_hist[b][z]) (void)hipFree(s->fs_hist[b][z]);
+        if (s->fs_ev[z]) (void)hipEventDestroy(s->fs_ev[z]);
     }
     if (s->win_ctr) (void)hipFree(s->win_ctr);
     delete s;
@@ -503,6 +514,43 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
         if (s->cf_ev[1]) SCHK(h, hipEventRecord(s->cf_ev[1], st));
     }
+    if (s->fir_synth) {
+        // FIR synthesis in place of K3 and K4: the hop's taps and the taps of the hop before it applied to the input signals in
+        // one launch, the target paths (pure delays) included, written where K4 writes; a second, small launch then makes this
+        // hop's taps and the newest J - 1 samples the next hop's.  Only the per-hop path reaches here (process_signal_t sends a
+        // constrained stream through it), after enqueue_front: the hop's samples lie behind `keep` older ones in the current
+        // input history, and the synthesis' own history alternates between two buffers with it.
+        const int J = s->taps, c = s->cur;
+        FirSynthArgs a{};
+        FirSynthAdvance adv{};
+        int nz = 0;
+        for (int z = 0; z < 2; ++z) {
+            if (!(z ? runB : runA)) continue;
+            a.prev[nz] = s->fs_taps[z]; a.cur[nz] = s->wtaps[z]; a.sig[nz] = z;
+            adv.cur[nz] = s->wtaps[z]; adv.prev[nz] = s->fs_taps[z];
+            ++nz;
+        }
+        for (int g = 0; g < 2; ++g) {
+            a.xhist[g] = s->fs_hist[c ^ 1][g];
+            a.xhop[g] = static_cast<const char*>(s->xhist[c][g]) + (size_t)s->keep * s->esz;
+            adv.old_hist[g] = a.xhist[g]; adv.xhop[g] = a.xhop[g]; adv.new_hist[g] = s->fs_hist[c][g];
+        }
+        a.nz = nz; a.nV = s->nV; a.L = L; a.J = J; a.H = H;
+        a.n_tgt = 2; a.ref = s->fs_ref; a.delay = s->fs_delay;
+        a.out = obuf;
+        a.sn = s->out_group > 0 ? L : 1;
+        a.sl = s->out_group > 0 ? 1 : H;
+        adv.n_taps = (size_t)s->nV * J * L; adv.nz = nz; adv.J = J; adv.H = H;
+        if (s->fs_ev[0]) SCHK(h, hipEventRecord(s->fs_ev[0], st));
+        hipError_t e = apv_launch_fir_synthesis(h->cfg.out_c128, f64, a, st, &why);
+        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+        if (s->fs_ev[1]) SCHK(h, hipEventRecord(s->fs_ev[1], st));
+        SCHK(h, apv_launch_fir_synth_advance(h->cfg.out_c128, f64, adv, st));
+        if (sch.spectra_free) SCHK(h, hipEventRecord(sch.spectra_free, st));
+        if (sch.no_copy) return APV_OK;
+        SCHK(h, hipMemcpyAsync(pin_dst, obuf, hop_result_bytes(s), hipMemcpyDeviceToHost, st));     // samples + status: one copy
+        return APV_OK;
+    }
     {
         // K3: output spectra in one launch: each live zone's nV*L filtered channels, then the target paths A_t, B_t
         const void* jin[4];
@@ -601,6 +649,12 @@ static int run_hop(apv_handle* h) {
         SCHK(h, hipEventElapsedTime(&ms, s->cf_ev[0], s->cf_ev[1]));
         s->cf_ms[0] += ms;
         s->cf_ms[1] += 1.0;
+    }
+    if (s->fs_ev[0]) {
+        float ms = 0.f;
+        SCHK(h, hipEventElapsedTime(&ms, s->fs_ev[0], s->fs_ev[1]));
+        s->fs_ms[0] += ms;
+        s->fs_ms[1] += 1.0;
     }
     return APV_OK;
 }
@@ -1296,6 +1350,8 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (modeling_delay >= h->filter_taps) return apv_fail(h, APV_ERR_ARG, "modeling_delay must be below the filter taps (apv_stream_set_filter_taps)");
         if (!apv_constrain_size_ok(c.out_c128, N, &why)) return apv_fail(h, APV_ERR_ARG, why);
     }
+    if (h->synthesis == APV_SYNTH_FIR && h->filter_taps < 1)
+        return apv_fail(h, APV_ERR_ARG, "FIR synthesis (apv_stream_set_synthesis) needs the filter taps of apv_stream_set_filter_taps");
     SCHK(h, hipSetDevice(h->device));
     apv_stream_free(h);
     apv_stream* s = new apv_stream();
@@ -1439,6 +1495,18 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (getenv("APV_FILTER_CONSTRAINT_TIMING") != nullptr)
             for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->cf_ev[i]));
     }
+    if (h->synthesis == APV_SYNTH_FIR) {
+        s->fir_synth = 1;
+        s->fs_ref = reference_index_A;
+        s->fs_delay = modeling_delay;
+        for (int z = 0; z < 2; ++z)
+            if ((s->zones & (1 << z)) && (rc = dalloc(h, &s->fs_taps[z], (size_t)s->nV * s->taps * L, lsz(h)))) return rc;
+        for (int b = 0; b < 2; ++b)
+            for (int g = 0; g < 2; ++g)
+                if ((rc = dalloc(h, &s->fs_hist[b][g], (size_t)s->taps - 1, e1))) return rc;
+        if (getenv("APV_FIR_SYNTHESIS_TIMING") != nullptr)
+            for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->fs_ev[i]));
+    }
     // target filter spectra: rfft of a unit impulse at tap modeling_delay of the A reference loudspeaker
     // (apvast.py:389-390, 418, 422: the same filter serves A_t and B_t)
     std::vector<double> tg((size_t)L * K * 2, 0.0);
@@ -1468,7 +1536,8 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (per % 2) per *= 2;
         // (the statistics window adds no phase: its ring position is two device words that a kernel of the hop advances.  Timed
         // statistics launches -- a measuring aid -- run eagerly: their events are read after every hop)
-        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr && !s->win_ev[0] && !s->cf_ev[0]) ? per : 0;
+        // (the FIR synthesis alternates its history buffers with cur, whose period of 2 is part of per already)
+        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr && !s->win_ev[0] && !s->cf_ev[0] && !s->fs_ev[0]) ? per : 0;
         s->execs.assign(s->period > 0 ? s->period : 0, nullptr);
     }
     s->hop = 0;
@@ -1493,6 +1562,15 @@ int apv_stream_set_filter_taps(apv_handle* h, int32_t J) {
     if (J < 0 || (h->cfg.block_size > 0 && J > h->cfg.block_size))
         return apv_fail(h, APV_ERR_ARG, "filter taps: 0 (off) or between 1 and block_size");
     h->filter_taps = J;
+    return APV_OK;
+}
+
+int apv_stream_set_synthesis(apv_handle* h, int32_t mode) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_synthesis: the stream is initialised (its buffers are allocated there)");
+    if (mode != APV_SYNTH_WOLA && mode != APV_SYNTH_FIR)
+        return apv_fail(h, APV_ERR_ARG, "synthesis: APV_SYNTH_WOLA (0) or APV_SYNTH_FIR (1)");
+    h->synthesis = mode;
     return APV_OK;
 }
 
@@ -1722,6 +1800,9 @@ int apv_set_mu(apv_handle* h, double mu) {
 //   "w_time_A" / "w_time_B" [nV][J][L] f32|f64 (cfg.out_c128)   the J taps of the last hop's projected filters; only a stream with
 //                                  the filter-length constraint (apv_stream_set_filter_taps) and only zone programs that run have them
 //   "filter_constraint_kernel_ms" {sum, count} of the timed projections (APV_FILTER_CONSTRAINT_TIMING), read-only
+//   "fir_synth_taps_A" / "fir_synth_taps_B" [nV][J][L] f32|f64 (cfg.out_c128)   the taps the next hop's FIR synthesis fades from;
+//   "fir_synth_history<g>" [J-1]   the newest samples of input signal g; both only with apv_stream_set_synthesis(h, APV_SYNTH_FIR)
+//   "fir_synthesis_kernel_ms" {sum, count} of the timed synthesis launches (APV_FIR_SYNTHESIS_TIMING), read-only
 static int live_index(const char* name) {
     const std::string n(name);
     if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
@@ -1828,6 +1909,10 @@ static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* by
     if (n == "lambda_A" || n == "lambda_B") { *dptr = s->lam[n == "lambda_B"]; *bytes = K * L * lsz(h); return APV_OK; }
     if ((n == "w_time_A" || n == "w_time_B") && s->wtaps[n == "w_time_B"]) {
         *dptr = s->wtaps[n == "w_time_B"]; *bytes = (size_t)s->nV * s->taps * L * lsz(h); return APV_OK; }
+    if ((n == "fir_synth_taps_A" || n == "fir_synth_taps_B") && s->fs_taps[n.back() == 'B']) {
+        *dptr = s->fs_taps[n.back() == 'B']; *bytes = (size_t)s->nV * s->taps * L * lsz(h); return APV_OK; }
+    if ((n == "fir_synth_history0" || n == "fir_synth_history1") && s->fir_synth) {
+        *dptr = s->fs_hist[s->cur][n.back() - '0']; *bytes = (size_t)(s->taps - 1) * e1; return APV_OK; }
     return apv_fail(h, APV_ERR_STATE, std::string("unknown state name: ") + name);
 }
 
@@ -1847,6 +1932,10 @@ int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
         *bytes = sizeof(h->st->cf_ms);
         return APV_OK;
     }
+    if (h->st->fir_synth && std::string(name) == "fir_synthesis_kernel_ms") {
+        *bytes = sizeof(h->st->fs_ms);
+        return APV_OK;
+    }
     void* d; int rr;
     return state_lookup(h, name, &d, bytes, &rr);
 }
@@ -1862,6 +1951,11 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
     if (h->st->taps > 0 && std::string(name) == "filter_constraint_kernel_ms") {
         if (bytes != sizeof(h->st->cf_ms)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
         std::memcpy(h_dst, h->st->cf_ms, sizeof(h->st->cf_ms));
+        return APV_OK;
+    }
+    if (h->st->fir_synth && std::string(name) == "fir_synthesis_kernel_ms") {
+        if (bytes != sizeof(h->st->fs_ms)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+        std::memcpy(h_dst, h->st->fs_ms, sizeof(h->st->fs_ms));
         return APV_OK;
     }
     void* d; size_t need; int rr;

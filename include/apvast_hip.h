@@ -171,6 +171,35 @@ int  apv_stream_set_filter_taps(apv_handle* h, int32_t J);
  *                                                         replaces: nothing in the reference (see apv_stream_set_filter_taps) */
 int  apv_constrain_filters(apv_handle* h, void* d_w, int32_t n_bins, int32_t nV, int32_t L, int32_t N, int32_t J, void* d_taps);
 
+/* Synthesis of the subband stream.  APV_SYNTH_WOLA (the default) is the reference's: output spectra, inverse transform, sine
+ * window, overlap-add; its output lags the input by block_size - hop_size samples.  APV_SYNTH_FIR applies the J taps of a
+ * constrained stream (apv_stream_set_filter_taps) as time-domain FIR filters with no latency: with x_z[n] the input of zone
+ * program z at absolute sample n (zero before the first hop; input A feeds program A, input B program B), g_h the taps
+ * "w_time_*" hold after hop h, g_{-1} = 0, and for hop h, t = 0 .. H - 1, n = h H + t, a_t = (t + 1) / H,
+ *   y[z, v][n, l] = (1 - a_t) sum_{j < J} g_{h-1}[z, v, j, l] x_z[n - j]  +  a_t sum_{j < J} g_h[z, v, j, l] x_z[n - j]
+ * -- a linear cross-fade over the hop from the previous hop's filter to this hop's -- and the target paths are the pure delays
+ * x_A[n - modeling_delay] and x_B[n - modeling_delay] in the column of reference_index_A, zero in the others.  The results take
+ * the places and the layout (cfg.out_layout) of the WOLA outputs; everything upstream of the synthesis, and every state and
+ * attribute it leaves, is unchanged, bit for bit.  One launch per hop on the matrix cores plus a small one that moves the taps
+ * and the history on (csrc/kernels_firsynth.hip), in the captured hop graphs; the output spectra and the inverse transform are
+ * not launched, and "out_overlap" stays as it is.  States only such a stream has: "fir_synth_taps_A" / "fir_synth_taps_B"
+ * [nV][J][L] in the filters' precision (the taps the next hop fades from; zone programs that run) and "fir_synth_history<g>"
+ * [J - 1] in the sample precision (the newest samples of input signal g).  Called between apv_create and apv_stream_init;
+ * APV_ERR_ARG (nothing changed) for an unknown mode or once the stream is initialised; apv_stream_init returns APV_ERR_ARG for
+ * APV_SYNTH_FIR without filter taps.
+ *                                                         replaces: nothing in the reference */
+#define APV_SYNTH_WOLA 0
+#define APV_SYNTH_FIR 1
+int  apv_stream_set_synthesis(apv_handle* h, int32_t mode);
+
+/* The synthesis kernel alone, on the handle's stream: d_x [J - 1 + H] samples of one signal (the J - 1 in front of the hop, then
+ * the hop), d_taps_prev / d_taps_cur [nV][J][L], d_out [nV][H][L] as defined above.  Samples and results are float64 with a
+ * float64 front-end (cfg.frontend / compute_dtype), else float32; taps float64 with cfg.out_c128, else float32.  APV_ERR_ARG for
+ * J < 1, H < 1, nV < 1, L < 1, null pointers, or J beyond what the history window holds in LDS (about 8000 taps in float64).
+ *                                                         replaces: nothing in the reference */
+int  apv_fir_synthesis(apv_handle* h, const void* d_x, const void* d_taps_prev, const void* d_taps_cur, int32_t nV, int32_t L,
+                       int32_t J, int32_t H, void* d_out);
+
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
 int  apv_dev_free(apv_handle* h, void* d_ptr);
