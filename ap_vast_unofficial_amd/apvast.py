@@ -498,6 +498,16 @@ class apvast:
         self._refresh_attributes()
         return res
 
+    @property
+    def signal_schedule(self):
+        """How the last process_signal call of a subband stream ran: (hops that went through the chunked schedule -- a chunk of
+        hops per launch --, hops that went hop by hop).  (0, 0) before the first such call; process_input_buffers does not change
+        it.  Read-only, and no part of get_state() / set_state().  Broadband mode has no such schedule: None."""
+        if self.mode == "broadband":
+            return None
+        c, p = self._eng.get_state("signal_schedule", (2,), np.int32)
+        return int(c), int(p)
+
     def signal_output_shape(self, n_samples):
         """Shape of process_signal's `out`: (zones x ranks + 2 target paths, n_samples, L)."""
         return (self._n_out // self.number_of_srcs, int(n_samples), self.number_of_srcs)

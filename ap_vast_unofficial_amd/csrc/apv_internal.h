@@ -270,6 +270,9 @@ int apv_fir_partitions(int f64, int P, int H);
 bool apv_constrain_size_ok(int c128, int N, std::string* why);
 hipError_t apv_launch_constrain_filters(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
                                         hipStream_t s, std::string* why);
+// ... of the n_hops filter sets w[z] + i hop_w, taps to taps[z] + i hop_taps (strides in elements), in one launch (grid.z = hop x zone)
+hipError_t apv_launch_constrain_filters_hops(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
+                                             int n_hops, size_t hop_w, size_t hop_taps, hipStream_t s, std::string* why);
 
 // kernels_firsynth.hip: the FIR synthesis of a constrained stream (see the file header).  One launch writes the groups
 // [program 0: nV][program 1: nV][target A][target B] (n_tgt = 0: no target groups) of H samples x L loudspeakers each; element
@@ -284,6 +287,12 @@ struct FirSynthArgs {
     int n_tgt, ref, delay;         // target groups: x[n - delay] in column ref, zeros elsewhere
     void* out;
     long sn, sl;
+    // a chunk of hops in ONE launch (chunked whole-signal path; blockIdx.z = hop x group): n_hops <= 1 is a single hop and the three
+    // strides are not used.  Hop i takes its taps from cur[z] + i hop_taps (elements) and fades from the taps of hop i - 1 there
+    // (hop 0: from prev[z]); its samples are xhist[g] + i hop_x and xhop[g] + i hop_x (elements: hop_x = H and xhop = xhist + J - 1
+    // read one linear row [J - 1 samples before the chunk | the chunk]); its result starts hop_out BYTES behind that of hop i - 1
+    int n_hops;
+    size_t hop_taps, hop_x, hop_out;
 };
 hipError_t apv_launch_fir_synthesis(int taps_f64, int x_f64, const FirSynthArgs& a, hipStream_t s, std::string* why);
 // behind it: prev[z] <- cur[z] (n_taps elements each), new_hist[g] <- the J - 1 newest samples of [old_hist[g] | xhop[g]], g < 2
@@ -297,6 +306,11 @@ struct FirSynthAdvance {
     int nz, J, H;
 };
 hipError_t apv_launch_fir_synth_advance(int taps_f64, int x_f64, const FirSynthAdvance& a, hipStream_t s);
+// the linear input rows of a chunk of nc hops, rows[g] = [J - 1 samples before the chunk | nc H samples of the chunk] for the two
+// input signals: the head from head[g] + head_off (the synthesis' history, or the tail of the previous chunk's rows), the body from
+// the pinned staging pin [nc][2][H]; samples float or double (x_f64).  head and rows must not overlap
+hipError_t apv_launch_fir_synth_rows(int x_f64, int J, int H, int nc, const void* const head[2], size_t head_off, const void* pin,
+                                     void* const rows[2], hipStream_t s);
 
 // whole-signal path, a chunk of hops per launch (kernels_stft.hip / kernels_stream.hip; see process_signal_chunked_t in stream.hip)
 hipError_t apv_launch_stft_analysis_chunk(int f64, int N, int n_jobs, const void* const* x, const int* n_ch, void* const* spec,

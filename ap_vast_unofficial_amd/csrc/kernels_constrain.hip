@@ -13,6 +13,10 @@
 // the transpose buffer: bins 1 .. N/2 - 1 sit in their slots, the two real bins 0 and N/2 share slot 0.
 //
 // TL is the largest of 4, 2, 1 whose slices fit 64 KB (a float64 Bluestein transform at M = 4096 fills that alone).
+//
+// The filters of several hops in one launch (apv_launch_constrain_filters_hops, the chunked whole-signal path): blockIdx.z = hop x
+// zone program, hop i's filters hop_w elements behind those of hop i - 1 and its taps hop_taps elements behind.  Plan, TL, LDS
+// per workgroup and the arithmetic of a channel are those of the launch of one hop.
 #include "apv_internal.h"
 #include "stft_fft.h"
 
@@ -25,6 +29,9 @@ template <typename T>
 struct ConstrainJobs {
     C2<T>* w[2];          // [K][nV][L] per zone program of the launch, projected in place
     T* taps[2];           // [nV][J][L]: g[:J] of every channel (may be null)
+    int zones;            // blockIdx.z = hop * zones + zone program
+    size_t hop_w;         // elements from one hop's filters / taps to the next hop's (a launch of one hop multiplies them by its
+    size_t hop_taps;      // hop index, 0)
 };
 
 template <typename T, int MI, bool BS>
@@ -37,9 +44,9 @@ __global__ void __launch_bounds__(STFT_TPB * CF_MAX_TL) constrain_filters_kernel
     C2<T>* const base = reinterpret_cast<C2<T>*>(smem_raw);
     C2<T>* const za = base + ty * slice;
     C2<T>* const zb = za + plan.buf;
-    const int v = blockIdx.y, zone = blockIdx.z, l0 = blockIdx.x * TL;
+    const int v = blockIdx.y, hop = blockIdx.z / jobs.zones, zone = blockIdx.z - hop * jobs.zones, l0 = blockIdx.x * TL;
     const size_t sk = (size_t)nV * L;                                      // elements from bin to bin
-    C2<T>* __restrict__ W = jobs.w[zone] + (size_t)v * L + l0;
+    C2<T>* __restrict__ W = jobs.w[zone] + (size_t)hop * jobs.hop_w + (size_t)v * L + l0;
     const int flat = ty * STFT_TPB + tid, nthr = STFT_TPB * TL;
 
     // bins in, loudspeaker fastest: slot k of row lt takes bin k, slot 0 the real parts of bins 0 and N/2 (irfft drops their
@@ -83,7 +90,7 @@ __global__ void __launch_bounds__(STFT_TPB * CF_MAX_TL) constrain_filters_kernel
     }
     __syncthreads();
     if (jobs.taps[zone] != nullptr) {
-        T* __restrict__ tp = jobs.taps[zone] + (size_t)v * J * L + l0;
+        T* __restrict__ tp = jobs.taps[zone] + (size_t)hop * jobs.hop_taps + (size_t)v * J * L + l0;
         const size_t zoff = z - za;                                        // the same for every row
         for (int e = flat; e < J * TL; e += nthr) {
             const int j = e >> tl_sh, lt = e & (TL - 1);
@@ -122,7 +129,8 @@ __global__ void __launch_bounds__(STFT_TPB * CF_MAX_TL) constrain_filters_kernel
 }
 
 template <typename T>
-hipError_t launch_constrain(const FftPlan& plan, int J, int nV, int L, int zones, void* const* w, void* const* taps, hipStream_t s) {
+hipError_t launch_constrain(const FftPlan& plan, int J, int nV, int L, int zones, void* const* w, void* const* taps, int n_hops,
+                            size_t hop_w, size_t hop_taps, hipStream_t s) {
     const void* tw = nullptr;
     hipError_t e = apv_stft_tables(sizeof(T) == 8, plan.N, &tw);
     if (e != hipSuccess) return e;
@@ -130,13 +138,16 @@ hipError_t launch_constrain(const FftPlan& plan, int J, int nV, int L, int zones
     int TL = CF_MAX_TL;
     while (TL > 1 && (TL * lds > CF_LDS_BUDGET || TL / 2 >= L)) TL /= 2;
     ConstrainJobs<T> jobs{};
+    jobs.zones = zones;
+    jobs.hop_w = hop_w;
+    jobs.hop_taps = hop_taps;
     for (int z = 0; z < zones; ++z) {
         jobs.w[z] = (C2<T>*)w[z];
         jobs.taps[z] = taps ? (T*)taps[z] : nullptr;
     }
     const auto kern = plan.bluestein ? (plan.max_it == 1 ? constrain_filters_kernel<T, 1, true> : constrain_filters_kernel<T, INPLACE_MAX_IT, true>)
                                      : (plan.max_it == 1 ? constrain_filters_kernel<T, 1, false> : constrain_filters_kernel<T, INPLACE_MAX_IT, false>);
-    hipLaunchKernelGGL(kern, dim3((L + TL - 1) / TL, nV, zones), dim3(STFT_TPB, TL), TL * lds, s, plan, jobs, nV, L, J, (const C2<T>*)tw);
+    hipLaunchKernelGGL(kern, dim3((L + TL - 1) / TL, nV, zones * n_hops), dim3(STFT_TPB, TL), TL * lds, s, plan, jobs, nV, L, J, (const C2<T>*)tw);
     return hipGetLastError();
 }
 
@@ -154,14 +165,22 @@ bool apv_constrain_size_ok(int c128, int N, std::string* why) {
 }
 
 // w[z] [N/2 + 1][nV][L] complex (c128: double, else float) of `zones` zone programs projected in place onto J-tap responses, the
-// taps g[:J] to taps[z] [nV][J][L] real of the same precision (taps or taps[z] may be null); 1 <= J <= N
-hipError_t apv_launch_constrain_filters(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
-                                        hipStream_t s, std::string* why) {
+// taps g[:J] to taps[z] [nV][J][L] real of the same precision (taps or taps[z] may be null); 1 <= J <= N.  n_hops > 1: the same for
+// the n_hops filter sets w[z] + i hop_w (elements), the taps of set i to taps[z] + i hop_taps, in one launch (grid.z = hop x zone
+// program); every (hop, zone program, rank, loudspeaker tile) is the workgroup the launch of that hop alone runs
+hipError_t apv_launch_constrain_filters_hops(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
+                                             int n_hops, size_t hop_w, size_t hop_taps, hipStream_t s, std::string* why) {
     FftPlan plan;
     if (!apv_constrain_size_ok(c128, N, why) || !apv_stft_make_plan(N, &plan, why)) return hipErrorInvalidValue;
-    if (J < 1 || J > N || nV < 1 || nV > 65535 || L < 1 || zones < 1 || zones > 2) {
-        if (why) *why = "filter constraint: 1 <= J <= N, 1 <= nV <= 65535, L >= 1, one or two zone programs";
+    if (J < 1 || J > N || nV < 1 || nV > 65535 || L < 1 || zones < 1 || zones > 2 || n_hops < 1 || zones * n_hops > 65535) {
+        if (why) *why = "filter constraint: 1 <= J <= N, 1 <= nV <= 65535, L >= 1, one or two zone programs, zone programs x hops <= 65535";
         return hipErrorInvalidValue;
     }
-    return c128 ? launch_constrain<double>(plan, J, nV, L, zones, w, taps, s) : launch_constrain<float>(plan, J, nV, L, zones, w, taps, s);
+    return c128 ? launch_constrain<double>(plan, J, nV, L, zones, w, taps, n_hops, hop_w, hop_taps, s)
+                : launch_constrain<float>(plan, J, nV, L, zones, w, taps, n_hops, hop_w, hop_taps, s);
+}
+
+hipError_t apv_launch_constrain_filters(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
+                                        hipStream_t s, std::string* why) {
+    return apv_launch_constrain_filters_hops(c128, N, J, nV, L, zones, w, taps, 1, 0, 0, s, why);
 }

@@ -17,6 +17,12 @@
 // samples x 16 loudspeakers of one group; blockIdx.z walks the groups [programs that run: nV][target A][target B], which is the
 // order of the stream's result buffer.  The target groups copy: a delay has nothing to round.
 //
+// A chunk of hops in one launch (FirSynthArgs::n_hops, the chunked whole-signal path): blockIdx.z = hop x group.  Hop i of the
+// chunk is the grid of a launch of its own, shifted: its taps lie i hop_taps elements into the chunk's taps buffer and the taps it
+// fades from directly in front of them (hop 0: a.prev), its samples i hop_x elements into one linear row per signal, its results
+// hop_out bytes behind those of hop i - 1.  No hop reads what another hop of the launch writes; a (hop, group, tile) runs the
+// arithmetic of the per-hop launch in the same order, so the bits are the same.
+//
 // Arithmetic: float64 on v_mfma_f64_16x16x4_f64 unless taps AND samples are float32 (v_mfma_f32_16x16x4_f32).  A dtype="mixed"
 // stream (float64 filters, float32 samples) widens the samples when it fills the window and rounds the result once.
 //
@@ -57,13 +63,14 @@ __global__ void __launch_bounds__(256) fir_synth_kernel(FirSynthArgs a) {
     CT* xw = reinterpret_cast<CT*>(fs_lds);      // [J - 1 + 16 NT] history window; afterwards [4][NT][FS_PT] partial tiles
     CT* part = xw;
     const int J = a.J, H = a.H, L = a.L;
-    const int g = blockIdx.z, l0 = blockIdx.y * 16, n0 = blockIdx.x * 16 * NT;
-    const int nfilt = a.nz * a.nV;
+    const int nfilt = a.nz * a.nV, groups = nfilt + a.n_tgt;
+    // a launch of one hop has gridDim.z = groups: hop = 0 and none of the hop strides is multiplied
+    const int hop = blockIdx.z / groups, g = blockIdx.z - hop * groups, l0 = blockIdx.y * 16, n0 = blockIdx.x * 16 * NT;
     const bool is_tgt = g >= nfilt;               // uniform per workgroup
     const int z = is_tgt ? 0 : g / a.nV, v = is_tgt ? 0 : g - z * a.nV;
     const int sig = is_tgt ? g - nfilt : a.sig[z];
-    const TX* __restrict__ xh = static_cast<const TX*>(a.xhist[sig]);
-    const TX* __restrict__ xp = static_cast<const TX*>(a.xhop[sig]);
+    const TX* __restrict__ xh = static_cast<const TX*>(a.xhist[sig]) + (size_t)hop * a.hop_x;
+    const TX* __restrict__ xp = static_cast<const TX*>(a.xhop[sig]) + (size_t)hop * a.hop_x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, il = lane & 15, kq = lane >> 4;
     // window element i is sample n0 - (J - 1) + i of the hop: the J - 1 samples in front of the hop, the hop, zeros past its end
     for (int i = tid; i < J - 1 + 16 * NT; i += 256) {
@@ -71,7 +78,7 @@ __global__ void __launch_bounds__(256) fir_synth_kernel(FirSynthArgs a) {
         xw[i] = q < J - 1 ? (CT)xh[q] : (q < J - 1 + H ? (CT)xp[q - (J - 1)] : (CT)0);
     }
     __syncthreads();
-    TX* __restrict__ out = static_cast<TX*>(a.out) + (size_t)g * H * L;
+    TX* __restrict__ out = reinterpret_cast<TX*>(static_cast<char*>(a.out) + (size_t)hop * a.hop_out) + (size_t)g * H * L;
     // the thread that stores sample row nl, loudspeaker column c of a tile: neighbouring threads along the contiguous axis of the result
     const int nl = a.sl == 1 ? tid >> 4 : tid & 15, c = a.sl == 1 ? tid & 15 : tid >> 4;
     if (is_tgt) {
@@ -82,8 +89,9 @@ __global__ void __launch_bounds__(256) fir_synth_kernel(FirSynthArgs a) {
         }
         return;
     }
-    const TT* __restrict__ gp = static_cast<const TT*>(a.prev[z]) + (size_t)v * J * L;
-    const TT* __restrict__ gc = static_cast<const TT*>(a.cur[z]) + (size_t)v * J * L;
+    // hop i of a chunk fades from the taps of hop i - 1, which lie in front of its own; the chunk's first hop from a.prev
+    const TT* __restrict__ gc = static_cast<const TT*>(a.cur[z]) + (size_t)hop * a.hop_taps + (size_t)v * J * L;
+    const TT* __restrict__ gp = hop > 0 ? gc - a.hop_taps : static_cast<const TT*>(a.prev[z]) + (size_t)v * J * L;
     const int steps_total = (J + 3) >> 2, spw = (steps_total + 3) >> 2;
     const int s_begin = wave * spw, s_end = min(s_begin + spw, steps_total);
     const int l = l0 + il;
@@ -170,6 +178,25 @@ __global__ void __launch_bounds__(256) fir_synth_advance_kernel(FirSynthAdvance 
     }
 }
 
+// rows[g][i], i < J - 1 + nc H: the head from head[g][head_off + i], the body from the staged hops pin [nc][2][H]
+template <typename TX>
+__global__ void __launch_bounds__(256) fir_synth_rows_kernel(int J, int H, int nc, const TX* __restrict__ head0, const TX* __restrict__ head1,
+                                                             size_t head_off, const TX* __restrict__ pin, TX* __restrict__ row0,
+                                                             TX* __restrict__ row1) {
+    const int g = blockIdx.y, keep = J - 1;
+    const TX* __restrict__ hd = (g ? head1 : head0) + head_off;
+    TX* __restrict__ row = g ? row1 : row0;
+    const size_t len = (size_t)keep + (size_t)nc * H;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (size_t)gridDim.x * 256) {
+        if (i < (size_t)keep) {
+            row[i] = hd[i];
+        } else {
+            const size_t m = i - keep, q = m / H, t = m - q * H;
+            row[i] = pin[(q * 2 + g) * H + t];
+        }
+    }
+}
+
 template <typename TT, typename TX>
 hipError_t launch_fir_synth(const FirSynthArgs& a, hipStream_t s, std::string* why) {
     using CT = typename std::conditional<std::is_same<TT, float>::value && std::is_same<TX, float>::value, float, double>::type;
@@ -180,7 +207,7 @@ hipError_t launch_fir_synth(const FirSynthArgs& a, hipStream_t s, std::string* w
         if (why) *why = "FIR synthesis: the history window of J - 1 + 64 samples does not fit 64 KB of LDS";
         return hipErrorInvalidValue;
     }
-    const dim3 grid((a.H + 16 * NT - 1) / (16 * NT), (a.L + 15) / 16, groups);
+    const dim3 grid((a.H + 16 * NT - 1) / (16 * NT), (a.L + 15) / 16, groups * std::max(a.n_hops, 1));
     if (NT == 4) hipLaunchKernelGGL((fir_synth_kernel<TT, TX, 4>), grid, dim3(256), lds, s, a);
     else hipLaunchKernelGGL((fir_synth_kernel<TT, TX, 1>), grid, dim3(256), lds, s, a);
     return hipGetLastError();
@@ -190,8 +217,8 @@ hipError_t launch_fir_synth(const FirSynthArgs& a, hipStream_t s, std::string* w
 
 hipError_t apv_launch_fir_synthesis(int taps_f64, int x_f64, const FirSynthArgs& a, hipStream_t s, std::string* why) {
     if (a.J < 1 || a.H < 1 || a.L < 1 || a.nV < 1 || a.nz < 0 || a.nz > 2 || (a.n_tgt != 0 && a.n_tgt != 2) ||
-        a.nz * a.nV + a.n_tgt < 1 || a.nz * a.nV + a.n_tgt > 65535 || !a.out) {
-        if (why) *why = "FIR synthesis: J, H, L, nV must be positive, with at most two zone programs";
+        a.nz * a.nV + a.n_tgt < 1 || (long)(a.nz * a.nV + a.n_tgt) * std::max(a.n_hops, 1) > 65535 || !a.out) {
+        if (why) *why = "FIR synthesis: J, H, L, nV must be positive, with at most two zone programs and at most 65535 groups x hops";
         return hipErrorInvalidValue;
     }
     if (a.n_tgt && (a.delay < 0 || a.delay >= a.J)) {
@@ -200,6 +227,20 @@ hipError_t apv_launch_fir_synthesis(int taps_f64, int x_f64, const FirSynthArgs&
     }
     if (taps_f64) return x_f64 ? launch_fir_synth<double, double>(a, s, why) : launch_fir_synth<double, float>(a, s, why);
     return x_f64 ? launch_fir_synth<float, double>(a, s, why) : launch_fir_synth<float, float>(a, s, why);
+}
+
+hipError_t apv_launch_fir_synth_rows(int x_f64, int J, int H, int nc, const void* const head[2], size_t head_off, const void* pin,
+                                     void* const rows[2], hipStream_t s) {
+    if (J < 1 || H < 1 || nc < 1) return hipErrorInvalidValue;
+    const size_t len = (size_t)J - 1 + (size_t)nc * H;
+    const dim3 grid((unsigned)std::min<size_t>((len + 255) / 256, 1024), 2);
+    if (x_f64)
+        hipLaunchKernelGGL(fir_synth_rows_kernel<double>, grid, dim3(256), 0, s, J, H, nc, (const double*)head[0], (const double*)head[1],
+                           head_off, (const double*)pin, (double*)rows[0], (double*)rows[1]);
+    else
+        hipLaunchKernelGGL(fir_synth_rows_kernel<float>, grid, dim3(256), 0, s, J, H, nc, (const float*)head[0], (const float*)head[1],
+                           head_off, (const float*)pin, (float*)rows[0], (float*)rows[1]);
+    return hipGetLastError();
 }
 
 hipError_t apv_launch_fir_synth_advance(int taps_f64, int x_f64, const FirSynthAdvance& a, hipStream_t s) {

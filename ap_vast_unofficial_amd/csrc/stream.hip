@@ -146,6 +146,11 @@ struct apv_stream {
     void* fs_hist[2][2];          // [buf][signal][J - 1]: the newest input samples; buf = cur, like the input histories of K1
     hipEvent_t fs_ev[2];          // APV_FIR_SYNTHESIS_TIMING (tools/bench_fir_synthesis.py): events around the synthesis launch
     double fs_ms[2];              // ... and {sum of its times in ms, hops timed}
+    // chunked whole-signal path of a constrained stream (process_signal_chunked_t; allocated by chunk_prepare for such a stream only)
+    void* ck_taps[2];             // per zone program: [sig_chunk][nV][J][L], the taps of every hop of a chunk (ONE projection launch)
+    void* ck_xrow[2][2];          // [chunk parity][signal]: [J - 1 samples before the chunk | sig_chunk H samples of the chunk], FIR synthesis
+    hipEvent_t ck_wallfree;       // hop-by-hop regime: the tail stream has read ck_wall / ck_taps of a chunk for the last time
+    int32_t sched[2];             // state "signal_schedule": hops of the last whole-signal call {through chunk launches, hop by hop}
     hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
     double win_ms[2];             // ... and {sum of its times in ms, hops timed}
     std::vector<hipGraphExec_t> execs;
@@ -267,6 +272,12 @@ void apv_stream_free(apv_handle* h) {
         if (s->ck_X[p]) (void)hipFree(s->ck_X[p]);
     if (s->ck_inspec) (void)hipFree(s->ck_inspec);
     if (s->ck_out) (void)hipFree(s->ck_out);
+    for (int z = 0; z < 2; ++z) {
+        if (s->ck_taps[z]) (void)hipFree(s->ck_taps[z]);
+        for (int g = 0; g < 2; ++g)
+            if (s->ck_xrow[z][g]) (void)hipFree(s->ck_xrow[z][g]);
+    }
+    if (s->ck_wallfree) (void)hipEventDestroy(s->ck_wallfree);
     if (s->ck_ospec) (void)hipFree(s->ck_ospec);
     apv_live_free(s->live);
     if (s->live_cm) (void)hipFree(s->live_cm);
@@ -433,6 +444,9 @@ struct BackSchedule {
     bool no_copy = false;
     void* lspill = nullptr;   // GevdParams::Lspill of this launch (nullptr: the handle's d_Lspill)
     bool skip_gevd = false;   // the filters are there already: the chunk's joint diagonalisations were one launch (enqueue_gevd_hops)
+    // chunked whole-signal path of a constrained stream: the projection of a whole chunk is one launch of the caller's
+    bool skip_constrain = false;   // ... so the filters are projected already
+    bool gevd_only = false;        // ... or will be: this call ends behind the joint diagonalisation (hop-by-hop regime, back streams)
 };
 
 // Back half of a hop on stream `st`: spectra of set `set` -> per-bin filters (K5'-K10), output spectra (K3), synthesis
@@ -500,7 +514,8 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
         hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why, h->rank_list.data());
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
     }
-    if (s->taps > 0) {
+    if (sch.gevd_only) return APV_OK;
+    if (s->taps > 0 && !sch.skip_constrain) {
         // the hop's filters projected onto J-tap responses, in place, both zone programs in one launch: K3, the attributes and the
         // states read the projected filters
         void *cw[2], *ct[2];
@@ -517,9 +532,9 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
     if (s->fir_synth) {
         // FIR synthesis in place of K3 and K4: the hop's taps and the taps of the hop before it applied to the input signals in
         // one launch, the target paths (pure delays) included, written where K4 writes; a second, small launch then makes this
-        // hop's taps and the newest J - 1 samples the next hop's.  Only the per-hop path reaches here (process_signal_t sends a
-        // constrained stream through it), after enqueue_front: the hop's samples lie behind `keep` older ones in the current
-        // input history, and the synthesis' own history alternates between two buffers with it.
+        // hop's taps and the newest J - 1 samples the next hop's.  Only the per-hop path reaches here (the chunked whole-signal
+        // path launches the synthesis of a whole chunk itself), after enqueue_front: the hop's samples lie behind `keep` older ones
+        // in the current input history, and the synthesis' own history alternates between two buffers with it.
         const int J = s->taps, c = s->cur;
         FirSynthArgs a{};
         FirSynthAdvance adv{};
@@ -820,11 +835,13 @@ static int signal_prepare(apv_handle* h) {
 // device works on the next.
 template <typename TI>
 static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out);
+template <typename TI>
+static int process_signal_pipelined_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out);
 
 // The whole-signal call of a stream with a statistics window: the hops one after the other through the per-hop path (its graphs
 // included), so the samples are those of n_hops per-hop calls by construction.  (One statistics launch per chunk of hops is the
-// follow-up named in DESIGN.md section 4.13.)  A stream with the filter-length constraint takes it too: the chunked and batched
-// schedules do not launch the projection (the follow-up named in DESIGN.md section 4.15).
+// follow-up named in DESIGN.md section 4.13.)  A constrained stream takes it where the chunked schedule does not apply (see
+// process_signal_t) and where the projection or the FIR synthesis is being timed launch by launch.
 template <typename TI>
 static int process_signal_hops_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
     apv_stream* s = h->st;
@@ -854,10 +871,26 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     if (!s) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
     if (n_hops < 0) return apv_fail(h, APV_ERR_ARG, "n_hops must be >= 0");
     if (n_hops == 0) return APV_OK;
-    if (explicit_stats(s) || s->taps > 0) return process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
-    // K1 as one fast-convolution segment (responses of 64 taps or more): a chunk of hops per launch (below); direct-form K1 (shorter
-    // responses, APV_FIR_DIRECT) and partitioned K1 keep the hop-by-hop pipeline of this function
-    if (s->fir_F > 0 && s->fir_np == 1) return process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    // K1 as one fast-convolution segment (responses of 64 taps or more): a chunk of hops per launch (process_signal_chunked_t);
+    // direct-form K1 (shorter responses, APV_FIR_DIRECT) and partitioned K1 keep the hop-by-hop pipeline (process_signal_pipelined_t).  A
+    // constrained stream takes the chunked schedule or the plain hop loop: never the pipeline, which does not order the projections
+    // of consecutive hops; and the hop loop when its projection or synthesis is timed (the switches promise un-captured per-hop
+    // launches, tools/bench_filter_constraint.py and tools/bench_fir_synthesis.py read one time per hop).
+    const bool chunked = !explicit_stats(s) && s->fir_F > 0 && s->fir_np == 1 && !(s->taps > 0 && (s->cf_ev[0] || s->fs_ev[0]));
+    const long hop_before = s->hop;
+    int rc;
+    if (chunked) rc = process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    else if (explicit_stats(s) || s->taps > 0) rc = process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    else rc = process_signal_pipelined_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    s->sched[0] = chunked ? (int32_t)(s->hop - hop_before) : 0;
+    s->sched[1] = chunked ? 0 : (int32_t)(s->hop - hop_before);
+    return rc;
+}
+
+// the hop-by-hop pipeline of the whole-signal call (direct-form or partitioned K1, no statistics window, no constraint)
+template <typename TI>
+static int process_signal_pipelined_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
+    apv_stream* s = h->st;
     SCHK(h, hipSetDevice(h->device));
     int rc = signal_prepare(h);
     if (rc != APV_OK) return rc;
@@ -993,6 +1026,15 @@ static int chunk_prepare(apv_handle* h) {
     if ((rc = dalloc(h, &s->ck_inspec, (size_t)2 * chunk * 2 * K, e2))) return rc;
     if ((rc = dalloc(h, &s->ck_out, (size_t)2 * chunk * hop_result_bytes(s), 1))) return rc;
     if ((rc = dalloc(h, &s->ck_ospec, (size_t)2 * chunk * s->n_out * K, e2))) return rc;
+    if (s->taps > 0) {
+        for (int z = 0; z < 2; ++z)
+            if ((s->zones & (1 << z)) && (rc = dalloc(h, &s->ck_taps[z], (size_t)chunk * s->nV * s->taps * L, lsz(h)))) return rc;
+        SCHK(h, hipEventCreateWithFlags(&s->ck_wallfree, hipEventDisableTiming));
+    }
+    if (s->fir_synth)
+        for (int q = 0; q < 2; ++q)
+            for (int g = 0; g < 2; ++g)
+                if ((rc = dalloc(h, &s->ck_xrow[q][g], (size_t)s->taps - 1 + (size_t)chunk * s->H, e1))) return rc;
     SCHK(h, hipStreamSynchronize(h->stream));               // the zero-fills above
     s->ck_RL = (int)RL;
     return APV_OK;
@@ -1020,6 +1062,11 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     const int N = s->N, H = s->H, K = s->K, L = s->L, M = s->M, C = s->C, P = s->P, f64 = s->f64, chunk = s->sig_chunk, RL = s->ck_RL;
     const size_t e1 = s->esz, e2 = 2 * s->esz;
     const bool runA = s->zones & 1, runB = s->zones & 2;
+    // a constrained stream: ONE projection launch per chunk behind the chunk's joint diagonalisations, whose filters all go to
+    // ck_wall; with FIR synthesis ONE synthesis launch per chunk in place of K3 and K4 (see the two regimes below)
+    const bool cons = s->taps > 0, fir = s->fir_synth != 0;
+    const int J = s->taps;
+    const size_t hop_w = (size_t)K * s->nV * L * wsz(h), hop_lam = (size_t)K * L * lsz(h), hop_taps = (size_t)s->nV * J * L * lsz(h);
     // the chunk's joint diagonalisations as one launch where the kernel that will run takes several hops (order 16, absolute loading,
     // no diagnostics); elsewhere hop by hop on the back streams
     bool batched = false;
@@ -1076,6 +1123,42 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     const size_t spec_bytes = ((size_t)s->fir_F / 2 + 1) * e2;       // one input spectrum of K1
     int last_par = 0, last_nc = 0, last_b = 0;
     std::string why;
+    // the filters of the chunk's nc hops (ck_wall) projected in place, their taps to ck_taps: one launch on `st`
+    auto project_chunk = [&](hipStream_t st, int nc) -> hipError_t {
+        void *cw[2], *ct[2];
+        int nz = 0;
+        for (int z = 0; z < 2; ++z) {
+            if (!(z ? runB : runA)) continue;
+            cw[nz] = s->ck_wall[z]; ct[nz] = s->ck_taps[z]; ++nz;
+        }
+        return apv_launch_constrain_filters_hops(h->cfg.out_c128, N, J, s->nV, L, nz, cw, ct, nc, hop_w / wsz(h), hop_taps / lsz(h), st, &why);
+    };
+    // the FIR synthesis of the chunk's nc hops into their result slots: one launch on `st`, hop i fading from the taps of hop i - 1
+    // (hop 0 from fs_taps), and behind it the last hop's taps to fs_taps for the next chunk or call
+    auto synth_chunk = [&](hipStream_t st, int par, int nc) -> hipError_t {
+        FirSynthArgs a{};
+        int nz = 0;
+        for (int z = 0; z < 2; ++z) {
+            if (!(z ? runB : runA)) continue;
+            a.prev[nz] = s->fs_taps[z]; a.cur[nz] = s->ck_taps[z]; a.sig[nz] = z; ++nz;
+        }
+        for (int g = 0; g < 2; ++g) {
+            a.xhist[g] = s->ck_xrow[par][g];
+            a.xhop[g] = (const char*)s->ck_xrow[par][g] + (size_t)(J - 1) * e1;
+        }
+        a.nz = nz; a.nV = s->nV; a.L = L; a.J = J; a.H = H;
+        a.n_tgt = 2; a.ref = s->fs_ref; a.delay = s->fs_delay;
+        a.out = (char*)s->ck_out + (size_t)par * chunk * hop_result_bytes(s);
+        a.sn = s->out_group > 0 ? L : 1;
+        a.sl = s->out_group > 0 ? 1 : H;
+        a.n_hops = nc; a.hop_taps = hop_taps / lsz(h); a.hop_x = H; a.hop_out = hop_result_bytes(s);
+        hipError_t e = apv_launch_fir_synthesis(h->cfg.out_c128, f64, a, st, &why);
+        for (int z = 0; z < 2 && e == hipSuccess; ++z)
+            if (z ? runB : runA)
+                e = hipMemcpyAsync(s->fs_taps[z], (char*)s->ck_taps[z] + (size_t)(nc - 1) * hop_taps, hop_taps, hipMemcpyDeviceToDevice, st);
+        return e;
+    };
+    auto ckl = [&](hipError_t e) { return bail(APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why); };
     for (int c = 0; c < n_chunks && worst != APV_ERR_NOT_PD; ++c) {
         const int base = c * chunk, nc = std::min(chunk, n_hops - base), par = c & 1;
         char* const pin = (char*)s->ck_pin_in + (size_t)(c % CK_NS) * chunk * 2 * H * e1;
@@ -1084,6 +1167,8 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
         // the spectra sets and linear buffers of this parity were last read by the back halves of chunk c - 2
         if (c >= 2)
             for (int b = 0; b < CK_NB; ++b) CK(hipStreamWaitEvent(s->front, s->ck_backdone[par][b], 0));
+        // ... and, in a constrained stream, by what follows the chunk's projection: K3, or the synthesis reading the input rows
+        if (cons && c >= 2) CK(hipStreamWaitEvent(s->front, s->ck_done[(c - 2) % CK_NS], 0));
         CK(apv_launch_fir_chunk_spectra(f64, s->fir_F, P, H, nc, s->xhist[s->cur][0], s->xhist[s->cur][1], pin, s->xspec_chunk, s->front));
         // heads of the linear buffers: the newest N - H samples before the chunk, from the rings (first chunk) or from the tail
         // of the previous chunk's buffers
@@ -1102,6 +1187,14 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             void* nh[2] = {s->xhist[s->cur ^ 1][0], s->xhist[s->cur ^ 1][1]};
             CK(apv_launch_chunk_inputs(f64, P, H, N, nc, s->pad, RL, oh, nh, pin, s->ck_in[par], s->front));
             s->cur ^= 1;
+        }
+        if (fir) {
+            // the synthesis' linear input rows [J - 1 samples before the chunk | the chunk]: the head from the synthesis' history
+            // (first chunk) or from the tail of the other parity's rows (the chunk before: always full)
+            const void* head[2] = {c == 0 ? s->fs_hist[cur_first][0] : s->ck_xrow[par ^ 1][0],
+                                   c == 0 ? s->fs_hist[cur_first][1] : s->ck_xrow[par ^ 1][1]};
+            void* rows[2] = {s->ck_xrow[par][0], s->ck_xrow[par][1]};
+            CK(apv_launch_fir_synth_rows(f64, J, H, nc, head, c == 0 ? 0 : (size_t)chunk * H, pin, rows, s->front));
         }
         {
             // K1: every (hop, channel) of the chunk in one launch
@@ -1166,7 +1259,6 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             hipStream_t b0 = bs[0];
             CK(hipStreamWaitEvent(b0, s->ev_front[par], 0));
             if (c >= 2) CK(hipStreamWaitEvent(b0, s->ck_done[(c - 2) % CK_NS], 0));        // the result slots of this parity are free
-            const size_t hop_w = (size_t)K * s->nV * L * wsz(h), hop_lam = (size_t)K * L * lsz(h);
             {
                 GevdParams p = apv_base_params(h);
                 const HopSpectra q0 = set_of(par, 0);
@@ -1196,10 +1288,25 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
                 hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, b0, &why);
                 if (e != hipSuccess) return bail(APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
             }
-            for (int i = 0; i < nc; ++i) {
+            if (cons) {
+                const hipError_t e = project_chunk(b0, nc);
+                if (e != hipSuccess) return ckl(e);
+            }
+            if (fir) {
+                // K3 and K4 are not launched: the chunk's synthesis writes the result slots, and the tail stream only copies them back
+                const hipError_t e = synth_chunk(b0, par, nc);
+                if (e != hipSuccess) return ckl(e);
+                CK(hipEventRecord(s->ck_k3[0], b0));
+                CK(hipStreamWaitEvent(s->tail, s->ck_k3[0], 0));
+                CK(hipEventRecord(s->ck_backdone[par][0], b0));
+                last_par = par; last_nc = nc; last_b = 0;
+                s->hop += nc;
+            }
+            for (int i = 0; i < nc && !fir; ++i) {
                 const size_t slot = (size_t)par * chunk + i;
                 BackSchedule sch;
                 sch.skip_gevd = true;
+                sch.skip_constrain = cons;
                 sch.spectra_free = s->ck_k3[0];
                 sch.tail_stream = s->tail;
                 sch.result = (char*)s->ck_out + slot * hop_result_bytes(s);
@@ -1222,6 +1329,8 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
                 // the result slots of this parity are being copied back for chunk c - 2 (still in flight: the host collects two
                 // chunks behind)
                 if (c >= 2) CK(hipStreamWaitEvent(bs[b], s->ck_done[(c - 2) % CK_NS], 0));
+                // a constrained stream: the tail stream is done with the filters and taps of chunk c - 1 (one set of each)
+                if (cons && c >= 1) CK(hipStreamWaitEvent(bs[b], s->ck_wallfree, 0));
             }
             // Every hop of the two chunks in flight has result and output-spectra slots of its own, so a back stream never waits
             // for the tail stream inside a chunk: its next diagonalisation follows the previous one directly.
@@ -1234,11 +1343,43 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
             sch.no_copy = true;
             sch.yield_issue = 1;
             sch.lspill = b > 0 ? s->ck_spill[b - 1] : nullptr;
-            rc = enqueue_back(h, bs[b], set_of(par, i), wset[b], lset[b], nullptr, sch);
+            if (cons) {
+                // the back stream runs the joint diagonalisation alone, into the hop's own slots of ck_wall / ck_lamall: the
+                // projections share one taps buffer and the cross-fade needs hop order, both of which the tail stream keeps (below)
+                void* wz[2] = {(char*)s->ck_wall[0] + i * hop_w, (char*)s->ck_wall[1] + i * hop_w};
+                void* lz[2] = {(char*)s->ck_lamall[0] + i * hop_lam, (char*)s->ck_lamall[1] + i * hop_lam};
+                sch.gevd_only = true;
+                sch.spectra_free = nullptr;
+                rc = enqueue_back(h, bs[b], set_of(par, i), wz, lz, nullptr, sch);
+            } else {
+                rc = enqueue_back(h, bs[b], set_of(par, i), wset[b], lset[b], nullptr, sch);
+            }
             if (rc != APV_OK) return bail(rc, h->err);
             if (i + CK_NB >= nc) CK(hipEventRecord(s->ck_backdone[par][b], bs[b]));   // this stream's last hop of the chunk
             last_par = par; last_nc = nc; last_b = b;
             s->hop++;
+        }
+        if (cons && !batched) {
+            // the tail stream, behind the chunk's last diagonalisation on every back stream: the chunk's projection, then K3 + K4 hop
+            // by hop, or the chunk's FIR synthesis
+            for (int b = 0; b < CK_NB; ++b) CK(hipStreamWaitEvent(s->tail, s->ck_backdone[par][b], 0));
+            hipError_t e = project_chunk(s->tail, nc);
+            if (e == hipSuccess && fir) e = synth_chunk(s->tail, par, nc);
+            if (e != hipSuccess) return ckl(e);
+            for (int i = 0; i < nc && !fir; ++i) {
+                const size_t slot = (size_t)par * chunk + i;
+                BackSchedule sch;
+                sch.skip_gevd = true;
+                sch.skip_constrain = true;
+                sch.result = (char*)s->ck_out + slot * hop_result_bytes(s);
+                sch.ospec = (char*)s->ck_ospec + slot * (size_t)s->n_out * K * e2;
+                sch.no_copy = true;
+                void* wz[2] = {(char*)s->ck_wall[0] + i * hop_w, (char*)s->ck_wall[1] + i * hop_w};
+                void* lz[2] = {(char*)s->ck_lamall[0] + i * hop_lam, (char*)s->ck_lamall[1] + i * hop_lam};
+                rc = enqueue_back(h, s->tail, set_of(par, i), wz, lz, nullptr, sch);
+                if (rc != APV_OK) return bail(rc, h->err);
+            }
+            CK(hipEventRecord(s->ck_wallfree, s->tail));
         }
         // the chunk's results in ONE copy behind its last synthesis (16 hops: 6.4 MB at cfg3)
         CK(hipMemcpyAsync((char*)s->ck_pin_out + (size_t)(c % CK_NS) * chunk * hop_result_bytes(s),
@@ -1286,12 +1427,19 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
         for (int p = 0; p < 4; ++p) CK(hipMemcpyAsync(s->X[p], q.X[p], (size_t)s->Kp * C * e2, hipMemcpyDeviceToDevice, st));
         for (int z = 0; z < 2; ++z) CK(hipMemcpyAsync(s->tspec[z], q.tspec[z], (size_t)K * M * e2, hipMemcpyDeviceToDevice, st));
         CK(hipMemcpyAsync(s->inspec, q.inspec, (size_t)2 * K * e2, hipMemcpyDeviceToDevice, st));
-        if (batched) {
-            const size_t hop_w = (size_t)K * s->nV * L * wsz(h), hop_lam = (size_t)K * L * lsz(h);
+        if (batched || cons) {
             for (int z = 0; z < 2; ++z) {
                 CK(hipMemcpyAsync(s->w[z], (char*)s->ck_wall[z] + (size_t)(last_nc - 1) * hop_w, hop_w, hipMemcpyDeviceToDevice, st));
                 CK(hipMemcpyAsync(s->lam[z], (char*)s->ck_lamall[z] + (size_t)(last_nc - 1) * hop_lam, hop_lam, hipMemcpyDeviceToDevice, st));
             }
+            // a constrained stream: the last hop's taps, and the newest J - 1 input samples in the history buffer the next per-hop
+            // call reads (fs_taps took the last hop's taps behind the chunk's synthesis)
+            for (int z = 0; z < 2 && cons; ++z)
+                if (z ? runB : runA)
+                    CK(hipMemcpyAsync(s->wtaps[z], (char*)s->ck_taps[z] + (size_t)(last_nc - 1) * hop_taps, hop_taps, hipMemcpyDeviceToDevice, st));
+            for (int g = 0; g < 2 && fir && J > 1; ++g)
+                CK(hipMemcpyAsync(s->fs_hist[s->cur][g], (char*)s->ck_xrow[last_par][g] + (size_t)last_nc * H * e1, (size_t)(J - 1) * e1,
+                                  hipMemcpyDeviceToDevice, st));
         } else if (last_b != 0) {
             for (int z = 0; z < 2; ++z) {
                 CK(hipMemcpyAsync(s->w[z], wset[last_b][z], (size_t)K * s->nV * L * wsz(h), hipMemcpyDeviceToDevice, st));
@@ -1803,6 +1951,8 @@ int apv_set_mu(apv_handle* h, double mu) {
 //   "fir_synth_taps_A" / "fir_synth_taps_B" [nV][J][L] f32|f64 (cfg.out_c128)   the taps the next hop's FIR synthesis fades from;
 //   "fir_synth_history<g>" [J-1]   the newest samples of input signal g; both only with apv_stream_set_synthesis(h, APV_SYNTH_FIR)
 //   "fir_synthesis_kernel_ms" {sum, count} of the timed synthesis launches (APV_FIR_SYNTHESIS_TIMING), read-only
+//   "signal_schedule" int32 {hops of the last apv_process_signal* call that went through chunk launches, hops of it that went hop by
+//                                  hop}, read-only; {0, 0} before the first such call, untouched by the per-hop calls
 static int live_index(const char* name) {
     const std::string n(name);
     if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
@@ -1936,6 +2086,10 @@ int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
         *bytes = sizeof(h->st->fs_ms);
         return APV_OK;
     }
+    if (std::string(name) == "signal_schedule") {
+        *bytes = sizeof(h->st->sched);
+        return APV_OK;
+    }
     void* d; int rr;
     return state_lookup(h, name, &d, bytes, &rr);
 }
@@ -1956,6 +2110,11 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
     if (h->st->fir_synth && std::string(name) == "fir_synthesis_kernel_ms") {
         if (bytes != sizeof(h->st->fs_ms)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
         std::memcpy(h_dst, h->st->fs_ms, sizeof(h->st->fs_ms));
+        return APV_OK;
+    }
+    if (std::string(name) == "signal_schedule") {
+        if (bytes != sizeof(h->st->sched)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+        std::memcpy(h_dst, h->st->sched, sizeof(h->st->sched));
         return APV_OK;
     }
     void* d; size_t need; int rr;
@@ -2005,6 +2164,7 @@ int apv_set_state(apv_handle* h, const char* name, const void* h_src, size_t byt
                               h->stream);
     }
     if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), const_cast<void*>(h_src), bytes, false);
+    if (std::string(name) == "signal_schedule") return apv_fail(h, APV_ERR_STATE, "signal_schedule is read-only");
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;

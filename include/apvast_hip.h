@@ -158,7 +158,8 @@ int  apv_stream_set_stat_forgetting(apv_handle* h, double beta);
  * states "w_time_A" / "w_time_B" [nV][J][L] (float64 with cfg.out_c128, else float32) hold the taps g[:J] of the last hop: the
  * subband counterpart of the reference's J-tap w_A / w_B.  The target paths are a delta already and are not touched.  One more
  * kernel per hop (csrc/kernels_constrain.hip), part of the captured hop graphs; the taps buffers are allocated by apv_stream_init
- * only when J > 0.  apv_process_signal* on such a stream runs its hops through the per-hop path.  J = 0 (the default) switches the
+ * only when J > 0.  apv_process_signal* on such a stream projects the filters of a chunk of 16 hops in one launch where its chunked
+ * schedule applies (see there), else it runs its hops through the per-hop path.  J = 0 (the default) switches the
  * constraint off: the stream launches what it launches without this call, and has no "w_time_*" states.  Called between apv_create
  * and apv_stream_init; APV_ERR_ARG (nothing changed) once the stream is initialised or for J outside 0..block_size;
  * apv_stream_init refuses modeling_delay >= J (the reference puts its target tap at J ref + delay).
@@ -320,7 +321,11 @@ int  apv_process_block_f64(apv_handle* h, const double* h_in_A, const double* h_
  * stream beside the joint diagonalisation of hop h, synthesis and copy back on a third, and the host stages / converts
  * one chunk of 16 hops while the device runs the next.  A hop with a bin that is not positive definite returns APV_ERR_NOT_PD once the
  * chunks in flight (its own and at most one more) have run (the message names the hop; the stream's state is then that
- * after the last hop run); APV_ERR_NO_CONVERGE is returned after all hops, every output written.
+ * after the last hop run); APV_ERR_NO_CONVERGE is returned after all hops, every output written.  With responses of 64 taps or
+ * more (K1 in one fast-convolution segment) and no statistics window or forgetting, a chunk of 16 hops is a handful of launches:
+ * the front halves, and for a constrained stream the projection and the FIR synthesis, one launch per chunk each.  The read-only
+ * state "signal_schedule", two int32, tells which way the last call went: {hops through chunk launches, hops hop by hop};
+ * {0, 0} before the first call, and apv_process_block* does not touch it.
  *                        replaces the hop loop around processInputBuffer, main.m:52-62 / make_python_test.m:44-51 */
 int  apv_process_signal(apv_handle* h, int32_t n_hops, const float* h_in_A, const float* h_in_B, float* h_out);
 int  apv_process_signal_f64(apv_handle* h, int32_t n_hops, const double* h_in_A, const double* h_in_B, double* h_out);
