@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -150,6 +150,9 @@ def load():
     lib.apv_constrain_filters.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.apv_stream_set_synthesis.argtypes = [vp, i32]
     lib.apv_fir_synthesis.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.apv_stream_set_evaluation.argtypes = [vp, i32, i32, vp, vp, i32, vp]
+    lib.apv_stream_reset_evaluation.argtypes = [vp]
+    lib.apv_eval_pressure.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -223,7 +226,7 @@ class Engine:
     def __init__(self, n_bins, n_srcs, n_mics, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=None,
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
-                 out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola"):
+                 out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola", evaluation=None):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -279,6 +282,50 @@ class Engine:
         self.synthesis = "wola"
         if synthesis != "wola":
             self.set_synthesis(synthesis)
+        self.evaluation = None
+        if evaluation is not None:
+            self.set_evaluation(*evaluation)
+
+    def set_evaluation(self, rv_A, rv_B, ranks):
+        """Evaluation stage of the subband stream, before stream_init (apv_stream_set_evaluation): rv_A / rv_B (Pv, L, Mv) float64,
+        the responses to the validation microphones of zone A / B; ranks: the evaluated ranks, ascending, from the rank list."""
+        rv_A = np.ascontiguousarray(rv_A, dtype=np.float64)
+        rv_B = np.ascontiguousarray(rv_B, dtype=np.float64)
+        if rv_A.ndim != 3 or rv_A.shape != rv_B.shape or rv_A.shape[1] != self.L:
+            raise ValueError("rv_A and rv_B must both be (Pv, n_srcs, Mv)")
+        r = np.ascontiguousarray(ranks, dtype=np.int32).ravel()
+        Pv, _, Mv = rv_A.shape
+        self._chk(self.lib.apv_stream_set_evaluation(self.h, Pv, Mv, _ptr(rv_A), _ptr(rv_B), int(r.size), _ptr(r) if r.size else None))
+        self.evaluation = (Pv, Mv, [int(v) for v in r])
+
+    def reset_evaluation(self):
+        """Totals and output histories of the evaluation stage to zero (apv_stream_reset_evaluation)."""
+        self._chk(self.lib.apv_stream_reset_evaluation(self.h))
+
+    def eval_pressure(self, y, rv, H):
+        """The pressure kernel alone (apv_eval_pressure): y (G, Pv - 1 + H, L) samples -- per group the Pv - 1 in front of the
+        hop, then the hop -- in s_dtype, rv (Pv, L, Mv) float64 -> (G, H, Mv) float64, p[g, n, m] = sum_l sum_j rv[j, l, m]
+        y[g, Pv - 1 + n - j, l]."""
+        rv = np.ascontiguousarray(rv, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=self.s_dtype)
+        if rv.ndim != 3 or y.ndim != 3:
+            raise ValueError("y must be (G, Pv - 1 + H, L) and rv (Pv, L, Mv)")
+        Pv, L, Mv = rv.shape
+        G, H = y.shape[0], int(H)
+        if Pv >= 1 and H >= 1 and y.shape[1:] != (Pv - 1 + H, L):
+            raise ValueError("y must hold Pv - 1 + H samples of L loudspeakers per group")
+        dy, dr = self.alloc(max(y.nbytes, 8)), self.alloc(max(rv.nbytes, 8))
+        dp = self.alloc(max(G * H * Mv, 1) * 8)
+        try:
+            if y.size:
+                dy.upload(y)
+            if rv.size:
+                dr.upload(rv)
+            self._chk(self.lib.apv_eval_pressure(self.h, dy.ptr, dr.ptr, G, L, Pv, H, Mv, dp.ptr))
+            return dp.download((G, H, Mv), np.float64)
+        finally:
+            for b in (dy, dr, dp):
+                b.free()
 
     def set_synthesis(self, mode):
         """Synthesis of the subband stream, before stream_init (apv_stream_set_synthesis): "wola" (the reference's overlap-add)

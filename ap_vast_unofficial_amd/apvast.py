@@ -54,6 +54,15 @@ What is different (keyword-only, after ``perceptual``)
     the hop; the target outputs are the inputs delayed by modeling_delay in column reference_index_A.  Return shapes, w_*,
     lambda_*, w_time_* and everything else the design half leaves are unchanged; get_state() gains ``fir_synthesis_taps`` (zone
     programs that run, V, J, L) and ``fir_synthesis_history`` (2, J - 1), and ``out_overlap`` stays, untouched by the hops.
+  * ``validation_rir_A`` / ``validation_rir_B`` (subband mode; both or neither, float64 (Pv, L, Mv), finite): an evaluation stage
+    behind the synthesis of every hop.  The device filters the hop's own drive signals through the responses to validation
+    microphones of both zones (Matlab/main.m:64-76 with predictPressure.m, carried across hops), keeps the pressures of the last
+    hop, and accumulates per microphone the energies bright = sum p_own^2, dark = sum p_other^2, error = sum (p_target - p_own)^2
+    and target = sum p_target^2, all in float64.  ``evaluation_ranks``: the ranks evaluated (None: every rank 1..V).
+    ``evaluation_hops()``, ``evaluation_totals()``, ``predicted_pressure()`` fetch them when called, ``reset_evaluation()`` zeroes
+    totals and histories, ``evaluation.metrics(totals)`` gives NMSE and contrast in dB (main.m:120-130); get_state() gains
+    ``evaluation_history`` (Z, E + 1, Pv - 1, L) and ``evaluation_totals`` (Z, 3 E + 1, Mv).  Outputs, filters and every other state
+    are those of the same stream without the keywords, bit for bit; process_signal runs such a stream hop by hop.
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).
@@ -148,6 +157,9 @@ class apvast:
                  sweep_tol2: float = 0.0,
                  constrain_filter_length=False,
                  synthesis="wola",
+                 validation_rir_A=None,
+                 validation_rir_B=None,
+                 evaluation_ranks=None,
                  statistics_forgetting=None,
                  statistics_hops=1):
         self.block_size = block_size
@@ -190,6 +202,7 @@ class apvast:
         self.window = np.sin(np.pi / self.block_size * np.arange(self.block_size)).reshape(-1, 1)   # apvast.py:94
         self.rir_length, self.number_of_srcs, self.number_of_mics = rir_A.shape  # apvast.py:97-99
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
+        self._evaluation = self._check_evaluation(validation_rir_A, validation_rir_B, evaluation_ranks, L, number_of_eigenvectors, mode)
         self._init_responses(rir_A, rir_B)
         if mode == "broadband":
             self._init_broadband(device, seed)
@@ -213,7 +226,7 @@ class apvast:
                                  out_layout=1,     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
                                  stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting,
                                  filter_taps=int(filter_length) if self.constrain_filter_length else 0,
-                                 synthesis=self.synthesis)
+                                 synthesis=self.synthesis, evaluation=self._evaluation)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -299,6 +312,86 @@ class apvast:
         if not constrain_filter_length:
             raise ValueError("synthesis='fir' needs constrain_filter_length=True: it applies the filter_length taps of w_time_*")
         return value
+
+    @staticmethod
+    def _check_evaluation(rv_A, rv_B, ranks, L, V, mode):
+        """The evaluation keywords as None (off) or (rv_A, rv_B, ranks): float64 (Pv, L, Mv) responses of equal shape, finite,
+        and the evaluated ranks, strictly ascending within 1..V (None: every rank)."""
+        if rv_A is None and rv_B is None:
+            if ranks is not None:
+                raise ValueError("evaluation_ranks needs validation_rir_A and validation_rir_B")
+            return None
+        if mode == "broadband":
+            raise ValueError("validation_rir_A / validation_rir_B are a subband keyword: broadband mode has no evaluation stage")
+        if rv_A is None or rv_B is None:
+            raise ValueError("validation_rir_A and validation_rir_B go together: both or neither")
+        a, b = np.array(rv_A, dtype=np.float64), np.array(rv_B, dtype=np.float64)
+        if a.ndim != 3 or a.shape != b.shape:
+            raise ValueError(f"validation_rir_A and validation_rir_B must have one shape (Pv, L, Mv), got {a.shape} and {b.shape}")
+        if a.shape[1] != L or a.shape[0] < 1 or a.shape[2] < 1:
+            raise ValueError(f"validation_rir_*: (Pv, L, Mv) with L = {L} loudspeakers (the constructor's) and Pv, Mv >= 1, got {a.shape}")
+        if not (np.isfinite(a).all() and np.isfinite(b).all()):
+            raise ValueError("validation_rir_A and validation_rir_B must be finite")
+        V = int(V)
+        if ranks is None:
+            r = list(range(1, V + 1))
+        else:
+            try:
+                r = list(ranks)
+            except TypeError:
+                raise ValueError("evaluation_ranks must be None or a strictly ascending list of ranks within 1..number_of_eigenvectors")
+            ok = len(r) >= 1 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 1 <= int(v) <= V for v in r)
+            if not ok or any(int(r[i]) <= int(r[i - 1]) for i in range(1, len(r))):
+                raise ValueError("evaluation_ranks must be None or a strictly ascending list of ranks within 1..number_of_eigenvectors")
+            r = [int(v) for v in r]
+        return a, b, r
+
+    # ---- the evaluation stage (validation_rir_A / validation_rir_B): read from the device when asked for ------------------
+    def _eval_dims(self):
+        if self.__dict__.get("_evaluation") is None:
+            raise RuntimeError("this object has no evaluation stage: pass validation_rir_A and validation_rir_B")
+        a, _, r = self._evaluation
+        return int(self.run_A) + int(self.run_B), len(r), a.shape[0], a.shape[2]
+
+    @staticmethod
+    def _eval_split(e, E):
+        """(..., Z, 3 E + 1, Mv) -> the dict of bright, dark, error (..., Z, E, Mv) and target (..., Z, Mv)."""
+        return {"bright": np.ascontiguousarray(e[..., :E, :]), "dark": np.ascontiguousarray(e[..., E:2 * E, :]),
+                "error": np.ascontiguousarray(e[..., 2 * E:3 * E, :]), "target": np.ascontiguousarray(e[..., 3 * E, :])}
+
+    def evaluation_hops(self):
+        """Energies per hop of the last process_input_buffers / process_signal call: "bright", "dark", "error" (n, Z, E, Mv) and
+        "target" (n, Z, Mv): n hops, Z zone programs that run (A first), E evaluated ranks.  None before the first hop."""
+        Z, E, _, Mv = self._eval_dims()
+        if self._hops == 0:
+            return None
+        n = self._eng.state_bytes("eval_hops") // (8 * Z * (3 * E + 1) * Mv)
+        if n == 0:
+            return None
+        return self._eval_split(self._eng.get_state("eval_hops", (n, Z, 3 * E + 1, Mv), np.float64), E)
+
+    def evaluation_totals(self):
+        """The energies summed over every hop since construction, set_state or reset_evaluation(): "bright", "dark", "error"
+        (Z, E, Mv), "target" (Z, Mv); evaluation.metrics() turns them into NMSE and contrast.  None before the first hop."""
+        Z, E, _, Mv = self._eval_dims()
+        if self._hops == 0:
+            return None
+        return self._eval_split(self._eng.get_state("eval_totals", (Z, 3 * E + 1, Mv), np.float64), E)
+
+    def predicted_pressure(self):
+        """Pressures of the last hop at the validation microphones: "bright" (own zone's microphones) and "dark" (the other
+        zone's) (Z, E, H, Mv), "target" (the target output at the own zone's) (Z, H, Mv).  None before the first hop."""
+        Z, E, _, Mv = self._eval_dims()
+        if self._hops == 0:
+            return None
+        p = self._eng.get_state("eval_pressure", (Z, 2 * E + 1, self.hop_size, Mv), np.float64)
+        return {"bright": np.ascontiguousarray(p[:, :E]), "dark": np.ascontiguousarray(p[:, E:2 * E]),
+                "target": np.ascontiguousarray(p[:, 2 * E])}
+
+    def reset_evaluation(self):
+        """Totals to zero and the output histories to silence: the next hop's totals are its own energies."""
+        self._eval_dims()
+        self._eng.reset_evaluation()
 
     # ---- responses and mu, reassignable between hops (the reference reads them on every hop, apvast.py:161, 167-193) ----
     def _init_responses(self, rir_A, rir_B):
@@ -665,6 +758,7 @@ class apvast:
     _WIN_STATE = ("statistics_window", "statistics_window_fill")    # present with statistics_hops > 1
     _FORGET_STATE = ("statistics_forgetting_sums",)                  # present with statistics_forgetting set
     _FIR_STATE = ("fir_synthesis_taps", "fir_synthesis_history")    # present with synthesis="fir"
+    _EVAL_STATE = ("evaluation_history", "evaluation_totals")       # present with validation_rir_A / validation_rir_B
 
     def get_state(self):
         """Everything the next hop depends on (the reference's instance attributes of apvast.py:115-151), as float64 arrays
@@ -696,6 +790,14 @@ class apvast:
                                                  for z, run in enumerate((self.run_A, self.run_B)) if run]).astype(np.float64)
             st["fir_synthesis_history"] = np.stack([e.get_state(f"fir_synth_history{g}", (J - 1,), e.s_dtype) if J > 1 else np.zeros(0)
                                                     for g in range(2)]).astype(np.float64)
+        if self.mode == "subband" and self._evaluation is not None:
+            # the newest Pv - 1 output samples of every evaluated group (zone programs that run; the E ranks, then the target)
+            # and the accumulated energies [bright of the E ranks | dark | error | target]
+            Z, E, Pv, Mv = self._eval_dims()
+            e, L = self._eng, self.number_of_srcs
+            st["evaluation_history"] = (e.get_state("eval_history", (Z, E + 1, Pv - 1, L), e.s_dtype) if Pv > 1
+                                        else np.zeros((Z, E + 1, 0, L))).astype(np.float64)
+            st["evaluation_totals"] = e.get_state("eval_totals", (Z, 3 * E + 1, Mv), np.float64)
         if self._live_applied:
             P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
             Q = max(P - 1, 1)
@@ -746,6 +848,8 @@ class apvast:
             known = known + self._FORGET_STATE
         if self.mode == "subband" and self.synthesis == "fir":
             known = known + self._FIR_STATE
+        if self.mode == "subband" and self._evaluation is not None:
+            known = known + self._EVAL_STATE
         unknown = sorted(set(state) - set(known))
         if unknown:
             raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
@@ -781,6 +885,20 @@ class apvast:
                 raise ValueError(f"fir_synthesis_history must have shape {(2, J - 1)}, got {hst.shape}")
             for g in range(2 if J > 1 else 0):
                 e.set_state(f"fir_synth_history{g}", np.ascontiguousarray(hst[g], dtype=e.s_dtype))
+        if "evaluation_history" in state or "evaluation_totals" in state:
+            Z, E, Pv, Mv = self._eval_dims()
+            L = self.number_of_srcs
+            if "evaluation_history" in state:
+                hst = np.asarray(state["evaluation_history"])
+                if hst.shape != (Z, E + 1, Pv - 1, L):
+                    raise ValueError(f"evaluation_history must have shape {(Z, E + 1, Pv - 1, L)}, got {hst.shape}")
+                if Pv > 1:
+                    e.set_state("eval_history", np.ascontiguousarray(hst, dtype=e.s_dtype))
+            if "evaluation_totals" in state:
+                tot = np.asarray(state["evaluation_totals"])
+                if tot.shape != (Z, 3 * E + 1, Mv):
+                    raise ValueError(f"evaluation_totals must have shape {(Z, 3 * E + 1, Mv)}, got {tot.shape}")
+                e.set_state("eval_totals", np.ascontiguousarray(tot, dtype=np.float64))
         if "statistics_window_fill" in state:
             e.set_state("stat_window_fill", np.array([int(state["statistics_window_fill"])], dtype=np.int32))
         if any(k in state for k in self._LIVE_STATE):

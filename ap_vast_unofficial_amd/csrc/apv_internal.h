@@ -90,6 +90,10 @@ struct apv_handle {
     double stat_forgetting;          // apv_stream_set_stat_forgetting: forgetting factor of the next apv_stream_init in (0, 1]; 0: off
     int filter_taps;                 // apv_stream_set_filter_taps: J of the next apv_stream_init's filter-length constraint; 0: off
     int synthesis;                   // apv_stream_set_synthesis: APV_SYNTH_WOLA (0) or APV_SYNTH_FIR of the next apv_stream_init
+    // apv_stream_set_evaluation: the evaluation stage of the next apv_stream_init (eval_Pv = 0: off)
+    int eval_Pv, eval_Mv;
+    std::vector<double> eval_rv[2];  // validation responses of zone A, zone B: [Pv][L][Mv]
+    std::vector<int32_t> eval_ranks; // evaluated ranks, ascending, each in rank_list
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -311,6 +315,43 @@ hipError_t apv_launch_fir_synth_advance(int taps_f64, int x_f64, const FirSynthA
 // the pinned staging pin [nc][2][H]; samples float or double (x_f64).  head and rows must not overlap
 hipError_t apv_launch_fir_synth_rows(int x_f64, int J, int H, int nc, const void* const head[2], size_t head_off, const void* pin,
                                      void* const rows[2], hipStream_t s);
+
+// kernels_streameval.hip: the evaluation stage of the subband stream (see the file header).  One launch computes the pressures
+// p [n_sets][H][Mv] (float64) of n_sets pressure sets; set i filters group map[4 i] of the hop's result buffer -- element (g, n, l)
+// at hop[g hop_stride + n sn + l sl], with the Pv - 1 samples in front of the hop at hist[map[4 i + 1] hist_stride + q L + l] --
+// through the bank rv[map[4 i + 2]] [Pv][L][Mv].  map = nullptr: set i reads group i, history i, bank 0.  Samples float or double
+// (x_f64); banks and pressures float64.
+struct EvalPressureArgs {
+    const void* hist;
+    const void* hop;
+    size_t hist_stride, hop_stride;
+    long sn, sl;
+    const double* rv[2];
+    const int32_t* map;
+    double* p;
+    int n_sets, Pv, H, L, Mv;
+};
+bool apv_eval_pressure_fits(int Pv);           // one loudspeaker's window fits LDS: Pv <= 20465
+// outside a capture, once per (precision, geometry): lets the kernel that (Pv, H, L) selects use more than 64 KB of LDS where it must
+hipError_t apv_eval_pressure_prepare(int x_f64, int Pv, int H, int L);
+hipError_t apv_launch_eval_pressure(int x_f64, const EvalPressureArgs& a, hipStream_t s, std::string* why);
+// behind it: the energies of the hop from p [Z][2 E + 1][H][Mv] (per program: bright of E ranks, dark of E ranks, target) into slot
+// ctl[2 + par] of the record at ctl[0] (ctl[1] slots; [Z][3 E + 1][Mv] per slot: bright, dark, error per rank, target) and added to
+// totals; ctl[2 + (par ^ 1)] <- slot + 1; new_hist[g] <- the Pv - 1 newest samples of [old_hist[g] | group hist_src[g] of the hop]
+struct EvalAdvanceArgs {
+    const double* p;
+    double* totals;
+    unsigned long long* ctl;
+    int par;
+    const void* old_hist;
+    void* new_hist;
+    const void* hop;
+    size_t hop_stride;
+    long sn, sl;
+    const int32_t* hist_src;
+    int Z, E, H, Mv, Pv, L, n_hist;
+};
+hipError_t apv_launch_eval_advance(int x_f64, const EvalAdvanceArgs& a, hipStream_t s);
 
 // whole-signal path, a chunk of hops per launch (kernels_stft.hip / kernels_stream.hip; see process_signal_chunked_t in stream.hip)
 hipError_t apv_launch_stft_analysis_chunk(int f64, int N, int n_jobs, const void* const* x, const int* n_ch, void* const* spec,

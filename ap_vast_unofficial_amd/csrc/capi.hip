@@ -232,6 +232,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     h->stat_forgetting = 0.0;
     h->filter_taps = 0;
     h->synthesis = APV_SYNTH_WOLA;
+    h->eval_Pv = h->eval_Mv = 0;
     h->gl_ws = nullptr;
     h->gl_tol2 = 0.0;
     h->gl_lead_rank = 0;
@@ -889,6 +890,28 @@ int apv_fir_synthesis(apv_handle* h, const void* d_x, const void* d_taps_prev, c
     a.out = d_out; a.sn = L; a.sl = 1;
     std::string why;
     hipError_t e = apv_launch_fir_synthesis(c.out_c128, x_f64, a, h->stream, &why);
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
+int apv_eval_pressure(apv_handle* h, const void* d_y, const double* d_rv, int32_t G, int32_t L, int32_t Pv, int32_t H, int32_t Mv,
+                      double* d_p) {
+    if (!h || !d_y || !d_rv || !d_p) return fail(h, APV_ERR_ARG, "null device pointer");
+    if (G < 1 || L < 1 || Pv < 1 || H < 1 || Mv < 1) return fail(h, APV_ERR_ARG, "apv_eval_pressure: G, L, Pv, H and Mv must be at least 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    const apv_config& c = h->cfg;
+    const int x_f64 = c.frontend == 1 ? 0 : c.frontend == 2 ? 1 : c.compute_dtype == APV_F64;
+    const size_t esz = x_f64 ? 8 : 4;
+    EvalPressureArgs a{};
+    a.hist = d_y; a.hop = static_cast<const char*>(d_y) + (size_t)(Pv - 1) * L * esz;
+    a.hist_stride = a.hop_stride = ((size_t)Pv - 1 + H) * L;
+    a.sn = L; a.sl = 1;
+    a.rv[0] = d_rv; a.map = nullptr; a.p = d_p;
+    a.n_sets = G; a.Pv = Pv; a.H = H; a.L = L; a.Mv = Mv;
+    std::string why;
+    hipError_t e = apv_launch_eval_pressure(x_f64, a, h->stream, &why);
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
     return APV_OK;

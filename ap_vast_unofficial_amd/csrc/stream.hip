@@ -150,6 +150,19 @@ struct apv_stream {
     void* ck_taps[2];             // per zone program: [sig_chunk][nV][J][L], the taps of every hop of a chunk (ONE projection launch)
     void* ck_xrow[2][2];          // [chunk parity][signal]: [J - 1 samples before the chunk | sig_chunk H samples of the chunk], FIR synthesis
     hipEvent_t ck_wallfree;       // hop-by-hop regime: the tail stream has read ck_wall / ck_taps of a chunk for the last time
+    // evaluation stage (apv_stream_set_evaluation, kernels_streameval.hip); ev_on = 0: off, nothing below exists
+    int ev_on;
+    int ev_Pv, ev_Mv, ev_E, ev_Z; // response taps, validation microphones, evaluated ranks, zone programs that run
+    int ev_sets, ev_nhist;        // pressure sets ev_Z (2 ev_E + 1), evaluated groups ev_Z (ev_E + 1)
+    double* ev_rv[2];             // validation responses of zone A, zone B: [Pv][L][Mv]
+    int32_t* ev_map;              // [ev_sets][4]: {group of the result buffer, history slot, response bank, 0}
+    int32_t* ev_hsrc;             // [ev_nhist]: group of the result buffer each history slot follows
+    void* ev_hist[2];             // [buf][ev_nhist][Pv - 1][L]: the newest output samples; buf = cur, like fs_hist
+    double* ev_p;                 // [ev_sets][H][Mv]: the pressures of the last hop
+    double* ev_tot;               // [ev_Z][3 ev_E + 1][Mv]: the energies summed over the hops
+    double* ev_rec;               // [ev_cap] slots of that shape: the energies of each hop of the last call (grow-only)
+    unsigned long long* ev_ctl;   // device words {ev_rec, ev_cap, slot counter of parity 0, of parity 1}: see kernels_streameval.hip
+    int ev_cap, ev_nrec;          // slots ev_rec holds; hops of the last call (the slots that are valid)
     int32_t sched[2];             // state "signal_schedule": hops of the last whole-signal call {through chunk launches, hop by hop}
     hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
     double win_ms[2];             // ... and {sum of its times in ms, hops timed}
@@ -294,6 +307,11 @@ void apv_stream_free(apv_handle* h) {
         if (s->fs_ev[z]) (void)hipEventDestroy(s->fs_ev[z]);
     }
     if (s->win_ctr) (void)hipFree(s->win_ctr);
+    {
+        void* eb[] = {s->ev_rv[0], s->ev_rv[1], s->ev_map, s->ev_hsrc, s->ev_hist[0], s->ev_hist[1], s->ev_p, s->ev_tot, s->ev_rec, s->ev_ctl};
+        for (void* b : eb)
+            if (b) (void)hipFree(b);
+    }
     delete s;
     h->st = nullptr;
 }
@@ -425,6 +443,55 @@ static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin
         }
         for (int z = 0; z < 2; ++z) SCHK(h, apv_launch_scale_spectra(f64, K, M, 1, q.tspec[z], s->Wgt[z], st));
     }
+    return APV_OK;
+}
+
+// Evaluation stage of a hop on stream `st`, behind the synthesis that wrote the result buffer `obuf` and in front of its copy back:
+// the pressures of every set in one launch, then the energies, the record, the totals and the histories in a second.  After
+// enqueue_front: the histories alternate with s->cur, and so do the two slot counters.
+static int enqueue_eval(apv_handle* h, hipStream_t st, const void* obuf) {
+    apv_stream* s = h->st;
+    const int c = s->cur, H = s->H, L = s->L;
+    EvalPressureArgs a{};
+    a.hist = s->ev_hist[c ^ 1]; a.hop = obuf;
+    a.hist_stride = (size_t)(s->ev_Pv - 1) * L; a.hop_stride = (size_t)H * L;
+    a.sn = s->out_group > 0 ? L : 1;
+    a.sl = s->out_group > 0 ? 1 : H;
+    a.rv[0] = s->ev_rv[0]; a.rv[1] = s->ev_rv[1];
+    a.map = s->ev_map; a.p = s->ev_p;
+    a.n_sets = s->ev_sets; a.Pv = s->ev_Pv; a.H = H; a.L = L; a.Mv = s->ev_Mv;
+    std::string why;
+    hipError_t e = apv_launch_eval_pressure(s->f64, a, st, &why);
+    if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    EvalAdvanceArgs adv{};
+    adv.p = s->ev_p; adv.totals = s->ev_tot; adv.ctl = s->ev_ctl; adv.par = c;
+    adv.old_hist = s->ev_hist[c ^ 1]; adv.new_hist = s->ev_hist[c];
+    adv.hop = obuf; adv.hop_stride = a.hop_stride; adv.sn = a.sn; adv.sl = a.sl;
+    adv.hist_src = s->ev_hsrc;
+    adv.Z = s->ev_Z; adv.E = s->ev_E; adv.H = H; adv.Mv = s->ev_Mv; adv.Pv = s->ev_Pv; adv.L = L; adv.n_hist = s->ev_nhist;
+    SCHK(h, apv_launch_eval_advance(s->f64, adv, st));
+    return APV_OK;
+}
+
+// Start of a call of n_hops hops on an evaluated stream: the per-call record holds at least n_hops slots (grow-only), and the slot
+// counter the call's first hop reads -- that of the parity enqueue_front will flip to -- is zero.
+static int eval_begin_call(apv_handle* h, int n_hops) {
+    apv_stream* s = h->st;
+    hipStream_t st = h->stream;
+    if (n_hops > s->ev_cap) {
+        const size_t slot = sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->ev_Mv;
+        SCHK(h, hipStreamSynchronize(st));
+        double* rec = nullptr;
+        SCHK(h, hipMalloc((void**)&rec, slot * n_hops));
+        if (s->ev_rec) (void)hipFree(s->ev_rec);
+        s->ev_rec = rec;
+        s->ev_cap = n_hops;
+        const unsigned long long words[2] = {(unsigned long long)reinterpret_cast<uintptr_t>(rec), (unsigned long long)n_hops};
+        SCHK(h, hipMemcpyAsync(s->ev_ctl, words, sizeof(words), hipMemcpyHostToDevice, st));
+        SCHK(h, hipStreamSynchronize(st));                   // words goes out of scope
+    }
+    SCHK(h, hipMemsetAsync(s->ev_ctl + 2 + (s->cur ^ 1), 0, sizeof(unsigned long long), st));
+    s->ev_nrec = 0;
     return APV_OK;
 }
 
@@ -561,6 +628,8 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
         if (s->fs_ev[1]) SCHK(h, hipEventRecord(s->fs_ev[1], st));
         SCHK(h, apv_launch_fir_synth_advance(h->cfg.out_c128, f64, adv, st));
+        if (s->ev_on)
+            if (int rc = enqueue_eval(h, st, obuf)) return rc;
         if (sch.spectra_free) SCHK(h, hipEventRecord(sch.spectra_free, st));
         if (sch.no_copy) return APV_OK;
         SCHK(h, hipMemcpyAsync(pin_dst, obuf, hop_result_bytes(s), hipMemcpyDeviceToHost, st));     // samples + status: one copy
@@ -599,6 +668,8 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
         hipError_t e = apv_launch_synthesis(f64, N, H, s->n_out, ospec, K, 1, s->outov, obuf, ts, &why, s->out_group);
         if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
     }
+    if (s->ev_on)
+        if (int rc = enqueue_eval(h, ts, obuf)) return rc;
     if (sch.no_copy) return APV_OK;
     SCHK(h, hipMemcpyAsync(pin_dst, obuf, hop_result_bytes(s), hipMemcpyDeviceToHost, ts));         // samples + status: one copy
     if (sch.tail_stream) SCHK(h, hipEventRecord(sch.copied, ts));
@@ -747,8 +818,11 @@ static int process_block_t(apv_handle* h, const TI* h_in_A, const TI* h_in_B, TI
     if (!s) return apv_fail(h, APV_ERR_ARG, "apv_stream_init has not been called");
     SCHK(h, hipSetDevice(h->device));
     stage_hops(s, h_in_A, h_in_B, 0, 1, s->pin_in);
+    if (s->ev_on)
+        if (int rc = eval_begin_call(h, 1)) return rc;
     int rc = run_hop(h);
     if (rc != APV_OK) return rc;
+    if (s->ev_on) s->ev_nrec = 1;
     copy_hop_out(s, s->pin_out, 1, 0, h_out);
     return scan_hop_status(h, hop_status_of(s, s->pin_out), s->hop - 1);
 }
@@ -848,10 +922,13 @@ static int process_signal_hops_t(apv_handle* h, int n_hops, const TI* h_in_A, co
     SCHK(h, hipSetDevice(h->device));
     int worst = APV_OK;                                      // first APV_ERR_NO_CONVERGE: every hop still runs
     std::string worst_msg;
+    if (s->ev_on)
+        if (int rc = eval_begin_call(h, n_hops)) return rc;
     for (int i = 0; i < n_hops; ++i) {
         stage_hops(s, h_in_A, h_in_B, i, 1, s->pin_in);
         int rc = run_hop(h);
         if (rc != APV_OK) return rc;
+        if (s->ev_on) s->ev_nrec = i + 1;
         copy_hop_out(s, s->pin_out, n_hops, i, h_out);
         rc = scan_hop_status(h, hop_status_of(s, s->pin_out), s->hop - 1);
         if (rc == APV_ERR_NO_CONVERGE) {
@@ -876,11 +953,12 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     // constrained stream takes the chunked schedule or the plain hop loop: never the pipeline, which does not order the projections
     // of consecutive hops; and the hop loop when its projection or synthesis is timed (the switches promise un-captured per-hop
     // launches, tools/bench_filter_constraint.py and tools/bench_fir_synthesis.py read one time per hop).
-    const bool chunked = !explicit_stats(s) && s->fir_F > 0 && s->fir_np == 1 && !(s->taps > 0 && (s->cf_ev[0] || s->fs_ev[0]));
+    // An evaluated stream takes the hop loop too: its output histories and totals make consecutive hops sequential.
+    const bool chunked = !explicit_stats(s) && !s->ev_on && s->fir_F > 0 && s->fir_np == 1 && !(s->taps > 0 && (s->cf_ev[0] || s->fs_ev[0]));
     const long hop_before = s->hop;
     int rc;
     if (chunked) rc = process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
-    else if (explicit_stats(s) || s->taps > 0) rc = process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
+    else if (explicit_stats(s) || s->taps > 0 || s->ev_on) rc = process_signal_hops_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
     else rc = process_signal_pipelined_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
     s->sched[0] = chunked ? (int32_t)(s->hop - hop_before) : 0;
     s->sched[1] = chunked ? 0 : (int32_t)(s->hop - hop_before);
@@ -1500,6 +1578,13 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     }
     if (h->synthesis == APV_SYNTH_FIR && h->filter_taps < 1)
         return apv_fail(h, APV_ERR_ARG, "FIR synthesis (apv_stream_set_synthesis) needs the filter taps of apv_stream_set_filter_taps");
+    if (h->eval_Pv > 0) {
+        const int nzp = ((c.n_zones & 1) ? 1 : 0) + ((c.n_zones & 2) ? 1 : 0);
+        if ((long)nzp * (2 * (long)h->eval_ranks.size() + 1) > 65535)
+            return apv_fail(h, APV_ERR_ARG, "evaluation (apv_stream_set_evaluation): at most 65535 pressure sets");
+        if (h->eval_rv[0].size() != (size_t)h->eval_Pv * c.n_srcs * h->eval_Mv)
+            return apv_fail(h, APV_ERR_ARG, "evaluation (apv_stream_set_evaluation): the responses were sized for another n_srcs");
+    }
     SCHK(h, hipSetDevice(h->device));
     apv_stream_free(h);
     apv_stream* s = new apv_stream();
@@ -1655,6 +1740,50 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (getenv("APV_FIR_SYNTHESIS_TIMING") != nullptr)
             for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->fs_ev[i]));
     }
+    if (h->eval_Pv > 0) {
+        // evaluation stage: per zone program that runs, the pressure sets [bright of E ranks][dark of E ranks][target]; bright and
+        // target through the responses of the program's own zone, dark through the other zone's
+        const int Pv = h->eval_Pv, Mv = h->eval_Mv, E = (int)h->eval_ranks.size(), nfilt = nz * s->nV;
+        s->ev_on = 1; s->ev_Pv = Pv; s->ev_Mv = Mv; s->ev_E = E; s->ev_Z = nz;
+        s->ev_sets = nz * (2 * E + 1); s->ev_nhist = nz * (E + 1);
+        std::vector<int32_t> map((size_t)4 * s->ev_sets, 0), hsrc(s->ev_nhist, 0);
+        int zi = 0;
+        for (int z = 0; z < 2; ++z) {
+            if (!(s->zones & (1 << z))) continue;
+            for (int e = 0; e <= E; ++e) {
+                int grp = nfilt + z;                         // e = E: the program's target output A_t / B_t
+                if (e < E) {
+                    const auto it = std::find(h->rank_list.begin(), h->rank_list.end(), h->eval_ranks[e]);
+                    if (it == h->rank_list.end()) return apv_fail(h, APV_ERR_ARG, "evaluation: a rank that is not in the handle's rank list");
+                    grp = zi * s->nV + (int)(it - h->rank_list.begin());
+                }
+                const int hs = zi * (E + 1) + e;
+                hsrc[hs] = grp;
+                int32_t* mb = &map[(size_t)4 * (zi * (2 * E + 1) + (e < E ? e : 2 * E))];
+                mb[0] = grp; mb[1] = hs; mb[2] = z;
+                if (e < E) {
+                    int32_t* md = mb + 4 * E;
+                    md[0] = grp; md[1] = hs; md[2] = z ^ 1;
+                }
+            }
+            ++zi;
+        }
+        for (int z = 0; z < 2; ++z) {
+            if ((rc = dalloc(h, &s->ev_rv[z], h->eval_rv[z].size()))) return rc;
+            SCHK(h, hipMemcpyAsync(s->ev_rv[z], h->eval_rv[z].data(), sizeof(double) * h->eval_rv[z].size(), hipMemcpyHostToDevice, h->stream));
+        }
+        if ((rc = dalloc(h, &s->ev_map, map.size()))) return rc;
+        if ((rc = dalloc(h, &s->ev_hsrc, hsrc.size()))) return rc;
+        SCHK(h, hipMemcpyAsync(s->ev_map, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, h->stream));
+        SCHK(h, hipMemcpyAsync(s->ev_hsrc, hsrc.data(), sizeof(int32_t) * hsrc.size(), hipMemcpyHostToDevice, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));            // map, hsrc go out of scope
+        for (int b = 0; b < 2; ++b)
+            if ((rc = dalloc(h, &s->ev_hist[b], (size_t)s->ev_nhist * (Pv - 1) * L, e1))) return rc;
+        if ((rc = dalloc(h, &s->ev_p, (size_t)s->ev_sets * H * Mv))) return rc;
+        if ((rc = dalloc(h, &s->ev_tot, (size_t)nz * (3 * E + 1) * Mv))) return rc;
+        if ((rc = dalloc(h, &s->ev_ctl, 4))) return rc;
+        SCHK(h, apv_eval_pressure_prepare(f64, Pv, H, L));
+    }
     // target filter spectra: rfft of a unit impulse at tap modeling_delay of the A reference loudspeaker
     // (apvast.py:389-390, 418, 422: the same filter serves A_t and B_t)
     std::vector<double> tg((size_t)L * K * 2, 0.0);
@@ -1719,6 +1848,40 @@ int apv_stream_set_synthesis(apv_handle* h, int32_t mode) {
     if (mode != APV_SYNTH_WOLA && mode != APV_SYNTH_FIR)
         return apv_fail(h, APV_ERR_ARG, "synthesis: APV_SYNTH_WOLA (0) or APV_SYNTH_FIR (1)");
     h->synthesis = mode;
+    return APV_OK;
+}
+
+int apv_stream_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
+                              const int32_t* ranks) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_evaluation: the stream is initialised (its buffers are allocated there)");
+    if (!h_rvA || !h_rvB || !ranks) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_evaluation: null argument");
+    if (Pv < 1 || Mv < 1 || Mv > 16 * 65535) return apv_fail(h, APV_ERR_ARG, "evaluation: Pv and Mv must be at least 1 (Mv at most 1048560)");
+    if (!apv_eval_pressure_fits(Pv))
+        return apv_fail(h, APV_ERR_ARG, "evaluation: one loudspeaker's window of Pv - 1 + 16 float64 samples does not fit 160 KB of LDS (Pv <= 20465)");
+    if (n_ranks < 1 || (size_t)n_ranks > h->rank_list.size()) return apv_fail(h, APV_ERR_ARG, "evaluation: between 1 and the handle's number of ranks");
+    for (int i = 0; i < n_ranks; ++i) {
+        if (i && ranks[i] <= ranks[i - 1]) return apv_fail(h, APV_ERR_ARG, "evaluation: the ranks must be strictly ascending");
+        if (std::find(h->rank_list.begin(), h->rank_list.end(), ranks[i]) == h->rank_list.end())
+            return apv_fail(h, APV_ERR_ARG, "evaluation: a rank that is not in the handle's rank list");
+    }
+    const size_t n = (size_t)Pv * h->cfg.n_srcs * Mv;
+    h->eval_rv[0].assign(h_rvA, h_rvA + n);
+    h->eval_rv[1].assign(h_rvB, h_rvB + n);
+    h->eval_ranks.assign(ranks, ranks + n_ranks);
+    h->eval_Pv = Pv;
+    h->eval_Mv = Mv;
+    return APV_OK;
+}
+
+int apv_stream_reset_evaluation(apv_handle* h) {
+    if (!h || !h->st || !h->st->ev_on) return apv_fail(h, APV_ERR_ARG, "apv_stream_reset_evaluation: no stream with an evaluation stage");
+    apv_stream* s = h->st;
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipMemsetAsync(s->ev_tot, 0, sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->ev_Mv, h->stream));
+    const size_t hb = (size_t)s->ev_nhist * (s->ev_Pv - 1) * s->L * s->esz;
+    for (int b = 0; b < 2 && hb > 0; ++b) SCHK(h, hipMemsetAsync(s->ev_hist[b], 0, hb, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
     return APV_OK;
 }
 
@@ -1951,6 +2114,9 @@ int apv_set_mu(apv_handle* h, double mu) {
 //   "fir_synth_taps_A" / "fir_synth_taps_B" [nV][J][L] f32|f64 (cfg.out_c128)   the taps the next hop's FIR synthesis fades from;
 //   "fir_synth_history<g>" [J-1]   the newest samples of input signal g; both only with apv_stream_set_synthesis(h, APV_SYNTH_FIR)
 //   "fir_synthesis_kernel_ms" {sum, count} of the timed synthesis launches (APV_FIR_SYNTHESIS_TIMING), read-only
+//   "eval_pressure" [sets][H][Mv] f64, "eval_hops" [hops of the last call][Z][3 E + 1][Mv] f64 (both read-only), "eval_totals"
+//                                  [Z][3 E + 1][Mv] f64, "eval_history" [Z (E + 1)][Pv - 1][L] samples: only a stream with
+//                                  apv_stream_set_evaluation has them (see include/apvast_hip.h)
 //   "signal_schedule" int32 {hops of the last apv_process_signal* call that went through chunk launches, hops of it that went hop by
 //                                  hop}, read-only; {0, 0} before the first such call, untouched by the per-hop calls
 static int live_index(const char* name) {
@@ -2063,6 +2229,13 @@ static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* by
         *dptr = s->fs_taps[n.back() == 'B']; *bytes = (size_t)s->nV * s->taps * L * lsz(h); return APV_OK; }
     if ((n == "fir_synth_history0" || n == "fir_synth_history1") && s->fir_synth) {
         *dptr = s->fs_hist[s->cur][n.back() - '0']; *bytes = (size_t)(s->taps - 1) * e1; return APV_OK; }
+    if (s->ev_on) {
+        const size_t slot = sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->ev_Mv;
+        if (n == "eval_pressure") { *dptr = s->ev_p; *bytes = sizeof(double) * (size_t)s->ev_sets * s->H * s->ev_Mv; return APV_OK; }
+        if (n == "eval_hops") { *dptr = s->ev_rec; *bytes = slot * (size_t)s->ev_nrec; return APV_OK; }
+        if (n == "eval_totals") { *dptr = s->ev_tot; *bytes = slot; return APV_OK; }
+        if (n == "eval_history") { *dptr = s->ev_hist[s->cur]; *bytes = (size_t)s->ev_nhist * (s->ev_Pv - 1) * L * e1; return APV_OK; }
+    }
     return apv_fail(h, APV_ERR_STATE, std::string("unknown state name: ") + name);
 }
 
@@ -2121,6 +2294,7 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;
     if (bytes != need) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+    if (need == 0) return APV_OK;                            // "eval_history" with Pv = 1, "eval_hops" before the first hop
     SCHK(h, hipSetDevice(h->device));
     if (rr == 0) {
         SCHK(h, hipMemcpyAsync(h_dst, d, need, hipMemcpyDeviceToHost, h->stream));
@@ -2165,10 +2339,13 @@ int apv_set_state(apv_handle* h, const char* name, const void* h_src, size_t byt
     }
     if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), const_cast<void*>(h_src), bytes, false);
     if (std::string(name) == "signal_schedule") return apv_fail(h, APV_ERR_STATE, "signal_schedule is read-only");
+    if (h->st->ev_on && (std::string(name) == "eval_pressure" || std::string(name) == "eval_hops"))
+        return apv_fail(h, APV_ERR_STATE, std::string(name) + " is read-only");
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;
     if (bytes != need) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+    if (need == 0) return APV_OK;
     SCHK(h, hipSetDevice(h->device));
     if (rr < 0) return apv_fail(h, APV_ERR_STATE, "the control-point spectra are recomputed by every hop and cannot be set");
     if (rr == 0) {

@@ -2,6 +2,7 @@
 
   predict_pressure   Matlab/ControlMethods/predictPressure.m:1-17
   nmse, acoustic_contrast_db   Matlab/main.m:120-130
+  metrics            the same two from the energies a subband stream's evaluation stage accumulates on the device
   vast               Matlab/ControlMethods/vast.m:1-97 (signal-independent VAST from the RIRs)
 
 MATLAB/Octave are not available where this was built, so these follow the .m files by reading only
@@ -36,6 +37,19 @@ def nmse(target_pressure, pressure):
 def acoustic_contrast_db(pressure_bright, pressure_dark):
     """10 log10(||p_bright||_F^2 / ||p_dark||_F^2) (main.m:129-130)."""
     return float(10.0 * np.log10(np.sum(np.asarray(pressure_bright) ** 2) / np.sum(np.asarray(pressure_dark) ** 2)))
+
+
+def metrics(totals):
+    """NMSE and acoustic contrast from accumulated energies (main.m:120-130): ``totals`` as apvast.evaluation_totals() returns
+    them (or a slot of evaluation_hops()): "bright", "dark", "error" (Z, E, Mv) and "target" (Z, Mv) ->
+    {"nmse": (Z, E), "contrast_db": (Z, E)} with nmse[z, v] = mean_m error[z, v, m] / target[z, m] and
+    contrast_db[z, v] = 10 log10(sum_m bright[z, v, m] / sum_m dark[z, v, m])."""
+    bright = np.asarray(totals["bright"], dtype=np.float64)
+    dark = np.asarray(totals["dark"], dtype=np.float64)
+    error = np.asarray(totals["error"], dtype=np.float64)
+    target = np.asarray(totals["target"], dtype=np.float64)
+    return {"nmse": np.mean(error / target[..., None, :], axis=-1),
+            "contrast_db": 10.0 * np.log10(np.sum(bright, axis=-1) / np.sum(dark, axis=-1))}
 
 
 def vast(gB, gD, filter_length, modelling_delay, reference_index, number_of_eigenvectors, mu, device=0):

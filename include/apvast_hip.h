@@ -201,6 +201,44 @@ int  apv_stream_set_synthesis(apv_handle* h, int32_t mode);
 int  apv_fir_synthesis(apv_handle* h, const void* d_x, const void* d_taps_prev, const void* d_taps_cur, int32_t nV, int32_t L,
                        int32_t J, int32_t H, void* d_out);
 
+/* Evaluation stage of the subband stream (off unless this is called): behind the synthesis of every hop, and in front of the copy
+ * back, the device filters the hop's own drive signals through the responses to validation microphones, keeps the pressures of
+ * the last hop, reduces them to energies per microphone and accumulates those (csrc/kernels_streameval.hip; two launches per hop,
+ * part of the captured hop graphs).  h_rvA / h_rvB: float64 [Pv][L][Mv], L = cfg.n_srcs, the responses to the validation
+ * microphones of zone A / zone B.  ranks: n_ranks rank values, strictly ascending, each in the handle's rank list: the evaluated
+ * ranks, E of them.  Z = zone programs that run (cfg.n_zones), A first; "own" zone of program A is A.  Per absolute sample n, with
+ * y zero before the first hop (lfilter with zero zi) and y_t the program's target output (A_t for program A, B_t for B):
+ *   p_bright[z, v][n, m] = sum_l sum_{j < Pv} rv_own(z)  [j, l, m] y[z, v][n - j, l]
+ *   p_dark  [z, v][n, m] = sum_l sum_{j < Pv} rv_other(z)[j, l, m] y[z, v][n - j, l]
+ *   p_target[z][n, m]    = sum_l sum_{j < Pv} rv_own(z)  [j, l, m] y_t[z][n - j, l]
+ * and per hop and microphone, summed over the hop's H samples in ascending order,
+ *   bright = sum p_bright^2, dark = sum p_dark^2, error = sum (p_target - p_bright)^2, target = sum p_target^2.
+ * All of it in float64 whatever the stream's precision (float32 samples are widened).  States only such a stream has
+ * (apv_get_state / apv_set_state):
+ *   "eval_pressure" f64 [Z][2 E + 1][H][Mv]: per program [bright of the E ranks][dark of the E ranks][target], last hop; read-only
+ *   "eval_hops"     f64 [n][Z][3 E + 1][Mv]: per hop of the last apv_process_* call (n of them; apv_state_bytes tells) and program
+ *                   [bright of the E ranks][dark ...][error ...][target]; read-only
+ *   "eval_totals"   f64 [Z][3 E + 1][Mv]: the same summed over every hop since apv_stream_init or apv_stream_reset_evaluation,
+ *                   total = total + hop, one addition per hop
+ *   "eval_history"  [Z][E + 1][Pv - 1][L] in the sample precision: the newest Pv - 1 output samples of every evaluated group
+ *                   (the E ranks, then the target), oldest first
+ * apv_process_signal* on such a stream runs its hops one after the other through the per-hop path ("signal_schedule" {0, n}).
+ * Called between apv_create and apv_stream_init.  APV_ERR_ARG (nothing changed) once the stream is initialised, for null pointers,
+ * Pv < 1, Mv < 1, n_ranks outside 1..the handle's ranks, ranks not strictly ascending or not in the rank list, or Pv > 20465: one
+ * loudspeaker's window of Pv - 1 + 16 float64 samples has to fit the 160 KB of LDS of a compute unit.  Mv up to 1048560.
+ *                                                         replaces: Matlab/main.m:64-76, 120-130 with predictPressure.m:12-16 */
+int  apv_stream_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
+                               const int32_t* ranks);
+/* "eval_totals" and both "eval_history" buffers to zero: the next hop's totals equal its own energies.  APV_ERR_ARG without such
+ * a stream. */
+int  apv_stream_reset_evaluation(apv_handle* h);
+/* The pressure kernel alone, on the handle's stream: d_y [G][Pv - 1 + H][L] samples (per group the Pv - 1 in front of the hop,
+ * then the hop; float64 with a float64 front-end, else float32), d_rv [Pv][L][Mv] float64, d_p [G][H][Mv] float64:
+ * p[g][n, m] = sum_l sum_j rv[j, l, m] y[g][Pv - 1 + n - j, l].  APV_ERR_ARG for a size below 1, null pointers, G > 65535 or
+ * Pv > 20465.                                             replaces: Matlab/predictPressure.m:12-16 */
+int  apv_eval_pressure(apv_handle* h, const void* d_y, const double* d_rv, int32_t G, int32_t L, int32_t Pv, int32_t H, int32_t Mv,
+                       double* d_p);
+
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
 int  apv_dev_free(apv_handle* h, void* d_ptr);
