@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -153,6 +153,8 @@ def load():
     lib.apv_stream_set_evaluation.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     lib.apv_stream_reset_evaluation.argtypes = [vp]
     lib.apv_eval_pressure.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.apv_stream_set_evaluation_spectra.argtypes = [vp, i32]
+    lib.apv_eval_spectrum_step.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -226,7 +228,8 @@ class Engine:
     def __init__(self, n_bins, n_srcs, n_mics, ranks=(1,), mu=1.0, compute_dtype="f64", out_c128=None,
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
-                 out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola", evaluation=None):
+                 out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola", evaluation=None,
+                 evaluation_spectra=False):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -285,6 +288,37 @@ class Engine:
         self.evaluation = None
         if evaluation is not None:
             self.set_evaluation(*evaluation)
+        self.evaluation_spectra = False
+        if evaluation_spectra:
+            self.set_evaluation_spectra(True)
+
+    def set_evaluation_spectra(self, on):
+        """Per-bin spectra of the evaluation stage, before stream_init (apv_stream_set_evaluation_spectra); needs set_evaluation."""
+        self._chk(self.lib.apv_stream_set_evaluation_spectra(self.h, int(bool(on))))
+        self.evaluation_spectra = bool(on)
+
+    def eval_spectrum_step(self, pressure, ring, ring_off, totals, Z, E):
+        """One step of the per-bin spectra alone (apv_eval_spectrum_step): pressure (Z (2 E + 1), H, Mv) float64 into ring
+        (Z (2 E + 1), Mv, N) as stored -- logical sample n at (n + ring_off) mod N, the hop in the last H logical samples; advance
+        ring_off by H mod N before each call -- then |rfft(window * frame)|^2 added to totals (Z, 3 E + 1, N/2 + 1, Mv).  Returns
+        the new (ring, totals)."""
+        pressure = np.ascontiguousarray(pressure, dtype=np.float64)
+        ring = np.ascontiguousarray(ring, dtype=np.float64)
+        totals = np.ascontiguousarray(totals, dtype=np.float64)
+        Z, E = int(Z), int(E)
+        if pressure.ndim != 3 or ring.ndim != 3:
+            raise ValueError("pressure must be (Z (2 E + 1), H, Mv) and ring (Z (2 E + 1), Mv, N)")
+        sets, H, Mv = pressure.shape
+        N = ring.shape[2]
+        if sets != Z * (2 * E + 1) or ring.shape != (sets, Mv, N) or totals.shape != (Z, 3 * E + 1, N // 2 + 1, Mv):
+            raise ValueError("pressure (Z (2 E + 1), H, Mv), ring (Z (2 E + 1), Mv, N) and totals (Z, 3 E + 1, N/2 + 1, Mv) do not agree")
+        dp, dr, dt = self.to_device(pressure), self.to_device(ring), self.to_device(totals)
+        try:
+            self._chk(self.lib.apv_eval_spectrum_step(self.h, dp.ptr, dr.ptr, int(ring_off), N, H, Z, E, Mv, dt.ptr))
+            return dr.download(ring.shape, np.float64), dt.download(totals.shape, np.float64)
+        finally:
+            for b in (dp, dr, dt):
+                b.free()
 
     def set_evaluation(self, rv_A, rv_B, ranks):
         """Evaluation stage of the subband stream, before stream_init (apv_stream_set_evaluation): rv_A / rv_B (Pv, L, Mv) float64,

@@ -63,6 +63,14 @@ What is different (keyword-only, after ``perceptual``)
     totals and histories, ``evaluation.metrics(totals)`` gives NMSE and contrast in dB (main.m:120-130); get_state() gains
     ``evaluation_history`` (Z, E + 1, Pv - 1, L) and ``evaluation_totals`` (Z, 3 E + 1, Mv).  Outputs, filters and every other state
     are those of the same stream without the keywords, bit for bit; process_signal runs such a stream hop by hop.
+  * ``evaluation_spectra=True`` (a bool; needs the validation responses): the evaluation stage also keeps the last block_size
+    pressure samples per set and microphone and, after every hop t, transforms the frame that ends with the hop under the analysis
+    window, P_t = rfft(window * p[(t + 1) H - N : (t + 1) H]) (zero before sample 0, unnormalised), and accumulates per bin
+    bright += |P_own|^2, dark += |P_other|^2, error += |P_target - P_own|^2, target += |P_target|^2 in float64.
+    ``evaluation_spectra()`` fetches them -- "bright", "dark", "error" (Z, E, Mv, K), "target" (Z, Mv, K) --
+    ``evaluation.spectral_metrics`` gives contrast and NMSE per bin or band, ``reset_evaluation()`` zeroes them too, and
+    get_state() gains ``evaluation_spectra`` (Z, 3 E + 1, K, Mv) and ``evaluation_ring`` (Z, 2 E + 1, Mv, N).  Everything else the
+    stream computes is unchanged, bit for bit.  Block sizes up to 4096.
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).
@@ -160,6 +168,7 @@ class apvast:
                  validation_rir_A=None,
                  validation_rir_B=None,
                  evaluation_ranks=None,
+                 evaluation_spectra=False,
                  statistics_forgetting=None,
                  statistics_hops=1):
         self.block_size = block_size
@@ -203,6 +212,7 @@ class apvast:
         self.rir_length, self.number_of_srcs, self.number_of_mics = rir_A.shape  # apvast.py:97-99
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
         self._evaluation = self._check_evaluation(validation_rir_A, validation_rir_B, evaluation_ranks, L, number_of_eigenvectors, mode)
+        self._evaluation_spectra = self._check_evaluation_spectra(evaluation_spectra, self._evaluation, mode)
         self._init_responses(rir_A, rir_B)
         if mode == "broadband":
             self._init_broadband(device, seed)
@@ -226,7 +236,8 @@ class apvast:
                                  out_layout=1,     # the device emits (hop, loudspeaker) arrays: nothing to transpose here
                                  stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting,
                                  filter_taps=int(filter_length) if self.constrain_filter_length else 0,
-                                 synthesis=self.synthesis, evaluation=self._evaluation)
+                                 synthesis=self.synthesis, evaluation=self._evaluation,
+                                 evaluation_spectra=self._evaluation_spectra)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -346,6 +357,19 @@ class apvast:
             r = [int(v) for v in r]
         return a, b, r
 
+    @staticmethod
+    def _check_evaluation_spectra(value, evaluation, mode):
+        """evaluation_spectra as a bool; True needs subband mode and the evaluation stage."""
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError("evaluation_spectra must be a bool")
+        if not value:
+            return False
+        if mode == "broadband":
+            raise ValueError("evaluation_spectra is a subband keyword: broadband mode has no evaluation stage")
+        if evaluation is None:
+            raise ValueError("evaluation_spectra needs validation_rir_A and validation_rir_B")
+        return True
+
     # ---- the evaluation stage (validation_rir_A / validation_rir_B): read from the device when asked for ------------------
     def _eval_dims(self):
         if self.__dict__.get("_evaluation") is None:
@@ -388,8 +412,24 @@ class apvast:
         return {"bright": np.ascontiguousarray(p[:, :E]), "dark": np.ascontiguousarray(p[:, E:2 * E]),
                 "target": np.ascontiguousarray(p[:, 2 * E])}
 
+    def evaluation_spectra(self):
+        """The per-bin energies summed over every hop since construction, set_state or reset_evaluation(): "bright", "dark",
+        "error" (Z, E, Mv, K) and "target" (Z, Mv, K), K = block_size / 2 + 1; evaluation.spectral_metrics() turns them into
+        contrast and NMSE per bin or band.  None before the first hop."""
+        Z, E, _, Mv = self._eval_dims()
+        if not self.__dict__.get("_evaluation_spectra"):
+            raise RuntimeError("this object keeps no evaluation spectra: pass evaluation_spectra=True")
+        if self._hops == 0:
+            return None
+        # the device accumulates bins before microphones (neighbouring threads along the microphones)
+        t = self._eng.get_state("eval_spectra", (Z, 3 * E + 1, self._K, Mv), np.float64)
+        t = t.transpose(0, 1, 3, 2)
+        return {"bright": np.ascontiguousarray(t[:, :E]), "dark": np.ascontiguousarray(t[:, E:2 * E]),
+                "error": np.ascontiguousarray(t[:, 2 * E:3 * E]), "target": np.ascontiguousarray(t[:, 3 * E])}
+
     def reset_evaluation(self):
-        """Totals to zero and the output histories to silence: the next hop's totals are its own energies."""
+        """Totals to zero and the output histories to silence: the next hop's totals are its own energies.  With
+        evaluation_spectra=True the per-bin energies and the pressure ring too."""
         self._eval_dims()
         self._eng.reset_evaluation()
 
@@ -759,6 +799,7 @@ class apvast:
     _FORGET_STATE = ("statistics_forgetting_sums",)                  # present with statistics_forgetting set
     _FIR_STATE = ("fir_synthesis_taps", "fir_synthesis_history")    # present with synthesis="fir"
     _EVAL_STATE = ("evaluation_history", "evaluation_totals")       # present with validation_rir_A / validation_rir_B
+    _EVALSPEC_STATE = ("evaluation_spectra", "evaluation_ring")     # present with evaluation_spectra=True
 
     def get_state(self):
         """Everything the next hop depends on (the reference's instance attributes of apvast.py:115-151), as float64 arrays
@@ -798,6 +839,11 @@ class apvast:
             st["evaluation_history"] = (e.get_state("eval_history", (Z, E + 1, Pv - 1, L), e.s_dtype) if Pv > 1
                                         else np.zeros((Z, E + 1, 0, L))).astype(np.float64)
             st["evaluation_totals"] = e.get_state("eval_totals", (Z, 3 * E + 1, Mv), np.float64)
+        if self.mode == "subband" and self._evaluation_spectra:
+            # the per-bin energies as the device keeps them and the last N pressure samples of every set, oldest first
+            Z, E, _, Mv = self._eval_dims()
+            st["evaluation_spectra"] = self._eng.get_state("eval_spectra", (Z, 3 * E + 1, self._K, Mv), np.float64)
+            st["evaluation_ring"] = self._eng.get_state("eval_ring", (Z, 2 * E + 1, Mv, self.block_size), np.float64)
         if self._live_applied:
             P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
             Q = max(P - 1, 1)
@@ -850,6 +896,8 @@ class apvast:
             known = known + self._FIR_STATE
         if self.mode == "subband" and self._evaluation is not None:
             known = known + self._EVAL_STATE
+        if self.mode == "subband" and self._evaluation_spectra:
+            known = known + self._EVALSPEC_STATE
         unknown = sorted(set(state) - set(known))
         if unknown:
             raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
@@ -899,6 +947,16 @@ class apvast:
                 if tot.shape != (Z, 3 * E + 1, Mv):
                     raise ValueError(f"evaluation_totals must have shape {(Z, 3 * E + 1, Mv)}, got {tot.shape}")
                 e.set_state("eval_totals", np.ascontiguousarray(tot, dtype=np.float64))
+        if "evaluation_spectra" in state or "evaluation_ring" in state:
+            Z, E, _, Mv = self._eval_dims()
+            shapes = {"evaluation_spectra": ("eval_spectra", (Z, 3 * E + 1, self._K, Mv)),
+                      "evaluation_ring": ("eval_ring", (Z, 2 * E + 1, Mv, self.block_size))}
+            for key, (name, shape) in shapes.items():
+                if key in state:
+                    a = np.asarray(state[key])
+                    if a.shape != shape:
+                        raise ValueError(f"{key} must have shape {shape}, got {a.shape}")
+                    e.set_state(name, np.ascontiguousarray(a, dtype=np.float64))
         if "statistics_window_fill" in state:
             e.set_state("stat_window_fill", np.array([int(state["statistics_window_fill"])], dtype=np.int32))
         if any(k in state for k in self._LIVE_STATE):

@@ -94,6 +94,7 @@ struct apv_handle {
     int eval_Pv, eval_Mv;
     std::vector<double> eval_rv[2];  // validation responses of zone A, zone B: [Pv][L][Mv]
     std::vector<int32_t> eval_ranks; // evaluated ranks, ascending, each in rank_list
+    int eval_spectra;                // apv_stream_set_evaluation_spectra: per-bin spectra of the evaluation stage (0: off)
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -352,6 +353,21 @@ struct EvalAdvanceArgs {
     int Z, E, H, Mv, Pv, L, n_hist;
 };
 hipError_t apv_launch_eval_advance(int x_f64, const EvalAdvanceArgs& a, hipStream_t s);
+
+// kernels_evalspec.hip: per-bin evaluation spectra (see the file header).  Three launches behind the two above: the hop's
+// pressures p [Z (2 E + 1)][H][Mv] into the ring [Z (2 E + 1) Mv][N] at the stream's ring offset (the offset AFTER the hop's
+// advance, as K1 and the analysis take it), the windowed float64 transform of every ring row into spec [N/2 + 1][Z (2 E + 1) Mv]
+// complex128, and |P|^2 added to totals [Z][3 E + 1][N/2 + 1][Mv].  The float64 tables of N must exist when it is captured
+// (apv_stft_prepare(N, 1)).
+struct EvalSpectraArgs {
+    const double* p;
+    double* ring;
+    void* spec;
+    double* totals;
+    int ring_off, N, H, Z, E, Mv;
+};
+bool apv_eval_spectra_size_ok(int N, int H, int Z, int E, int Mv, std::string* why);
+hipError_t apv_launch_eval_spectra(const EvalSpectraArgs& a, hipStream_t s, std::string* why);
 
 // whole-signal path, a chunk of hops per launch (kernels_stft.hip / kernels_stream.hip; see process_signal_chunked_t in stream.hip)
 hipError_t apv_launch_stft_analysis_chunk(int f64, int N, int n_jobs, const void* const* x, const int* n_ch, void* const* spec,

@@ -233,6 +233,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     h->filter_taps = 0;
     h->synthesis = APV_SYNTH_WOLA;
     h->eval_Pv = h->eval_Mv = 0;
+    h->eval_spectra = 0;
     h->gl_ws = nullptr;
     h->gl_tol2 = 0.0;
     h->gl_lead_rank = 0;
@@ -912,6 +913,32 @@ int apv_eval_pressure(apv_handle* h, const void* d_y, const double* d_rv, int32_
     a.n_sets = G; a.Pv = Pv; a.H = H; a.L = L; a.Mv = Mv;
     std::string why;
     hipError_t e = apv_launch_eval_pressure(x_f64, a, h->stream, &why);
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
+int apv_eval_spectrum_step(apv_handle* h, const double* d_pressure, double* d_ring, int32_t ring_off, int32_t N, int32_t H, int32_t Z,
+                           int32_t E, int32_t Mv, double* d_totals) {
+    if (!h || !d_pressure || !d_ring || !d_totals) return fail(h, APV_ERR_ARG, "null device pointer");
+    if (N < 1 || H < 1 || Z < 1 || E < 1 || Mv < 1) return fail(h, APV_ERR_ARG, "apv_eval_spectrum_step: N, H, Z, E and Mv must be at least 1");
+    if ((N & 1) || N > 4096) return fail(h, APV_ERR_ARG, "apv_eval_spectrum_step: N must be even and at most 4096 (float64 transforms)");
+    if (ring_off < 0 || ring_off >= N) return fail(h, APV_ERR_ARG, "apv_eval_spectrum_step: ring_off must be in 0..N - 1");
+    std::string why;
+    if (!apv_eval_spectra_size_ok(N, H, Z, E, Mv, &why)) return fail(h, APV_ERR_ARG, why);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    HIPCHK(h, apv_stft_prepare(N, 1));
+    // the bin-major scratch of the transform is this call's own: a test entry, not a per-hop path
+    void* spec = nullptr;
+    HIPCHK(h, hipMalloc(&spec, sizeof(double) * 2 * ((size_t)N / 2 + 1) * Z * (2 * (size_t)E + 1) * Mv));
+    EvalSpectraArgs a{};
+    a.p = d_pressure; a.ring = d_ring; a.spec = spec; a.totals = d_totals;
+    a.ring_off = ring_off; a.N = N; a.H = H; a.Z = Z; a.E = E; a.Mv = Mv;
+    hipError_t e = apv_launch_eval_spectra(a, h->stream, &why);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    (void)hipFree(spec);
+    if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
     return APV_OK;

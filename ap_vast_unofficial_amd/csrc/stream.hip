@@ -163,6 +163,11 @@ struct apv_stream {
     double* ev_rec;               // [ev_cap] slots of that shape: the energies of each hop of the last call (grow-only)
     unsigned long long* ev_ctl;   // device words {ev_rec, ev_cap, slot counter of parity 0, of parity 1}: see kernels_streameval.hip
     int ev_cap, ev_nrec;          // slots ev_rec holds; hops of the last call (the slots that are valid)
+    // per-bin evaluation spectra (apv_stream_set_evaluation_spectra, kernels_evalspec.hip); es_on = 0: off, nothing below exists
+    int es_on;
+    double* es_ring;              // [ev_sets ev_Mv][N] float64 ring of the pressures, channel-major, at the stream's ring_off
+    void* es_spec;                // [K][ev_sets ev_Mv] complex128: the hop's spectra, bin-major scratch
+    double* es_tot;               // [ev_Z][3 ev_E + 1][K][ev_Mv]: |P|^2 summed over the hops
     int32_t sched[2];             // state "signal_schedule": hops of the last whole-signal call {through chunk launches, hop by hop}
     hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
     double win_ms[2];             // ... and {sum of its times in ms, hops timed}
@@ -308,7 +313,8 @@ void apv_stream_free(apv_handle* h) {
     }
     if (s->win_ctr) (void)hipFree(s->win_ctr);
     {
-        void* eb[] = {s->ev_rv[0], s->ev_rv[1], s->ev_map, s->ev_hsrc, s->ev_hist[0], s->ev_hist[1], s->ev_p, s->ev_tot, s->ev_rec, s->ev_ctl};
+        void* eb[] = {s->ev_rv[0], s->ev_rv[1], s->ev_map, s->ev_hsrc, s->ev_hist[0], s->ev_hist[1], s->ev_p, s->ev_tot, s->ev_rec, s->ev_ctl,
+                      s->es_ring, s->es_spec, s->es_tot};
         for (void* b : eb)
             if (b) (void)hipFree(b);
     }
@@ -448,7 +454,9 @@ static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin
 
 // Evaluation stage of a hop on stream `st`, behind the synthesis that wrote the result buffer `obuf` and in front of its copy back:
 // the pressures of every set in one launch, then the energies, the record, the totals and the histories in a second.  After
-// enqueue_front: the histories alternate with s->cur, and so do the two slot counters.
+// enqueue_front: the histories alternate with s->cur, and so do the two slot counters.  With the per-bin spectra on, three more
+// launches behind them (kernels_evalspec.hip): they read s->ring_off as enqueue_front left it, like K1 and the analysis, so the
+// period of the captured graphs is unchanged.
 static int enqueue_eval(apv_handle* h, hipStream_t st, const void* obuf) {
     apv_stream* s = h->st;
     const int c = s->cur, H = s->H, L = s->L;
@@ -470,6 +478,13 @@ static int enqueue_eval(apv_handle* h, hipStream_t st, const void* obuf) {
     adv.hist_src = s->ev_hsrc;
     adv.Z = s->ev_Z; adv.E = s->ev_E; adv.H = H; adv.Mv = s->ev_Mv; adv.Pv = s->ev_Pv; adv.L = L; adv.n_hist = s->ev_nhist;
     SCHK(h, apv_launch_eval_advance(s->f64, adv, st));
+    if (s->es_on) {
+        EvalSpectraArgs sp{};
+        sp.p = s->ev_p; sp.ring = s->es_ring; sp.spec = s->es_spec; sp.totals = s->es_tot;
+        sp.ring_off = s->ring_off; sp.N = s->N; sp.H = H; sp.Z = s->ev_Z; sp.E = s->ev_E; sp.Mv = s->ev_Mv;
+        e = apv_launch_eval_spectra(sp, st, &why);
+        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    }
     return APV_OK;
 }
 
@@ -1585,6 +1600,16 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (h->eval_rv[0].size() != (size_t)h->eval_Pv * c.n_srcs * h->eval_Mv)
             return apv_fail(h, APV_ERR_ARG, "evaluation (apv_stream_set_evaluation): the responses were sized for another n_srcs");
     }
+    if (h->eval_spectra) {
+        if (h->eval_Pv <= 0)
+            return apv_fail(h, APV_ERR_ARG, "evaluation spectra (apv_stream_set_evaluation_spectra) need the evaluation stage of apv_stream_set_evaluation");
+        if (N > 4096)
+            return apv_fail(h, APV_ERR_ARG, "evaluation spectra (apv_stream_set_evaluation_spectra): block_size <= 4096 (the spectra are float64 "
+                                            "whatever the stream's precision, and the double-precision FFT in LDS stops there)");
+        const int nzp = ((c.n_zones & 1) ? 1 : 0) + ((c.n_zones & 2) ? 1 : 0);
+        std::string why;
+        if (!apv_eval_spectra_size_ok(N, H, nzp, (int)h->eval_ranks.size(), h->eval_Mv, &why)) return apv_fail(h, APV_ERR_ARG, why);
+    }
     SCHK(h, hipSetDevice(h->device));
     apv_stream_free(h);
     apv_stream* s = new apv_stream();
@@ -1783,6 +1808,13 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if ((rc = dalloc(h, &s->ev_tot, (size_t)nz * (3 * E + 1) * Mv))) return rc;
         if ((rc = dalloc(h, &s->ev_ctl, 4))) return rc;
         SCHK(h, apv_eval_pressure_prepare(f64, Pv, H, L));
+        if (h->eval_spectra) {
+            s->es_on = 1;
+            if ((rc = dalloc(h, &s->es_ring, (size_t)s->ev_sets * Mv * N))) return rc;
+            if ((rc = dalloc(h, &s->es_spec, (size_t)K * s->ev_sets * Mv, 2 * sizeof(double)))) return rc;
+            if ((rc = dalloc(h, &s->es_tot, (size_t)nz * (3 * E + 1) * K * Mv))) return rc;
+            SCHK(h, apv_stft_prepare(N, 1));                 // the float64 plan, beside the stream's own where that is float32
+        }
     }
     // target filter spectra: rfft of a unit impulse at tap modeling_delay of the A reference loudspeaker
     // (apvast.py:389-390, 418, 422: the same filter serves A_t and B_t)
@@ -1874,6 +1906,14 @@ int apv_stream_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const doubl
     return APV_OK;
 }
 
+int apv_stream_set_evaluation_spectra(apv_handle* h, int32_t on) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_evaluation_spectra: the stream is initialised (its buffers are allocated there)");
+    if (on != 0 && on != 1) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_evaluation_spectra: 0 (off) or 1 (on)");
+    h->eval_spectra = on;
+    return APV_OK;
+}
+
 int apv_stream_reset_evaluation(apv_handle* h) {
     if (!h || !h->st || !h->st->ev_on) return apv_fail(h, APV_ERR_ARG, "apv_stream_reset_evaluation: no stream with an evaluation stage");
     apv_stream* s = h->st;
@@ -1881,6 +1921,10 @@ int apv_stream_reset_evaluation(apv_handle* h) {
     SCHK(h, hipMemsetAsync(s->ev_tot, 0, sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->ev_Mv, h->stream));
     const size_t hb = (size_t)s->ev_nhist * (s->ev_Pv - 1) * s->L * s->esz;
     for (int b = 0; b < 2 && hb > 0; ++b) SCHK(h, hipMemsetAsync(s->ev_hist[b], 0, hb, h->stream));
+    if (s->es_on) {
+        SCHK(h, hipMemsetAsync(s->es_tot, 0, sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->K * s->ev_Mv, h->stream));
+        SCHK(h, hipMemsetAsync(s->es_ring, 0, sizeof(double) * (size_t)s->ev_sets * s->ev_Mv * s->N, h->stream));
+    }
     SCHK(h, hipStreamSynchronize(h->stream));
     return APV_OK;
 }
@@ -2117,6 +2161,8 @@ int apv_set_mu(apv_handle* h, double mu) {
 //   "eval_pressure" [sets][H][Mv] f64, "eval_hops" [hops of the last call][Z][3 E + 1][Mv] f64 (both read-only), "eval_totals"
 //                                  [Z][3 E + 1][Mv] f64, "eval_history" [Z (E + 1)][Pv - 1][L] samples: only a stream with
 //                                  apv_stream_set_evaluation has them (see include/apvast_hip.h)
+//   "eval_spectra" [Z][3 E + 1][K][Mv] f64, "eval_ring" [sets Mv][N] f64 (a ring: logical order): only a stream with
+//                                  apv_stream_set_evaluation_spectra has them
 //   "signal_schedule" int32 {hops of the last apv_process_signal* call that went through chunk launches, hops of it that went hop by
 //                                  hop}, read-only; {0, 0} before the first such call, untouched by the per-hop calls
 static int live_index(const char* name) {
@@ -2236,6 +2282,11 @@ static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* by
         if (n == "eval_totals") { *dptr = s->ev_tot; *bytes = slot; return APV_OK; }
         if (n == "eval_history") { *dptr = s->ev_hist[s->cur]; *bytes = (size_t)s->ev_nhist * (s->ev_Pv - 1) * L * e1; return APV_OK; }
     }
+    if (s->es_on) {
+        if (n == "eval_spectra") { *dptr = s->es_tot; *bytes = sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * K * s->ev_Mv; return APV_OK; }
+        if (n == "eval_ring") {
+            *dptr = s->es_ring; *bytes = sizeof(double) * (size_t)s->ev_sets * s->ev_Mv * N; *ring_rows = s->ev_sets * s->ev_Mv; return APV_OK; }
+    }
     return apv_fail(h, APV_ERR_STATE, std::string("unknown state name: ") + name);
 }
 
@@ -2314,8 +2365,8 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
                 std::memcpy(out + (k * C + c) * e2, tmp.data() + ((k / g) * g * C + c * g + k % g) * e2, e2);
         return APV_OK;
     }
-    // ring: rotate rows into logical order
-    const size_t N = h->st->N, off = h->st->ring_off, e1 = h->st->esz;
+    // ring: rotate rows into logical order (rows of N elements: the pressure ring's are float64 whatever the stream's precision)
+    const size_t N = h->st->N, off = h->st->ring_off, e1 = need / ((size_t)rr * N);
     std::vector<char> tmp(need);
     SCHK(h, hipMemcpyAsync(tmp.data(), d, need, hipMemcpyDeviceToHost, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
@@ -2353,7 +2404,7 @@ int apv_set_state(apv_handle* h, const char* name, const void* h_src, size_t byt
         SCHK(h, hipStreamSynchronize(h->stream));
         return APV_OK;
     }
-    const size_t N = h->st->N, off = h->st->ring_off, e1 = h->st->esz;
+    const size_t N = h->st->N, off = h->st->ring_off, e1 = need / ((size_t)rr * N);
     std::vector<char> tmp(need);
     const char* in = (const char*)h_src;
     for (int r = 0; r < rr; ++r) {

@@ -229,9 +229,35 @@ int  apv_fir_synthesis(apv_handle* h, const void* d_x, const void* d_taps_prev, 
  *                                                         replaces: Matlab/main.m:64-76, 120-130 with predictPressure.m:12-16 */
 int  apv_stream_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
                                const int32_t* ranks);
-/* "eval_totals" and both "eval_history" buffers to zero: the next hop's totals equal its own energies.  APV_ERR_ARG without such
- * a stream. */
+/* "eval_totals" and both "eval_history" buffers to zero: the next hop's totals equal its own energies; with the per-bin spectra
+ * on, "eval_spectra" and "eval_ring" too.  APV_ERR_ARG without such a stream. */
 int  apv_stream_reset_evaluation(apv_handle* h);
+/* Per-bin spectra of the evaluation stage (off unless called with on = 1; needs apv_stream_set_evaluation): behind the two launches
+ * of the evaluation stage the device keeps the last N = block_size pressure samples of every pressure set and microphone in a
+ * ring, and after every hop transforms the newest N of them under the stream's analysis window and accumulates the squared
+ * magnitudes per bin (csrc/kernels_evalspec.hip; three more launches per hop, part of the captured hop graphs).  With H the hop,
+ * K = N/2 + 1, w[i] = sin(pi i / N), hop t counted from apv_stream_init, a set "eval_ring" or apv_stream_reset_evaluation
+ * (t = 0 first), and p as defined above, zero before sample 0:
+ *   f_t[s][i, m] = p[s][(t + 1) H - N + i, m], i < N        P_t[s][k, m] = sum_i w[i] f_t[s][i, m] exp(-2 pi i k i / N), k < K
+ *   bright[z, v, m, k] += |P_bright|^2, dark += |P_dark|^2, error += |P_target - P_bright|^2, target[z, m, k] += |P_target|^2
+ * -- one addition per element and hop, no atomics, float64 whatever the stream's precision.  States only such a stream has:
+ *   "eval_spectra"  f64 [Z][3 E + 1][K][Mv]: per program [bright of the E ranks][dark ...][error ...][target], bins before
+ *                   microphones (the order the device accumulates in), summed since apv_stream_init or the last reset
+ *   "eval_ring"     f64 [Z (2 E + 1)][Mv][N]: the last N pressure samples per set (the order of "eval_pressure") and microphone,
+ *                   oldest first
+ * apv_stream_reset_evaluation zeroes both.  Called between apv_create and apv_stream_init; APV_ERR_ARG (nothing changed) once the
+ * stream is initialised or for a value other than 0 and 1.  apv_stream_init returns APV_ERR_ARG when it is on without
+ * apv_stream_set_evaluation, and for block_size > 4096: the float64 transforms in LDS stop there, so a float32 stream with a
+ * larger block cannot have the spectra.                     replaces: nothing in the reference (pwelch on the host) */
+int  apv_stream_set_evaluation_spectra(apv_handle* h, int32_t on);
+/* One step of that stage alone, on device pointers and the handle's stream: d_pressure [Z (2 E + 1)][H][Mv] goes into the ring
+ * d_ring [Z (2 E + 1)][Mv][N] behind the offset ring_off -- logical sample n of a row lives at (n + ring_off) mod N, the hop
+ * takes the logical samples N - H .. N - 1; a caller stepping through hops advances ring_off by H mod N BEFORE each call, as the
+ * stream does -- every row is windowed and transformed, and |P|^2 is added to d_totals [Z][3 E + 1][N/2 + 1][Mv].  All float64.
+ * The call allocates and frees the transform's scratch and synchronises.  APV_ERR_ARG for null pointers, sizes below 1, odd N,
+ * N > 4096, Z > 2, H > N or ring_off outside 0..N - 1.       replaces: nothing in the reference */
+int  apv_eval_spectrum_step(apv_handle* h, const double* d_pressure, double* d_ring, int32_t ring_off, int32_t N, int32_t H, int32_t Z,
+                            int32_t E, int32_t Mv, double* d_totals);
 /* The pressure kernel alone, on the handle's stream: d_y [G][Pv - 1 + H][L] samples (per group the Pv - 1 in front of the hop,
  * then the hop; float64 with a float64 front-end, else float32), d_rv [Pv][L][Mv] float64, d_p [G][H][Mv] float64:
  * p[g][n, m] = sum_l sum_j rv[j, l, m] y[g][Pv - 1 + n - j, l].  APV_ERR_ARG for a size below 1, null pointers, G > 65535 or

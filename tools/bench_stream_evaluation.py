@@ -13,6 +13,11 @@ microphones:
   * contrast_db and nmse (evaluation.metrics on the accumulated totals) of the WOLA, constrained-WOLA and FIR streams on the same
     signal: recorded, not gated.  The validation responses are the control responses with 10 % independent noise added.
 
+`--spectra` runs the leg of the per-bin spectra instead (apvast(..., evaluation_spectra=True), csrc/kernels_evalspec.hip): ms per
+hop of process_input_buffers with the evaluation stage alone and with the spectra, WOLA stream, V = 1 and V = 16, same protocol;
+and contrast and NMSE per third-octave band from the accumulated spectra (recorded, not gated).  It replaces the section "Per-bin
+spectra" of the file and leaves the rest as it is.
+
 Writes profiles/stream_evaluation.md (and one JSON line per leg on stdout).  A leg that fails or overruns its time limit ends the
 run.  `--bench-parent A,B,C --bench-this A,B,C` adds the ms_per_step of bench.py on the parent commit and on this one to the file.
 """
@@ -44,7 +49,7 @@ def validation(a0, b0):
     return tuple(r + 0.1 * np.sqrt(np.mean(r ** 2, axis=(1, 2), keepdims=True)) * rng.standard_normal(r.shape) for r in (a0, b0))
 
 
-def make(synth, V, evaluate):
+def make(synth, V, evaluate, spectra=False):
     from ap_vast_unofficial_amd.apvast import apvast
     s = CFG3
     a0, b0 = rirs(s["P"], s["L"], s["M"], 99)
@@ -56,12 +61,14 @@ def make(synth, V, evaluate):
     if evaluate:
         va, vb = validation(a0, b0)
         kw.update(validation_rir_A=va, validation_rir_B=vb, evaluation_ranks=[V])
+    if spectra:
+        kw.update(evaluation_spectra=True)
     return apvast(s["N"], a0, b0, s["J"], 20, 0, 0, V, 1.0, 4 * s["N"], hop_size=s["H"], perceptual=False, dtype="f64", seed=0, **kw)
 
 
-def leg_hop(synth, V, evaluate, hops):
+def leg_hop(synth, V, evaluate, hops, spectra=False):
     H = CFG3["H"]
-    obj = make(synth, V, evaluate)
+    obj = make(synth, V, evaluate, spectra)
     warm = 8
     x = np.random.default_rng(3).standard_normal((2, (warm + hops) * H))
     ts = []
@@ -70,11 +77,16 @@ def leg_hop(synth, V, evaluate, hops):
         obj.process_input_buffers(x[0, h * H:(h + 1) * H], x[1, h * H:(h + 1) * H])
         ts.append(time.perf_counter() - t0)
     ts = np.array(ts[warm:]) * 1e3
-    res = dict(leg="hop", synthesis=synth, V=V, evaluation=bool(evaluate), hops=hops, hop_ms_median=float(np.median(ts)),
+    res = dict(leg="hop", synthesis=synth, V=V, evaluation=bool(evaluate), spectra=bool(spectra), hops=hops, hop_ms_median=float(np.median(ts)),
                hop_ms_p10=float(np.percentile(ts, 10)), hop_ms_p90=float(np.percentile(ts, 90)), audio_hop_ms=H / 48.0)
     if evaluate:
         m = __import__("ap_vast_unofficial_amd.evaluation", fromlist=["metrics"]).metrics(obj.evaluation_totals())
         res.update(nmse=m["nmse"][:, 0].tolist(), contrast_db=m["contrast_db"][:, 0].tolist())
+    if spectra:
+        from ap_vast_unofficial_amd.evaluation import spectral_metrics, third_octave_bands
+        centres, bands = third_octave_bands(48000, CFG3["N"], f_min=100.0, f_max=16000.0)
+        m = spectral_metrics(obj.evaluation_spectra(), bands)
+        res.update(band_hz=centres.tolist(), band_contrast_db=m["contrast_db"][:, 0].tolist(), band_nmse=m["nmse"][:, 0].tolist())
     obj.close()
     print(json.dumps(res), flush=True)
 
@@ -119,6 +131,62 @@ def child(args, timeout):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
+def spectra_section(args):
+    """the --spectra leg: evaluation alone against evaluation + spectra, alternating, fresh processes; the section's lines"""
+    rows = []
+    for V in (1, 16):
+        for rep in range(2):
+            for sp in (0, 1):
+                r = child(["--leg", "hop", "--synthesis", "wola", "--V", str(V), "--evaluation", "1", "--with-spectra", str(sp),
+                           "--hops", str(args.hops)], args.timeout)
+                if r is None:
+                    return None
+                rows.append(r)
+    lines = [SPECTRA_HEAD, "",
+             "`tools/bench_stream_evaluation.py --spectra`: the WOLA stream above with the evaluation stage, without and with",
+             f"`evaluation_spectra=True` (three more launches per hop); {args.hops} timed hops per leg after 8 warm-up hops, every leg a",
+             "fresh process, without / with alternating.  ms per hop of `process_input_buffers` (median; p10 .. p90):", "",
+             "| V | spectra | run 1 | run 2 |", "|---|---|---|---|"]
+    for V in (1, 16):
+        for sp in (False, True):
+            q = [r for r in rows if r["V"] == V and r["spectra"] == sp]
+            cells = " | ".join(f"{r['hop_ms_median']:.3f} ({r['hop_ms_p10']:.3f} .. {r['hop_ms_p90']:.3f})" for r in q)
+            lines.append(f"| {V} | {'on' if sp else 'off'} | {cells} |")
+    for V in (1, 16):
+        off = np.median([r["hop_ms_median"] for r in rows if r["V"] == V and not r["spectra"]])
+        on = np.median([r["hop_ms_median"] for r in rows if r["V"] == V and r["spectra"]])
+        lines.append("")
+        lines.append(f"V = {V}: {on - off:+.3f} ms per hop for the spectra (median of the runs with, less median of the runs without).")
+    q = [r for r in rows if r["V"] == 16 and r["spectra"]][0]
+    lines += ["", "Contrast and NMSE per third-octave band (`evaluation.third_octave_bands(48000, 2048, 100, 16000)` into",
+              "`evaluation.spectral_metrics`), V = 16, rank 16, totals over all hops of the leg; recorded, not gated.  Per zone",
+              "program [A, B].", "", "| band (Hz) | contrast_db | nmse |", "|---|---|---|"]
+    for i, fc in enumerate(q["band_hz"]):
+        lines.append(f"| {fc:.0f} | {', '.join('%.2f' % z[i] for z in q['band_contrast_db'])} | "
+                     f"{', '.join('%.4f' % z[i] for z in q['band_nmse'])} |")
+    return lines
+
+
+SPECTRA_HEAD = "## Per-bin spectra"
+
+
+def replace_section(text, head, lines):
+    """`text` with the section that starts at the line `head` (up to the next '## ' line or the end) replaced by `lines`"""
+    old = text.split("\n")
+    out, skip = [], False
+    for ln in old:
+        if ln == head:
+            skip = True
+            continue
+        if skip and ln.startswith("## "):
+            skip = False
+        if not skip:
+            out.append(ln)
+    while out and out[-1] == "":
+        out.pop()
+    return "\n".join(out + [""] + lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", choices=("hop", "kernel"))
@@ -126,16 +194,27 @@ def main():
     ap.add_argument("--V", type=int, default=16)
     ap.add_argument("--evaluation", type=int, default=0)
     ap.add_argument("--hops", type=int, default=100)
+    ap.add_argument("--with-spectra", type=int, default=0, help="a hop leg with evaluation_spectra=True")
+    ap.add_argument("--spectra", action="store_true", help="run the per-bin spectra leg and replace its section of the file")
     ap.add_argument("--timeout", type=int, default=120, help="seconds per leg")
     ap.add_argument("--bench-parent", default="", help="ms_per_step of bench.py on the parent commit, comma separated")
     ap.add_argument("--bench-this", default="", help="... and on this commit")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_evaluation.md"))
     args = ap.parse_args()
     if args.leg == "hop":
-        leg_hop(args.synthesis, args.V, args.evaluation, args.hops)
+        leg_hop(args.synthesis, args.V, args.evaluation, args.hops, bool(args.with_spectra))
         return 0
     if args.leg == "kernel":
         leg_kernel(20)
+        return 0
+    if args.spectra:
+        lines = spectra_section(args)
+        if lines is None:
+            return 1
+        text = open(args.out).read() if os.path.exists(args.out) else ""
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(replace_section(text, SPECTRA_HEAD, lines))
         return 0
     rows, metrics = [], []
     for synth in ("wola", "fir"):
@@ -190,9 +269,17 @@ def main():
                   f"* parent: ms_per_step {', '.join('%.4f' % v for v in p)} (range {min(p):.4f} .. {max(p):.4f})",
                   f"* this commit: ms_per_step {', '.join('%.4f' % v for v in t)} (range {min(t):.4f} .. {max(t):.4f})",
                   "", "The default stream launches nothing new: the evaluation stage is behind `ev_on`, which only the keywords set."]
+    # the section of the --spectra leg, if the file has one, stays
+    kept = []
+    if os.path.exists(args.out):
+        for ln in open(args.out).read().split("\n"):
+            if ln == SPECTRA_HEAD or (kept and not ln.startswith("## ")):
+                kept.append(ln)
+            elif kept:
+                break
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
+        fh.write("\n".join(lines + ([""] + kept if kept else [])).rstrip("\n") + "\n")
     return 0
 
 
