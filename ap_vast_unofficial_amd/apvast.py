@@ -190,7 +190,7 @@ class apvast:
         if rir_A.shape != rir_B.shape:
             raise RuntimeError("rirs of unequal size")                        # apvast.py:89-90
         self._fullscale_db_spl = fullscale_db_spl
-        self._max_sweeps = int(max_sweeps)       # Jacobi sweep cap (0 = default); a hop that reaches it raises LinAlgError
+        self._max_sweeps = int(max_sweeps)       # Jacobi sweep cap (0 = default); a hop that reaches it still returns its outputs and warns (ConvergenceWarning)
         if mode not in ("subband", "broadband"):
             raise ValueError("mode must be 'subband' or 'broadband'")
         if dialect not in ("python", "matlab"):

@@ -63,7 +63,12 @@ struct GevdParams {
     // below n (a statistics window that holds fewer than n rows): loaded with 1e-7 alone, the whitened matrix spans more decades
     // than the float32 sweeps of the order-64 kernel resolve; the LDS kernel's float64 instance sweeps in float64, and its parked
     // factor fits the same scratch slots.  (Explicit float32 statistics never reach kernels_gevd64.hip: nothing to reroute there.)
+    // (The fused update of ONE block with fewer control points than loudspeakers, M < n, is such a pencil too: the stream's plain
+    // hop and apv_update_dev of a float64 handle, and apv_stream_get_statistics, set the field for it.)
     int no_gevd64;
+    // 1: second launch behind kernels_gevd64.hip on the same stream (apv_launch_gevd makes it): a small grid whose workgroups walk
+    // the status words and solve the bins left at 2 again, from the same inputs, in float64 throughout
+    int only_status2;
 };
 
 struct apv_handle {

@@ -432,6 +432,9 @@ int apv_update_dev(apv_handle* h, const void* d_XB, const void* d_XD, const void
     p.w = d_w;
     p.lam = d_lam;
     p.status = d_status;
+    // slabs of rank below the order: not for kernels_gevd64.hip (apv_internal.h).  A float32 handle keeps that kernel and its
+    // float64 fall-back: the float LDS kernel it would get instead is the less accurate of the two
+    p.no_gevd64 = c.n_mics < c.n_srcs && c.compute_dtype == APV_F64;
     std::string why;
     hipError_t e;
     // order 64 takes the fused order-64 kernel in either arithmetic (kernels_gevd64.hip) unless that kernel is switched off

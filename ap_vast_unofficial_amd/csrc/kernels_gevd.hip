@@ -48,10 +48,17 @@ template <> struct Tol<double> {
     // quadratic convergence: the sweep that meets it leaves ~tol2^2 behind.  The threshold is relative to ||C||_F, so the
     // vectors of eigenvalues far below ||C|| need it tight: see Prec<double> in gevd16_common.h for the measurements
     static constexpr double sweep_tol2 = 1e-16;
-    static constexpr int max_sweeps = 16;
+    // ... and tighter still where the spectrum reaches below 1e-8 lambda_1 (the off-diagonal weight 1e-16 ||C||^2 leaves) AND the
+    // filter's denominators lambda + mu below 1e-2 lambda_1, so that this weight shows in w (a spectrum over 1e12 with
+    // mu = 1e-3 lambda_1 at order 24: w at 1.1e-7 of the oracle's with 1e-16, 5e-14 with 1e-20).  Looked at only by a sweep that
+    // met sweep_tol2, so every other launch sweeps as before; unconditionally it cost 1.5 .. 6 % (profiles/order64_fallback.md)
+    static constexpr double sweep_tol2_wide = 1e-20;
+    // a spectrum over 1e12 takes 17 .. 20 sweeps at order 64: the float rotations drop a pivot by 1e-7 at a time
+    static constexpr int max_sweeps = 24;
 };
 template <> struct Tol<float> {
     static constexpr float sweep_tol2 = 1e-8f;
+    static constexpr float sweep_tol2_wide = 1e-8f;      // (float32: one threshold)
     static constexpr int max_sweeps = 14;
 };
 
@@ -122,8 +129,9 @@ __device__ __forceinline__ void rr_pair(int ne, int r, int a, int& p, int& q) {
 }
 
 // XT: element type of the fused input slabs (float2 = c64, double2 = c128: the float64 streaming front-end)
+// one bin (k) of one zone program (blockIdx.y) by one workgroup
 template <typename T, int NMAX, int TPB, bool FUSED, bool SPILL, bool EXACT, typename XT>
-__global__ void __launch_bounds__(TPB) gevd_vast_kernel(const GevdParams p) {
+__device__ __forceinline__ void gevd_vast_bin(const GevdParams& p, const int k) {
     // zone program of a two-zone launch (blockIdx.y); the argument block itself stays in scalar registers
     const bool z1 = (blockIdx.y == 1);
     const XT* const pXB = reinterpret_cast<const XT*>(z1 ? p.XB1 : p.XB);
@@ -161,7 +169,6 @@ __global__ void __launch_bounds__(TPB) gevd_vast_kernel(const GevdParams p) {
 
     const int n = EXACT ? NMAX : p.n;          // EXACT: order known at compile time (index arithmetic folds)
     const int tid = threadIdx.x;
-    const int k = blockIdx.x;
     int status = 0;
 
     // ---------------- stage 0: load or correlate ----------------
@@ -537,7 +544,19 @@ __global__ void __launch_bounds__(TPB) gevd_vast_kernel(const GevdParams p) {
             T off = 0;
             for (int a = 0; a < np; ++a) off += roff[a];
             __syncthreads();
-            if (off <= (p.sweep_tol2 > 0.0 ? (T)p.sweep_tol2 : Tol<T>::sweep_tol2) * normF2) converged = true;
+            if (off <= (p.sweep_tol2 > 0.0 ? (T)p.sweep_tol2 : Tol<T>::sweep_tol2) * normF2) {
+                converged = true;
+                if (sizeof(T) == 8 && !(p.sweep_tol2 > 0.0) && off > Tol<T>::sweep_tol2_wide * normF2) {
+                    // (every thread reads the same n words: uniform.  The diagonal is next written behind the barrier of round 0)
+                    T dmin = sA[0].x, dmax = sA[0].x;
+                    for (int j = 1; j < n; ++j) {
+                        const T dj = sA[j * LD + j].x;
+                        dmin = fmin(dmin, dj);
+                        dmax = fmax(dmax, dj);
+                    }
+                    if (dmin < (T)1e-8 * dmax && dmin + (T)p.mu < (T)1e-2 * dmax) converged = false;
+                }
+            }
         }
         if (!converged) status = 2;
 
@@ -623,10 +642,33 @@ __global__ void __launch_bounds__(TPB) gevd_vast_kernel(const GevdParams p) {
     if (pstatus != nullptr && tid == 0) pstatus[k] = status;
 }
 
+template <typename T, int NMAX, int TPB, bool FUSED, bool SPILL, bool EXACT, typename XT>
+__global__ void __launch_bounds__(TPB) gevd_vast_kernel(const GevdParams p) {
+    if (!p.only_status2) {
+        gevd_vast_bin<T, NMAX, TPB, FUSED, SPILL, EXACT, XT>(p, blockIdx.x);
+        return;
+    }
+    // fall-back launch behind the order-64 kernel: a small grid whose workgroups walk the status words and solve only the bins
+    // that kernel gave up on (each test is uniform over the workgroup; the barrier separates one bin's use of the LDS from the next)
+    const int32_t* const pstatus = (blockIdx.y == 1) ? p.status1 : p.status;
+    if (pstatus == nullptr) return;
+    // the common case, no bin of this workgroup's at status 2, costs one round of loads and a vote
+    int mine = 0;
+    for (int k = blockIdx.x + (int)threadIdx.x * (int)gridDim.x; k < p.K; k += TPB * (int)gridDim.x) mine |= (pstatus[k] == 2);
+    if (!__syncthreads_or(mine)) return;
+    for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
+        if (pstatus[k] != 2) continue;
+        gevd_vast_bin<T, NMAX, TPB, FUSED, SPILL, EXACT, XT>(p, k);
+        __syncthreads();
+    }
+}
+
 template <typename T, int NMAX, int TPB, bool SPILL>
 hipError_t launch_t(const GevdParams& p, bool fused, hipStream_t s) {
     if (p.K <= 0) return hipSuccess;
-    const dim3 grid(p.K, p.n_zones > 1 ? 2 : 1);
+    // (fall-back launch: 64 workgroups a zone program.  Every workgroup reserves the kernel's LDS whether or not it finds a bin, so
+    // a grid of K would queue for the compute units beside the next order-64 launch of a pipelined caller)
+    const dim3 grid(p.only_status2 && p.K > 64 ? 64 : p.K, p.n_zones > 1 ? 2 : 1);
     const bool xd = fused && p.x_c128;
     if (p.n == NMAX) {
         if (xd) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, true, double2>), grid, dim3(TPB), 0, s, p);
@@ -681,7 +723,24 @@ hipError_t apv_launch_gevd(const GevdParams& p, int compute_dtype, bool fused, h
         const hipError_t e16 = apv_launch_gevd16m(p, compute_dtype, fused, s);
         if (e16 != hipErrorNotSupported) return e16;
         const hipError_t e64 = p.no_gevd64 ? hipErrorNotSupported : apv_launch_gevd64(p, compute_dtype, fused, s);
-        if (e64 != hipErrorNotSupported) return e64;
+        if (e64 != hipErrorNotSupported) {
+            // Bins whose float64 refinement gave up (status 2: Rayleigh quotients too close for its first-order step) are solved
+            // again by the float64 LDS kernel from the same slabs or matrices; every other workgroup of this second launch reads
+            // its status word and returns.  Launched whether or not a bin needs it: a captured hop keeps one shape.  The parked
+            // factor (n x n c128 per bin) fits the order-64 kernel's scratch slots, which that kernel has finished with.  Without
+            // status words there is nothing to select by, and the timing aids measure the order-64 kernel alone.
+            const bool words = p.status != nullptr && (p.n_zones <= 1 || p.status1 != nullptr);
+            if (e64 != hipSuccess || p.K <= 0 || !words || p.debug_stop != 0 || p.stamps != nullptr) return e64;
+            GevdParams q = p;
+            q.only_status2 = 1;
+            // the last resort is thorough: at least 32 sweeps (a caller's cap was chosen for the order-64 kernel's float32 sweeps,
+            // not for a float64 cyclic Jacobi from scratch, which takes 17 .. 20 on a spectrum over 1e12) and the tight threshold
+            // throughout.  Few bins come here, so neither costs a launch.  (sweep_tol2 is zero or a negative tuning value of the
+            // order-64 pre-solve here, which means nothing to this kernel: overwritten either way.)
+            if (q.max_sweeps < 32) q.max_sweeps = 32;
+            q.sweep_tol2 = 1e-20;
+            return launch_t<double, 64, 1024, true>(q, fused, s);
+        }
     }
     if (n < 1 || n > APV_MAX_N) {
         if (why) *why = "GEVD order n out of range (1..64)";

@@ -588,6 +588,8 @@ static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void
         p.status = ostatus[first];
         p.n_zones = (runA && runB) ? 2 : 1;
         p.yield_issue = sch.yield_issue;
+        // one block of fewer than L rows: win_low_rank's route at T = 1, on every hop (float64 arithmetic only, as in apv_update_dev)
+        p.no_gevd64 = s->M < L && h->cfg.compute_dtype == APV_F64;
         if (sch.lspill) p.Lspill = sch.lspill;
         if (p.n_zones == 2) {
             p.XB1 = q.X[3]; p.XD1 = q.X[2]; p.d1 = q.tspec[1];
@@ -2031,7 +2033,7 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         }
         p.nV = 1; p.ranks[0] = 1; p.out_c128 = 1; p.n_zones = 1;
         // a window of fewer than L rows (win_fill_host hops are in it now): not for kernels_gevd64.hip, see win_low_rank
-        p.no_gevd64 = s->fg_beta > 0.0 ? s->fg_no_gevd64 : (s->win_T > 1 && (long)s->win_fill_host * M < L);
+        p.no_gevd64 = s->fg_beta > 0.0 ? s->fg_no_gevd64 : (s->win_T > 1 ? (long)s->win_fill_host * M < L : M < L);
         p.RB = dRB; p.RD = dRD; p.r = dr; p.w = dw; p.lam = dl; p.status = (int32_t*)dst; p.U = dU; p.Lspill = dspill;
         std::string why;
         e = apv_launch_gevd(p, APV_F64, false, st, &why);
