@@ -36,7 +36,7 @@ EXPORTS = (
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
     "apv_comm_unique_id", "apv_comm_init", "apv_allgather_filters_dev", "apv_comm_count", "apv_comm_last_gather", "apv_comm_barrier",
-    "apv_debug_set_stamps", "apv_device_sync", "apv_device_info",
+    "apv_debug_set_stamps", "apv_debug_live_resources", "apv_device_sync", "apv_device_info",
 )
 
 
@@ -172,6 +172,7 @@ def load():
     lib.apv_comm_last_gather.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(sz)]
     lib.apv_comm_barrier.argtypes = [vp]
     lib.apv_debug_set_stamps.argtypes = [vp, vp]
+    lib.apv_debug_live_resources.argtypes = [C.POINTER(i32)]
     lib.apv_device_sync.argtypes = [vp]
     lib.apv_device_info.argtypes = [vp, C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
     for name in EXPORTS:
@@ -926,6 +927,13 @@ class Engine:
     def debug_set_stamps(self, dbuf):
         """Diagnostics: register (or, with None, remove) the stage-stamp buffer of the order-16 kernel's diagnostic instantiation."""
         self._chk(self.lib.apv_debug_set_stamps(self.h, dbuf.ptr if dbuf is not None else None))
+
+    @staticmethod
+    def debug_live_resources():
+        """Diagnostics: (device buffers, pinned blocks, events, streams) the stream states of this process hold now."""
+        counts = (C.c_int32 * 4)()
+        load().apv_debug_live_resources(counts)
+        return tuple(counts)
 
     def device_sync(self):
         self._chk(self.lib.apv_device_sync(self.h))

@@ -1,5 +1,6 @@
 // C ABI of libapvast_hip.so (see include/apvast_hip.h for the contract).
 #include "apv_internal.h"
+#include "apv_owned.h"
 #include <utility>
 
 #include <cstdlib>
@@ -265,7 +266,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
         hipError_t _e = (call);                                          \
         if (_e != hipSuccess) {                                          \
             g_create_err = std::string(#call) + ": " + hipGetErrorString(_e); \
-            delete h;                                                    \
+            apv_destroy(h);                                              \
             return APV_ERR_HIP;                                          \
         }                                                                \
     } while (0)
@@ -278,7 +279,7 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     if (rc == APV_OK) rc = ensure_rscratch(h);
     if (rc != APV_OK) {
         g_create_err = h->err;
-        delete h;
+        apv_destroy(h);
         return rc;
     }
     *out = h;
@@ -637,21 +638,17 @@ int apv_jdiag_batched(apv_handle* h, int32_t n, int32_t batch, const double* h_A
     HIPCHK(h, hipSetDevice(h->device));
     // always runs in f64 / c128, whatever the handle's streaming dtype
     const size_t mat = (size_t)batch * n * n * 16;
-    struct Tmp {
-        void* p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Tmp() { for (void* q : p) if (q) (void)hipFree(q); }
-    } t;                                                    // freed on every way out
-    void*& dA = t.p[0]; void*& dB = t.p[1]; void*& dU = t.p[2]; void*& dw = t.p[3]; void*& dl = t.p[4];
-    void*& dsv = t.p[5]; void*& spill = t.p[6];
-    HIPCHK(h, hipMalloc(&dA, mat));
-    HIPCHK(h, hipMalloc(&dB, mat));
-    HIPCHK(h, hipMalloc(&dU, mat));
-    HIPCHK(h, hipMalloc(&dw, (size_t)batch * n * 16));
-    HIPCHK(h, hipMalloc(&dl, (size_t)batch * n * 8));
-    HIPCHK(h, hipMalloc(&dsv, (size_t)batch * sizeof(int32_t)));
-    int32_t* ds = (int32_t*)dsv;
+    ApvOwned t;                                             // freed on every way out
+    void *dA = nullptr, *dB = nullptr, *dU = nullptr, *dw = nullptr, *dl = nullptr, *spill = nullptr;
+    int32_t* ds = nullptr;
+    HIPCHK(h, t.device(&dA, mat));
+    HIPCHK(h, t.device(&dB, mat));
+    HIPCHK(h, t.device(&dU, mat));
+    HIPCHK(h, t.device(&dw, (size_t)batch * n * 16));
+    HIPCHK(h, t.device(&dl, (size_t)batch * n * 8));
+    HIPCHK(h, t.device(&ds, (size_t)batch * sizeof(int32_t)));
     const size_t sb = apv_gevd_spill_bytes(n, batch, APV_F64, h->cfg.reg_mode, 0.0, 1e-17, 1);   // as launched below: f64, tol 1e-17
-    if (sb) HIPCHK(h, hipMalloc(&spill, sb));
+    if (sb) HIPCHK(h, t.device(&spill, sb));
     HIPCHK(h, hipMemcpyAsync(dA, h_A, mat, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(dB, h_B, mat, hipMemcpyHostToDevice, h->stream));
     GevdParams p = base_params(h);
@@ -698,15 +695,12 @@ int apv_jdiag_large(apv_handle* h, int32_t n, int32_t batch, const double* h_A, 
     if (batch == 0) return APV_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t mat = (size_t)batch * n * n * sizeof(double);
-    struct Tmp {
-        double* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Tmp() { for (double* q : p) if (q) (void)hipFree(q); }
-    } t;                                                    // freed on every way out
-    double*& dA = t.p[0]; double*& dB = t.p[1]; double*& dU = t.p[2]; double*& dl = t.p[3]; double*& dn = t.p[4];
-    HIPCHK(h, hipMalloc((void**)&dA, mat));
-    HIPCHK(h, hipMalloc((void**)&dB, mat));
-    HIPCHK(h, hipMalloc((void**)&dU, mat));
-    HIPCHK(h, hipMalloc((void**)&dl, (size_t)batch * n * sizeof(double)));
+    ApvOwned t;                                             // freed on every way out
+    double *dA = nullptr, *dB = nullptr, *dU = nullptr, *dl = nullptr, *dn = nullptr;
+    HIPCHK(h, t.device(&dA, mat));
+    HIPCHK(h, t.device(&dB, mat));
+    HIPCHK(h, t.device(&dU, mat));
+    HIPCHK(h, t.device(&dl, (size_t)batch * n * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(dA, h_A, mat, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(dB, h_B, mat, hipMemcpyHostToDevice, h->stream));
     std::unique_ptr<int32_t[]> tmp;
@@ -717,7 +711,7 @@ int apv_jdiag_large(apv_handle* h, int32_t n, int32_t batch, const double* h_A, 
     }
     if (h->cfg.reg_mode == APV_REG_REL) {
         // B + reg_dark ||B||_2 I (apvast.py:26-27): the spectral norms first, four matrices per launch
-        HIPCHK(h, hipMalloc((void**)&dn, (size_t)batch * sizeof(double)));
+        HIPCHK(h, t.device(&dn, (size_t)batch * sizeof(double)));
         for (int z0 = 0; z0 < batch; z0 += 4) {
             const double* mats[4];
             const int cnt = batch - z0 < 4 ? batch - z0 : 4;
@@ -745,20 +739,17 @@ int apv_norm2(apv_handle* h, int32_t n, int32_t count, const double* h_mats, dou
     if (count == 0) return APV_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t nn = (size_t)n * n;
-    struct Tmp {
-        double* p[2] = {nullptr, nullptr};
-        ~Tmp() { for (double* q : p) if (q) (void)hipFree(q); }
-    } t;
-    double*& dM = t.p[0]; double*& dn = t.p[1];
-    HIPCHK(h, hipMalloc((void**)&dM, sizeof(double) * nn * count));
-    HIPCHK(h, hipMalloc((void**)&dn, sizeof(double) * count));
+    ApvOwned t;                                             // buffers and timing events: freed on every way out
+    double *dM = nullptr, *dn = nullptr;
+    HIPCHK(h, t.device(&dM, sizeof(double) * nn * count));
+    HIPCHK(h, t.device(&dn, sizeof(double) * count));
     HIPCHK(h, hipMemcpyAsync(dM, h_mats, sizeof(double) * nn * count, hipMemcpyHostToDevice, h->stream));
     // APV_BB_TIMING=1: the device time of the norms alone, between two events (profiling aid, as in stream_bb.hip)
     static const bool timing = getenv("APV_BB_TIMING") != nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     if (timing) {
-        HIPCHK(h, hipEventCreate(&ev[0]));
-        HIPCHK(h, hipEventCreate(&ev[1]));
+        HIPCHK(h, t.event(&ev[0], hipEventDefault));
+        HIPCHK(h, t.event(&ev[1], hipEventDefault));
         HIPCHK(h, hipEventRecord(ev[0], h->stream));
     }
     for (int z0 = 0; z0 < count; z0 += 4) {          // four matrices per call, as a hop has them
@@ -773,8 +764,6 @@ int apv_norm2(apv_handle* h, int32_t n, int32_t count, const double* h_mats, dou
         HIPCHK(h, hipEventSynchronize(ev[1]));
         HIPCHK(h, hipEventElapsedTime(&ms, ev[0], ev[1]));
         fprintf(stderr, "[apv norm2] n=%d count=%d method=%d: %.3f ms\n", n, count, method, ms);
-        (void)hipEventDestroy(ev[0]);
-        (void)hipEventDestroy(ev[1]);
     }
     HIPCHK(h, hipMemcpyAsync(h_out, dn, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -799,20 +788,17 @@ int apv_jdiag_leading(apv_handle* h, int32_t n, int32_t batch, int32_t rank, con
     if (batch == 0) return APV_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t mat = (size_t)batch * n * n * sizeof(double);
-    struct Tmp {
-        double* p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Tmp() { for (double* q : p) if (q) (void)hipFree(q); }
-    } t;
-    double*& dA = t.p[0]; double*& dB = t.p[1]; double*& dU = t.p[2]; double*& dl = t.p[3]; double*& dn = t.p[4]; double*& dV = t.p[5];
-    HIPCHK(h, hipMalloc((void**)&dA, mat));
-    HIPCHK(h, hipMalloc((void**)&dB, mat));
-    HIPCHK(h, hipMalloc((void**)&dU, mat));
-    HIPCHK(h, hipMalloc((void**)&dl, (size_t)batch * n * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&dV, (size_t)batch * n * rank * sizeof(double)));
+    ApvOwned t;                                             // freed on every way out
+    double *dA = nullptr, *dB = nullptr, *dU = nullptr, *dl = nullptr, *dn = nullptr, *dV = nullptr;
+    HIPCHK(h, t.device(&dA, mat));
+    HIPCHK(h, t.device(&dB, mat));
+    HIPCHK(h, t.device(&dU, mat));
+    HIPCHK(h, t.device(&dl, (size_t)batch * n * sizeof(double)));
+    HIPCHK(h, t.device(&dV, (size_t)batch * n * rank * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(dA, h_A, mat, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(dB, h_B, mat, hipMemcpyHostToDevice, h->stream));
     if (h->cfg.reg_mode == APV_REG_REL) {
-        HIPCHK(h, hipMalloc((void**)&dn, (size_t)batch * sizeof(double)));
+        HIPCHK(h, t.device(&dn, (size_t)batch * sizeof(double)));
         for (int z0 = 0; z0 < batch; z0 += 4) {
             const double* mats[4];
             const int cnt = batch - z0 < 4 ? batch - z0 : 4;
@@ -933,14 +919,14 @@ int apv_eval_spectrum_step(apv_handle* h, const double* d_pressure, double* d_ri
     if (int rc = lanes_join(h, true)) return rc;
     HIPCHK(h, apv_stft_prepare(N, 1));
     // the bin-major scratch of the transform is this call's own: a test entry, not a per-hop path
+    ApvOwned t;
     void* spec = nullptr;
-    HIPCHK(h, hipMalloc(&spec, sizeof(double) * 2 * ((size_t)N / 2 + 1) * Z * (2 * (size_t)E + 1) * Mv));
+    HIPCHK(h, t.device(&spec, sizeof(double) * 2 * ((size_t)N / 2 + 1) * Z * (2 * (size_t)E + 1) * Mv));
     EvalSpectraArgs a{};
     a.p = d_pressure; a.ring = d_ring; a.spec = spec; a.totals = d_totals;
     a.ring_off = ring_off; a.N = N; a.H = H; a.Z = Z; a.E = E; a.Mv = Mv;
     hipError_t e = apv_launch_eval_spectra(a, h->stream, &why);
     const hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipFree(spec);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
@@ -1083,6 +1069,12 @@ int apv_comm_barrier(apv_handle* h) {
 int apv_debug_set_stamps(apv_handle* h, void* d_stamps) {
     if (!h) return APV_ERR_ARG;
     h->d_stamps = static_cast<unsigned long long*>(d_stamps);
+    return APV_OK;
+}
+
+int apv_debug_live_resources(int32_t counts[4]) {
+    if (!counts) return APV_ERR_ARG;
+    for (int i = 0; i < 4; ++i) counts[i] = ApvOwned::live[i].load();
     return APV_OK;
 }
 

@@ -11,6 +11,7 @@
 // Device layouts: control-point channel c = m*L + l (loudspeaker fastest), so a bin's control-point
 // matrix X[k] = [M][L] is one contiguous slab of the bin-major spectra [K][M*L].
 #include "apv_internal.h"
+#include "apv_owned.h"
 
 #include <algorithm>
 #include <cmath>
@@ -173,6 +174,7 @@ struct apv_stream {
     double win_ms[2];             // ... and {sum of its times in ms, hops timed}
     std::vector<hipGraphExec_t> execs;
     std::vector<int32_t> h_status;
+    ApvOwned own;                 // every buffer, pinned block, event and stream above: made through it, freed by it
 };
 
 namespace {
@@ -183,11 +185,10 @@ namespace {
         if (_e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
-// `count` elements of `esz` bytes, zeroed
+// `count` elements of `esz` bytes, zeroed, kept by the stream
 template <typename T>
 int dalloc(apv_handle* h, T** p, size_t count, size_t esz = sizeof(T)) {
-    SCHK(h, hipMalloc((void**)p, esz * (count ? count : 1)));
-    SCHK(h, hipMemsetAsync(*p, 0, esz * (count ? count : 1), h->stream));
+    SCHK(h, h->st->own.zeroed(p, count, esz, h->stream));
     return APV_OK;
 }
 
@@ -227,97 +228,22 @@ inline int path_zone(int p) { return p & 1; }
 
 }  // namespace
 
+// the captured launch sequences of the hops: captured again at the next hop of each phase
+static void drop_hop_graphs(apv_stream* s) {
+    for (hipGraphExec_t& e : s->execs) {
+        if (e) (void)hipGraphExecDestroy(e);
+        e = nullptr;
+    }
+}
+
 void apv_stream_free(apv_handle* h) {
     apv_stream* s = h->st;
     if (!s) return;
-    void* bufs[] = {s->rir[0], s->rir[1], s->trir[0], s->trir[1], s->xhist[0][0], s->xhist[0][1], s->xhist[1][0],
-                    s->xhist[1][1], s->resp[0], s->resp[1], s->resp[2], s->resp[3], s->tresp[0], s->tresp[1],
-                    s->inblk, s->X[0], s->X[1], s->X[2], s->X[3], s->tspec[0], s->tspec[1], s->inspec, s->w[0],
-                    s->w[1], s->lam[0], s->lam[1], s->tgt, s->outspec, s->outov, s->out,
-                    s->G2, s->G2T, s->Wgt[0], s->Wgt[1], s->rirspec[0], s->rirspec[1], s->trirspec[0], s->trirspec[1], s->xspec, s->xspec_chunk};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (hipGraphExec_t e : s->execs)
-        if (e) (void)hipGraphExecDestroy(e);
-    if (s->pin_in) (void)hipHostFree(s->pin_in);
-    if (s->pin_out) (void)hipHostFree(s->pin_out);
-    void* second[] = {s->X1[0], s->X1[1], s->X1[2], s->X1[3], s->tspec1[0], s->tspec1[1], s->inspec1};
-    for (void* b : second)
-        if (b) (void)hipFree(b);
-    for (int p = 0; p < 2; ++p) {
-        if (s->ev_front[p]) (void)hipEventDestroy(s->ev_front[p]);
-        if (s->ev_back[p]) (void)hipEventDestroy(s->ev_back[p]);
-        if (s->ev_chunk[p]) (void)hipEventDestroy(s->ev_chunk[p]);
-        if (s->ev_copied[p]) (void)hipEventDestroy(s->ev_copied[p]);
-    }
-    if (s->out1) (void)hipFree(s->out1);
-    if (s->outspec1) (void)hipFree(s->outspec1);
-    if (s->front) (void)hipStreamDestroy(s->front);
-    if (s->tail) (void)hipStreamDestroy(s->tail);
-    if (s->sig_in) (void)hipHostFree(s->sig_in);
-    if (s->sig_out) (void)hipHostFree(s->sig_out);
-    for (void* b : s->stat_ws)
-        if (b) (void)hipFree(b);
-    for (int q = 0; q < 2; ++q) {
-        for (int p = 0; p < 4; ++p)
-            if (s->ck_resp[q][p]) (void)hipFree(s->ck_resp[q][p]);
-        for (int z = 0; z < 2; ++z)
-            if (s->ck_tresp[q][z]) (void)hipFree(s->ck_tresp[q][z]);
-        if (s->ck_in[q]) (void)hipFree(s->ck_in[q]);
-        if (s->ck_tspec[q]) (void)hipFree(s->ck_tspec[q]);
-        for (int b = 0; b < CK_NB; ++b)
-            if (s->ck_backdone[q][b]) (void)hipEventDestroy(s->ck_backdone[q][b]);
-    }
-    for (int b = 0; b < CK_NB; ++b)
-        if (s->ck_k3[b]) (void)hipEventDestroy(s->ck_k3[b]);
-    for (int z = 0; z < 2; ++z) {
-        if (s->ck_wall[z]) (void)hipFree(s->ck_wall[z]);
-        if (s->ck_lamall[z]) (void)hipFree(s->ck_lamall[z]);
-    }
-    for (int b = 0; b + 1 < CK_NB; ++b) {
-        for (int z = 0; z < 2; ++z) {
-            if (s->ck_w[b][z]) (void)hipFree(s->ck_w[b][z]);
-            if (s->ck_lam[b][z]) (void)hipFree(s->ck_lam[b][z]);
-        }
-        if (s->ck_spill[b]) (void)hipFree(s->ck_spill[b]);
-        if (s->ck_back[b]) (void)hipStreamDestroy(s->ck_back[b]);
-    }
-    for (int q = 0; q < CK_NS; ++q)
-        if (s->ck_done[q]) (void)hipEventDestroy(s->ck_done[q]);
-    if (s->ck_pin_in) (void)hipHostFree(s->ck_pin_in);
-    if (s->ck_pin_out) (void)hipHostFree(s->ck_pin_out);
-    for (int p = 0; p < 4; ++p)
-        if (s->ck_X[p]) (void)hipFree(s->ck_X[p]);
-    if (s->ck_inspec) (void)hipFree(s->ck_inspec);
-    if (s->ck_out) (void)hipFree(s->ck_out);
-    for (int z = 0; z < 2; ++z) {
-        if (s->ck_taps[z]) (void)hipFree(s->ck_taps[z]);
-        for (int g = 0; g < 2; ++g)
-            if (s->ck_xrow[z][g]) (void)hipFree(s->ck_xrow[z][g]);
-    }
-    if (s->ck_wallfree) (void)hipEventDestroy(s->ck_wallfree);
-    if (s->ck_ospec) (void)hipFree(s->ck_ospec);
+    // the graphs and everything below may still be in flight on the handle's stream or the stream state's own (a re-init, an init
+    // that failed half-way): wait for the device first, as the first hipFree of the buffers would
+    (void)hipDeviceSynchronize();
+    drop_hop_graphs(s);
     apv_live_free(s->live);
-    if (s->live_cm) (void)hipFree(s->live_cm);
-    for (int z = 0; z < 2; ++z) {
-        void* wb[] = {s->win_ring[z], s->win_RB[z], s->win_RD[z], s->win_r[z]};
-        for (void* b : wb)
-            if (b) (void)hipFree(b);
-        if (s->win_ev[z]) (void)hipEventDestroy(s->win_ev[z]);
-        if (s->wtaps[z]) (void)hipFree(s->wtaps[z]);
-        if (s->cf_ev[z]) (void)hipEventDestroy(s->cf_ev[z]);
-        if (s->fs_taps[z]) (void)hipFree(s->fs_taps[z]);
-        for (int b = 0; b < 2; ++b)
-            if (s->fs_hist[b][z]) (void)hipFree(s->fs_hist[b][z]);
-        if (s->fs_ev[z]) (void)hipEventDestroy(s->fs_ev[z]);
-    }
-    if (s->win_ctr) (void)hipFree(s->win_ctr);
-    {
-        void* eb[] = {s->ev_rv[0], s->ev_rv[1], s->ev_map, s->ev_hsrc, s->ev_hist[0], s->ev_hist[1], s->ev_p, s->ev_tot, s->ev_rec, s->ev_ctl,
-                      s->es_ring, s->es_spec, s->es_tot};
-        for (void* b : eb)
-            if (b) (void)hipFree(b);
-    }
     delete s;
     h->st = nullptr;
 }
@@ -497,8 +423,8 @@ static int eval_begin_call(apv_handle* h, int n_hops) {
         const size_t slot = sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->ev_Mv;
         SCHK(h, hipStreamSynchronize(st));
         double* rec = nullptr;
-        SCHK(h, hipMalloc((void**)&rec, slot * n_hops));
-        if (s->ev_rec) (void)hipFree(s->ev_rec);
+        SCHK(h, s->own.device(&rec, slot * n_hops));
+        s->own.release(s->ev_rec);
         s->ev_rec = rec;
         s->ev_cap = n_hops;
         const unsigned long long words[2] = {(unsigned long long)reinterpret_cast<uintptr_t>(rec), (unsigned long long)n_hops};
@@ -900,18 +826,18 @@ static int signal_prepare(apv_handle* h) {
     // 0.069 / 0.102 / 0.092 ms per hop at cfg3 after 0 / 3 / 5 earlier streams, against 0.074 / 0.071 / 0.074 at the default
     // priority (profiles/r04/cfg3_front_prio.txt).  The schedule with one joint-diagonalisation launch per chunk measures the same
     // either way.)
-    if (!s->front) SCHK(h, hipStreamCreateWithPriority(&s->front, hipStreamNonBlocking, 0));
-    if (!s->tail) SCHK(h, hipStreamCreateWithPriority(&s->tail, hipStreamNonBlocking, 0));
+    if (!s->front) SCHK(h, s->own.stream(&s->front, hipStreamNonBlocking, 0));
+    if (!s->tail) SCHK(h, s->own.stream(&s->tail, hipStreamNonBlocking, 0));
     for (int p = 0; p < 2; ++p) {
-        if (!s->ev_copied[p]) SCHK(h, hipEventCreateWithFlags(&s->ev_copied[p], hipEventDisableTiming));
-        if (!s->ev_front[p]) SCHK(h, hipEventCreateWithFlags(&s->ev_front[p], hipEventDisableTiming));
-        if (!s->ev_back[p]) SCHK(h, hipEventCreateWithFlags(&s->ev_back[p], hipEventDisableTiming));
-        if (!s->ev_chunk[p]) SCHK(h, hipEventCreateWithFlags(&s->ev_chunk[p], hipEventDisableTiming));
+        if (!s->ev_copied[p]) SCHK(h, s->own.event(&s->ev_copied[p], hipEventDisableTiming));
+        if (!s->ev_front[p]) SCHK(h, s->own.event(&s->ev_front[p], hipEventDisableTiming));
+        if (!s->ev_back[p]) SCHK(h, s->own.event(&s->ev_back[p], hipEventDisableTiming));
+        if (!s->ev_chunk[p]) SCHK(h, s->own.event(&s->ev_chunk[p], hipEventDisableTiming));
     }
     // two chunks of pinned staging: the host converts chunk c-1 while the device runs chunk c
-    if (!s->sig_in) SCHK(h, hipHostMalloc(&s->sig_in, e1 * 2 * chunk * 2 * H, hipHostMallocDefault));
+    if (!s->sig_in) SCHK(h, s->own.pinned(&s->sig_in, e1 * 2 * chunk * 2 * H));
     if (!s->sig_out) {
-        SCHK(h, hipHostMalloc(&s->sig_out, 2 * chunk * hop_result_bytes(s), hipHostMallocDefault));
+        SCHK(h, s->own.pinned(&s->sig_out, 2 * chunk * hop_result_bytes(s)));
         std::memset(s->sig_out, 0, 2 * chunk * hop_result_bytes(s));
     }
     SCHK(h, hipStreamSynchronize(h->stream));               // the zero-fills above
@@ -1092,9 +1018,9 @@ static int chunk_prepare(apv_handle* h) {
             if ((rc = dalloc(h, &s->ck_tresp[q][z], M * RL, e1))) return rc;
         if ((rc = dalloc(h, &s->ck_in[q], 2 * RL, e1))) return rc;
         if ((rc = dalloc(h, &s->ck_tspec[q], (size_t)2 * chunk * K * M, e2))) return rc;
-        for (int b = 0; b < CK_NB; ++b) SCHK(h, hipEventCreateWithFlags(&s->ck_backdone[q][b], hipEventDisableTiming));
+        for (int b = 0; b < CK_NB; ++b) SCHK(h, s->own.event(&s->ck_backdone[q][b], hipEventDisableTiming));
     }
-    for (int b = 0; b < CK_NB; ++b) SCHK(h, hipEventCreateWithFlags(&s->ck_k3[b], hipEventDisableTiming));
+    for (int b = 0; b < CK_NB; ++b) SCHK(h, s->own.event(&s->ck_k3[b], hipEventDisableTiming));
     for (int z = 0; z < 2; ++z) {
         if ((rc = dalloc(h, &s->ck_wall[z], (size_t)chunk * K * s->nV * L, wsz(h)))) return rc;
         if ((rc = dalloc(h, &s->ck_lamall[z], (size_t)chunk * K * L, lsz(h)))) return rc;
@@ -1112,9 +1038,9 @@ static int chunk_prepare(apv_handle* h) {
         // (the back streams themselves are made by process_signal_chunked_t, and only where the hop-by-hop schedule runs: the
         // runtime deals a process's streams over four hardware queues, and a stream that exists takes part whether it is used or not)
     }
-    for (int q = 0; q < CK_NS; ++q) SCHK(h, hipEventCreateWithFlags(&s->ck_done[q], hipEventDisableTiming));
-    SCHK(h, hipHostMalloc(&s->ck_pin_in, e1 * CK_NS * chunk * 2 * s->H, hipHostMallocDefault));
-    SCHK(h, hipHostMalloc(&s->ck_pin_out, (size_t)CK_NS * chunk * hop_result_bytes(s), hipHostMallocDefault));
+    for (int q = 0; q < CK_NS; ++q) SCHK(h, s->own.event(&s->ck_done[q], hipEventDisableTiming));
+    SCHK(h, s->own.pinned(&s->ck_pin_in, e1 * CK_NS * chunk * 2 * s->H));
+    SCHK(h, s->own.pinned(&s->ck_pin_out, (size_t)CK_NS * chunk * hop_result_bytes(s)));
     std::memset(s->ck_pin_out, 0, (size_t)CK_NS * chunk * hop_result_bytes(s));
     for (int p = 0; p < 4; ++p)
         if ((rc = dalloc(h, &s->ck_X[p], (size_t)2 * chunk * s->Kp * C, e2))) return rc;
@@ -1124,7 +1050,7 @@ static int chunk_prepare(apv_handle* h) {
     if (s->taps > 0) {
         for (int z = 0; z < 2; ++z)
             if ((s->zones & (1 << z)) && (rc = dalloc(h, &s->ck_taps[z], (size_t)chunk * s->nV * s->taps * L, lsz(h)))) return rc;
-        SCHK(h, hipEventCreateWithFlags(&s->ck_wallfree, hipEventDisableTiming));
+        SCHK(h, s->own.event(&s->ck_wallfree, hipEventDisableTiming));
     }
     if (s->fir_synth)
         for (int q = 0; q < 2; ++q)
@@ -1175,7 +1101,7 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     }
     if (!batched)
         for (int b = 0; b + 1 < CK_NB; ++b)
-            if (!s->ck_back[b]) SCHK(h, hipStreamCreateWithFlags(&s->ck_back[b], hipStreamNonBlocking));
+            if (!s->ck_back[b]) SCHK(h, s->own.stream(&s->ck_back[b], hipStreamNonBlocking));
     hipStream_t bs[CK_NB];
     void* wset[CK_NB][2];
     void* lset[CK_NB][2];
@@ -1614,9 +1540,10 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     }
     SCHK(h, hipSetDevice(h->device));
     apv_stream_free(h);
-    apv_stream* s = new apv_stream();
-    std::memset(static_cast<void*>(s), 0, offsetof(apv_stream, execs));
+    apv_stream* s = new apv_stream();                       // value-initialised: every scalar, pointer and array member starts at zero
     h->st = s;
+    // an init that fails from here on leaves no half-built stream behind
+    struct Guard { apv_handle* h; bool ok; ~Guard() { if (!ok) apv_stream_free(h); } } built{h, false};
     s->N = N; s->H = H; s->K = N / 2 + 1; s->L = c.n_srcs; s->M = c.n_mics; s->C = s->L * s->M;
     s->P = rir_len; s->nV = c.n_ranks; s->zones = c.n_zones; s->pad = apv_fir_pad();
     s->f64 = f64; s->esz = f64 ? 8 : 4;
@@ -1668,8 +1595,9 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     if (s->fir_F > 0) {
         const int F = s->fir_F, np = s->fir_np;
         const size_t Kf = (size_t)F / 2 + 1;
+        ApvOwned scratch;
         void* cm = nullptr;                                  // [C][P] channel-major copy of one bank, set-up only
-        if ((rc = dalloc(h, &cm, (size_t)C * P, e1))) return rc;
+        SCHK(h, scratch.zeroed(&cm, (size_t)C * P, e1, h->stream));
         std::vector<double> tr((size_t)C * P);
         for (int z = 0; z < 2; ++z) {
             const double* src = z ? h_rir_B : h_rir_A;
@@ -1689,7 +1617,6 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
             if ((rc = bank_spectra(h, cm, M, s->trirspec[z]))) return rc;
             SCHK(h, hipStreamSynchronize(h->stream));
         }
-        (void)hipFree(cm);
         if ((rc = dalloc(h, &s->xspec, (size_t)np * 2 * Kf, e2))) return rc;
     }
     const size_t hist = (size_t)s->keep + H + s->pad;
@@ -1727,12 +1654,11 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         const size_t ring_bytes = (size_t)s->win_T * K * E * ce;
         for (int z = 0; z < 2; ++z) {
             if (!(s->zones & (1 << z))) continue;
-            hipError_t e = hipMalloc(&s->win_ring[z], ring_bytes);
+            hipError_t e = s->own.device(&s->win_ring[z], ring_bytes);
             if (e != hipSuccess) {
                 char buf[192];
                 std::snprintf(buf, sizeof(buf), "statistics %s: the ring of %d hop(s) needs %zu bytes per zone program (%d of them): %s",
                               s->fg_beta > 0.0 ? "accumulator" : "window", s->win_T, ring_bytes, nz, hipGetErrorString(e));
-                s->win_ring[z] = nullptr;
                 return apv_fail(h, APV_ERR_HIP, buf);
             }
             SCHK(h, hipMemsetAsync(s->win_ring[z], 0, ring_bytes, h->stream));
@@ -1746,14 +1672,14 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         // hop count separates the two: such a stream keeps every solve off that kernel, so its launch sequence is one and captured.
         s->fg_no_gevd64 = s->fg_beta > 0.0 && s->win_c128 && M < L && apv_gevd64_eligible(L, c.reg_mode, c.reg_bright, c.sweep_tol2);
         if (getenv("APV_STAT_WINDOW_TIMING") != nullptr)
-            for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->win_ev[i]));
+            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->win_ev[i], hipEventDefault));
     }
     if (s->taps > 0) {
         for (int z = 0; z < 2; ++z)
             if ((s->zones & (1 << z)) && (rc = dalloc(h, &s->wtaps[z], (size_t)s->nV * s->taps * L, lsz(h)))) return rc;
         SCHK(h, apv_stft_prepare(N, c.out_c128));           // the projection runs in the filters' precision
         if (getenv("APV_FILTER_CONSTRAINT_TIMING") != nullptr)
-            for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->cf_ev[i]));
+            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->cf_ev[i], hipEventDefault));
     }
     if (h->synthesis == APV_SYNTH_FIR) {
         s->fir_synth = 1;
@@ -1765,7 +1691,7 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
             for (int g = 0; g < 2; ++g)
                 if ((rc = dalloc(h, &s->fs_hist[b][g], (size_t)s->taps - 1, e1))) return rc;
         if (getenv("APV_FIR_SYNTHESIS_TIMING") != nullptr)
-            for (int i = 0; i < 2; ++i) SCHK(h, hipEventCreate(&s->fs_ev[i]));
+            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->fs_ev[i], hipEventDefault));
     }
     if (h->eval_Pv > 0) {
         // evaluation stage: per zone program that runs, the pressure sets [bright of E ranks][dark of E ranks][target]; bright and
@@ -1836,8 +1762,8 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     }
     if ((rc = upload(h, f64, s->tgt, tg))) return rc;
     s->h_status.assign((size_t)2 * K, 0);
-    SCHK(h, hipHostMalloc((void**)&s->pin_in, e1 * 2 * H, hipHostMallocDefault));
-    SCHK(h, hipHostMalloc((void**)&s->pin_out, hop_result_bytes(s), hipHostMallocDefault));
+    SCHK(h, s->own.pinned(&s->pin_in, e1 * 2 * H));
+    SCHK(h, s->own.pinned(&s->pin_out, hop_result_bytes(s)));
     std::memset(s->pin_out, 0, hop_result_bytes(s));
     // the launch sequence of a hop depends on (ring_off, cur) only: ring_off has period N / gcd(N, H), cur period 2
     {
@@ -1854,6 +1780,7 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     s->hop = 0;
     SCHK(h, apv_stft_prepare(N, f64));
     SCHK(h, hipStreamSynchronize(h->stream));
+    built.ok = true;
     return APV_OK;
 }
 
@@ -1980,9 +1907,9 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
     // the work space is sized by (K, L) alone, which a stream never changes: allocated once, kept until apv_stream_free
     void*& dRB = s->stat_ws[0]; void*& dRD = s->stat_ws[1]; void*& dr = s->stat_ws[2]; void*& dU = s->stat_ws[3];
     void*& dw = s->stat_ws[4]; void*& dl = s->stat_ws[5]; void*& dspill = s->stat_ws[6]; void*& dst = s->stat_ws[7];
-    if (!dRB) SCHK(h, hipMalloc(&dRB, mat));
-    if (!dRD) SCHK(h, hipMalloc(&dRD, mat));
-    if (!dr) SCHK(h, hipMalloc(&dr, vec));
+    if (!dRB) SCHK(h, s->own.device(&dRB, mat));
+    if (!dRD) SCHK(h, s->own.device(&dRD, mat));
+    if (!dr) SCHK(h, s->own.device(&dr, vec));
     if (explicit_stats(s)) {
         // the windowed (or forgetting) statistics of the last hop are in device memory: handed out as they are (c64 widened first)
         const size_t nm = (size_t)K * L * L, nv = (size_t)K * L;
@@ -2003,8 +1930,8 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         // grouped spectra: the correlation kernel reads bin-major slabs, so the two sets are regrouped into scratch first
         void*& dgb = s->stat_ws[8]; void*& dgd = s->stat_ws[9];
         const size_t sb = (size_t)K * s->C * 2 * s->esz;
-        if (!dgb) SCHK(h, hipMalloc(&dgb, sb));
-        if (!dgd) SCHK(h, hipMalloc(&dgd, sb));
+        if (!dgb) SCHK(h, s->own.device(&dgb, sb));
+        if (!dgd) SCHK(h, s->own.device(&dgd, sb));
         SCHK(h, apv_launch_ungroup_spectra(s->f64, K, s->C, s->xg, XB, dgb, st));
         SCHK(h, apv_launch_ungroup_spectra(s->f64, K, s->C, s->xg, XD, dgd, st));
         XB = dgb;
@@ -2018,17 +1945,16 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
                                             dr, st);
     if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string("statistics: ") + hipGetErrorString(e));
     if (h_U || h_lam) {
-        if (!dU) SCHK(h, hipMalloc(&dU, mat));
-        if (!dw) SCHK(h, hipMalloc(&dw, vec));
-        if (!dl) SCHK(h, hipMalloc(&dl, (size_t)K * L * 8));
-        if (!dst) SCHK(h, hipMalloc(&dst, (size_t)K * 4));
+        if (!dU) SCHK(h, s->own.device(&dU, mat));
+        if (!dw) SCHK(h, s->own.device(&dw, vec));
+        if (!dl) SCHK(h, s->own.device(&dl, (size_t)K * L * 8));
+        if (!dst) SCHK(h, s->own.device(&dst, (size_t)K * 4));
         GevdParams p = apv_base_params(h);
         const size_t sb = apv_gevd_spill_bytes(L, K, APV_F64, p.reg_mode, p.reg_bright, p.sweep_tol2, 1);
         if (sb > s->stat_spill_bytes) {
-            if (dspill) SCHK(h, hipFree(dspill));
-            dspill = nullptr;
+            s->own.release(dspill);
             s->stat_spill_bytes = 0;
-            SCHK(h, hipMalloc(&dspill, sb));
+            SCHK(h, s->own.device(&dspill, sb));
             s->stat_spill_bytes = sb;
         }
         p.nV = 1; p.ranks[0] = 1; p.out_c128 = 1; p.n_zones = 1;
@@ -2058,30 +1984,24 @@ int apv_stream_set_perceptual(apv_handle* h, int32_t n_channels, const double* h
     apv_stream* s = h->st;
     SCHK(h, hipSetDevice(h->device));
     SCHK(h, hipStreamSynchronize(h->stream));
-    // the captured launch sequences depend on whether the weighting is on
-    for (hipGraphExec_t& e : s->execs) {
-        if (e) (void)hipGraphExecDestroy(e);
-        e = nullptr;
-    }
+    drop_hop_graphs(s);          // the captured launch sequences depend on whether the weighting is on
     if (n_channels <= 0) {
         s->nch = 0;
         s->xg = s->xg_default;
         return APV_OK;
     }
-    s->xg = 1;                   // the weighting's kernels scale bin-major spectra
     if (!h_G2 || n_channels > 512 || (normalisation != 0 && normalisation != 1)) return apv_fail(h, APV_ERR_ARG, "bad perceptual tables");
+    s->xg = 1;                   // the weighting's kernels scale bin-major spectra
     const int K = s->K;
-    void* old[] = {s->G2, s->G2T, s->Wgt[0], s->Wgt[1]};
-    for (void* b : old)
-        if (b) (void)hipFree(b);
-    s->G2 = s->G2T = nullptr;
-    s->Wgt[0] = s->Wgt[1] = nullptr;
+    s->own.release(s->G2);
+    s->own.release(s->G2T);
+    for (int z = 0; z < 2; ++z) s->own.release(s->Wgt[z]);
     std::vector<double> gt((size_t)n_channels * K);
     for (int k = 0; k < K; ++k)
         for (int i = 0; i < n_channels; ++i) gt[(size_t)i * K + k] = h_G2[(size_t)k * n_channels + i];
-    SCHK(h, hipMalloc((void**)&s->G2, sizeof(double) * (size_t)K * n_channels));
-    SCHK(h, hipMalloc((void**)&s->G2T, sizeof(double) * (size_t)K * n_channels));
-    for (int z = 0; z < 2; ++z) SCHK(h, hipMalloc((void**)&s->Wgt[z], s->esz * (size_t)K * s->M));
+    SCHK(h, s->own.device(&s->G2, sizeof(double) * (size_t)K * n_channels));
+    SCHK(h, s->own.device(&s->G2T, sizeof(double) * (size_t)K * n_channels));
+    for (int z = 0; z < 2; ++z) SCHK(h, s->own.device(&s->Wgt[z], s->esz * (size_t)K * s->M));
     // on the handle's stream, like every other upload of this file (a null-stream copy is not ordered with it)
     SCHK(h, hipMemcpyAsync(s->G2, h_G2, sizeof(double) * (size_t)K * n_channels, hipMemcpyHostToDevice, h->stream));
     SCHK(h, hipMemcpyAsync(s->G2T, gt.data(), sizeof(double) * gt.size(), hipMemcpyHostToDevice, h->stream));
@@ -2114,7 +2034,7 @@ int apv_stream_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, c
     if (rc != APV_OK) return rc;
     if (s->fir_F > 0) {
         // the fast-convolution K1 reads spectra of the banks: recomputed in place from the new ones
-        if (!s->live_cm) SCHK(h, hipMalloc(&s->live_cm, s->esz * (size_t)s->P * s->C));
+        if (!s->live_cm) SCHK(h, s->own.device(&s->live_cm, s->esz * (size_t)s->P * s->C));
         for (int k = 0; k < 4; ++k) {
             if (!nw[k]) continue;
             const int n_ch = k < 2 ? s->C : s->M;
@@ -2134,10 +2054,7 @@ int apv_set_mu(apv_handle* h, double mu) {
     if (h->st) {
         SCHK(h, hipSetDevice(h->device));
         SCHK(h, hipStreamSynchronize(h->stream));
-        for (hipGraphExec_t& e : h->st->execs) {
-            if (e) (void)hipGraphExecDestroy(e);
-            e = nullptr;
-        }
+        drop_hop_graphs(h->st);
     }
     h->cfg.mu = mu;
     return APV_OK;

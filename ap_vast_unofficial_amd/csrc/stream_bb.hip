@@ -15,6 +15,7 @@
 // Channel order on the device: c = m*L + l (as in stream.hip).  Everything is double: the dark matrix is loaded
 // with an ABSOLUTE 1e-7 (apvast.py:23) against entries of order 1e-3, so float statistics would not survive.
 #include "apv_internal.h"
+#include "apv_owned.h"
 
 #include <chrono>
 #include <cstdio>
@@ -100,6 +101,7 @@ struct apv_bb {
     hipEvent_t ev_front[2], ev_back[2];      // group set filled / group set read for the last time
     hipEvent_t ev_out[2];                    // a group's outputs have reached g_pin
     FirLive live;          // responses reassigned between hops (apv_bb_set_rirs): the correction tails still to be added to K1's output
+    ApvOwned own;          // every buffer, pinned block, event and stream above: made through it, freed by it
 };
 
 namespace {
@@ -151,9 +153,9 @@ void copy_rows(double* dst, size_t dpitch, const double* src, size_t spitch, siz
     for (auto& x : th) x.join();
 }
 
+// `count` doubles, zeroed, kept by the stream
 int dalloc(apv_handle* h, double** p, size_t count) {
-    BCHK(h, hipMalloc((void**)p, sizeof(double) * (count ? count : 1)));
-    BCHK(h, hipMemsetAsync(*p, 0, sizeof(double) * (count ? count : 1), h->stream));
+    BCHK(h, h->bb->own.zeroed(p, count, sizeof(double), h->stream));
     return APV_OK;
 }
 
@@ -844,28 +846,6 @@ hipError_t apv_launch_norm2(int n, int count, const double* const* d_mats, doubl
 void apv_bb_free(apv_handle* h) {
     apv_bb* s = h->bb;
     if (!s) return;
-    double* bufs[] = {s->rir[0], s->rir[1], s->trir[0], s->trir[1], s->xhist[0][0], s->xhist[0][1], s->xhist[1][0],
-                      s->xhist[1][1], s->xin, s->resp_all, s->ov_all, s->stats_all, s->pspec_all,
-                      s->inblk, s->spec, s->R, s->r, s->U, s->lam, s->w,
-                      s->fspec, s->inspec, s->outov, s->out, s->G2, s->G2T, s->Wgt[0], s->Wgt[1], s->nrm,
-                      s->g_xin, s->g_RA, s->g_RB, s->g_U, s->g_lam, s->g_r, s->g_w, s->g_nrm, s->g_inspec, s->spec_out, s->g_out};
-    for (double* b : bufs)
-        if (b) (void)hipFree(b);
-    if (s->g_pin) (void)hipHostFree(s->g_pin);
-    if (s->g_pin_in) (void)hipHostFree(s->g_pin_in);
-    if (s->d_ranks) (void)hipFree(s->d_ranks);
-    if (s->pin_in) (void)hipHostFree(s->pin_in);
-    if (s->pin_out) (void)hipHostFree(s->pin_out);
-    if (s->front) (void)hipStreamDestroy(s->front);
-    if (s->copy) (void)hipStreamDestroy(s->copy);
-    if (s->front2) (void)hipStreamDestroy(s->front2);
-    if (s->ev_ring) (void)hipEventDestroy(s->ev_ring);
-    if (s->ev_stat) (void)hipEventDestroy(s->ev_stat);
-    for (int i = 0; i < 2; ++i) {
-        if (s->ev_front[i]) (void)hipEventDestroy(s->ev_front[i]);
-        if (s->ev_back[i]) (void)hipEventDestroy(s->ev_back[i]);
-        if (s->ev_out[i]) (void)hipEventDestroy(s->ev_out[i]);
-    }
     apv_live_free(s->live);
     delete s;
     h->bb = nullptr;
@@ -914,9 +894,10 @@ int apv_bb_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const dou
     if (c.n_zones < 1 || c.n_zones > 3) return apv_fail(h, APV_ERR_ARG, "n_zones is a bit mask: 1 = A, 2 = B, 3 = both");
     BCHK(h, hipSetDevice(h->device));
     apv_bb_free(h);
-    apv_bb* s = new apv_bb();
-    std::memset(static_cast<void*>(s), 0, sizeof(apv_bb));
+    apv_bb* s = new apv_bb();                               // value-initialised: every scalar, pointer and array member starts at zero
     h->bb = s;
+    // an init that fails from here on leaves no half-built stream behind
+    struct Guard { apv_handle* h; bool ok; ~Guard() { if (!ok) apv_bb_free(h); } } built{h, false};
     const int nsol = (int)ranks.size();
     s->N = N; s->H = H; s->K = N / 2 + 1; s->L = L; s->M = M; s->C = L * M; s->P = rir_len; s->J = J; s->S = S; s->V = nsol;
     s->n = n; s->zones = c.n_zones; s->pad = apv_fir_pad_f64();
@@ -931,7 +912,7 @@ int apv_bb_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const dou
     s->out_group = c.out_layout == 1 ? L : 0;
     s->max_rank = ranks.back();
     s->full_valid = 1;
-    BCHK(h, hipMalloc((void**)&s->d_ranks, sizeof(int) * nsol));
+    BCHK(h, s->own.device(&s->d_ranks, sizeof(int) * nsol));
     BCHK(h, hipMemcpyAsync(s->d_ranks, ranks.data(), sizeof(int) * nsol, hipMemcpyHostToDevice, h->stream));
     BCHK(h, hipStreamSynchronize(h->stream));
     const int C = s->C, P = s->P, K = s->K;
@@ -987,8 +968,8 @@ int apv_bb_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const dou
     if ((rc = dalloc(h, &s->inspec, (size_t)2 * K * 2))) return rc;
     if ((rc = dalloc(h, &s->outov, (size_t)s->n_out * N))) return rc;
     if ((rc = dalloc(h, &s->out, (size_t)s->n_out * H))) return rc;
-    BCHK(h, hipHostMalloc((void**)&s->pin_in, sizeof(double) * 2 * H, hipHostMallocDefault));
-    BCHK(h, hipHostMalloc((void**)&s->pin_out, sizeof(double) * (size_t)s->n_out * H, hipHostMallocDefault));
+    BCHK(h, s->own.pinned(&s->pin_in, sizeof(double) * 2 * H));
+    BCHK(h, s->own.pinned(&s->pin_out, sizeof(double) * (size_t)s->n_out * H));
     // target filter spectra: the Python class uses the zone-A reference for both A_t and B_t (apvast.py:389-390, 418,
     // 422), the MATLAB class one reference per zone (apVast.m:597-602)
     std::vector<double> tg((size_t)2 * L * K * 2, 0.0);
@@ -1005,6 +986,7 @@ int apv_bb_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const dou
                            h->stream));
     BCHK(h, apv_stft_prepare(N, 1));
     BCHK(h, hipStreamSynchronize(h->stream));
+    built.ok = true;
     return APV_OK;
 }
 
@@ -1320,10 +1302,7 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
                  z_insp = (size_t)G * 2 * K * 2, z_out = (size_t)G * s->n_out * H;
     if (s->grp < G) {
         double** bufs[] = {&s->g_xin, &s->g_RA, &s->g_RB, &s->g_U, &s->g_lam, &s->g_r, &s->g_w, &s->g_nrm, &s->g_inspec, &s->g_out};
-        for (double** b : bufs) {
-            if (*b) (void)hipFree(*b);
-            *b = nullptr;
-        }
+        for (double** b : bufs) s->own.release(*b);
         s->grp = 0;
         int rc;
         if ((rc = dalloc(h, &s->g_xin, 2 * z_xin))) return rc;
@@ -1336,23 +1315,22 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
         if ((rc = dalloc(h, &s->g_nrm, 2 * z_nrm))) return rc;
         if ((rc = dalloc(h, &s->g_inspec, 2 * z_insp))) return rc;
         if ((rc = dalloc(h, &s->g_out, 2 * z_out))) return rc;
-        if (s->g_pin_in) (void)hipHostFree(s->g_pin_in);
-        s->g_pin_in = nullptr;
-        BCHK(h, hipHostMalloc((void**)&s->g_pin_in, sizeof(double) * 2 * z_xin, hipHostMallocDefault));
+        s->own.release(s->g_pin_in);
+        BCHK(h, s->own.pinned(&s->g_pin_in, sizeof(double) * 2 * z_xin));
         if (!s->spec_out && (rc = dalloc(h, &s->spec_out, (size_t)s->n_out * K * 2))) return rc;
         if (!s->front) {
-            BCHK(h, hipStreamCreateWithFlags(&s->front, hipStreamNonBlocking));
+            BCHK(h, s->own.stream(&s->front, hipStreamNonBlocking));
             // a copy stream of its own only where a group's outputs are large enough for the next group's solve to notice the
             // transfer (84 MB at the reference's test parameters; 131 KB at cfg1: there the copy rides on the handle's stream --
             // every stream fewer is one fewer to share the runtime's few hardware queues with)
-            if (sizeof(double) * (size_t)G * s->n_out * s->H >= ((size_t)4 << 20)) BCHK(h, hipStreamCreateWithFlags(&s->copy, hipStreamNonBlocking));
-            BCHK(h, hipStreamCreateWithFlags(&s->front2, hipStreamNonBlocking));
-            BCHK(h, hipEventCreateWithFlags(&s->ev_ring, hipEventDisableTiming));
-            BCHK(h, hipEventCreateWithFlags(&s->ev_stat, hipEventDisableTiming));
+            if (sizeof(double) * (size_t)G * s->n_out * s->H >= ((size_t)4 << 20)) BCHK(h, s->own.stream(&s->copy, hipStreamNonBlocking));
+            BCHK(h, s->own.stream(&s->front2, hipStreamNonBlocking));
+            BCHK(h, s->own.event(&s->ev_ring, hipEventDisableTiming));
+            BCHK(h, s->own.event(&s->ev_stat, hipEventDisableTiming));
             for (int i = 0; i < 2; ++i) {
-                BCHK(h, hipEventCreateWithFlags(&s->ev_front[i], hipEventDisableTiming));
-                BCHK(h, hipEventCreateWithFlags(&s->ev_back[i], hipEventDisableTiming));
-                BCHK(h, hipEventCreateWithFlags(&s->ev_out[i], hipEventDisableTiming));
+                BCHK(h, s->own.event(&s->ev_front[i], hipEventDisableTiming));
+                BCHK(h, s->own.event(&s->ev_back[i], hipEventDisableTiming));
+                BCHK(h, s->own.event(&s->ev_out[i], hipEventDisableTiming));
             }
         }
         BCHK(h, hipStreamSynchronize(st));            // the zero fills
@@ -1369,10 +1347,9 @@ int apv_bb_process_signal(apv_handle* h, int32_t n_hops, const double* h_in_A, c
     const size_t ngrp = og > 0 ? (size_t)s->n_out / og : 1, HL = (size_t)H * (og > 0 ? og : s->n_out);
     const bool direct = host_is_pinned(h_out, sizeof(double) * (size_t)n_hops * s->n_out * H, true);
     if (!direct && s->g_pin_cap < z_out) {
-        if (s->g_pin) (void)hipHostFree(s->g_pin);
-        s->g_pin = nullptr;
+        s->own.release(s->g_pin);
         s->g_pin_cap = 0;
-        BCHK(h, hipHostMalloc((void**)&s->g_pin, sizeof(double) * 2 * z_out, hipHostMallocDefault));
+        BCHK(h, s->own.pinned(&s->g_pin, sizeof(double) * 2 * z_out));
         s->g_pin_cap = z_out;
     }
     hipStream_t fs = s->front;
@@ -1567,11 +1544,9 @@ int apv_bb_set_perceptual(apv_handle* h, int32_t n_channels, const double* h_G2,
     }
     if (!h_G2 || n_channels > 512 || (normalisation != 0 && normalisation != 1)) return apv_fail(h, APV_ERR_ARG, "bad perceptual tables");
     const int K = s->K;
-    double* old[] = {s->G2, s->G2T, s->Wgt[0], s->Wgt[1]};
-    for (double* b : old)
-        if (b) (void)hipFree(b);
-    s->G2 = s->G2T = nullptr;
-    s->Wgt[0] = s->Wgt[1] = nullptr;
+    s->own.release(s->G2);
+    s->own.release(s->G2T);
+    for (int z = 0; z < 2; ++z) s->own.release(s->Wgt[z]);
     std::vector<double> gt((size_t)n_channels * K);
     for (int k = 0; k < K; ++k)
         for (int i = 0; i < n_channels; ++i) gt[(size_t)i * K + k] = h_G2[(size_t)k * n_channels + i];
@@ -1596,14 +1571,11 @@ int apv_predict_pressure(apv_handle* h, int32_t T, int32_t L, int32_t M, int32_t
     if (T < 0 || L < 1 || M < 1 || M > 256 || P < 1) return apv_fail(h, APV_ERR_ARG, "predict_pressure: bad sizes (M <= 256)");
     if (T == 0) return APV_OK;
     BCHK(h, hipSetDevice(h->device));
-    struct Tmp {
-        double* p[3] = {nullptr, nullptr, nullptr};
-        ~Tmp() { for (double* q : p) if (q) (void)hipFree(q); }
-    } tmpbufs;                                              // freed on every way out
-    double*& dx = tmpbufs.p[0]; double*& dr = tmpbufs.p[1]; double*& dout = tmpbufs.p[2];
-    BCHK(h, hipMalloc((void**)&dx, sizeof(double) * (size_t)T * L));
-    BCHK(h, hipMalloc((void**)&dr, sizeof(double) * (size_t)P * L * M));
-    BCHK(h, hipMalloc((void**)&dout, sizeof(double) * (size_t)T * M));
+    ApvOwned tmp;                                           // freed on every way out
+    double *dx = nullptr, *dr = nullptr, *dout = nullptr;
+    BCHK(h, tmp.device(&dx, sizeof(double) * (size_t)T * L));
+    BCHK(h, tmp.device(&dr, sizeof(double) * (size_t)P * L * M));
+    BCHK(h, tmp.device(&dout, sizeof(double) * (size_t)T * M));
     BCHK(h, hipMemcpyAsync(dx, h_x, sizeof(double) * (size_t)T * L, hipMemcpyHostToDevice, h->stream));
     BCHK(h, hipMemcpyAsync(dr, h_rir, sizeof(double) * (size_t)P * L * M, hipMemcpyHostToDevice, h->stream));
     const int tpb = 256 / M;
@@ -1639,20 +1611,16 @@ int apv_vast_static(apv_handle* h, int32_t Nb, int32_t Nd, int32_t P, int32_t L,
     for (int m = 0; m < Nb; ++m)                                                   // target: delayed reference RIR (vast.m:59)
         for (int q = modeling_delay; q < P && J + q < S; ++q)
             td[(size_t)m * S + J + q] = h_gB[((size_t)m * P + (q - modeling_delay)) * L + reference_index];
-    struct Tmp {
-        double* p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Tmp() { for (double* q : p) if (q) (void)hipFree(q); }
-    } tmpbufs;                                              // freed on every way out
-    double*& dsb = tmpbufs.p[0]; double*& dsd = tmpbufs.p[1]; double*& dtd = tmpbufs.p[2]; double*& dR = tmpbufs.p[3];
-    double*& dr = tmpbufs.p[4]; double*& dU = tmpbufs.p[5]; double*& dl = tmpbufs.p[6]; double*& dw = tmpbufs.p[7];
-    BCHK(h, hipMalloc((void**)&dsb, sizeof(double) * sb.size()));
-    BCHK(h, hipMalloc((void**)&dsd, sizeof(double) * sd.size()));
-    BCHK(h, hipMalloc((void**)&dtd, sizeof(double) * td.size()));
-    BCHK(h, hipMalloc((void**)&dR, sizeof(double) * 2 * (size_t)n * n));
-    BCHK(h, hipMalloc((void**)&dr, sizeof(double) * n));
-    BCHK(h, hipMalloc((void**)&dU, sizeof(double) * (size_t)n * n));
-    BCHK(h, hipMalloc((void**)&dl, sizeof(double) * n));
-    BCHK(h, hipMalloc((void**)&dw, sizeof(double) * (size_t)V * n));
+    ApvOwned tmp;                                           // freed on every way out
+    double *dsb = nullptr, *dsd = nullptr, *dtd = nullptr, *dR = nullptr, *dr = nullptr, *dU = nullptr, *dl = nullptr, *dw = nullptr;
+    BCHK(h, tmp.device(&dsb, sizeof(double) * sb.size()));
+    BCHK(h, tmp.device(&dsd, sizeof(double) * sd.size()));
+    BCHK(h, tmp.device(&dtd, sizeof(double) * td.size()));
+    BCHK(h, tmp.device(&dR, sizeof(double) * 2 * (size_t)n * n));
+    BCHK(h, tmp.device(&dr, sizeof(double) * n));
+    BCHK(h, tmp.device(&dU, sizeof(double) * (size_t)n * n));
+    BCHK(h, tmp.device(&dl, sizeof(double) * n));
+    BCHK(h, tmp.device(&dw, sizeof(double) * (size_t)V * n));
     BCHK(h, hipMemcpyAsync(dsb, sb.data(), sizeof(double) * sb.size(), hipMemcpyHostToDevice, st));
     BCHK(h, hipMemcpyAsync(dsd, sd.data(), sizeof(double) * sd.size(), hipMemcpyHostToDevice, st));
     BCHK(h, hipMemcpyAsync(dtd, td.data(), sizeof(double) * td.size(), hipMemcpyHostToDevice, st));

@@ -504,6 +504,9 @@ int  apv_comm_barrier(apv_handle* h);
  * the order-16 update runs its diagnostic instantiation, in which lane 0 of every bin's wave stores the shader clock (s_memtime)
  * at the stage boundaries; NULL switches it off again.  The stamps go to this buffer only; no result depends on them. */
 int  apv_debug_set_stamps(apv_handle* h, void* d_stamps);
+/* Diagnostics (the leak checks of tests/test_gpu_stream_lifecycle.py): what the stream states and the scratch of running calls of
+ * this process hold now: {device buffers, page-locked blocks, events, streams}.  The handle's own workspaces are not counted. */
+int  apv_debug_live_resources(int32_t counts[4]);
 /* hipDeviceSynchronize on the handle's device, and what that device is */
 int  apv_device_sync(apv_handle* h);
 int  apv_device_info(apv_handle* h, char name_out[128], int32_t* n_cus, int32_t* clock_mhz);
