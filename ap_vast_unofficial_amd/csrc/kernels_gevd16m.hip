@@ -45,15 +45,47 @@ template <int CTRL> __device__ __forceinline__ void tp_dpp_add(float& v) {
 }
 // sum over the four lanes of a quad (one matrix row), in all of them: quad_perm [1,0,3,2] and [2,3,0,1]
 __device__ __forceinline__ float tp_sum_quad(float v) { tp_dpp_add<0xB1>(v); tp_dpp_add<0x4E>(v); return v; }
-// sum over the sixteen quads of a value every lane of a quad holds, in all lanes, on the VALU: row_ror 8 and 4 inside a 16-lane
-// row, v_permlane16_swap and v_permlane32_swap across rows
+// sum over the sixteen quads of a value every lane of a quad holds, as a wave-uniform scalar: row_ror 8 and 4 inside a 16-lane
+// row, then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3 (the rows outside the mask keep their value:
+// destination and source are one register), which leaves the total in lane 63, and one v_readlane_b32.  Both users want the
+// value in a scalar register; delivering it to all 64 lanes took two v_permlane swaps with a move and an add each.  The DPP
+// combiner does not produce the masked form, so the two adds are assembly, and they carry their own two wait states in front
+// of a DPP read of a VALU result.
 __device__ __forceinline__ float tp_sum_quads(float v) {
     tp_dpp_add<0x128>(v);                                                                          // row_ror:8
     tp_dpp_add<0x124>(v);                                                                          // row_ror:4
-    const auto r16 = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
-    v = __int_as_float((int)r16[0]) + __int_as_float((int)r16[1]);
-    const auto r32 = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(v), (unsigned)__float_as_int(v), false, false);
-    return __int_as_float((int)r32[0]) + __int_as_float((int)r32[1]);
+    asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(v));
+    return tp_lane(v, 63);
+}
+// Complex multiply-accumulate on (re, im) pairs with the swap and the sign of the imaginary unit as operand modifiers of
+// v_pk_fma_f32: acc += (i z) s.y = (-z.y s.y, z.x s.y).  With acc += z s.x (plain source, the compiler folds the broadcast and
+// a negation of z into op_sel_hi and neg_lo / neg_hi) it makes acc += z s; with acc -= z s.x it makes acc -= z conj(s).  The
+// compiler does not fold the swap-and-negate form, hence the assembly.  Callers end an accumulation that feeds a DPP add with a
+// compiler-emitted instruction: the hazard recogniser does not count wait states after an asm statement.
+__device__ __forceinline__ void tp_fma_iy(f2v& acc, f2v z, f2v s) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "+v"(acc) : "v"(z), "v"(s));
+}
+// v in the lanes of a compile-time lane mask, zero in the others: one v_cndmask_b32 on a mask in a scalar pair.  The rows a
+// reflector acts on are known once the reflector loop is unrolled; as a test of the row index every mask cost a v_cmp, and the
+// fifteen of them, scheduled early, filled the scalar file until masks were spilled into lanes of a VGPR.  The mask is `bits`
+// shifted up by `sh` lanes, formed by s_lshl_b64 from an inline constant: handed over as a 64-bit constant it came out as an
+// s_mov_b64 with a 32-bit literal, which is right only for the masks whose upper half is the literal's extension.
+__device__ __forceinline__ unsigned long long tp_lanes(long long bits, int sh) {
+    unsigned long long m;
+    if (bits == -1) asm("s_lshl_b64 %0, -1, %1" : "=s"(m) : "s"(sh) : "scc");
+    else asm("s_lshl_b64 %0, 15, %1" : "=s"(m) : "s"(sh) : "scc");
+    return m;
+}
+__device__ __forceinline__ float tp_keep(float v, unsigned long long mask) {
+    float r;
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(v), "s"(mask));
+    return r;
+}
+__device__ __forceinline__ f2v tp_mul_iy(f2v z, f2v s) {                                           // (i z) s.y
+    f2v r;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,1] neg_lo:[1,0]" : "=v"(r) : "v"(z), "v"(s));
+    return r;
 }
 // The wide multisection step's votes: nb_m = the number of lanes whose Sturm count is <= m (one v_cmp into a scalar pair and a
 // scalar population count) goes into lane m of nbv, m = M .. 15 (v_writelane_b32 with the lane as an immediate; the compiler has
@@ -104,32 +136,38 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
     // modulus ||x|| goes on (e[k], and e2[k] = n^2 for the Sturm recurrence).  The phases are put back at the end:
     // diag(delta)^H T diag(delta) is real with delta_0 = 1, delta_{k+1} = -delta_k phi_k, and Q's column m is scaled by delta_m.
     // u needs no scaling (rows beyond k+1 take the raw column entry) and a column with nothing below alpha no special case
-    // (u_0 = 2 alpha, H_k a sign flip); a zero column gets gamma = 0.
+    // (u_0 = 2 alpha, H_k a sign flip: the last reflector is compiled as that); a zero column gets gamma = 0.
     // Lane (i, jq) holds A[i][jq + 4 t] and Q[i][jq + 4 t].  The rank-2 updates run on whole rows: rows and columns <= k only
     // collect garbage that is never read again (u is zero there).
-    f2v a[4], q[4], dq[4];                                                 // dq[t]: delta of column jq + 4 t
+    // delta_m is the same in every lane and wanted once, at the end, by the lanes of column m: it waits in LDS (the first 32 floats
+    // of fX, free until the inverse iteration; one wave, whose LDS accesses execute in order), not in eight registers per lane
+    f2v a[4], q[4];
+    f2v* const sdel = reinterpret_cast<f2v*>(fX);
+    sdel[0] = (f2v){1.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const Cx<TS> c = sA[i * LD + jq + 4 * t];
         a[t] = (f2v){scale_to_f32(c.x, sexp), scale_to_f32(c.y, sexp)};
         q[t] = (f2v){(jq + 4 * t == i) ? 1.f : 0.f, 0.f};
-        dq[t] = (f2v){1.f, 0.f};
     }
     // u and w are formed once per row (quad i: A[i][k] by a quad broadcast) and every lane fetches the entries of its own columns
     // jq + 4 t from quad jq + 4 t (ds_bpermute: one crossbar trip each, no LDS storage, no barrier); ||x||^2 and u^H A u are summed
-    // over the quads on the VALU.
+    // over the quads on the VALU into a scalar register.
     float e[N - 1], e2[N - 1];                                             // |sub-diagonal| and its square (wave-uniform)
     float dlr = 1.f, dli = 0.f;                                            // delta_k (the same in every lane)
 #pragma unroll
-    for (int k = 0; k < N - 1; ++k) {
+    for (int k = 0; k < N - 2; ++k) {
         const int t0 = (k + 1) >> 2;                                       // slots 0 .. t0-1 lie in columns <= k: u is zero there
         const int k1 = k + 1, tk = k >> 2, jk = k & 3;
         // A[i][k] to every lane of quad i
         const float akx = tp_quad_bcast(a[tk].x, jk), aky = tp_quad_bcast(a[tk].y, jk);
         // n^2 and alpha from the very column entries u is made of (row k is their conjugate only up to the rounding of the
-        // updates, and 1e-7 ||A|| is 1e-5 of a small column: H_k would be that far from unitary).  The quads of the rows <= k
-        // add 1e-31 each: e2 is never zero (0 * inf in the Sturm recurrence would be NaN), at no instruction.
-        const float n2 = uniform_scalar(tp_sum_quads((i > k) ? fmaf(akx, akx, aky * aky) : 1e-31f));
+        // updates, and 1e-7 ||A|| is 1e-5 of a small column: H_k would be that far from unitary).  Every quad adds 1e-31 (the
+        // addend of an FMA): e2 is never zero (0 * inf in the Sturm recurrence would be NaN), at no instruction.
+        // the column below the diagonal: zero in the rows <= k (quads 0 .. k)
+        const unsigned long long low = tp_lanes(-1, 4 * k1);
+        const float bx = tp_keep(akx, low), by = tp_keep(aky, low);
+        const float n2 = tp_sum_quads(fmaf(bx, bx, fmaf(by, by, 1e-31f)));
         const float alr = tp_lane(akx, 4 * k1), ali = tp_lane(aky, 4 * k1);
         // the scalar chain: two v_rsq_f32 and one reciprocal.  1/|alpha| and gamma take a Newton step: errors of 1 ulp in all
         // three scalars leave H_k unitary to 1e-7 still, but coherently over the whole matrix, and cost 0.2 % of the bench bins
@@ -139,36 +177,40 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
         const float ra = rsq_full(fmaxf(a2, 1e-36f));
         const bool pha = a2 > 1e-36f;
         const float phr = pha ? alr * ra : 1.f, phi = pha ? ali * ra : 0.f;
-        const float gam = n2 > 4e-30f ? rcp_full(fmaf(nrm, a2 * ra, n2)) : 0.f;
-        const float u0r = fmaf(phr, nrm, alr), u0i = fmaf(phi, nrm, ali);
+        // n2 is a non-negative float in a scalar register: it orders as its bit pattern, and the test runs on the scalar unit
+        const float gam = __float_as_uint(n2) > __builtin_bit_cast(unsigned, 4e-30f) ? rcp_full(fmaf(nrm, a2 * ra, n2)) : 0.f;
         e[k] = uniform_scalar(nrm);
         e2[k] = n2;
-        // u_i in quad i, then this lane's columns from quads jq + 4 t
-        const CF vi = (i > k1) ? mk<float>(akx, aky) : (i == k1) ? mk<float>(u0r, u0i) : mk<float>(0.f, 0.f);
+        // u_i in quad i: the column entry, plus phi ||x|| in row k + 1 (whose entry is alpha itself), zero in the rows <= k.  One
+        // masked ||x|| and two FMAs: straight-line code (the nested select on the pair compiled to a branch over the quads, and a
+        // packed operation scheduled across it lost its operand modifiers).  Then this lane's columns from quads jq + 4 t
+        const float un = tp_keep(nrm, tp_lanes(15, 4 * k1));
+        const CF vi = mk<float>(fmaf(phr, un, bx), fmaf(phi, un, by));
         f2v vj[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (t < t0) continue;
             vj[t] = (f2v){tp_from(vi.x, 4 * (jq + 4 * t)), tp_from(vi.y, 4 * (jq + 4 * t))};
         }
-        // delta_{k+1} = -delta_k phi_k, kept by the lanes that hold column k+1 (off the chain: it fills the permutes' wait)
+        // delta_{k+1} = -delta_k phi_k (off the chain: it fills the permutes' wait)
         {
             const float ndr = fmaf(dli, phi, -dlr * phr), ndi = -fmaf(dlr, phi, dli * phr);
             dlr = ndr; dli = ndi;
-            if (jq == (k1 & 3)) dq[k1 >> 2] = (f2v){dlr, dli};
+            sdel[k1] = (f2v){dlr, dli};
         }
-        // A u and Q u as sums of a[t] u.x and of a[t] u.y (packed, no swap and no negation per slot), put together once
-        f2v px = {0.f, 0.f}, py = {0.f, 0.f}, ux = {0.f, 0.f}, uy = {0.f, 0.f};
+        // A u and Q u, one complex accumulator each: per slot acc += a[t] u.x and acc += (i a[t]) u.y, the operands read as they are
+        // (the first slot multiplies: no zero to materialise; the last instruction of each chain is the compiler's, see tp_fma_iy)
+        f2v p, uq;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (t < t0) continue;
-            const f2v vx = {vj[t].x, vj[t].x}, vy = {vj[t].y, vj[t].y};
-            px = __builtin_elementwise_fma(a[t], vx, px);
-            py = __builtin_elementwise_fma(a[t], vy, py);
-            ux = __builtin_elementwise_fma(q[t], vx, ux);
-            uy = __builtin_elementwise_fma(q[t], vy, uy);
+            const f2v vx = {vj[t].x, vj[t].x};
+            if (t == t0) { p = tp_mul_iy(a[t], vj[t]); uq = tp_mul_iy(q[t], vj[t]); }
+            else { tp_fma_iy(p, a[t], vj[t]); tp_fma_iy(uq, q[t], vj[t]); }
+            p = __builtin_elementwise_fma(a[t], vx, p);
+            uq = __builtin_elementwise_fma(q[t], vx, uq);
         }
-        float pr = px.x - py.y, pi = px.y + py.x, ur = ux.x - uy.y, ui = ux.y + uy.x;      // (A u)_i, (Q u)_i
+        float pr = p.x, pi = p.y, ur = uq.x, ui = uq.y;                                      // (A u)_i, (Q u)_i
         // four chains, stage by stage
         tp_dpp_add<0xB1>(pr); tp_dpp_add<0xB1>(pi); tp_dpp_add<0xB1>(ur); tp_dpp_add<0xB1>(ui);
         tp_dpp_add<0x4E>(pr); tp_dpp_add<0x4E>(pi); tp_dpp_add<0x4E>(ur); tp_dpp_add<0x4E>(ui);
@@ -183,27 +225,43 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
             if (t < t0) continue;
             wj[t] = (f2v){tp_from(wi.x, 4 * (jq + 4 * t)), tp_from(wi.y, 4 * (jq + 4 * t))};
         }
-        const f2v nu = {-vi.x, -vi.y}, nus = {-vi.y, vi.x}, nw = {-wi.x, -wi.y}, nws = {-wi.y, wi.x};
-        const f2v ntu = {-tu.x, -tu.y}, ntus = {-tu.y, tu.x};
+        const f2v uv = {vi.x, vi.y}, wv = {wi.x, wi.y};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (t < t0) continue;
-            // A -= u w^H + w u^H;  Q -= (gamma Q u) u^H
-            const f2v vx = {vj[t].x, vj[t].x}, vy = {vj[t].y, vj[t].y}, wx = {wj[t].x, wj[t].x}, wy = {wj[t].y, wj[t].y};
-            a[t] = __builtin_elementwise_fma(nu, wx, a[t]);
-            a[t] = __builtin_elementwise_fma(nus, wy, a[t]);
-            a[t] = __builtin_elementwise_fma(nw, vx, a[t]);
-            a[t] = __builtin_elementwise_fma(nws, vy, a[t]);
-            q[t] = __builtin_elementwise_fma(ntu, vx, q[t]);
-            q[t] = __builtin_elementwise_fma(ntus, vy, q[t]);
+            // A -= u w^H + w u^H;  Q -= (gamma Q u) u^H: acc -= z conj(s) is acc -= z s.x and acc += (i z) s.y
+            const f2v vx = {vj[t].x, vj[t].x}, wx = {wj[t].x, wj[t].x};
+            tp_fma_iy(a[t], uv, wj[t]);
+            a[t] = __builtin_elementwise_fma(-uv, wx, a[t]);
+            tp_fma_iy(a[t], wv, vj[t]);
+            a[t] = __builtin_elementwise_fma(-wv, vx, a[t]);                                  // the next reflector reads a[t] by DPP
+            tp_fma_iy(q[t], tu, vj[t]);
+            q[t] = __builtin_elementwise_fma(-tu, vx, q[t]);
         }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    {
+        // The last reflector is a sign.  The column below the diagonal is the single element alpha = A[15][14] (lane 62, slot 3),
+        // so u_0 = 2 alpha, gamma = 1 / (2 |alpha|^2) and H_14 = diag(1, ..., 1, -1): A[15][15] stays, Q's column 15 changes sign
+        // and delta_15 = -delta_14 phi.  The two signs cancel in Q diag(delta): the column is left alone and delta_15 =
+        // +delta_14 phi.  No products, no wave sum, no permute, no update; e2 stays non-zero.
+        const float alr = tp_lane(a[3].x, 62), ali = tp_lane(a[3].y, 62);
+        const float a2 = fmaf(alr, alr, ali * ali);
+        const float n2 = fmaxf(a2, 1e-31f);
+        const float ra = rsq_full(fmaxf(a2, 1e-36f));
+        const bool pha = a2 > 1e-36f;
+        const float phr = pha ? alr * ra : 1.f, phi = pha ? ali * ra : 0.f;
+        e[N - 2] = uniform_scalar(n2 * __builtin_amdgcn_rsqf(n2));
+        e2[N - 2] = uniform_scalar(n2);
+        sdel[N - 1] = (f2v){fmaf(-dli, phi, dlr * phr), fmaf(dlr, phi, dli * phr)};
     }
     float d[N];                                                            // diagonal (wave-uniform)
 #pragma unroll
     for (int m = 0; m < N; ++m) d[m] = uniform_scalar(tp_lane(a[m >> 2].x, 4 * m + (m & 3)));
 #pragma unroll
     for (int t = 0; t < 4; ++t) {                                          // Q diag(delta) to LDS for the back-transform
-        const f2v s = __builtin_elementwise_fma((f2v){-q[t].y, q[t].x}, (f2v){dq[t].y, dq[t].y}, q[t] * (f2v){dq[t].x, dq[t].x});
+        const f2v dq = sdel[jq + 4 * t];
+        const f2v s = __builtin_elementwise_fma((f2v){-q[t].y, q[t].x}, (f2v){dq.y, dq.y}, q[t] * (f2v){dq.x, dq.x});
         fQ[i * LDQ + jq + 4 * t] = mk<float>(s.x, s.y);
     }
     stamp(4);

@@ -6,6 +6,7 @@ over bins and in the kernel's order of operations:
      H = I - gamma u u^H with a real gamma (u the raw column, u_0 = alpha + alpha/|alpha| ||x||), Q accumulated as
      Q H_0 H_1 ... H_14; the sub-diagonal comes out complex, only its modulus goes on, and the phases delta_0 = 1,
      delta_{k+1} = -delta_k alpha_k/|alpha_k| scale Q's columns at the end: T = (Q diag delta)^H C (Q diag delta) is real.
+     The last reflector, H_14 = diag(1, ..., 1, -1), is taken as the sign it is: column 15 of Q and delta_15 keep theirs.
      ||x|| = n^2 rsq(n^2) carries a random error of up to 1 ulp, as the bare v_rsq_f32 does (ULP_NOISE=0: correctly
      rounded); 1/|alpha| and gamma take a Newton step in the kernel.  With bare instructions for all three the share of
      bins inside the one-step guard falls from 99.70 % to 99.53 %;
@@ -100,8 +101,19 @@ def tridiag(A, rng=None):
         # updates, H is unitary to 1e-5 only where the column is small, and 99.56 % of the bins pass the one-step guard)
         col = A[:, k + 1:, k]
         alpha = col[:, 0].copy()
-        n2 = (f32(1e-31 * (k + 1)) + (col.real * col.real + col.imag * col.imag).sum(1, dtype=f32)).astype(f32)
         a2 = (alpha.real * alpha.real + alpha.imag * alpha.imag).astype(f32)
+        if k == N - 2:
+            # the last reflector is a sign, H = diag(1, ..., 1, -1): A[15][15] stays, Q's column 15 and delta_15 both change
+            # sign, and the kernel leaves both alone (delta_15 = +delta_14 phi).  No products, no update.
+            n2 = np.maximum(a2, f32(1e-31))
+            e[:, k] = (n2 * ulp_noise(f32(1) / np.sqrt(n2), rng)).astype(f32)
+            e2[:, k] = n2
+            ra = (f32(1) / np.sqrt(np.maximum(a2, f32(1e-36)))).astype(f32)
+            phi = np.where(a2 > f32(1e-36), (alpha * ra).astype(np.complex64), np.complex64(1))
+            delta[:, k + 1] = (delta[:, k] * phi).astype(np.complex64)
+            break
+        # every one of the sixteen rows adds 1e-31 (the kernel: the addend of an FMA): e2 is never zero
+        n2 = (f32(16e-31) + (col.real * col.real + col.imag * col.imag).sum(1, dtype=f32)).astype(f32)
         nrm = (n2 * ulp_noise(f32(1) / np.sqrt(n2), rng)).astype(f32)
         ra = (f32(1) / np.sqrt(np.maximum(a2, f32(1e-36)))).astype(f32)     # a Newton step in the kernel
         pha = a2 > f32(1e-36)
