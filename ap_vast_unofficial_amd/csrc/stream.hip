@@ -22,6 +22,20 @@
 constexpr int CK_NB = 4;      // back streams of the chunked whole-signal path
 constexpr int CK_NS = 3;      // pinned staging slots (chunks) of that path
 
+// A measuring aid around one launch of the hop (statistics, projection, FIR synthesis): the events exist only where the stage's
+// environment switch is set, and run_hop reads them after every hop.
+struct StageTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};      // recorded in front of and behind the launch
+    double ms[2] = {0.0, 0.0};                  // {sum of its times in ms, hops timed}
+    hipError_t read() {
+        if (!ev[0]) return hipSuccess;
+        float t = 0.f;
+        const hipError_t e = hipEventElapsedTime(&t, ev[0], ev[1]);
+        if (e == hipSuccess) { ms[0] += t; ms[1] += 1.0; }
+        return e;
+    }
+};
+
 struct apv_stream {
     int N, H, K, L, M, C, P, nV, zones, pad;
     int f64;                      // precision of the whole front-end: RIRs, rings, spectra, overlap buffers, outputs
@@ -132,21 +146,19 @@ struct apv_stream {
                                   // the state "stat_window_fill".  Only win_low_rank reads it (which KERNEL solves an order-64 hop):
                                   // the ring position itself never enters a launch from the host
     // exponentially forgetting statistics (apv_stream_set_stat_forgetting): R <- fg_beta R + G per hop.  win_T stays 1; the
-    // accumulator is the one slot win_ring[z] [K][2 L^2 + L], and win_c128, win_RB / win_RD / win_r, win_ev / win_ms serve as above
+    // accumulator is the one slot win_ring[z] [K][2 L^2 + L], and win_c128, win_RB / win_RD / win_r, win_tm serve as above
     double fg_beta;               // 0: off
     int fg_no_gevd64;             // GevdParams::no_gevd64 of every hop and of apv_stream_get_statistics: see apv_stream_init
     // filter-length constraint (apv_stream_set_filter_taps, kernels_constrain.hip); taps = 0: off, nothing below exists
     int taps;                     // J
     void* wtaps[2];               // per zone program: [nV][J][L] real, the J taps of the hop's projected filters (precision of w)
-    hipEvent_t cf_ev[2];          // APV_FILTER_CONSTRAINT_TIMING (tools/bench_filter_constraint.py): events around the projection
-    double cf_ms[2];              // ... and {sum of its times in ms, hops timed}
+    StageTimer cf_tm;             // APV_FILTER_CONSTRAINT_TIMING (tools/bench_filter_constraint.py): the projection
     // FIR synthesis (apv_stream_set_synthesis, kernels_firsynth.hip); fir_synth = 0: off, nothing below exists
     int fir_synth;
     int fs_ref, fs_delay;         // the target paths: column reference_index_A, modeling_delay samples late
     void* fs_taps[2];             // per zone program that runs: [nV][J][L], the taps the next hop fades from (precision of w)
     void* fs_hist[2][2];          // [buf][signal][J - 1]: the newest input samples; buf = cur, like the input histories of K1
-    hipEvent_t fs_ev[2];          // APV_FIR_SYNTHESIS_TIMING (tools/bench_fir_synthesis.py): events around the synthesis launch
-    double fs_ms[2];              // ... and {sum of its times in ms, hops timed}
+    StageTimer fs_tm;             // APV_FIR_SYNTHESIS_TIMING (tools/bench_fir_synthesis.py): the synthesis launch
     // chunked whole-signal path of a constrained stream (process_signal_chunked_t; allocated by chunk_prepare for such a stream only)
     void* ck_taps[2];             // per zone program: [sig_chunk][nV][J][L], the taps of every hop of a chunk (ONE projection launch)
     void* ck_xrow[2][2];          // [chunk parity][signal]: [J - 1 samples before the chunk | sig_chunk H samples of the chunk], FIR synthesis
@@ -170,8 +182,7 @@ struct apv_stream {
     void* es_spec;                // [K][ev_sets ev_Mv] complex128: the hop's spectra, bin-major scratch
     double* es_tot;               // [ev_Z][3 ev_E + 1][K][ev_Mv]: |P|^2 summed over the hops
     int32_t sched[2];             // state "signal_schedule": hops of the last whole-signal call {through chunk launches, hop by hop}
-    hipEvent_t win_ev[2];         // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): events around the statistics launch
-    double win_ms[2];             // ... and {sum of its times in ms, hops timed}
+    StageTimer win_tm;            // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): the statistics launch
     std::vector<hipGraphExec_t> execs;
     std::vector<int32_t> h_status;
     ApvOwned own;                 // every buffer, pinned block, event and stream above: made through it, freed by it
@@ -179,11 +190,20 @@ struct apv_stream {
 
 namespace {
 
-#define SCHK(h, call)                                                                    \
+#define HIPCHK(h, call, what)                                                            \
     do {                                                                                 \
         hipError_t _e = (call);                                                          \
-        if (_e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
+        if (_e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string(what) + ": " + hipGetErrorString(_e)); \
     } while (0)
+#define SCHK(h, call) HIPCHK(h, call, #call)
+
+// the same inside the whole-signal path, whose callers add how far the call got (signal_bail)
+#define SIGCHK(h, call) HIPCHK(h, call, "apv_process_signal")
+
+// a launcher that failed: its own account of it where it gave one, else the runtime's
+int launch_fail(apv_handle* h, hipError_t e, const std::string& why) {
+    return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+}
 
 // `count` elements of `esz` bytes, zeroed, kept by the stream
 template <typename T>
@@ -278,6 +298,120 @@ static bool win_low_rank(const apv_handle* h) {
     return hops * s->M < s->L;
 }
 
+// ---- job tables: each is filled in one place, for one hop (per-hop path, pipeline) and for a chunk of hops alike ----
+
+// the zone programs that run, in zone order: z[0 .. nz)
+struct LiveZones {
+    int nz = 0, z[2];
+    explicit LiveZones(const apv_stream* s) {
+        for (int i = 0; i < 2; ++i)
+            if (s->zones & (1 << i)) z[nz++] = i;
+    }
+};
+
+// K1 by fast convolution, one launch for all six filter banks: the four response paths into the rows `resp`, the two target paths
+// into `tresp` (the rings, or a chunk's linear buffers); `xspec` holds the spectra of the two input signals
+struct K1Jobs {
+    const void *jh[6], *jx[6];
+    void* jr[6];
+    int jc[6];
+};
+static K1Jobs k1_jobs(const apv_stream* s, void* const* resp, void* const* tresp, const void* xspec) {
+    const size_t spec_bytes = ((size_t)s->fir_F / 2 + 1) * 2 * s->esz;      // one input spectrum
+    K1Jobs j;
+    for (int p = 0; p < 4; ++p) {
+        j.jh[p] = s->rirspec[path_zone(p)]; j.jx[p] = (const char*)xspec + spec_bytes * path_sig(p);
+        j.jr[p] = resp[p]; j.jc[p] = s->C;
+    }
+    for (int z = 0; z < 2; ++z) {
+        j.jh[4 + z] = s->trirspec[z]; j.jx[4 + z] = (const char*)xspec + spec_bytes * z;
+        j.jr[4 + z] = tresp[z]; j.jc[4 + z] = s->M;
+    }
+    return j;
+}
+
+// K2, every analysis transform in one launch: the live response paths, both targets, the two inputs, from the rows `resp`, `tresp`,
+// `inblk` into the spectra set `q` (a chunk: into its first hop's set, hop i's jhop elements further on)
+struct AnalysisJobs {
+    const void* jx[7];
+    void* jspec[7];
+    int jch[7], nj = 0;
+    long jsc[7], jsk[7], jhop[7];
+};
+static AnalysisJobs analysis_jobs(const apv_stream* s, void* const* resp, void* const* tresp, const void* inblk, const HopSpectra& q) {
+    const bool runA = s->zones & 1, runB = s->zones & 2;
+    const int K = s->K, M = s->M, C = s->C;
+    AnalysisJobs j;
+    int& nj = j.nj;
+    for (int p = 0; p < 4; ++p) {
+        const bool need = (p < 2) ? runA : runB;       // A->A, A->B feed zone program A; B->A, B->B feed B
+        if (!need) continue;
+        j.jx[nj] = resp[p]; j.jspec[nj] = q.X[p]; j.jch[nj] = C; j.jsc[nj] = s->xg; j.jsk[nj] = C;      // (xg, C): grouped when xg > 1
+        j.jhop[nj] = (long)s->Kp * C; ++nj;
+    }
+    for (int z = 0; z < 2; ++z) {
+        j.jx[nj] = tresp[z]; j.jspec[nj] = q.tspec[z]; j.jch[nj] = M; j.jsc[nj] = 1; j.jsk[nj] = M; j.jhop[nj] = (long)K * M; ++nj;
+    }
+    j.jx[nj] = inblk; j.jspec[nj] = q.inspec; j.jch[nj] = 2; j.jsc[nj] = K; j.jsk[nj] = 1; j.jhop[nj] = 2L * K; ++nj;
+    return j;
+}
+
+// Perceptual weighting of the spectra set `q` (nothing where it is off): weights from the UNWEIGHTED target spectra
+// (apvast.py:205), then spectra x weights (apvast.py:208-209, 258-262): A->A and B->A take zone A's curve, A->B and B->B zone B's
+static int enqueue_weighting(apv_handle* h, const HopSpectra& q, hipStream_t st) {
+    const apv_stream* s = h->st;
+    if (s->nch <= 0) return APV_OK;
+    const int K = s->K, L = s->L, M = s->M, C = s->C, f64 = s->f64;
+    const bool runA = s->zones & 1, runB = s->zones & 2;
+    for (int z = 0; z < 2; ++z)
+        SCHK(h, apv_launch_perceptual_weights(f64, K, M, s->nch, q.tspec[z], s->G2, s->G2T, s->Cs, s->Ca, s->Leff, s->N,
+                                              s->norm_mode, s->Wgt[z], st));
+    for (int p = 0; p < 4; ++p) {
+        const bool need = (p < 2) ? runA : runB;
+        if (need) SCHK(h, apv_launch_scale_spectra(f64, K, C, L, q.X[p], s->Wgt[path_zone(p)], st));
+    }
+    for (int z = 0; z < 2; ++z) SCHK(h, apv_launch_scale_spectra(f64, K, M, 1, q.tspec[z], s->Wgt[z], st));
+    return APV_OK;
+}
+
+// The fused solve (statistics and joint diagonalisation in one kernel) of both zone programs in ONE launch (blockIdx.y = zone;
+// K = N/2+1 bins alone cannot fill the chip): spectra `q`, filters to wz / lamz, status words [2][K] at `status`.  The caller adds
+// what belongs to its launch: yield_issue, no_gevd64, Lspill, and for a chunk n_hops and the hop_* strides.
+static GevdParams fused_gevd_params(const apv_handle* h, const HopSpectra& q, void* const* wz, void* const* lamz, int32_t* status) {
+    const apv_stream* s = h->st;
+    const bool runA = s->zones & 1, runB = s->zones & 2;
+    GevdParams p = apv_base_params(h);
+    const int first = runA ? 0 : 1;
+    p.x_c128 = s->f64;
+    p.x_group = s->xg;
+    p.XB = first ? q.X[3] : q.X[0];
+    p.XD = first ? q.X[2] : q.X[1];
+    p.d = q.tspec[first];
+    p.w = wz[first];
+    p.lam = lamz[first];
+    p.status = status + (size_t)first * s->K;
+    p.n_zones = (runA && runB) ? 2 : 1;
+    if (p.n_zones == 2) {
+        p.XB1 = q.X[3]; p.XD1 = q.X[2]; p.d1 = q.tspec[1];
+        p.w1 = wz[1]; p.lam1 = lamz[1]; p.status1 = status + s->K;
+    }
+    return p;
+}
+
+// FIR synthesis: what its per-hop and per-chunk launches share.  Per live zone program the taps to fade from (`prev`) and to
+// (`cur`), the signal it filters; the target paths (pure delays); the layout of the result.  The caller sets the input side
+// (xhist, xhop), `out` and, for a chunk, n_hops and the hop_* strides.
+static FirSynthArgs fir_synth_args(const apv_stream* s, void* const* prev, void* const* cur) {
+    FirSynthArgs a{};
+    const LiveZones lz(s);
+    for (int i = 0; i < lz.nz; ++i) { a.prev[i] = prev[lz.z[i]]; a.cur[i] = cur[lz.z[i]]; a.sig[i] = lz.z[i]; }
+    a.nz = lz.nz; a.nV = s->nV; a.L = s->L; a.J = s->taps; a.H = s->H;
+    a.n_tgt = 2; a.ref = s->fs_ref; a.delay = s->fs_delay;
+    a.sn = s->out_group > 0 ? s->L : 1;
+    a.sl = s->out_group > 0 ? 1 : s->H;
+    return a;
+}
+
 // Front half of a hop on stream `st`: pinned hop `pin_src` [2][H] -> input histories, response rings (K1), analysis
 // spectra of set `set` (K2, perceptual weighting).  Advances (ring_off, cur) on the host.  Pure enqueue: also used
 // under stream capture.
@@ -285,8 +419,7 @@ static bool win_low_rank(const apv_handle* h) {
 static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin_src, hipEvent_t set_free = nullptr) {
     apv_stream* s = h->st;
     const HopSpectra q = hop_spectra(s, set);
-    const int N = s->N, H = s->H, K = s->K, L = s->L, M = s->M, C = s->C, P = s->P, f64 = s->f64;
-    std::string why;
+    const int N = s->N, H = s->H, M = s->M, C = s->C, P = s->P, f64 = s->f64;
     // hop -> device, input history and input-block rings
     // the hop [A | B] is read by the input-update kernel straight from the pinned host staging (16 KB over PCIe inside a kernel
     // that has nothing else to do) instead of through a copy node of its own
@@ -300,23 +433,12 @@ static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin
     s->cur = nxt;
     // K1: RIR convolution into the response rings (one MFMA launch for all six filter banks)
     if (s->fir_F > 0) {
-        const size_t spec_bytes = ((size_t)s->fir_F / 2 + 1) * 2 * s->esz;
         if (s->fir_np > 1)
             SCHK(h, apv_launch_fir_input_spectra_parts(f64, s->fir_F, s->fir_np, s->xhist[s->cur][0], s->xhist[s->cur][1], s->xspec, st));
         else
             SCHK(h, apv_launch_fir_input_spectra(f64, s->fir_F, s->xhist[s->cur][0], s->xhist[s->cur][1], P - 1 + H, s->xspec, st));
-        const void *jh[6], *jx[6];
-        void* jr[6];
-        int jc[6];
-        for (int p = 0; p < 4; ++p) {
-            jh[p] = s->rirspec[path_zone(p)]; jx[p] = (const char*)s->xspec + spec_bytes * path_sig(p);
-            jr[p] = s->resp[p]; jc[p] = C;
-        }
-        for (int z = 0; z < 2; ++z) {
-            jh[4 + z] = s->trirspec[z]; jx[4 + z] = (const char*)s->xspec + spec_bytes * z;
-            jr[4 + z] = s->tresp[z]; jc[4 + z] = M;
-        }
-        SCHK(h, apv_launch_fir_fft_jobs(f64, s->fir_F, 6, jh, jx, jr, jc, P, H, N, s->ring_off, st, s->fir_np));
+        const K1Jobs j = k1_jobs(s, s->resp, s->tresp, s->xspec);
+        SCHK(h, apv_launch_fir_fft_jobs(f64, s->fir_F, 6, j.jh, j.jx, j.jr, j.jc, P, H, N, s->ring_off, st, s->fir_np));
     } else if (f64) {
         FirJobsD jobs{};
         for (int p = 0; p < 4; ++p) {
@@ -345,37 +467,12 @@ static int enqueue_front(apv_handle* h, hipStream_t st, int set, const void* pin
         apv_live_advance(s->live, 1);
     }
     // K2: analysis, bin-major output
-    const bool runA = s->zones & 1, runB = s->zones & 2;
     if (set_free) SCHK(h, hipStreamWaitEvent(st, set_free, 0));       // histories, rings and K1 above did not need the set
-    {
-        // every analysis transform of the hop in one launch: the live response paths, both targets, the two inputs
-        const void* jx[7];
-        void* jspec[7];
-        int jch[7], nj = 0;
-        long jsc[7], jsk[7];
-        for (int p = 0; p < 4; ++p) {
-            const bool need = (p < 2) ? runA : runB;       // A->A, A->B feed zone program A; B->A, B->B feed B
-            if (!need) continue;
-            jx[nj] = s->resp[p]; jspec[nj] = q.X[p]; jch[nj] = C; jsc[nj] = s->xg; jsk[nj] = C; ++nj;      // (xg, C): grouped when xg > 1
-        }
-        for (int z = 0; z < 2; ++z) { jx[nj] = s->tresp[z]; jspec[nj] = q.tspec[z]; jch[nj] = M; jsc[nj] = 1; jsk[nj] = M; ++nj; }
-        jx[nj] = s->inblk; jspec[nj] = q.inspec; jch[nj] = 2; jsc[nj] = K; jsk[nj] = 1; ++nj;
-        hipError_t e = apv_launch_stft_analysis_jobs(f64, N, nj, jx, jch, jspec, jsc, jsk, s->ring_off, st, &why);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
-    }
-    if (s->nch > 0) {
-        // weights from the UNWEIGHTED target spectra (apvast.py:205), then spectra x weights (apvast.py:208-209,
-        // 258-262): A->A and B->A take zone A's curve, A->B and B->B zone B's
-        for (int z = 0; z < 2; ++z)
-            SCHK(h, apv_launch_perceptual_weights(f64, K, M, s->nch, q.tspec[z], s->G2, s->G2T, s->Cs, s->Ca, s->Leff, N,
-                                                  s->norm_mode, s->Wgt[z], st));
-        for (int p = 0; p < 4; ++p) {
-            const bool need = (p < 2) ? runA : runB;
-            if (need) SCHK(h, apv_launch_scale_spectra(f64, K, C, L, q.X[p], s->Wgt[path_zone(p)], st));
-        }
-        for (int z = 0; z < 2; ++z) SCHK(h, apv_launch_scale_spectra(f64, K, M, 1, q.tspec[z], s->Wgt[z], st));
-    }
-    return APV_OK;
+    const AnalysisJobs j = analysis_jobs(s, s->resp, s->tresp, s->inblk, q);
+    std::string why;
+    hipError_t e = apv_launch_stft_analysis_jobs(f64, N, j.nj, j.jx, j.jch, j.jspec, j.jsc, j.jsk, s->ring_off, st, &why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    return enqueue_weighting(h, q, st);
 }
 
 // Evaluation stage of a hop on stream `st`, behind the synthesis that wrote the result buffer `obuf` and in front of its copy back:
@@ -396,7 +493,7 @@ static int enqueue_eval(apv_handle* h, hipStream_t st, const void* obuf) {
     a.n_sets = s->ev_sets; a.Pv = s->ev_Pv; a.H = H; a.L = L; a.Mv = s->ev_Mv;
     std::string why;
     hipError_t e = apv_launch_eval_pressure(s->f64, a, st, &why);
-    if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
     EvalAdvanceArgs adv{};
     adv.p = s->ev_p; adv.totals = s->ev_tot; adv.ctl = s->ev_ctl; adv.par = c;
     adv.old_hist = s->ev_hist[c ^ 1]; adv.new_hist = s->ev_hist[c];
@@ -409,7 +506,7 @@ static int enqueue_eval(apv_handle* h, hipStream_t st, const void* obuf) {
         sp.p = s->ev_p; sp.ring = s->es_ring; sp.spec = s->es_spec; sp.totals = s->es_tot;
         sp.ring_off = s->ring_off; sp.N = s->N; sp.H = H; sp.Z = s->ev_Z; sp.E = s->ev_E; sp.Mv = s->ev_Mv;
         e = apv_launch_eval_spectra(sp, st, &why);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+        if (e != hipSuccess) return launch_fail(h, e, why);
     }
     return APV_OK;
 }
@@ -436,187 +533,186 @@ static int eval_begin_call(apv_handle* h, int n_hops) {
     return APV_OK;
 }
 
-// How the whole-signal path runs the back half: which output-spectra / result buffers, an event to record once the
-// spectra set has been read for the last time (after K3), and a stream of its own for synthesis and copy back, which
-// start at that event.  The per-hop path takes the defaults.
+// Where the back half of a hop puts its results and how it is scheduled: the result buffer (samples, then status words) and the
+// output spectra; for the whole-signal path an event to record once the spectra set has been read for the last time (after K3),
+// and a stream of its own for synthesis and copy back, which start at that event.  The copy back goes to the pinned `pin_dst` of
+// the stages; none where that is null (chunked whole-signal path: one copy per chunk, by the caller).
 struct BackSchedule {
+    char* result;
+    char* ospec;
     int yield_issue = 0;      // GevdParams::yield_issue
-    int obuf = 0;
     hipEvent_t spectra_free = nullptr;
     hipStream_t tail_stream = nullptr;
     hipEvent_t copied = nullptr;
-    // chunked whole-signal path: the hop's own result and output-spectra slots (then `obuf` is not used) and no copy back per
-    // hop (one copy per chunk, by the caller)
-    void* result = nullptr;
-    void* ospec = nullptr;
-    bool no_copy = false;
     void* lspill = nullptr;   // GevdParams::Lspill of this launch (nullptr: the handle's d_Lspill)
-    bool skip_gevd = false;   // the filters are there already: the chunk's joint diagonalisations were one launch (enqueue_gevd_hops)
-    // chunked whole-signal path of a constrained stream: the projection of a whole chunk is one launch of the caller's
-    bool skip_constrain = false;   // ... so the filters are projected already
-    bool gevd_only = false;        // ... or will be: this call ends behind the joint diagonalisation (hop-by-hop regime, back streams)
+    BackSchedule(void* result_, void* ospec_) : result((char*)result_), ospec((char*)ospec_) {}
 };
 
-// Back half of a hop on stream `st`: spectra of set `set` -> per-bin filters (K5'-K10), output spectra (K3), synthesis
-// and overlap-add (K4); the emitted samples [n_out][H] and, behind them, the status words [2][K] land in pinned `pin_dst`.
-static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void* const* wz, void* const* lamz, void* pin_dst,
-                        const BackSchedule& sch = BackSchedule()) {
+// ---- the stages of the back half of a hop.  enqueue_back runs them in order; the chunked whole-signal path, which makes some of
+// them one launch per chunk, calls the others directly ----
+
+// Per-bin filters (K5'-K10) of both zone programs from the spectra `q`, on `st`: filters to wz / lamz, status words behind the
+// samples of the hop's result buffer.
+// per-bin update per zone program: A: bright A->A, dark A->B, target A;  B: bright B->B, dark B->A, target B
+static int back_solve(apv_handle* h, hipStream_t st, const HopSpectra& q, void* const* wz, void* const* lamz, const BackSchedule& sch) {
     apv_stream* s = h->st;
-    char* const obuf = static_cast<char*>(sch.result ? sch.result : (sch.obuf ? s->out1 : s->out));
-    char* const ospec = static_cast<char*>(sch.ospec ? sch.ospec : (sch.obuf ? s->outspec1 : s->outspec));
-    int32_t* const ostatus[2] = {reinterpret_cast<int32_t*>(obuf + hop_out_bytes(s)),
-                                 reinterpret_cast<int32_t*>(obuf + hop_out_bytes(s)) + s->K};
-    const int N = s->N, H = s->H, K = s->K, L = s->L, f64 = s->f64;
-    const size_t e2 = 2 * s->esz;
-    const bool runA = s->zones & 1, runB = s->zones & 2;
+    int32_t* const status = reinterpret_cast<int32_t*>(sch.result + hop_out_bytes(s));
+    const int K = s->K, L = s->L, f64 = s->f64;
     std::string why;
-    // per-bin update per zone program: A: bright A->A, dark A->B, target A;  B: bright B->B, dark B->A, target B
-    int oc = 0;     // output channel cursor
     if (explicit_stats(s)) {
         // statistics over the last win_T hops: this hop's Gram matrices into the ring and the window sums in one launch for both
         // zone programs (forgetting: beta x accumulator + Gram matrices, likewise one launch), then the joint diagonalisation from
         // explicit R_B, R_D, r (the launch apv_gevd_vast_dev makes), per zone
         const void *xb[2], *xd[2], *dd[2];
         void *ring[2], *RB[2], *RD[2], *rr[2];
-        int zlist[2], nz = 0;
-        for (int z = 0; z < 2; ++z) {
-            if (!(z ? runB : runA)) continue;
-            xb[nz] = z ? q.X[3] : q.X[0]; xd[nz] = z ? q.X[2] : q.X[1]; dd[nz] = q.tspec[z];
-            ring[nz] = s->win_ring[z]; RB[nz] = s->win_RB[z]; RD[nz] = s->win_RD[z]; rr[nz] = s->win_r[z];
-            zlist[nz++] = z;
+        const LiveZones lz(s);
+        const int nz = lz.nz;
+        for (int i = 0; i < nz; ++i) {
+            const int z = lz.z[i];
+            xb[i] = z ? q.X[3] : q.X[0]; xd[i] = z ? q.X[2] : q.X[1]; dd[i] = q.tspec[z];
+            ring[i] = s->win_ring[z]; RB[i] = s->win_RB[z]; RD[i] = s->win_RD[z]; rr[i] = s->win_r[z];
         }
-        if (s->win_ev[0]) SCHK(h, hipEventRecord(s->win_ev[0], st));
+        if (s->win_tm.ev[0]) SCHK(h, hipEventRecord(s->win_tm.ev[0], st));
         if (s->fg_beta > 0.0) SCHK(h, apv_launch_statforget(f64, s->win_c128, K, s->M, L, s->fg_beta, nz, xb, xd, dd, ring, RB, RD, rr, st));
         else SCHK(h, apv_launch_statwin(f64, s->win_c128, K, s->M, L, s->win_T, nz, xb, xd, dd, ring, RB, RD, rr, s->win_ctr, st));
-        if (s->win_ev[1]) SCHK(h, hipEventRecord(s->win_ev[1], st));
+        if (s->win_tm.ev[1]) SCHK(h, hipEventRecord(s->win_tm.ev[1], st));
         for (int i = 0; i < nz; ++i) {
-            const int z = zlist[i];
+            const int z = lz.z[i];
             GevdParams p = apv_base_params(h);
             p.RB = s->win_RB[z]; p.RD = s->win_RD[z]; p.r = s->win_r[z];
-            p.w = wz[z]; p.lam = lamz[z]; p.status = ostatus[z];
+            p.w = wz[z]; p.lam = lamz[z]; p.status = status + (size_t)z * K;
             p.n_zones = 1;
             p.no_gevd64 = s->fg_beta > 0.0 ? s->fg_no_gevd64 : win_low_rank(h);
             if (sch.lspill) p.Lspill = sch.lspill;
             hipError_t e = apv_launch_gevd(p, s->win_c128 ? APV_F64 : APV_F32, false, st, &why, h->rank_list.data());
-            if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+            if (e != hipSuccess) return launch_fail(h, e, why);
         }
-    } else if (!sch.skip_gevd) {
-        // both zone programs go out in ONE launch (blockIdx.y = zone): K = N/2+1 bins alone cannot fill the chip
-        GevdParams p = apv_base_params(h);
-        const int first = runA ? 0 : 1;
-        p.x_c128 = f64;
-        p.x_group = s->xg;
-        p.XB = first ? q.X[3] : q.X[0];
-        p.XD = first ? q.X[2] : q.X[1];
-        p.d = q.tspec[first];
-        p.w = wz[first];
-        p.lam = lamz[first];
-        p.status = ostatus[first];
-        p.n_zones = (runA && runB) ? 2 : 1;
-        p.yield_issue = sch.yield_issue;
-        // one block of fewer than L rows: win_low_rank's route at T = 1, on every hop (float64 arithmetic only, as in apv_update_dev)
-        p.no_gevd64 = s->M < L && h->cfg.compute_dtype == APV_F64;
-        if (sch.lspill) p.Lspill = sch.lspill;
-        if (p.n_zones == 2) {
-            p.XB1 = q.X[3]; p.XD1 = q.X[2]; p.d1 = q.tspec[1];
-            p.w1 = wz[1]; p.lam1 = lamz[1]; p.status1 = ostatus[1];
-        }
-        hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why, h->rank_list.data());
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
-    }
-    if (sch.gevd_only) return APV_OK;
-    if (s->taps > 0 && !sch.skip_constrain) {
-        // the hop's filters projected onto J-tap responses, in place, both zone programs in one launch: K3, the attributes and the
-        // states read the projected filters
-        void *cw[2], *ct[2];
-        int nz = 0;
-        for (int z = 0; z < 2; ++z) {
-            if (!(z ? runB : runA)) continue;
-            cw[nz] = wz[z]; ct[nz] = s->wtaps[z]; ++nz;
-        }
-        if (s->cf_ev[0]) SCHK(h, hipEventRecord(s->cf_ev[0], st));
-        hipError_t e = apv_launch_constrain_filters(h->cfg.out_c128, N, s->taps, s->nV, L, nz, cw, ct, st, &why);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
-        if (s->cf_ev[1]) SCHK(h, hipEventRecord(s->cf_ev[1], st));
-    }
-    if (s->fir_synth) {
-        // FIR synthesis in place of K3 and K4: the hop's taps and the taps of the hop before it applied to the input signals in
-        // one launch, the target paths (pure delays) included, written where K4 writes; a second, small launch then makes this
-        // hop's taps and the newest J - 1 samples the next hop's.  Only the per-hop path reaches here (the chunked whole-signal
-        // path launches the synthesis of a whole chunk itself), after enqueue_front: the hop's samples lie behind `keep` older ones
-        // in the current input history, and the synthesis' own history alternates between two buffers with it.
-        const int J = s->taps, c = s->cur;
-        FirSynthArgs a{};
-        FirSynthAdvance adv{};
-        int nz = 0;
-        for (int z = 0; z < 2; ++z) {
-            if (!(z ? runB : runA)) continue;
-            a.prev[nz] = s->fs_taps[z]; a.cur[nz] = s->wtaps[z]; a.sig[nz] = z;
-            adv.cur[nz] = s->wtaps[z]; adv.prev[nz] = s->fs_taps[z];
-            ++nz;
-        }
-        for (int g = 0; g < 2; ++g) {
-            a.xhist[g] = s->fs_hist[c ^ 1][g];
-            a.xhop[g] = static_cast<const char*>(s->xhist[c][g]) + (size_t)s->keep * s->esz;
-            adv.old_hist[g] = a.xhist[g]; adv.xhop[g] = a.xhop[g]; adv.new_hist[g] = s->fs_hist[c][g];
-        }
-        a.nz = nz; a.nV = s->nV; a.L = L; a.J = J; a.H = H;
-        a.n_tgt = 2; a.ref = s->fs_ref; a.delay = s->fs_delay;
-        a.out = obuf;
-        a.sn = s->out_group > 0 ? L : 1;
-        a.sl = s->out_group > 0 ? 1 : H;
-        adv.n_taps = (size_t)s->nV * J * L; adv.nz = nz; adv.J = J; adv.H = H;
-        if (s->fs_ev[0]) SCHK(h, hipEventRecord(s->fs_ev[0], st));
-        hipError_t e = apv_launch_fir_synthesis(h->cfg.out_c128, f64, a, st, &why);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
-        if (s->fs_ev[1]) SCHK(h, hipEventRecord(s->fs_ev[1], st));
-        SCHK(h, apv_launch_fir_synth_advance(h->cfg.out_c128, f64, adv, st));
-        if (s->ev_on)
-            if (int rc = enqueue_eval(h, st, obuf)) return rc;
-        if (sch.spectra_free) SCHK(h, hipEventRecord(sch.spectra_free, st));
-        if (sch.no_copy) return APV_OK;
-        SCHK(h, hipMemcpyAsync(pin_dst, obuf, hop_result_bytes(s), hipMemcpyDeviceToHost, st));     // samples + status: one copy
         return APV_OK;
     }
-    {
-        // K3: output spectra in one launch: each live zone's nV*L filtered channels, then the target paths A_t, B_t
-        const void* jin[4];
-        const void* jw[4];
-        const void* jt[4];
-        void* jout[4];
-        int jf[4], jtg[4], nj = 0;
-        for (int z = 0; z < 2; ++z) {
-            if (!(z ? runB : runA)) continue;
-            jin[nj] = (const char*)q.inspec + (size_t)z * K * e2; jw[nj] = wz[z]; jt[nj] = nullptr;
-            jout[nj] = ospec + (size_t)oc * K * e2;
-            jf[nj] = s->nV * L; jtg[nj] = 0; ++nj;
-            oc += s->nV * L;
-        }
-        for (int z = 0; z < 2; ++z) {
-            jin[nj] = (const char*)q.inspec + (size_t)z * K * e2; jw[nj] = nullptr; jt[nj] = s->tgt;
-            jout[nj] = ospec + (size_t)oc * K * e2;
-            jf[nj] = 0; jtg[nj] = L; ++nj;
-            oc += L;
-        }
-        SCHK(h, apv_launch_apply_jobs(K, nj, jin, jw, jt, jout, jf, jtg, h->cfg.out_c128, f64, st));
+    GevdParams p = fused_gevd_params(h, q, wz, lamz, status);
+    p.yield_issue = sch.yield_issue;
+    // one block of fewer than L rows: win_low_rank's route at T = 1, on every hop (float64 arithmetic only, as in apv_update_dev)
+    p.no_gevd64 = s->M < L && h->cfg.compute_dtype == APV_F64;
+    if (sch.lspill) p.Lspill = sch.lspill;
+    hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why, h->rank_list.data());
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    return APV_OK;
+}
+
+// The hop's filters `wz` projected onto J-tap responses, in place, both zone programs in one launch (nothing in an unconstrained
+// stream): K3, the attributes and the states read the projected filters; the taps go to wtaps.
+static int back_constrain(apv_handle* h, hipStream_t st, void* const* wz) {
+    apv_stream* s = h->st;
+    if (s->taps <= 0) return APV_OK;
+    void *cw[2], *ct[2];
+    const LiveZones lz(s);
+    for (int i = 0; i < lz.nz; ++i) { cw[i] = wz[lz.z[i]]; ct[i] = s->wtaps[lz.z[i]]; }
+    std::string why;
+    if (s->cf_tm.ev[0]) SCHK(h, hipEventRecord(s->cf_tm.ev[0], st));
+    hipError_t e = apv_launch_constrain_filters(h->cfg.out_c128, s->N, s->taps, s->nV, s->L, lz.nz, cw, ct, st, &why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    if (s->cf_tm.ev[1]) SCHK(h, hipEventRecord(s->cf_tm.ev[1], st));
+    return APV_OK;
+}
+
+// FIR synthesis in place of K3 and K4: the hop's taps and the taps of the hop before it applied to the input signals in
+// one launch, the target paths (pure delays) included, written where K4 writes; a second, small launch then makes this
+// hop's taps and the newest J - 1 samples the next hop's.  Only the per-hop path reaches here (the chunked whole-signal
+// path launches the synthesis of a whole chunk itself), after enqueue_front: the hop's samples lie behind `keep` older ones
+// in the current input history, and the synthesis' own history alternates between two buffers with it.  Evaluation, the event
+// and the copy back follow on the same stream.
+static int back_fir_synthesis(apv_handle* h, hipStream_t st, void* pin_dst, const BackSchedule& sch) {
+    apv_stream* s = h->st;
+    char* const obuf = sch.result;
+    const int J = s->taps, c = s->cur, f64 = s->f64;
+    FirSynthArgs a = fir_synth_args(s, s->fs_taps, s->wtaps);
+    FirSynthAdvance adv{};
+    for (int i = 0; i < a.nz; ++i) { adv.cur[i] = a.cur[i]; adv.prev[i] = s->fs_taps[a.sig[i]]; }
+    for (int g = 0; g < 2; ++g) {
+        a.xhist[g] = s->fs_hist[c ^ 1][g];
+        a.xhop[g] = static_cast<const char*>(s->xhist[c][g]) + (size_t)s->keep * s->esz;
+        adv.old_hist[g] = a.xhist[g]; adv.xhop[g] = a.xhop[g]; adv.new_hist[g] = s->fs_hist[c][g];
     }
+    a.out = obuf;
+    adv.n_taps = (size_t)s->nV * J * s->L; adv.nz = a.nz; adv.J = J; adv.H = s->H;
+    std::string why;
+    if (s->fs_tm.ev[0]) SCHK(h, hipEventRecord(s->fs_tm.ev[0], st));
+    hipError_t e = apv_launch_fir_synthesis(h->cfg.out_c128, f64, a, st, &why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    if (s->fs_tm.ev[1]) SCHK(h, hipEventRecord(s->fs_tm.ev[1], st));
+    SCHK(h, apv_launch_fir_synth_advance(h->cfg.out_c128, f64, adv, st));
+    if (s->ev_on)
+        if (int rc = enqueue_eval(h, st, obuf)) return rc;
+    if (sch.spectra_free) SCHK(h, hipEventRecord(sch.spectra_free, st));
+    if (!pin_dst) return APV_OK;
+    SCHK(h, hipMemcpyAsync(pin_dst, obuf, hop_result_bytes(s), hipMemcpyDeviceToHost, st));     // samples + status: one copy
+    return APV_OK;
+}
+
+// K3: output spectra in one launch: each live zone's nV*L filtered channels, then the target paths A_t, B_t
+static int back_output_spectra(apv_handle* h, hipStream_t st, const HopSpectra& q, void* const* wz, const BackSchedule& sch) {
+    const apv_stream* s = h->st;
+    char* const ospec = sch.ospec;
+    const int K = s->K, L = s->L;
+    const size_t e2 = 2 * s->esz;
+    const void* jin[4];
+    const void* jw[4];
+    const void* jt[4];
+    void* jout[4];
+    int jf[4], jtg[4], nj = 0;
+    int oc = 0;     // output channel cursor
+    const LiveZones lz(s);
+    for (int i = 0; i < lz.nz; ++i) {
+        const int z = lz.z[i];
+        jin[nj] = (const char*)q.inspec + (size_t)z * K * e2; jw[nj] = wz[z]; jt[nj] = nullptr;
+        jout[nj] = ospec + (size_t)oc * K * e2;
+        jf[nj] = s->nV * L; jtg[nj] = 0; ++nj;
+        oc += s->nV * L;
+    }
+    for (int z = 0; z < 2; ++z) {
+        jin[nj] = (const char*)q.inspec + (size_t)z * K * e2; jw[nj] = nullptr; jt[nj] = s->tgt;
+        jout[nj] = ospec + (size_t)oc * K * e2;
+        jf[nj] = 0; jtg[nj] = L; ++nj;
+        oc += L;
+    }
+    SCHK(h, apv_launch_apply_jobs(K, nj, jin, jw, jt, jout, jf, jtg, h->cfg.out_c128, s->f64, st));
+    return APV_OK;
+}
+
+// Behind K3 on `st`: the event that says the spectra set has been read for the last time; then, on the tail stream where the
+// schedule names one (it starts at that event), K4 (synthesis + overlap-add + emit), the evaluation and the copy back.
+static int back_synthesis(apv_handle* h, hipStream_t st, void* pin_dst, const BackSchedule& sch) {
+    apv_stream* s = h->st;
+    char* const obuf = sch.result;
     if (sch.spectra_free) SCHK(h, hipEventRecord(sch.spectra_free, st));
     hipStream_t ts = st;
     if (sch.tail_stream) {
         ts = sch.tail_stream;
         SCHK(h, hipStreamWaitEvent(ts, sch.spectra_free, 0));
     }
-    // K4: synthesis + overlap-add + emit
-    {
-        hipError_t e = apv_launch_synthesis(f64, N, H, s->n_out, ospec, K, 1, s->outov, obuf, ts, &why, s->out_group);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
-    }
+    std::string why;
+    hipError_t e = apv_launch_synthesis(s->f64, s->N, s->H, s->n_out, sch.ospec, s->K, 1, s->outov, obuf, ts, &why, s->out_group);
+    if (e != hipSuccess) return launch_fail(h, e, why);
     if (s->ev_on)
         if (int rc = enqueue_eval(h, ts, obuf)) return rc;
-    if (sch.no_copy) return APV_OK;
+    if (!pin_dst) return APV_OK;
     SCHK(h, hipMemcpyAsync(pin_dst, obuf, hop_result_bytes(s), hipMemcpyDeviceToHost, ts));         // samples + status: one copy
     if (sch.tail_stream) SCHK(h, hipEventRecord(sch.copied, ts));
     return APV_OK;
+}
+
+// Back half of a hop on stream `st`: spectra `q` -> per-bin filters (K5'-K10), their projection in a constrained stream, then
+// output spectra (K3), synthesis and overlap-add (K4), or the FIR synthesis in their place; the emitted samples [n_out][H] and,
+// behind them, the status words [2][K] land in pinned `pin_dst`.
+static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void* const* wz, void* const* lamz, void* pin_dst,
+                        const BackSchedule& sch) {
+    int rc = back_solve(h, st, q, wz, lamz, sch);
+    if (rc == APV_OK) rc = back_constrain(h, st, wz);
+    if (rc != APV_OK) return rc;
+    if (h->st->fir_synth) return back_fir_synthesis(h, st, pin_dst, sch);
+    rc = back_output_spectra(h, st, q, wz, sch);
+    if (rc == APV_OK) rc = back_synthesis(h, st, pin_dst, sch);
+    return rc;
 }
 
 // everything one hop puts on the handle's stream, from the pinned input staging to the pinned output staging
@@ -624,7 +720,7 @@ static int enqueue_hop(apv_handle* h) {
     apv_stream* s = h->st;
     int rc = enqueue_front(h, h->stream, 0, s->pin_in);
     if (rc != APV_OK) return rc;
-    return enqueue_back(h, h->stream, hop_spectra(s, 0), s->w, s->lam, s->pin_out);
+    return enqueue_back(h, h->stream, hop_spectra(s, 0), s->w, s->lam, s->pin_out, BackSchedule(s->out, s->outspec));
 }
 
 // run one hop whose input is already in the pinned staging; the output is left in the pinned staging
@@ -667,24 +763,7 @@ static int run_hop(apv_handle* h) {
     s->hop++;
     if (s->win_fill_host < s->win_T) s->win_fill_host++;
     SCHK(h, hipStreamSynchronize(st));
-    if (s->win_ev[0]) {
-        float ms = 0.f;
-        SCHK(h, hipEventElapsedTime(&ms, s->win_ev[0], s->win_ev[1]));
-        s->win_ms[0] += ms;
-        s->win_ms[1] += 1.0;
-    }
-    if (s->cf_ev[0]) {
-        float ms = 0.f;
-        SCHK(h, hipEventElapsedTime(&ms, s->cf_ev[0], s->cf_ev[1]));
-        s->cf_ms[0] += ms;
-        s->cf_ms[1] += 1.0;
-    }
-    if (s->fs_ev[0]) {
-        float ms = 0.f;
-        SCHK(h, hipEventElapsedTime(&ms, s->fs_ev[0], s->fs_ev[1]));
-        s->fs_ms[0] += ms;
-        s->fs_ms[1] += 1.0;
-    }
+    for (StageTimer* t : {&s->win_tm, &s->cf_tm, &s->fs_tm}) SCHK(h, t->read());
     return APV_OK;
 }
 
@@ -772,19 +851,15 @@ static int process_block_t(apv_handle* h, const TI* h_in_A, const TI* h_in_B, TI
 
 // ---- whole-signal path (apv_process_signal) ----
 
-// hops [base, base + nc) of the call: results (pinned `res`, one every hop_result_bytes) into h_out, and their status words scanned.
-// `worst` keeps the first APV_ERR_NO_CONVERGE, overridden by APV_ERR_NOT_PD, and `worst_msg` its message.
-template <typename TI>
-static void collect_hops(apv_handle* h, const char* res, int n_hops, int base, int nc, long hop_first, TI* h_out, int& worst,
-                         std::string& worst_msg) {
-    const apv_stream* s = h->st;
-    for (int i = 0; i < nc; ++i, res += hop_result_bytes(s)) {
-        copy_hop_out(s, res, n_hops, base + i, h_out);
-        const int r = scan_hop_status(h, hop_status_of(s, res), hop_first + base + i);
-        if (r == APV_ERR_NOT_PD && worst != APV_ERR_NOT_PD) { worst = r; worst_msg = h->err; }
-        if (r == APV_ERR_NO_CONVERGE && worst == APV_OK) { worst = r; worst_msg = h->err; }
+// the worst status of the hops of a call: the first APV_ERR_NO_CONVERGE, overridden by APV_ERR_NOT_PD, and its message
+struct WorstStatus {
+    int code = APV_OK;
+    std::string msg;
+    void note(const apv_handle* h, int r) {
+        if (r == APV_ERR_NOT_PD && code != APV_ERR_NOT_PD) { code = r; msg = h->err; }
+        if (r == APV_ERR_NO_CONVERGE && code == APV_OK) { code = r; msg = h->err; }
     }
-}
+};
 
 // Every failure after the first enqueue leaves through here: the front stream, the `n_back` back streams and the tail stream are
 // drained (kernels may still be reading the pinned staging and writing the result buffers), and the message says how far the call
@@ -802,6 +877,59 @@ static int signal_bail(apv_handle* h, const hipStream_t* back, int n_back, int n
                   "with apv_set_state or re-initialise before continuing]", deliv, n_hops, enq);
     return apv_fail(h, code, msg + buf);
 }
+
+// The bookkeeping of one call of the pipeline or of the chunked driver: which chunks of the signal have been collected from the
+// pinned staging, the worst status among their hops, and the two ways out of the call.  Chunk c lives in slot c mod n_slots of the
+// staging `pin_out`, and `done[c mod n_slots]` says that it has been copied back.
+template <typename TI>
+struct SignalCall {
+    apv_handle* h;
+    int n_hops;
+    TI* h_out;
+    const hipStream_t* back;      // the back streams signal_bail drains
+    int n_back;
+    const hipEvent_t* done;
+    const char* pin_out;
+    int n_slots;
+    int chunk, n_chunks;
+    long hop_first;
+    WorstStatus worst;
+    int c_done = 0;               // chunks collected
+
+    SignalCall(apv_handle* h_, int n_hops_, TI* h_out_, const hipStream_t* back_, int n_back_, const hipEvent_t* done_,
+               const void* pin_out_, int n_slots_)
+        : h(h_), n_hops(n_hops_), h_out(h_out_), back(back_), n_back(n_back_), done(done_), pin_out((const char*)pin_out_),
+          n_slots(n_slots_), chunk(h_->st->sig_chunk), n_chunks((n_hops_ + chunk - 1) / chunk), hop_first(h_->st->hop) {}
+
+    // hops of chunk c: results (one every hop_result_bytes) into h_out, and their status words scanned
+    int collect(int c) {
+        const apv_stream* s = h->st;
+        const int base = c * chunk, nc = std::min(chunk, n_hops - base);
+        hipError_t e = hipEventSynchronize(done[c % n_slots]);
+        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e));
+        const char* res = pin_out + (size_t)(c % n_slots) * chunk * hop_result_bytes(s);
+        for (int i = 0; i < nc; ++i, res += hop_result_bytes(s)) {
+            copy_hop_out(s, res, n_hops, base + i, h_out);
+            worst.note(h, scan_hop_status(h, hop_status_of(s, res), hop_first + base + i));
+        }
+        return APV_OK;
+    }
+    int bail(int code, const std::string& msg) { return signal_bail(h, back, n_back, n_hops, hop_first, (long)c_done * chunk, code, msg); }
+    int hipbail(hipError_t e) { return bail(APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e)); }
+    // Behind the driver's loop: the chunks still in flight (none of those behind a hop that was not positive definite), then
+    // `leave_state` (the driver's: every stream drained, the stream state where the per-hop path expects it), then the call's status.
+    template <typename F>
+    int finish(F leave_state) {
+        for (int c = c_done; c < n_chunks && (size_t)c * chunk < (size_t)(h->st->hop - hop_first); ++c) {
+            if (int rc = collect(c)) return bail(rc, h->err);
+            c_done = c + 1;
+        }
+        if (int rc = leave_state()) return bail(rc, h->err);
+        if (worst.code == APV_ERR_NOT_PD) return bail(worst.code, worst.msg);     // the hops behind the failing one were not run
+        if (worst.code != APV_OK) return apv_fail(h, worst.code, worst.msg);      // APV_ERR_NO_CONVERGE: every hop ran, every output is written
+        return APV_OK;
+    }
+};
 
 // what the whole-signal path needs beyond the per-hop path; allocated at its first call
 static int signal_prepare(apv_handle* h) {
@@ -863,8 +991,7 @@ template <typename TI>
 static int process_signal_hops_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
     apv_stream* s = h->st;
     SCHK(h, hipSetDevice(h->device));
-    int worst = APV_OK;                                      // first APV_ERR_NO_CONVERGE: every hop still runs
-    std::string worst_msg;
+    WorstStatus worst;                                       // first APV_ERR_NO_CONVERGE: every hop still runs
     if (s->ev_on)
         if (int rc = eval_begin_call(h, n_hops)) return rc;
     for (int i = 0; i < n_hops; ++i) {
@@ -874,13 +1001,10 @@ static int process_signal_hops_t(apv_handle* h, int n_hops, const TI* h_in_A, co
         if (s->ev_on) s->ev_nrec = i + 1;
         copy_hop_out(s, s->pin_out, n_hops, i, h_out);
         rc = scan_hop_status(h, hop_status_of(s, s->pin_out), s->hop - 1);
-        if (rc == APV_ERR_NO_CONVERGE) {
-            if (worst == APV_OK) { worst = rc; worst_msg = h->err; }
-        } else if (rc != APV_OK) {
-            return rc;
-        }
+        if (rc != APV_OK && rc != APV_ERR_NO_CONVERGE) return rc;
+        worst.note(h, rc);
     }
-    if (worst != APV_OK) return apv_fail(h, worst, worst_msg);
+    if (worst.code != APV_OK) return apv_fail(h, worst.code, worst.msg);
     return APV_OK;
 }
 
@@ -897,7 +1021,7 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     // of consecutive hops; and the hop loop when its projection or synthesis is timed (the switches promise un-captured per-hop
     // launches, tools/bench_filter_constraint.py and tools/bench_fir_synthesis.py read one time per hop).
     // An evaluated stream takes the hop loop too: its output histories and totals make consecutive hops sequential.
-    const bool chunked = !explicit_stats(s) && !s->ev_on && s->fir_F > 0 && s->fir_np == 1 && !(s->taps > 0 && (s->cf_ev[0] || s->fs_ev[0]));
+    const bool chunked = !explicit_stats(s) && !s->ev_on && s->fir_F > 0 && s->fir_np == 1 && !(s->taps > 0 && (s->cf_tm.ev[0] || s->fs_tm.ev[0]));
     const long hop_before = s->hop;
     int rc;
     if (chunked) rc = process_signal_chunked_t<TI>(h, n_hops, h_in_A, h_in_B, h_out);
@@ -908,6 +1032,57 @@ static int process_signal_t(apv_handle* h, int n_hops, const TI* h_in_A, const T
     return rc;
 }
 
+// the two spectra sets (and the result buffers that follow them) of the hop-by-hop pipeline
+struct PipelineSets {
+    int set = 0, last_set = 0;
+    bool released[2] = {true, true};                         // nothing reads either set yet
+    bool out_idle[2] = {true, true};                         // no copy of either result buffer pending
+};
+
+// one hop of the pipeline: front half on the front stream into the next set, back half on the handle's stream, synthesis and copy
+// back (to pinned `pin_dst`) on the tail stream
+static int pipeline_hop(apv_handle* h, PipelineSets& ps, const void* pin_src, void* pin_dst) {
+    apv_stream* s = h->st;
+    const int set = ps.set;
+    hipStream_t back = h->stream;
+    // hop h-2 has to be done with this set before the analysis transforms write it
+    int rc = enqueue_front(h, s->front, set, pin_src, ps.released[set] ? nullptr : s->ev_back[set]);
+    if (rc != APV_OK) return rc;
+    SIGCHK(h, hipEventRecord(s->ev_front[set], s->front));
+    SIGCHK(h, hipStreamWaitEvent(back, s->ev_front[set], 0));
+    // the output buffers follow the set; hop h-2's synthesis and copy have to be through before this hop writes them
+    if (!ps.out_idle[set]) SIGCHK(h, hipStreamWaitEvent(back, s->ev_copied[set], 0));
+    BackSchedule sch(set ? s->out1 : s->out, set ? s->outspec1 : s->outspec);    // the output buffers follow the set
+    sch.spectra_free = s->ev_back[set];          // recorded after K3, the set's last reader
+    sch.tail_stream = s->tail;
+    sch.copied = s->ev_copied[set];
+    rc = enqueue_back(h, back, hop_spectra(s, set), s->w, s->lam, pin_dst, sch);
+    if (rc != APV_OK) return rc;
+    ps.out_idle[set] = false;
+    ps.released[set] = false;
+    ps.last_set = set;
+    ps.set ^= 1;
+    s->hop++;
+    return APV_OK;
+}
+
+// behind the last hop: the state arrays and apv_process_block live in set 0, so the last hop's spectra are brought there; then
+// every stream of the pipeline is drained
+static int pipeline_leave_state(apv_handle* h, const PipelineSets& ps) {
+    apv_stream* s = h->st;
+    hipStream_t back = h->stream;
+    if (ps.last_set == 1) {
+        const size_t K = s->K, C = s->C, M = s->M, e2 = 2 * s->esz;
+        for (int p = 0; p < 4; ++p) SIGCHK(h, hipMemcpyAsync(s->X[p], s->X1[p], (size_t)s->Kp * C * e2, hipMemcpyDeviceToDevice, back));
+        for (int z = 0; z < 2; ++z) SIGCHK(h, hipMemcpyAsync(s->tspec[z], s->tspec1[z], K * M * e2, hipMemcpyDeviceToDevice, back));
+        SIGCHK(h, hipMemcpyAsync(s->inspec, s->inspec1, 2 * K * e2, hipMemcpyDeviceToDevice, back));
+    }
+    SIGCHK(h, hipStreamSynchronize(s->front));
+    SIGCHK(h, hipStreamSynchronize(back));
+    SIGCHK(h, hipStreamSynchronize(s->tail));
+    return APV_OK;
+}
+
 // the hop-by-hop pipeline of the whole-signal call (direct-form or partitioned K1, no statistics window, no constraint)
 template <typename TI>
 static int process_signal_pipelined_t(apv_handle* h, int n_hops, const TI* h_in_A, const TI* h_in_B, TI* h_out) {
@@ -915,91 +1090,31 @@ static int process_signal_pipelined_t(apv_handle* h, int n_hops, const TI* h_in_
     SCHK(h, hipSetDevice(h->device));
     int rc = signal_prepare(h);
     if (rc != APV_OK) return rc;
-    const int H = s->H, K = s->K, chunk = s->sig_chunk;
+    const int H = s->H, chunk = s->sig_chunk;
     const size_t e1 = s->esz;
     hipStream_t back = h->stream;
-    int set = 0, last_set = 0;
-    bool released[2] = {true, true};                         // nothing reads either set yet
-    bool out_idle[2] = {true, true};                         // no copy of either result buffer pending
-    int worst = APV_OK;                                      // first APV_ERR_NO_CONVERGE, overridden by APV_ERR_NOT_PD
-    std::string worst_msg;
-    const int n_chunks = (n_hops + chunk - 1) / chunk;
-    const long hop_first = s->hop;
+    PipelineSets ps;
     // chunk c of the signal lives in half c & 1 of the pinned staging
-    auto collect = [&](int c) -> int {
-        const int base = c * chunk, nc = std::min(chunk, n_hops - base);
-        hipError_t e = hipEventSynchronize(s->ev_chunk[c & 1]);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e));
-        collect_hops(h, (const char*)s->sig_out + (size_t)(c & 1) * chunk * hop_result_bytes(s), n_hops, base, nc, hop_first, h_out,
-                     worst, worst_msg);
-        return APV_OK;
-    };
-    int c_done = 0;                                          // chunks collected
-    auto bail = [&](int code, const std::string& msg) {
-        return signal_bail(h, &back, 1, n_hops, hop_first, (long)c_done * chunk, code, msg);
-    };
-    auto hipbail = [&](hipError_t e) { return bail(APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e)); };
-    for (int c = 0; c < n_chunks && worst != APV_ERR_NOT_PD; ++c) {
+    SignalCall<TI> call(h, n_hops, h_out, &back, 1, s->ev_chunk, s->sig_out, 2);
+    for (int c = 0; c < call.n_chunks && call.worst.code != APV_ERR_NOT_PD; ++c) {
         const int base = c * chunk, nc = std::min(chunk, n_hops - base);
         // this half was collected when chunk c-2's event came in
         stage_hops(s, h_in_A, h_in_B, base, nc, (char*)s->sig_in + (size_t)(c & 1) * chunk * 2 * H * e1);
         for (int i = 0; i < nc; ++i) {
             const size_t slot = (size_t)(c & 1) * chunk + i;
-            // hop h-2 has to be done with this set before the analysis transforms write it
-            rc = enqueue_front(h, s->front, set, (const char*)s->sig_in + slot * 2 * H * e1, released[set] ? nullptr : s->ev_back[set]);
-            if (rc != APV_OK) return bail(rc, h->err);
-            hipError_t e = hipEventRecord(s->ev_front[set], s->front);
-            if (e == hipSuccess) e = hipStreamWaitEvent(back, s->ev_front[set], 0);
-            // the output buffers follow the set; hop h-2's synthesis and copy have to be through before this hop writes them
-            if (e == hipSuccess && !out_idle[set]) e = hipStreamWaitEvent(back, s->ev_copied[set], 0);
-            if (e == hipSuccess) {
-                BackSchedule sch;
-                sch.obuf = set;
-                sch.spectra_free = s->ev_back[set];          // recorded after K3, the set's last reader
-                sch.tail_stream = s->tail;
-                sch.copied = s->ev_copied[set];
-                rc = enqueue_back(h, back, hop_spectra(s, set), s->w, s->lam, (char*)s->sig_out + slot * hop_result_bytes(s), sch);
-                if (rc != APV_OK) return bail(rc, h->err);
-                out_idle[set] = false;
-            }
-            if (e != hipSuccess) return hipbail(e);
-            released[set] = false;
-            last_set = set;
-            set ^= 1;
-            s->hop++;
+            rc = pipeline_hop(h, ps, (const char*)s->sig_in + slot * 2 * H * e1, (char*)s->sig_out + slot * hop_result_bytes(s));
+            if (rc != APV_OK) return call.bail(rc, h->err);
         }
         {
             const hipError_t e = hipEventRecord(s->ev_chunk[c & 1], s->tail);   // every front and back half is upstream of some copy
-            if (e != hipSuccess) return hipbail(e);
+            if (e != hipSuccess) return call.hipbail(e);
         }
         if (c > 0) {
-            if ((rc = collect(c - 1)) != APV_OK) return bail(rc, h->err);
-            c_done = c;
+            if ((rc = call.collect(c - 1)) != APV_OK) return call.bail(rc, h->err);
+            call.c_done = c;
         }
     }
-    // the chunks still in flight (one, or none if a hop was not positive definite in the last one collected)
-    for (int c = c_done; c < n_chunks && (size_t)c * chunk < (size_t)(s->hop - hop_first); ++c) {
-        if ((rc = collect(c)) != APV_OK) return bail(rc, h->err);
-        c_done = c + 1;
-    }
-    if (last_set == 1) {
-        // the state arrays and apv_process_block live in set 0: bring the last hop's spectra there
-        const size_t C = s->C, M = s->M, e2 = 2 * e1;
-        hipError_t e = hipSuccess;
-        for (int p = 0; p < 4 && e == hipSuccess; ++p) e = hipMemcpyAsync(s->X[p], s->X1[p], (size_t)s->Kp * C * e2, hipMemcpyDeviceToDevice, back);
-        for (int z = 0; z < 2 && e == hipSuccess; ++z) e = hipMemcpyAsync(s->tspec[z], s->tspec1[z], (size_t)K * M * e2, hipMemcpyDeviceToDevice, back);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->inspec, s->inspec1, (size_t)2 * K * e2, hipMemcpyDeviceToDevice, back);
-        if (e != hipSuccess) return hipbail(e);
-    }
-    {
-        hipError_t e = hipStreamSynchronize(s->front);
-        if (e == hipSuccess) e = hipStreamSynchronize(back);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->tail);
-        if (e != hipSuccess) return hipbail(e);
-    }
-    if (worst == APV_ERR_NOT_PD) return bail(worst, worst_msg);     // the hops behind the failing one were not run
-    if (worst != APV_OK) return apv_fail(h, worst, worst_msg);      // APV_ERR_NO_CONVERGE: every hop ran, every output is written
-    return APV_OK;
+    return call.finish([&] { return pipeline_leave_state(h, ps); });
 }
 
 // what the chunked whole-signal path needs beyond signal_prepare(); allocated at its first call
@@ -1035,7 +1150,7 @@ static int chunk_prepare(apv_handle* h) {
             const size_t spill = apv_gevd_spill_bytes((int)L, (int)K, c.compute_dtype, c.reg_mode, c.reg_bright, c.sweep_tol2, c.n_zones == 3 ? 2 : 1);
             if (spill > 0 && (rc = dalloc(h, &s->ck_spill[b], spill, 1))) return rc;
         }
-        // (the back streams themselves are made by process_signal_chunked_t, and only where the hop-by-hop schedule runs: the
+        // (the back streams themselves are made by chunk_begin, and only where the hop-by-hop schedule runs: the
         // runtime deals a process's streams over four hardware queues, and a stream that exists takes part whether it is used or not)
     }
     for (int q = 0; q < CK_NS; ++q) SCHK(h, s->own.event(&s->ck_done[q], hipEventDisableTiming));
@@ -1061,6 +1176,366 @@ static int chunk_prepare(apv_handle* h) {
     return APV_OK;
 }
 
+// One call of the chunked whole-signal path (process_signal_chunked_t): its constants, the back streams with their filter sets,
+// where the stream stood when the call began and where the call's last hop ran.
+struct ChunkCall {
+    apv_handle* h;
+    apv_stream* s;
+    // a constrained stream: ONE projection launch per chunk behind the chunk's joint diagonalisations, whose filters all go to
+    // ck_wall; with FIR synthesis ONE synthesis launch per chunk in place of K3 and K4 (chunk_back_batched, chunk_constrained_tail)
+    bool cons, fir;
+    // the chunk's joint diagonalisations as one launch where the kernel that will run takes several hops (order 16, absolute loading,
+    // no diagnostics); elsewhere hop by hop on the back streams
+    bool batched;
+    size_t hop_w, hop_lam, hop_taps;             // bytes of one hop's filters, eigenvalues and taps of one zone program
+    hipStream_t bs[CK_NB];                       // back streams, with the filters and eigenvalues each writes
+    void* wset[CK_NB][2];
+    void* lset[CK_NB][2];
+    long hop_first;
+    int ring_first, cur_first;
+    int last_par = 0, last_nc = 0, last_b = 0;   // chunk parity, hops and back stream of the last hop enqueued
+};
+
+static int chunk_begin(apv_handle* h, ChunkCall& k) {
+    apv_stream* s = h->st;
+    k.h = h;
+    k.s = s;
+    k.cons = s->taps > 0;
+    k.fir = s->fir_synth != 0;
+    k.hop_w = (size_t)s->K * s->nV * s->L * wsz(h);
+    k.hop_lam = (size_t)s->K * s->L * lsz(h);
+    k.hop_taps = (size_t)s->nV * s->taps * s->L * lsz(h);
+    {
+        GevdParams probe = apv_base_params(h);
+        probe.x_c128 = s->f64;
+        probe.x_group = s->xg;
+        probe.n_hops = 2;
+        static const bool force_generic = getenv("APV_FORCE_GENERIC") != nullptr;
+        k.batched = !force_generic && apv_gevd16m_takes_hops(probe, h->cfg.compute_dtype, true);
+    }
+    if (!k.batched)
+        for (int b = 0; b + 1 < CK_NB; ++b)
+            if (!s->ck_back[b]) SCHK(h, s->own.stream(&s->ck_back[b], hipStreamNonBlocking));
+    for (int b = 0; b < CK_NB; ++b) {
+        k.bs[b] = (b && s->ck_back[b - 1]) ? s->ck_back[b - 1] : h->stream;
+        for (int z = 0; z < 2; ++z) {
+            k.wset[b][z] = b ? s->ck_w[b - 1][z] : s->w[z];
+            k.lset[b][z] = b ? s->ck_lam[b - 1][z] : s->lam[z];
+        }
+    }
+    k.hop_first = s->hop;
+    k.ring_first = s->ring_off;
+    k.cur_first = s->cur;
+    return APV_OK;
+}
+
+// the spectra set of hop i of a chunk of parity par
+static HopSpectra chunk_set(const apv_stream* s, int par, int i) {
+    HopSpectra q;
+    const size_t idx = (size_t)par * s->sig_chunk + i, K = s->K, e2 = 2 * s->esz;
+    for (int p = 0; p < 4; ++p) q.X[p] = (char*)s->ck_X[p] + idx * (size_t)s->Kp * s->C * e2;
+    for (int z = 0; z < 2; ++z) q.tspec[z] = (char*)s->ck_tspec[z] + idx * K * s->M * e2;
+    q.inspec = (char*)s->ck_inspec + idx * 2 * K * e2;
+    return q;
+}
+
+// ... and its result and output-spectra slots: every hop of the two chunks in flight has its own, and the chunk's results go back
+// in one copy (chunk_copy_back)
+static BackSchedule chunk_slots(const apv_stream* s, int par, int i) {
+    const size_t slot = (size_t)par * s->sig_chunk + i;
+    return BackSchedule((char*)s->ck_out + slot * hop_result_bytes(s), (char*)s->ck_ospec + slot * (size_t)s->n_out * s->K * 2 * s->esz);
+}
+
+// ... and its slots of ck_wall / ck_lamall
+static void chunk_filters(const ChunkCall& k, int i, void** wz, void** lz) {
+    for (int z = 0; z < 2; ++z) {
+        wz[z] = (char*)k.s->ck_wall[z] + i * k.hop_w;
+        lz[z] = (char*)k.s->ck_lamall[z] + i * k.hop_lam;
+    }
+}
+
+// the filters of the chunk's nc hops (ck_wall) projected in place, their taps to ck_taps: one launch on `st`
+static int chunk_project(const ChunkCall& k, hipStream_t st, int nc) {
+    apv_handle* h = k.h;
+    const apv_stream* s = k.s;
+    void *cw[2], *ct[2];
+    const LiveZones lz(s);
+    for (int i = 0; i < lz.nz; ++i) { cw[i] = s->ck_wall[lz.z[i]]; ct[i] = s->ck_taps[lz.z[i]]; }
+    std::string why;
+    hipError_t e = apv_launch_constrain_filters_hops(h->cfg.out_c128, s->N, s->taps, s->nV, s->L, lz.nz, cw, ct, nc, k.hop_w / wsz(h),
+                                                     k.hop_taps / lsz(h), st, &why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    return APV_OK;
+}
+
+// the FIR synthesis of the chunk's nc hops into their result slots: one launch on `st`, hop i fading from the taps of hop i - 1
+// (hop 0 from fs_taps), and behind it the last hop's taps to fs_taps for the next chunk or call
+static int chunk_synthesis(const ChunkCall& k, hipStream_t st, int par, int nc) {
+    apv_handle* h = k.h;
+    const apv_stream* s = k.s;
+    FirSynthArgs a = fir_synth_args(s, s->fs_taps, s->ck_taps);
+    for (int g = 0; g < 2; ++g) {
+        a.xhist[g] = s->ck_xrow[par][g];
+        a.xhop[g] = (const char*)s->ck_xrow[par][g] + (size_t)(s->taps - 1) * s->esz;
+    }
+    a.out = (char*)s->ck_out + (size_t)par * s->sig_chunk * hop_result_bytes(s);
+    a.n_hops = nc; a.hop_taps = k.hop_taps / lsz(h); a.hop_x = s->H; a.hop_out = hop_result_bytes(s);
+    std::string why;
+    hipError_t e = apv_launch_fir_synthesis(h->cfg.out_c128, s->f64, a, st, &why);
+    const LiveZones lz(s);
+    for (int i = 0; i < lz.nz && e == hipSuccess; ++i)
+        e = hipMemcpyAsync(s->fs_taps[lz.z[i]], (char*)s->ck_taps[lz.z[i]] + (size_t)(nc - 1) * k.hop_taps, k.hop_taps,
+                           hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    return APV_OK;
+}
+
+// Front half of the whole chunk c (nc hops, staged in pinned `pin`) on the front stream: input side, K1, analysis, weighting.
+static int chunk_front(ChunkCall& k, int c, int nc, const char* pin) {
+    apv_handle* h = k.h;
+    apv_stream* s = k.s;
+    const int N = s->N, H = s->H, M = s->M, C = s->C, P = s->P, f64 = s->f64, chunk = s->sig_chunk, RL = s->ck_RL, par = c & 1;
+    // the spectra sets and linear buffers of this parity were last read by the back halves of chunk c - 2
+    if (c >= 2)
+        for (int b = 0; b < CK_NB; ++b) SIGCHK(h, hipStreamWaitEvent(s->front, s->ck_backdone[par][b], 0));
+    // ... and, in a constrained stream, by what follows the chunk's projection: K3, or the synthesis reading the input rows
+    if (k.cons && c >= 2) SIGCHK(h, hipStreamWaitEvent(s->front, s->ck_done[(c - 2) % CK_NS], 0));
+    SIGCHK(h, apv_launch_fir_chunk_spectra(f64, s->fir_F, P, H, nc, s->xhist[s->cur][0], s->xhist[s->cur][1], pin, s->xspec_chunk, s->front));
+    // heads of the linear buffers: the newest N - H samples before the chunk, from the rings (first chunk) or from the tail
+    // of the previous chunk's buffers
+    {
+        const int prev = par ^ 1, prev_nc = chunk;               // every chunk but the last is full
+        auto head = [&](void* dst, const void* ring, const void* lin_prev, int rows) -> hipError_t {
+            if (c == 0) return apv_launch_rows_copy(f64, rows, N - H, dst, RL, 0, RL, ring, N, (H + k.ring_first) % N, N, s->front);
+            return apv_launch_rows_copy(f64, rows, N - H, dst, RL, 0, RL, lin_prev, RL, prev_nc * H, RL, s->front);
+        };
+        for (int p = 0; p < 4; ++p) SIGCHK(h, head(s->ck_resp[par][p], s->resp[p], s->ck_resp[prev][p], C));
+        for (int z = 0; z < 2; ++z) SIGCHK(h, head(s->ck_tresp[par][z], s->tresp[z], s->ck_tresp[prev][z], M));
+        SIGCHK(h, head(s->ck_in[par], s->inblk, s->ck_in[prev], 2));
+    }
+    {
+        const void* oh[2] = {s->xhist[s->cur][0], s->xhist[s->cur][1]};
+        void* nh[2] = {s->xhist[s->cur ^ 1][0], s->xhist[s->cur ^ 1][1]};
+        SIGCHK(h, apv_launch_chunk_inputs(f64, P, H, N, nc, s->pad, RL, oh, nh, pin, s->ck_in[par], s->front));
+        s->cur ^= 1;
+    }
+    if (k.fir) {
+        // the synthesis' linear input rows [J - 1 samples before the chunk | the chunk]: the head from the synthesis' history
+        // (first chunk) or from the tail of the other parity's rows (the chunk before: always full)
+        const void* head[2] = {c == 0 ? s->fs_hist[k.cur_first][0] : s->ck_xrow[par ^ 1][0],
+                               c == 0 ? s->fs_hist[k.cur_first][1] : s->ck_xrow[par ^ 1][1]};
+        void* rows[2] = {s->ck_xrow[par][0], s->ck_xrow[par][1]};
+        SIGCHK(h, apv_launch_fir_synth_rows(f64, s->taps, H, nc, head, c == 0 ? 0 : (size_t)chunk * H, pin, rows, s->front));
+    }
+    {
+        // K1: every (hop, channel) of the chunk in one launch
+        const K1Jobs j = k1_jobs(s, s->ck_resp[par], s->ck_tresp[par], s->xspec_chunk);
+        SIGCHK(h, apv_launch_fir_fft_chunk(f64, s->fir_F, 6, j.jh, j.jx, (long)(2 * (s->fir_F / 2 + 1)), j.jr, j.jc, P, H, RL, N - H, nc, s->front));
+    }
+    if (s->live.hops_left > 0) {
+        // the chunk's share of the pending correction tails, on the samples the per-hop path would add them to
+        void* dst[6] = {s->ck_resp[par][0], s->ck_resp[par][1], s->ck_resp[par][2], s->ck_resp[par][3], s->ck_tresp[par][0],
+                        s->ck_tresp[par][1]};
+        if (int rc = apv_live_apply(h, s->live, P, C, M, f64, dst, nc * H, nc * H, RL, N - H, RL, s->front)) return rc;
+        apv_live_advance(s->live, nc);
+    }
+    {
+        // K2: every analysis transform of the chunk in one launch; hop i's block starts i H samples into the rows
+        const AnalysisJobs j = analysis_jobs(s, s->ck_resp[par], s->ck_tresp[par], s->ck_in[par], chunk_set(s, par, 0));
+        std::string why;
+        hipError_t e = apv_launch_stft_analysis_chunk(f64, N, j.nj, j.jx, j.jch, j.jspec, j.jsc, j.jsk, RL, H, j.jhop, nc, s->front, &why);
+        if (e != hipSuccess) return launch_fail(h, e, why);
+    }
+    for (int i = 0; i < nc; ++i)
+        if (int rc = enqueue_weighting(h, chunk_set(s, par, i), s->front)) return rc;
+    SIGCHK(h, hipEventRecord(s->ev_front[par], s->front));
+    return APV_OK;
+}
+
+// hop i of the chunk behind its filters (and their projection): K3 on `st`, K4 where `sch` says
+static int chunk_hop_outputs(const ChunkCall& k, hipStream_t st, int par, int i, const BackSchedule& sch) {
+    void *wz[2], *lz[2];
+    chunk_filters(k, i, wz, lz);
+    int rc = back_output_spectra(k.h, st, chunk_set(k.s, par, i), wz, sch);
+    if (rc == APV_OK) rc = back_synthesis(k.h, st, nullptr, sch);
+    return rc;
+}
+
+// Back halves of chunk c, regime (a): the joint diagonalisations of the whole chunk as ONE launch (blockIdx.z = hop), then output
+// spectra and synthesis hop by hop.  A hop's 2050 waves are two per SIMD, all head and tail; every input of the
+// sixteen exists once the chunk's transforms have ended, and sixteen hops are a launch of the headline's size.  Same values per bin.
+// A constrained stream projects the chunk's filters behind the launch, on the same stream.
+static int chunk_back_batched(ChunkCall& k, int c, int nc) {
+    apv_handle* h = k.h;
+    apv_stream* s = k.s;
+    const int par = c & 1;
+    const size_t e2 = 2 * s->esz;
+    hipStream_t b0 = k.bs[0];
+    SIGCHK(h, hipStreamWaitEvent(b0, s->ev_front[par], 0));
+    if (c >= 2) SIGCHK(h, hipStreamWaitEvent(b0, s->ck_done[(c - 2) % CK_NS], 0));        // the result slots of this parity are free
+    {
+        char* const obuf0 = (char*)s->ck_out + (size_t)par * s->sig_chunk * hop_result_bytes(s);
+        GevdParams p = fused_gevd_params(h, chunk_set(s, par, 0), s->ck_wall, s->ck_lamall, reinterpret_cast<int32_t*>(obuf0 + hop_out_bytes(s)));
+        p.yield_issue = 1;
+        p.n_hops = nc;
+        p.hop_X = (size_t)s->Kp * s->C * e2;
+        p.hop_d = (size_t)s->K * s->M * e2;
+        p.hop_w = k.hop_w;
+        p.hop_lam = k.hop_lam;
+        p.hop_status = hop_result_bytes(s);
+        std::string why;
+        hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, b0, &why);
+        if (e != hipSuccess) return launch_fail(h, e, why);
+    }
+    if (k.cons)
+        if (int rc = chunk_project(k, b0, nc)) return rc;
+    if (k.fir) {
+        // K3 and K4 are not launched: the chunk's synthesis writes the result slots, and the tail stream only copies them back
+        if (int rc = chunk_synthesis(k, b0, par, nc)) return rc;
+        SIGCHK(h, hipEventRecord(s->ck_k3[0], b0));
+        SIGCHK(h, hipStreamWaitEvent(s->tail, s->ck_k3[0], 0));
+        SIGCHK(h, hipEventRecord(s->ck_backdone[par][0], b0));
+        k.last_par = par; k.last_nc = nc; k.last_b = 0;
+        s->hop += nc;
+        return APV_OK;
+    }
+    for (int i = 0; i < nc; ++i) {
+        BackSchedule sch = chunk_slots(s, par, i);
+        sch.spectra_free = s->ck_k3[0];
+        sch.tail_stream = s->tail;
+        if (int rc = chunk_hop_outputs(k, b0, par, i, sch)) return rc;
+        if (i + 1 == nc) SIGCHK(h, hipEventRecord(s->ck_backdone[par][0], b0));
+        k.last_par = par; k.last_nc = nc; k.last_b = 0;
+        s->hop++;
+    }
+    return APV_OK;
+}
+
+// Back halves of chunk c, regime (b): hop by hop, alternating between the back streams (configurations the batched launch does
+// not take).
+static int chunk_back_hops(ChunkCall& k, int c, int nc) {
+    apv_handle* h = k.h;
+    apv_stream* s = k.s;
+    const int par = c & 1;
+    for (int i = 0; i < nc; ++i) {
+        const int b = (int)((s->hop - k.hop_first) % CK_NB);
+        if (i < CK_NB) {
+            SIGCHK(h, hipStreamWaitEvent(k.bs[b], s->ev_front[par], 0));
+            // the result slots of this parity are being copied back for chunk c - 2 (still in flight: the host collects two
+            // chunks behind)
+            if (c >= 2) SIGCHK(h, hipStreamWaitEvent(k.bs[b], s->ck_done[(c - 2) % CK_NS], 0));
+            // a constrained stream: the tail stream is done with the filters and taps of chunk c - 1 (one set of each)
+            if (k.cons && c >= 1) SIGCHK(h, hipStreamWaitEvent(k.bs[b], s->ck_wallfree, 0));
+        }
+        // Every hop of the two chunks in flight has result and output-spectra slots of its own, so a back stream never waits
+        // for the tail stream inside a chunk: its next diagonalisation follows the previous one directly.
+        BackSchedule sch = chunk_slots(s, par, i);
+        sch.yield_issue = 1;
+        sch.lspill = b > 0 ? s->ck_spill[b - 1] : nullptr;
+        int rc;
+        if (k.cons) {
+            // the back stream runs the joint diagonalisation alone, into the hop's own slots of ck_wall / ck_lamall: the
+            // projections share one taps buffer and the cross-fade needs hop order, both of which the tail stream keeps
+            // (chunk_constrained_tail)
+            void *wz[2], *lz[2];
+            chunk_filters(k, i, wz, lz);
+            rc = back_solve(h, k.bs[b], chunk_set(s, par, i), wz, lz, sch);
+        } else {
+            sch.spectra_free = s->ck_k3[b];                  // recorded after K3: the tail stream starts the synthesis there
+            sch.tail_stream = s->tail;
+            rc = enqueue_back(h, k.bs[b], chunk_set(s, par, i), k.wset[b], k.lset[b], nullptr, sch);
+        }
+        if (rc != APV_OK) return rc;
+        if (i + CK_NB >= nc) SIGCHK(h, hipEventRecord(s->ck_backdone[par][b], k.bs[b]));   // this stream's last hop of the chunk
+        k.last_par = par; k.last_nc = nc; k.last_b = b;
+        s->hop++;
+    }
+    return APV_OK;
+}
+
+// A constrained stream in regime (b): the tail stream, behind the chunk's last diagonalisation on every back stream, runs the
+// chunk's projection, then K3 + K4 hop by hop, or the chunk's FIR synthesis.
+static int chunk_constrained_tail(const ChunkCall& k, int par, int nc) {
+    apv_handle* h = k.h;
+    const apv_stream* s = k.s;
+    for (int b = 0; b < CK_NB; ++b) SIGCHK(h, hipStreamWaitEvent(s->tail, s->ck_backdone[par][b], 0));
+    int rc = chunk_project(k, s->tail, nc);
+    if (rc == APV_OK && k.fir) rc = chunk_synthesis(k, s->tail, par, nc);
+    for (int i = 0; i < nc && !k.fir && rc == APV_OK; ++i) rc = chunk_hop_outputs(k, s->tail, par, i, chunk_slots(s, par, i));
+    if (rc != APV_OK) return rc;
+    SIGCHK(h, hipEventRecord(s->ck_wallfree, s->tail));
+    return APV_OK;
+}
+
+// the chunk's results in ONE copy behind its last synthesis (16 hops: 6.4 MB at cfg3)
+static int chunk_copy_back(const ChunkCall& k, int c, int nc) {
+    apv_handle* h = k.h;
+    const apv_stream* s = k.s;
+    const size_t chunk_bytes = (size_t)s->sig_chunk * hop_result_bytes(s);
+    SIGCHK(h, hipMemcpyAsync((char*)s->ck_pin_out + (size_t)(c % CK_NS) * chunk_bytes, (char*)s->ck_out + (size_t)(c & 1) * chunk_bytes,
+                             (size_t)nc * hop_result_bytes(s), hipMemcpyDeviceToHost, s->tail));
+    SIGCHK(h, hipEventRecord(s->ck_done[c % CK_NS], s->tail)); // every front and back half of the chunk is upstream of this copy
+    return APV_OK;
+}
+
+// Behind the last chunk, every stream drained: the state n_hops per-hop calls would have left.
+static int chunk_leave_state(ChunkCall& k) {
+    apv_handle* h = k.h;
+    apv_stream* s = k.s;
+    const int N = s->N, H = s->H, K = s->K, M = s->M, C = s->C, f64 = s->f64, RL = s->ck_RL, J = s->taps;
+    const size_t e1 = s->esz, e2 = 2 * s->esz;
+    SIGCHK(h, hipStreamSynchronize(s->front));
+    for (int b = 1; b < CK_NB; ++b) SIGCHK(h, hipStreamSynchronize(k.bs[b]));
+    SIGCHK(h, hipStreamSynchronize(s->tail));
+    SIGCHK(h, hipStreamSynchronize(k.bs[0]));
+    const long done = s->hop - k.hop_first;
+    if (done <= 0) return APV_OK;
+    hipStream_t st = k.bs[0];
+    const int last_par = k.last_par, last_nc = k.last_nc;
+    // rings: the last hop's block, written at the ring offset the per-hop path (and its captured graphs) expects after
+    // `done` more hops
+    s->ring_off = (int)((k.ring_first + done * H) % N);
+    const int src0 = (last_nc - 1) * H;
+    for (int p = 0; p < 4; ++p) SIGCHK(h, apv_launch_rows_copy(f64, C, N, s->resp[p], N, s->ring_off, N, s->ck_resp[last_par][p], RL, src0, RL, st));
+    for (int z = 0; z < 2; ++z) SIGCHK(h, apv_launch_rows_copy(f64, M, N, s->tresp[z], N, s->ring_off, N, s->ck_tresp[last_par][z], RL, src0, RL, st));
+    SIGCHK(h, apv_launch_rows_copy(f64, 2, N, s->inblk, N, s->ring_off, N, s->ck_in[last_par], RL, src0, RL, st));
+    // histories: the per-hop path alternates the two buffers every hop
+    const int cur_expected = k.cur_first ^ (int)(done & 1);
+    if (s->cur != cur_expected) {
+        const size_t hb = ((size_t)s->P - 1 + H + s->pad) * e1;
+        for (int g = 0; g < 2; ++g) SIGCHK(h, hipMemcpyAsync(s->xhist[cur_expected][g], s->xhist[s->cur][g], hb, hipMemcpyDeviceToDevice, st));
+        s->cur = cur_expected;
+    }
+    // the last hop's spectra, filters and eigenvalues where the state arrays and the per-hop path keep them
+    const HopSpectra q = chunk_set(s, last_par, last_nc - 1);
+    for (int p = 0; p < 4; ++p) SIGCHK(h, hipMemcpyAsync(s->X[p], q.X[p], (size_t)s->Kp * C * e2, hipMemcpyDeviceToDevice, st));
+    for (int z = 0; z < 2; ++z) SIGCHK(h, hipMemcpyAsync(s->tspec[z], q.tspec[z], (size_t)K * M * e2, hipMemcpyDeviceToDevice, st));
+    SIGCHK(h, hipMemcpyAsync(s->inspec, q.inspec, (size_t)2 * K * e2, hipMemcpyDeviceToDevice, st));
+    if (k.batched || k.cons) {
+        void *wz[2], *lz[2];
+        chunk_filters(k, last_nc - 1, wz, lz);
+        for (int z = 0; z < 2; ++z) {
+            SIGCHK(h, hipMemcpyAsync(s->w[z], wz[z], k.hop_w, hipMemcpyDeviceToDevice, st));
+            SIGCHK(h, hipMemcpyAsync(s->lam[z], lz[z], k.hop_lam, hipMemcpyDeviceToDevice, st));
+        }
+        // a constrained stream: the last hop's taps, and the newest J - 1 input samples in the history buffer the next per-hop
+        // call reads (fs_taps took the last hop's taps behind the chunk's synthesis)
+        for (int z = 0; z < 2 && k.cons; ++z)
+            if (s->zones & (1 << z))
+                SIGCHK(h, hipMemcpyAsync(s->wtaps[z], (char*)s->ck_taps[z] + (size_t)(last_nc - 1) * k.hop_taps, k.hop_taps, hipMemcpyDeviceToDevice, st));
+        for (int g = 0; g < 2 && k.fir && J > 1; ++g)
+            SIGCHK(h, hipMemcpyAsync(s->fs_hist[s->cur][g], (char*)s->ck_xrow[last_par][g] + (size_t)last_nc * H * e1, (size_t)(J - 1) * e1,
+                                     hipMemcpyDeviceToDevice, st));
+    } else if (k.last_b != 0) {
+        for (int z = 0; z < 2; ++z) {
+            SIGCHK(h, hipMemcpyAsync(s->w[z], k.wset[k.last_b][z], k.hop_w, hipMemcpyDeviceToDevice, st));
+            SIGCHK(h, hipMemcpyAsync(s->lam[z], k.lset[k.last_b][z], k.hop_lam, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    SIGCHK(h, hipStreamSynchronize(st));
+    return APV_OK;
+}
+
 // n_hops consecutive hops in one call, a CHUNK of hops at a time (responses of >= 64 taps, i.e. K1 by fast convolution).
 //
 // Nothing in the front half of a hop (input histories, K1, analysis transforms, perceptual weighting) depends on any hop's
@@ -1080,399 +1555,28 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     SCHK(h, hipSetDevice(h->device));
     int rc = chunk_prepare(h);
     if (rc != APV_OK) return rc;
-    const int N = s->N, H = s->H, K = s->K, L = s->L, M = s->M, C = s->C, P = s->P, f64 = s->f64, chunk = s->sig_chunk, RL = s->ck_RL;
-    const size_t e1 = s->esz, e2 = 2 * s->esz;
-    const bool runA = s->zones & 1, runB = s->zones & 2;
-    // a constrained stream: ONE projection launch per chunk behind the chunk's joint diagonalisations, whose filters all go to
-    // ck_wall; with FIR synthesis ONE synthesis launch per chunk in place of K3 and K4 (see the two regimes below)
-    const bool cons = s->taps > 0, fir = s->fir_synth != 0;
-    const int J = s->taps;
-    const size_t hop_w = (size_t)K * s->nV * L * wsz(h), hop_lam = (size_t)K * L * lsz(h), hop_taps = (size_t)s->nV * J * L * lsz(h);
-    // the chunk's joint diagonalisations as one launch where the kernel that will run takes several hops (order 16, absolute loading,
-    // no diagnostics); elsewhere hop by hop on the back streams
-    bool batched = false;
-    {
-        GevdParams probe = apv_base_params(h);
-        probe.x_c128 = f64;
-        probe.x_group = s->xg;
-        probe.n_hops = 2;
-        static const bool force_generic = getenv("APV_FORCE_GENERIC") != nullptr;
-        batched = !force_generic && apv_gevd16m_takes_hops(probe, h->cfg.compute_dtype, true);
-    }
-    if (!batched)
-        for (int b = 0; b + 1 < CK_NB; ++b)
-            if (!s->ck_back[b]) SCHK(h, s->own.stream(&s->ck_back[b], hipStreamNonBlocking));
-    hipStream_t bs[CK_NB];
-    void* wset[CK_NB][2];
-    void* lset[CK_NB][2];
-    for (int b = 0; b < CK_NB; ++b) {
-        bs[b] = (b && s->ck_back[b - 1]) ? s->ck_back[b - 1] : h->stream;
-        for (int z = 0; z < 2; ++z) {
-            wset[b][z] = b ? s->ck_w[b - 1][z] : s->w[z];
-            lset[b][z] = b ? s->ck_lam[b - 1][z] : s->lam[z];
-        }
-    }
-    const int n_chunks = (n_hops + chunk - 1) / chunk;
-    const long hop_first = s->hop;
-    const int ring_first = s->ring_off, cur_first = s->cur;
-    int worst = APV_OK;
-    std::string worst_msg;
-    int c_done = 0;
-    auto bail = [&](int code, const std::string& msg) {
-        return signal_bail(h, bs, CK_NB, n_hops, hop_first, (long)c_done * chunk, code, msg);
-    };
-    auto hipbail = [&](hipError_t e) { return bail(APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e)); };
-#define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) return hipbail(_e); } while (0)
+    ChunkCall k;
+    if ((rc = chunk_begin(h, k)) != APV_OK) return rc;
+    const int H = s->H, chunk = s->sig_chunk;
     // staging slot c mod 3 holds chunk c
-    auto collect = [&](int c) -> int {
+    SignalCall<TI> call(h, n_hops, h_out, k.bs, CK_NB, s->ck_done, s->ck_pin_out, CK_NS);
+    for (int c = 0; c < call.n_chunks && call.worst.code != APV_ERR_NOT_PD; ++c) {
         const int base = c * chunk, nc = std::min(chunk, n_hops - base);
-        hipError_t e = hipEventSynchronize(s->ck_done[c % CK_NS]);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string("apv_process_signal: ") + hipGetErrorString(e));
-        collect_hops(h, (const char*)s->ck_pin_out + (size_t)(c % CK_NS) * chunk * hop_result_bytes(s), n_hops, base, nc, hop_first,
-                     h_out, worst, worst_msg);
-        return APV_OK;
-    };
-    // the spectra set of hop i of a chunk of parity par
-    auto set_of = [&](int par, int i) {
-        HopSpectra q;
-        const size_t idx = (size_t)par * chunk + i;
-        for (int p = 0; p < 4; ++p) q.X[p] = (char*)s->ck_X[p] + idx * (size_t)s->Kp * C * e2;
-        for (int z = 0; z < 2; ++z) q.tspec[z] = (char*)s->ck_tspec[z] + idx * K * M * e2;
-        q.inspec = (char*)s->ck_inspec + idx * 2 * K * e2;
-        return q;
-    };
-    const size_t spec_bytes = ((size_t)s->fir_F / 2 + 1) * e2;       // one input spectrum of K1
-    int last_par = 0, last_nc = 0, last_b = 0;
-    std::string why;
-    // the filters of the chunk's nc hops (ck_wall) projected in place, their taps to ck_taps: one launch on `st`
-    auto project_chunk = [&](hipStream_t st, int nc) -> hipError_t {
-        void *cw[2], *ct[2];
-        int nz = 0;
-        for (int z = 0; z < 2; ++z) {
-            if (!(z ? runB : runA)) continue;
-            cw[nz] = s->ck_wall[z]; ct[nz] = s->ck_taps[z]; ++nz;
-        }
-        return apv_launch_constrain_filters_hops(h->cfg.out_c128, N, J, s->nV, L, nz, cw, ct, nc, hop_w / wsz(h), hop_taps / lsz(h), st, &why);
-    };
-    // the FIR synthesis of the chunk's nc hops into their result slots: one launch on `st`, hop i fading from the taps of hop i - 1
-    // (hop 0 from fs_taps), and behind it the last hop's taps to fs_taps for the next chunk or call
-    auto synth_chunk = [&](hipStream_t st, int par, int nc) -> hipError_t {
-        FirSynthArgs a{};
-        int nz = 0;
-        for (int z = 0; z < 2; ++z) {
-            if (!(z ? runB : runA)) continue;
-            a.prev[nz] = s->fs_taps[z]; a.cur[nz] = s->ck_taps[z]; a.sig[nz] = z; ++nz;
-        }
-        for (int g = 0; g < 2; ++g) {
-            a.xhist[g] = s->ck_xrow[par][g];
-            a.xhop[g] = (const char*)s->ck_xrow[par][g] + (size_t)(J - 1) * e1;
-        }
-        a.nz = nz; a.nV = s->nV; a.L = L; a.J = J; a.H = H;
-        a.n_tgt = 2; a.ref = s->fs_ref; a.delay = s->fs_delay;
-        a.out = (char*)s->ck_out + (size_t)par * chunk * hop_result_bytes(s);
-        a.sn = s->out_group > 0 ? L : 1;
-        a.sl = s->out_group > 0 ? 1 : H;
-        a.n_hops = nc; a.hop_taps = hop_taps / lsz(h); a.hop_x = H; a.hop_out = hop_result_bytes(s);
-        hipError_t e = apv_launch_fir_synthesis(h->cfg.out_c128, f64, a, st, &why);
-        for (int z = 0; z < 2 && e == hipSuccess; ++z)
-            if (z ? runB : runA)
-                e = hipMemcpyAsync(s->fs_taps[z], (char*)s->ck_taps[z] + (size_t)(nc - 1) * hop_taps, hop_taps, hipMemcpyDeviceToDevice, st);
-        return e;
-    };
-    auto ckl = [&](hipError_t e) { return bail(APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why); };
-    for (int c = 0; c < n_chunks && worst != APV_ERR_NOT_PD; ++c) {
-        const int base = c * chunk, nc = std::min(chunk, n_hops - base), par = c & 1;
-        char* const pin = (char*)s->ck_pin_in + (size_t)(c % CK_NS) * chunk * 2 * H * e1;
+        char* const pin = (char*)s->ck_pin_in + (size_t)(c % CK_NS) * chunk * 2 * H * s->esz;
         stage_hops(s, h_in_A, h_in_B, base, nc, pin);        // staging slot c mod 3: chunk c - 3 was collected an iteration ago
-        // ---------------- front half of the whole chunk ----------------
-        // the spectra sets and linear buffers of this parity were last read by the back halves of chunk c - 2
-        if (c >= 2)
-            for (int b = 0; b < CK_NB; ++b) CK(hipStreamWaitEvent(s->front, s->ck_backdone[par][b], 0));
-        // ... and, in a constrained stream, by what follows the chunk's projection: K3, or the synthesis reading the input rows
-        if (cons && c >= 2) CK(hipStreamWaitEvent(s->front, s->ck_done[(c - 2) % CK_NS], 0));
-        CK(apv_launch_fir_chunk_spectra(f64, s->fir_F, P, H, nc, s->xhist[s->cur][0], s->xhist[s->cur][1], pin, s->xspec_chunk, s->front));
-        // heads of the linear buffers: the newest N - H samples before the chunk, from the rings (first chunk) or from the tail
-        // of the previous chunk's buffers
-        {
-            const int prev = par ^ 1, prev_nc = chunk;               // every chunk but the last is full
-            auto head = [&](void* dst, const void* ring, const void* lin_prev, int rows) -> hipError_t {
-                if (c == 0) return apv_launch_rows_copy(f64, rows, N - H, dst, RL, 0, RL, ring, N, (H + ring_first) % N, N, s->front);
-                return apv_launch_rows_copy(f64, rows, N - H, dst, RL, 0, RL, lin_prev, RL, prev_nc * H, RL, s->front);
-            };
-            for (int p = 0; p < 4; ++p) CK(head(s->ck_resp[par][p], s->resp[p], s->ck_resp[prev][p], C));
-            for (int z = 0; z < 2; ++z) CK(head(s->ck_tresp[par][z], s->tresp[z], s->ck_tresp[prev][z], M));
-            CK(head(s->ck_in[par], s->inblk, s->ck_in[prev], 2));
-        }
-        {
-            const void* oh[2] = {s->xhist[s->cur][0], s->xhist[s->cur][1]};
-            void* nh[2] = {s->xhist[s->cur ^ 1][0], s->xhist[s->cur ^ 1][1]};
-            CK(apv_launch_chunk_inputs(f64, P, H, N, nc, s->pad, RL, oh, nh, pin, s->ck_in[par], s->front));
-            s->cur ^= 1;
-        }
-        if (fir) {
-            // the synthesis' linear input rows [J - 1 samples before the chunk | the chunk]: the head from the synthesis' history
-            // (first chunk) or from the tail of the other parity's rows (the chunk before: always full)
-            const void* head[2] = {c == 0 ? s->fs_hist[cur_first][0] : s->ck_xrow[par ^ 1][0],
-                                   c == 0 ? s->fs_hist[cur_first][1] : s->ck_xrow[par ^ 1][1]};
-            void* rows[2] = {s->ck_xrow[par][0], s->ck_xrow[par][1]};
-            CK(apv_launch_fir_synth_rows(f64, J, H, nc, head, c == 0 ? 0 : (size_t)chunk * H, pin, rows, s->front));
-        }
-        {
-            // K1: every (hop, channel) of the chunk in one launch
-            const void *jh[6], *jx[6];
-            void* jr[6];
-            int jc[6];
-            for (int p = 0; p < 4; ++p) {
-                jh[p] = s->rirspec[path_zone(p)]; jx[p] = (const char*)s->xspec_chunk + spec_bytes * path_sig(p);
-                jr[p] = s->ck_resp[par][p]; jc[p] = C;
-            }
-            for (int z = 0; z < 2; ++z) {
-                jh[4 + z] = s->trirspec[z]; jx[4 + z] = (const char*)s->xspec_chunk + spec_bytes * z;
-                jr[4 + z] = s->ck_tresp[par][z]; jc[4 + z] = M;
-            }
-            CK(apv_launch_fir_fft_chunk(f64, s->fir_F, 6, jh, jx, (long)(2 * (s->fir_F / 2 + 1)), jr, jc, P, H, RL, N - H, nc, s->front));
-        }
-        if (s->live.hops_left > 0) {
-            // the chunk's share of the pending correction tails, on the samples the per-hop path would add them to
-            void* dst[6] = {s->ck_resp[par][0], s->ck_resp[par][1], s->ck_resp[par][2], s->ck_resp[par][3], s->ck_tresp[par][0],
-                            s->ck_tresp[par][1]};
-            if ((rc = apv_live_apply(h, s->live, P, C, M, f64, dst, nc * H, nc * H, RL, N - H, RL, s->front)) != APV_OK) return bail(rc, h->err);
-            apv_live_advance(s->live, nc);
-        }
-        {
-            // K2: every analysis transform of the chunk in one launch; hop i's block starts i H samples into the rows
-            const HopSpectra q0 = set_of(par, 0);
-            const void* jx[7];
-            void* jspec[7];
-            int jch[7], nj = 0;
-            long jsc[7], jsk[7], jhop[7];
-            for (int p = 0; p < 4; ++p) {
-                const bool need = (p < 2) ? runA : runB;
-                if (!need) continue;
-                jx[nj] = s->ck_resp[par][p]; jspec[nj] = q0.X[p]; jch[nj] = C; jsc[nj] = s->xg; jsk[nj] = C; jhop[nj] = (long)s->Kp * C; ++nj;
-            }
-            for (int z = 0; z < 2; ++z) {
-                jx[nj] = s->ck_tresp[par][z]; jspec[nj] = q0.tspec[z]; jch[nj] = M; jsc[nj] = 1; jsk[nj] = M; jhop[nj] = (long)K * M; ++nj;
-            }
-            jx[nj] = s->ck_in[par]; jspec[nj] = q0.inspec; jch[nj] = 2; jsc[nj] = K; jsk[nj] = 1; jhop[nj] = 2L * K; ++nj;
-            hipError_t e = apv_launch_stft_analysis_chunk(f64, N, nj, jx, jch, jspec, jsc, jsk, RL, H, jhop, nc, s->front, &why);
-            if (e != hipSuccess) return bail(APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
-        }
-        if (s->nch > 0) {
-            for (int i = 0; i < nc; ++i) {
-                const HopSpectra q = set_of(par, i);
-                for (int z = 0; z < 2; ++z)
-                    CK(apv_launch_perceptual_weights(f64, K, M, s->nch, q.tspec[z], s->G2, s->G2T, s->Cs, s->Ca, s->Leff, N, s->norm_mode,
-                                                     s->Wgt[z], s->front));
-                for (int p = 0; p < 4; ++p) {
-                    const bool need = (p < 2) ? runA : runB;
-                    if (need) CK(apv_launch_scale_spectra(f64, K, C, L, q.X[p], s->Wgt[path_zone(p)], s->front));
-                }
-                for (int z = 0; z < 2; ++z) CK(apv_launch_scale_spectra(f64, K, M, 1, q.tspec[z], s->Wgt[z], s->front));
-            }
-        }
-        CK(hipEventRecord(s->ev_front[par], s->front));
-        // ---------------- back halves ----------------
-        // (a) the joint diagonalisations of the whole chunk as ONE launch (blockIdx.z = hop), then output spectra and synthesis hop
-        //     by hop.  A hop's 2050 waves are two per SIMD, all head and tail; every input of the sixteen exists once
-        //     the chunk's transforms have ended, and sixteen hops are a launch of the headline's size.  Same values per bin.
-        if (batched) {
-            hipStream_t b0 = bs[0];
-            CK(hipStreamWaitEvent(b0, s->ev_front[par], 0));
-            if (c >= 2) CK(hipStreamWaitEvent(b0, s->ck_done[(c - 2) % CK_NS], 0));        // the result slots of this parity are free
-            {
-                GevdParams p = apv_base_params(h);
-                const HopSpectra q0 = set_of(par, 0);
-                const int first = runA ? 0 : 1;
-                char* const obuf0 = (char*)s->ck_out + (size_t)par * chunk * hop_result_bytes(s);
-                int32_t* const st0 = reinterpret_cast<int32_t*>(obuf0 + hop_out_bytes(s));
-                p.x_c128 = f64;
-                p.x_group = s->xg;
-                p.XB = first ? q0.X[3] : q0.X[0];
-                p.XD = first ? q0.X[2] : q0.X[1];
-                p.d = q0.tspec[first];
-                p.w = s->ck_wall[first];
-                p.lam = s->ck_lamall[first];
-                p.status = st0 + (size_t)first * K;
-                p.n_zones = (runA && runB) ? 2 : 1;
-                p.yield_issue = 1;
-                if (p.n_zones == 2) {
-                    p.XB1 = q0.X[3]; p.XD1 = q0.X[2]; p.d1 = q0.tspec[1];
-                    p.w1 = s->ck_wall[1]; p.lam1 = s->ck_lamall[1]; p.status1 = st0 + K;
-                }
-                p.n_hops = nc;
-                p.hop_X = (size_t)s->Kp * C * e2;
-                p.hop_d = (size_t)K * M * e2;
-                p.hop_w = hop_w;
-                p.hop_lam = hop_lam;
-                p.hop_status = hop_result_bytes(s);
-                hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, b0, &why);
-                if (e != hipSuccess) return bail(APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
-            }
-            if (cons) {
-                const hipError_t e = project_chunk(b0, nc);
-                if (e != hipSuccess) return ckl(e);
-            }
-            if (fir) {
-                // K3 and K4 are not launched: the chunk's synthesis writes the result slots, and the tail stream only copies them back
-                const hipError_t e = synth_chunk(b0, par, nc);
-                if (e != hipSuccess) return ckl(e);
-                CK(hipEventRecord(s->ck_k3[0], b0));
-                CK(hipStreamWaitEvent(s->tail, s->ck_k3[0], 0));
-                CK(hipEventRecord(s->ck_backdone[par][0], b0));
-                last_par = par; last_nc = nc; last_b = 0;
-                s->hop += nc;
-            }
-            for (int i = 0; i < nc && !fir; ++i) {
-                const size_t slot = (size_t)par * chunk + i;
-                BackSchedule sch;
-                sch.skip_gevd = true;
-                sch.skip_constrain = cons;
-                sch.spectra_free = s->ck_k3[0];
-                sch.tail_stream = s->tail;
-                sch.result = (char*)s->ck_out + slot * hop_result_bytes(s);
-                sch.ospec = (char*)s->ck_ospec + slot * (size_t)s->n_out * K * e2;
-                sch.no_copy = true;
-                void* wz[2] = {(char*)s->ck_wall[0] + i * hop_w, (char*)s->ck_wall[1] + i * hop_w};
-                void* lz[2] = {(char*)s->ck_lamall[0] + i * hop_lam, (char*)s->ck_lamall[1] + i * hop_lam};
-                rc = enqueue_back(h, b0, set_of(par, i), wz, lz, nullptr, sch);
-                if (rc != APV_OK) return bail(rc, h->err);
-                if (i + 1 == nc) CK(hipEventRecord(s->ck_backdone[par][0], b0));
-                last_par = par; last_nc = nc; last_b = 0;
-                s->hop++;
-            }
-        }
-        // (b) hop by hop, alternating between the back streams (configurations the batched launch does not take)
-        for (int i = 0; i < nc && !batched; ++i) {
-            const int b = (int)((s->hop - hop_first) % CK_NB);
-            if (i < CK_NB) {
-                CK(hipStreamWaitEvent(bs[b], s->ev_front[par], 0));
-                // the result slots of this parity are being copied back for chunk c - 2 (still in flight: the host collects two
-                // chunks behind)
-                if (c >= 2) CK(hipStreamWaitEvent(bs[b], s->ck_done[(c - 2) % CK_NS], 0));
-                // a constrained stream: the tail stream is done with the filters and taps of chunk c - 1 (one set of each)
-                if (cons && c >= 1) CK(hipStreamWaitEvent(bs[b], s->ck_wallfree, 0));
-            }
-            // Every hop of the two chunks in flight has result and output-spectra slots of its own, so a back stream never waits
-            // for the tail stream inside a chunk: its next diagonalisation follows the previous one directly.
-            const size_t slot = (size_t)par * chunk + i;
-            BackSchedule sch;
-            sch.spectra_free = s->ck_k3[b];                  // recorded after K3: the tail stream starts the synthesis there
-            sch.tail_stream = s->tail;
-            sch.result = (char*)s->ck_out + slot * hop_result_bytes(s);
-            sch.ospec = (char*)s->ck_ospec + slot * (size_t)s->n_out * K * e2;
-            sch.no_copy = true;
-            sch.yield_issue = 1;
-            sch.lspill = b > 0 ? s->ck_spill[b - 1] : nullptr;
-            if (cons) {
-                // the back stream runs the joint diagonalisation alone, into the hop's own slots of ck_wall / ck_lamall: the
-                // projections share one taps buffer and the cross-fade needs hop order, both of which the tail stream keeps (below)
-                void* wz[2] = {(char*)s->ck_wall[0] + i * hop_w, (char*)s->ck_wall[1] + i * hop_w};
-                void* lz[2] = {(char*)s->ck_lamall[0] + i * hop_lam, (char*)s->ck_lamall[1] + i * hop_lam};
-                sch.gevd_only = true;
-                sch.spectra_free = nullptr;
-                rc = enqueue_back(h, bs[b], set_of(par, i), wz, lz, nullptr, sch);
-            } else {
-                rc = enqueue_back(h, bs[b], set_of(par, i), wset[b], lset[b], nullptr, sch);
-            }
-            if (rc != APV_OK) return bail(rc, h->err);
-            if (i + CK_NB >= nc) CK(hipEventRecord(s->ck_backdone[par][b], bs[b]));   // this stream's last hop of the chunk
-            last_par = par; last_nc = nc; last_b = b;
-            s->hop++;
-        }
-        if (cons && !batched) {
-            // the tail stream, behind the chunk's last diagonalisation on every back stream: the chunk's projection, then K3 + K4 hop
-            // by hop, or the chunk's FIR synthesis
-            for (int b = 0; b < CK_NB; ++b) CK(hipStreamWaitEvent(s->tail, s->ck_backdone[par][b], 0));
-            hipError_t e = project_chunk(s->tail, nc);
-            if (e == hipSuccess && fir) e = synth_chunk(s->tail, par, nc);
-            if (e != hipSuccess) return ckl(e);
-            for (int i = 0; i < nc && !fir; ++i) {
-                const size_t slot = (size_t)par * chunk + i;
-                BackSchedule sch;
-                sch.skip_gevd = true;
-                sch.skip_constrain = true;
-                sch.result = (char*)s->ck_out + slot * hop_result_bytes(s);
-                sch.ospec = (char*)s->ck_ospec + slot * (size_t)s->n_out * K * e2;
-                sch.no_copy = true;
-                void* wz[2] = {(char*)s->ck_wall[0] + i * hop_w, (char*)s->ck_wall[1] + i * hop_w};
-                void* lz[2] = {(char*)s->ck_lamall[0] + i * hop_lam, (char*)s->ck_lamall[1] + i * hop_lam};
-                rc = enqueue_back(h, s->tail, set_of(par, i), wz, lz, nullptr, sch);
-                if (rc != APV_OK) return bail(rc, h->err);
-            }
-            CK(hipEventRecord(s->ck_wallfree, s->tail));
-        }
-        // the chunk's results in ONE copy behind its last synthesis (16 hops: 6.4 MB at cfg3)
-        CK(hipMemcpyAsync((char*)s->ck_pin_out + (size_t)(c % CK_NS) * chunk * hop_result_bytes(s),
-                          (char*)s->ck_out + (size_t)par * chunk * hop_result_bytes(s), (size_t)nc * hop_result_bytes(s),
-                          hipMemcpyDeviceToHost, s->tail));
-        CK(hipEventRecord(s->ck_done[c % CK_NS], s->tail)); // every front and back half of the chunk is upstream of this copy
+        rc = chunk_front(k, c, nc, pin);
+        if (rc == APV_OK) rc = k.batched ? chunk_back_batched(k, c, nc) : chunk_back_hops(k, c, nc);
+        if (rc == APV_OK && k.cons && !k.batched) rc = chunk_constrained_tail(k, c & 1, nc);
+        if (rc == APV_OK) rc = chunk_copy_back(k, c, nc);
+        if (rc != APV_OK) return call.bail(rc, h->err);
         // the host collects TWO chunks behind: while it waits for chunk c - 2 and copies it out, chunks c - 1 and c are queued on
         // the device, so the front half of chunk c runs beside the back halves of chunk c - 1 whatever the host is doing
         if (c > 1) {
-            if ((rc = collect(c - 2)) != APV_OK) return bail(rc, h->err);
-            c_done = c - 1;
+            if ((rc = call.collect(c - 2)) != APV_OK) return call.bail(rc, h->err);
+            call.c_done = c - 1;
         }
     }
-    for (int c = c_done; c < n_chunks && (size_t)c * chunk < (size_t)(s->hop - hop_first); ++c) {
-        if ((rc = collect(c)) != APV_OK) return bail(rc, h->err);
-        c_done = c + 1;
-    }
-    // ---------------- the state n_hops per-hop calls would have left ----------------
-    {
-        hipError_t e = hipStreamSynchronize(s->front);
-        for (int b = 1; b < CK_NB && e == hipSuccess; ++b) e = hipStreamSynchronize(bs[b]);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->tail);
-        if (e == hipSuccess) e = hipStreamSynchronize(bs[0]);
-        if (e != hipSuccess) return hipbail(e);
-    }
-    const long done = s->hop - hop_first;
-    if (done > 0) {
-        hipStream_t st = bs[0];
-        // rings: the last hop's block, written at the ring offset the per-hop path (and its captured graphs) expects after
-        // `done` more hops
-        s->ring_off = (int)((ring_first + done * H) % N);
-        const int src0 = (last_nc - 1) * H;
-        for (int p = 0; p < 4; ++p) CK(apv_launch_rows_copy(f64, C, N, s->resp[p], N, s->ring_off, N, s->ck_resp[last_par][p], RL, src0, RL, st));
-        for (int z = 0; z < 2; ++z) CK(apv_launch_rows_copy(f64, M, N, s->tresp[z], N, s->ring_off, N, s->ck_tresp[last_par][z], RL, src0, RL, st));
-        CK(apv_launch_rows_copy(f64, 2, N, s->inblk, N, s->ring_off, N, s->ck_in[last_par], RL, src0, RL, st));
-        // histories: the per-hop path alternates the two buffers every hop
-        const int cur_expected = cur_first ^ (int)(done & 1);
-        if (s->cur != cur_expected) {
-            const size_t hb = ((size_t)P - 1 + H + s->pad) * e1;
-            for (int g = 0; g < 2; ++g) CK(hipMemcpyAsync(s->xhist[cur_expected][g], s->xhist[s->cur][g], hb, hipMemcpyDeviceToDevice, st));
-            s->cur = cur_expected;
-        }
-        // the last hop's spectra, filters and eigenvalues where the state arrays and the per-hop path keep them
-        const HopSpectra q = set_of(last_par, last_nc - 1);
-        for (int p = 0; p < 4; ++p) CK(hipMemcpyAsync(s->X[p], q.X[p], (size_t)s->Kp * C * e2, hipMemcpyDeviceToDevice, st));
-        for (int z = 0; z < 2; ++z) CK(hipMemcpyAsync(s->tspec[z], q.tspec[z], (size_t)K * M * e2, hipMemcpyDeviceToDevice, st));
-        CK(hipMemcpyAsync(s->inspec, q.inspec, (size_t)2 * K * e2, hipMemcpyDeviceToDevice, st));
-        if (batched || cons) {
-            for (int z = 0; z < 2; ++z) {
-                CK(hipMemcpyAsync(s->w[z], (char*)s->ck_wall[z] + (size_t)(last_nc - 1) * hop_w, hop_w, hipMemcpyDeviceToDevice, st));
-                CK(hipMemcpyAsync(s->lam[z], (char*)s->ck_lamall[z] + (size_t)(last_nc - 1) * hop_lam, hop_lam, hipMemcpyDeviceToDevice, st));
-            }
-            // a constrained stream: the last hop's taps, and the newest J - 1 input samples in the history buffer the next per-hop
-            // call reads (fs_taps took the last hop's taps behind the chunk's synthesis)
-            for (int z = 0; z < 2 && cons; ++z)
-                if (z ? runB : runA)
-                    CK(hipMemcpyAsync(s->wtaps[z], (char*)s->ck_taps[z] + (size_t)(last_nc - 1) * hop_taps, hop_taps, hipMemcpyDeviceToDevice, st));
-            for (int g = 0; g < 2 && fir && J > 1; ++g)
-                CK(hipMemcpyAsync(s->fs_hist[s->cur][g], (char*)s->ck_xrow[last_par][g] + (size_t)last_nc * H * e1, (size_t)(J - 1) * e1,
-                                  hipMemcpyDeviceToDevice, st));
-        } else if (last_b != 0) {
-            for (int z = 0; z < 2; ++z) {
-                CK(hipMemcpyAsync(s->w[z], wset[last_b][z], (size_t)K * s->nV * L * wsz(h), hipMemcpyDeviceToDevice, st));
-                CK(hipMemcpyAsync(s->lam[z], lset[last_b][z], (size_t)K * L * lsz(h), hipMemcpyDeviceToDevice, st));
-            }
-        }
-        CK(hipStreamSynchronize(st));
-    }
-#undef CK
-    if (worst == APV_ERR_NOT_PD) return bail(worst, worst_msg);     // the hops behind the failing one were not run
-    if (worst != APV_OK) return apv_fail(h, worst, worst_msg);      // APV_ERR_NO_CONVERGE: every hop ran, every output is written
-    return APV_OK;
+    return call.finish([&] { return chunk_leave_state(k); });
 }
 
 // spectra of one bank for the fast-convolution K1: cm [n_ch][P] channel-major -> spec [fir_np][n_ch][fir_F/2 + 1] (one segment: the
@@ -1488,7 +1592,7 @@ static int bank_spectra(apv_handle* h, const void* cm, int n_ch, void* spec) {
         e = apv_launch_fir_spectra_part(s->f64, s->fir_F, n_ch, (const char*)cm + (size_t)q * (np == 1 ? 0 : H) * s->esz, P, taps,
                                         (char*)spec + (size_t)q * Kf * n_ch * 2 * s->esz, h->stream, &why);
     }
-    if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
     return APV_OK;
 }
 
@@ -1672,14 +1776,14 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         // hop count separates the two: such a stream keeps every solve off that kernel, so its launch sequence is one and captured.
         s->fg_no_gevd64 = s->fg_beta > 0.0 && s->win_c128 && M < L && apv_gevd64_eligible(L, c.reg_mode, c.reg_bright, c.sweep_tol2);
         if (getenv("APV_STAT_WINDOW_TIMING") != nullptr)
-            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->win_ev[i], hipEventDefault));
+            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->win_tm.ev[i], hipEventDefault));
     }
     if (s->taps > 0) {
         for (int z = 0; z < 2; ++z)
             if ((s->zones & (1 << z)) && (rc = dalloc(h, &s->wtaps[z], (size_t)s->nV * s->taps * L, lsz(h)))) return rc;
         SCHK(h, apv_stft_prepare(N, c.out_c128));           // the projection runs in the filters' precision
         if (getenv("APV_FILTER_CONSTRAINT_TIMING") != nullptr)
-            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->cf_ev[i], hipEventDefault));
+            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->cf_tm.ev[i], hipEventDefault));
     }
     if (h->synthesis == APV_SYNTH_FIR) {
         s->fir_synth = 1;
@@ -1691,7 +1795,7 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
             for (int g = 0; g < 2; ++g)
                 if ((rc = dalloc(h, &s->fs_hist[b][g], (size_t)s->taps - 1, e1))) return rc;
         if (getenv("APV_FIR_SYNTHESIS_TIMING") != nullptr)
-            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->fs_ev[i], hipEventDefault));
+            for (int i = 0; i < 2; ++i) SCHK(h, s->own.event(&s->fs_tm.ev[i], hipEventDefault));
     }
     if (h->eval_Pv > 0) {
         // evaluation stage: per zone program that runs, the pressure sets [bright of E ranks][dark of E ranks][target]; bright and
@@ -1774,7 +1878,7 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         // (the statistics window adds no phase: its ring position is two device words that a kernel of the hop advances.  Timed
         // statistics launches -- a measuring aid -- run eagerly: their events are read after every hop)
         // (the FIR synthesis alternates its history buffers with cur, whose period of 2 is part of per already)
-        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr && !s->win_ev[0] && !s->cf_ev[0] && !s->fs_ev[0]) ? per : 0;
+        s->period = (per <= 16 && getenv("APV_NO_GRAPH") == nullptr && !s->win_tm.ev[0] && !s->cf_tm.ev[0] && !s->fs_tm.ev[0]) ? per : 0;
         s->execs.assign(s->period > 0 ? s->period : 0, nullptr);
     }
     s->hop = 0;
@@ -1963,7 +2067,7 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         p.RB = dRB; p.RD = dRD; p.r = dr; p.w = dw; p.lam = dl; p.status = (int32_t*)dst; p.U = dU; p.Lspill = dspill;
         std::string why;
         e = apv_launch_gevd(p, APV_F64, false, st, &why);
-        if (e != hipSuccess) return apv_fail(h, APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+        if (e != hipSuccess) return launch_fail(h, e, why);
     }
     if (h_RB) SCHK(h, hipMemcpyAsync(h_RB, dRB, mat, hipMemcpyDeviceToHost, st));
     if (h_RD) SCHK(h, hipMemcpyAsync(h_RD, dRD, mat, hipMemcpyDeviceToHost, st));
@@ -2124,7 +2228,7 @@ static int win_state(apv_handle* h, int j, void* h_buf, size_t bytes, bool get) 
     const int T = s->win_T;
     if (j == 3) {
         if (!get) return apv_fail(h, APV_ERR_STATE, "stat_window_kernel_ms is read-only");
-        std::memcpy(h_buf, s->win_ms, sizeof(s->win_ms));
+        std::memcpy(h_buf, s->win_tm.ms, sizeof(s->win_tm.ms));
         return APV_OK;
     }
     if (j >= 4) {
@@ -2209,6 +2313,15 @@ static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* by
     return apv_fail(h, APV_ERR_STATE, std::string("unknown state name: ") + name);
 }
 
+// read-only states kept on the host: the timers of the projection and of the FIR synthesis, the schedule of the last whole-signal call
+static const void* host_state(const apv_stream* s, const char* name, size_t* bytes) {
+    const std::string n(name);
+    if (s->taps > 0 && n == "filter_constraint_kernel_ms") { *bytes = sizeof(s->cf_tm.ms); return s->cf_tm.ms; }
+    if (s->fir_synth && n == "fir_synthesis_kernel_ms") { *bytes = sizeof(s->fs_tm.ms); return s->fs_tm.ms; }
+    if (n == "signal_schedule") { *bytes = sizeof(s->sched); return s->sched; }
+    return nullptr;
+}
+
 int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
     if (!h || !h->st || !name || !bytes) return apv_fail(h, APV_ERR_ARG, "null argument / no stream");
     const int j = live_index(name);
@@ -2221,18 +2334,7 @@ int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
         *bytes = win_state_bytes(h->st, wj);
         return APV_OK;
     }
-    if (h->st->taps > 0 && std::string(name) == "filter_constraint_kernel_ms") {
-        *bytes = sizeof(h->st->cf_ms);
-        return APV_OK;
-    }
-    if (h->st->fir_synth && std::string(name) == "fir_synthesis_kernel_ms") {
-        *bytes = sizeof(h->st->fs_ms);
-        return APV_OK;
-    }
-    if (std::string(name) == "signal_schedule") {
-        *bytes = sizeof(h->st->sched);
-        return APV_OK;
-    }
+    if (host_state(h->st, name, bytes)) return APV_OK;
     void* d; int rr;
     return state_lookup(h, name, &d, bytes, &rr);
 }
@@ -2245,19 +2347,10 @@ int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
         return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, h_dst, bytes, true, h->stream);
     }
     if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), h_dst, bytes, true);
-    if (h->st->taps > 0 && std::string(name) == "filter_constraint_kernel_ms") {
-        if (bytes != sizeof(h->st->cf_ms)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
-        std::memcpy(h_dst, h->st->cf_ms, sizeof(h->st->cf_ms));
-        return APV_OK;
-    }
-    if (h->st->fir_synth && std::string(name) == "fir_synthesis_kernel_ms") {
-        if (bytes != sizeof(h->st->fs_ms)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
-        std::memcpy(h_dst, h->st->fs_ms, sizeof(h->st->fs_ms));
-        return APV_OK;
-    }
-    if (std::string(name) == "signal_schedule") {
-        if (bytes != sizeof(h->st->sched)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
-        std::memcpy(h_dst, h->st->sched, sizeof(h->st->sched));
+    size_t host_bytes;
+    if (const void* src = host_state(h->st, name, &host_bytes)) {
+        if (bytes != host_bytes) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+        std::memcpy(h_dst, src, host_bytes);
         return APV_OK;
     }
     void* d; size_t need; int rr;

@@ -21,10 +21,10 @@ N, H, J, DELAY = 128, 64, 16, 5
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g10_per_hop_entry_points.npz")
 
 
-def make(L=4, M=8, P=70, n=N, h=H, j=J, delay=DELAY, dtype="f64", seed=3, **kw):
+def make(L=4, M=8, P=70, n=N, h=H, j=J, delay=DELAY, dtype="f64", seed=3, perceptual=False, **kw):
     from ap_vast_unofficial_amd.apvast import apvast
     rirA, rirB = synth_rirs(P, L, M, 11)
-    return apvast(n, rirA, rirB, j, delay, 1, 2, 2, 1.0, 4 * n, hop_size=h, seed=seed, dtype=dtype, perceptual=False,
+    return apvast(n, rirA, rirB, j, delay, 1, 2, 2, 1.0, 4 * n, hop_size=h, seed=seed, dtype=dtype, perceptual=perceptual,
                   sampling_rate=16000, **kw)
 
 
@@ -83,13 +83,9 @@ def test_schedule_taken(name, kw, n_hops, expected):
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("L,M", [(4, 8), (16, 20)])
-@pytest.mark.parametrize("dtype", ["f64", "mixed", "f32"])
-@pytest.mark.parametrize("synthesis", ["wola", "fir"])
-def test_bit_for_bit_against_the_hop_loop(synthesis, dtype, L, M):
+def against_the_hop_loop(mk):
     """per-hop calls, 41 hops (three chunks, the last partial), per-hop calls, 4 hops, a per-hop call: samples, states and
     attributes are those of the hop loop"""
-    mk = lambda: make(L=L, M=M, dtype=dtype, constrain_filter_length=True, synthesis=synthesis)
     a, b, c = mk(), mk(), mk()
     n_hops = 2 + 41 + 2 + 4 + 1
     x = signal(n_hops)
@@ -112,6 +108,20 @@ def test_bit_for_bit_against_the_hop_loop(synthesis, dtype, L, M):
     same_signal(got, ref)
     for o in (a, b, c):
         o.close()
+
+
+@pytest.mark.parametrize("L,M", [(4, 8), (16, 20)])
+@pytest.mark.parametrize("dtype", ["f64", "mixed", "f32"])
+@pytest.mark.parametrize("synthesis", ["wola", "fir"])
+def test_bit_for_bit_against_the_hop_loop(synthesis, dtype, L, M):
+    against_the_hop_loop(lambda: make(L=L, M=M, dtype=dtype, constrain_filter_length=True, synthesis=synthesis))
+
+
+@pytest.mark.parametrize("perceptual", [False, True], ids=["plain", "perceptual"])
+def test_bit_for_bit_unconstrained_one_launch_per_chunk(perceptual):
+    """the same against an unconstrained stream whose joint diagonalisations are one launch per chunk: that launch without a
+    projection behind it and, with the perceptual weighting on, the weighting of every hop of a chunk on the front stream"""
+    against_the_hop_loop(lambda: make(L=16, M=20, dtype="f64", perceptual=perceptual))
 
 
 # 3 ---------------------------------------------------------------------------------------------------------------
