@@ -204,7 +204,7 @@ bool apv_host_block_contains(const void* p, size_t bytes);
 int apv_gevd_lead(apv_handle* h, int n, int ne, int batch, int b, int rank, const double* C, const double* WT, double* d_U,
                   double* d_lam, const int* h_pd_flags, int* done);
 
-// stream_bb.hip: d_out[i] = ||mats[i]||_2 (largest eigenvalue of a symmetric PSD n x n matrix, Lanczos), i < count <= 4,
+// kernels_norm2.hip: d_out[i] = ||mats[i]||_2 (largest eigenvalue of a symmetric PSD n x n matrix, Lanczos), i < count <= 4,
 // n <= APV_NORM2_MAX_N.  method: APV_NORM2_AUTO (the chip-wide steps above APV_NORM2_GRID_MIN_N, else one workgroup per
 // matrix), APV_NORM2_ONE_WG or APV_NORM2_GRID (include/apvast_hip.h).
 constexpr int APV_NORM2_MAX_N = 4096;
@@ -402,6 +402,38 @@ struct FirJobsD {
 };
 hipError_t apv_launch_fir_jobs_f64(FirJobsD jobs, int njobs, int P, int H, int N, int ring_off, hipStream_t s);
 int apv_fir_pad_f64();
+// kernels_bb.hip: the broadband stream's own stages, float64 (the comments of the kernels say what each computes)
+struct SyrkJobs {
+    const double* stats[4];
+    double* R[4];
+};
+// up to four channel groups with inputs of their own, one launch (a hop's zone programs and target paths)
+struct ApplyJobsD {
+    const double2* in[4];
+    const double2* filt[4];
+    double2* out[4];
+    int first[5];          // first channel of each job in the launch's channel index; first[n] = total
+    int n;
+};
+// both input signals' histories: new = [old[H:], x, zeros(pad)], x [2][H]
+hipError_t apv_launch_hist2_f64(int P, int H, int pad, const double* old0, const double* old1, const double* x, double* new0,
+                                double* new1, hipStream_t s);
+// ring[c][(len - H + n + off) % len] = src[c][n], n < H, c < n_ch
+hipError_t apv_launch_ring_append_f64(int len, int H, int off, const double* src, long src_ld, double* ring, int n_ch, hipStream_t s);
+// R = sum_m Y_m Y_m^T of njobs Hankel data matrices (displacement form where it fits, else dense products on the matrix cores)
+hipError_t apv_launch_syrk_hankel(hipStream_t s, int n, int J, int L, int M, int S, int off, int skip, int ncols, int njobs,
+                                  const SyrkJobs& jobs);
+// r = sum_m Y_m d_m[toff:]
+hipError_t apv_launch_xcorr_hankel(int n, int J, int L, int M, int S, int off, int skip, int ncols, int toff, const double* stats,
+                                   const double* tstats, double* r, hipStream_t s);
+// R[i][i] += coef * nrm[0]
+hipError_t apv_launch_add_rel_diag(int n, double* R, double coef, const double* nrm, hipStream_t s);
+// out[q][ch][k] = in[q][k] * filt[q][ch][k] over the jobs' j.first[j.n] channels
+hipError_t apv_launch_apply_jobs_f64(int K, const ApplyJobsD& j, hipStream_t s);
+// p[t][m] = sum_s sum_q rir[q][s][m] x[t-q][s], M <= 256
+hipError_t apv_launch_predict_pressure(int T, int L, int M, int P, const double* x, const double* rir, double* out, hipStream_t s);
+// v[i] *= f
+hipError_t apv_launch_scale_f64(size_t count, double* v, double f, hipStream_t s);
 // kernels_live.hip: responses reassigned between hops (apv_stream_set_rirs / apv_bb_set_rirs).  Jobs 0..3 are the paths A->A, A->B,
 // B->A, B->B ([C][P-1] tails), 4..5 the targets ([M][P-1]); all buffers in the stream's front-end precision.
 struct FirLive {

@@ -824,6 +824,90 @@ int apv_jdiag_leading(apv_handle* h, int32_t n, int32_t batch, int32_t rank, con
     return APV_OK;
 }
 
+// Evaluation: pressure at the microphones for given loudspeaker signals.  h_x [T][L], h_rir [P][L][M] (the
+// (rir_len, L, M) layout of rirs.mat), h_out [T][M], all float64.      replaces predictPressure.m:1-17
+int apv_predict_pressure(apv_handle* h, int32_t T, int32_t L, int32_t M, int32_t P, const double* h_x,
+                         const double* h_rir, double* h_out) {
+    if (!h || !h_x || !h_rir || !h_out) return fail(h, APV_ERR_ARG, "null argument");
+    if (T < 0 || L < 1 || M < 1 || M > 256 || P < 1) return fail(h, APV_ERR_ARG, "predict_pressure: bad sizes (M <= 256)");
+    if (T == 0) return APV_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    ApvOwned tmp;                                           // freed on every way out
+    double *dx = nullptr, *dr = nullptr, *dout = nullptr;
+    HIPCHK(h, tmp.device(&dx, sizeof(double) * (size_t)T * L));
+    HIPCHK(h, tmp.device(&dr, sizeof(double) * (size_t)P * L * M));
+    HIPCHK(h, tmp.device(&dout, sizeof(double) * (size_t)T * M));
+    HIPCHK(h, hipMemcpyAsync(dx, h_x, sizeof(double) * (size_t)T * L, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dr, h_rir, sizeof(double) * (size_t)P * L * M, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, apv_launch_predict_pressure(T, L, M, P, dx, dr, dout, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h_out, dout, sizeof(double) * (size_t)T * M, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
+// Static (signal-independent) VAST from the impulse responses alone.  h_gB [Nb][P][L], h_gD [Nd][P][L] (the
+// (mics, rirLength, sources) layout of vast.m), h_w [J L].               replaces Matlab/ControlMethods/vast.m:46-91
+int apv_vast_static(apv_handle* h, int32_t Nb, int32_t Nd, int32_t P, int32_t L, int32_t J, int32_t modeling_delay,
+                    int32_t reference_index, int32_t V, double mu, const double* h_gB, const double* h_gD, double* h_w) {
+    if (!h || !h_gB || !h_gD || !h_w) return fail(h, APV_ERR_ARG, "null argument");
+    const int n = J * L;
+    if (Nb < 1 || Nd < 1 || P < 1 || L < 1 || J < 1 || n > 4096 || V < 1 || V > n || modeling_delay < 0 || modeling_delay >= P ||
+        reference_index < 0 || reference_index >= L || P <= J)
+        return fail(h, APV_ERR_ARG, "vast_static: bad sizes (J L <= 4096, rir_len > J)");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    // vast.m drives the filters with a unit impulse for N = 1000 steps (vast.m:50-53): 999 of them are non-trivial
+    const int ncols = 999, S = ncols + J;
+    auto pack = [&](const double* g, int Nm, std::vector<double>& out) {          // [m*L + s][S], g'[u] = g[u-(J-1)]
+        out.assign((size_t)Nm * L * S, 0.0);
+        for (int m = 0; m < Nm; ++m)
+            for (int sI = 0; sI < L; ++sI)
+                for (int q = 0; q < P && q + J - 1 < S; ++q)
+                    out[((size_t)m * L + sI) * S + q + J - 1] = g[((size_t)m * P + q) * L + sI];
+    };
+    std::vector<double> sb, sd, td((size_t)Nb * S, 0.0);
+    pack(h_gB, Nb, sb);
+    pack(h_gD, Nd, sd);
+    for (int m = 0; m < Nb; ++m)                                                   // target: delayed reference RIR (vast.m:59)
+        for (int q = modeling_delay; q < P && J + q < S; ++q)
+            td[(size_t)m * S + J + q] = h_gB[((size_t)m * P + (q - modeling_delay)) * L + reference_index];
+    ApvOwned tmp;                                           // freed on every way out
+    double *dsb = nullptr, *dsd = nullptr, *dtd = nullptr, *dR = nullptr, *dr = nullptr, *dU = nullptr, *dl = nullptr, *dw = nullptr;
+    HIPCHK(h, tmp.device(&dsb, sizeof(double) * sb.size()));
+    HIPCHK(h, tmp.device(&dsd, sizeof(double) * sd.size()));
+    HIPCHK(h, tmp.device(&dtd, sizeof(double) * td.size()));
+    HIPCHK(h, tmp.device(&dR, sizeof(double) * 2 * (size_t)n * n));
+    HIPCHK(h, tmp.device(&dr, sizeof(double) * n));
+    HIPCHK(h, tmp.device(&dU, sizeof(double) * (size_t)n * n));
+    HIPCHK(h, tmp.device(&dl, sizeof(double) * n));
+    HIPCHK(h, tmp.device(&dw, sizeof(double) * (size_t)V * n));
+    HIPCHK(h, hipMemcpyAsync(dsb, sb.data(), sizeof(double) * sb.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(dsd, sd.data(), sizeof(double) * sd.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(dtd, td.data(), sizeof(double) * td.size(), hipMemcpyHostToDevice, st));
+    {
+        SyrkJobs jb{}, jd{};
+        jb.stats[0] = dsb; jb.R[0] = dR;
+        jd.stats[0] = dsd; jd.R[0] = dR + (size_t)n * n;
+        HIPCHK(h, apv_launch_syrk_hankel(st, n, J, L, Nb, S, 0, 0, S - J, 1, jb));
+        HIPCHK(h, apv_launch_syrk_hankel(st, n, J, L, Nd, S, 0, 0, S - J, 1, jd));
+    }
+    HIPCHK(h, apv_launch_xcorr_hankel(n, J, L, Nb, S, 0, 0, S - J, J, dsb, dtd, dr, st));
+    // vast.m:71-73 normalises all three by numberOfMics (of the BRIGHT zone) * (rirLength - filterLength)
+    const double f = 1.0 / ((double)Nb * (double)(P - J));
+    const size_t nn = (size_t)n * n;
+    HIPCHK(h, apv_launch_scale_f64(2 * nn, dR, f, st));
+    HIPCHK(h, apv_launch_scale_f64((size_t)n, dr, f, st));
+    int32_t status = 0;
+    int rc = apv_gevd_large(h, n, 1, dR, dR + nn, 0.0, nullptr, dU, dl, dr, mu, V, nullptr, dw, &status);     // jdiag(RB, RD, 'vector', true): no loading
+    if (rc == APV_OK) {
+        (void)hipMemcpyAsync(h_w, dw + (size_t)(V - 1) * n, sizeof(double) * n, hipMemcpyDeviceToHost, st);
+        (void)hipStreamSynchronize(st);
+    }
+    if (rc == APV_OK && status == 2)
+        return fail(h, APV_ERR_NO_CONVERGE, "vast_static: eigen-iteration did not converge (Jacobi sweep cap reached); w was written");
+    return rc;
+}
+
 int apv_stft_analysis_dev(apv_handle* h, int32_t n_ch, const float* d_x, void* d_spec) {
     if (!h || !d_x || !d_spec) return fail(h, APV_ERR_ARG, "null device pointer");
     if (h->cfg.block_size <= 0) return fail(h, APV_ERR_ARG, "handle was created without an STFT geometry");

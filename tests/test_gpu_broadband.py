@@ -557,3 +557,94 @@ def test_broadband_silence_is_finite(golden):
     res = ap.process_signal(x[0], x[1])
     assert all(np.isfinite(np.stack(res[q])).all() for q in range(4))
     ap.close()
+
+
+@pytest.mark.parametrize("dialect,zone", [("python", "A"), ("python", "B"), ("matlab", "A"), ("matlab", "B")])
+def test_broadband_single_zone_relative_loading(golden, dialect, zone):
+    """ONE zone program with the loading relative to the spectral norm: the norm entry of a matrix that does not exist is taken from
+    the one that does, and the dark norm of the zone that runs is re-packed for the batch of a whole signal.  L = 3, M = 2,
+    n = J L = 24, five hops.  Python dialect with EXPERIMENTAL_REGULARIZATION = False (apvast.py:26-27) and MATLAB dialect
+    (apVast.m:552-569, ranks 1, 2, 5): every hop against the oracle (outputs and lambda 1e-9, w 1e-8 as for G7; 1e-6 in the MATLAB
+    dialect), then the same hops through process_signal against the hop loop (outputs 1e-9, attributes 1e-8), and the other zone's
+    attributes absent.  MatlabBroadbandOracle has no switch for zone A (apVast.m always runs it), so MATLAB / zone B is held to
+    the hop loop alone."""
+    import ap_vast_unofficial_amd.apvast as mod
+    from oracle import gevd
+    from oracle.broadband import BroadbandOracle
+    from oracle.broadband_matlab import MatlabBroadbandOracle
+    rirs = golden("rirs_cfg1")
+    rA, rB = rirs["rirA"][:96, :3, :2], rirs["rirB"][:96, :3, :2]
+    N, H, J, S, hops = 128, 64, 8, 160, 5
+    matlab, runA = dialect == "matlab", zone == "A"
+    ranks = [1, 2, 5] if matlab else [1, 2, 3]
+    kept = [v - 1 for v in ranks]
+    other = "B" if runA else "A"
+    attrs = [f"R_{zone}_to_{zone}", f"R_{zone}_to_{other}", f"r_{zone}", f"lambda_{zone}", f"w_{zone}"]
+    absent = [f"R_{other}_to_{other}", f"R_{other}_to_{zone}", f"r_{other}", f"lambda_{other}", f"w_{other}"]
+    x = np.random.default_rng(5).standard_normal((2, hops * H))
+    keep = mod.EXPERIMENTAL_REGULARIZATION
+    mod.EXPERIMENTAL_REGULARIZATION = False
+    try:
+        def mk():
+            if not matlab:
+                return mod.apvast(N, rA, rB, J, 3, 0, 1, 3, 1.0, S, hop_size=H, run_A=runA, run_B=not runA, perceptual=False,
+                                  mode="broadband", seed=3)
+            o = mod.apvast(N, rA, rB, J, 3, 0, 1, ranks, 1.0, S, run_A=runA, run_B=not runA, perceptual=False, mode="broadband",
+                           dialect="matlab")
+            rng = np.random.default_rng(21)
+            st = o.get_state()
+            o.set_state({"response": 1e-3 * rng.standard_normal(st["response"].shape),
+                         "target_response": 1e-3 * rng.standard_normal(st["target_response"].shape)})
+            return o
+        a, b = mk(), mk()
+        orc = None
+        if not matlab:
+            np.random.seed(3)
+            orc = BroadbandOracle(N, rA, rB, J, 3, 0, 1, 3, 1.0, S, hop_size=H, run_A=runA, run_B=not runA,
+                                  reg_mode=gevd.REG_MODE_REL)
+        elif runA:
+            orc = MatlabBroadbandOracle(N, rA, rB, J, 3, 0, 1, ranks, 1.0, S, calculate_zone_B=False)
+            rng = np.random.default_rng(21)
+            orc.response[:] = 1e-3 * rng.standard_normal(orc.response.shape)
+            orc.target_response[:] = 1e-3 * rng.standard_normal(orc.target_response.shape)
+        tol_out, tol_lam, tol_w = (1e-6, 1e-6, 1e-6) if matlab else (1e-9, 1e-9, 1e-8)
+        worst = dict(out=0.0, lam=0.0, w=0.0, signal_out=0.0, signal_attr=0.0)
+        per_hop = []
+        for h in range(hops):
+            xa, xb = x[0, h * H:(h + 1) * H], x[1, h * H:(h + 1) * H]
+            got = a.process_input_buffers(xa, xb)
+            per_hop.append(got)
+            assert got[0 if not runA else 1] is None
+            if orc is None:
+                continue
+            exp = orc.process_input_buffers(xa, xb)
+            assert exp[0 if not runA else 1] is None
+            for q in range(4):
+                if exp[q] is not None:
+                    worst["out"] = max(worst["out"], np.abs(np.stack(got[q]) - exp[q]).max() / np.abs(exp[q]).max())
+            lam, w = getattr(a, f"lambda_{zone}"), getattr(a, f"w_{zone}")
+            elam, ew = getattr(orc, f"lambda_{zone}"), getattr(orc, f"w_{zone}")
+            worst["lam"] = max(worst["lam"], np.abs(lam[kept] / elam[kept] - 1).max())
+            for i in range(len(ranks)):
+                worst["w"] = max(worst["w"], np.linalg.norm(w[i, :, 0] - ew[i]) / np.linalg.norm(ew[i]))
+        whole = b.process_signal(x[0], x[1])
+        assert whole[0 if not runA else 1] is None
+        for q in range(4):
+            if whole[q] is None:
+                continue
+            for v in range(len(whole[q])):
+                ref = np.concatenate([per_hop[h][q][v] for h in range(hops)])
+                worst["signal_out"] = max(worst["signal_out"], np.abs(whole[q][v] - ref).max() / np.abs(ref).max())
+        for name in attrs:
+            va, vb = getattr(a, name), getattr(b, name)
+            worst["signal_attr"] = max(worst["signal_attr"], np.abs(vb - va).max() / np.abs(va).max())
+        print(f"single zone {zone}, {dialect} dialect, relative loading: worst errors", worst)
+        assert worst["out"] <= tol_out and worst["lam"] <= tol_lam and worst["w"] <= tol_w
+        assert worst["signal_out"] <= 1e-9 and worst["signal_attr"] <= 1e-8
+        for o in (a, b):
+            for name in absent:
+                assert getattr(o, name) is None, name
+        a.close()
+        b.close()
+    finally:
+        mod.EXPERIMENTAL_REGULARIZATION = keep
