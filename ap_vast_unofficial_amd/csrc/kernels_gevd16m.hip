@@ -446,7 +446,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
     using C = Cx<T>;
     __shared__ C sA[N * LD];       // R_B -> W R_B -> C -> Q (eigenvectors of C) -> X
     __shared__ C sB[N * LD];       // R_D -> W = L^-1
-    __shared__ C scol[2][N];       // Cholesky: current column of B (double buffered)
+    __shared__ C scol[2][N];       // (stage 1 keeps its columns in sB; the later stages' small arrays live here)
     __shared__ C swr[2][N];        // Cholesky: current row of W
     __shared__ C sr[N];
     __shared__ C scoef[N];
@@ -455,7 +455,6 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
     T* const sLam = reinterpret_cast<T*>(&scol[0][0]);                 // [N]
     int* const sOrder = reinterpret_cast<int*>(&scol[1][0]);           // [N]
     T (*const srot)[4] = reinterpret_cast<T(*)[4]>(&swr[0][0]);        // Jacobi: (c, s.x, s.y) of the eight rotations of a round
-    T* const sPiv = reinterpret_cast<T*>(&scoef[0]);                   // [N] stage 1: the pivots (scoef is idle until stage 6)
 
     const int lane = threadIdx.x;
     int status = 0;
@@ -506,22 +505,33 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
         if (j == i) brow[t] = mk<T>(brow[t].x + (T)p.reg_dark, 0);
         wrow[t] = mk<T>((j == i) ? (T)1 : (T)0, 0);
     }
+    // Every step has a column buffer of its own in sB (R_D is in brow[] by now and W goes back there only after the loop): column
+    // kk of the working B, pivot included, stays at ccol[kk] until the loop is over.  So the loop neither tests nor stores the
+    // pivot: a step is one LDS round trip (pivot, column and row behind one wsync) and straight-line code, and the pivots are
+    // tested afterwards, all sixteen at once.  After a bad pivot the remaining steps compute inf / NaN that nothing reads.
+    C (*const ccol)[N] = reinterpret_cast<C(*)[N]>(&sB[0]);
+    wsync();                                                                    // every lane has its row of R_D
 #pragma unroll
     for (int kk = 0; kk < N; ++kk) {
         const int buf = kk & 1;
-        if (jq == (kk & 3)) scol[buf][i] = brow[kk >> 2];                       // column kk of the working B
+        if (jq == (kk & 3)) ccol[kk][i] = brow[kk >> 2];                        // column kk of the working B
         if (i == kk) {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
                 if (4 * t <= kk) swr[buf][jq + 4 * t] = wrow[t];                // row kk of the working W (zero beyond column kk)
         }
         wsync();
-        const T dkk = scol[buf][kk].x;
-        if (!(dkk > (T)0) || !(dkk < (T)3.0e38)) { status = 1; break; }         // uniform: same LDS word for all lanes
+        // all of the step's reads behind the one wsync: pivot, B[i][kk], the column entries and the row of W
+        const T dkk = ccol[kk][kk].x;
+        const C li = ccol[kk][i];
+        C lj[4], wk[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (4 * t + 3 > kk) lj[t] = ccol[kk][jq + 4 * t];
+            if (4 * t <= kk) wk[t] = swr[buf][jq + 4 * t];
+        }
         // 1/d for the updates now; the 1/sqrt(d) that scales row kk of W is taken once, for all rows together, after the loop
         const T inv2 = rcp_full(dkk);
-        if (lane == 0) sPiv[kk] = dkk;
-        const C li = scol[buf][i];
         const C li2 = mk<T>(li.x * inv2, li.y * inv2);
         // The outer-product update of B runs on the whole Hermitian matrix, without the triangle tests: rows and columns
         // already eliminated only cancel to rounding level and are never read again, and the unconditional update costs less
@@ -531,28 +541,33 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (4 * t + 3 <= kk) continue;
-            const C lj = scol[buf][jq + 4 * t];                  // B[i][j] -= B[i][kk] conj(B[j][kk]) / d
+            // B[i][j] -= B[i][kk] conj(B[j][kk]) / d
             // each component as two chained FMAs (written a -= p q + r s it compiles to a product, an FMA and a subtraction)
-            brow[t].x = fma_t(-li2.y, lj.y, fma_t(-li2.x, lj.x, brow[t].x));
-            brow[t].y = fma_t(li2.x, lj.y, fma_t(-li2.y, lj.x, brow[t].y));
+            brow[t].x = fma_t(-li2.y, lj[t].y, fma_t(-li2.x, lj[t].x, brow[t].x));
+            brow[t].y = fma_t(li2.x, lj[t].y, fma_t(-li2.y, lj[t].x, brow[t].y));
         }
         if (i > kk) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 if (4 * t > kk) continue;
-                const C wk = swr[buf][jq + 4 * t];               // W[i][j] -= (B[i][kk] / d) W[kk][j]
-                wrow[t].x = fma_t(li2.y, wk.y, fma_t(-li2.x, wk.x, wrow[t].x));
-                wrow[t].y = fma_t(-li2.y, wk.x, fma_t(-li2.x, wk.y, wrow[t].y));
+                // W[i][j] -= (B[i][kk] / d) W[kk][j]
+                wrow[t].x = fma_t(li2.y, wk[t].y, fma_t(-li2.x, wk[t].x, wrow[t].x));
+                wrow[t].y = fma_t(-li2.y, wk[t].x, fma_t(-li2.x, wk[t].y, wrow[t].y));
             }
         }
     }
     wsync();
-    if (status == 0) {
-        // W = D^-1/2 (unit lower factor)^-1: every row by the reciprocal root of its pivot, one rsq for the sixteen rows at once
-        // (inside the loop it was a serial rsq per step and a branch for the pivot row)
-        const T ri = rsq_full(sPiv[i]);
+    {
+        // the pivots, each row's own: one bad one (not positive, NaN, or beyond 3e38) fails the bin
+        const T di = ccol[i][i].x;
+        if (__any(!(di > (T)0) || !(di < (T)3.0e38))) status = 1;
+        if (status == 0) {
+            // W = D^-1/2 (unit lower factor)^-1: every row by the reciprocal root of its pivot, one rsq for the sixteen rows at once
+            // (inside the loop it was a serial rsq per step and a branch for the pivot row)
+            const T ri = rsq_full(di);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) wrow[t] = mk<T>(wrow[t].x * ri, wrow[t].y * ri);
+            for (int t = 0; t < 4; ++t) wrow[t] = mk<T>(wrow[t].x * ri, wrow[t].y * ri);
+        }
     }
     stamp(2);
     if (dstop == 2) return;
@@ -683,11 +698,12 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                     }
                     wsync();
                     bool bad = false, hopeless = false;
+                    const T dj = sLam[mcol];
+                    T l2 = (T)0;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const int row = mfma_row<T>(lane, t);
-                        const T di = sLam[row], dj = sLam[mcol];
-                        T l2 = (T)0;
+                        const T di = sLam[row];
                         C z;
                         if (row == mcol) {
                             z = mk<T>((T)0.5 * ((T)1 - accG[t].x), (T)0);
@@ -700,20 +716,19 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                             bad = bad || !(zz <= (T)kRefineGuard2);                      // NaN / inf (equal quotients) count as bad
                             hopeless = hopeless || !(zz <= (T)kSecondStep2);
                             z = mk<T>(zx, zy);
-                            // second-order term of the eigenvalue of the pencil (S, Gram) next to d_i: -|S_ij - d_i E_ij|^2 / (d_j - d_i).
-                            // (Exact to third order in Z AND E: a float32 pre-solve can leave E ~ 1e-5 between the columns of small
-                            // eigenvalues, where a formula that orthonormalises to first order only is off by E^2.)
-                            const T nx = __builtin_fma(-di, accG[t].x, accC[t].x), ny = __builtin_fma(-di, accG[t].y, accC[t].y);
-                            l2 = -(nx * nx + ny * ny) * inv;
+                            // second-order term of the eigenvalue of the pencil (S, Gram) next to d_j, summed by COLUMNS: S and E are
+                            // Hermitian, so row i gives eigenvalue j the term |S_ij - d_j E_ij|^2 / (d_j - d_i) = |Z_ij|^2 (d_j - d_i),
+                            // one FMA on what the guard has formed already.  (Exact to third order in Z AND E: a float32 pre-solve
+                            // can leave E ~ 1e-5 between the columns of small eigenvalues, where a formula that orthonormalises to
+                            // first order only is off by E^2.)  Equal quotients give NaN: such a step is `bad` and never reads it.
+                            l2 = __builtin_fma(zz, den, l2);
                         }
                         sA[row * LD + mcol] = z;
-                        // sum over the 16 lanes that share this row (lane ^ 1, 2, 4, 8), then add the quotient itself
-                        l2 += xcol<1>(l2);
-                        l2 += xcol<2>(l2);
-                        l2 += xcol<4>(l2);
-                        l2 += xrow<1>(l2, lane);
-                        if (mcol == 0) sLam2[row] = l2 + di;
                     }
+                    // the column's sixteen rows sit in this lane's four slots and in lanes ^ 16, ^ 32; then add the quotient itself
+                    l2 += __shfl_xor(l2, 16, 64);
+                    l2 += __shfl_xor(l2, 32, 64);
+                    if (lane < N) sLam2[mcol] = l2 + dj;
                     const bool pass = !__any(bad) || dstop == 10;                 // 10: guard off (timing aid, results invalid)
                     if (dstop == 9 && !pass) status = 8 << step;                  // 9: mark the bins by the step they miss
                     // the double sweeps start from the triple (V, S, Gram) as it is: leave before anything of it is touched
@@ -911,23 +926,33 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
     }
 
     // ---------------- outputs ----------------
-    if (lane < N) {
+    // all 64 lanes: lane (i = lane & 15, q = lane >> 4) sums the terms of the sorted columns q, q + 4, ... of element i, carried on
+    // from rank to rank; per rank the four partial sums meet over q (the partials themselves stay).  Which lane takes a column
+    // does not depend on the rank list, so a rank's filter has the same bits whatever other ranks the launch asks for.
+    {
+        const int i16 = lane & 15;
         T ax = 0, ay = 0;
-        int done = 0;
+        int done = lane >> 4;
         for (int t = 0; t < p.nV; ++t) {
             const int V = p.ranks[t];
             if (status != 1) {
-                for (; done < V; ++done) {
+                for (; done < V; done += 4) {
                     const int c = sOrder[done];
-                    const C cf = scoef[c], v = sA[lane * LD + c];
+                    const C cf = scoef[c], v = sA[i16 * LD + c];
                     ax = fma_t(-cf.y, v.y, fma_t(cf.x, v.x, ax));
                     ay = fma_t(cf.y, v.x, fma_t(cf.x, v.y, ay));
                 }
             }
-            const size_t o = ((size_t)k * p.nV + t) * N + lane;
-            if (p.out_c128) reinterpret_cast<double2*>(pw)[o] = make_double2((double)ax, (double)ay);
-            else reinterpret_cast<float2*>(pw)[o] = make_float2((float)ax, (float)ay);
+            T wx = ax + __shfl_xor(ax, 16, 64), wy = ay + __shfl_xor(ay, 16, 64);
+            wx += __shfl_xor(wx, 32, 64); wy += __shfl_xor(wy, 32, 64);
+            if (lane < N) {
+                const size_t o = ((size_t)k * p.nV + t) * N + lane;
+                if (p.out_c128) reinterpret_cast<double2*>(pw)[o] = make_double2((double)wx, (double)wy);
+                else reinterpret_cast<float2*>(pw)[o] = make_float2((float)wx, (float)wy);
+            }
         }
+    }
+    if (lane < N) {
         if (plam != nullptr) {
             const T lv = (status != 1) ? sLam[sOrder[lane]] : (T)0;
             if (p.out_c128) reinterpret_cast<double*>(plam)[(size_t)k * N + lane] = (double)lv;

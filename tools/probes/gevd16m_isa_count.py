@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Static instruction counts of the whole product instantiation of the order-16 float64 kernel, gevd16m_kernel_f64<true, float2,
+false>: every path of the function, the rare ones (double sweeps, second refinement step, failed pivot) included, so the figures
+are larger than what a wave issues.  Compiles kernels_gevd16m.hip to gfx950 assembly with hipcc (no GPU needed) and prints one
+table row in the form of DESIGN 4.1:
+
+  VALU          every v_* but the MFMAs            SALU        every s_* but waits, nops, branches and barriers
+  branches      s_branch and s_cbranch_*           LDS         every ds_* (ds_bpermute included)
+  waits/nops    s_waitcnt* and s_nop               MFMA        v_mfma_*
+
+with the register count, spill stores and reloads, scratch and LDS bytes from the function's own footer.  Instructions are
+classed by the prefix of their mnemonic only.  (The regions of the float32 pre-solve: presolve_isa_count.py.)
+
+    python tools/probes/gevd16m_isa_count.py [--asm FILE.s] [--kernel MANGLED_SUBSTRING] [--label NAME] [--top N]
+"""
+import argparse
+import collections
+import os
+import re
+import subprocess
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+SRC = os.path.join(ROOT, "ap_vast_unofficial_amd", "csrc", "kernels_gevd16m.hip")
+KERNEL = "gevd16m_kernel_f64ILb1E15HIP_vector_typeIfLj2EELb0EE"      # <true, float2, false>
+
+
+def compile_asm(path):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I/opt/rocm/include", "-S", "--cuda-device-only",
+                    SRC, "-o", path], check=True, stderr=subprocess.DEVNULL)
+
+
+def function_lines(text, kernel):
+    lines = text.splitlines()
+    start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and kernel in l.split(":")[0])
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    meta = {}
+    for l in lines[end:end + 80]:
+        m = re.match(r";\s*(NumVgprs|NumSgprs|ScratchSize|LDSByteSize|Occupancy):\s*(\d+)", l)
+        if m:
+            meta.setdefault(m.group(1), int(m.group(2)))
+    return lines[start + 1:end], meta
+
+
+def mnemonic(line):
+    s = line.strip()
+    if not s or s.startswith((";", ".", "/")) or re.match(r"[\w.$]+:", s):
+        return None
+    return s.split()[0]
+
+
+def classify(ms):
+    c = collections.Counter()
+    for m in ms:
+        if m.startswith("v_mfma"):
+            c["mfma"] += 1
+        elif m.startswith("v_"):
+            c["valu"] += 1
+        elif m.startswith(("s_waitcnt", "s_nop")):
+            c["wait"] += 1
+        elif m.startswith(("s_cbranch", "s_branch")):
+            c["branch"] += 1
+        elif m.startswith("s_barrier"):
+            c["barrier"] += 1
+        elif m.startswith("s_"):
+            c["salu"] += 1
+        elif m.startswith("ds_"):
+            c["lds"] += 1
+        else:
+            c["other"] += 1                     # global / scratch / buffer memory
+    return c
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--asm", help="count an assembly file made earlier instead of compiling")
+    ap.add_argument("--kernel", default=KERNEL, help="substring of the mangled name of the function to count")
+    ap.add_argument("--label", default="this tree")
+    ap.add_argument("--top", type=int, default=0, help="also list the N commonest VALU mnemonics")
+    args = ap.parse_args()
+    if args.asm:
+        text = open(args.asm).read()
+    else:
+        with tempfile.TemporaryDirectory() as td:
+            compile_asm(os.path.join(td, "k.s"))
+            text = open(os.path.join(td, "k.s")).read()
+    body, meta = function_lines(text, args.kernel)
+    spills = sum(1 for l in body if "Folded Spill" in l or "Spill" in l and "scratch_store" in l)
+    reloads = sum(1 for l in body if "Reload" in l)
+    ms = [m for m in map(mnemonic, body) if m]
+    c = classify(ms)
+    print("| build | VALU | SALU | branches | LDS | waits/nops | MFMA | memory | VGPRs | spill st / reloads | scratch | LDS bytes |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+    print(f"| {args.label} | {c['valu']} | {c['salu']} | {c['branch']} | {c['lds']} | {c['wait']} | {c['mfma']} | {c['other']} | "
+          f"{meta.get('NumVgprs')} | {spills} / {reloads} | {meta.get('ScratchSize')} B | {meta.get('LDSByteSize')} |")
+    if args.top:
+        top = collections.Counter(re.sub(r"_e(32|64)$", "", m) for m in ms if m.startswith("v_") and not m.startswith("v_mfma"))
+        print("\nVALU by mnemonic: " + ", ".join(f"{k} {v}" for k, v in top.most_common(args.top)))
+
+
+if __name__ == "__main__":
+    main()
