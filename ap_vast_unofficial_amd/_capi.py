@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -138,6 +138,8 @@ def load():
     lib.apv_stream_not_converged.argtypes = [vp]
     lib.apv_stream_set_rirs.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.apv_set_mu.argtypes = [vp, C.c_double]
+    lib.apv_set_span.argtypes = [vp, vp, vp, C.c_double]
+    lib.apv_get_span.argtypes = [vp, i32, vp, vp]
     lib.apv_state_bytes.argtypes = [vp, C.c_char_p, C.POINTER(sz)]
     lib.apv_get_state.argtypes = [vp, C.c_char_p, vp, sz]
     lib.apv_set_state.argtypes = [vp, C.c_char_p, vp, sz]
@@ -191,6 +193,18 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def contrast_floor(floor_db):
+    """phi = 10^(floor_db / 10) as apv_set_span takes it.  ValueError where it leaves the doubles: phi = 0 means "no floor" there,
+    so a floor that underflows would silently remove the part."""
+    try:
+        phi = 10.0 ** (float(floor_db) / 10.0)
+    except OverflowError:
+        phi = float("inf")
+    if not 0.0 < phi < float("inf"):
+        raise ValueError(f"contrast_floor_db = {floor_db}: 10^(dB / 10) must be a positive, finite double")
+    return phi
+
+
 class DeviceBuffer:
     """A hipMalloc'd block owned through the C ABI."""
 
@@ -230,7 +244,7 @@ class Engine:
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
                  out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola", evaluation=None,
-                 evaluation_spectra=False):
+                 evaluation_spectra=False, span=None):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -292,6 +306,9 @@ class Engine:
         self.evaluation_spectra = False
         if evaluation_spectra:
             self.set_evaluation_spectra(True)
+        self.span_parts = None
+        if span is not None:
+            self.set_span(**span)
 
     def set_evaluation_spectra(self, on):
         """Per-bin spectra of the evaluation stage, before stream_init (apv_stream_set_evaluation_spectra); needs set_evaluation."""
@@ -691,6 +708,33 @@ class Engine:
     def set_mu(self, mu):
         """mu of the next hop on (either stream mode)."""
         self._chk(self.lib.apv_set_mu(self.h, float(mu)))
+
+    def set_span(self, mu_profile=None, rank_cap=None, contrast_floor_db=None):
+        """The per-bin span (apv_set_span): mu_profile (K,) or (2, K) floats, mu of bin k = mu * profile; rank_cap (K,) or (2, K)
+        ints in 1..L; contrast_floor_db a float.  Row 0 of a (2, K) table is zone program A and every kernel-level call (update,
+        gevd_vast), row 1 program B.  The first call fixes which parts exist (before stream_init); later calls change their
+        values from the next launch or hop on."""
+        def table(a, dtype):
+            if a is None:
+                return None
+            a = np.asarray(a, dtype=dtype)
+            if a.shape == (self.K,):
+                a = np.stack([a, a])
+            if a.shape != (2, self.K):
+                raise ValueError(f"a span table has shape ({self.K},) or (2, {self.K}), got {a.shape}")
+            return np.ascontiguousarray(a)
+        m, c = table(mu_profile, np.float64), table(rank_cap, np.int32)
+        phi = 0.0 if contrast_floor_db is None else contrast_floor(contrast_floor_db)
+        self._chk(self.lib.apv_set_span(self.h, None if m is None else _ptr(m), None if c is None else _ptr(c), phi))
+        self.span_parts = (m is not None, c is not None, contrast_floor_db is not None)
+
+    def span(self, zone):
+        """Outputs of the span of the last launch or hop for zone program `zone` (apv_get_span): (rank (K,) int32, contrast (K, L)
+        float64 or None without a contrast floor)."""
+        rank = np.empty(self.K, dtype=np.int32)
+        con = np.empty((self.K, self.L), dtype=np.float64) if self.span_parts and self.span_parts[2] else None
+        self._chk(self.lib.apv_get_span(self.h, int(zone), _ptr(rank), None if con is None else _ptr(con)))
+        return rank, con
 
     def stream_set_perceptual(self, tables, normalisation):
         """tables: ap_vast_unofficial_amd.perceptual.PerceptualTables (or None to switch the weighting off)."""

@@ -170,6 +170,9 @@ class apvast:
                  evaluation_ranks=None,
                  evaluation_spectra=False,
                  statistics_forgetting=None,
+                 mu_profile=None,
+                 rank_profile=None,
+                 contrast_floor_db=None,
                  statistics_hops=1):
         self.block_size = block_size
         self.filter_length = filter_length
@@ -213,6 +216,11 @@ class apvast:
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
         self._evaluation = self._check_evaluation(validation_rir_A, validation_rir_B, evaluation_ranks, L, number_of_eigenvectors, mode)
         self._evaluation_spectra = self._check_evaluation_spectra(evaluation_spectra, self._evaluation, mode)
+        # the per-bin span: which of its three parts exist is fixed here, their values may be reassigned between hops
+        self._span = {"mu_profile": self._check_mu_profile(mu_profile, N // 2 + 1, mode),
+                      "rank_profile": self._check_rank_profile(rank_profile, N // 2 + 1, L, mode),
+                      "contrast_floor_db": self._check_contrast_floor_db(contrast_floor_db, mode)}
+        self._span_pending = False
         self._init_responses(rir_A, rir_B)
         if mode == "broadband":
             self._init_broadband(device, seed)
@@ -237,7 +245,7 @@ class apvast:
                                  stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting,
                                  filter_taps=int(filter_length) if self.constrain_filter_length else 0,
                                  synthesis=self.synthesis, evaluation=self._evaluation,
-                                 evaluation_spectra=self._evaluation_spectra)
+                                 evaluation_spectra=self._evaluation_spectra, span=self._span_args())
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -370,6 +378,101 @@ class apvast:
             raise ValueError("evaluation_spectra needs validation_rir_A and validation_rir_B")
         return True
 
+    # ---- the per-bin span (mu_profile, rank_profile, contrast_floor_db) -------------------------------------
+    @staticmethod
+    def _span_table(name, value, K, check):
+        a = np.asarray(value)
+        if a.shape == (K,):
+            a = np.stack([a, a])
+        if a.shape != (2, K):
+            raise ValueError(f"{name} must have shape ({K},) (both zone programs) or (2, {K}) (one row per program), got {a.shape}")
+        a = check(a)
+        a.flags.writeable = False
+        return a
+
+    @staticmethod
+    def _check_mu_profile(value, K, mode):
+        """mu_profile as a read-only (2, K) float64 array, or None: finite, non-negative factors of mu per bin."""
+        if value is None:
+            return None
+        if mode == "broadband":
+            raise ValueError("mu_profile is a subband keyword: broadband mode designs one filter for the whole band")
+
+        def check(a):
+            if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+                raise ValueError("mu_profile must hold finite, non-negative floats")
+            a = np.array(a, dtype=np.float64)
+            if not np.isfinite(a).all() or (a < 0).any():
+                raise ValueError("mu_profile must hold finite, non-negative floats")
+            return a
+        return apvast._span_table("mu_profile", value, K, check)
+
+    @staticmethod
+    def _check_rank_profile(value, K, L, mode):
+        """rank_profile as a read-only (2, K) int32 array, or None: the largest rank of each bin, integers in 1..L."""
+        if value is None:
+            return None
+        if mode == "broadband":
+            raise ValueError("rank_profile is a subband keyword: broadband mode designs one filter for the whole band")
+
+        def check(a):
+            if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"rank_profile must hold integers in 1..{L} (number_of_srcs)")
+            if (a < 1).any() or (a > L).any():
+                raise ValueError(f"rank_profile must hold integers in 1..{L} (number_of_srcs)")
+            return np.array(a, dtype=np.int32)
+        return apvast._span_table("rank_profile", value, K, check)
+
+    @staticmethod
+    def _check_contrast_floor_db(value, mode):
+        """contrast_floor_db as a finite float, or None."""
+        if value is None:
+            return None
+        if mode == "broadband":
+            raise ValueError("contrast_floor_db is a subband keyword: broadband mode designs one filter for the whole band")
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value):
+            raise ValueError("contrast_floor_db must be a finite float")
+        _capi.contrast_floor(value)          # ... whose 10^(dB / 10) is a positive, finite double
+        return float(value)
+
+    def _span_args(self):
+        """The span as _capi.Engine takes it; None when no part was given."""
+        s = self._span
+        if all(v is None for v in s.values()):
+            return None
+        return {"mu_profile": s["mu_profile"], "rank_cap": s["rank_profile"], "contrast_floor_db": s["contrast_floor_db"]}
+
+    def _set_span_part(self, name, value):
+        span = self.__dict__.get("_span")
+        if span is None or span[name] is None:
+            raise ValueError(f"{name} was not given at construction: the parts of the span are fixed there")
+        K, L = self._K, self.number_of_srcs
+        new = {"mu_profile": lambda: self._check_mu_profile(value, K, self.mode),
+               "rank_profile": lambda: self._check_rank_profile(value, K, L, self.mode),
+               "contrast_floor_db": lambda: self._check_contrast_floor_db(value, self.mode)}[name]()
+        if new is None:
+            raise ValueError(f"{name} cannot be removed: the parts of the span are fixed at construction")
+        span[name] = new
+        self._span_pending = True
+
+    # an assignment between two hops takes effect at the next one (_apply_live); `mu` stays the common factor of mu_profile
+    mu_profile = property(lambda self: self._span["mu_profile"], lambda self, v: self._set_span_part("mu_profile", v))
+    rank_profile = property(lambda self: self._span["rank_profile"], lambda self, v: self._set_span_part("rank_profile", v))
+    contrast_floor_db = property(lambda self: self._span["contrast_floor_db"],
+                                 lambda self, v: self._set_span_part("contrast_floor_db", v))
+
+    def _span_output(self, zone, what):
+        """span_rank (K,) int32 / span_contrast (K, L) float64 of the last hop, fetched when read.  None for an object without a
+        span, before the first hop, for a zone program that does not run, and for the contrast without a floor."""
+        if self.mode == "broadband" or self._span_args() is None or self._hops == 0 or not (self.run_A, self.run_B)[zone]:
+            return None
+        return self._eng.span(zone)[what]
+
+    span_rank_A = property(lambda self: self._span_output(0, 0))
+    span_rank_B = property(lambda self: self._span_output(1, 0))
+    span_contrast_A = property(lambda self: self._span_output(0, 1))
+    span_contrast_B = property(lambda self: self._span_output(1, 1))
+
     # ---- the evaluation stage (validation_rir_A / validation_rir_B): read from the device when asked for ------------------
     def _eval_dims(self):
         if self.__dict__.get("_evaluation") is None:
@@ -475,6 +578,9 @@ class apvast:
         if self._mu_pending:
             self._eng.set_mu(self._mu)
             self._mu_pending = False
+        if self._span_pending:
+            self._eng.set_span(**self._span_args())
+            self._span_pending = False
 
     # rir_A / rir_B (rir_length, L, M) and target_rir_A / target_rir_B (rir_length, M): an assignment between two hops takes effect at
     # the next one as lfilter(..., zi=state) makes it in the reference -- the samples already in take the old response's tail with

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/apvast_hip.h"
+#include "gevd_span.h"
 
 struct GevdParams {
     int n;            // GEVD order (= L in subband mode)
@@ -69,6 +70,10 @@ struct GevdParams {
     // 1: second launch behind kernels_gevd64.hip on the same stream (apv_launch_gevd makes it): a small grid whose workgroups walk
     // the status words and solve the bins left at 2 again, from the same inputs, in float64 throughout
     int only_status2;
+    // per-bin mu, per-bin rank cap, contrast floor and their outputs (gevd_span.h); apv_base_params fills it from the handle's span
+    // (apv_set_span): z[0] = table row 0 (program A), z[1] = row 1.  A launch whose FIRST zone program is B takes row 1 as z[0]
+    // (apv_span_first_zone).  span.on = 0: the launch does what it did before the span existed
+    SpanParams span;
 };
 
 struct apv_handle {
@@ -100,6 +105,16 @@ struct apv_handle {
     std::vector<double> eval_rv[2];  // validation responses of zone A, zone B: [Pv][L][Mv]
     std::vector<int32_t> eval_ranks; // evaluated ranks, ascending, each in rank_list
     int eval_spectra;                // apv_stream_set_evaluation_spectra: per-bin spectra of the evaluation stage (0: off)
+    // apv_set_span: which parts exist is fixed by the first call; the tables and outputs are [2][n_bins] (row = zone program)
+    struct Span {
+        bool on = false, has_mu = false, has_cap = false, has_floor = false;
+        double phi = 0.0;
+        std::vector<double> profile;     // [2][K] as given: apv_set_mu re-forms mu_eff from it
+        double* d_mu_eff = nullptr;      // [2][K]
+        int32_t* d_cap = nullptr;        // [2][K]
+        int32_t* d_rank = nullptr;       // [2][K]
+        double* d_contrast = nullptr;    // [2][K][L], only with a floor
+    } span;
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -148,6 +163,8 @@ int apv_fail(apv_handle* h, int code, const std::string& msg);
 // helper thread of a call sets it, so that h->err has one writer: the thread that returns the call's code.
 void apv_fail_redirect(std::string* sink);
 GevdParams apv_base_params(const apv_handle* h);
+// the launch's first (or only) zone program is program `zone`: its row of the span's tables and outputs becomes span.z[0]
+inline void apv_span_first_zone(GevdParams& p, int zone) { if (zone) p.span.z[0] = p.span.z[1]; }
 
 // hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, bytes) on the current device, once per device: the attribute is the
 // device's.  `done` is the caller's static record for this kernel, bit d for device d (from device 64 on: set at every call).

@@ -74,6 +74,19 @@ GevdParams apv_base_params(const apv_handle* h) {
     p.out_c128 = c.out_c128;
     p.Lspill = h->d_Lspill;
     p.stamps = h->d_stamps;
+    // the span of the handle (apv_set_span): row z of its tables and outputs for zone program z
+    const apv_handle::Span& sp = h->span;
+    if (sp.on) {
+        const size_t K = c.n_bins, L = c.n_srcs;
+        p.span.on = 1;
+        p.span.phi = sp.phi;
+        for (size_t z = 0; z < 2; ++z) {
+            p.span.z[z].mu_eff = sp.d_mu_eff ? sp.d_mu_eff + z * K : nullptr;
+            p.span.z[z].cap = sp.d_cap ? sp.d_cap + z * K : nullptr;
+            p.span.z[z].rank = sp.d_rank + z * K;
+            p.span.z[z].contrast = sp.d_contrast ? sp.d_contrast + z * K * L : nullptr;
+        }
+    }
     return p;
 }
 
@@ -310,7 +323,8 @@ int apv_destroy(apv_handle* h) {
     if (h->ev_ag1) (void)hipEventDestroy(h->ev_ag1);
     if (h->d_bar) (void)hipFree(h->d_bar);
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
-    void* bufs[] = {h->d_XB, h->d_XD, h->d_d, h->d_w, h->d_lam, h->d_status, h->d_Lspill, h->d_Lspill_lane1, h->d_Rscratch};
+    void* bufs[] = {h->d_XB, h->d_XD, h->d_d, h->d_w, h->d_lam, h->d_status, h->d_Lspill, h->d_Lspill_lane1, h->d_Rscratch,
+                    h->span.d_mu_eff, h->span.d_cap, h->span.d_rank, h->span.d_contrast};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -475,6 +489,7 @@ int apv_update_dev(apv_handle* h, const void* d_XB, const void* d_XD, const void
 int apv_set_update_streams(apv_handle* h, int32_t n) {
     if (!h) return APV_ERR_ARG;
     if (n != 1 && n != 2) return fail(h, APV_ERR_ARG, "update streams: 1 or 2");
+    if (n == 2 && h->span.on) return fail(h, APV_ERR_ARG, "update streams: one with a span (its outputs are one buffer)");
     HIPCHK(h, hipSetDevice(h->device));
     // drain first: whatever is in flight was ordered under the old scheme
     if (int rc = lanes_sync(h)) return rc;
@@ -652,6 +667,7 @@ int apv_jdiag_batched(apv_handle* h, int32_t n, int32_t batch, const double* h_A
     HIPCHK(h, hipMemcpyAsync(dA, h_A, mat, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(dB, h_B, mat, hipMemcpyHostToDevice, h->stream));
     GevdParams p = base_params(h);
+    p.span = SpanParams{};         // another order and batch than the span's tables; U and lambda do not depend on it
     p.n = n;
     p.K = batch;
     p.nV = 1;

@@ -16,6 +16,8 @@
 // gfx950 only.  Wavefront = 64.
 #include "apv_internal.h"
 
+#include <type_traits>
+
 #include <cstdlib>
 
 namespace {
@@ -130,7 +132,8 @@ __device__ __forceinline__ void rr_pair(int ne, int r, int a, int& p, int& q) {
 
 // XT: element type of the fused input slabs (float2 = c64, double2 = c128: the float64 streaming front-end)
 // one bin (k) of one zone program (blockIdx.y) by one workgroup
-template <typename T, int NMAX, int TPB, bool FUSED, bool SPILL, bool EXACT, typename XT>
+// SPAN: the instantiation of launches with a span (gevd_span.h); the other one holds none of its code
+template <typename T, int NMAX, int TPB, bool FUSED, bool SPILL, bool EXACT, typename XT, bool SPAN>
 __device__ __forceinline__ void gevd_vast_bin(const GevdParams& p, const int k) {
     // zone program of a two-zone launch (blockIdx.y); the argument block itself stays in scalar registers
     const bool z1 = (blockIdx.y == 1);
@@ -554,7 +557,7 @@ __device__ __forceinline__ void gevd_vast_bin(const GevdParams& p, const int k) 
                         dmin = fmin(dmin, dj);
                         dmax = fmax(dmax, dj);
                     }
-                    if (dmin < (T)1e-8 * dmax && dmin + (T)p.mu < (T)1e-2 * dmax) converged = false;
+                    if (dmin < (T)1e-8 * dmax && dmin + span_mu<SPAN, T>(p.span, z1, k, p.mu) < (T)1e-2 * dmax) converged = false;
                 }
             }
         }
@@ -601,18 +604,20 @@ __device__ __forceinline__ void gevd_vast_bin(const GevdParams& p, const int k) 
         if (tid < n) {
             C s = mk<T>(0, 0);
             for (int l = 0; l < n; ++l) s = cadd(s, ccmul(sV[l * LD + tid], sr[l]));
-            const T den = (T)1 / (sLam[tid] + (T)p.mu);
+            const T den = (T)1 / (sLam[tid] + span_mu<SPAN, T>(p.span, z1, k, p.mu));
             scoef[tid] = cscale(s, den);
         }
         __syncthreads();
     }
 
     // ---------------- outputs ----------------
+    // the span of the bin (gevd_span.h): no slot goes past s_k; n without a span
+    const int s_k = span_limit<SPAN, T>(p.span, z1, k, n, p.ranks[p.nV - 1], status != 1, true, sLam, scoef, sOrder, tid);
     if (tid < n) {
         C acc = mk<T>(0, 0);
         int done = 0;
         for (int t = 0; t < p.nV; ++t) {
-            const int V = p.ranks[t];
+            const int V = SPAN ? min(p.ranks[t], s_k) : p.ranks[t];
             if (status != 1) {
                 for (; done < V; ++done) {
                     const int c = sOrder[done];
@@ -642,10 +647,10 @@ __device__ __forceinline__ void gevd_vast_bin(const GevdParams& p, const int k) 
     if (pstatus != nullptr && tid == 0) pstatus[k] = status;
 }
 
-template <typename T, int NMAX, int TPB, bool FUSED, bool SPILL, bool EXACT, typename XT>
+template <typename T, int NMAX, int TPB, bool FUSED, bool SPILL, bool EXACT, typename XT, bool SPAN>
 __global__ void __launch_bounds__(TPB) gevd_vast_kernel(const GevdParams p) {
     if (!p.only_status2) {
-        gevd_vast_bin<T, NMAX, TPB, FUSED, SPILL, EXACT, XT>(p, blockIdx.x);
+        gevd_vast_bin<T, NMAX, TPB, FUSED, SPILL, EXACT, XT, SPAN>(p, blockIdx.x);
         return;
     }
     // fall-back launch behind the order-64 kernel: a small grid whose workgroups walk the status words and solve only the bins
@@ -658,7 +663,7 @@ __global__ void __launch_bounds__(TPB) gevd_vast_kernel(const GevdParams p) {
     if (!__syncthreads_or(mine)) return;
     for (int k = blockIdx.x; k < p.K; k += gridDim.x) {
         if (pstatus[k] != 2) continue;
-        gevd_vast_bin<T, NMAX, TPB, FUSED, SPILL, EXACT, XT>(p, k);
+        gevd_vast_bin<T, NMAX, TPB, FUSED, SPILL, EXACT, XT, SPAN>(p, k);
         __syncthreads();
     }
 }
@@ -670,15 +675,20 @@ hipError_t launch_t(const GevdParams& p, bool fused, hipStream_t s) {
     // a grid of K would queue for the compute units beside the next order-64 launch of a pipelined caller)
     const dim3 grid(p.only_status2 && p.K > 64 ? 64 : p.K, p.n_zones > 1 ? 2 : 1);
     const bool xd = fused && p.x_c128;
-    if (p.n == NMAX) {
-        if (xd) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, true, double2>), grid, dim3(TPB), 0, s, p);
-        else if (fused) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, true, float2>), grid, dim3(TPB), 0, s, p);
-        else hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, false, SPILL, true, float2>), grid, dim3(TPB), 0, s, p);
-    } else {
-        if (xd) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, false, double2>), grid, dim3(TPB), 0, s, p);
-        else if (fused) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, false, float2>), grid, dim3(TPB), 0, s, p);
-        else hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, false, SPILL, false, float2>), grid, dim3(TPB), 0, s, p);
-    }
+    auto launch = [&](auto span) {
+        constexpr bool SP = decltype(span)::value;
+        if (p.n == NMAX) {
+            if (xd) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, true, double2, SP>), grid, dim3(TPB), 0, s, p);
+            else if (fused) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, true, float2, SP>), grid, dim3(TPB), 0, s, p);
+            else hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, false, SPILL, true, float2, SP>), grid, dim3(TPB), 0, s, p);
+        } else {
+            if (xd) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, false, double2, SP>), grid, dim3(TPB), 0, s, p);
+            else if (fused) hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, true, SPILL, false, float2, SP>), grid, dim3(TPB), 0, s, p);
+            else hipLaunchKernelGGL((gevd_vast_kernel<T, NMAX, TPB, false, SPILL, false, float2, SP>), grid, dim3(TPB), 0, s, p);
+        }
+    };
+    if (p.span.on) launch(std::true_type{});
+    else launch(std::false_type{});
     return hipGetLastError();
 }
 

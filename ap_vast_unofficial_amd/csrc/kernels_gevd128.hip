@@ -27,6 +27,8 @@
 // dtype.  status 1 = loaded R_D (or R_B's bright loading) not positive definite: w, lam and U are zeros.  gfx950, wave 64.
 #include "apv_internal.h"
 
+#include <type_traits>
+
 #include <cstdlib>
 
 namespace {
@@ -53,6 +55,7 @@ struct Gevd128Args {
     void* U;                 // zone 0 only (explicit path)
     double2* slot;           // [zones][K] slots of (2 n^2 + n) c128
     int ranks[NM];
+    SpanParams span;         // GevdParams::span
 };
 
 struct Corr128Args {
@@ -260,7 +263,8 @@ __device__ double norm2_packed(const double2* sP, int n, double* sAl, double* sB
 // scalars 128 = 162688 of the CU's 163840
 constexpr int LDS_BYTES = NPK * 16 + 8 * NM * 16 + 4 * NM * 16 + 5 * NM * 8 + (NM + 64) * 4 + 16 * 8;
 
-template <typename RT>
+// SPAN: the instantiation of launches with a span (gevd_span.h); the other one holds none of its code
+template <typename RT, bool SPAN>
 __global__ void __launch_bounds__(TPB) gevd128_kernel(const Gevd128Args a) {
     extern __shared__ __align__(16) unsigned char lds[];
     double2* const sP = reinterpret_cast<double2*>(lds);
@@ -562,7 +566,7 @@ __global__ void __launch_bounds__(TPB) gevd128_kernel(const Gevd128Args a) {
             sOrd[rank] = tid;
             double2 c = c2(0, 0);
             for (int r = 0; r < n; ++r) c = cadd(c, cscale(sR[r], sZ[r * NM + tid]));
-            sU[tid] = cscale(c, 1.0 / (li + a.mu));
+            sU[tid] = cscale(c, 1.0 / (li + span_mu<SPAN, double>(a.span, z == 1, k, a.mu)));
         }
         __syncthreads();
         if (tid < n) sLam[tid] = sD[sOrd[tid]];
@@ -579,13 +583,15 @@ __global__ void __launch_bounds__(TPB) gevd128_kernel(const Gevd128Args a) {
     if (tid == 0 && a.status[z]) a.status[z][k] = status;
     // columns in groups of 8: the nV filters, then (U requested) the n eigenvectors.  col < nV: s_V; else z of rank col - nV
     const int ncols = a.nV + ((a.U && z == 0) ? n : 0);
+    // the span of the bin (gevd_span.h): no slot goes past s_k; n without a span.  (sD, sU: by unsorted column, like sOrd's entries)
+    const int s_k = span_limit<SPAN, double>(a.span, z == 1, k, n, a.ranks[a.nV - 1], ok, true, sD, sU, sOrd, tid);
     for (int c0 = 0; c0 < ncols; c0 += 8) {
         const int col = c0 + rg;
         const bool live = col < ncols && cl < n;
         double2 y = c2(0, 0);
         if (ok && live) {
             if (col < a.nV) {
-                const int V = a.ranks[col];
+                const int V = SPAN ? min(a.ranks[col], s_k) : a.ranks[col];
                 for (int t = 0; t < V; ++t) {
                     const int q = sOrd[t];
                     y = cadd(y, cscale(sU[q], sZ[cl * NM + q]));
@@ -653,7 +659,7 @@ __global__ void __launch_bounds__(TPB) gevd128_kernel(const Gevd128Args a) {
     }
 }
 
-std::atomic<unsigned long long> g_attr_c64{0}, g_attr_c128{0};
+std::atomic<unsigned long long> g_attr_c64{0}, g_attr_c128{0}, g_attr_span_c64{0}, g_attr_span_c128{0};
 
 }  // namespace
 
@@ -704,6 +710,7 @@ hipError_t apv_launch_gevd128(const GevdParams& p, int compute_dtype, bool fused
     a.n = n; a.K = p.K; a.nV = p.nV;
     a.reg_mode = p.reg_mode; a.out_c128 = p.out_c128;
     a.reg_dark = p.reg_dark; a.reg_bright = p.reg_bright; a.mu = p.mu;
+    a.span = p.span;
     for (int t = 0; t < p.nV; ++t) {
         const int V = ranks_all ? ranks_all[t] : p.ranks[t];
         if (V < 1 || V > n) {
@@ -749,14 +756,13 @@ hipError_t apv_launch_gevd128(const GevdParams& p, int compute_dtype, bool fused
         in64 = compute_dtype != APV_F64;
     }
     const dim3 grid(p.K, zones);
-    if (in64) {
-        const hipError_t e = apv_set_max_dynamic_lds(reinterpret_cast<const void*>(&gevd128_kernel<float2>), LDS_BYTES, g_attr_c64);
+    // one instantiation per (input type, span or none), each with its own record of the LDS attribute
+    auto launch = [&](auto kernel, std::atomic<unsigned long long>& done) -> hipError_t {
+        const hipError_t e = apv_set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), LDS_BYTES, done);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(gevd128_kernel<float2>, grid, dim3(TPB), LDS_BYTES, s, a);
-    } else {
-        const hipError_t e = apv_set_max_dynamic_lds(reinterpret_cast<const void*>(&gevd128_kernel<double2>), LDS_BYTES, g_attr_c128);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(gevd128_kernel<double2>, grid, dim3(TPB), LDS_BYTES, s, a);
-    }
-    return hipGetLastError();
+        hipLaunchKernelGGL(kernel, grid, dim3(TPB), LDS_BYTES, s, a);
+        return hipGetLastError();
+    };
+    if (p.span.on) return in64 ? launch(&gevd128_kernel<float2, true>, g_attr_span_c64) : launch(&gevd128_kernel<double2, true>, g_attr_span_c128);
+    return in64 ? launch(&gevd128_kernel<float2, false>, g_attr_c64) : launch(&gevd128_kernel<double2, false>, g_attr_c128);
 }

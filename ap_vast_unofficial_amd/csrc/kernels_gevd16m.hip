@@ -918,7 +918,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
             sx += __shfl_xor(sx, 16, 64); sy += __shfl_xor(sy, 16, 64);
             sx += __shfl_xor(sx, 32, 64); sy += __shfl_xor(sy, 32, 64);
             if (q4 == 0) {
-                const T den = rcp_full(sLam[i16] + (T)p.mu);
+                const T den = rcp_full(sLam[i16] + span_mu<true, T>(p.span, z1, k, p.mu));
                 scoef[i16] = mk<T>(sx * den, sy * den);
             }
         }
@@ -933,8 +933,11 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
         const int i16 = lane & 15;
         T ax = 0, ay = 0;
         int done = lane >> 4;
+        // the span of the bin (gevd_span.h): no slot goes past s_k.  Without a span s_k = N and the loop is the one it was
+        const int s_k = span_limit<true, T>(p.span, z1, k, N, p.ranks[p.nV - 1], status != 1, !HOPS || hop == p.span.last_hop, sLam,
+                                      scoef, sOrder, lane);
         for (int t = 0; t < p.nV; ++t) {
-            const int V = p.ranks[t];
+            const int V = min(p.ranks[t], s_k);
             if (status != 1) {
                 for (; done < V; done += 4) {
                     const int c = sOrder[done];

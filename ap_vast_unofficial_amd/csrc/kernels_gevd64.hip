@@ -33,6 +33,8 @@
 // grid, mirrored; the four diagonal tiles come rotated out of the pair solves themselves).
 #include "apv_internal.h"
 
+#include <type_traits>
+
 #include "gevd16_common.h"
 
 namespace {
@@ -635,7 +637,8 @@ __device__ __forceinline__ bool presolve_done(double off, double off_prev, doubl
 }
 
 // stage 3b .. 6 and the outputs of bin k; vf_src: the float32 eigenvector matrix of the sweeps (row stride vf_ld; LDS or scratch)
-template <typename XT>
+// SPAN: the instantiation of launches with a span (gevd_span.h); the other one holds none of its code
+template <typename XT, bool SPAN>
 __device__ __forceinline__ void back64(const GevdParams& p, const Sh& sh, bool z1, int k, const C128* gC, const C128* gW,
                                        const C64* vf_src, int vf_ld, int status, int n_sweeps) {
     void* const pw = z1 ? p.w1 : p.w;
@@ -786,7 +789,7 @@ __device__ __forceinline__ void back64(const GevdParams& p, const Sh& sh, bool z
                 sx += v.x * rr.x + v.y * rr.y;
                 sy += v.x * rr.y - v.y * rr.x;
             }
-            const double den = 1.0 / (sLam[tid] + p.mu);
+            const double den = 1.0 / (sLam[tid] + span_mu<SPAN, double>(p.span, z1, k, p.mu));
             scoef[tid] = mk<double>(sx * den, sy * den);
         }
         __syncthreads();
@@ -799,6 +802,8 @@ __device__ __forceinline__ void back64(const GevdParams& p, const Sh& sh, bool z
     // the segments in front of its last column plus the running sum inside that segment.  (Rounds 2-3a walked the sorted
     // columns one after the other in 64 threads, every step an index read and two dependent reads behind it: 8 us.)
     C128* const Tp = RB;
+    // the span of the bin (gevd_span.h): no slot goes past s_k; N64 without a span
+    const int s_k = span_limit<SPAN, double>(p.span, z1, k, N64, p.ranks[p.nV - 1], status != 1, true, sLam, scoef, sOrder, tid);
     if (status != 1) {
         const int l = tid & 63, part = tid >> 6;
         double ax = 0, ay = 0;
@@ -814,7 +819,7 @@ __device__ __forceinline__ void back64(const GevdParams& p, const Sh& sh, bool z
     __syncthreads();
     for (int idx = tid; idx < p.nV * N64; idx += 1024) {
         const int t = idx >> 6, l = idx & 63;
-        const int V = p.ranks[t];
+        const int V = SPAN ? min(p.ranks[t], s_k) : p.ranks[t];
         double ax = 0, ay = 0;
         if (status != 1 && V > 0) {
             const int seg = (V - 1) >> 2;
@@ -851,7 +856,7 @@ __device__ __forceinline__ void back64(const GevdParams& p, const Sh& sh, bool z
 
 // ---- one bin per workgroup ---------------------------------------------------------------------------------------------
 // XT: element type of the fused input slabs (float2 = c64, double2 = c128); FUSED = false takes explicit R_B, R_D, r (c128)
-template <bool FUSED, typename XT>
+template <bool FUSED, typename XT, bool SPAN>
 __global__ void __launch_bounds__(1024) gevd64_kernel(const GevdParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char sRegA[REGION];
     __shared__ __attribute__((aligned(16))) unsigned char sRegB[REGION];
@@ -906,14 +911,14 @@ __global__ void __launch_bounds__(1024) gevd64_kernel(const GevdParams p) {
         if (pstatus != nullptr && tid == 0) pstatus[k] = 100 * n_sweeps;
         return;
     }
-    back64<XT>(p, sh, z1, k, gC, gW, Vf, LDF, status, n_sweeps);
+    back64<XT, SPAN>(p, sh, z1, k, gC, gW, Vf, LDF, status, n_sweeps);
 }
 
 // ---- two bins per workgroup: float32 sweeps of the two bins interleaved ----------------------------------------------
 __constant__ signed char kUpperA[6] = {0, 0, 0, 1, 1, 2};          // the six tiles above the diagonal of the 4 x 4 pair grid
 __constant__ signed char kUpperB[6] = {1, 2, 3, 2, 3, 3};
 
-template <bool FUSED, typename XT>
+template <bool FUSED, typename XT, bool SPAN>
 __global__ void __launch_bounds__(1024) gevd64x2_kernel(const GevdParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char sRegA[REGION];
     __shared__ __attribute__((aligned(16))) unsigned char sRegB[REGION];
@@ -1080,13 +1085,13 @@ __global__ void __launch_bounds__(1024) gevd64x2_kernel(const GevdParams p) {
     if (tid < N64) sr[tid] = gRb(0)[tid];
     __syncthreads();
     stamp64(p, z1, k0, 4);
-    back64<XT>(p, sh, z1, k0, gCb(0), gWb(0), Vfb(0), LDF, status0, swp0);
+    back64<XT, SPAN>(p, sh, z1, k0, gCb(0), gWb(0), Vfb(0), LDF, status0, swp0);
     stamp64(p, z1, k0, 5);
     if (nb == 2) {
         __syncthreads();
         if (tid < N64) sr[tid] = gRb(1)[tid];
         __syncthreads();
-        back64<XT>(p, sh, z1, k0 + 1, gCb(1), gWb(1), gFb(1), N64, status1, swp1);
+        back64<XT, SPAN>(p, sh, z1, k0 + 1, gCb(1), gWb(1), gFb(1), N64, status1, swp1);
     }
     stamp64(p, z1, k0, 6);
 }
@@ -1116,16 +1121,21 @@ hipError_t apv_launch_gevd64(const GevdParams& p, int compute_dtype, bool fused,
     const bool xd = fused && p.x_c128;
     // one bin per workgroup while that still gives every CU its own workgroup (the two-bin kernel halves the grid), and for the
     // timing aids of the single-bin kernel (debug_stop 6, 7, 8)
-    if (p.K * (p.n_zones > 1 ? 2 : 1) < 512 || p.debug_stop >= 6) {
-        const dim3 grid(p.K, p.n_zones > 1 ? 2 : 1);
-        if (xd) hipLaunchKernelGGL((gevd64_kernel<true, double2>), grid, dim3(1024), 0, s, p);
-        else if (fused) hipLaunchKernelGGL((gevd64_kernel<true, float2>), grid, dim3(1024), 0, s, p);
-        else hipLaunchKernelGGL((gevd64_kernel<false, float2>), grid, dim3(1024), 0, s, p);
-    } else {
-        const dim3 grid((p.K + 1) / 2, p.n_zones > 1 ? 2 : 1);
-        if (xd) hipLaunchKernelGGL((gevd64x2_kernel<true, double2>), grid, dim3(1024), 0, s, p);
-        else if (fused) hipLaunchKernelGGL((gevd64x2_kernel<true, float2>), grid, dim3(1024), 0, s, p);
-        else hipLaunchKernelGGL((gevd64x2_kernel<false, float2>), grid, dim3(1024), 0, s, p);
-    }
+    auto launch = [&](auto span) {
+        constexpr bool SP = decltype(span)::value;
+        if (p.K * (p.n_zones > 1 ? 2 : 1) < 512 || p.debug_stop >= 6) {
+            const dim3 grid(p.K, p.n_zones > 1 ? 2 : 1);
+            if (xd) hipLaunchKernelGGL((gevd64_kernel<true, double2, SP>), grid, dim3(1024), 0, s, p);
+            else if (fused) hipLaunchKernelGGL((gevd64_kernel<true, float2, SP>), grid, dim3(1024), 0, s, p);
+            else hipLaunchKernelGGL((gevd64_kernel<false, float2, SP>), grid, dim3(1024), 0, s, p);
+        } else {
+            const dim3 grid((p.K + 1) / 2, p.n_zones > 1 ? 2 : 1);
+            if (xd) hipLaunchKernelGGL((gevd64x2_kernel<true, double2, SP>), grid, dim3(1024), 0, s, p);
+            else if (fused) hipLaunchKernelGGL((gevd64x2_kernel<true, float2, SP>), grid, dim3(1024), 0, s, p);
+            else hipLaunchKernelGGL((gevd64x2_kernel<false, float2, SP>), grid, dim3(1024), 0, s, p);
+        }
+    };
+    if (p.span.on) launch(std::true_type{});
+    else launch(std::false_type{});
     return hipGetLastError();
 }

@@ -390,6 +390,7 @@ static GevdParams fused_gevd_params(const apv_handle* h, const HopSpectra& q, vo
     p.w = wz[first];
     p.lam = lamz[first];
     p.status = status + (size_t)first * s->K;
+    apv_span_first_zone(p, first);
     p.n_zones = (runA && runB) ? 2 : 1;
     if (p.n_zones == 2) {
         p.XB1 = q.X[3]; p.XD1 = q.X[2]; p.d1 = q.tspec[1];
@@ -545,6 +546,7 @@ struct BackSchedule {
     hipStream_t tail_stream = nullptr;
     hipEvent_t copied = nullptr;
     void* lspill = nullptr;   // GevdParams::Lspill of this launch (nullptr: the handle's d_Lspill)
+    bool span_quiet = false;  // the launch does not write the span's outputs (hops that run side by side on several back streams)
     BackSchedule(void* result_, void* ospec_) : result((char*)result_), ospec((char*)ospec_) {}
 };
 
@@ -556,6 +558,10 @@ struct BackSchedule {
 // per-bin update per zone program: A: bright A->A, dark A->B, target A;  B: bright B->B, dark B->A, target B
 static int back_solve(apv_handle* h, hipStream_t st, const HopSpectra& q, void* const* wz, void* const* lamz, const BackSchedule& sch) {
     apv_stream* s = h->st;
+    auto hush = [&](GevdParams& p) {
+        if (sch.span_quiet)
+            for (SpanZone& z : p.span.z) { z.rank = nullptr; z.contrast = nullptr; }
+    };
     int32_t* const status = reinterpret_cast<int32_t*>(sch.result + hop_out_bytes(s));
     const int K = s->K, L = s->L, f64 = s->f64;
     std::string why;
@@ -581,9 +587,11 @@ static int back_solve(apv_handle* h, hipStream_t st, const HopSpectra& q, void* 
             GevdParams p = apv_base_params(h);
             p.RB = s->win_RB[z]; p.RD = s->win_RD[z]; p.r = s->win_r[z];
             p.w = wz[z]; p.lam = lamz[z]; p.status = status + (size_t)z * K;
+            apv_span_first_zone(p, z);
             p.n_zones = 1;
             p.no_gevd64 = s->fg_beta > 0.0 ? s->fg_no_gevd64 : win_low_rank(h);
             if (sch.lspill) p.Lspill = sch.lspill;
+            hush(p);
             hipError_t e = apv_launch_gevd(p, s->win_c128 ? APV_F64 : APV_F32, false, st, &why, h->rank_list.data());
             if (e != hipSuccess) return launch_fail(h, e, why);
         }
@@ -594,6 +602,7 @@ static int back_solve(apv_handle* h, hipStream_t st, const HopSpectra& q, void* 
     // one block of fewer than L rows: win_low_rank's route at T = 1, on every hop (float64 arithmetic only, as in apv_update_dev)
     p.no_gevd64 = s->M < L && h->cfg.compute_dtype == APV_F64;
     if (sch.lspill) p.Lspill = sch.lspill;
+    hush(p);
     hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, st, &why, h->rank_list.data());
     if (e != hipSuccess) return launch_fail(h, e, why);
     return APV_OK;
@@ -1192,6 +1201,7 @@ struct ChunkCall {
     void* wset[CK_NB][2];
     void* lset[CK_NB][2];
     long hop_first;
+    int n_hops = 0;                              // hops of the call
     int ring_first, cur_first;
     int last_par = 0, last_nc = 0, last_b = 0;   // chunk parity, hops and back stream of the last hop enqueued
 };
@@ -1383,6 +1393,7 @@ static int chunk_back_batched(ChunkCall& k, int c, int nc) {
         p.hop_w = k.hop_w;
         p.hop_lam = k.hop_lam;
         p.hop_status = hop_result_bytes(s);
+        p.span.last_hop = nc - 1;        // the span's outputs are those of the chunk's last hop
         std::string why;
         hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, b0, &why);
         if (e != hipSuccess) return launch_fail(h, e, why);
@@ -1432,6 +1443,8 @@ static int chunk_back_hops(ChunkCall& k, int c, int nc) {
         BackSchedule sch = chunk_slots(s, par, i);
         sch.yield_issue = 1;
         sch.lspill = b > 0 ? s->ck_spill[b - 1] : nullptr;
+        // the hops of the back streams run side by side: the span's outputs are written by the call's last hop alone
+        sch.span_quiet = s->hop - k.hop_first != k.n_hops - 1;
         int rc;
         if (k.cons) {
             // the back stream runs the joint diagonalisation alone, into the hop's own slots of ck_wall / ck_lamall: the
@@ -1557,6 +1570,7 @@ static int process_signal_chunked_t(apv_handle* h, int n_hops, const TI* h_in_A,
     if (rc != APV_OK) return rc;
     ChunkCall k;
     if ((rc = chunk_begin(h, k)) != APV_OK) return rc;
+    k.n_hops = n_hops;
     const int H = s->H, chunk = s->sig_chunk;
     // staging slot c mod 3 holds chunk c
     SignalCall<TI> call(h, n_hops, h_out, k.bs, CK_NB, s->ck_done, s->ck_pin_out, CK_NS);
@@ -2054,6 +2068,7 @@ int apv_stream_get_statistics(apv_handle* h, int32_t zone, double* h_RB, double*
         if (!dl) SCHK(h, s->own.device(&dl, (size_t)K * L * 8));
         if (!dst) SCHK(h, s->own.device(&dst, (size_t)K * 4));
         GevdParams p = apv_base_params(h);
+        p.span = SpanParams{};     // U and lambda do not depend on the span, and its outputs stay those of the last hop
         const size_t sb = apv_gevd_spill_bytes(L, K, APV_F64, p.reg_mode, p.reg_bright, p.sweep_tol2, 1);
         if (sb > s->stat_spill_bytes) {
             s->own.release(dspill);
@@ -2150,6 +2165,18 @@ int apv_stream_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, c
     return APV_OK;
 }
 
+// ---- the per-bin span (include/apvast_hip.h, gevd_span.h) ----
+// mu_eff = cfg.mu * profile, uploaded on the handle's stream
+static int span_upload_mu(apv_handle* h) {
+    apv_handle::Span& sp = h->span;
+    std::vector<double> eff(sp.profile.size());
+    for (size_t i = 0; i < eff.size(); ++i) eff[i] = h->cfg.mu * sp.profile[i];
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipMemcpyAsync(sp.d_mu_eff, eff.data(), sizeof(double) * eff.size(), hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));               // eff goes out of scope
+    return APV_OK;
+}
+
 // mu of the next hop on (either stream mode).  The per-hop graphs of the subband stream hold it by value: they are captured again.
 //                                                         replaces `ap.mu = ...`, read at apvast.py:161, 406-414
 int apv_set_mu(apv_handle* h, double mu) {
@@ -2161,6 +2188,81 @@ int apv_set_mu(apv_handle* h, double mu) {
         drop_hop_graphs(h->st);
     }
     h->cfg.mu = mu;
+    // a span with a mu profile: the kernels read mu * profile from a table, not the launch's mu
+    if (h->span.on && h->span.has_mu) return span_upload_mu(h);
+    return APV_OK;
+}
+
+int apv_set_span(apv_handle* h, const double* h_mu_profile, const int32_t* h_rank_cap, double contrast_floor) {
+    if (!h) return apv_fail(h, APV_ERR_ARG, "null handle");
+    apv_handle::Span& sp = h->span;
+    const size_t K = (size_t)h->cfg.n_bins, L = (size_t)h->cfg.n_srcs, n = 2 * K;
+    const bool has_mu = h_mu_profile != nullptr, has_cap = h_rank_cap != nullptr, has_floor = contrast_floor != 0.0;
+    // everything is checked before anything changes
+    if (!std::isfinite(contrast_floor) || contrast_floor < 0.0) return apv_fail(h, APV_ERR_ARG, "apv_set_span: the contrast floor must be finite and >= 0");
+    if (!has_mu && !has_cap && !has_floor) return apv_fail(h, APV_ERR_ARG, "apv_set_span: no part given");
+    if (sp.on) {
+        if (has_mu != sp.has_mu || has_cap != sp.has_cap || has_floor != sp.has_floor)
+            return apv_fail(h, APV_ERR_ARG, "apv_set_span: the first call fixed which parts the span has; a part cannot be added or removed");
+    } else {
+        if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_set_span: the stream is initialised (a span is given before apv_stream_init)");
+        if (h->bb) return apv_fail(h, APV_ERR_ARG, "apv_set_span: the span is a subband feature; this handle runs the broadband stream");
+        if (h->n_lanes > 1) return apv_fail(h, APV_ERR_ARG, "apv_set_span: not with two update streams (the span's outputs are one buffer)");
+    }
+    for (size_t i = 0; has_mu && i < n; ++i)
+        if (!std::isfinite(h_mu_profile[i]) || h_mu_profile[i] < 0.0) return apv_fail(h, APV_ERR_ARG, "apv_set_span: the mu profile must be finite and >= 0");
+    for (size_t i = 0; has_cap && i < n; ++i)
+        if (h_rank_cap[i] < 1 || h_rank_cap[i] > (int32_t)L) return apv_fail(h, APV_ERR_ARG, "apv_set_span: rank cap out of 1..L");
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    if (!sp.on) {
+        const size_t nn = n ? n : 1, nc = nn * (L ? L : 1);
+        // all four buffers or none: a failure frees what the call had allocated, so that a second first call starts clean
+        hipError_t e = hipSuccess;
+        if (has_mu) e = hipMalloc((void**)&sp.d_mu_eff, sizeof(double) * nn);
+        if (e == hipSuccess && has_cap) e = hipMalloc((void**)&sp.d_cap, sizeof(int32_t) * nn);
+        if (e == hipSuccess) e = hipMalloc((void**)&sp.d_rank, sizeof(int32_t) * nn);
+        if (e == hipSuccess) e = hipMemsetAsync(sp.d_rank, 0, sizeof(int32_t) * nn, h->stream);
+        if (e == hipSuccess && has_floor) e = hipMalloc((void**)&sp.d_contrast, sizeof(double) * nc);
+        if (e == hipSuccess && has_floor) e = hipMemsetAsync(sp.d_contrast, 0, sizeof(double) * nc, h->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);
+            void** bufs[] = {(void**)&sp.d_mu_eff, (void**)&sp.d_cap, (void**)&sp.d_rank, (void**)&sp.d_contrast};
+            for (void** b : bufs) {
+                if (*b) (void)hipFree(*b);
+                *b = nullptr;
+            }
+            return apv_fail(h, APV_ERR_HIP, std::string("apv_set_span: ") + hipGetErrorString(e));
+        }
+        sp.has_mu = has_mu; sp.has_cap = has_cap; sp.has_floor = has_floor;
+        sp.on = true;
+    }
+    if (has_cap) {
+        SCHK(h, hipMemcpyAsync(sp.d_cap, h_rank_cap, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));           // h_rank_cap is the caller's
+    }
+    if (has_floor && contrast_floor != sp.phi) {
+        if (h->st) drop_hop_graphs(h->st);                  // the per-hop graphs hold phi by value, like mu
+        sp.phi = contrast_floor;
+    }
+    if (has_mu) {
+        sp.profile.assign(h_mu_profile, h_mu_profile + n);
+        return span_upload_mu(h);
+    }
+    return APV_OK;
+}
+
+int apv_get_span(apv_handle* h, int32_t zone, int32_t* h_rank, double* h_contrast) {
+    if (!h) return apv_fail(h, APV_ERR_ARG, "null handle");
+    const apv_handle::Span& sp = h->span;
+    if (!sp.on) return apv_fail(h, APV_ERR_ARG, "apv_get_span: the handle has no span (apv_set_span)");
+    if (zone != 0 && zone != 1) return apv_fail(h, APV_ERR_ARG, "apv_get_span: zone must be 0 or 1");
+    if (h_contrast && !sp.has_floor) return apv_fail(h, APV_ERR_ARG, "apv_get_span: the contrast curve is written only with a contrast floor");
+    const size_t K = (size_t)h->cfg.n_bins, L = (size_t)h->cfg.n_srcs;
+    SCHK(h, hipSetDevice(h->device));
+    if (h_rank) SCHK(h, hipMemcpyAsync(h_rank, sp.d_rank + zone * K, sizeof(int32_t) * K, hipMemcpyDeviceToHost, h->stream));
+    if (h_contrast) SCHK(h, hipMemcpyAsync(h_contrast, sp.d_contrast + zone * K * L, sizeof(double) * K * L, hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
     return APV_OK;
 }
 

@@ -422,6 +422,25 @@ int  apv_stream_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, 
 /* mu of the next hop on, either stream mode (the subband stream's captured per-hop graphs are captured again).
  *                        replaces `ap.mu = ...` between two hops, read at apvast.py:161, 406-414 */
 int  apv_set_mu(apv_handle* h, double mu);
+/* The per-bin span of the subband filters.  With lambda_1 >= ... >= lambda_L, u_i the sorted joint eigenvectors of
+ * bin k of zone program z and a_i = (u_i^H r) / (lambda_i + mu_k):
+ *   h_mu_profile [2][n_bins] (>= 0, finite)  mu_k = cfg.mu * profile[z][k]
+ *   h_rank_cap   [2][n_bins] (1..n_srcs)     no output slot of the bin goes past rank cap[z][k]
+ *   contrast_floor phi (> 0; 0 = none)       ... nor past f_k, the number of leading v for which
+ *                                            sum_{i<=v} lambda_i |a_i|^2 >= phi sum_{i<=v} |a_i|^2   (at least 1)
+ * Output slot t of the bin holds the filter of rank min(ranks[t], cap, f_k); lambda is unchanged.  Row 0 of a table is zone
+ * program A and every kernel-level call (apv_update*, apv_gevd_vast_dev), row 1 program B.  NULL / 0: that part is absent.
+ * The first call fixes which parts exist; for a stream it precedes apv_stream_init.  Later calls change the values of the parts
+ * that exist, from the next launch or hop on (tables are uploaded on the handle's stream; for phi the per-hop graphs of a stream
+ * are captured again).  APV_ERR_ARG, with nothing changed: a part added or removed later, a negative or non-finite profile, a cap
+ * outside 1..n_srcs, phi < 0 or non-finite, a handle with two update streams.  apv_set_mu on such a handle re-forms cfg.mu *
+ * profile.  The broadband entry points refuse a handle with a span.           replaces: nothing in the reference */
+int  apv_set_span(apv_handle* h, const double* h_mu_profile, const int32_t* h_rank_cap, double contrast_floor);
+/* Outputs of the span of the last launch (after apv_process_signal*: of its last hop) for zone program `zone` (0 / 1):
+ * h_rank [n_bins] int32 = min(last rank of the list, cap, f_k), 0 in a bin of status 1; h_contrast [n_bins][n_srcs] float64 (may be
+ * NULL) = the contrast curve c_v = sum_{i<=v} lambda_i |a_i|^2 / sum_{i<=v} |a_i|^2.  APV_ERR_ARG on a handle without a span and
+ * when h_contrast is asked for without a floor.  Synchronises the handle's stream. */
+int  apv_get_span(apv_handle* h, int32_t zone, int32_t* h_rank, double* h_contrast);
 /* Named state arrays for fixtures / checkpoint-resume (names: see stream.hip), in the front-end precision:
  * float32 / complex64, or float64 / complex128 with the float64 front-end.          apvast.py:115-151 */
 int  apv_state_bytes(apv_handle* h, const char* name, size_t* bytes);
