@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -140,6 +140,9 @@ def load():
     lib.apv_set_mu.argtypes = [vp, C.c_double]
     lib.apv_set_span.argtypes = [vp, vp, vp, C.c_double]
     lib.apv_get_span.argtypes = [vp, i32, vp, vp]
+    lib.apv_stream_set_effort_limit.argtypes = [vp, vp]
+    lib.apv_get_effort.argtypes = [vp, i32, vp, vp, vp]
+    lib.apv_limit_effort.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.apv_state_bytes.argtypes = [vp, C.c_char_p, C.POINTER(sz)]
     lib.apv_get_state.argtypes = [vp, C.c_char_p, vp, sz]
     lib.apv_set_state.argtypes = [vp, C.c_char_p, vp, sz]
@@ -244,7 +247,7 @@ class Engine:
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
                  out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola", evaluation=None,
-                 evaluation_spectra=False, span=None):
+                 evaluation_spectra=False, span=None, effort_limit=None):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -309,6 +312,9 @@ class Engine:
         self.span_parts = None
         if span is not None:
             self.set_span(**span)
+        self.effort_limited = False
+        if effort_limit is not None:
+            self.set_effort_limit(effort_limit)
 
     def set_evaluation_spectra(self, on):
         """Per-bin spectra of the evaluation stage, before stream_init (apv_stream_set_evaluation_spectra); needs set_evaluation."""
@@ -735,6 +741,50 @@ class Engine:
         con = np.empty((self.K, self.L), dtype=np.float64) if self.span_parts and self.span_parts[2] else None
         self._chk(self.lib.apv_get_span(self.h, int(zone), _ptr(rank), None if con is None else _ptr(con)))
         return rank, con
+
+    def set_effort_limit(self, limit):
+        """The per-bin array-effort limit of the stream's filters (apv_stream_set_effort_limit): linear values > 0, +inf = no limit
+        in that bin, as (K,) (both zone programs) or (2, K) (row 0 = program A).  The first call comes before stream_init; later
+        calls change the values from the next hop on."""
+        a = np.asarray(limit, dtype=np.float64)
+        if a.shape == (self.K,):
+            a = np.stack([a, a])
+        if a.shape != (2, self.K):
+            raise ValueError(f"the effort limit has shape ({self.K},) or (2, {self.K}), got {a.shape}")
+        a = np.ascontiguousarray(a)
+        self._chk(self.lib.apv_stream_set_effort_limit(self.h, _ptr(a)))
+        self.effort_limited = True
+
+    def effort(self, zone):
+        """Outputs of the effort limit of the last hop for zone program `zone` (apv_get_effort): (effort (K, nV) float64, the
+        filters' efforts before the stage; rank (K,) int32, the rank the top slot was taken from; gain (K,) float64 of the top slot)."""
+        eff = np.empty((self.K, self.nV), dtype=np.float64)
+        rank = np.empty(self.K, dtype=np.int32)
+        gain = np.empty(self.K, dtype=np.float64)
+        self._chk(self.lib.apv_get_effort(self.h, int(zone), _ptr(eff), _ptr(rank), _ptr(gain)))
+        return eff, rank, gain
+
+    def limit_effort(self, w, limit):
+        """The stage alone (apv_limit_effort): w (K, nV, L) or (hops, K, nV, L), complex64 or complex128 (anything else is taken as
+        complex128), limit (K,) linear -> (w', effort (.., K, nV) float64, src_top (.., K) int32, gain (.., K) float64); src_top is
+        the index of the slot the top slot was taken from (its own where it was scaled, -1 where its effort was not finite)."""
+        w = np.asarray(w)
+        dt = np.complex64 if w.dtype == np.complex64 else np.complex128
+        w = np.array(w, dtype=dt, order="C")                 # a copy: the call works in place
+        if w.ndim not in (3, 4):
+            raise ValueError("w must be (K, nV, L) or (hops, K, nV, L)")
+        lead = w.shape[:-2]
+        hops = 1 if w.ndim == 3 else w.shape[0]
+        K, nV, L = w.shape[-3:]
+        lim = np.ascontiguousarray(limit, dtype=np.float64)
+        if lim.shape != (K,):
+            raise ValueError(f"limit must have shape ({K},), got {lim.shape}")
+        eff = np.empty(lead + (nV,), dtype=np.float64)
+        src = np.empty(lead, dtype=np.int32)
+        gain = np.empty(lead, dtype=np.float64)
+        self._chk(self.lib.apv_limit_effort(self.h, int(dt == np.complex128), hops, K, nV, L, _ptr(w), _ptr(lim), _ptr(eff),
+                                            _ptr(src), _ptr(gain)))
+        return w, eff, src, gain
 
     def stream_set_perceptual(self, tables, normalisation):
         """tables: ap_vast_unofficial_amd.perceptual.PerceptualTables (or None to switch the weighting off)."""

@@ -71,6 +71,15 @@ What is different (keyword-only, after ``perceptual``)
     ``evaluation.spectral_metrics`` gives contrast and NMSE per bin or band, ``reset_evaluation()`` zeroes them too, and
     get_state() gains ``evaluation_spectra`` (Z, 3 E + 1, K, Mv) and ``evaluation_ring`` (Z, 2 E + 1, Mv, N).  Everything else the
     stream computes is unchanged, bit for bit.  Block sizes up to 4096.
+  * ``effort_limit_db`` (subband mode; a float, (K,) or (2, K) array of dB values, row 0 = zone program A, ``+inf`` = no limit in
+    that bin): the array effort e = sum_l |W[k, v, l]|^2 of every filter of a hop -- relative to the reference loudspeaker alone,
+    whose effort is 0 dB -- is held to E = 10^(dB / 10) between the joint diagonalisation and the filter-length projection.  A
+    filter with e <= E stays as it is; one above takes the filter of the largest lower rank that holds the limit, or is scaled by
+    sqrt(E / e) when there is none.  ``effort_A`` / ``_B`` (K, V) return the efforts before the stage (linear), ``effort_rank_*``
+    (K,) the rank the top filter was taken from (its own where it was scaled) and ``effort_gain_*`` (K,) its gain, all of the last
+    hop; None without the keyword, before the first hop and for a zone that does not run.  The value can be reassigned between
+    hops (not to None); w_*, w_time_* and the outputs are those of the limited filters, lambda_*, U_*, R_*, r_* and span_* are
+    unchanged, and get_state() has the same keys.
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).
@@ -173,6 +182,7 @@ class apvast:
                  mu_profile=None,
                  rank_profile=None,
                  contrast_floor_db=None,
+                 effort_limit_db=None,
                  statistics_hops=1):
         self.block_size = block_size
         self.filter_length = filter_length
@@ -221,6 +231,9 @@ class apvast:
                       "rank_profile": self._check_rank_profile(rank_profile, N // 2 + 1, L, mode),
                       "contrast_floor_db": self._check_contrast_floor_db(contrast_floor_db, mode)}
         self._span_pending = False
+        # the per-bin array-effort limit: whether the stage exists is fixed here, its values may be reassigned between hops
+        self._effort_limit_db = self._check_effort_limit_db(effort_limit_db, N // 2 + 1, mode)
+        self._effort_pending = False
         self._init_responses(rir_A, rir_B)
         if mode == "broadband":
             self._init_broadband(device, seed)
@@ -245,7 +258,8 @@ class apvast:
                                  stat_hops=self.statistics_hops, stat_forgetting=self.statistics_forgetting,
                                  filter_taps=int(filter_length) if self.constrain_filter_length else 0,
                                  synthesis=self.synthesis, evaluation=self._evaluation,
-                                 evaluation_spectra=self._evaluation_spectra, span=self._span_args())
+                                 evaluation_spectra=self._evaluation_spectra, span=self._span_args(),
+                                 effort_limit=self._effort_table())
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
@@ -473,6 +487,73 @@ class apvast:
     span_contrast_A = property(lambda self: self._span_output(0, 1))
     span_contrast_B = property(lambda self: self._span_output(1, 1))
 
+    # ---- the per-bin array-effort limit (effort_limit_db) ---------------------------------------------------
+    @staticmethod
+    def _check_effort_limit_db(value, K, mode):
+        """effort_limit_db as a read-only (2, K) float64 array of dB values, or None: a float, (K,) or (2, K); +inf = no limit."""
+        if value is None:
+            return None
+        if mode == "broadband":
+            raise ValueError("effort_limit_db is a subband keyword: broadband mode designs one filter for the whole band")
+        bad = "effort_limit_db must hold dB values that are floats, not NaN and not -inf (+inf: no limit in that bin)"
+        if isinstance(value, (bool, np.bool_, str, bytes)):
+            raise ValueError(bad)
+        try:
+            a = np.asarray(value)
+        except Exception:
+            raise ValueError(bad) from None
+        if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(bad)
+        a = np.array(a, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full((2, K), float(a))
+        elif a.shape == (K,):
+            a = np.stack([a, a])
+        if a.shape != (2, K):
+            raise ValueError(f"effort_limit_db must be a float or have shape ({K},) (both zone programs) or (2, {K}) (one row per "
+                             f"program), got {a.shape}")
+        if np.isnan(a).any() or np.isneginf(a).any():
+            raise ValueError(bad)
+        with np.errstate(over="ignore"):
+            lin = 10.0 ** (a / 10.0)
+        if (lin <= 0).any():
+            raise ValueError("effort_limit_db: 10^(dB / 10) must be a positive double")
+        a.flags.writeable = False
+        return a
+
+    def _effort_table(self):
+        """The limit as _capi.Engine takes it, (2, K) linear; None without the keyword."""
+        if self._effort_limit_db is None:
+            return None
+        with np.errstate(over="ignore"):
+            return 10.0 ** (self._effort_limit_db / 10.0)
+
+    def _set_effort_limit_db(self, value):
+        if self.__dict__.get("_effort_limit_db") is None:
+            raise ValueError("effort_limit_db was not given at construction: whether the stage exists is fixed there")
+        new = self._check_effort_limit_db(value, self._K, self.mode)
+        if new is None:
+            raise ValueError("effort_limit_db cannot be removed: whether the stage exists is fixed at construction (+inf lifts the limit)")
+        self._effort_limit_db = new
+        self._effort_pending = True
+
+    # an assignment between two hops takes effect at the next one (_apply_live)
+    effort_limit_db = property(lambda self: self._effort_limit_db, _set_effort_limit_db)
+
+    def _effort_output(self, zone, what):
+        """effort (K, V) float64 linear / effort_rank (K,) int32 / effort_gain (K,) float64 of the last hop, fetched when read.  None
+        for an object without the keyword, before the first hop and for a zone program that does not run."""
+        if self.mode == "broadband" or self._effort_limit_db is None or self._hops == 0 or not (self.run_A, self.run_B)[zone]:
+            return None
+        return self._eng.effort(zone)[what]
+
+    effort_A = property(lambda self: self._effort_output(0, 0))
+    effort_B = property(lambda self: self._effort_output(1, 0))
+    effort_rank_A = property(lambda self: self._effort_output(0, 1))
+    effort_rank_B = property(lambda self: self._effort_output(1, 1))
+    effort_gain_A = property(lambda self: self._effort_output(0, 2))
+    effort_gain_B = property(lambda self: self._effort_output(1, 2))
+
     # ---- the evaluation stage (validation_rir_A / validation_rir_B): read from the device when asked for ------------------
     def _eval_dims(self):
         if self.__dict__.get("_evaluation") is None:
@@ -581,6 +662,9 @@ class apvast:
         if self._span_pending:
             self._eng.set_span(**self._span_args())
             self._span_pending = False
+        if self._effort_pending:
+            self._eng.set_effort_limit(self._effort_table())
+            self._effort_pending = False
 
     # rir_A / rir_B (rir_length, L, M) and target_rir_A / target_rir_B (rir_length, M): an assignment between two hops takes effect at
     # the next one as lfilter(..., zi=state) makes it in the reference -- the samples already in take the old response's tail with

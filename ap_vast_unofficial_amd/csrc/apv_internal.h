@@ -115,6 +115,16 @@ struct apv_handle {
         int32_t* d_rank = nullptr;       // [2][K]
         double* d_contrast = nullptr;    // [2][K][L], only with a floor
     } span;
+    // apv_stream_set_effort_limit: the per-bin array-effort limit of the subband stream's filters (kernels_effort.hip).  The table
+    // and the outputs of the last hop are [2][n_bins] (row = zone program); `own` (an ApvOwned, made by the first call) holds them
+    struct Effort {
+        bool on = false;
+        class ApvOwned* own = nullptr;
+        double* d_limit = nullptr;       // [2][K], linear, +inf = no limit
+        double* d_effort = nullptr;      // [2][K][nV]
+        int32_t* d_src = nullptr;        // [2][K]: source slot of the top slot (kernels_effort.hip)
+        double* d_gain = nullptr;        // [2][K]
+    } effort;
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -300,6 +310,23 @@ hipError_t apv_launch_constrain_filters(int c128, int N, int J, int nV, int L, i
 // ... of the n_hops filter sets w[z] + i hop_w, taps to taps[z] + i hop_taps (strides in elements), in one launch (grid.z = hop x zone)
 hipError_t apv_launch_constrain_filters_hops(int c128, int N, int J, int nV, int L, int zones, void* const* w, void* const* taps,
                                              int n_hops, size_t hop_w, size_t hop_taps, hipStream_t s, std::string* why);
+
+// kernels_effort.hip: the array-effort limit (see the file header).  The filters w[z] [K][nV][L] complex (c128: double, else
+// float) of `zones` zone programs and n_hops hops (hop i at w[z] + i hop_w elements) limited in place by limit[z] [K], one launch.
+constexpr int APV_EFFORT_MAX_SLOTS = APV_MAX_SRCS;     // nV of a launch
+constexpr int EFFORT_EMIT_NONE = -1, EFFORT_EMIT_ALL = -2;
+struct EffortArgs {
+    void* w[2];
+    const double* limit[2];
+    double* effort[2];             // outputs (may be null with EFFORT_EMIT_NONE): [K][nV], ...
+    int32_t* src[2];               // ... [K] ...
+    double* gain[2];               // ... [K]
+    int zones = 1, n_hops = 1;
+    size_t hop_w = 0;
+    int emit_hop = 0;              // the hop that writes the outputs; EFFORT_EMIT_ALL: every hop, hop i's hop_bins bins further on
+    size_t hop_bins = 0;
+};
+hipError_t apv_launch_limit_effort(int c128, int K, int nV, int L, const EffortArgs& a, hipStream_t s, std::string* why);
 
 // kernels_firsynth.hip: the FIR synthesis of a constrained stream (see the file header).  One launch writes the groups
 // [program 0: nV][program 1: nV][target A][target B] (n_tgt = 0: no target groups) of H samples x L loudspeakers each; element

@@ -327,6 +327,7 @@ int apv_destroy(apv_handle* h) {
                     h->span.d_mu_eff, h->span.d_cap, h->span.d_rank, h->span.d_contrast};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    delete h->effort.own;
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -960,6 +961,44 @@ int apv_constrain_filters(apv_handle* h, void* d_w, int32_t n_bins, int32_t nV, 
     hipError_t e = apv_launch_constrain_filters(h->cfg.out_c128, N, J, nV, L, 1, w, taps, h->stream, &why);
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
+int apv_limit_effort(apv_handle* h, int32_t c128, int32_t n_hops, int32_t K, int32_t nV, int32_t L, void* h_w, const double* h_limit,
+                     double* h_effort, int32_t* h_rank, double* h_gain) {
+    if (!h || !h_w || !h_limit) return fail(h, APV_ERR_ARG, "apv_limit_effort: null argument");
+    if (n_hops < 1 || K < 1 || nV < 1 || L < 1) return fail(h, APV_ERR_ARG, "apv_limit_effort: n_hops, K, nV and L must be at least 1");
+    for (int32_t k = 0; k < K; ++k)
+        if (!(h_limit[k] > 0.0)) return fail(h, APV_ERR_ARG, "apv_limit_effort: a limit must be > 0 (+inf: no limit), not NaN");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    ApvOwned t;                                             // freed on every way out
+    const size_t nb = (size_t)n_hops * K, wbytes = nb * nV * L * (c128 ? 16 : 8);
+    char* dw = nullptr;
+    double *dlim = nullptr, *deff = nullptr, *dgain = nullptr;
+    int32_t* dsrc = nullptr;
+    HIPCHK(h, t.device(&dw, wbytes));
+    HIPCHK(h, t.device(&dlim, sizeof(double) * K));
+    HIPCHK(h, t.device(&deff, sizeof(double) * nb * nV));
+    HIPCHK(h, t.device(&dsrc, sizeof(int32_t) * nb));
+    HIPCHK(h, t.device(&dgain, sizeof(double) * nb));
+    HIPCHK(h, hipMemcpyAsync(dw, h_w, wbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dlim, h_limit, sizeof(double) * K, hipMemcpyHostToDevice, h->stream));
+    EffortArgs a;
+    a.w[0] = dw; a.limit[0] = dlim; a.effort[0] = deff; a.src[0] = dsrc; a.gain[0] = dgain;
+    a.n_hops = n_hops;
+    a.hop_w = (size_t)K * nV * L;
+    a.emit_hop = EFFORT_EMIT_ALL;
+    a.hop_bins = K;
+    std::string why;
+    hipError_t e = apv_launch_limit_effort(c128 != 0, K, nV, L, a, h->stream, &why);
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    HIPCHK(h, hipMemcpyAsync(h_w, dw, wbytes, hipMemcpyDeviceToHost, h->stream));
+    if (h_effort) HIPCHK(h, hipMemcpyAsync(h_effort, deff, sizeof(double) * nb * nV, hipMemcpyDeviceToHost, h->stream));
+    if (h_rank) HIPCHK(h, hipMemcpyAsync(h_rank, dsrc, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream));
+    if (h_gain) HIPCHK(h, hipMemcpyAsync(h_gain, dgain, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return APV_OK;
 }
 

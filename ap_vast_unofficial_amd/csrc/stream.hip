@@ -546,7 +546,8 @@ struct BackSchedule {
     hipStream_t tail_stream = nullptr;
     hipEvent_t copied = nullptr;
     void* lspill = nullptr;   // GevdParams::Lspill of this launch (nullptr: the handle's d_Lspill)
-    bool span_quiet = false;  // the launch does not write the span's outputs (hops that run side by side on several back streams)
+    bool span_quiet = false;  // the launch does not write the span's outputs, nor the effort limit's (hops that run side by side on
+                              // several back streams)
     BackSchedule(void* result_, void* ospec_) : result((char*)result_), ospec((char*)ospec_) {}
 };
 
@@ -622,6 +623,39 @@ static int back_constrain(apv_handle* h, hipStream_t st, void* const* wz) {
     if (e != hipSuccess) return launch_fail(h, e, why);
     if (s->cf_tm.ev[1]) SCHK(h, hipEventRecord(s->cf_tm.ev[1], st));
     return APV_OK;
+}
+
+// The array-effort limit on n_hops filter sets, w[z] + i hop_w (elements) of the zone programs that run: one launch on `st`.  The
+// outputs of the handle (apv_get_effort) are written by hop emit_hop of the launch (EFFORT_EMIT_NONE: by none).
+static int effort_launch(apv_handle* h, hipStream_t st, void* const* w, int n_hops, size_t hop_w, int emit_hop) {
+    const apv_stream* s = h->st;
+    const apv_handle::Effort& ef = h->effort;
+    const size_t K = s->K, nV = s->nV;
+    EffortArgs a;
+    const LiveZones lz(s);
+    a.zones = lz.nz;
+    for (int i = 0; i < lz.nz; ++i) {
+        const size_t z = lz.z[i];
+        a.w[i] = w[z];
+        a.limit[i] = ef.d_limit + z * K;
+        a.effort[i] = ef.d_effort + z * K * nV;
+        a.src[i] = ef.d_src + z * K;
+        a.gain[i] = ef.d_gain + z * K;
+    }
+    a.n_hops = n_hops;
+    a.hop_w = hop_w;
+    a.emit_hop = emit_hop;
+    std::string why;
+    hipError_t e = apv_launch_limit_effort(h->cfg.out_c128, s->K, s->nV, s->L, a, st, &why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    return APV_OK;
+}
+
+// The hop's filters `wz` held to the per-bin effort limit, in place, both zone programs in one launch (nothing in a stream without
+// a limit): the projection, K3, the attributes and the states read the limited filters.
+static int back_limit_effort(apv_handle* h, hipStream_t st, void* const* wz, const BackSchedule& sch) {
+    if (!h->effort.on) return APV_OK;
+    return effort_launch(h, st, wz, 1, 0, sch.span_quiet ? EFFORT_EMIT_NONE : 0);
 }
 
 // FIR synthesis in place of K3 and K4: the hop's taps and the taps of the hop before it applied to the input signals in
@@ -716,6 +750,7 @@ static int back_synthesis(apv_handle* h, hipStream_t st, void* pin_dst, const Ba
 static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void* const* wz, void* const* lamz, void* pin_dst,
                         const BackSchedule& sch) {
     int rc = back_solve(h, st, q, wz, lamz, sch);
+    if (rc == APV_OK) rc = back_limit_effort(h, st, wz, sch);
     if (rc == APV_OK) rc = back_constrain(h, st, wz);
     if (rc != APV_OK) return rc;
     if (h->st->fir_synth) return back_fir_synthesis(h, st, pin_dst, sch);
@@ -1398,6 +1433,10 @@ static int chunk_back_batched(ChunkCall& k, int c, int nc) {
         hipError_t e = apv_launch_gevd(p, h->cfg.compute_dtype, true, b0, &why);
         if (e != hipSuccess) return launch_fail(h, e, why);
     }
+    // the effort limit of the whole chunk in one launch; the outputs are those of the chunk's last hop (the chunks follow one
+    // another on this stream, so the call's last hop writes last)
+    if (h->effort.on)
+        if (int rc = effort_launch(h, b0, s->ck_wall, nc, k.hop_w / wsz(h), nc - 1)) return rc;
     if (k.cons)
         if (int rc = chunk_project(k, b0, nc)) return rc;
     if (k.fir) {
@@ -1472,7 +1511,9 @@ static int chunk_constrained_tail(const ChunkCall& k, int par, int nc) {
     apv_handle* h = k.h;
     const apv_stream* s = k.s;
     for (int b = 0; b < CK_NB; ++b) SIGCHK(h, hipStreamWaitEvent(s->tail, s->ck_backdone[par][b], 0));
-    int rc = chunk_project(k, s->tail, nc);
+    // the effort limit of the chunk's hops in one launch ahead of the projection (the back streams ran the diagonalisations alone)
+    int rc = h->effort.on ? effort_launch(h, s->tail, s->ck_wall, nc, k.hop_w / wsz(h), nc - 1) : APV_OK;
+    if (rc == APV_OK) rc = chunk_project(k, s->tail, nc);
     if (rc == APV_OK && k.fir) rc = chunk_synthesis(k, s->tail, par, nc);
     for (int i = 0; i < nc && !k.fir && rc == APV_OK; ++i) rc = chunk_hop_outputs(k, s->tail, par, i, chunk_slots(s, par, i));
     if (rc != APV_OK) return rc;
@@ -2263,6 +2304,62 @@ int apv_get_span(apv_handle* h, int32_t zone, int32_t* h_rank, double* h_contras
     if (h_rank) SCHK(h, hipMemcpyAsync(h_rank, sp.d_rank + zone * K, sizeof(int32_t) * K, hipMemcpyDeviceToHost, h->stream));
     if (h_contrast) SCHK(h, hipMemcpyAsync(h_contrast, sp.d_contrast + zone * K * L, sizeof(double) * K * L, hipMemcpyDeviceToHost, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
+// ---- the per-bin array-effort limit (include/apvast_hip.h, kernels_effort.hip) ----
+int apv_stream_set_effort_limit(apv_handle* h, const double* h_limit) {
+    if (!h) return apv_fail(h, APV_ERR_ARG, "null handle");
+    if (!h_limit) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_effort_limit: null table");
+    apv_handle::Effort& ef = h->effort;
+    const size_t K = (size_t)h->cfg.n_bins, L = (size_t)h->cfg.n_srcs, n = 2 * K;
+    // everything is checked before anything changes
+    if (h->bb) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_effort_limit: the effort limit is a subband feature; this handle runs the broadband stream");
+    if (!ef.on && h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_effort_limit: the stream is initialised (the first limit is given before apv_stream_init)");
+    for (size_t i = 0; i < n; ++i)
+        if (!(h_limit[i] > 0.0)) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_effort_limit: a limit must be > 0 (+inf: no limit), not NaN");
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    if (!ef.on) {
+        // the table and the outputs, all or none: a failure frees what the call had allocated.  The effort curve has room for
+        // every rank list the handle can take (n_ranks <= n_srcs)
+        ApvOwned* own = new ApvOwned;
+        double *lim = nullptr, *eff = nullptr, *gain = nullptr;
+        int32_t* src = nullptr;
+        hipError_t e = own->device(&lim, sizeof(double) * (n ? n : 1));
+        if (e == hipSuccess) e = own->zeroed(&eff, n * (L ? L : 1), sizeof(double), h->stream);
+        if (e == hipSuccess) e = own->device(&src, sizeof(int32_t) * (n ? n : 1));
+        if (e == hipSuccess) e = hipMemsetAsync(src, 0xff, sizeof(int32_t) * (n ? n : 1), h->stream);     // -1: nothing yet
+        if (e == hipSuccess) e = own->zeroed(&gain, n, sizeof(double), h->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);
+            delete own;
+            return apv_fail(h, APV_ERR_HIP, std::string("apv_stream_set_effort_limit: ") + hipGetErrorString(e));
+        }
+        ef.own = own; ef.d_limit = lim; ef.d_effort = eff; ef.d_src = src; ef.d_gain = gain;
+        ef.on = true;
+    }
+    // the hop graphs hold the table's address, not its values: no new capture
+    SCHK(h, hipMemcpyAsync(ef.d_limit, h_limit, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));               // h_limit is the caller's
+    return APV_OK;
+}
+
+int apv_get_effort(apv_handle* h, int32_t zone, double* h_effort, int32_t* h_rank, double* h_gain) {
+    if (!h) return apv_fail(h, APV_ERR_ARG, "null handle");
+    const apv_handle::Effort& ef = h->effort;
+    if (!ef.on) return apv_fail(h, APV_ERR_ARG, "apv_get_effort: the handle has no effort limit (apv_stream_set_effort_limit)");
+    if (zone != 0 && zone != 1) return apv_fail(h, APV_ERR_ARG, "apv_get_effort: zone must be 0 or 1");
+    const size_t K = (size_t)h->cfg.n_bins, nV = (size_t)h->cfg.n_ranks;
+    SCHK(h, hipSetDevice(h->device));
+    if (h_effort) SCHK(h, hipMemcpyAsync(h_effort, ef.d_effort + zone * K * nV, sizeof(double) * K * nV, hipMemcpyDeviceToHost, h->stream));
+    if (h_rank) SCHK(h, hipMemcpyAsync(h_rank, ef.d_src + zone * K, sizeof(int32_t) * K, hipMemcpyDeviceToHost, h->stream));
+    if (h_gain) SCHK(h, hipMemcpyAsync(h_gain, ef.d_gain + zone * K, sizeof(double) * K, hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    // the kernel leaves the source slot of the top slot (-1: its effort was not finite, or no hop has run); the caller gets that
+    // slot's rank
+    if (h_rank)
+        for (size_t k = 0; k < K; ++k) h_rank[k] = (h_rank[k] < 0 || (size_t)h_rank[k] >= nV) ? 0 : h->rank_list[(size_t)h_rank[k]];
     return APV_OK;
 }
 

@@ -172,6 +172,34 @@ int  apv_stream_set_filter_taps(apv_handle* h, int32_t J);
  *                                                         replaces: nothing in the reference (see apv_stream_set_filter_taps) */
 int  apv_constrain_filters(apv_handle* h, void* d_w, int32_t n_bins, int32_t nV, int32_t L, int32_t N, int32_t J, void* d_taps);
 
+/* Array-effort limit of the subband stream's filters.  The effort of output slot t of bin k is
+ * e_t = sum_l |W[k, t, l]|^2; the target path is a unit filter on the reference loudspeaker, so e_t is the array effort relative
+ * to that loudspeaker alone (1 = 0 dB).  With E = h_limit[z][k] (linear, > 0, +inf = no limit in that bin) every hop, behind the
+ * joint diagonalisation and ahead of the filter-length projection, one more kernel (csrc/kernels_effort.hip) makes slot t
+ *   unchanged                      if e_t <= E  (the slot is admissible; a non-finite e_t never is, and such a slot is left alone),
+ *   a bit copy of slot t'          t' the largest admissible slot below t, if there is one,
+ *   W[k, t, :] * sqrt(E / e_t)     otherwise (gain in float64, product rounded once to the filters' type).
+ * e_t is summed in float64 in an order fixed by n_srcs.  Everything downstream (projection, taps, output spectra, FIR synthesis,
+ * the states "w_A" / "w_B") sees the limited filters; eigenvalues, eigenvectors, statistics and the span's outputs do not change.
+ * h_limit is [2][n_bins], row 0 = zone program A.  The first call allocates the table and the outputs and comes between apv_create
+ * and apv_stream_init; later calls upload new values, which hold from the next hop on (the table is device memory: the captured
+ * hop graphs stay).  A handle that never had a limit launches what it launched before.  APV_ERR_ARG, nothing changed: a value
+ * that is NaN or <= 0, a first call on an initialised stream, a broadband handle.  The stage keeps no state from hop to hop.
+ *                                                         replaces: nothing in the reference */
+int  apv_stream_set_effort_limit(apv_handle* h, const double* h_limit);
+/* Outputs of the effort limit of the last hop (after apv_process_signal*: of its last hop) for zone program `zone` (0 / 1), any of
+ * them NULL when not wanted: h_effort [n_bins][n_ranks] float64 = the e_t before the stage; h_rank [n_bins] int32 = the rank (entry
+ * of the rank list) of the slot the top slot was taken from, its own rank where it was scaled, 0 where its effort was not finite or
+ * no hop has run; h_gain [n_bins] float64 = the gain of the top slot (1 unless scaled).  APV_ERR_ARG on a handle without a limit.
+ * Synchronises the handle's stream. */
+int  apv_get_effort(apv_handle* h, int32_t zone, double* h_effort, int32_t* h_rank, double* h_gain);
+/* The stage alone, on host arrays: h_w [n_hops][K][nV][L] complex (c128 != 0: complex128, else complex64) limited in place by
+ * h_limit [K] (the same table for every hop), nV <= 128; h_effort [n_hops][K][nV], h_rank [n_hops][K], h_gain [n_hops][K] as above
+ * (may be NULL), except that h_rank is the INDEX of the source slot of the top slot (its own index where it was scaled, -1 where its
+ * effort was not finite).  One launch, blockIdx.z = hop; every hop is computed as a call with that hop alone computes it. */
+int  apv_limit_effort(apv_handle* h, int32_t c128, int32_t n_hops, int32_t K, int32_t nV, int32_t L, void* h_w, const double* h_limit,
+                      double* h_effort, int32_t* h_rank, double* h_gain);
+
 /* Synthesis of the subband stream.  APV_SYNTH_WOLA (the default) is the reference's: output spectra, inverse transform, sine
  * window, overlap-add; its output lags the input by block_size - hop_size samples.  APV_SYNTH_FIR applies the J taps of a
  * constrained stream (apv_stream_set_filter_taps) as time-domain FIR filters with no latency: with x_z[n] the input of zone
