@@ -572,6 +572,8 @@ int apv_corr_dev(apv_handle* h, const void* d_XB, const void* d_XD, const void* 
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = lanes_join(h, true)) return rc;
     const apv_config& c = h->cfg;
+    // (a handle may have up to 128 loudspeakers; the kernels behind this entry point hold an order of at most APV_MAX_N)
+    if (c.n_srcs > APV_MAX_N) return fail(h, APV_ERR_ARG, "apv_corr_dev: n_srcs must be in 1..64");
     hipError_t e = apv_launch_corr(c.compute_dtype, c.n_bins, c.n_mics, c.n_srcs, (const float2*)d_XB,
                                    (const float2*)d_XD, (const float2*)d_d, d_RB, d_RD, d_r, h->stream);
     if (e != hipSuccess) return hipfail(h, e, "corr launch");

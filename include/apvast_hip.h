@@ -329,7 +329,8 @@ int  apv_update(apv_handle* h, const float* h_XB, const float* h_XD, const float
                 void* h_w, void* h_lam, int32_t* h_status);
 
 /* K5': correlation only -> R_B, R_D [K][L][L], r [K][L] in the compute dtype
- * (c64 for APV_F32, c128 for APV_F64), device-resident.   replaces apvast.py:329-364 */
+ * (c64 for APV_F32, c128 for APV_F64), device-resident.   replaces apvast.py:329-364
+ * n_srcs <= 64: APV_ERR_ARG on a handle of a larger order. */
 int  apv_corr_dev(apv_handle* h, const void* d_XB, const void* d_XD, const void* d_d,
                   void* d_RB, void* d_RD, void* d_r);
 

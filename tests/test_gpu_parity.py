@@ -421,19 +421,22 @@ def test_corr_mfma_f32_and_bf16(Engine, L, M):
     assert np.abs(RBh - RBh.conj().transpose(0, 2, 1)).max() <= 1e-5 * np.abs(RBh).max()
 
 
+def bf16_round(a):
+    """Real and imaginary parts of a complex array rounded to bf16 (to nearest even), as float32 values."""
+    def r32(x):
+        u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+        u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+        return u.astype(np.uint32).view(np.float32)
+    return r32(a.real) + 1j * r32(a.imag)
+
+
 def test_corr_bf16_exact_on_rounded_inputs(Engine):
     """The bf16 path is exact up to f32 accumulation once the inputs are rounded to bf16: many bins, two runs
     (a scheduling-dependent fault in an earlier build showed up in a few bins per launch only)."""
     rng = np.random.default_rng(77)
     K, L, M = 300, 64, 128
     XB, XD, d = cn(rng, K, M, L), cn(rng, K, M, L), cn(rng, K, M)
-
-    def rnd(a):
-        def r32(x):
-            u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-            u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-            return u.astype(np.uint32).view(np.float32)
-        return r32(a.real) + 1j * r32(a.imag)
+    rnd = bf16_round
     RB0, RD0, r0 = subband.correlate(rnd(XB), rnd(XD), rnd(d))
     eng = Engine(K, L, M, compute_dtype="f32")
     first = None
