@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -160,6 +160,8 @@ def load():
     lib.apv_eval_pressure.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.apv_stream_set_evaluation_spectra.argtypes = [vp, i32]
     lib.apv_eval_spectrum_step.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.apv_stream_set_evaluation_detectability.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double]
+    lib.apv_eval_detect_step.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp]
     lib.apv_bb_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_bb_process_block.argtypes = [vp, vp, vp, vp]
     lib.apv_bb_process_signal.argtypes = [vp, i32, vp, vp, vp]
@@ -247,7 +249,7 @@ class Engine:
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
                  out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola", evaluation=None,
-                 evaluation_spectra=False, span=None, effort_limit=None):
+                 evaluation_spectra=False, span=None, effort_limit=None, evaluation_detectability=None):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -315,6 +317,47 @@ class Engine:
         self.effort_limited = False
         if effort_limit is not None:
             self.set_effort_limit(effort_limit)
+        self.evaluation_detectability = False
+        if evaluation_detectability is not None:
+            self.set_evaluation_detectability(evaluation_detectability)
+
+    def set_evaluation_detectability(self, tables):
+        """Perceptual detectability of the evaluated pressures, before stream_init (apv_stream_set_evaluation_detectability); needs
+        set_evaluation_spectra.  tables: ap_vast_unofficial_amd.perceptual.PerceptualTables of the block size, or None (off)."""
+        if tables is None:
+            self._chk(self.lib.apv_stream_set_evaluation_detectability(self.h, 0, None, 0.0, 0.0, 0.0))
+            self.evaluation_detectability = False
+            return
+        G2 = np.ascontiguousarray(tables.G2, dtype=np.float64)
+        if G2.ndim != 2 or G2.shape[0] != self.K:
+            raise ValueError("the tables' G2 must be (n_bins, n_channels)")
+        self._chk(self.lib.apv_stream_set_evaluation_detectability(self.h, G2.shape[1], _ptr(G2), float(tables.Cs), float(tables.Ca),
+                                                                   float(tables.Leff)))
+        self.evaluation_detectability = True
+
+    def eval_detect_step(self, spec, tables, totals, Z, E):
+        """One step of the detectability stage alone (apv_eval_detect_step): spec (N/2 + 1, Z (2 E + 1), Mv) complex128, the bin-major
+        spectra of the pressure sets (per program: bright of the E ranks, dark of the E ranks, target); tables: PerceptualTables of
+        N (or any object with G2 (N/2 + 1, C), Cs, Ca, Leff); totals (Z, 6 E, Mv) float64.  Returns the hop's values (Z, 2 E, Mv)
+        -- per program the error of the E ranks, then the leak -- and the new totals."""
+        spec = np.ascontiguousarray(spec, dtype=np.complex128)
+        totals = np.ascontiguousarray(totals, dtype=np.float64)
+        G2 = np.ascontiguousarray(tables.G2, dtype=np.float64)
+        Z, E = int(Z), int(E)
+        if spec.ndim != 3 or G2.ndim != 2:
+            raise ValueError("spec must be (N/2 + 1, Z (2 E + 1), Mv) and the tables' G2 (N/2 + 1, C)")
+        K, sets, Mv = spec.shape
+        if sets != Z * (2 * E + 1) or G2.shape[0] != K or totals.shape != (Z, 6 * E, Mv):
+            raise ValueError("spec (N/2 + 1, Z (2 E + 1), Mv), G2 (N/2 + 1, C) and totals (Z, 6 E, Mv) do not agree")
+        ds, dt = self.to_device(spec), self.to_device(totals)
+        dh = DeviceBuffer(self, 8 * Z * 2 * E * Mv)
+        try:
+            self._chk(self.lib.apv_eval_detect_step(self.h, ds.ptr, 2 * (K - 1), Z, E, Mv, G2.shape[1], _ptr(G2), float(tables.Cs),
+                                                    float(tables.Ca), float(tables.Leff), dh.ptr, dt.ptr))
+            return dh.download((Z, 2 * E, Mv), np.float64), dt.download(totals.shape, np.float64)
+        finally:
+            for b in (ds, dt, dh):
+                b.free()
 
     def set_evaluation_spectra(self, on):
         """Per-bin spectra of the evaluation stage, before stream_init (apv_stream_set_evaluation_spectra); needs set_evaluation."""

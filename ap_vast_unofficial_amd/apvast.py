@@ -71,6 +71,16 @@ What is different (keyword-only, after ``perceptual``)
     ``evaluation.spectral_metrics`` gives contrast and NMSE per bin or band, ``reset_evaluation()`` zeroes them too, and
     get_state() gains ``evaluation_spectra`` (Z, 3 E + 1, K, Mv) and ``evaluation_ring`` (Z, 2 E + 1, Mv, N).  Everything else the
     stream computes is unchanged, bit for bit.  Block sizes up to 4096.
+  * ``evaluation_detectability=True`` (a bool; needs ``evaluation_spectra=True``): behind the spectra of every hop the device
+    evaluates the second half of the masking model, evaluateDetectability (perceptualModel.m:192-206): with w2_S the squared
+    weighting curve of a masker spectrum S (perceptualModel.m:118-139, un-normalised) and f = 2 / N^2, per program z, evaluated
+    rank e and validation microphone m, error = sum_{k>=1} w2_{T[z,m]}[k] f |T - B|^2 -- the reproduction error masked by the
+    program the listener wants -- and leak = sum_{k>=1} w2_{T[1-z,m]}[k] f |Dk|^2 -- the other program's leakage masked by this
+    zone's own target (with one program: by silence, the threshold in quiet).  D = 1 is just audible.  float64 whatever dtype is;
+    works with perceptual=False too (the tables are built once and shared).  ``evaluation_detectability()`` returns sums, maxima
+    and audible-hop counts, ``evaluation_detectability_hops()`` the last call's hops, ``evaluation.detectability_metrics`` means
+    and audible shares; get_state() gains ``evaluation_detectability`` (Z, 6 E + 1, Mv): the device's totals and, in a last row,
+    the hops they cover.  Everything else the stream computes is unchanged, bit for bit.
   * ``effort_limit_db`` (subband mode; a float, (K,) or (2, K) array of dB values, row 0 = zone program A, ``+inf`` = no limit in
     that bin): the array effort e = sum_l |W[k, v, l]|^2 of every filter of a hop -- relative to the reference loudspeaker alone,
     whose effort is 0 dB -- is held to E = 10^(dB / 10) between the joint diagonalisation and the filter-length projection.  A
@@ -178,6 +188,7 @@ class apvast:
                  validation_rir_B=None,
                  evaluation_ranks=None,
                  evaluation_spectra=False,
+                 evaluation_detectability=False,
                  statistics_forgetting=None,
                  mu_profile=None,
                  rank_profile=None,
@@ -226,6 +237,7 @@ class apvast:
         L, M, N, H = self.number_of_srcs, self.number_of_mics, self.block_size, self.hop_size
         self._evaluation = self._check_evaluation(validation_rir_A, validation_rir_B, evaluation_ranks, L, number_of_eigenvectors, mode)
         self._evaluation_spectra = self._check_evaluation_spectra(evaluation_spectra, self._evaluation, mode)
+        self._evaluation_detectability = self._check_evaluation_detectability(evaluation_detectability, self._evaluation_spectra, mode)
         # the per-bin span: which of its three parts exist is fixed here, their values may be reassigned between hops
         self._span = {"mu_profile": self._check_mu_profile(mu_profile, N // 2 + 1, mode),
                       "rank_profile": self._check_rank_profile(rank_profile, N // 2 + 1, L, mode),
@@ -250,6 +262,13 @@ class apvast:
         else:
             reg_mode, reg_dark, reg_bright = _capi.REG_REL, 5e-3, 1e-8        # apVast.m:552-569
         zones = (1 if run_A else 0) | (2 if run_B else 0)
+        tables = None
+        if self._evaluation_detectability:
+            # the detectability stage takes the model's tables before the stream is initialised; the design weighting below
+            # reuses them
+            from .perceptual import PerceptualTables
+            tables = PerceptualTables(N, sampling_rate, fullscale_db_spl)
+        self.detectability_model = tables               # what the device received; None without the keyword
         self._eng = _capi.Engine(self._K, L, M, ranks=self._ranks, mu=self._mu, compute_dtype="f32" if dtype == "f32" else "f64",
                                  reg_mode=reg_mode, reg_dark=reg_dark, reg_bright=reg_bright, device=device,
                                  block_size=N, hop_size=H, n_zones=zones, frontend="f32" if dtype == "mixed" else None,
@@ -259,14 +278,15 @@ class apvast:
                                  filter_taps=int(filter_length) if self.constrain_filter_length else 0,
                                  synthesis=self.synthesis, evaluation=self._evaluation,
                                  evaluation_spectra=self._evaluation_spectra, span=self._span_args(),
-                                 effort_limit=self._effort_table())
+                                 effort_limit=self._effort_table(),
+                                 evaluation_detectability=tables if self._evaluation_detectability else None)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
             # the masking model carried by the MATLAB twin (perceptualModel.m); per-block curves are formed on the
             # device from the target spectra, normalised as the dialect prescribes (apvast.py:322-324 /
             # perceptualModel.m:177-190)
             from .perceptual import PerceptualTables
-            self.model = PerceptualTables(N, sampling_rate, fullscale_db_spl)
+            self.model = tables if tables is not None else PerceptualTables(N, sampling_rate, fullscale_db_spl)
             self._eng.stream_set_perceptual(self.model, dialect)
         self._n_out = (int(run_A) + int(run_B)) * V * L + 2 * L
         tgt = np.zeros((N, L))
@@ -282,6 +302,7 @@ class apvast:
             tresp = [1e-3 * rs.randn(N, M) for _ in range(2)]
             self.set_state({"response": np.stack(resp), "target_response": np.stack(tresp)})
         self._hops = 0                      # attributes of apvast.py:368-403 exist once a hop has run
+        self._detect_hops = 0               # hops since construction, reset_evaluation() or a restored evaluation_detectability
         self._sb_cache = {}
 
     @staticmethod
@@ -390,6 +411,19 @@ class apvast:
             raise ValueError("evaluation_spectra is a subband keyword: broadband mode has no evaluation stage")
         if evaluation is None:
             raise ValueError("evaluation_spectra needs validation_rir_A and validation_rir_B")
+        return True
+
+    @staticmethod
+    def _check_evaluation_detectability(value, evaluation_spectra, mode):
+        """evaluation_detectability as a bool; True needs subband mode and the per-bin spectra."""
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError("evaluation_detectability must be a bool")
+        if not value:
+            return False
+        if mode == "broadband":
+            raise ValueError("evaluation_detectability is a subband keyword: broadband mode has no evaluation stage")
+        if not evaluation_spectra:
+            raise ValueError("evaluation_detectability needs evaluation_spectra=True")
         return True
 
     # ---- the per-bin span (mu_profile, rank_profile, contrast_floor_db; DESIGN.md 4.23) -------------------------------------
@@ -611,11 +645,48 @@ class apvast:
         return {"bright": np.ascontiguousarray(t[:, :E]), "dark": np.ascontiguousarray(t[:, E:2 * E]),
                 "error": np.ascontiguousarray(t[:, 2 * E:3 * E]), "target": np.ascontiguousarray(t[:, 3 * E])}
 
+    def _detect_dims(self):
+        Z, E, _, Mv = self._eval_dims()
+        if not self.__dict__.get("_evaluation_detectability"):
+            raise RuntimeError("this object keeps no detectabilities: pass evaluation_detectability=True")
+        return Z, E, Mv
+
+    def evaluation_detectability(self):
+        """Perceptual detectability D of the evaluated pressures (D = 1: just audible) over every hop since construction, set_state
+        or reset_evaluation(): "error" -- the reproduction error in the bright zone, masked by the program the listener wants --
+        and "leak" -- the other program's leakage, masked by this zone's own target -- as sums over the hops (Z, E, Mv),
+        "error_max" / "leak_max" the largest hop, "error_audible" / "leak_audible" the number of hops with D > 1 (int64), and
+        "hops", the hops counted; evaluation.detectability_metrics() turns them into means and audible shares.  None before the
+        first hop."""
+        Z, E, Mv = self._detect_dims()
+        if self._hops == 0:
+            return None
+        t = self._eng.get_state("eval_detect", (Z, 2, 3, E, Mv), np.float64)
+        out = {"hops": int(self._detect_hops)}
+        for i, name in enumerate(("error", "leak")):
+            out[name] = np.ascontiguousarray(t[:, i, 0])
+            out[name + "_max"] = np.ascontiguousarray(t[:, i, 1])
+            out[name + "_audible"] = t[:, i, 2].astype(np.int64)
+        return out
+
+    def evaluation_detectability_hops(self):
+        """The detectabilities per hop of the last process_input_buffers / process_signal call: "error" and "leak" (n, Z, E, Mv).
+        None before the first hop."""
+        Z, E, Mv = self._detect_dims()
+        if self._hops == 0:
+            return None
+        n = self._eng.state_bytes("eval_detect_hops") // (8 * Z * 2 * E * Mv)
+        if n == 0:
+            return None
+        r = self._eng.get_state("eval_detect_hops", (n, Z, 2, E, Mv), np.float64)
+        return {"error": np.ascontiguousarray(r[:, :, 0]), "leak": np.ascontiguousarray(r[:, :, 1])}
+
     def reset_evaluation(self):
         """Totals to zero and the output histories to silence: the next hop's totals are its own energies.  With
-        evaluation_spectra=True the per-bin energies and the pressure ring too."""
+        evaluation_spectra=True the per-bin energies and the pressure ring too, with evaluation_detectability=True its totals."""
         self._eval_dims()
         self._eng.reset_evaluation()
+        self._detect_hops = 0
 
     # ---- responses and mu, reassignable between hops (the reference reads them on every hop, apvast.py:161, 167-193) ----
     def _init_responses(self, rir_A, rir_B):
@@ -783,6 +854,7 @@ class apvast:
         if out.dtype != np.float64:
             out = out.astype(np.float64)
         res = self._split_groups(out)
+        self._detect_hops += 1
         self._refresh_attributes()
         return res
 
@@ -818,6 +890,7 @@ class apvast:
         if out.dtype != np.float64 and not given:
             out = out.astype(np.float64)
         res = self._split_groups(out)
+        self._detect_hops += input_A.size // self.hop_size
         self._refresh_attributes()
         return res
 
@@ -990,6 +1063,7 @@ class apvast:
     _FIR_STATE = ("fir_synthesis_taps", "fir_synthesis_history")    # present with synthesis="fir"
     _EVAL_STATE = ("evaluation_history", "evaluation_totals")       # present with validation_rir_A / validation_rir_B
     _EVALSPEC_STATE = ("evaluation_spectra", "evaluation_ring")     # present with evaluation_spectra=True
+    _EVALDETECT_STATE = ("evaluation_detectability",)               # present with evaluation_detectability=True
 
     def get_state(self):
         """Everything the next hop depends on (the reference's instance attributes of apvast.py:115-151), as float64 arrays
@@ -1034,6 +1108,12 @@ class apvast:
             Z, E, _, Mv = self._eval_dims()
             st["evaluation_spectra"] = self._eng.get_state("eval_spectra", (Z, 3 * E + 1, self._K, Mv), np.float64)
             st["evaluation_ring"] = self._eng.get_state("eval_ring", (Z, 2 * E + 1, Mv, self.block_size), np.float64)
+        if self.mode == "subband" and self._evaluation_detectability:
+            # the totals as the device keeps them -- per program sum, max and audible count of the error, then of the leak -- and
+            # in a last row the hops they cover, which only the host counts
+            Z, E, _, Mv = self._eval_dims()
+            st["evaluation_detectability"] = np.concatenate(
+                [self._eng.get_state("eval_detect", (Z, 6 * E, Mv), np.float64), np.full((Z, 1, Mv), float(self._detect_hops))], axis=1)
         if self._live_applied:
             P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
             Q = max(P - 1, 1)
@@ -1088,6 +1168,8 @@ class apvast:
             known = known + self._EVAL_STATE
         if self.mode == "subband" and self._evaluation_spectra:
             known = known + self._EVALSPEC_STATE
+        if self.mode == "subband" and self._evaluation_detectability:
+            known = known + self._EVALDETECT_STATE
         unknown = sorted(set(state) - set(known))
         if unknown:
             raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
@@ -1147,6 +1229,16 @@ class apvast:
                     if a.shape != shape:
                         raise ValueError(f"{key} must have shape {shape}, got {a.shape}")
                     e.set_state(name, np.ascontiguousarray(a, dtype=np.float64))
+        if "evaluation_detectability" in state:
+            Z, E, _, Mv = self._eval_dims()
+            a = np.asarray(state["evaluation_detectability"], dtype=np.float64)
+            if a.shape != (Z, 6 * E + 1, Mv):
+                raise ValueError(f"evaluation_detectability must have shape {(Z, 6 * E + 1, Mv)}, got {a.shape}")
+            hops = a[0, 6 * E, 0]
+            if not (hops >= 0 and hops == np.floor(hops) and np.all(a[:, 6 * E] == hops)):
+                raise ValueError("evaluation_detectability: the last row must hold one hop count, a non-negative integer")
+            e.set_state("eval_detect", np.ascontiguousarray(a[:, :6 * E]))
+            self._detect_hops = int(hops)
         if "statistics_window_fill" in state:
             e.set_state("stat_window_fill", np.array([int(state["statistics_window_fill"])], dtype=np.int32))
         if any(k in state for k in self._LIVE_STATE):

@@ -105,6 +105,10 @@ struct apv_handle {
     std::vector<double> eval_rv[2];  // validation responses of zone A, zone B: [Pv][L][Mv]
     std::vector<int32_t> eval_ranks; // evaluated ranks, ascending, each in rank_list
     int eval_spectra;                // apv_stream_set_evaluation_spectra: per-bin spectra of the evaluation stage (0: off)
+    // apv_stream_set_evaluation_detectability: the model tables of the next apv_stream_init's detectability stage (eval_detect_C = 0: off)
+    int eval_detect_C;
+    std::vector<double> eval_detect_G2;  // [n_bins][eval_detect_C]
+    double eval_detect_Cs, eval_detect_Ca, eval_detect_Leff;
     // apv_set_span: which parts exist is fixed by the first call; the tables and outputs are [2][n_bins] (row = zone program)
     struct Span {
         bool on = false, has_mu = false, has_cap = false, has_floor = false;
@@ -417,6 +421,31 @@ struct EvalSpectraArgs {
 };
 bool apv_eval_spectra_size_ok(int N, int H, int Z, int E, int Mv, std::string* why);
 hipError_t apv_launch_eval_spectra(const EvalSpectraArgs& a, hipStream_t s, std::string* why);
+
+// kernels_evaldetect.hip: perceptual detectability of the evaluated pressures (see the file header).  Three launches behind the
+// spectra above, on their bin-major scratch spec [N/2 + 1][Z (2 E + 1) Mv]: the squared weighting curves of the Z Mv target
+// spectra into curves [N/2 + 1][Z Mv], the weighted sums of every (program, rank, microphone) over the bins 1.. as `chunks`
+// partial sums into part [chunks][Z][2 E][Mv] (per program: error of the E ranks, leak of the E ranks), and their sum, in chunk
+// order, into the hop's slot [Z][2 E][Mv] and the totals [Z][6 E][Mv] (per program: sum, max, count of D > 1 of the error, then of
+// the leak).  The slot is `hop`, or where that is null slot ctl[2] - 1 of the record at ctl[0] (ctl[1] slots), ctl[2] the hops of the
+// call so far, which the first launch advances.  G2T [C][N/2 + 1]: the model's squared channel responses, channel-major; quiet
+// [N/2 + 1]: the curve of a silent masker (apv_launch_eval_detect_quiet), read where Z = 1.
+struct EvalDetectArgs {
+    const void* spec;
+    const double* G2T;
+    const double* quiet;
+    double* curves;
+    double* part;
+    double* hop;
+    unsigned long long* ctl;
+    double* totals;
+    int N, Z, E, Mv, C;
+    double Cs, Ca, Leff;
+};
+bool apv_eval_detect_size_ok(int N, int Z, int E, int Mv, int C, std::string* why);
+int apv_eval_detect_chunks(int N, int Z, int E, int Mv);      // partial sums per element: a function of the sizes alone
+hipError_t apv_launch_eval_detect_quiet(int N, int C, const double* G2T, double Cs, double Ca, double Leff, double* quiet, hipStream_t s);
+hipError_t apv_launch_eval_detect(const EvalDetectArgs& a, hipStream_t s, std::string* why);
 
 // whole-signal path, a chunk of hops per launch (kernels_stft.hip / kernels_stream.hip; see process_signal_chunked_t in stream.hip)
 hipError_t apv_launch_stft_analysis_chunk(int f64, int N, int n_jobs, const void* const* x, const int* n_ch, void* const* spec,

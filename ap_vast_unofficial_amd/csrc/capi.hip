@@ -3,6 +3,7 @@
 #include "apv_owned.h"
 #include <utility>
 
+#include <cmath>
 #include <cstdlib>
 
 #include <rccl/rccl.h>
@@ -248,6 +249,8 @@ int apv_create(const apv_config* cfg, apv_handle** out) {
     h->synthesis = APV_SYNTH_WOLA;
     h->eval_Pv = h->eval_Mv = 0;
     h->eval_spectra = 0;
+    h->eval_detect_C = 0;
+    h->eval_detect_Cs = h->eval_detect_Ca = h->eval_detect_Leff = 0.0;
     h->gl_ws = nullptr;
     h->gl_tol2 = 0.0;
     h->gl_lead_rank = 0;
@@ -1068,6 +1071,46 @@ int apv_eval_spectrum_step(apv_handle* h, const double* d_pressure, double* d_ri
     a.ring_off = ring_off; a.N = N; a.H = H; a.Z = Z; a.E = E; a.Mv = Mv;
     hipError_t e = apv_launch_eval_spectra(a, h->stream, &why);
     const hipError_t es = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
+int apv_eval_detect_step(apv_handle* h, const void* d_spec, int32_t N, int32_t Z, int32_t E, int32_t Mv, int32_t n_channels,
+                         const double* h_G2, double Cs, double Ca, double Leff, double* d_hop, double* d_totals) {
+    if (!h || !d_spec || !h_G2 || !d_hop || !d_totals) return fail(h, APV_ERR_ARG, "null pointer");
+    if (N < 1 || Z < 1 || E < 1 || Mv < 1 || n_channels < 1)
+        return fail(h, APV_ERR_ARG, "apv_eval_detect_step: N, Z, E, Mv and n_channels must be at least 1");
+    if (N & 1) return fail(h, APV_ERR_ARG, "apv_eval_detect_step: N must be even");
+    if (!std::isfinite(Cs) || !std::isfinite(Ca) || !std::isfinite(Leff) || !(Ca > 0.0))
+        return fail(h, APV_ERR_ARG, "apv_eval_detect_step: Cs, Ca and Leff must be finite, Ca positive");
+    std::string why;
+    if (!apv_eval_detect_size_ok(N, Z, E, Mv, n_channels, &why)) return fail(h, APV_ERR_ARG, why);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    // the table, the curves and the partial sums are this call's own: a test entry, not a per-hop path
+    const int K = N / 2 + 1, chunks = apv_eval_detect_chunks(N, Z, E, Mv);
+    std::vector<double> gt((size_t)n_channels * K);
+    for (int k = 0; k < K; ++k)
+        for (int i = 0; i < n_channels; ++i) gt[(size_t)i * K + k] = h_G2[(size_t)k * n_channels + i];
+    ApvOwned t;
+    double *G2T = nullptr, *quiet = nullptr, *curves = nullptr, *part = nullptr;
+    HIPCHK(h, t.device(&G2T, sizeof(double) * gt.size()));
+    HIPCHK(h, t.device(&quiet, sizeof(double) * K));
+    HIPCHK(h, t.device(&curves, sizeof(double) * (size_t)K * Z * Mv));
+    HIPCHK(h, t.device(&part, sizeof(double) * (size_t)chunks * Z * 2 * E * Mv));
+    HIPCHK(h, hipMemcpyAsync(G2T, gt.data(), sizeof(double) * gt.size(), hipMemcpyHostToDevice, h->stream));
+    hipError_t e = apv_launch_eval_detect_quiet(N, n_channels, G2T, Cs, Ca, Leff, quiet, h->stream);
+    if (e == hipSuccess) {
+        EvalDetectArgs a{};
+        a.spec = d_spec; a.G2T = G2T; a.quiet = quiet; a.curves = curves; a.part = part;
+        a.hop = d_hop; a.ctl = nullptr; a.totals = d_totals;
+        a.N = N; a.Z = Z; a.E = E; a.Mv = Mv; a.C = n_channels;
+        a.Cs = Cs; a.Ca = Ca; a.Leff = Leff;
+        e = apv_launch_eval_detect(a, h->stream, &why);
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);  // gt and the scratch go out of scope
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
                                      why.empty() ? hipGetErrorString(e) : why);

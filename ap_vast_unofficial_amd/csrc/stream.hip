@@ -181,6 +181,19 @@ struct apv_stream {
     double* es_ring;              // [ev_sets ev_Mv][N] float64 ring of the pressures, channel-major, at the stream's ring_off
     void* es_spec;                // [K][ev_sets ev_Mv] complex128: the hop's spectra, bin-major scratch
     double* es_tot;               // [ev_Z][3 ev_E + 1][K][ev_Mv]: |P|^2 summed over the hops
+    // perceptual detectability of the evaluated pressures (apv_stream_set_evaluation_detectability, kernels_evaldetect.hip), on
+    // es_spec; ed_on = 0: off, nothing below exists
+    int ed_on;
+    int ed_C;                     // channels of the model
+    double ed_Cs, ed_Ca, ed_Leff;
+    double* ed_G2T;               // [ed_C][K]: the squared channel responses, channel-major
+    double* ed_quiet;             // [K]: the curve of a silent masker (read with one zone program), formed once
+    double* ed_curves;            // [K][ev_Z ev_Mv]: the hop's squared weighting curves
+    double* ed_part;              // [chunks][ev_Z][2 ev_E][ev_Mv]: partial sums of the hop
+    double* ed_tot;               // [ev_Z][6 ev_E][ev_Mv]: per program sum, max and count of D > 1 of the error, then of the leak
+    double* ed_rec;               // [ed_cap] slots [ev_Z][2 ev_E][ev_Mv]: the values of each hop of the last call (grow-only, like ev_rec)
+    unsigned long long* ed_ctl;   // device words {ed_rec, ed_cap, hops of the call so far}: see kernels_evaldetect.hip
+    int ed_cap;                   // slots ed_rec holds (ev_nrec of them are valid)
     int32_t sched[2];             // state "signal_schedule": hops of the last whole-signal call {through chunk launches, hop by hop}
     StageTimer win_tm;            // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): the statistics launch
     std::vector<hipGraphExec_t> execs;
@@ -509,6 +522,16 @@ static int enqueue_eval(apv_handle* h, hipStream_t st, const void* obuf) {
         e = apv_launch_eval_spectra(sp, st, &why);
         if (e != hipSuccess) return launch_fail(h, e, why);
     }
+    if (s->ed_on) {
+        // three more behind them, on the scratch the transform just filled: nothing here has a period (the record's slot is a device word)
+        EvalDetectArgs d{};
+        d.spec = s->es_spec; d.G2T = s->ed_G2T; d.quiet = s->ed_quiet; d.curves = s->ed_curves; d.part = s->ed_part;
+        d.hop = nullptr; d.ctl = s->ed_ctl; d.totals = s->ed_tot;
+        d.N = s->N; d.Z = s->ev_Z; d.E = s->ev_E; d.Mv = s->ev_Mv; d.C = s->ed_C;
+        d.Cs = s->ed_Cs; d.Ca = s->ed_Ca; d.Leff = s->ed_Leff;
+        e = apv_launch_eval_detect(d, st, &why);
+        if (e != hipSuccess) return launch_fail(h, e, why);
+    }
     return APV_OK;
 }
 
@@ -530,6 +553,21 @@ static int eval_begin_call(apv_handle* h, int n_hops) {
         SCHK(h, hipStreamSynchronize(st));                   // words goes out of scope
     }
     SCHK(h, hipMemsetAsync(s->ev_ctl + 2 + (s->cur ^ 1), 0, sizeof(unsigned long long), st));
+    if (s->ed_on) {
+        if (n_hops > s->ed_cap) {
+            const size_t slot = sizeof(double) * (size_t)s->ev_Z * 2 * s->ev_E * s->ev_Mv;
+            SCHK(h, hipStreamSynchronize(st));
+            double* rec = nullptr;
+            SCHK(h, s->own.device(&rec, slot * n_hops));
+            s->own.release(s->ed_rec);
+            s->ed_rec = rec;
+            s->ed_cap = n_hops;
+            const unsigned long long words[2] = {(unsigned long long)reinterpret_cast<uintptr_t>(rec), (unsigned long long)n_hops};
+            SCHK(h, hipMemcpyAsync(s->ed_ctl, words, sizeof(words), hipMemcpyHostToDevice, st));
+            SCHK(h, hipStreamSynchronize(st));               // words goes out of scope
+        }
+        SCHK(h, hipMemsetAsync(s->ed_ctl + 2, 0, sizeof(unsigned long long), st));
+    }
     s->ev_nrec = 0;
     return APV_OK;
 }
@@ -1697,6 +1735,16 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         std::string why;
         if (!apv_eval_spectra_size_ok(N, H, nzp, (int)h->eval_ranks.size(), h->eval_Mv, &why)) return apv_fail(h, APV_ERR_ARG, why);
     }
+    if (h->eval_detect_C > 0) {
+        if (!h->eval_spectra)
+            return apv_fail(h, APV_ERR_ARG, "evaluation detectability (apv_stream_set_evaluation_detectability) needs the per-bin spectra of "
+                                            "apv_stream_set_evaluation_spectra");
+        if (h->eval_detect_G2.size() != (size_t)c.n_bins * h->eval_detect_C)
+            return apv_fail(h, APV_ERR_ARG, "evaluation detectability (apv_stream_set_evaluation_detectability): the table was sized for another n_bins");
+        const int nzp = ((c.n_zones & 1) ? 1 : 0) + ((c.n_zones & 2) ? 1 : 0);
+        std::string why;
+        if (!apv_eval_detect_size_ok(N, nzp, (int)h->eval_ranks.size(), h->eval_Mv, h->eval_detect_C, &why)) return apv_fail(h, APV_ERR_ARG, why);
+    }
     SCHK(h, hipSetDevice(h->device));
     apv_stream_free(h);
     apv_stream* s = new apv_stream();                       // value-initialised: every scalar, pointer and array member starts at zero
@@ -1902,6 +1950,23 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
             if ((rc = dalloc(h, &s->es_tot, (size_t)nz * (3 * E + 1) * K * Mv))) return rc;
             SCHK(h, apv_stft_prepare(N, 1));                 // the float64 plan, beside the stream's own where that is float32
         }
+        if (h->eval_detect_C > 0) {
+            const int Cn = h->eval_detect_C;
+            s->ed_on = 1; s->ed_C = Cn;
+            s->ed_Cs = h->eval_detect_Cs; s->ed_Ca = h->eval_detect_Ca; s->ed_Leff = h->eval_detect_Leff;
+            std::vector<double> gt((size_t)Cn * K);
+            for (int k = 0; k < K; ++k)
+                for (int i = 0; i < Cn; ++i) gt[(size_t)i * K + k] = h->eval_detect_G2[(size_t)k * Cn + i];
+            if ((rc = dalloc(h, &s->ed_G2T, gt.size()))) return rc;
+            SCHK(h, hipMemcpyAsync(s->ed_G2T, gt.data(), sizeof(double) * gt.size(), hipMemcpyHostToDevice, h->stream));
+            SCHK(h, hipStreamSynchronize(h->stream));        // gt goes out of scope
+            if ((rc = dalloc(h, &s->ed_quiet, (size_t)K))) return rc;
+            if ((rc = dalloc(h, &s->ed_curves, (size_t)K * nz * Mv))) return rc;
+            if ((rc = dalloc(h, &s->ed_part, (size_t)apv_eval_detect_chunks(N, nz, E, Mv) * nz * 2 * E * Mv))) return rc;
+            if ((rc = dalloc(h, &s->ed_tot, (size_t)nz * 6 * E * Mv))) return rc;
+            if ((rc = dalloc(h, &s->ed_ctl, 3))) return rc;
+            SCHK(h, apv_launch_eval_detect_quiet(N, Cn, s->ed_G2T, s->ed_Cs, s->ed_Ca, s->ed_Leff, s->ed_quiet, h->stream));
+        }
     }
     // target filter spectra: rfft of a unit impulse at tap modeling_delay of the A reference loudspeaker
     // (apvast.py:389-390, 418, 422: the same filter serves A_t and B_t)
@@ -2002,6 +2067,26 @@ int apv_stream_set_evaluation_spectra(apv_handle* h, int32_t on) {
     return APV_OK;
 }
 
+int apv_stream_set_evaluation_detectability(apv_handle* h, int32_t n_channels, const double* h_G2, double Cs, double Ca, double Leff) {
+    if (!h) return APV_ERR_ARG;
+    if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_evaluation_detectability: the stream is initialised (its buffers are allocated there)");
+    if (n_channels == 0) {
+        h->eval_detect_C = 0;
+        h->eval_detect_G2.clear();
+        return APV_OK;
+    }
+    if (n_channels < 0 || n_channels > 512 || !h_G2) return apv_fail(h, APV_ERR_ARG, "evaluation detectability: a table of 1..512 channels");
+    if (!std::isfinite(Cs) || !std::isfinite(Ca) || !std::isfinite(Leff) || !(Ca > 0.0))
+        return apv_fail(h, APV_ERR_ARG, "evaluation detectability: Cs, Ca and Leff must be finite, Ca positive");
+    const size_t n = (size_t)h->cfg.n_bins * n_channels;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(h_G2[i])) return apv_fail(h, APV_ERR_ARG, "evaluation detectability: the table must be finite");
+    h->eval_detect_G2.assign(h_G2, h_G2 + n);
+    h->eval_detect_C = n_channels;
+    h->eval_detect_Cs = Cs; h->eval_detect_Ca = Ca; h->eval_detect_Leff = Leff;
+    return APV_OK;
+}
+
 int apv_stream_reset_evaluation(apv_handle* h) {
     if (!h || !h->st || !h->st->ev_on) return apv_fail(h, APV_ERR_ARG, "apv_stream_reset_evaluation: no stream with an evaluation stage");
     apv_stream* s = h->st;
@@ -2013,6 +2098,7 @@ int apv_stream_reset_evaluation(apv_handle* h) {
         SCHK(h, hipMemsetAsync(s->es_tot, 0, sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->K * s->ev_Mv, h->stream));
         SCHK(h, hipMemsetAsync(s->es_ring, 0, sizeof(double) * (size_t)s->ev_sets * s->ev_Mv * s->N, h->stream));
     }
+    if (s->ed_on) SCHK(h, hipMemsetAsync(s->ed_tot, 0, sizeof(double) * (size_t)s->ev_Z * 6 * s->ev_E * s->ev_Mv, h->stream));
     SCHK(h, hipStreamSynchronize(h->stream));
     return APV_OK;
 }
@@ -2385,6 +2471,8 @@ int apv_get_effort(apv_handle* h, int32_t zone, double* h_effort, int32_t* h_ran
 //                                  apv_stream_set_evaluation has them (see include/apvast_hip.h)
 //   "eval_spectra" [Z][3 E + 1][K][Mv] f64, "eval_ring" [sets Mv][N] f64 (a ring: logical order): only a stream with
 //                                  apv_stream_set_evaluation_spectra has them
+//   "eval_detect" [Z][6 E][Mv] f64, "eval_detect_hops" [hops of the last call][Z][2 E][Mv] f64 (read-only): only a stream with
+//                                  apv_stream_set_evaluation_detectability has them
 //   "signal_schedule" int32 {hops of the last apv_process_signal* call that went through chunk launches, hops of it that went hop by
 //                                  hop}, read-only; {0, 0} before the first such call, untouched by the per-hop calls
 static int live_index(const char* name) {
@@ -2509,6 +2597,11 @@ static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* by
         if (n == "eval_ring") {
             *dptr = s->es_ring; *bytes = sizeof(double) * (size_t)s->ev_sets * s->ev_Mv * N; *ring_rows = s->ev_sets * s->ev_Mv; return APV_OK; }
     }
+    if (s->ed_on) {
+        const size_t slot = sizeof(double) * (size_t)s->ev_Z * 2 * s->ev_E * s->ev_Mv;
+        if (n == "eval_detect") { *dptr = s->ed_tot; *bytes = 3 * slot; return APV_OK; }
+        if (n == "eval_detect_hops") { *dptr = s->ed_rec; *bytes = slot * (size_t)s->ev_nrec; return APV_OK; }
+    }
     return apv_fail(h, APV_ERR_STATE, std::string("unknown state name: ") + name);
 }
 
@@ -2603,6 +2696,7 @@ int apv_set_state(apv_handle* h, const char* name, const void* h_src, size_t byt
     if (std::string(name) == "signal_schedule") return apv_fail(h, APV_ERR_STATE, "signal_schedule is read-only");
     if (h->st->ev_on && (std::string(name) == "eval_pressure" || std::string(name) == "eval_hops"))
         return apv_fail(h, APV_ERR_STATE, std::string(name) + " is read-only");
+    if (h->st->ed_on && std::string(name) == "eval_detect_hops") return apv_fail(h, APV_ERR_STATE, "eval_detect_hops is read-only");
     void* d; size_t need; int rr;
     int rc = state_lookup(h, name, &d, &need, &rr);
     if (rc != APV_OK) return rc;

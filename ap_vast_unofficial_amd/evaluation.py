@@ -4,6 +4,7 @@
   nmse, acoustic_contrast_db   Matlab/main.m:120-130
   metrics            the same two from the energies a subband stream's evaluation stage accumulates on the device
   spectral_metrics   contrast and NMSE per bin or band from the per-bin energies (apvast.evaluation_spectra())
+  detectability_metrics   mean detectability and audible share of hops (apvast.evaluation_detectability())
   third_octave_bands the bin ranges of base-2 third-octave bands, for spectral_metrics
   vast               Matlab/ControlMethods/vast.m:1-97 (signal-independent VAST from the RIRs)
 
@@ -52,6 +53,21 @@ def metrics(totals):
     target = np.asarray(totals["target"], dtype=np.float64)
     return {"nmse": np.mean(error / target[..., None, :], axis=-1),
             "contrast_db": 10.0 * np.log10(np.sum(bright, axis=-1) / np.sum(dark, axis=-1))}
+
+
+def detectability_metrics(totals):
+    """Mean detectability per hop and the audible share of hops from accumulated detectabilities: ``totals`` as
+    apvast.evaluation_detectability() returns them -- "error", "leak" (sums, (Z, E, Mv)), "error_audible", "leak_audible" (hops
+    with D > 1, (Z, E, Mv)) and "hops" -> {"error_mean", "leak_mean", "error_audible_share", "leak_audible_share"}, each (Z, E):
+    mean[z, v] = mean_m sum[z, v, m] / hops (D = 1: just audible) and share[z, v] = mean_m audible[z, v, m] / hops."""
+    hops = int(totals["hops"])
+    if hops < 1:
+        raise ValueError("detectability_metrics: totals of at least one hop")
+    out = {}
+    for name in ("error", "leak"):
+        out[name + "_mean"] = np.mean(np.asarray(totals[name], dtype=np.float64), axis=-1) / hops
+        out[name + "_audible_share"] = np.mean(np.asarray(totals[name + "_audible"], dtype=np.float64), axis=-1) / hops
+    return out
 
 
 def spectral_metrics(spectra, bands=None):

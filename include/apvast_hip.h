@@ -258,7 +258,7 @@ int  apv_fir_synthesis(apv_handle* h, const void* d_x, const void* d_taps_prev, 
 int  apv_stream_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
                                const int32_t* ranks);
 /* "eval_totals" and both "eval_history" buffers to zero: the next hop's totals equal its own energies; with the per-bin spectra
- * on, "eval_spectra" and "eval_ring" too.  APV_ERR_ARG without such a stream. */
+ * on, "eval_spectra" and "eval_ring" too, and with the detectability stage "eval_detect".  APV_ERR_ARG without such a stream. */
 int  apv_stream_reset_evaluation(apv_handle* h);
 /* Per-bin spectra of the evaluation stage (off unless called with on = 1; needs apv_stream_set_evaluation): behind the two launches
  * of the evaluation stage the device keeps the last N = block_size pressure samples of every pressure set and microphone in a
@@ -286,6 +286,35 @@ int  apv_stream_set_evaluation_spectra(apv_handle* h, int32_t on);
  * N > 4096, Z > 2, H > N or ring_off outside 0..N - 1.       replaces: nothing in the reference */
 int  apv_eval_spectrum_step(apv_handle* h, const double* d_pressure, double* d_ring, int32_t ring_off, int32_t N, int32_t H, int32_t Z,
                             int32_t E, int32_t Mv, double* d_totals);
+/* Perceptual detectability of the evaluated pressures (off unless called with n_channels > 0; needs the per-bin spectra): behind
+ * the launches of the spectra stage three more (csrc/kernels_evaldetect.hip, part of the captured hop graphs) evaluate the second
+ * half of the masking model, evaluateDetectability, on the hop's spectra P_t.  With f = 2 / N^2, G2 [K][C] the model's squared
+ * channel responses, and the squared weighting curve of a masker spectrum S
+ *   w2_S[k] = Cs Leff sum_c G2[k, c] / (f sum_j G2[j, c] |S[j]|^2 + Ca)                       (the masker includes bin 0)
+ * per hop, program z, evaluated rank e and validation microphone m, T the target, B the bright and Dk the dark spectrum:
+ *   error[z, e, m] = sum_{k >= 1} w2_{T[z, m]}[k] f |T[z, m, k] - B[z, e, m, k]|^2            the reproduction error, masked by the
+ *                                                                                             programme the listener wants
+ *   leak [z, e, m] = sum_{k >= 1} w2_{T[1 - z, m]}[k] f |Dk[z, e, m, k]|^2                    the other programme's leakage, masked
+ *                                                                                             by that zone's own target
+ * -- D = 1 is just audible; with one program (Z = 1) the leak's masker is silence, the threshold in quiet.  float64 whatever the
+ * stream's precision, no atomics.  States only such a stream has:
+ *   "eval_detect"       f64 [Z][6 E][Mv]: per program [sum | max | number of hops with D > 1] of the error of the E ranks, then the
+ *                       same three of the leak, since apv_stream_init or the last reset (total = total + hop per hop)
+ *   "eval_detect_hops"  f64 [hops of the last call][Z][2 E][Mv], read-only: per program the error of the E ranks, then the leak
+ * apv_stream_reset_evaluation zeroes "eval_detect".  h_G2 [n_bins][n_channels], Cs, Ca, Leff: the tables of the model
+ * (perceptual.PerceptualTables).  Called between apv_create and apv_stream_init; n_channels = 0 switches the stage off.
+ * APV_ERR_ARG (nothing changed) once the stream is initialised, for n_channels outside 0..512, a null table, a non-finite table
+ * entry or constant, or Ca <= 0.  apv_stream_init returns APV_ERR_ARG when the stage is on without
+ * apv_stream_set_evaluation_spectra.                     replaces: Matlab/ControlMethods/perceptualModel.m:192-206, on the device */
+int  apv_stream_set_evaluation_detectability(apv_handle* h, int32_t n_channels, const double* h_G2, double Cs, double Ca, double Leff);
+/* One step of that stage alone, on device pointers and the handle's stream: d_spec [N/2 + 1][Z (2 E + 1) Mv] complex128, the
+ * bin-major spectra of the pressure sets (per program: bright of the E ranks, dark of the E ranks, target); h_G2 [N/2 + 1][n_channels]
+ * on the host.  The hop's values go to d_hop [Z][2 E][Mv] and into d_totals [Z][6 E][Mv] as above.  The call uploads the tables,
+ * allocates and frees its scratch and synchronises.  APV_ERR_ARG for null pointers, sizes below 1, odd N, Z > 2, n_channels > 512,
+ * non-finite constants, Ca <= 0 or a block the curve kernel's LDS does not hold (N/2 + 1 + n_channels > 8192).
+ *                                                        replaces: nothing in the reference */
+int  apv_eval_detect_step(apv_handle* h, const void* d_spec, int32_t N, int32_t Z, int32_t E, int32_t Mv, int32_t n_channels,
+                          const double* h_G2, double Cs, double Ca, double Leff, double* d_hop, double* d_totals);
 /* The pressure kernel alone, on the handle's stream: d_y [G][Pv - 1 + H][L] samples (per group the Pv - 1 in front of the hop,
  * then the hop; float64 with a float64 front-end, else float32), d_rv [Pv][L][Mv] float64, d_p [G][H][Mv] float64:
  * p[g][n, m] = sum_l sum_j rv[j, l, m] y[g][Pv - 1 + n - j, l].  APV_ERR_ARG for a size below 1, null pointers, G > 65535 or

@@ -18,6 +18,11 @@ hop of process_input_buffers with the evaluation stage alone and with the spectr
 and contrast and NMSE per third-octave band from the accumulated spectra (recorded, not gated).  It replaces the section "Per-bin
 spectra" of the file and leaves the rest as it is.
 
+`--detectability` runs the leg of the detectability stage (apvast(..., evaluation_detectability=True), csrc/kernels_evaldetect.hip)
+beside the spectra leg of the same run: ms per hop with the spectra alone and with the detectabilities, same protocol, and the mean
+detectability and audible share of hops (evaluation.detectability_metrics; recorded, not gated).  It writes
+profiles/evaluation_detectability.md.
+
 Writes profiles/stream_evaluation.md (and one JSON line per leg on stdout).  A leg that fails or overruns its time limit ends the
 run.  `--bench-parent A,B,C --bench-this A,B,C` adds the ms_per_step of bench.py on the parent commit and on this one to the file.
 """
@@ -49,7 +54,7 @@ def validation(a0, b0):
     return tuple(r + 0.1 * np.sqrt(np.mean(r ** 2, axis=(1, 2), keepdims=True)) * rng.standard_normal(r.shape) for r in (a0, b0))
 
 
-def make(synth, V, evaluate, spectra=False):
+def make(synth, V, evaluate, spectra=False, detect=False):
     from ap_vast_unofficial_amd.apvast import apvast
     s = CFG3
     a0, b0 = rirs(s["P"], s["L"], s["M"], 99)
@@ -63,12 +68,14 @@ def make(synth, V, evaluate, spectra=False):
         kw.update(validation_rir_A=va, validation_rir_B=vb, evaluation_ranks=[V])
     if spectra:
         kw.update(evaluation_spectra=True)
+    if detect:
+        kw.update(evaluation_detectability=True)
     return apvast(s["N"], a0, b0, s["J"], 20, 0, 0, V, 1.0, 4 * s["N"], hop_size=s["H"], perceptual=False, dtype="f64", seed=0, **kw)
 
 
-def leg_hop(synth, V, evaluate, hops, spectra=False):
+def leg_hop(synth, V, evaluate, hops, spectra=False, detect=False):
     H = CFG3["H"]
-    obj = make(synth, V, evaluate, spectra)
+    obj = make(synth, V, evaluate, spectra, detect)
     warm = 8
     x = np.random.default_rng(3).standard_normal((2, (warm + hops) * H))
     ts = []
@@ -87,6 +94,10 @@ def leg_hop(synth, V, evaluate, hops, spectra=False):
         centres, bands = third_octave_bands(48000, CFG3["N"], f_min=100.0, f_max=16000.0)
         m = spectral_metrics(obj.evaluation_spectra(), bands)
         res.update(band_hz=centres.tolist(), band_contrast_db=m["contrast_db"][:, 0].tolist(), band_nmse=m["nmse"][:, 0].tolist())
+    if detect:
+        from ap_vast_unofficial_amd.evaluation import detectability_metrics
+        m = detectability_metrics(obj.evaluation_detectability())
+        res.update(detectability=True, **{k: v[:, 0].tolist() for k, v in m.items()})
     obj.close()
     print(json.dumps(res), flush=True)
 
@@ -170,6 +181,55 @@ def spectra_section(args):
 SPECTRA_HEAD = "## Per-bin spectra"
 
 
+def detectability_file(args):
+    """the --detectability leg: evaluation + spectra against evaluation + spectra + detectabilities, alternating, fresh processes;
+    the lines of profiles/evaluation_detectability.md"""
+    rows = []
+    for V in (1, 16):
+        for rep in range(2):
+            for dt in (0, 1):
+                r = child(["--leg", "hop", "--synthesis", "wola", "--V", str(V), "--evaluation", "1", "--with-spectra", "1",
+                           "--with-detectability", str(dt), "--hops", str(args.hops)], args.timeout)
+                if r is None:
+                    return None
+                rows.append(r)
+    on_of = lambda r: bool(r.get("detectability"))
+    lines = ["# Detectability stage of the subband stream: cost and first results", "",
+             "Written by `tools/bench_stream_evaluation.py --detectability` on an MI355X.  cfg3's shape (16 loudspeakers x 32 control",
+             f"microphones, N 2048, H 1024, 800-tap responses, float64, both zone programs), Pv = {PV}, Mv = {MV},",
+             "`evaluation_ranks=[V]`, `evaluation_spectra=True`, without and with `evaluation_detectability=True` (three more launches per",
+             f"hop); {args.hops} timed hops per leg after 8 warm-up hops, every leg a fresh process, without / with alternating.  A hop of",
+             "audio at 48 kHz lasts 21.33 ms.", "",
+             "## ms per hop of `process_input_buffers` (median; p10 .. p90)", "",
+             "| V | detectability | run 1 | run 2 |", "|---|---|---|---|"]
+    for V in (1, 16):
+        for dt in (False, True):
+            q = [r for r in rows if r["V"] == V and on_of(r) == dt]
+            cells = " | ".join(f"{r['hop_ms_median']:.3f} ({r['hop_ms_p10']:.3f} .. {r['hop_ms_p90']:.3f})" for r in q)
+            lines.append(f"| {V} | {'on' if dt else 'off'} | {cells} |")
+    for V in (1, 16):
+        off = np.median([r["hop_ms_median"] for r in rows if r["V"] == V and not on_of(r)])
+        on = np.median([r["hop_ms_median"] for r in rows if r["V"] == V and on_of(r)])
+        lines.append("")
+        lines.append(f"V = {V}: {on - off:+.3f} ms per hop for the detectabilities (median of the runs with, less median of the runs without).")
+    lines += ["", "## Mean detectability and audible share of hops (recorded, not gated)", "",
+              "`evaluation.detectability_metrics` on the totals over all hops of the leg (warm-up included), white-noise inputs at full",
+              "scale; D = 1 is just audible.  Per zone program [A, B].", "",
+              "| V | error_mean | error_audible_share | leak_mean | leak_audible_share |", "|---|---|---|---|---|"]
+    for V in (1, 16):
+        q = [r for r in rows if r["V"] == V and on_of(r)][0]
+        f = lambda k: ", ".join("%.4g" % v for v in q[k])
+        lines.append(f"| {V} | {f('error_mean')} | {f('error_audible_share')} | {f('leak_mean')} | {f('leak_audible_share')} |")
+    if args.bench_parent or args.bench_this:
+        f = lambda s: [float(v) for v in s.split(",") if v]
+        p, t = f(args.bench_parent), f(args.bench_this)
+        lines += ["", "## bench.py --gpus 1 --steps 200 --warmup 20, parent commit and this one, alternating", "",
+                  f"* parent: ms_per_step {', '.join('%.4f' % v for v in p)} (range {min(p):.4f} .. {max(p):.4f})",
+                  f"* this commit: ms_per_step {', '.join('%.4f' % v for v in t)} (range {min(t):.4f} .. {max(t):.4f})",
+                  "", "The default stream launches nothing new: the stage is behind `ed_on`, which only the keyword sets."]
+    return lines
+
+
 def replace_section(text, head, lines):
     """`text` with the section that starts at the line `head` (up to the next '## ' line or the end) replaced by `lines`"""
     old = text.split("\n")
@@ -195,6 +255,9 @@ def main():
     ap.add_argument("--evaluation", type=int, default=0)
     ap.add_argument("--hops", type=int, default=100)
     ap.add_argument("--with-spectra", type=int, default=0, help="a hop leg with evaluation_spectra=True")
+    ap.add_argument("--with-detectability", type=int, default=0, help="a hop leg with evaluation_detectability=True")
+    ap.add_argument("--detectability", action="store_true",
+                    help="run the detectability leg and write profiles/evaluation_detectability.md")
     ap.add_argument("--spectra", action="store_true", help="run the per-bin spectra leg and replace its section of the file")
     ap.add_argument("--timeout", type=int, default=120, help="seconds per leg")
     ap.add_argument("--bench-parent", default="", help="ms_per_step of bench.py on the parent commit, comma separated")
@@ -202,10 +265,19 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_evaluation.md"))
     args = ap.parse_args()
     if args.leg == "hop":
-        leg_hop(args.synthesis, args.V, args.evaluation, args.hops, bool(args.with_spectra))
+        leg_hop(args.synthesis, args.V, args.evaluation, args.hops, bool(args.with_spectra), bool(args.with_detectability))
         return 0
     if args.leg == "kernel":
         leg_kernel(20)
+        return 0
+    if args.detectability:
+        lines = detectability_file(args)
+        if lines is None:
+            return 1
+        out = os.path.join(os.path.dirname(args.out), "evaluation_detectability.md")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
         return 0
     if args.spectra:
         lines = spectra_section(args)
