@@ -115,12 +115,10 @@ __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* 
         const XT* const drow0 = WITH_D ? dvec + mc + msub : nullptr;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            // UNCONDITIONAL loads (from a clamped row when the chunk is ragged), then a select: written as `ok ? X[...] : zero`
-            // every load sat in a branch of its own (the address might be out of bounds), the compiler split it into two dword
-            // loads and put an `s_waitcnt vmcnt(0)` behind each -- 48 memory round trips one after the other per bin, a quarter
-            // of a wave's life (profiles/r03/stage_stamps_32768.md: 24 k + 12 k cycles "waiting for the slabs")
-            const int m = mc + 4 * q + msub;
-            const bool ok = FULL || m < M;
+            // UNCONDITIONAL loads (from a clamped row when the chunk is ragged); the rows past M are set to zero below.  Written as
+            // `ok ? X[...] : zero` every load sat in a branch of its own (the address might be out of bounds), the compiler split it
+            // into two dword loads and put an `s_waitcnt vmcnt(0)` behind each -- 48 memory round trips one after the other per
+            // bin, a quarter of a wave's life (profiles/r03/stage_stamps_32768.md: 24 k + 12 k cycles "waiting for the slabs")
             XT xl, dl = zero;
             if constexpr (FULL) {
                 // one base address per chunk, the eight rows at constant offsets (512 q bytes: immediate offsets of the loads;
@@ -128,14 +126,29 @@ __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* 
                 xl = xrow0[(size_t)(4 * q) * N * GS];
                 if constexpr (WITH_D) dl = drow0[4 * q];
             } else {
-                const int mcl = ok ? m : M - 1;
+                const int m = mc + 4 * q + msub;
+                const int mcl = m < M ? m : M - 1;
                 xl = X[((size_t)mcl * N + (lane & 15)) * GS];
                 if constexpr (WITH_D) dl = dvec[mcl];
             }
-            xv[q].x = ok ? xl.x : zero.x;
-            xv[q].y = ok ? xl.y : zero.y;
-            dv[q].x = ok ? dl.x : zero.x;
-            dv[q].y = ok ? dl.y : zero.y;
+            xv[q] = xl;
+            dv[q] = dl;
+        }
+        if constexpr (!FULL) {
+            // A select on the loaded value alone does not keep the load unconditional: the compiler sinks it under the row's predicate
+            // again (an exec-masked block per load, split into dwords, `s_waitcnt vmcnt(0)` behind each).  An empty asm statement
+            // that takes the loaded value is a use the predicate does not cover, so the load stays where it is; all of a chunk's
+            // loads are issued above, before the first value is taken.
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                asm volatile("" : "+v"(xv[q].x), "+v"(xv[q].y));
+                if constexpr (WITH_D) asm volatile("" : "+v"(dv[q].x), "+v"(dv[q].y));
+                const bool ok = mc + 4 * q + msub < M;
+                xv[q].x = ok ? xv[q].x : zero.x;
+                xv[q].y = ok ? xv[q].y : zero.y;
+                dv[q].x = ok ? dv[q].x : zero.x;
+                dv[q].y = ok ? dv[q].y : zero.y;
+            }
         }
         if constexpr (!__is_same(ST, NoStamp)) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -12,8 +12,8 @@
 //            orthonormalises exactly, re-forms C on the MFMA and runs register-resident double sweeps (XOR pairing schedule)
 //            float32: the one-sided Jacobi is the solve
 //   stage 4  sort                                                                            apvast.py:32-35
-//   stage 5  X = W^H Q                             one complex MFMA product                  apvast.py:31
-//   stage 6  w_V = sum_{i<V} (x_i^H r)/(lam_i+mu) x_i                                        apvast.py:406-414
+//   stage 5  g = W r                               (X = W^H Q, apvast.py:31, only for a caller that asks for U)
+//   stage 6  w_V = W^H sum_{i<V} (q_i^H g)/(lam_i+mu) q_i   = sum_{i<V} (x_i^H r)/(lam_i+mu) x_i      apvast.py:406-414
 //
 // Against a textbook arrangement this removes 48 of the 64 sequential substitution steps (the two forward
 // substitutions and the backward one become three MFMA products) and needs two LDS matrices (10 KiB per wave).
@@ -444,7 +444,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
     void* const plam = const_cast<char*>(at_hop(z1 ? p.lam1 : p.lam, p.hop_lam));
     int32_t* const pstatus = reinterpret_cast<int32_t*>(const_cast<char*>(at_hop(z1 ? p.status1 : p.status, p.hop_status)));
     using C = Cx<T>;
-    __shared__ C sA[N * LD];       // R_B -> W R_B -> C -> Q (eigenvectors of C) -> X
+    __shared__ C sA[N * LD];       // R_B -> W R_B -> C -> Q (eigenvectors of C) (-> X for U)
     __shared__ C sB[N * LD];       // R_D -> W = L^-1
     __shared__ C scol[2][N];       // (stage 1 keeps its columns in sB; the later stages' small arrays live here)
     __shared__ C swr[2][N];        // Cholesky: current row of W
@@ -895,16 +895,29 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
             if (q4 == 0) sOrder[rank] = i16;
         }
 
-        // ---------------- stage 5: X = W^H Q ----------------
-        cmm16([&](int r, int kx) { const C w = sB[kx * LD + r]; return mk<T>(w.x, -w.y); },
-              [&](int kx, int c) { return sA[kx * LD + c]; }, lane, acc);
-        wsync();
+        // ---------------- stage 5: g = W r ----------------
+        // The filter needs X = W^H Q only through x_i^H r = q_i^H (W r) and sum a_i x_i = W^H (sum a_i q_i): two matrix-vector
+        // products in place of the 16 x 16 x 16 one (which is formed at the very end, and only for a caller that asks for U).
+        // all 64 lanes: lane (i, q) sums four of the sixteen terms of row i of W, the partial sums meet over q; g takes r's place
+        {
+            const int i16 = lane & 15, q4 = lane >> 4;
+            T gx = 0, gy = 0;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) sA[mfma_row<T>(lane, t) * LD + col] = acc[t];
+            for (int ll = 0; ll < 4; ++ll) {
+                const int l = 4 * q4 + ll;
+                const C w = sB[i16 * LD + l], rr = sr[l];
+                gx = fma_t(-w.y, rr.y, fma_t(w.x, rr.x, gx));
+                gy = fma_t(w.y, rr.x, fma_t(w.x, rr.y, gy));
+            }
+            gx += __shfl_xor(gx, 16, 64); gy += __shfl_xor(gy, 16, 64);
+            gx += __shfl_xor(gx, 32, 64); gy += __shfl_xor(gy, 32, 64);
+            wsync();                                                        // every lane has read r
+            if (q4 == 0) sr[i16] = mk<T>(gx, gy);
+        }
         wsync();
 
-        // ---------------- stage 6: coefficients (x_i^H r) / (lam_i + mu) ----------------
-        // all 64 lanes: lane (i, q) sums four of the sixteen terms of x_i^H r, the partial sums meet over q
+        // ---------------- stage 6: coefficients (x_i^H r) / (lam_i + mu) = (q_i^H g) / (lam_i + mu) ----------------
+        // all 64 lanes: lane (i, q) sums four of the sixteen terms of q_i^H g, the partial sums meet over q
         {
             const int i16 = lane & 15, q4 = lane >> 4;
             T sx = 0, sy = 0;
@@ -926,13 +939,19 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
     }
 
     // ---------------- outputs ----------------
-    // all 64 lanes: lane (i = lane & 15, q = lane >> 4) sums the terms of the sorted columns q, q + 4, ... of element i, carried on
-    // from rank to rank; per rank the four partial sums meet over q (the partials themselves stay).  Which lane takes a column
-    // does not depend on the rank list, so a rank's filter has the same bits whatever other ranks the launch asks for.
+    // all 64 lanes: lane (i = lane & 15, q = lane >> 4) sums the terms of the sorted columns q, q + 4, ... of element i of
+    // y = sum a_c q_c, carried on from rank to rank; per rank the four partial sums meet over q (the partials themselves stay), y
+    // goes through sixteen LDS elements (g's place: it is spent) and w = W^H y is one more matrix-vector product in stage 5's
+    // form, on four elements of W the lane loads once.  Which lane takes a column does not depend on the rank list, so a rank's
+    // filter has the same bits whatever other ranks the launch asks for.
     {
-        const int i16 = lane & 15;
+        const int i16 = lane & 15, q4 = lane >> 4;
         T ax = 0, ay = 0;
-        int done = lane >> 4;
+        int done = q4;
+        // W[4 q + ll][i]; a bin whose Cholesky failed has no W (sB holds what the elimination left) and gets zeros
+        C wl[4];
+#pragma unroll
+        for (int ll = 0; ll < 4; ++ll) wl[ll] = (status != 1) ? sB[(4 * q4 + ll) * LD + i16] : mk<T>(0, 0);
         // the span of the bin (gevd_span.h): no slot goes past s_k.  Without a span s_k = N and the loop is the one it was
         const int s_k = span_limit<true, T>(p.span, z1, k, N, p.ranks[p.nV - 1], status != 1, !HOPS || hop == p.span.last_hop, sLam,
                                       scoef, sOrder, lane);
@@ -946,7 +965,19 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                     ay = fma_t(cf.y, v.x, fma_t(cf.x, v.y, ay));
                 }
             }
-            T wx = ax + __shfl_xor(ax, 16, 64), wy = ay + __shfl_xor(ay, 16, 64);
+            T yx = ax + __shfl_xor(ax, 16, 64), yy = ay + __shfl_xor(ay, 16, 64);
+            yx += __shfl_xor(yx, 32, 64); yy += __shfl_xor(yy, 32, 64);
+            wsync();                                                        // the rank before has read its y
+            if (q4 == 0) sr[i16] = mk<T>(yx, yy);
+            wsync();
+            T wx = 0, wy = 0;
+#pragma unroll
+            for (int ll = 0; ll < 4; ++ll) {
+                const C y = sr[4 * q4 + ll];
+                wx = fma_t(wl[ll].y, y.y, fma_t(wl[ll].x, y.x, wx));       // conj(W[l][i]) y_l
+                wy = fma_t(-wl[ll].y, y.x, fma_t(wl[ll].x, y.y, wy));
+            }
+            wx += __shfl_xor(wx, 16, 64); wy += __shfl_xor(wy, 16, 64);
             wx += __shfl_xor(wx, 32, 64); wy += __shfl_xor(wy, 32, 64);
             if (lane < N) {
                 const size_t o = ((size_t)k * p.nV + t) * N + lane;
@@ -963,6 +994,17 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
         }
     }
     if (p.U != nullptr) {
+        // X = W^H Q, one complex MFMA product, for the caller that asks for the eigenvectors only (the filter above is formed the
+        // same way with and without them)
+        if (status != 1) {
+            C xacc[4];
+            cmm16([&](int r, int kx) { const C w = sB[kx * LD + r]; return mk<T>(w.x, -w.y); },
+                  [&](int kx, int c) { return sA[kx * LD + c]; }, lane, xacc);
+            wsync();
+#pragma unroll
+            for (int t = 0; t < 4; ++t) sA[mfma_row<T>(lane, t) * LD + (lane & 15)] = xacc[t];
+            wsync();
+        }
         C* U = reinterpret_cast<C*>(p.U) + (size_t)k * N * N;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {

@@ -11,6 +11,11 @@ table row in the form of DESIGN 4.1:
 with the register count, spill stores and reloads, scratch and LDS bytes from the function's own footer.  Instructions are
 classed by the prefix of their mnemonic only.  (The regions of the float32 pre-solve: presolve_isa_count.py.)
 
+Below the table: the slab loops of stage 0 (every loop of the function that holds both global loads and MFMAs), one line each with
+its global loads, its full waits `s_waitcnt vmcnt(0)` and the loads issued before the first wait of any kind.  A loop that selects
+or masks (v_cndmask, s_and_saveexec) is a ragged-M loop, (M & 31) != 0; it should read like the full loops: 16 loads (X_B and d) or
+8 (X_D) ahead of the first wait and one full wait.  With every load under its own predicate it reads 24 loads, 24 full waits.
+
     python tools/probes/gevd16m_isa_count.py [--asm FILE.s] [--kernel MANGLED_SUBSTRING] [--label NAME] [--top N]
 """
 import argparse
@@ -48,6 +53,34 @@ def mnemonic(line):
     if not s or s.startswith((";", ".", "/")) or re.match(r"[\w.$]+:", s):
         return None
     return s.split()[0]
+
+
+def slab_loops(body):
+    """(header label, ragged, loads, full waits, loads before the first wait) of every loop with global loads and MFMAs.  The
+    compiler marks a loop's blocks in the label comments: `=>This Inner Loop Header` and `in Loop: Header=BBn_m`."""
+    blocks, cur = [], None                       # (label, header it belongs to or None, lines)
+    for l in body:
+        m = re.match(r"\.L(BB\d+_\d+):(.*)", l)
+        if m:
+            h = re.search(r"Header=(BB\d+_\d+)", m.group(2))
+            cur = (m.group(1), m.group(1) if "Loop Header" in m.group(2) else h.group(1) if h else None, [])
+            blocks.append(cur)
+        elif cur is not None:
+            cur[2].append(l)
+    out = []
+    for head in [b[0] for b in blocks if b[1] == b[0]]:
+        members = [b for b in blocks if b[1] == head]
+        members.sort(key=lambda b: b[0] != head)                  # execution starts at the header block
+        ms = [m for b in members for m in ((mnemonic(l), l) for l in b[2]) if m[0]]
+        loads = [i for i, (m, _) in enumerate(ms) if m.startswith("global_load")]
+        if not loads or not any(m.startswith("v_mfma") for m, _ in ms):
+            continue
+        waits = [i for i, (m, _) in enumerate(ms) if m == "s_waitcnt" or m.startswith("s_waitcnt_")]
+        full = sum(1 for m, l in ms if m == "s_waitcnt" and re.search(r"vmcnt\(0\)", l))
+        first = min([i for i in waits if i > loads[0]], default=len(ms))
+        ragged = any(m.startswith(("v_cndmask", "s_and_saveexec")) for m, _ in ms)
+        out.append((head, ragged, len(loads), full, sum(1 for i in loads if i < first)))
+    return out
 
 
 def classify(ms):
@@ -94,6 +127,10 @@ def main():
     print("|---|---|---|---|---|---|---|---|---|---|---|---|")
     print(f"| {args.label} | {c['valu']} | {c['salu']} | {c['branch']} | {c['lds']} | {c['wait']} | {c['mfma']} | {c['other']} | "
           f"{meta.get('NumVgprs')} | {spills} / {reloads} | {meta.get('ScratchSize')} B | {meta.get('LDSByteSize')} |")
+    print()
+    for head, ragged, loads, full, ahead in slab_loops(body):
+        print(f"slab loop {head} ({'ragged M' if ragged else 'full chunks'}): {loads} global loads, {full} full vmcnt(0) waits, "
+              f"{ahead} loads before the first wait")
     if args.top:
         top = collections.Counter(re.sub(r"_e(32|64)$", "", m) for m in ms if m.startswith("v_") and not m.startswith("v_mfma"))
         print("\nVALU by mnemonic: " + ", ".join(f"{k} {v}" for k, v in top.most_common(args.top)))
