@@ -71,7 +71,7 @@ using f4 = __attribute__((ext_vector_type(4))) float;
 
 // R = X^H X for one [M][16] slab of c64 (XT = float2) or c128 (XT = double2) elements, result written to dst (LDS, row
 // stride LD); optional r = X^H d -> sr.  Lane l loads slab element 64 s + l: fully coalesced, and that one register is
-// both the A (X^H) and the B (X) operand of the 16x16x4 MFMA.
+// both the A (X^H) and the B (X) operand of the 16x16x4 MFMA (float64: the B operands are xr + xi and xi - xr of it).
 template <typename T> struct Mfma16;
 // a b + c in one rounding, float or double (written a += p q + r s the compiler emits a product, an FMA and an addition)
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -96,10 +96,13 @@ struct NoStamp { __device__ __forceinline__ void operator()(int) const {} };
 // that ended in `s_waitcnt vmcnt(0)`, i.e. waited for the x loads before it as well)
 // GS: element stride of the slab (1: bin-major [K][M][L]; 4: the grouped layout [K/4][M L][4] of the float64 streaming front-end,
 // where X points at the bin's first element inside its group and consecutive slab elements are four apart)
+// float64 takes two real products per k-step (the tile G below), float32 three: there xr + xi would round in float32, and the
+// cheaper f32 MFMA leaves too little to gain
 template <typename T, typename XT, bool WITH_D, typename ST = NoStamp, int GS = 1>
 __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* __restrict__ dvec, int M,
                                             Cx<T>* dst, Cx<T>* sr, int lane, ST stamp = ST(), int stamp_base = 0) {
     using MM = Mfma16<T>;
+    constexpr bool TWO = sizeof(T) == 8;
     typename MM::V re = {0, 0, 0, 0}, im = {0, 0, 0, 0};
     T rx = 0, ry = 0;
     const int msub = lane >> 4;
@@ -150,6 +153,9 @@ __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* 
                 dv[q].y = ok ? dv[q].y : zero.y;
             }
         }
+        // every load of the chunk is issued before its first value is taken (left alone, the scheduler starts on xr + xi of the
+        // early rows with the chunk's last loads still to issue)
+        if constexpr (TWO && FULL) __builtin_amdgcn_sched_barrier(0);
         if constexpr (!__is_same(ST, NoStamp)) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             stamp(stamp_base);                                   // the chunk's loads have landed
@@ -157,9 +163,15 @@ __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* 
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const T xr = (T)xv[q].x, xi = (T)xv[q].y;
-            re = MM::mac(xr, xr, re);
-            re = MM::mac(xi, xi, re);
-            im = MM::mac(xr, xi, im);                            // P = sum xr (x) xi; Im R = P - P^T, formed below
+            if constexpr (TWO) {
+                // G = sum xr (x) (xr + xi) + xi (x) (xi - xr) = Re R + (P - P^T): R comes out of G and G^T below
+                re = MM::mac(xr, xr + xi, re);
+                re = MM::mac(xi, xi - xr, re);
+            } else {
+                re = MM::mac(xr, xr, re);
+                re = MM::mac(xi, xi, re);
+                im = MM::mac(xr, xi, im);                        // P = sum xr (x) xi; Im R = P - P^T, formed below
+            }
             if constexpr (WITH_D) {
                 rx = fma_t(xi, (T)dv[q].y, fma_t(xr, (T)dv[q].x, rx));        // conj(x) * d, as chained FMAs
                 ry = fma_t(-xi, (T)dv[q].x, fma_t(xr, (T)dv[q].y, ry));
@@ -171,19 +183,35 @@ __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* 
     } else {
         for (int mc = 0; mc < M; mc += 32) chunk(mc, std::false_type{});
     }
-    // Im R = P - P^T: three MFMAs per k-step instead of four (the f64 matrix pipe is busy half of this kernel's time at the rate
-    // the instruction sustains, profiles/r02/mfma_issue_rate.md); the transpose goes through the destination tile
     const int col = lane & 15;
+    if constexpr (TWO) {
+        // R from the real tile: Re R is symmetric and Im R antisymmetric, so R_ij = ((G_ij + G_ji) / 2, (G_ij - G_ji) / 2).  Two
+        // MFMAs per k-step instead of three (an f64 MFMA costs the issue port as much as 14 vector instructions); the transpose goes
+        // through the destination tile.  R = R^H bit for bit and Im R_ii = 0 exactly.
 #pragma unroll
-    for (int t = 0; t < 4; ++t) dst[MM::row(lane, t) * LD + col] = mk<T>(re[t], im[t]);
-    stamp(stamp_base + 1);                                   // MFMAs retired (the stores above read the accumulators)
-    wsync();
-    T pt[4];
+        for (int t = 0; t < 4; ++t) dst[MM::row(lane, t) * LD + col].x = re[t];
+        stamp(stamp_base + 1);                               // MFMAs retired (the stores above read the accumulator)
+        wsync();
+        T gt[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) pt[t] = dst[col * LD + MM::row(lane, t)].y;
-    wsync();
+        for (int t = 0; t < 4; ++t) gt[t] = dst[col * LD + MM::row(lane, t)].x;
+        wsync();
 #pragma unroll
-    for (int t = 0; t < 4; ++t) dst[MM::row(lane, t) * LD + col].y = im[t] - pt[t];
+        for (int t = 0; t < 4; ++t)
+            dst[MM::row(lane, t) * LD + col] = mk<T>((T)0.5 * (re[t] + gt[t]), (T)0.5 * (re[t] - gt[t]));
+    } else {
+        // Im R = P - P^T: three MFMAs per k-step instead of four; the transpose goes through the destination tile
+#pragma unroll
+        for (int t = 0; t < 4; ++t) dst[MM::row(lane, t) * LD + col] = mk<T>(re[t], im[t]);
+        stamp(stamp_base + 1);                               // MFMAs retired (the stores above read the accumulators)
+        wsync();
+        T pt[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) pt[t] = dst[col * LD + MM::row(lane, t)].y;
+        wsync();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) dst[MM::row(lane, t) * LD + col].y = im[t] - pt[t];
+    }
     if constexpr (WITH_D) {
         rx += __shfl_xor(rx, 16, 64); ry += __shfl_xor(ry, 16, 64);
         rx += __shfl_xor(rx, 32, 64); ry += __shfl_xor(ry, 32, 64);

@@ -27,7 +27,7 @@ ms = eng.timer_stop() / 50
 st16 = dst.download((K, 16), np.uint64).astype(np.int64)
 st = st16[:, :8]
 eng.debug_set_stamps(None)
-names = ["correlate (2 slabs: loads, 48 MFMA)", "f64 Cholesky + inverse", "whitening (24 MFMA)", "pre-solve: Householder tridiagonal",
+names = ["correlate (2 slabs: loads, 32 MFMA)", "f64 Cholesky + inverse", "whitening (24 MFMA)", "pre-solve: Householder tridiagonal",
          "pre-solve: multisection, inverse iteration, Q X", "refinement (48+ MFMA)", "sort, back-transform, filter, stores"]
 dur = np.diff(st, axis=1)
 life = st[:, 7] - st[:, 0]
@@ -40,9 +40,9 @@ for i, n in enumerate(names):
     print(f"| {n} | {q[1]:.0f} | {q[0]:.0f} - {q[2]:.0f} | {q[1] / ghz / 1e3:.2f} | {100 * dur[:, i].sum() / life.sum():.1f} % |")
 q = np.percentile(life, [25, 50, 75])
 print(f"| whole life | {q[1]:.0f} | {q[0]:.0f} - {q[2]:.0f} | {q[1] / ghz / 1e3:.2f} | 100 % |")
-fine = [("start -> loads of X_B, d landed", st16[:, 8] - st16[:, 0]), ("24 MFMA of X_B + r", st16[:, 9] - st16[:, 8]),
-        ("Im R = P - P^T through LDS", st16[:, 10] - st16[:, 9]), ("loads of X_D landed", st16[:, 11] - st16[:, 10]),
-        ("24 MFMA of X_D", st16[:, 12] - st16[:, 11]), ("Im R through LDS, sync", st16[:, 1] - st16[:, 12])]
+fine = [("start -> loads of X_B, d landed", st16[:, 8] - st16[:, 0]), ("16 MFMA of X_B + r", st16[:, 9] - st16[:, 8]),
+        ("R from G, G^T through LDS", st16[:, 10] - st16[:, 9]), ("loads of X_D landed", st16[:, 11] - st16[:, 10]),
+        ("16 MFMA of X_D", st16[:, 12] - st16[:, 11]), ("R from G, G^T through LDS, sync", st16[:, 1] - st16[:, 12])]
 pre = [("Householder reduction (3 -> 4)", st16[:, 4] - st16[:, 3]), ("Sturm multisection (4 -> 13)", st16[:, 13] - st16[:, 4]),
        ("inverse iteration (13 -> 14)", st16[:, 14] - st16[:, 13]), ("gate, Q X (14 -> 5)", st16[:, 5] - st16[:, 14])]
 print("\ninside the float32 pre-solve (tridiag_presolve16):\n\n| step | median cycles | quartiles | share of the wave's life |\n|---|---|---|---|")
