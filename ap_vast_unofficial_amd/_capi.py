@@ -30,7 +30,7 @@ EXPORTS = (
     "apv_dev_alloc", "apv_dev_free", "apv_memcpy_h2d", "apv_memcpy_d2h", "apv_sync",
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
-    "apv_stft_analysis_dev", "apv_istft_ola_dev",
+    "apv_stft_analysis_dev", "apv_istft_ola_dev", "apv_analysis_dev", "apv_analysis_jobs_dev", "apv_synthesis_dev",
     "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
@@ -127,6 +127,10 @@ def load():
     lib.apv_norm2.argtypes = [vp, i32, i32, vp, vp, i32]
     lib.apv_stft_analysis_dev.argtypes = [vp, i32, vp, vp]
     lib.apv_istft_ola_dev.argtypes = [vp, i32, vp, vp, vp]
+    i64 = C.c_int64
+    lib.apv_analysis_dev.argtypes = [vp, i32, i32, vp, i64, i32, i32, i32, vp, i64, i64]
+    lib.apv_analysis_jobs_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i64, i64, vp]
+    lib.apv_synthesis_dev.argtypes = [vp, i32, i32, vp, i64, i64, vp, vp, i32, i64]
     lib.apv_stream_init.argtypes = [vp, i32, vp, vp, i32, i32, i32]
     lib.apv_stream_set_perceptual.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double, i32]
     lib.apv_process_block.argtypes = [vp, vp, vp, vp]
@@ -208,6 +212,59 @@ def contrast_floor(floor_db):
     if not 0.0 < phi < float("inf"):
         raise ValueError(f"contrast_floor_db = {floor_db}: 10^(dB / 10) must be a positive, finite double")
     return phi
+
+
+STFT_MAX_JOBS = 8     # channel sets of one analysis launch (APV_STFT_MAX_JOBS)
+SPECTRUM_LAYOUTS = ("channel", "bin", "grouped")
+
+
+def transform_dtypes(dtype):
+    """(f64 flag, real dtype, complex dtype) of Engine.analysis / analysis_jobs / synthesize"""
+    if dtype in ("f32", F32, np.float32):
+        return 0, np.float32, np.complex64
+    if dtype in ("f64", F64, np.float64):
+        return 1, np.float64, np.complex128
+    raise ValueError(f"dtype must be 'f32' or 'f64', not {dtype!r}")
+
+
+def spectrum_layout(layout, n_ch, K, group=4):
+    """Where spectrum element (c, k) of a set of n_ch channels and K bins lies: (stride_c, stride_k, elements of the set,
+    (n_ch, K) array of element offsets).  "channel": [C][K]; "bin": [K][C]; "grouped": [ceil(K / g)][C][g], g neighbouring bins of
+    a channel contiguous (the last group may be partial: its tail elements belong to no bin)."""
+    c, k = np.arange(n_ch)[:, None], np.arange(K)[None, :]
+    if layout == "channel":
+        return K, 1, n_ch * K, c * K + k
+    if layout == "bin":
+        return 1, max(n_ch, 1), n_ch * K, k * n_ch + c
+    if layout == "grouped":
+        g = int(group)
+        if g < 2:
+            raise ValueError("a grouped layout needs group >= 2")
+        return g, max(n_ch, 1), -(-K // g) * n_ch * g, (k // g) * g * n_ch + c * g + k % g
+    raise ValueError(f"layout must be one of {SPECTRUM_LAYOUTS}, not {layout!r}")
+
+
+def check_analysis_args(N, in_len, x_stride, ring_off):
+    """The argument rules of apv_analysis_dev (include/apvast_hip.h), raised here as ValueError before anything is uploaded"""
+    if not 0 <= in_len <= N:
+        raise ValueError(f"in_len = {in_len} must be in 0..block_size = {N}")
+    if x_stride < in_len:
+        raise ValueError(f"x_stride = {x_stride} must be at least in_len = {in_len}")
+    if ring_off % N != 0 and (in_len != N or x_stride < N):
+        raise ValueError("a ring offset needs in_len == block_size and x_stride >= block_size")
+
+
+def check_jobs_args(N, n_jobs, n_hops, ring_off, x_stride, x_hop):
+    """The argument rules of apv_analysis_jobs_dev"""
+    if not 1 <= n_jobs <= STFT_MAX_JOBS:
+        raise ValueError(f"between 1 and {STFT_MAX_JOBS} channel sets per launch, not {n_jobs}")
+    if not 0 <= n_hops <= 65535:
+        raise ValueError(f"n_hops = {n_hops} must be in 0..65535")
+    if n_hops >= 1:
+        if ring_off != 0:
+            raise ValueError("the chunk form reads linear rows: ring_off must be 0")
+        if x_hop < 0 or x_stride < N + (n_hops - 1) * x_hop:
+            raise ValueError("x_stride must hold block_size + (n_hops - 1) x_hop samples")
 
 
 class DeviceBuffer:
@@ -738,6 +795,140 @@ class Engine:
         for b in (dsp, dov, dout):
             b.free()
         return ov, out
+
+    # -- the transforms as the streams launch them ------------------------------
+    # (any precision, zero padding, ring offset, strides, channel sets, chunk form: include/apvast_hip.h).  Host arrays in, arrays
+    # in natural (channel, bin) / (channel, sample) order out; the device layouts are built and undone here.  Row padding on the
+    # device is NaN and spectra / output buffers are pre-filled with `sentinel`, so that a read or a write in the wrong place shows.
+    def _rows_to_device(self, x, stride, rdt):
+        n_ch, W = x.shape
+        rows = np.full((n_ch + 1, stride) if stride else (1, 1), np.nan, dtype=rdt)      # one spare row behind the last
+        if stride:
+            rows[:n_ch, :W] = x
+        return self.to_device(rows)
+
+    def analysis(self, x, dtype="f32", in_len=None, ring_off=0, window=True, x_stride=None, layout="channel"):
+        """x: (n_ch, W) rows as stored -> (n_ch, N/2+1) spectra of rfft(w * y), y[n] = row[(n + ring_off) mod N] for n < in_len
+        (default W) and 0 up to N; rows lie x_stride (default W) samples apart on the device.  layout: "channel" or "bin"."""
+        f64, rdt, cdt = transform_dtypes(dtype)
+        x = np.asarray(x, dtype=rdt)
+        if x.ndim != 2:
+            raise ValueError("x must be (n_ch, samples)")
+        N = int(self.cfg.block_size)
+        n_ch, W = x.shape
+        in_len = W if in_len is None else int(in_len)
+        x_stride = W if x_stride is None else int(x_stride)
+        if x_stride < W or in_len > W:
+            raise ValueError("rows of x must hold in_len samples and fit x_stride")
+        if layout not in ("channel", "bin"):
+            raise ValueError("layout must be 'channel' or 'bin' (the grouped layout belongs to analysis_jobs)")
+        check_analysis_args(N, in_len, x_stride, int(ring_off))
+        K = N // 2 + 1
+        sc, sk, size, index = spectrum_layout(layout, n_ch, K)
+        dx = self._rows_to_device(x, x_stride, rdt)
+        ds = self.to_device(np.full(size + 1, np.nan, dtype=cdt))
+        try:
+            self._chk(self.lib.apv_analysis_dev(self.h, f64, n_ch, dx.ptr, x_stride, in_len, int(ring_off), int(bool(window)),
+                                                ds.ptr, sc, sk))
+            return ds.download((size + 1,), cdt)[index]
+        finally:
+            dx.free()
+            ds.free()
+
+    def analysis_jobs(self, sets, dtype="f32", ring_off=0, layouts=None, group=4, n_hops=0, x_stride=None, x_hop=None,
+                      sentinel=12345.5 + 67.25j, hop_gap=5):
+        """Windowed full-length analysis of up to 8 channel sets in one launch.  sets[j]: (n_ch_j, N) rings read at ring_off
+        (n_hops = 0), or (n_ch_j, W) linear rows of which hop i takes samples [i x_hop, i x_hop + N) (n_hops >= 1: the chunk form;
+        x_hop defaults to the handle's hop size, rows lie x_stride >= W apart).  layouts[j]: "channel", "bin" or "grouped" (groups of
+        `group` bins).  Returns (spectra, stray): spectra[j] is (n_ch_j, K), or (n_hops, n_ch_j, K) in the chunk form; stray[j] counts
+        the elements of set j's buffer that no (hop, channel, bin) maps to -- the tails of partial groups, hop_gap elements between
+        hops and behind the last -- which no longer hold `sentinel`."""
+        f64, rdt, cdt = transform_dtypes(dtype)
+        N = int(self.cfg.block_size)
+        K = N // 2 + 1
+        sets = [np.asarray(s, dtype=rdt) for s in sets]
+        n_jobs, n_hops, ring_off = len(sets), int(n_hops), int(ring_off)
+        layouts = ["channel"] * n_jobs if layouts is None else list(layouts)
+        if len(layouts) != n_jobs or any(s.ndim != 2 for s in sets):
+            raise ValueError("one layout per set, sets of shape (n_ch, samples)")
+        W = sets[0].shape[1] if sets else N
+        if any(s.shape[1] != W for s in sets) or (n_hops == 0 and W != N):
+            raise ValueError("rows of every set must be equally long (block_size samples for one hop)")
+        x_stride = W if x_stride is None else int(x_stride)
+        x_hop = int(self.cfg.hop_size) if x_hop is None else int(x_hop)
+        if x_stride < W or (n_hops == 0 and x_stride != N):
+            raise ValueError("x_stride must hold the rows (one hop: rows lie block_size apart)")
+        check_jobs_args(N, n_jobs, n_hops, ring_off, x_stride, x_hop)
+        hops = max(n_hops, 1)
+        lay = [spectrum_layout(l, s.shape[0], K, group) for l, s in zip(layouts, sets)]
+        spec_hop = [size + int(hop_gap) for _, _, size, _ in lay]
+        dx = [self._rows_to_device(s, x_stride, rdt) for s in sets]
+        ds = [self.to_device(np.full(hops * sh + 1, sentinel, dtype=cdt)) for sh in spec_hop]
+        vpa, i64a = C.c_void_p * n_jobs, C.c_int64 * n_jobs
+        try:
+            self._chk(self.lib.apv_analysis_jobs_dev(
+                self.h, f64, n_jobs, vpa(*[b.ptr.value for b in dx]), (C.c_int32 * n_jobs)(*[s.shape[0] for s in sets]),
+                vpa(*[b.ptr.value for b in ds]), i64a(*[l[0] for l in lay]), i64a(*[l[1] for l in lay]), ring_off, n_hops,
+                x_stride if n_hops else 0, x_hop if n_hops else 0, i64a(*spec_hop)))
+            spectra, stray = [], []
+            for b, sh, (_, _, size, index) in zip(ds, spec_hop, lay):
+                raw = b.download((hops * sh + 1,), cdt)
+                at = np.arange(hops)[:, None, None] * sh + index[None]
+                spectra.append(raw[at] if n_hops else raw[at[0]])
+                free = np.ones(raw.size, dtype=bool)
+                free[at.ravel()] = False
+                stray.append(int(np.count_nonzero(raw[free] != cdt(sentinel))))
+            return spectra, stray
+        finally:
+            for b in dx + ds:
+                b.free()
+
+    def synthesize(self, spec, overlap, dtype="f32", layout="channel", out_group=0, out_gstride=0, emit=True, sentinel=-54321.25):
+        """spec (n_ch, N/2+1), overlap (n_ch, N) -> (new overlap (n_ch, N), out (n_ch, H) or None with emit=False, details).
+        layout: "channel" or "bin" spectra on the device.  out_group > 0: the hop is emitted sample-major in groups of out_group
+        channels, out_gstride elements apart (0: H * out_group) -- channel-major when out_group does not divide n_ch;
+        details["emit"] names the form the output was read back in ("grouped" / "channel"), details["stray"] counts the elements
+        of the output buffer outside the emitted hop that no longer hold `sentinel`."""
+        f64, rdt, cdt = transform_dtypes(dtype)
+        N, H = int(self.cfg.block_size), int(self.cfg.hop_size)
+        K = N // 2 + 1
+        spec = np.asarray(spec, dtype=cdt)
+        overlap = np.ascontiguousarray(overlap, dtype=rdt)
+        n_ch = overlap.shape[0]
+        if spec.shape != (n_ch, K) or overlap.shape != (n_ch, N):
+            raise ValueError("spec must be (n_ch, N/2+1) and overlap (n_ch, N)")
+        if layout not in ("channel", "bin"):
+            raise ValueError("layout must be 'channel' or 'bin'")
+        out_group, out_gstride = int(out_group), int(out_gstride)
+        if out_group < 0 or (out_gstride != 0 and out_gstride < H * out_group):
+            raise ValueError("out_group >= 0, and out_gstride 0 or at least hop_size * out_group")
+        sc, sk, size, index = spectrum_layout(layout, n_ch, K)
+        raw = np.full(size + 1, np.nan, dtype=cdt)
+        raw[index] = spec
+        grouped = out_group > 0 and n_ch % out_group == 0
+        gs = out_gstride if out_gstride else H * out_group
+        c, n = np.arange(n_ch)[:, None], np.arange(H)[None, :]
+        at = (c // out_group) * gs + n * out_group + c % out_group if grouped else c * H + n
+        n_out = max(int(at.max()) + 1 if at.size else 0, n_ch * H, (n_ch // max(out_group, 1)) * gs) + 1
+        bufs = [self.to_device(raw), self.to_device(overlap)]
+        if emit:
+            bufs.append(self.to_device(np.full(n_out, sentinel, dtype=rdt)))
+        try:
+            self._chk(self.lib.apv_synthesis_dev(self.h, f64, n_ch, bufs[0].ptr, sc, sk, bufs[1].ptr, bufs[2].ptr if emit else None,
+                                                 out_group, out_gstride))
+            ov = bufs[1].download((n_ch, N), rdt)
+            details = {"emit": "grouped" if grouped else "channel", "stray": 0}
+            out = None
+            if emit:
+                o = bufs[2].download((n_out,), rdt)
+                out = o[at]
+                free = np.ones(n_out, dtype=bool)
+                free[at.ravel()] = False
+                details["stray"] = int(np.count_nonzero(o[free] != rdt(sentinel)))
+            return ov, out, details
+        finally:
+            for b in bufs:
+                b.free()
 
     # -- streaming ------------------------------------------------------------
     def stream_init(self, rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay):

@@ -269,6 +269,7 @@ hipError_t apv_launch_statforget(int x_c128, int acc_f64, int K, int M, int L, d
 hipError_t apv_launch_widen_c64(size_t count, const void* in, void* out, hipStream_t s);     // c64 -> c128
 
 // kernels_stft.hip
+constexpr int APV_STFT_MAX_JOBS = 8;            // channel sets of one analysis launch (STFT_MAX_JOBS there)
 hipError_t apv_launch_stft_analysis(int N, int n_ch, const float* x, float2* spec, hipStream_t s, std::string* why);
 hipError_t apv_launch_istft_ola(int N, int H, int n_ch, const float2* spec, float* overlap, float* out,
                                 hipStream_t s, std::string* why);

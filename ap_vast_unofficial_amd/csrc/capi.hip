@@ -955,6 +955,88 @@ int apv_istft_ola_dev(apv_handle* h, int32_t n_ch, const void* d_spec, float* d_
     return APV_OK;
 }
 
+// The transforms as the streams launch them (any precision, strides, zero padding, ring offset, channel sets, chunk form).  The
+// kernels take their arguments on trust; what could make them read or write outside the caller's buffers is refused here.
+namespace {
+bool transform_refused(apv_handle* h, int32_t f64, std::string* msg) {    // the handle's block size has no plan in this precision
+    if (h->cfg.block_size <= 0) *msg = "handle was created without an STFT geometry";
+    else if (apv_stft_size_ok(h->cfg.block_size, msg) && f64 && h->cfg.block_size > 4096)
+        *msg = "float64 transforms: block_size <= 4096 (double-precision FFT in LDS)";
+    return !msg->empty();
+}
+int transform_done(apv_handle* h, hipError_t e, const std::string& why) {
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+}  // namespace
+
+int apv_analysis_dev(apv_handle* h, int32_t f64, int32_t n_ch, const void* d_x, int64_t x_stride, int32_t in_len,
+                     int32_t ring_off, int32_t use_win, void* d_spec, int64_t stride_c, int64_t stride_k) {
+    if (!h || !d_x || !d_spec) return fail(h, APV_ERR_ARG, "null device pointer");
+    if (std::string msg; transform_refused(h, f64, &msg)) return fail(h, APV_ERR_ARG, msg);
+    const int N = h->cfg.block_size;
+    if (n_ch < 0) return fail(h, APV_ERR_ARG, "apv_analysis_dev: n_ch must not be negative");
+    if (in_len < 0 || in_len > N) return fail(h, APV_ERR_ARG, "apv_analysis_dev: in_len must be in 0..block_size");
+    if (x_stride < in_len) return fail(h, APV_ERR_ARG, "apv_analysis_dev: x_stride must be at least in_len");
+    if (ring_off % N != 0 && (in_len != N || x_stride < N))
+        return fail(h, APV_ERR_ARG, "apv_analysis_dev: a ring offset needs in_len == block_size and x_stride >= block_size");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    std::string why;
+    return transform_done(h, apv_launch_analysis(f64 ? 1 : 0, N, n_ch, d_x, (long)x_stride, in_len, ring_off, use_win ? 1 : 0, d_spec,
+                                                 (long)stride_c, (long)stride_k, h->stream, &why), why);
+}
+
+int apv_analysis_jobs_dev(apv_handle* h, int32_t f64, int32_t n_jobs, const void* const* d_x, const int32_t* n_ch,
+                          void* const* d_spec, const int64_t* stride_c, const int64_t* stride_k, int32_t ring_off,
+                          int32_t n_hops, int64_t x_stride, int64_t x_hop, const int64_t* spec_hop) {
+    if (!h || !d_x || !n_ch || !d_spec || !stride_c || !stride_k) return fail(h, APV_ERR_ARG, "null argument");
+    if (std::string msg; transform_refused(h, f64, &msg)) return fail(h, APV_ERR_ARG, msg);
+    const int N = h->cfg.block_size;
+    if (n_jobs < 1 || n_jobs > APV_STFT_MAX_JOBS) return fail(h, APV_ERR_ARG, "apv_analysis_jobs_dev: n_jobs must be in 1..8");
+    if (n_hops < 0 || n_hops > 65535) return fail(h, APV_ERR_ARG, "apv_analysis_jobs_dev: n_hops must be in 0..65535");
+    const void* x[APV_STFT_MAX_JOBS];
+    void* spec[APV_STFT_MAX_JOBS];
+    int nc[APV_STFT_MAX_JOBS];
+    long sc[APV_STFT_MAX_JOBS], sk[APV_STFT_MAX_JOBS], sh[APV_STFT_MAX_JOBS];
+    for (int j = 0; j < n_jobs; ++j) {
+        if (n_ch[j] < 0) return fail(h, APV_ERR_ARG, "apv_analysis_jobs_dev: n_ch must not be negative");
+        if (n_ch[j] > 0 && (!d_x[j] || !d_spec[j])) return fail(h, APV_ERR_ARG, "null device pointer");
+        if (stride_c[j] < 1 || stride_k[j] < 1) return fail(h, APV_ERR_ARG, "apv_analysis_jobs_dev: strides must be at least 1");
+        x[j] = d_x[j]; spec[j] = d_spec[j]; nc[j] = n_ch[j];
+        sc[j] = (long)stride_c[j]; sk[j] = (long)stride_k[j]; sh[j] = spec_hop ? (long)spec_hop[j] : 0;
+    }
+    if (n_hops >= 1) {
+        if (ring_off != 0) return fail(h, APV_ERR_ARG, "apv_analysis_jobs_dev: the chunk form reads linear rows (ring_off must be 0)");
+        if (x_hop < 0 || x_stride < N + (int64_t)(n_hops - 1) * x_hop)
+            return fail(h, APV_ERR_ARG, "apv_analysis_jobs_dev: x_stride must hold block_size + (n_hops - 1) x_hop samples");
+        if (n_hops > 1 && !spec_hop) return fail(h, APV_ERR_ARG, "apv_analysis_jobs_dev: spec_hop is needed with more than one hop");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    std::string why;
+    const hipError_t e = n_hops >= 1 ? apv_launch_stft_analysis_chunk(f64 ? 1 : 0, N, n_jobs, x, nc, spec, sc, sk, (long)x_stride, (long)x_hop,
+                                                                      sh, n_hops, h->stream, &why)
+                                     : apv_launch_stft_analysis_jobs(f64 ? 1 : 0, N, n_jobs, x, nc, spec, sc, sk, ring_off, h->stream, &why);
+    return transform_done(h, e, why);
+}
+
+int apv_synthesis_dev(apv_handle* h, int32_t f64, int32_t n_ch, const void* d_spec, int64_t stride_c, int64_t stride_k,
+                      void* d_overlap, void* d_out, int32_t out_group, int64_t out_gstride) {
+    if (!h || !d_spec || !d_overlap) return fail(h, APV_ERR_ARG, "null device pointer");
+    if (std::string msg; transform_refused(h, f64, &msg)) return fail(h, APV_ERR_ARG, msg);
+    const int N = h->cfg.block_size, H = h->cfg.hop_size;
+    if (n_ch < 0) return fail(h, APV_ERR_ARG, "apv_synthesis_dev: n_ch must not be negative");
+    if (out_group < 0) return fail(h, APV_ERR_ARG, "apv_synthesis_dev: out_group must not be negative");
+    if (out_gstride != 0 && out_gstride < (int64_t)H * out_group)
+        return fail(h, APV_ERR_ARG, "apv_synthesis_dev: out_gstride must be 0 or at least hop_size * out_group");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    std::string why;
+    return transform_done(h, apv_launch_synthesis(f64 ? 1 : 0, N, H, n_ch, d_spec, (long)stride_c, (long)stride_k, d_overlap, d_out,
+                                                  h->stream, &why, out_group, (long)out_gstride), why);
+}
+
 int apv_constrain_filters(apv_handle* h, void* d_w, int32_t n_bins, int32_t nV, int32_t L, int32_t N, int32_t J, void* d_taps) {
     if (!h || !d_w) return fail(h, APV_ERR_ARG, "null device pointer");
     if (N < 4 || (N & 1) || n_bins != N / 2 + 1) return fail(h, APV_ERR_ARG, "apv_constrain_filters: n_bins must be N / 2 + 1, N even");

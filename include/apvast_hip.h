@@ -419,6 +419,30 @@ int  apv_stft_analysis_dev(apv_handle* h, int32_t n_ch, const float* d_x, void* 
 /* overlap[c] = shift(overlap[c], H) + window * irfft(spec[c]); out[c][0:H] = overlap[c][0:H].
  *                                   replaces apvast.py:212-225, 265-293, 457-504 */
 int  apv_istft_ola_dev(apv_handle* h, int32_t n_ch, const void* d_spec, float* d_overlap, float* d_out);
+/* The transforms as the streams launch them, on their own (block and hop size from the handle's config; f64 = 0: float / c64
+ * data, 1: double / c128; every pointer is device memory).
+ * Analysis: spec[c * stride_c + k * stride_k] = rfft(w * y_c)[k], k <= N/2, with y_c[n] = x[c * x_stride + (n + ring_off) mod N]
+ * for n < in_len and 0 for in_len <= n < N; w the sine window (use_win = 1) or all ones (use_win = 0).  APV_ERR_ARG unless
+ * 0 <= in_len <= N and x_stride >= in_len; a non-zero ring_off (any sign, taken modulo N) needs in_len == N and x_stride >= N;
+ * f64 needs N <= 4096.                                  apvast.py:246-255, 417-422, 430-431 */
+int  apv_analysis_dev(apv_handle* h, int32_t f64, int32_t n_ch, const void* d_x, int64_t x_stride, int32_t in_len,
+                      int32_t ring_off, int32_t use_win, void* d_spec, int64_t stride_c, int64_t stride_k);
+/* Windowed full-length analysis of n_jobs (1..8) channel sets in ONE launch, the form a streaming hop runs: set j has n_ch[j]
+ * channels at d_x[j] and writes spec[j][c * stride_c[j] + k * stride_k[j]].  A set whose stride_c and stride_k both exceed 1 is
+ * GROUPED: g = stride_c[j] neighbouring bins of a channel are contiguous, element (c, k) at (k / g) * g * stride_k[j] + c * g + k % g.
+ * n_hops = 0: one hop, rows of N samples read as rings at ring_off.  n_hops in 1..65535: the chunk form, rows x_stride >= N +
+ * (n_hops - 1) * x_hop samples apart, hop i reads its block i * x_hop samples into the row and writes spec_hop[j] * i elements
+ * further on (ring_off must be 0). */
+int  apv_analysis_jobs_dev(apv_handle* h, int32_t f64, int32_t n_jobs, const void* const* d_x, const int32_t* n_ch,
+                           void* const* d_spec, const int64_t* stride_c, const int64_t* stride_k, int32_t ring_off,
+                           int32_t n_hops, int64_t x_stride, int64_t x_hop, const int64_t* spec_hop);
+/* Synthesis + overlap-add: new = w * irfft(spec_c) (imaginary parts of DC and Nyquist ignored), overlap[c] (N samples, channel-
+ * major) = shift(overlap[c], H) + new, and, unless d_out is NULL, out = overlap[c][0:H]: channel-major [n_ch][H], or with
+ * out_group > 0 dividing n_ch sample-major in groups [n_ch / out_group][H][out_group], the groups out_gstride elements apart
+ * (0: H * out_group; otherwise at least that).  An out_group that does not divide n_ch emits channel-major.
+ *                                                         apvast.py:265-293, 457-504 */
+int  apv_synthesis_dev(apv_handle* h, int32_t f64, int32_t n_ch, const void* d_spec, int64_t stride_c, int64_t stride_k,
+                       void* d_overlap, void* d_out, int32_t out_group, int64_t out_gstride);
 
 /* ---- streaming composition (one call = one hop) -------------------------- */
 /* Upload the room impulse responses and allocate all streaming state.  h_rir_A / h_rir_B: (rir_len, L, M)
