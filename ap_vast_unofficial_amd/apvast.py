@@ -107,6 +107,8 @@ What is different (keyword-only, after ``perceptual``)
     masking model carried by the reference's MATLAB twin (perceptualModel.m), evaluated per block on the
     device.  Parity for it is unpinned (no MATLAB here).
 """
+import collections
+
 import numpy as np
 
 from . import _capi
@@ -1078,224 +1080,174 @@ class apvast:
         programs that run, K, 2 L^2 + L), per bin [R_B (lower triangle) | R_D (lower triangle) | r], complex128 (complex64 with
         ``dtype="f32"`` up to 64 loudspeakers: the precision they are kept in); absent otherwise.  R_*, r_*, U_*, lambda_* are what the last hop of THIS object left on the device: they follow a restored
         window from the next hop on, not from set_state."""
-        st = self._get_state()
-        if self.mode == "subband" and self.statistics_hops > 1:
-            e, T, L = self._eng, self.statistics_hops, self.number_of_srcs
-            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
-            st["statistics_window"] = np.stack([e.get_state(f"stat_window{z}", (T, self._K, 2 * L * L + L), e.stat_dtype)
-                                                for z in zs]).astype(np.complex128)
-            st["statistics_window_fill"] = int(e.get_state("stat_window_fill", (1,), np.int32)[0])
-        if self.mode == "subband" and self.statistics_forgetting is not None:
-            e, L = self._eng, self.number_of_srcs
-            st["statistics_forgetting_sums"] = np.stack([e.get_state(f"stat_forget{z}", (self._K, 2 * L * L + L), e.stat_dtype)
-                                                         for z, run in enumerate((self.run_A, self.run_B)) if run])
-        if self.mode == "subband" and self.synthesis == "fir":
-            e, L, V, J = self._eng, self.number_of_srcs, len(self._ranks), int(self.filter_length)
-            st["fir_synthesis_taps"] = np.stack([e.get_state(f"fir_synth_taps_{'AB'[z]}", (V, J, L), e.lam_dtype)
-                                                 for z, run in enumerate((self.run_A, self.run_B)) if run]).astype(np.float64)
-            st["fir_synthesis_history"] = np.stack([e.get_state(f"fir_synth_history{g}", (J - 1,), e.s_dtype) if J > 1 else np.zeros(0)
-                                                    for g in range(2)]).astype(np.float64)
-        if self.mode == "subband" and self._evaluation is not None:
-            # the newest Pv - 1 output samples of every evaluated group (zone programs that run; the E ranks, then the target)
-            # and the accumulated energies [bright of the E ranks | dark | error | target]
-            Z, E, Pv, Mv = self._eval_dims()
-            e, L = self._eng, self.number_of_srcs
-            st["evaluation_history"] = (e.get_state("eval_history", (Z, E + 1, Pv - 1, L), e.s_dtype) if Pv > 1
-                                        else np.zeros((Z, E + 1, 0, L))).astype(np.float64)
-            st["evaluation_totals"] = e.get_state("eval_totals", (Z, 3 * E + 1, Mv), np.float64)
-        if self.mode == "subband" and self._evaluation_spectra:
-            # the per-bin energies as the device keeps them and the last N pressure samples of every set, oldest first
-            Z, E, _, Mv = self._eval_dims()
-            st["evaluation_spectra"] = self._eng.get_state("eval_spectra", (Z, 3 * E + 1, self._K, Mv), np.float64)
-            st["evaluation_ring"] = self._eng.get_state("eval_ring", (Z, 2 * E + 1, Mv, self.block_size), np.float64)
-        if self.mode == "subband" and self._evaluation_detectability:
-            # the totals as the device keeps them -- per program sum, max and audible count of the error, then of the leak -- and
-            # in a last row the hops they cover, which only the host counts
-            Z, E, _, Mv = self._eval_dims()
-            st["evaluation_detectability"] = np.concatenate(
-                [self._eng.get_state("eval_detect", (Z, 6 * E, Mv), np.float64), np.full((Z, 1, Mv), float(self._detect_hops))], axis=1)
-        if self._live_applied:
-            P, L, M = self.rir_length, self.number_of_srcs, self.number_of_mics
-            Q = max(P - 1, 1)
-            if self.mode == "broadband":
-                g = lambda name, shape: self._eng.bb_get_state(name, shape)
-            else:
-                g = lambda name, shape: self._eng.get_state(name, shape, self._eng.s_dtype).astype(np.float64)
-            st["fir_correction"] = np.stack([g(f"fir_correction{p}", (M, L, Q)) for p in range(4)]).transpose(0, 3, 2, 1)
-            st["target_fir_correction"] = np.stack([g(f"target_fir_correction{z}", (M, Q)) for z in range(2)]).transpose(0, 2, 1)
-        return st
-
-    def _get_state(self):
-        e, N, L, M = self._eng, self.block_size, self.number_of_srcs, self.number_of_mics
-        if self.mode == "broadband":
-            S, P, H = self.statistics_buffer_length, self.rir_length, self.hop_size
-            g = e.bb_get_state
-            return {
-                "response": np.stack([g(f"response{p}", (M, L, N)) for p in range(4)]).transpose(0, 3, 2, 1),
-                "target_response": np.stack([g(f"target_response{z}", (M, N)) for z in range(2)]).transpose(0, 2, 1),
-                "stats": np.stack([g(f"stats{p}", (M, L, S)) for p in range(4)]).transpose(0, 3, 2, 1),
-                "target_stats": np.stack([g(f"target_stats{z}", (M, S)) for z in range(2)]).transpose(0, 2, 1),
-                "overlap": np.stack([g(f"overlap{p}", (M, L, N)) for p in range(4)]).transpose(0, 3, 2, 1),
-                "target_overlap": np.stack([g(f"target_overlap{z}", (M, N)) for z in range(2)]).transpose(0, 2, 1),
-                "input_block": g("input_block", (2, N)),
-                "input_history": np.stack([g(f"input_history{k}", (P - 1 + H,)) for k in range(2)]),
-                "out_overlap": g("out_overlap", (self._n_out, N)),
-            }
-        sd = e.s_dtype                      # float32, or float64 with the float64 front-end (dtype="f64")
-        resp = np.stack([e.get_state(f"response{p}", (M, L, N), sd) for p in range(4)])
-        tresp = np.stack([e.get_state(f"target_response{z}", (M, N), sd) for z in range(2)])
-        st = {
-            "response": resp.transpose(0, 3, 2, 1).astype(np.float64),           # (4, N, L, M)
-            "target_response": tresp.transpose(0, 2, 1).astype(np.float64),      # (2, N, M)
-            "input_block": e.get_state("input_block", (2, N), sd).astype(np.float64),
-            # rir_length - 1 + hop_size samples; more when the RIR convolution is uniformly partitioned (long responses)
-            "input_history": np.stack([e.get_state(f"input_history{g}", (e.state_bytes(f"input_history{g}") // np.dtype(sd).itemsize,),
-                                                   sd) for g in range(2)]).astype(np.float64),
-            "out_overlap": e.get_state("out_overlap", (self._n_out, N), sd).astype(np.float64),
-        }
-        return st
+        return {row.key: row.get(self) for row in self._STATE_ROWS if (row.reports or row.accepts)(self)}
 
     def set_state(self, state):
-        e = self._eng
-        known = (self._BB_STATE if self.mode == "broadband" else self._SB_STATE) + self._LIVE_STATE
-        if self.mode == "subband" and self.statistics_hops > 1:
-            known = known + self._WIN_STATE
-        if self.mode == "subband" and self.statistics_forgetting is not None:
-            known = known + self._FORGET_STATE
-        if self.mode == "subband" and self.synthesis == "fir":
-            known = known + self._FIR_STATE
-        if self.mode == "subband" and self._evaluation is not None:
-            known = known + self._EVAL_STATE
-        if self.mode == "subband" and self._evaluation_spectra:
-            known = known + self._EVALSPEC_STATE
-        if self.mode == "subband" and self._evaluation_detectability:
-            known = known + self._EVALDETECT_STATE
+        rows = [row for row in self._STATE_ROWS if row.accepts(self)]
+        known = [row.key for row in rows]
         unknown = sorted(set(state) - set(known))
         if unknown:
-            raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {list(known)}")
-        self._set_state(state)
-        if "statistics_window" in state:
-            T, L = self.statistics_hops, self.number_of_srcs
-            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
-            win = np.asarray(state["statistics_window"])
-            if win.shape != (len(zs), T, self._K, 2 * L * L + L):
-                raise ValueError(f"statistics_window must have shape {(len(zs), T, self._K, 2 * L * L + L)}, got {win.shape}")
-            for i, z in enumerate(zs):
-                e.set_state(f"stat_window{z}", np.ascontiguousarray(win[i], dtype=e.stat_dtype))
-        if "statistics_forgetting_sums" in state:
-            L = self.number_of_srcs
-            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
-            sums = np.asarray(state["statistics_forgetting_sums"])
-            if sums.shape != (len(zs), self._K, 2 * L * L + L):
-                raise ValueError(f"statistics_forgetting_sums must have shape {(len(zs), self._K, 2 * L * L + L)}, got {sums.shape}")
-            for i, z in enumerate(zs):
-                e.set_state(f"stat_forget{z}", np.ascontiguousarray(sums[i], dtype=e.stat_dtype))
-        if "fir_synthesis_taps" in state:
-            L, V, J = self.number_of_srcs, len(self._ranks), int(self.filter_length)
-            zs = [z for z, run in enumerate((self.run_A, self.run_B)) if run]
-            taps = np.asarray(state["fir_synthesis_taps"])
-            if taps.shape != (len(zs), V, J, L):
-                raise ValueError(f"fir_synthesis_taps must have shape {(len(zs), V, J, L)}, got {taps.shape}")
-            for i, z in enumerate(zs):
-                e.set_state(f"fir_synth_taps_{'AB'[z]}", np.ascontiguousarray(taps[i], dtype=e.lam_dtype))
-        if "fir_synthesis_history" in state:
-            J = int(self.filter_length)
-            hst = np.asarray(state["fir_synthesis_history"])
-            if hst.shape != (2, J - 1):
-                raise ValueError(f"fir_synthesis_history must have shape {(2, J - 1)}, got {hst.shape}")
-            for g in range(2 if J > 1 else 0):
-                e.set_state(f"fir_synth_history{g}", np.ascontiguousarray(hst[g], dtype=e.s_dtype))
-        if "evaluation_history" in state or "evaluation_totals" in state:
-            Z, E, Pv, Mv = self._eval_dims()
-            L = self.number_of_srcs
-            if "evaluation_history" in state:
-                hst = np.asarray(state["evaluation_history"])
-                if hst.shape != (Z, E + 1, Pv - 1, L):
-                    raise ValueError(f"evaluation_history must have shape {(Z, E + 1, Pv - 1, L)}, got {hst.shape}")
-                if Pv > 1:
-                    e.set_state("eval_history", np.ascontiguousarray(hst, dtype=e.s_dtype))
-            if "evaluation_totals" in state:
-                tot = np.asarray(state["evaluation_totals"])
-                if tot.shape != (Z, 3 * E + 1, Mv):
-                    raise ValueError(f"evaluation_totals must have shape {(Z, 3 * E + 1, Mv)}, got {tot.shape}")
-                e.set_state("eval_totals", np.ascontiguousarray(tot, dtype=np.float64))
-        if "evaluation_spectra" in state or "evaluation_ring" in state:
-            Z, E, _, Mv = self._eval_dims()
-            shapes = {"evaluation_spectra": ("eval_spectra", (Z, 3 * E + 1, self._K, Mv)),
-                      "evaluation_ring": ("eval_ring", (Z, 2 * E + 1, Mv, self.block_size))}
-            for key, (name, shape) in shapes.items():
-                if key in state:
-                    a = np.asarray(state[key])
-                    if a.shape != shape:
-                        raise ValueError(f"{key} must have shape {shape}, got {a.shape}")
-                    e.set_state(name, np.ascontiguousarray(a, dtype=np.float64))
-        if "evaluation_detectability" in state:
-            Z, E, _, Mv = self._eval_dims()
-            a = np.asarray(state["evaluation_detectability"], dtype=np.float64)
-            if a.shape != (Z, 6 * E + 1, Mv):
-                raise ValueError(f"evaluation_detectability must have shape {(Z, 6 * E + 1, Mv)}, got {a.shape}")
-            hops = a[0, 6 * E, 0]
-            if not (hops >= 0 and hops == np.floor(hops) and np.all(a[:, 6 * E] == hops)):
-                raise ValueError("evaluation_detectability: the last row must hold one hop count, a non-negative integer")
-            e.set_state("eval_detect", np.ascontiguousarray(a[:, :6 * E]))
-            self._detect_hops = int(hops)
-        if "statistics_window_fill" in state:
-            e.set_state("stat_window_fill", np.array([int(state["statistics_window_fill"])], dtype=np.int32))
-        if any(k in state for k in self._LIVE_STATE):
-            self._apply_live()             # responses assigned before the resume are in place before their tails are
-            dt = np.float64 if self.mode == "broadband" else e.s_dtype
-            put = e.bb_set_state if self.mode == "broadband" else e.set_state
-            if "fir_correction" in state:
-                r = np.asarray(state["fir_correction"], dtype=dt)                 # (4, P-1, L, M) -> [M][L][P-1]
-                for p in range(4):
-                    put(f"fir_correction{p}", np.ascontiguousarray(r[p].transpose(2, 1, 0)))
-            if "target_fir_correction" in state:
-                t = np.asarray(state["target_fir_correction"], dtype=dt)          # (2, P-1, M) -> [M][P-1]
-                for z in range(2):
-                    put(f"target_fir_correction{z}", np.ascontiguousarray(t[z].T))
-            self._live_applied = True
+            raise KeyError(f"set_state: no such state array(s) in {self.mode} mode: {unknown}; known: {known}")
+        rows = [row for row in rows if row.key in state]
+        for row in rows:
+            if row.shape is not None:
+                want, got = row.shape(self), np.asarray(state[row.key]).shape
+                if got != want:
+                    raise ValueError(f"{row.key} must have shape {want}, got {got}")
+        for row in rows:
+            row.put(self, state[row.key])
 
-    def _set_state(self, state):
+    # What the rows of the table (_state_rows, below the class) are made of.  Real samples cross in float64: broadband mode keeps
+    # them so, subband mode in the front-end's own precision (float32, or float64 with dtype="f64").
+    def _get_real(self, name, shape):
+        e = self._eng
+        return e.bb_get_state(name, shape) if self.mode == "broadband" else e.get_state(name, shape, e.s_dtype).astype(np.float64)
+
+    def _put_real(self, name, value):
         e = self._eng
         if self.mode == "broadband":
-            f = lambda a: np.asarray(a, dtype=np.float64)
-            per_path = {"response": "response", "stats": "stats", "overlap": "overlap"}
-            per_zone = {"target_response": "target_response", "target_stats": "target_stats", "target_overlap": "target_overlap"}
-            for key, name in per_path.items():
-                if key in state:
-                    r = f(state[key])                                             # (4, len, L, M) -> [M][L][len]
-                    for p in range(4):
-                        e.bb_set_state(f"{name}{p}", np.ascontiguousarray(r[p].transpose(2, 1, 0)))
-            for key, name in per_zone.items():
-                if key in state:
-                    t = f(state[key])                                             # (2, len, M) -> [M][len]
-                    for z in range(2):
-                        e.bb_set_state(f"{name}{z}", np.ascontiguousarray(t[z].T))
-            if "input_block" in state:
-                e.bb_set_state("input_block", f(state["input_block"]))
-            if "input_history" in state:
-                for g in range(2):
-                    e.bb_set_state(f"input_history{g}", f(state["input_history"])[g])
-            if "out_overlap" in state:
-                e.bb_set_state("out_overlap", f(state["out_overlap"]))
-            return
-        sd = e.s_dtype
-        if "response" in state:
-            r = np.asarray(state["response"], dtype=sd)                          # (4, N, L, M) -> [M][L][N]
-            for p in range(4):
-                e.set_state(f"response{p}", np.ascontiguousarray(r[p].transpose(2, 1, 0)))
-        if "target_response" in state:
-            t = np.asarray(state["target_response"], dtype=sd)                   # (2, N, M) -> [M][N]
-            for z in range(2):
-                e.set_state(f"target_response{z}", np.ascontiguousarray(t[z].T))
-        if "input_block" in state:
-            e.set_state("input_block", np.asarray(state["input_block"], dtype=sd))
-        if "input_history" in state:
-            hst = np.asarray(state["input_history"], dtype=sd)
-            for g in range(2):
-                e.set_state(f"input_history{g}", hst[g])
-        if "out_overlap" in state:
-            e.set_state("out_overlap", np.asarray(state["out_overlap"], dtype=sd))
+            e.bb_set_state(name, np.asarray(value, dtype=np.float64))
+        else:
+            e.set_state(name, np.asarray(value, dtype=e.s_dtype))
+
+    def _get_banks(self, name, count, length):
+        """the device's [M][L][len] of the four paths (count = 4) as (4, len, L, M), its [M][len] of the two targets as (2, len, M)"""
+        shape = (self.number_of_mics,) + ((self.number_of_srcs,) if count == 4 else ()) + (length,)
+        return np.stack([self._get_real(f"{name}{i}", shape).T for i in range(count)])
+
+    def _put_banks(self, name, count, value):
+        for i in range(count):
+            self._put_real(f"{name}{i}", np.asarray(value)[i].T)
+
+    def _put_live(self, name, count, value):
+        self._apply_live()                 # responses assigned before the resume are in place before their tails are
+        self._put_banks(name, count, value)
+        self._live_applied = True
+
+    def _zones(self):
+        return [z for z, run in enumerate((self.run_A, self.run_B)) if run]
+
+    def _get_zones(self, name, shape, dtype):
+        """one engine array per zone program that runs ({z}: 0 / 1, {Z}: A / B), stacked"""
+        return np.stack([self._eng.get_state(name.format(z=z, Z="AB"[z]), shape, dtype) for z in self._zones()])
+
+    def _put_zones(self, name, value, dtype):
+        for i, z in enumerate(self._zones()):
+            self._eng.set_state(name.format(z=z, Z="AB"[z]), np.asarray(value)[i].astype(dtype))
+
+    def _get_signals(self, name, length):
+        """one engine array per input signal as (2, len); not fetched where len = 0"""
+        return np.stack([self._get_real(f"{name}{g}", (length,)) if length else np.zeros(0) for g in range(2)])
+
+    def _put_signals(self, name, value):
+        a = np.asarray(value)
+        for g in range(2 if a.size else 0):
+            self._put_real(f"{name}{g}", a[g])
+
+    def _input_history_len(self):
+        # rir_length - 1 + hop_size samples; more in subband mode when the RIR convolution is uniformly partitioned (long responses)
+        if self.mode == "broadband":
+            return self.rir_length - 1 + self.hop_size
+        return self._eng.state_bytes("input_history0") // np.dtype(self._eng.s_dtype).itemsize
+
+    def _get_detectability(self):
+        # the totals as the device keeps them -- per program sum, max and audible count of the error, then of the leak -- and
+        # in a last row the hops they cover, which only the host counts
+        Z, E, _, Mv = self._eval_dims()
+        return np.concatenate([self._eng.get_state("eval_detect", (Z, 6 * E, Mv), np.float64),
+                               np.full((Z, 1, Mv), float(self._detect_hops))], axis=1)
+
+    def _put_detectability(self, value):
+        a, E = np.asarray(value, dtype=np.float64), self._eval_dims()[1]
+        hops = a[0, 6 * E, 0]
+        if not (hops >= 0 and hops == np.floor(hops) and np.all(a[:, 6 * E] == hops)):
+            raise ValueError("evaluation_detectability: the last row must hold one hop count, a non-negative integer")
+        self._eng.set_state("eval_detect", np.ascontiguousarray(a[:, :6 * E]))
+        self._detect_hops = int(hops)
 
     def close(self):
         self._eng.close()
+
+
+# One row per key of the state dict.  accepts(self): set_state takes the key; reports(self) (None: as accepts): get_state returns
+# it; shape(self) (None: the device's size check is the only one): what set_state compares the value's shape with; get(self) -> the
+# value; put(self, value).
+_StateRow = collections.namedtuple("_StateRow", "key accepts reports shape get put")
+
+
+def _state_rows():
+    """The table, in the order set_state applies the keys."""
+    always = lambda self: True
+    bb = lambda self: self.mode == "broadband"
+    sub = lambda on: (lambda self: self.mode == "subband" and bool(on(self)))         # a subband feature behind its keyword
+    win, forget = sub(lambda self: self.statistics_hops > 1), sub(lambda self: self.statistics_forgetting is not None)
+    fir, ev = sub(lambda self: self.synthesis == "fir"), sub(lambda self: self._evaluation is not None)
+    evs, evd = sub(lambda self: self._evaluation_spectra), sub(lambda self: self._evaluation_detectability)
+    live = lambda self: self._live_applied
+    N = lambda self: self.block_size
+    S = lambda self: self.statistics_buffer_length
+    Q = lambda self: max(self.rir_length - 1, 1)
+    J = lambda self: int(self.filter_length)
+    slot = lambda self: 2 * self.number_of_srcs ** 2 + self.number_of_srcs             # a bin's [R_B | R_D | r], lower triangles
+    taps = lambda self: (len(self._ranks), J(self), self.number_of_srcs)
+    dims = lambda f: (lambda self: f(self, *self._eval_dims()))                        # f(self, Z, E, Pv, Mv)
+
+    def banks(key, count, length, accepts=always, reports=None, put=apvast._put_banks):
+        """(4, len, L, M) of the four paths or (2, len, M) of the two targets; no shape check of its own"""
+        return _StateRow(key, accepts, reports, None, lambda self: self._get_banks(key, count, length(self)),
+                         lambda self, v: put(self, key, count, v))
+
+    def real(key, shape):
+        """one array of real samples under the key's own name; no shape check of its own"""
+        return _StateRow(key, always, None, None, lambda self: self._get_real(key, shape(self)), lambda self, v: self._put_real(key, v))
+
+    def zones(key, name, accepts, shape, dtype, out=None):
+        """(zone programs that run, *shape) of a subband feature, kept in dtype(engine) and handed out as `out` (None: as kept)"""
+        return _StateRow(key, accepts, None, lambda self: (len(self._zones()),) + shape(self),
+                         lambda self: self._get_zones(name, shape(self), dtype(self._eng)).astype(out or dtype(self._eng)),
+                         lambda self, v: self._put_zones(name, v, dtype(self._eng)))
+
+    def whole(key, name, accepts, shape, dtype=lambda e: np.float64):
+        """one engine array of a subband feature, handed out as float64; neither fetched nor sent where it has no elements"""
+        return _StateRow(key, accepts, None, shape,
+                         lambda self: (self._eng.get_state(name, shape(self), dtype(self._eng)).astype(np.float64) if all(shape(self))
+                                       else np.zeros(shape(self))),
+                         lambda self, v: all(shape(self)) and self._eng.set_state(name, np.ascontiguousarray(v, dtype=dtype(self._eng))))
+
+    return (
+        banks("response", 4, N),
+        banks("target_response", 2, N),
+        banks("stats", 4, S, bb),
+        banks("target_stats", 2, S, bb),
+        banks("overlap", 4, N, bb),
+        banks("target_overlap", 2, N, bb),
+        real("input_block", lambda self: (2, N(self))),
+        _StateRow("input_history", always, None, None, lambda self: self._get_signals("input_history", self._input_history_len()),
+                  lambda self, v: self._put_signals("input_history", v)),
+        real("out_overlap", lambda self: (self._n_out, N(self))),
+        zones("statistics_window", "stat_window{z}", win, lambda self: (self.statistics_hops, self._K, slot(self)),
+              lambda e: e.stat_dtype, out=np.complex128),
+        _StateRow("statistics_window_fill", win, None, None, lambda self: int(self._eng.get_state("stat_window_fill", (1,), np.int32)[0]),
+                  lambda self, v: self._eng.set_state("stat_window_fill", np.array([int(v)], dtype=np.int32))),
+        zones("statistics_forgetting_sums", "stat_forget{z}", forget, lambda self: (self._K, slot(self)), lambda e: e.stat_dtype),
+        zones("fir_synthesis_taps", "fir_synth_taps_{Z}", fir, taps, lambda e: e.lam_dtype, out=np.float64),
+        _StateRow("fir_synthesis_history", fir, None, lambda self: (2, J(self) - 1),
+                  lambda self: self._get_signals("fir_synth_history", J(self) - 1),
+                  lambda self, v: self._put_signals("fir_synth_history", v)),
+        # the newest Pv - 1 output samples of every evaluated group (zone programs that run; the E ranks, then the target)
+        # and the accumulated energies [bright of the E ranks | dark | error | target]
+        whole("evaluation_history", "eval_history", ev, dims(lambda self, Z, E, Pv, Mv: (Z, E + 1, Pv - 1, self.number_of_srcs)),
+              dtype=lambda e: e.s_dtype),
+        whole("evaluation_totals", "eval_totals", ev, dims(lambda self, Z, E, Pv, Mv: (Z, 3 * E + 1, Mv))),
+        # the per-bin energies as the device keeps them and the last N pressure samples of every set, oldest first
+        whole("evaluation_spectra", "eval_spectra", evs, dims(lambda self, Z, E, Pv, Mv: (Z, 3 * E + 1, self._K, Mv))),
+        whole("evaluation_ring", "eval_ring", evs, dims(lambda self, Z, E, Pv, Mv: (Z, 2 * E + 1, Mv, N(self)))),
+        _StateRow("evaluation_detectability", evd, None, dims(lambda self, Z, E, Pv, Mv: (Z, 6 * E + 1, Mv)),
+                  apvast._get_detectability, apvast._put_detectability),
+        # the two correction keys last: always taken, handed out once a response update has reached the device
+        banks("fir_correction", 4, Q, reports=live, put=apvast._put_live),
+        banks("target_fir_correction", 2, Q, reports=live, put=apvast._put_live),
+    )
+
+
+apvast._STATE_ROWS = _state_rows()

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -542,7 +543,20 @@ int apv_live_update(apv_handle* h, FirLive& fl, const FirLiveBanks& b, const dou
 int apv_live_apply(apv_handle* h, FirLive& fl, int P, int C, int M, int f64, void* const dst[6], int n_add, int shift, long row_len,
                    int d0, int dmod, hipStream_t st);
 void apv_live_advance(FirLive& fl, int hops);
-// named state "fir_correction<j>" (j < 4) / "target_fir_correction<j - 4>": get or set tail j, esz bytes per sample
+// state names of an indexed family, "<pre><c>" with c one of the `count` characters from `first` on ('0': an index, 'A': a zone
+// program): c - first, else -1
+inline int apv_name_index(const char* name, const char* pre, int count, char first = '0') {
+    const size_t pl = std::strlen(pre);
+    if (std::strncmp(name, pre, pl) != 0 || name[pl] == 0 || name[pl + 1] != 0) return -1;
+    const int q = name[pl] - first;
+    return q >= 0 && q < count ? q : -1;
+}
+// named state "fir_correction<j>" (j < 4) / "target_fir_correction<j - 4>" of either stream: j, else -1 ...
+inline int apv_live_index(const char* name) {
+    const int p = apv_name_index(name, "fir_correction", 4), z = apv_name_index(name, "target_fir_correction", 2);
+    return p >= 0 ? p : z >= 0 ? 4 + z : -1;
+}
+// ... and get or set tail j, esz bytes per sample
 int apv_live_state(apv_handle* h, FirLive& fl, int j, int P, int H, int C, int M, size_t esz, void* h_buf, size_t bytes, bool get,
                    hipStream_t st);
 void apv_live_free(FirLive& fl);

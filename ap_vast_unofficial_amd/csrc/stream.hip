@@ -10,8 +10,7 @@
 //
 // Device layouts: control-point channel c = m*L + l (loudspeaker fastest), so a bin's control-point
 // matrix X[k] = [M][L] is one contiguous slab of the bin-major spectra [K][M*L].
-#include "apv_internal.h"
-#include "apv_owned.h"
+#include "stream_types.h"
 
 #include <algorithm>
 #include <cmath>
@@ -19,196 +18,7 @@
 #include <cstring>
 #include <vector>
 
-constexpr int CK_NB = 4;      // back streams of the chunked whole-signal path
-constexpr int CK_NS = 3;      // pinned staging slots (chunks) of that path
-
-// A measuring aid around one launch of the hop (statistics, projection, FIR synthesis): the events exist only where the stage's
-// environment switch is set, and run_hop reads them after every hop.
-struct StageTimer {
-    hipEvent_t ev[2] = {nullptr, nullptr};      // recorded in front of and behind the launch
-    double ms[2] = {0.0, 0.0};                  // {sum of its times in ms, hops timed}
-    hipError_t read() {
-        if (!ev[0]) return hipSuccess;
-        float t = 0.f;
-        const hipError_t e = hipEventElapsedTime(&t, ev[0], ev[1]);
-        if (e == hipSuccess) { ms[0] += t; ms[1] += 1.0; }
-        return e;
-    }
-};
-
-struct apv_stream {
-    int N, H, K, L, M, C, P, nV, zones, pad;
-    int f64;                      // precision of the whole front-end: RIRs, rings, spectra, overlap buffers, outputs
-    size_t esz;                   // bytes per real sample (4 | 8); a complex spectrum element is 2 esz
-    int ring_off;                 // physical index of logical sample 0 in every ring
-    int cur;                      // which input-history buffer is current
-    int n_out;                    // synthesis channels: zones*nV*L filtered + 2*L target
-    int out_group;                // cfg.out_layout = 1: L (hops are emitted [n_out / L][H][L]); 0 = channel-major [n_out][H]
-    void* rir[2];                 // [P][C]  zone A, zone B
-    void* trir[2];                // [P][M]  target RIRs (reference loudspeaker, delayed)
-    void* xhist[2][2];            // [buf][signal][keep+H+pad]
-    void* resp[4];                // [C][N] rings: A->A, A->B, B->A, B->B
-    void* tresp[2];               // [M][N] rings: target A, target B
-    void* inblk;                  // [2][N] rings: input blocks
-    void* X[4];                   // control-point spectra: bin-major [K][C], or grouped [Kp / xg][C][xg] (see xg); Kp C elements each
-    int xg, xg_default;           // bins per group of the spectra layout (1 = bin-major).  4 where the joint diagonalisation that will
-                                  // run reads groups (float64 front-end, order 16, apv_gevd_reads_groups) and no perceptual weighting
-                                  // is on (its kernels scale bin-major spectra): a transform then fills 64-byte lines
-    int Kp;                       // K rounded up to a multiple of 8: bins a spectra set is allocated for
-    void* tspec[2];               // [K][M]
-    void* inspec;                 // [2][K]
-    void* w[2];                   // [K][nV][L] per zone
-    void* lam[2];                 // [K][L]
-    int32_t* status[2];           // [K]
-    void* tgt;                    // [L][K] target filter spectra (shared by A_t and B_t, apvast.py:389-390)
-    void* outspec;                // [n_out][K]
-    void* outov;                  // [n_out][N]
-    void* out;                    // [n_out][H] samples, then the [2][K] status words of the hop: one copy back
-    // perceptual weighting (off when nch == 0)
-    int nch, norm_mode;
-    double Cs, Ca, Leff;
-    double* G2;                   // [K][nch]
-    double* G2T;                  // [nch][K]
-    void* Wgt[2];                 // [K][M] per zone
-    // pinned staging + one captured hipGraph per phase of the (ring offset, history buffer) cycle
-    void* pin_in;                 // [2][H]
-    void* pin_out;                // [n_out][H] samples + [2][K] status words
-    int period;                   // hops after which (ring_off, cur) repeat; 0 = graphs off
-    // whole-signal path (apv_process_signal): a second set of the hop's spectra, a second stream and four events, so
-    // that the front half (FIR + analysis) of hop h+1 runs beside the back half (GEVD + synthesis) of hop h
-    void* X1[4];                  // like X, tspec, inspec: hops alternate between the two sets
-    void* tspec1[2];
-    void* inspec1;
-    hipStream_t front;            // front-half stream; the back half stays on the handle's stream
-    hipEvent_t ev_front[2];       // set p filled by the front half
-    hipEvent_t ev_back[2];        // set p released by the back half
-    hipEvent_t ev_chunk[2];       // chunk c & 1 of the pinned staging complete
-    // ... and a tail stream with second output-spectra and result buffers: synthesis and copy back of hop h run beside
-    // the joint diagonalisation of hop h+1 instead of in front of it
-    void* outspec1;               // like outspec, out; hops alternate between the two
-    void* out1;
-    hipStream_t tail;
-    hipEvent_t ev_copied[2];      // result buffer b copied to the host
-    void* sig_in;                 // pinned [2][chunk][2][H]
-    void* sig_out;                // pinned [2][chunk] hop results (samples [n_out][H] + status words [2][K] each)
-    int sig_chunk;                // hops per half of the pinned staging
-    // K1 by fast convolution (fir_F > 0): spectra of the zero-padded impulse responses and of the two input histories
-    // of the hop, in the front-end precision
-    int fir_F;                    // segment length, 0 = direct form
-    int fir_np;                   // partitions of the uniformly partitioned form (responses too long for one segment), else 1
-    int keep;                     // input samples the histories keep in front of the hop: P - 1, or fir_np H when partitioned
-    void* rirspec[2];             // [fir_np][C][fir_F/2 + 1] complex, zone A, zone B
-    void* trirspec[2];            // [fir_np][M][fir_F/2 + 1]
-    void* xspec;                  // [fir_np][2][fir_F/2 + 1]
-    void* xspec_chunk;            // [sig_chunk][2][fir_F/2 + 1]: whole-signal path, the spectra of a staged chunk in one launch
-    long hop;                     // hops processed
-    long not_converged;           // hops in which some bin hit the sweep cap (status 2)
-    // chunked whole-signal path (process_signal_chunked_t): the FRONT half of a whole chunk of hops is three launches (input side,
-    // K1, analysis) into linear buffers and one spectra set per hop; the back halves of consecutive hops alternate between two
-    // streams with their own filters, output spectra and result buffers.  Everything is allocated at the path's first call.
-    int ck_RL;                    // row length of the linear buffers: N - H + sig_chunk H (0 = not set up)
-    void* ck_resp[2][4];          // [chunk parity][path]: [C][RL]
-    void* ck_tresp[2][2];         // [M][RL]
-    void* ck_in[2];               // [2][RL]
-    void* ck_X[4];                // [2 sig_chunk][K][C]: set (parity, i) = parity sig_chunk + i
-    void* ck_tspec[2];            // [2 sig_chunk][K][M]
-    void* ck_inspec;              // [2 sig_chunk][2][K]
-    void* ck_w[CK_NB - 1][2];     // [K][nV][L] per zone: filters of back streams 1 ... (back stream 0 uses w, lam)
-    void* ck_lam[CK_NB - 1][2];
-    void* ck_wall[2];             // [sig_chunk][K][nV][L] per zone: the filters of every hop of a chunk whose joint diagonalisations are ONE launch
-    void* ck_lamall[2];           // [sig_chunk][K][L]
-    void* ck_spill[CK_NB - 1];    // per-bin scratch of the joint diagonalisation (orders 33..64) for back streams 1 ...: two hops' workgroups for
-                                  // the same bin run at once, each parks its state in its own stream's slot (back stream 0 uses d_Lspill)
-    hipStream_t ck_back[CK_NB - 1];
-    void* ck_pin_in;              // pinned [CK_NS][sig_chunk][2][H]: the host stages chunk c + 1 while chunks c - 1 and c are in flight
-    void* ck_pin_out;             // pinned [CK_NS][sig_chunk] hop results
-    hipEvent_t ck_done[CK_NS];    // the chunk in staging slot q has been copied back
-    void* ck_out;                 // [2 sig_chunk] hop results (samples [n_out][H] + status words [2][K]): one slot per hop of two chunks
-    void* ck_ospec;               // [2 sig_chunk][n_out][K] output spectra, likewise
-    hipEvent_t ck_backdone[2][CK_NB]; // [chunk parity][back stream]: that stream has read the parity's spectra sets for the last time
-    hipEvent_t ck_k3[CK_NB];      // [back stream]: output spectra written (the tail stream starts the synthesis there)
-    // work space of apv_stream_get_statistics (R_B, R_D, r, U, w, lam, spill, status), allocated at its first call and kept
-    void* stat_ws[10];
-    size_t stat_spill_bytes;
-    // responses reassigned between hops (apv_stream_set_rirs): the tails still to be added to K1's output, and a channel-major
-    // copy of one bank for its fast-convolution spectra; allocated at the first update
-    FirLive live;
-    void* live_cm;
-    // statistics window (apv_stream_set_stat_hops, kernels_statwin.hip); win_T = 1: off, the fused single-block update runs
-    int win_T;                    // hops in the window
-    int win_c128;                 // ring and window sums are c128 (float64 joint diagonalisation), else c64
-    void* win_ring[2];            // per zone program: [win_T][K][2 L^2 + L] Gram matrices of the last hops
-    void* win_RB[2];              // per zone program: the window sums the joint diagonalisation reads, [K][L][L], [K][L][L], [K][L]
-    void* win_RD[2];
-    void* win_r[2];
-    int32_t* win_ctr;             // device words {head, fill}: read by the hop's statistics kernel, advanced behind it
-    int win_fill_host;            // the host's copy of fill (hops in the window before the next one), kept in step by run_hop and by
-                                  // the state "stat_window_fill".  Only win_low_rank reads it (which KERNEL solves an order-64 hop):
-                                  // the ring position itself never enters a launch from the host
-    // exponentially forgetting statistics (apv_stream_set_stat_forgetting): R <- fg_beta R + G per hop.  win_T stays 1; the
-    // accumulator is the one slot win_ring[z] [K][2 L^2 + L], and win_c128, win_RB / win_RD / win_r, win_tm serve as above
-    double fg_beta;               // 0: off
-    int fg_no_gevd64;             // GevdParams::no_gevd64 of every hop and of apv_stream_get_statistics: see apv_stream_init
-    // filter-length constraint (apv_stream_set_filter_taps, kernels_constrain.hip); taps = 0: off, nothing below exists
-    int taps;                     // J
-    void* wtaps[2];               // per zone program: [nV][J][L] real, the J taps of the hop's projected filters (precision of w)
-    StageTimer cf_tm;             // APV_FILTER_CONSTRAINT_TIMING (tools/bench_filter_constraint.py): the projection
-    // FIR synthesis (apv_stream_set_synthesis, kernels_firsynth.hip); fir_synth = 0: off, nothing below exists
-    int fir_synth;
-    int fs_ref, fs_delay;         // the target paths: column reference_index_A, modeling_delay samples late
-    void* fs_taps[2];             // per zone program that runs: [nV][J][L], the taps the next hop fades from (precision of w)
-    void* fs_hist[2][2];          // [buf][signal][J - 1]: the newest input samples; buf = cur, like the input histories of K1
-    StageTimer fs_tm;             // APV_FIR_SYNTHESIS_TIMING (tools/bench_fir_synthesis.py): the synthesis launch
-    // chunked whole-signal path of a constrained stream (process_signal_chunked_t; allocated by chunk_prepare for such a stream only)
-    void* ck_taps[2];             // per zone program: [sig_chunk][nV][J][L], the taps of every hop of a chunk (ONE projection launch)
-    void* ck_xrow[2][2];          // [chunk parity][signal]: [J - 1 samples before the chunk | sig_chunk H samples of the chunk], FIR synthesis
-    hipEvent_t ck_wallfree;       // hop-by-hop regime: the tail stream has read ck_wall / ck_taps of a chunk for the last time
-    // evaluation stage (apv_stream_set_evaluation, kernels_streameval.hip); ev_on = 0: off, nothing below exists
-    int ev_on;
-    int ev_Pv, ev_Mv, ev_E, ev_Z; // response taps, validation microphones, evaluated ranks, zone programs that run
-    int ev_sets, ev_nhist;        // pressure sets ev_Z (2 ev_E + 1), evaluated groups ev_Z (ev_E + 1)
-    double* ev_rv[2];             // validation responses of zone A, zone B: [Pv][L][Mv]
-    int32_t* ev_map;              // [ev_sets][4]: {group of the result buffer, history slot, response bank, 0}
-    int32_t* ev_hsrc;             // [ev_nhist]: group of the result buffer each history slot follows
-    void* ev_hist[2];             // [buf][ev_nhist][Pv - 1][L]: the newest output samples; buf = cur, like fs_hist
-    double* ev_p;                 // [ev_sets][H][Mv]: the pressures of the last hop
-    double* ev_tot;               // [ev_Z][3 ev_E + 1][Mv]: the energies summed over the hops
-    double* ev_rec;               // [ev_cap] slots of that shape: the energies of each hop of the last call (grow-only)
-    unsigned long long* ev_ctl;   // device words {ev_rec, ev_cap, slot counter of parity 0, of parity 1}: see kernels_streameval.hip
-    int ev_cap, ev_nrec;          // slots ev_rec holds; hops of the last call (the slots that are valid)
-    // per-bin evaluation spectra (apv_stream_set_evaluation_spectra, kernels_evalspec.hip); es_on = 0: off, nothing below exists
-    int es_on;
-    double* es_ring;              // [ev_sets ev_Mv][N] float64 ring of the pressures, channel-major, at the stream's ring_off
-    void* es_spec;                // [K][ev_sets ev_Mv] complex128: the hop's spectra, bin-major scratch
-    double* es_tot;               // [ev_Z][3 ev_E + 1][K][ev_Mv]: |P|^2 summed over the hops
-    // perceptual detectability of the evaluated pressures (apv_stream_set_evaluation_detectability, kernels_evaldetect.hip), on
-    // es_spec; ed_on = 0: off, nothing below exists
-    int ed_on;
-    int ed_C;                     // channels of the model
-    double ed_Cs, ed_Ca, ed_Leff;
-    double* ed_G2T;               // [ed_C][K]: the squared channel responses, channel-major
-    double* ed_quiet;             // [K]: the curve of a silent masker (read with one zone program), formed once
-    double* ed_curves;            // [K][ev_Z ev_Mv]: the hop's squared weighting curves
-    double* ed_part;              // [chunks][ev_Z][2 ev_E][ev_Mv]: partial sums of the hop
-    double* ed_tot;               // [ev_Z][6 ev_E][ev_Mv]: per program sum, max and count of D > 1 of the error, then of the leak
-    double* ed_rec;               // [ed_cap] slots [ev_Z][2 ev_E][ev_Mv]: the values of each hop of the last call (grow-only, like ev_rec)
-    unsigned long long* ed_ctl;   // device words {ed_rec, ed_cap, hops of the call so far}: see kernels_evaldetect.hip
-    int ed_cap;                   // slots ed_rec holds (ev_nrec of them are valid)
-    int32_t sched[2];             // state "signal_schedule": hops of the last whole-signal call {through chunk launches, hop by hop}
-    StageTimer win_tm;            // APV_STAT_WINDOW_TIMING (tools/bench_stat_window.py): the statistics launch
-    std::vector<hipGraphExec_t> execs;
-    std::vector<int32_t> h_status;
-    ApvOwned own;                 // every buffer, pinned block, event and stream above: made through it, freed by it
-};
-
 namespace {
-
-#define HIPCHK(h, call, what)                                                            \
-    do {                                                                                 \
-        hipError_t _e = (call);                                                          \
-        if (_e != hipSuccess) return apv_fail(h, APV_ERR_HIP, std::string(what) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-#define SCHK(h, call) HIPCHK(h, call, #call)
 
 // the same inside the whole-signal path, whose callers add how far the call got (signal_bail)
 #define SIGCHK(h, call) HIPCHK(h, call, "apv_process_signal")
@@ -244,9 +54,6 @@ int upload_as(apv_handle* h, void* dst, const std::vector<double>& src) {
 int upload(apv_handle* h, int f64, void* dst, const std::vector<double>& src) {
     return f64 ? upload_as<double>(h, dst, src) : upload_as<float>(h, dst, src);
 }
-
-size_t wsz(const apv_handle* h) { return h->cfg.out_c128 ? 16 : 8; }
-size_t lsz(const apv_handle* h) { return h->cfg.out_c128 ? 8 : 4; }
 
 // bytes of one hop's result: [n_out][H] samples and, behind them, the [2][K] status words
 inline size_t hop_out_bytes(const apv_stream* s) { return s->esz * (size_t)s->n_out * s->H; }
@@ -2446,278 +2253,6 @@ int apv_get_effort(apv_handle* h, int32_t zone, double* h_effort, int32_t* h_ran
     // slot's rank
     if (h_rank)
         for (size_t k = 0; k < K; ++k) h_rank[k] = (h_rank[k] < 0 || (size_t)h_rank[k] >= nV) ? 0 : h->rank_list[(size_t)h_rank[k]];
-    return APV_OK;
-}
-
-// Named state arrays, as stored on the device: real samples are float32 (float64 with the float64 front-end),
-// spectra the matching complex type; rings are returned in LOGICAL order:
-//   "response<p>"     [C][N]           "target_response<z>" [M][N]       "input_block" [2][N]
-//   "input_history<g>" [keep+H] (keep = P-1; fir_np H when K1 is partitioned: apv_state_bytes tells)   "out_overlap" [n_out][N]
-//   "spectra<p>"      [K][C] complex   "target_spectra<z>"  [K][M] complex   "input_spectrum" [2][K] complex
-//   "weights<z>"      [K][M]
-//   "w_A" / "w_B"     [K][nV][L] c64|c128        "lambda_A" / "lambda_B" [K][L] f32|f64   (cfg.out_c128)
-//   "fir_correction<p>" [C][P-1]   "target_fir_correction<z>" [M][P-1]   pending correction tails (apv_stream_set_rirs): zeros in a
-//                                  stream that was never updated; handled by apv_live_state
-//   "stat_window<z>" [T][K][2 L^2 + L] complex, "stat_window_fill" int32   the statistics window (apv_stream_set_stat_hops), see win_index
-//   "stat_forget<z>" [K][2 L^2 + L] complex   the forgetting accumulator (apv_stream_set_stat_forgetting), see win_index
-//   "w_time_A" / "w_time_B" [nV][J][L] f32|f64 (cfg.out_c128)   the J taps of the last hop's projected filters; only a stream with
-//                                  the filter-length constraint (apv_stream_set_filter_taps) and only zone programs that run have them
-//   "filter_constraint_kernel_ms" {sum, count} of the timed projections (APV_FILTER_CONSTRAINT_TIMING), read-only
-//   "fir_synth_taps_A" / "fir_synth_taps_B" [nV][J][L] f32|f64 (cfg.out_c128)   the taps the next hop's FIR synthesis fades from;
-//   "fir_synth_history<g>" [J-1]   the newest samples of input signal g; both only with apv_stream_set_synthesis(h, APV_SYNTH_FIR)
-//   "fir_synthesis_kernel_ms" {sum, count} of the timed synthesis launches (APV_FIR_SYNTHESIS_TIMING), read-only
-//   "eval_pressure" [sets][H][Mv] f64, "eval_hops" [hops of the last call][Z][3 E + 1][Mv] f64 (both read-only), "eval_totals"
-//                                  [Z][3 E + 1][Mv] f64, "eval_history" [Z (E + 1)][Pv - 1][L] samples: only a stream with
-//                                  apv_stream_set_evaluation has them (see include/apvast_hip.h)
-//   "eval_spectra" [Z][3 E + 1][K][Mv] f64, "eval_ring" [sets Mv][N] f64 (a ring: logical order): only a stream with
-//                                  apv_stream_set_evaluation_spectra has them
-//   "eval_detect" [Z][6 E][Mv] f64, "eval_detect_hops" [hops of the last call][Z][2 E][Mv] f64 (read-only): only a stream with
-//                                  apv_stream_set_evaluation_detectability has them
-//   "signal_schedule" int32 {hops of the last apv_process_signal* call that went through chunk launches, hops of it that went hop by
-//                                  hop}, read-only; {0, 0} before the first such call, untouched by the per-hop calls
-static int live_index(const char* name) {
-    const std::string n(name);
-    if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
-    if (n.size() == 22 && n.rfind("target_fir_correction", 0) == 0 && (n[21] == '0' || n[21] == '1')) return 4 + n[21] - '0';
-    return -1;
-}
-
-// "stat_window<z>" [win_T][K][2 L^2 + L] complex of the ring's precision, slots in the order of age (oldest first, zeros beyond the fill
-// level): 0 / 1; "stat_window_fill" one int32: 2; "stat_window_kernel_ms" {sum, count} of the timed statistics launches
-// (APV_STAT_WINDOW_TIMING, read-only): 3.  Only a stream with a statistics window has them.  A forgetting stream has
-// "stat_forget<z>" [K][2 L^2 + L], its accumulator: 4 / 5, and "stat_window_kernel_ms" for its own statistics launch.
-static int win_index(const apv_stream* s, const char* name) {
-    const std::string n(name);
-    if (s->fg_beta > 0.0) {
-        if ((n == "stat_forget0" || n == "stat_forget1") && s->win_ring[n.back() - '0']) return 4 + (n.back() - '0');
-        return n == "stat_window_kernel_ms" ? 3 : -1;
-    }
-    if (s->win_T <= 1) return -1;
-    if ((n == "stat_window0" || n == "stat_window1") && s->win_ring[n.back() - '0']) return n.back() - '0';
-    if (n == "stat_window_fill") return 2;
-    if (n == "stat_window_kernel_ms") return 3;
-    return -1;
-}
-
-static size_t win_state_bytes(const apv_stream* s, int j) {
-    if (j == 2) return sizeof(int32_t);
-    if (j == 3) return 2 * sizeof(double);
-    if (j >= 4) return (size_t)s->K * apv_statwin_slot_elems(s->L) * (s->win_c128 ? 16 : 8);
-    return (size_t)s->win_T * s->K * apv_statwin_slot_elems(s->L) * (s->win_c128 ? 16 : 8);
-}
-
-static int win_state(apv_handle* h, int j, void* h_buf, size_t bytes, bool get) {
-    apv_stream* s = h->st;
-    if (bytes != win_state_bytes(s, j)) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
-    SCHK(h, hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    SCHK(h, hipStreamSynchronize(st));
-    const int T = s->win_T;
-    if (j == 3) {
-        if (!get) return apv_fail(h, APV_ERR_STATE, "stat_window_kernel_ms is read-only");
-        std::memcpy(h_buf, s->win_tm.ms, sizeof(s->win_tm.ms));
-        return APV_OK;
-    }
-    if (j >= 4) {
-        if (get) SCHK(h, hipMemcpyAsync(h_buf, s->win_ring[j - 4], bytes, hipMemcpyDeviceToHost, st));
-        else SCHK(h, hipMemcpyAsync(s->win_ring[j - 4], h_buf, bytes, hipMemcpyHostToDevice, st));
-        SCHK(h, hipStreamSynchronize(st));
-        return APV_OK;
-    }
-    int32_t ctr[2];
-    SCHK(h, hipMemcpyAsync(ctr, s->win_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
-    SCHK(h, hipStreamSynchronize(st));
-    if (j == 2) {
-        if (get) {
-            *static_cast<int32_t*>(h_buf) = ctr[1];
-            return APV_OK;
-        }
-        // a restored window lies in slots 0 .. fill - 1 (see below): the next hop goes to slot fill mod T
-        const int32_t fill = *static_cast<const int32_t*>(h_buf);
-        if (fill < 0 || fill > T) return apv_fail(h, APV_ERR_STATE, "stat_window_fill out of 0..statistics hops");
-        const int32_t nw[2] = {fill % T, fill};
-        SCHK(h, hipMemcpyAsync(s->win_ctr, nw, sizeof(nw), hipMemcpyHostToDevice, st));
-        SCHK(h, hipStreamSynchronize(st));
-        s->win_fill_host = fill;
-        return APV_OK;
-    }
-    const size_t slot = bytes / T;
-    char* ring = static_cast<char*>(s->win_ring[j]);
-    if (!get) {
-        // slots in the order of age into slots 0, 1, ...: where a ring stands does not enter the window sum
-        SCHK(h, hipMemcpyAsync(ring, h_buf, bytes, hipMemcpyHostToDevice, st));
-        SCHK(h, hipStreamSynchronize(st));
-        return APV_OK;
-    }
-    const int head = ctr[0], fill = ctr[1];
-    std::memset(h_buf, 0, bytes);
-    for (int a = 0; a < fill; ++a) {
-        const int from = ((head - fill + a) % T + T) % T;
-        SCHK(h, hipMemcpyAsync(static_cast<char*>(h_buf) + (size_t)a * slot, ring + (size_t)from * slot, slot, hipMemcpyDeviceToHost, st));
-    }
-    SCHK(h, hipStreamSynchronize(st));
-    return APV_OK;
-}
-
-static int state_lookup(apv_handle* h, const char* name, void** dptr, size_t* bytes, int* ring_rows) {
-    apv_stream* s = h->st;
-    *ring_rows = 0;
-    const std::string n(name);
-    const size_t N = s->N, K = s->K, C = s->C, M = s->M, L = s->L, e1 = s->esz, e2 = 2 * s->esz;
-    if (n.rfind("response", 0) == 0 && n.size() == 9 && n[8] >= '0' && n[8] <= '3') {
-        *dptr = s->resp[n[8] - '0']; *bytes = C * N * e1; *ring_rows = (int)C; return APV_OK; }
-    if (n == "target_response0" || n == "target_response1") {
-        *dptr = s->tresp[n.back() - '0']; *bytes = M * N * e1; *ring_rows = (int)M; return APV_OK; }
-    if (n == "input_block") { *dptr = s->inblk; *bytes = 2 * N * e1; *ring_rows = 2; return APV_OK; }
-    if (n == "input_history0" || n == "input_history1") {
-        *dptr = s->xhist[s->cur][n.back() - '0']; *bytes = (size_t)(s->keep + s->H) * e1; return APV_OK; }
-    if (n == "out_overlap") { *dptr = s->outov; *bytes = (size_t)s->n_out * N * e1; return APV_OK; }
-    if (n.rfind("spectra", 0) == 0 && n.size() == 8 && n[7] >= '0' && n[7] <= '3') {
-        *dptr = s->X[n[7] - '0']; *bytes = K * C * e2; *ring_rows = s->xg > 1 ? -1 : 0; return APV_OK; }      // -1: grouped on the device
-    if (n == "target_spectra0" || n == "target_spectra1") { *dptr = s->tspec[n.back() - '0']; *bytes = K * M * e2; return APV_OK; }
-    if (n == "input_spectrum") { *dptr = s->inspec; *bytes = 2 * K * e2; return APV_OK; }
-    if ((n == "weights0" || n == "weights1") && s->nch > 0) { *dptr = s->Wgt[n.back() - '0']; *bytes = K * M * e1; return APV_OK; }
-    if (n == "w_A" || n == "w_B") { *dptr = s->w[n == "w_B"]; *bytes = K * s->nV * L * wsz(h); return APV_OK; }
-    if (n == "lambda_A" || n == "lambda_B") { *dptr = s->lam[n == "lambda_B"]; *bytes = K * L * lsz(h); return APV_OK; }
-    if ((n == "w_time_A" || n == "w_time_B") && s->wtaps[n == "w_time_B"]) {
-        *dptr = s->wtaps[n == "w_time_B"]; *bytes = (size_t)s->nV * s->taps * L * lsz(h); return APV_OK; }
-    if ((n == "fir_synth_taps_A" || n == "fir_synth_taps_B") && s->fs_taps[n.back() == 'B']) {
-        *dptr = s->fs_taps[n.back() == 'B']; *bytes = (size_t)s->nV * s->taps * L * lsz(h); return APV_OK; }
-    if ((n == "fir_synth_history0" || n == "fir_synth_history1") && s->fir_synth) {
-        *dptr = s->fs_hist[s->cur][n.back() - '0']; *bytes = (size_t)(s->taps - 1) * e1; return APV_OK; }
-    if (s->ev_on) {
-        const size_t slot = sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * s->ev_Mv;
-        if (n == "eval_pressure") { *dptr = s->ev_p; *bytes = sizeof(double) * (size_t)s->ev_sets * s->H * s->ev_Mv; return APV_OK; }
-        if (n == "eval_hops") { *dptr = s->ev_rec; *bytes = slot * (size_t)s->ev_nrec; return APV_OK; }
-        if (n == "eval_totals") { *dptr = s->ev_tot; *bytes = slot; return APV_OK; }
-        if (n == "eval_history") { *dptr = s->ev_hist[s->cur]; *bytes = (size_t)s->ev_nhist * (s->ev_Pv - 1) * L * e1; return APV_OK; }
-    }
-    if (s->es_on) {
-        if (n == "eval_spectra") { *dptr = s->es_tot; *bytes = sizeof(double) * (size_t)s->ev_Z * (3 * s->ev_E + 1) * K * s->ev_Mv; return APV_OK; }
-        if (n == "eval_ring") {
-            *dptr = s->es_ring; *bytes = sizeof(double) * (size_t)s->ev_sets * s->ev_Mv * N; *ring_rows = s->ev_sets * s->ev_Mv; return APV_OK; }
-    }
-    if (s->ed_on) {
-        const size_t slot = sizeof(double) * (size_t)s->ev_Z * 2 * s->ev_E * s->ev_Mv;
-        if (n == "eval_detect") { *dptr = s->ed_tot; *bytes = 3 * slot; return APV_OK; }
-        if (n == "eval_detect_hops") { *dptr = s->ed_rec; *bytes = slot * (size_t)s->ev_nrec; return APV_OK; }
-    }
-    return apv_fail(h, APV_ERR_STATE, std::string("unknown state name: ") + name);
-}
-
-// read-only states kept on the host: the timers of the projection and of the FIR synthesis, the schedule of the last whole-signal call
-static const void* host_state(const apv_stream* s, const char* name, size_t* bytes) {
-    const std::string n(name);
-    if (s->taps > 0 && n == "filter_constraint_kernel_ms") { *bytes = sizeof(s->cf_tm.ms); return s->cf_tm.ms; }
-    if (s->fir_synth && n == "fir_synthesis_kernel_ms") { *bytes = sizeof(s->fs_tm.ms); return s->fs_tm.ms; }
-    if (n == "signal_schedule") { *bytes = sizeof(s->sched); return s->sched; }
-    return nullptr;
-}
-
-int apv_state_bytes(apv_handle* h, const char* name, size_t* bytes) {
-    if (!h || !h->st || !name || !bytes) return apv_fail(h, APV_ERR_ARG, "null argument / no stream");
-    const int j = live_index(name);
-    if (j >= 0) {
-        *bytes = h->st->esz * (size_t)(j < 4 ? h->st->C : h->st->M) * (size_t)std::max(h->st->P - 1, 1);
-        return APV_OK;
-    }
-    const int wj = win_index(h->st, name);
-    if (wj >= 0) {
-        *bytes = win_state_bytes(h->st, wj);
-        return APV_OK;
-    }
-    if (host_state(h->st, name, bytes)) return APV_OK;
-    void* d; int rr;
-    return state_lookup(h, name, &d, bytes, &rr);
-}
-
-int apv_get_state(apv_handle* h, const char* name, void* h_dst, size_t bytes) {
-    if (!h || !h->st || !name || !h_dst) return apv_fail(h, APV_ERR_ARG, "null argument / no stream");
-    if (live_index(name) >= 0) {
-        apv_stream* s = h->st;
-        SCHK(h, hipSetDevice(h->device));
-        return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, h_dst, bytes, true, h->stream);
-    }
-    if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), h_dst, bytes, true);
-    size_t host_bytes;
-    if (const void* src = host_state(h->st, name, &host_bytes)) {
-        if (bytes != host_bytes) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
-        std::memcpy(h_dst, src, host_bytes);
-        return APV_OK;
-    }
-    void* d; size_t need; int rr;
-    int rc = state_lookup(h, name, &d, &need, &rr);
-    if (rc != APV_OK) return rc;
-    if (bytes != need) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
-    if (need == 0) return APV_OK;                            // "eval_history" with Pv = 1, "eval_hops" before the first hop
-    SCHK(h, hipSetDevice(h->device));
-    if (rr == 0) {
-        SCHK(h, hipMemcpyAsync(h_dst, d, need, hipMemcpyDeviceToHost, h->stream));
-        SCHK(h, hipStreamSynchronize(h->stream));
-        return APV_OK;
-    }
-    if (rr < 0) {
-        // control-point spectra in the grouped layout [Kp / g][C][g]: the caller gets them bin-major [K][C], as documented
-        const apv_stream* s = h->st;
-        const size_t K = s->K, C = s->C, g = s->xg, e2 = 2 * s->esz;
-        std::vector<char> tmp((size_t)s->Kp * C * e2);
-        SCHK(h, hipMemcpyAsync(tmp.data(), d, tmp.size(), hipMemcpyDeviceToHost, h->stream));
-        SCHK(h, hipStreamSynchronize(h->stream));
-        char* out = (char*)h_dst;
-        for (size_t k = 0; k < K; ++k)
-            for (size_t c = 0; c < C; ++c)
-                std::memcpy(out + (k * C + c) * e2, tmp.data() + ((k / g) * g * C + c * g + k % g) * e2, e2);
-        return APV_OK;
-    }
-    // ring: rotate rows into logical order (rows of N elements: the pressure ring's are float64 whatever the stream's precision)
-    const size_t N = h->st->N, off = h->st->ring_off, e1 = need / ((size_t)rr * N);
-    std::vector<char> tmp(need);
-    SCHK(h, hipMemcpyAsync(tmp.data(), d, need, hipMemcpyDeviceToHost, h->stream));
-    SCHK(h, hipStreamSynchronize(h->stream));
-    char* out = (char*)h_dst;
-    for (int r = 0; r < rr; ++r) {
-        // logical [0, N - off) = physical [off, N); logical [N - off, N) = physical [0, off)
-        std::memcpy(out + ((size_t)r * N) * e1, tmp.data() + ((size_t)r * N + off) * e1, (N - off) * e1);
-        std::memcpy(out + ((size_t)r * N + (N - off)) * e1, tmp.data() + ((size_t)r * N) * e1, off * e1);
-    }
-    return APV_OK;
-}
-
-int apv_set_state(apv_handle* h, const char* name, const void* h_src, size_t bytes) {
-    if (!h || !h->st || !name || !h_src) return apv_fail(h, APV_ERR_ARG, "null argument / no stream");
-    if (live_index(name) >= 0) {
-        apv_stream* s = h->st;
-        SCHK(h, hipSetDevice(h->device));
-        SCHK(h, hipStreamSynchronize(h->stream));
-        return apv_live_state(h, s->live, live_index(name), s->P, s->H, s->C, s->M, s->esz, const_cast<void*>(h_src), bytes, false,
-                              h->stream);
-    }
-    if (win_index(h->st, name) >= 0) return win_state(h, win_index(h->st, name), const_cast<void*>(h_src), bytes, false);
-    if (std::string(name) == "signal_schedule") return apv_fail(h, APV_ERR_STATE, "signal_schedule is read-only");
-    if (h->st->ev_on && (std::string(name) == "eval_pressure" || std::string(name) == "eval_hops"))
-        return apv_fail(h, APV_ERR_STATE, std::string(name) + " is read-only");
-    if (h->st->ed_on && std::string(name) == "eval_detect_hops") return apv_fail(h, APV_ERR_STATE, "eval_detect_hops is read-only");
-    void* d; size_t need; int rr;
-    int rc = state_lookup(h, name, &d, &need, &rr);
-    if (rc != APV_OK) return rc;
-    if (bytes != need) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
-    if (need == 0) return APV_OK;
-    SCHK(h, hipSetDevice(h->device));
-    if (rr < 0) return apv_fail(h, APV_ERR_STATE, "the control-point spectra are recomputed by every hop and cannot be set");
-    if (rr == 0) {
-        SCHK(h, hipMemcpyAsync(d, h_src, need, hipMemcpyHostToDevice, h->stream));
-        SCHK(h, hipStreamSynchronize(h->stream));
-        return APV_OK;
-    }
-    const size_t N = h->st->N, off = h->st->ring_off, e1 = need / ((size_t)rr * N);
-    std::vector<char> tmp(need);
-    const char* in = (const char*)h_src;
-    for (int r = 0; r < rr; ++r) {
-        std::memcpy(tmp.data() + ((size_t)r * N + off) * e1, in + ((size_t)r * N) * e1, (N - off) * e1);
-        std::memcpy(tmp.data() + ((size_t)r * N) * e1, in + ((size_t)r * N + (N - off)) * e1, off * e1);
-    }
-    SCHK(h, hipMemcpyAsync(d, tmp.data(), need, hipMemcpyHostToDevice, h->stream));
-    SCHK(h, hipStreamSynchronize(h->stream));               // tmp goes out of scope
     return APV_OK;
 }
 

@@ -18,6 +18,7 @@
 // with an ABSOLUTE 1e-7 (apvast.py:23) against entries of order 1e-3, so float statistics would not survive.
 #include "apv_internal.h"
 #include "apv_owned.h"
+#include "state_layout.h"
 
 #include <chrono>
 #include <cstdio>
@@ -1045,14 +1046,6 @@ int apv_bb_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
     return APV_OK;
 }
 
-static int bb_live_index(const char* name) {
-    const std::string n(name);
-    if (n.size() == 15 && n.rfind("fir_correction", 0) == 0 && n[14] >= '0' && n[14] <= '3') return n[14] - '0';
-    if (n.size() == 22 && n.rfind("target_fir_correction", 0) == 0 && (n[21] == '0' || n[21] == '1')) return 4 + n[21] - '0';
-    return -1;
-}
-
-
 // state: "response<p>" [C][N], "target_response<z>" [M][N], "input_block" [2][N] (rings, logical order); "R<q>" [n][n]
 // (AA, BB, AB, BA), "r" [2][n], "lambda" [2][n], "w" [2][V][n], "U<z>" [n][n] (columns = eigenvectors, descending),
 // "stats<p>" [C][S], "target_stats<z>" [M][S] (rings, logical order); and what a bit-for-bit resume also needs:
@@ -1107,10 +1100,10 @@ static int bb_complete_eigenpairs(apv_handle* h) {
 
 int apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t count) {
     if (!h || !h->bb || !name || !h_dst) return apv_fail(h, APV_ERR_ARG, "null argument / broadband stream not initialised");
-    if (bb_live_index(name) >= 0) {
+    if (apv_live_index(name) >= 0) {
         apv_bb* s = h->bb;
         BCHK(h, hipSetDevice(h->device));
-        return apv_live_state(h, s->live, bb_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), h_dst, sizeof(double) * count,
+        return apv_live_state(h, s->live, apv_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), h_dst, sizeof(double) * count,
                               true, h->stream);
     }
     double* d; size_t need; int rows, len, off;
@@ -1129,18 +1122,17 @@ int apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t coun
     std::vector<double> tmp(need);
     BCHK(h, hipMemcpyAsync(tmp.data(), d, sizeof(double) * need, hipMemcpyDeviceToHost, h->stream));
     BCHK(h, hipStreamSynchronize(h->stream));
-    for (int r = 0; r < rows; ++r)
-        for (int t = 0; t < len; ++t) h_dst[(size_t)r * len + t] = tmp[(size_t)r * len + (t + off) % len];
+    ring_to_logical(h_dst, tmp.data(), rows, len, off, sizeof(double));
     return APV_OK;
 }
 
 int apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size_t count) {
     if (!h || !h->bb || !name || !h_src) return apv_fail(h, APV_ERR_ARG, "null argument / broadband stream not initialised");
-    if (bb_live_index(name) >= 0) {
+    if (apv_live_index(name) >= 0) {
         apv_bb* s = h->bb;
         BCHK(h, hipSetDevice(h->device));
         BCHK(h, hipStreamSynchronize(h->stream));
-        return apv_live_state(h, s->live, bb_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), const_cast<double*>(h_src),
+        return apv_live_state(h, s->live, apv_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), const_cast<double*>(h_src),
                               sizeof(double) * count, false, h->stream);
     }
     double* d; size_t need; int rows, len, off;
@@ -1154,8 +1146,7 @@ int apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size_
         return APV_OK;
     }
     std::vector<double> tmp(need);
-    for (int r = 0; r < rows; ++r)
-        for (int t = 0; t < len; ++t) tmp[(size_t)r * len + (t + off) % len] = h_src[(size_t)r * len + t];
+    ring_from_logical(tmp.data(), h_src, rows, len, off, sizeof(double));
     BCHK(h, hipMemcpyAsync(d, tmp.data(), sizeof(double) * need, hipMemcpyHostToDevice, h->stream));
     BCHK(h, hipStreamSynchronize(h->stream));               // tmp goes out of scope
     return APV_OK;

@@ -4,6 +4,7 @@ state keys and the C ABI's declarations."""
 import inspect
 import os
 import re
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -116,8 +117,13 @@ def test_state_keys_and_accessor():
     others = (apvast._SB_STATE + apvast._BB_STATE + apvast._LIVE_STATE + apvast._WIN_STATE + apvast._FORGET_STATE + apvast._FIR_STATE
               + apvast._EVAL_STATE)
     assert not set(apvast._EVALSPEC_STATE) & set(others)
-    src = inspect.getsource(apvast.get_state) + inspect.getsource(apvast.set_state)
-    assert src.count("self._evaluation_spectra") == 2     # both places add the keys only behind the object's own keyword
+    # get_state and set_state take the keys only in subband mode and behind the object's own keyword
+    rows = [r for r in apvast._STATE_ROWS if r.key in apvast._EVALSPEC_STATE]
+    flags = lambda **kw: [bool(f(SimpleNamespace(**kw))) for r in rows for f in (r.accepts, r.reports or r.accepts)]
+    assert len(rows) == len(apvast._EVALSPEC_STATE)
+    assert not any(flags(mode="subband", _evaluation_spectra=False))
+    assert all(flags(mode="subband", _evaluation_spectra=True))
+    assert not any(flags(mode="broadband", _evaluation_spectra=True))
     assert callable(apvast.evaluation_spectra)
 
 

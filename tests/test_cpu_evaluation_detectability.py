@@ -4,6 +4,7 @@ condition its bound must meet) and evaluation.detectability_metrics."""
 import inspect
 import os
 import re
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -60,8 +61,13 @@ def test_state_key_and_accessors():
     others = (apvast._SB_STATE + apvast._BB_STATE + apvast._LIVE_STATE + apvast._WIN_STATE + apvast._FORGET_STATE + apvast._FIR_STATE
               + apvast._EVAL_STATE + apvast._EVALSPEC_STATE)
     assert not set(apvast._EVALDETECT_STATE) & set(others)
-    src = inspect.getsource(apvast.get_state) + inspect.getsource(apvast.set_state)
-    assert src.count("self._evaluation_detectability") == 2   # both places add the key only behind the object's own keyword
+    # get_state and set_state take the key only in subband mode and behind the object's own keyword
+    rows = [r for r in apvast._STATE_ROWS if r.key in apvast._EVALDETECT_STATE]
+    flags = lambda **kw: [bool(f(SimpleNamespace(**kw))) for r in rows for f in (r.accepts, r.reports or r.accepts)]
+    assert len(rows) == len(apvast._EVALDETECT_STATE)
+    assert not any(flags(mode="subband", _evaluation_detectability=False))
+    assert all(flags(mode="subband", _evaluation_detectability=True))
+    assert not any(flags(mode="broadband", _evaluation_detectability=True))
     assert callable(apvast.evaluation_detectability) and callable(apvast.evaluation_detectability_hops)
 
 

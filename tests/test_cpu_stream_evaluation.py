@@ -5,6 +5,7 @@ declarations and exports."""
 import inspect
 import os
 import re
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -157,9 +158,13 @@ def test_state_keys_unchanged_without_the_keywords():
     others = apvast._SB_STATE + apvast._BB_STATE + apvast._LIVE_STATE + apvast._WIN_STATE + apvast._FORGET_STATE + apvast._FIR_STATE
     assert not set(apvast._EVAL_STATE) & set(others)
     assert apvast._SB_STATE == ("response", "target_response", "input_block", "input_history", "out_overlap")
-    src = inspect.getsource(apvast.get_state) + inspect.getsource(apvast.set_state)
-    # both places add the evaluation keys only behind the object's own evaluation stage
-    assert src.count("self._evaluation is not None") == 2
+    # get_state and set_state take the evaluation keys only in subband mode and behind the object's own evaluation stage
+    rows = [r for r in apvast._STATE_ROWS if r.key in apvast._EVAL_STATE]
+    flags = lambda **kw: [bool(f(SimpleNamespace(**kw))) for r in rows for f in (r.accepts, r.reports or r.accepts)]
+    assert len(rows) == len(apvast._EVAL_STATE)
+    assert not any(flags(mode="subband", _evaluation=None))
+    assert all(flags(mode="subband", _evaluation=(None, None, [1])))
+    assert not any(flags(mode="broadband", _evaluation=(None, None, [1])))
     for name in ("evaluation_hops", "evaluation_totals", "predicted_pressure", "reset_evaluation"):
         assert callable(getattr(apvast, name))
 
