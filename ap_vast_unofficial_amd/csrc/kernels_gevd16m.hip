@@ -650,14 +650,8 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
 #pragma unroll
                 for (int t = 0; t < 4; ++t) sB[mfma_row<float>(lane, t) * LD + mcol] = mk<T>((T)v32[t].x, (T)v32[t].y);   // V32 takes W's place
                 wsync();
-                C accT[4], accG[4], accC[4], accV[4];
+                C accT[4];
                 cmm16([&](int r, int kx) { return sA[r * LD + kx]; }, [&](int kx, int c) { return sB[kx * LD + c]; }, lane, accT);       // C V
-                cmm16([&](int r, int kx) { return cj(sB[kx * LD + r]); }, [&](int kx, int c) { return sB[kx * LD + c]; }, lane, accG);   // V^H V
-                wsync();
-#pragma unroll
-                for (int t = 0; t < 4; ++t) sA[mfma_row<T>(lane, t) * LD + mcol] = accT[t];
-                wsync();
-                cmm16([&](int r, int kx) { return cj(sB[kx * LD + r]); }, [&](int kx, int c) { return sA[kx * LD + c]; }, lane, accC);   // C1 = V^H C V
                 // ---- one refinement step on the matrix cores in place of the double sweep (Ogita & Aishima 2018) ---------
                 // With S = V^H C V, Gram = V^H V = I + E and the Rayleigh quotients d_i = S_ii / Gram_ii, the update
                 //   V'' = V (I + Z),  Z_ij = (S_ij - d_j E_ij) / (d_j - d_i)  (i != j),  Z_ii = -E_ii / 2
@@ -676,6 +670,95 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 // Z goes straight into sA (T = C V is spent: every lane is past the third product) and the second-order
                 // eigenvalue terms into the idle coefficient array: nothing of this step stays in registers
                 T* const sLam2 = reinterpret_cast<T*>(&scoef[0]);
+                // ---- the first step from the residual: one float64 product and two float32 ones -------------------
+                // Off the diagonal the step needs S and Gram only through S_ij - d_j E_ij = (V^H (C V - V D))_ij.  The residual
+                // Rs = T - V D, formed element by element in float64, carries the whole cancellation (it is ~1e-6 ||C|| after the
+                // float32 pre-solve); V^H Rs and V Z then need relative accuracy only and run as float32 products (V is
+                // float32-valued exactly here, |Z| <= 3e-5).  On the diagonal d_j = (v_j^H t_j) / g_j and g_j = v_j^H v_j are
+                // sixteen column dot products.  A bin that misses the guard has lost nothing: T is still in accT, V in sB, and the
+                // float64 products below start from them as they always did.
+                if (refine_ok) {
+                    constexpr int LDR = 17;
+                    CF* const fR = reinterpret_cast<CF*>(&sA[0]);       // Rs; C is spent once T is in registers
+                    CF* const fZ = fR + N * LDR;                        // Z behind it: 2 x 16 x 17 x 8 B = all of sA
+                    const T scl = (T)ldexp(1.0, sexp);                  // the pre-solve's scale: Rs 2^sexp is ~1e-6 whatever ||C|| is
+                    C vv[4];
+                    T num = (T)0, g = (T)0;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        vv[t] = sB[mfma_row<T>(lane, t) * LD + mcol];
+                        num = __builtin_fma(vv[t].y, accT[t].y, __builtin_fma(vv[t].x, accT[t].x, num));
+                        g = __builtin_fma(vv[t].y, vv[t].y, __builtin_fma(vv[t].x, vv[t].x, g));
+                    }
+                    // the column's sixteen rows sit in this lane's four slots and in lanes ^ 16, ^ 32
+                    num += __shfl_xor(num, 16, 64); g += __shfl_xor(g, 16, 64);
+                    num += __shfl_xor(num, 32, 64); g += __shfl_xor(g, 32, 64);
+                    T ginv = __builtin_amdgcn_rcp(g);
+                    ginv = ginv * __builtin_fma(-g, ginv, (T)2);
+                    T dj = num * ginv;
+                    dj = __builtin_fma(__builtin_fma(-g, dj, num), ginv, dj);
+                    if (lane < N) sLam[mcol] = dj;
+                    wsync();                                            // every lane is past the product that read C
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const T rx = __builtin_fma(-vv[t].x, dj, accT[t].x) * scl, ry = __builtin_fma(-vv[t].y, dj, accT[t].y) * scl;
+                        fR[mfma_row<T>(lane, t) * LDR + mcol] = mk<float>((float)rx, (float)ry);
+                    }
+                    wsync();
+                    CF accP[4];
+                    cmm16([&](int r, int kx) { const C v = sB[kx * LD + r]; return mk<float>((float)v.x, -(float)v.y); },
+                          [&](int kx, int c) { return fR[kx * LDR + c]; }, lane, accP);                                                  // V^H Rs
+                    bool bad = false;
+                    T l2 = (T)0;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int row = mfma_row<float>(lane, t);
+                        T zx = (T)0.5 * ((T)1 - g), zy = (T)0;
+                        if (row != mcol) {
+                            const T den = dj - sLam[row], dens = den * scl;
+                            T inv = __builtin_amdgcn_rcp(dens);
+                            inv = inv * __builtin_fma(-dens, inv, (T)2);
+                            zx = (T)accP[t].x * inv;
+                            zy = (T)accP[t].y * inv;
+                            const T zz = zx * zx + zy * zy;
+                            bad = bad || !(zz <= (T)kRefineGuard2);                      // NaN / inf count as bad
+                            l2 = __builtin_fma(zz, den, l2);                             // the eigenvalue's second-order term, as below
+                        }
+                        fZ[row * LDR + mcol] = mk<float>((float)zx, (float)zy);
+                    }
+                    l2 += __shfl_xor(l2, 16, 64);
+                    l2 += __shfl_xor(l2, 32, 64);
+                    if (!__any(bad) || dstop == 10) {
+                        if (lane < N) sLam2[mcol] = l2 + dj;
+                        wsync();
+                        CF accZ[4];
+                        cmm16([&](int r, int kx) { const C v = sB[r * LD + kx]; return mk<float>((float)v.x, (float)v.y); },
+                              [&](int kx, int c) { return fZ[kx * LDR + c]; }, lane, accZ);                                              // V Z
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const C v = sB[mfma_row<float>(lane, t) * LD + mcol];
+                            vv[t] = mk<T>(v.x + (T)accZ[t].x, v.y + (T)accZ[t].y);      // V'' = V + V Z, added in float64
+                        }
+                        if (lane < N) sLam[lane] = sLam2[lane];
+                        wsync();
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            sA[mfma_row<float>(lane, t) * LD + mcol] = vv[t];           // Q for stage 5; sLam holds the eigenvalues
+                            sB[i * LD + jq + 4 * t] = wrow[t];                          // W back in place for stage 5
+                        }
+                        wsync();
+                        refined = true;
+                    }
+                }
+                if (!refined) {
+                // ---- the guarded path: the step in float64 throughout, the second step, the double sweeps ----------------------
+                C accG[4], accC[4], accV[4];
+                cmm16([&](int r, int kx) { return cj(sB[kx * LD + r]); }, [&](int kx, int c) { return sB[kx * LD + c]; }, lane, accG);   // V^H V
+                wsync();
+#pragma unroll
+                for (int t = 0; t < 4; ++t) sA[mfma_row<T>(lane, t) * LD + mcol] = accT[t];
+                wsync();
+                cmm16([&](int r, int kx) { return cj(sB[kx * LD + r]); }, [&](int kx, int c) { return sA[kx * LD + c]; }, lane, accC);   // C1 = V^H C V
                 for (int step = 0; step < 2; ++step) {
                     {
                         // Rayleigh quotients S_jj / Gram_jj of the sixteen lanes that hold a diagonal element: the element is
@@ -806,6 +889,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                     wsync();
                     }
                     v_in_lds = true;
+                }
                 }
                 }
             }
