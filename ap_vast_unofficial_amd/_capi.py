@@ -31,7 +31,7 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev", "apv_analysis_dev", "apv_analysis_jobs_dev", "apv_synthesis_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_stream_set_validation_span", "apv_get_validation_span", "apv_validation_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
@@ -147,6 +147,9 @@ def load():
     lib.apv_stream_set_effort_limit.argtypes = [vp, vp]
     lib.apv_get_effort.argtypes = [vp, i32, vp, vp, vp]
     lib.apv_limit_effort.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.apv_stream_set_validation_span.argtypes = [vp, vp, vp, vp]
+    lib.apv_get_validation_span.argtypes = [vp, i32, i32, vp]
+    lib.apv_validation_span.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.apv_state_bytes.argtypes = [vp, C.c_char_p, C.POINTER(sz)]
     lib.apv_get_state.argtypes = [vp, C.c_char_p, vp, sz]
     lib.apv_set_state.argtypes = [vp, C.c_char_p, vp, sz]
@@ -306,7 +309,8 @@ class Engine:
                  reg_mode=REG_ABS, reg_dark=1e-7, reg_bright=0.0, device=0, max_sweeps=0,
                  block_size=0, hop_size=0, n_zones=1, debug_stop=0, dialect="python", frontend=None, sweep_tol2=0.0,
                  out_layout=0, stat_hops=1, stat_forgetting=None, filter_taps=0, synthesis="wola", evaluation=None,
-                 evaluation_spectra=False, span=None, effort_limit=None, evaluation_detectability=None):
+                 evaluation_spectra=False, span=None, effort_limit=None, evaluation_detectability=None,
+                 validation_span=None):
         self.lib = load()
         self.h = None
         ranks = [int(v) for v in ranks]
@@ -377,6 +381,9 @@ class Engine:
         self.evaluation_detectability = False
         if evaluation_detectability is not None:
             self.set_evaluation_detectability(evaluation_detectability)
+        self.validation_span_on = False
+        if validation_span is not None:
+            self.set_validation_span(*validation_span)
 
     def set_evaluation_detectability(self, tables):
         """Perceptual detectability of the evaluated pressures, before stream_init (apv_stream_set_evaluation_detectability); needs
@@ -1019,6 +1026,63 @@ class Engine:
         self._chk(self.lib.apv_limit_effort(self.h, int(dt == np.complex128), hops, K, nV, L, _ptr(w), _ptr(lim), _ptr(eff),
                                             _ptr(src), _ptr(gain)))
         return w, eff, src, gain
+
+    def set_validation_span(self, floor, G_A=None, G_B=None):
+        """The rank choice by the contrast at the validation microphones (apv_stream_set_validation_span): floor, linear phi >= 0
+        (0 = no floor in that bin) as (K,) (both zone programs) or (2, K) (row 0 = program A); G_A, G_B (K, Mv, L) complex128, the
+        transfer functions of the validation responses of zone A and zone B at the bin centres.  The first call comes after
+        set_evaluation and before stream_init and needs both; later calls without them change the floor from the next hop on."""
+        a = np.asarray(floor, dtype=np.float64)
+        if a.shape == (self.K,):
+            a = np.stack([a, a])
+        if a.shape != (2, self.K):
+            raise ValueError(f"the validation floor has shape ({self.K},) or (2, {self.K}), got {a.shape}")
+        a = np.ascontiguousarray(a)
+        g = [None, None]
+        for i, G in enumerate((G_A, G_B)):
+            if G is None:
+                continue
+            G = np.ascontiguousarray(G, dtype=np.complex128)
+            if G.ndim != 3 or G.shape[0] != self.K or G.shape[2] != self.L or (self.evaluation and G.shape[1] != self.evaluation[1]):
+                raise ValueError(f"a validation transfer function has shape ({self.K}, Mv, {self.L}), Mv that of set_evaluation; got {G.shape}")
+            g[i] = G
+        self._chk(self.lib.apv_stream_set_validation_span(self.h, None if g[0] is None else _ptr(g[0]),
+                                                          None if g[1] is None else _ptr(g[1]), _ptr(a)))
+        self.validation_span_on = True
+
+    def validation_span(self, zone, what):
+        """An output of the validation span of the last hop for zone program `zone` (apv_get_validation_span): what = 0 bright,
+        1 dark ((K, nV) float64, before the choice), 2 source ((K, nV) int32, -1: left as it is), 3 rank ((K,) int32)."""
+        what = int(what)
+        out = np.empty(self.K if what == 3 else (self.K, self.nV), dtype=np.float64 if what < 2 else np.int32)
+        self._chk(self.lib.apv_get_validation_span(self.h, int(zone), what, _ptr(out)))
+        return out
+
+    def validation_span_kernel(self, w, G_bright, G_dark, phi, timed=False):
+        """The stage alone for one program (apv_validation_span): w (K, nV, L) complex64 or complex128 (anything else is taken as
+        complex128), G_bright, G_dark (K, Mv, L) complex128, phi (K,) linear -> (w', bright (K, nV), dark (K, nV), src (K, nV)
+        int32, rank (K,) int32 = src of the top slot + 1, guard = the guard bytes around the call's device buffers that changed);
+        timed=True appends the time of the launch alone (HIP events), in milliseconds."""
+        w = np.asarray(w)
+        dt = np.complex64 if w.dtype == np.complex64 else np.complex128
+        w = np.array(w, dtype=dt, order="C")                 # a copy: the call works in place
+        if w.ndim != 3:
+            raise ValueError("w must be (K, nV, L)")
+        K, nV, L = w.shape
+        gb, gd = (np.ascontiguousarray(g, dtype=np.complex128) for g in (G_bright, G_dark))
+        if gb.ndim != 3 or gb.shape != gd.shape or gb.shape[0] != K or gb.shape[2] != L:
+            raise ValueError(f"G_bright and G_dark must have one shape ({K}, Mv, {L}), got {gb.shape} and {gd.shape}")
+        p = np.ascontiguousarray(phi, dtype=np.float64)
+        if p.shape != (K,):
+            raise ValueError(f"phi must have shape ({K},), got {p.shape}")
+        bright, dark = np.empty((K, nV), dtype=np.float64), np.empty((K, nV), dtype=np.float64)
+        src, rank = np.empty((K, nV), dtype=np.int32), np.empty(K, dtype=np.int32)
+        guard, ms = C.c_int64(-1), C.c_float(-1.0)
+        self._chk(self.lib.apv_validation_span(self.h, int(dt == np.complex128), K, nV, L, gb.shape[1], _ptr(w), _ptr(gb), _ptr(gd),
+                                               _ptr(p), _ptr(bright), _ptr(dark), _ptr(src), _ptr(rank), C.byref(guard),
+                                               C.byref(ms) if timed else None))
+        out = (w, bright, dark, src, rank, int(guard.value))
+        return out + (float(ms.value),) if timed else out
 
     def stream_set_perceptual(self, tables, normalisation):
         """tables: ap_vast_unofficial_amd.perceptual.PerceptualTables (or None to switch the weighting off)."""

@@ -90,6 +90,19 @@ What is different (keyword-only, after ``perceptual``)
     hop; None without the keyword, before the first hop and for a zone that does not run.  The value can be reassigned between
     hops (not to None); w_*, w_time_* and the outputs are those of the limited filters, lambda_*, U_*, R_*, r_* and span_* are
     unchanged, and get_state() has the same keys.
+  * ``validation_floor_db`` (subband mode; needs the validation responses; a float, (K,) or (2, K) array of dB values, row 0 =
+    zone program A, ``-inf`` = no floor in that bin): the rank of every bin is chosen by the contrast the designed filters reach
+    at the VALIDATION microphones (main.m:129-130), not at the control points they were fitted to.  With the static transfer
+    functions G_z[k, m, l] = sum_j rv_z[j, l, m] exp(-2 pi i j k / N) (float64, once at construction) the stage predicts per bin k
+    and filter v bright = sum_m |sum_l G_own[k, m, l] W[k, v, l]|^2 and dark likewise with the other zone's responses; a filter is
+    admissible if bright >= 10^(dB / 10) dark.  Between the joint diagonalisation (span included) and the effort limit every
+    filter takes the filter of the largest admissible rank at or below its own, or of the rank of largest contrast at or below
+    its own when none is admissible.  ``validation_bright_A`` / ``_B``, ``validation_dark_*`` (K, V) return the energies before the
+    choice, ``validation_source_*`` (K, V) int32 the index of the filter each filter was taken from (-1: left as it is) and
+    ``validation_rank_*`` (K,) the rank of the top filter's source, all of the last hop; None without the keyword, before the
+    first hop and for a zone that does not run.  The value can be reassigned between hops (not to None); w_*, filter_spectra_*,
+    w_time_* and the outputs are those of the chosen filters, lambda_*, U_*, R_*, r_*, span_* are unchanged, and get_state() has
+    the same keys.  ``evaluation.validation_contrast_db`` turns the energies into dB.
   * ``mode="broadband"``: the reference's own time-domain algorithm (one (J L) x (J L) pair per zone from
     ``statistics_buffer_length`` samples, apvast.py:329-422), float64 on the device, checked against the
     golden outputs of the reference (tests/test_gpu_broadband.py).
@@ -195,6 +208,7 @@ class apvast:
                  mu_profile=None,
                  rank_profile=None,
                  contrast_floor_db=None,
+                 validation_floor_db=None,
                  effort_limit_db=None,
                  statistics_hops=1):
         self.block_size = block_size
@@ -248,6 +262,9 @@ class apvast:
         # the per-bin array-effort limit: whether the stage exists is fixed here, its values may be reassigned between hops
         self._effort_limit_db = self._check_effort_limit_db(effort_limit_db, N // 2 + 1, mode)
         self._effort_pending = False
+        # the rank choice at the validation microphones: whether the stage exists is fixed here, its floor may be reassigned
+        self._validation_floor_db = self._check_validation_floor_db(validation_floor_db, N // 2 + 1, self._evaluation, mode)
+        self._validation_pending = False
         self._init_responses(rir_A, rir_B)
         if mode == "broadband":
             self._init_broadband(device, seed)
@@ -281,6 +298,7 @@ class apvast:
                                  synthesis=self.synthesis, evaluation=self._evaluation,
                                  evaluation_spectra=self._evaluation_spectra, span=self._span_args(),
                                  effort_limit=self._effort_table(),
+                                 validation_span=self._validation_span_args(),
                                  evaluation_detectability=tables if self._evaluation_detectability else None)
         self._eng.stream_init(rir_A, rir_B, reference_index_A, reference_index_B, modeling_delay)
         if perceptual:
@@ -590,6 +608,96 @@ class apvast:
     effort_gain_A = property(lambda self: self._effort_output(0, 2))
     effort_gain_B = property(lambda self: self._effort_output(1, 2))
 
+    # ---- the rank choice at the validation microphones (validation_floor_db) --------------------------------
+    @staticmethod
+    def _check_validation_floor_db(value, K, evaluation, mode):
+        """validation_floor_db as a read-only (2, K) float64 array of dB values, or None: a float, (K,) or (2, K); -inf = no floor."""
+        if value is None:
+            return None
+        if mode == "broadband":
+            raise ValueError("validation_floor_db is a subband keyword: broadband mode has no evaluation stage")
+        if evaluation is None:
+            raise ValueError("validation_floor_db needs validation_rir_A and validation_rir_B")
+        bad = "validation_floor_db must hold dB values that are floats, not NaN and not +inf (-inf: no floor in that bin)"
+        if isinstance(value, (bool, np.bool_, str, bytes)):
+            raise ValueError(bad)
+        try:
+            a = np.asarray(value)
+        except Exception:
+            raise ValueError(bad) from None
+        if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(bad)
+        a = np.array(a, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full((2, K), float(a))
+        elif a.shape == (K,):
+            a = np.stack([a, a])
+        if a.shape != (2, K):
+            raise ValueError(f"validation_floor_db must be a float or have shape ({K},) (both zone programs) or (2, {K}) (one row "
+                             f"per program), got {a.shape}")
+        if np.isnan(a).any() or np.isposinf(a).any():
+            raise ValueError(bad)
+        with np.errstate(over="ignore"):
+            lin = 10.0 ** (a / 10.0)
+        if not np.isfinite(lin).all() or (lin[np.isfinite(a)] <= 0).any():
+            raise ValueError("validation_floor_db: 10^(dB / 10) must be a positive, finite double (-inf: no floor)")
+        a.flags.writeable = False
+        return a
+
+    @staticmethod
+    def validation_transfer(rv, block_size):
+        """G[k, m, l] = sum_j rv[j, l, m] exp(-2 pi i j k / N), k = 0 .. N/2: the response of (Pv, L, Mv) validation responses at
+        the bin centres, (K, Mv, L) complex128, for any Pv (taps beyond N fold back onto the N bin frequencies)."""
+        rv = np.asarray(rv, dtype=np.float64)
+        N = int(block_size)
+        Pv, L, Mv = rv.shape
+        folded = np.zeros((N, L, Mv))
+        for j0 in range(0, Pv, N):
+            part = rv[j0:j0 + N]
+            folded[:part.shape[0]] += part
+        return np.ascontiguousarray(np.fft.rfft(folded, axis=0).transpose(0, 2, 1))
+
+    def _validation_floor_table(self):
+        """The floor as _capi.Engine takes it, (2, K) linear phi (0 = no floor)."""
+        return 10.0 ** (self._validation_floor_db / 10.0)
+
+    def _validation_span_args(self):
+        """(floor, G_A, G_B) as _capi.Engine takes them; None without the keyword."""
+        if self._validation_floor_db is None:
+            return None
+        rvA, rvB, _ = self._evaluation
+        return (self._validation_floor_table(), self.validation_transfer(rvA, self.block_size),
+                self.validation_transfer(rvB, self.block_size))
+
+    def _set_validation_floor_db(self, value):
+        if self.__dict__.get("_validation_floor_db") is None:
+            raise ValueError("validation_floor_db was not given at construction: whether the stage exists is fixed there")
+        new = self._check_validation_floor_db(value, self._K, self._evaluation, self.mode)
+        if new is None:
+            raise ValueError("validation_floor_db cannot be removed: whether the stage exists is fixed at construction (-inf lifts "
+                             "the floor)")
+        self._validation_floor_db = new
+        self._validation_pending = True
+
+    # an assignment between two hops takes effect at the next one (_apply_live)
+    validation_floor_db = property(lambda self: self._validation_floor_db, _set_validation_floor_db)
+
+    def _validation_output(self, zone, what):
+        """validation_bright / _dark (K, V) float64, _source (K, V) int32, _rank (K,) int32 of the last hop, fetched when read.
+        None for an object without the keyword, before the first hop and for a zone program that does not run."""
+        if self.mode == "broadband" or self._validation_floor_db is None or self._hops == 0 or not (self.run_A, self.run_B)[zone]:
+            return None
+        return self._eng.validation_span(zone, what)
+
+    validation_bright_A = property(lambda self: self._validation_output(0, 0))
+    validation_bright_B = property(lambda self: self._validation_output(1, 0))
+    validation_dark_A = property(lambda self: self._validation_output(0, 1))
+    validation_dark_B = property(lambda self: self._validation_output(1, 1))
+    validation_source_A = property(lambda self: self._validation_output(0, 2))
+    validation_source_B = property(lambda self: self._validation_output(1, 2))
+    validation_rank_A = property(lambda self: self._validation_output(0, 3))
+    validation_rank_B = property(lambda self: self._validation_output(1, 3))
+
     # ---- the evaluation stage (validation_rir_A / validation_rir_B): read from the device when asked for ------------------
     def _eval_dims(self):
         if self.__dict__.get("_evaluation") is None:
@@ -738,6 +846,9 @@ class apvast:
         if self._effort_pending:
             self._eng.set_effort_limit(self._effort_table())
             self._effort_pending = False
+        if self._validation_pending:
+            self._eng.set_validation_span(self._validation_floor_table())
+            self._validation_pending = False
 
     # rir_A / rir_B (rir_length, L, M) and target_rir_A / target_rir_B (rir_length, M): an assignment between two hops takes effect at
     # the next one as lfilter(..., zi=state) makes it in the reference -- the samples already in take the old response's tail with

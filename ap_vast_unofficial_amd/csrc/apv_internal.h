@@ -130,6 +130,19 @@ struct apv_handle {
         int32_t* d_src = nullptr;        // [2][K]: source slot of the top slot (kernels_effort.hip)
         double* d_gain = nullptr;        // [2][K]
     } effort;
+    // apv_stream_set_validation_span: the rank choice by the contrast at the validation microphones (kernels_valspan.hip).  The
+    // banks are those of zone A and zone B at the bin centres; the floor and the outputs of the last hop are rows per zone program.
+    // `own` (an ApvOwned, made by the first call) holds them
+    struct ValSpan {
+        bool on = false;
+        class ApvOwned* own = nullptr;
+        int Mv = 0;                      // eval_Mv of the first call
+        void* d_G[2] = {nullptr, nullptr};   // [K][Mv][L] complex128: zone A, zone B
+        double* d_phi = nullptr;         // [2][K], linear, 0 = no floor
+        double* d_bright = nullptr;      // [2][K][nV]
+        double* d_dark = nullptr;        // [2][K][nV]
+        int32_t* d_src = nullptr;        // [2][K][nV]: source slot of every slot, -1 = none
+    } valspan;
     std::vector<int> bb_rank_list;   // apv_bb_set_rank_list: ranks of the next apv_bb_init (empty = 1..V)
     void* gl_ws;             // workspace + captured sweep graph of apv_gevd_large, owned
     double gl_tol2;          // > 0: stop threshold of apv_gevd_large's sweeps for the next call (the complex path asks for accurate eigenVECTORS)
@@ -333,6 +346,23 @@ struct EffortArgs {
     size_t hop_bins = 0;
 };
 hipError_t apv_launch_limit_effort(int c128, int K, int nV, int L, const EffortArgs& a, hipStream_t s, std::string* why);
+
+// kernels_valspan.hip: the rank choice by the contrast at validation microphones (see the file header).  The filters w[z]
+// [K][nV][L] complex (c128: double, else float) of `zones` zone programs, replaced in place from the energies their slots put on
+// the banks g_bright[z] / g_dark[z] [K][Mv][L] complex128 under the floor phi[z] [K], one launch.
+constexpr int APV_VALSPAN_MAX_SLOTS = APV_MAX_SRCS;    // nV of a launch
+struct ValSpanArgs {
+    void* w[2];
+    const void* g_bright[2];       // the bank of the program's own zone ...
+    const void* g_dark[2];         // ... and of the other zone
+    const double* phi[2];
+    double* bright[2];             // outputs (may be null with emit = 0): [K][nV], ...
+    double* dark[2];               // ... [K][nV] ...
+    int32_t* src[2];               // ... [K][nV]
+    int zones = 1;
+    int emit = 1;                  // 0: the launch writes the filters alone
+};
+hipError_t apv_launch_validation_span(int c128, int K, int nV, int L, int Mv, const ValSpanArgs& a, hipStream_t s, std::string* why);
 
 // kernels_firsynth.hip: the FIR synthesis of a constrained stream (see the file header).  One launch writes the groups
 // [program 0: nV][program 1: nV][target A][target B] (n_tgt = 0: no target groups) of H samples x L loudspeakers each; element

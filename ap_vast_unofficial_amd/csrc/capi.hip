@@ -331,6 +331,7 @@ int apv_destroy(apv_handle* h) {
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h->effort.own;
+    delete h->valspan.own;
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1086,6 +1087,78 @@ int apv_limit_effort(apv_handle* h, int32_t c128, int32_t n_hops, int32_t K, int
     if (h_rank) HIPCHK(h, hipMemcpyAsync(h_rank, dsrc, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, h->stream));
     if (h_gain) HIPCHK(h, hipMemcpyAsync(h_gain, dgain, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
+int apv_validation_span(apv_handle* h, int32_t c128, int32_t K, int32_t nV, int32_t L, int32_t Mv, void* h_w, const void* h_G_bright,
+                        const void* h_G_dark, const double* h_phi, double* h_bright, double* h_dark, int32_t* h_src, int32_t* h_rank,
+                        int64_t* h_guard, float* h_ms) {
+    if (!h || !h_w || !h_G_bright || !h_G_dark || !h_phi) return fail(h, APV_ERR_ARG, "apv_validation_span: null argument");
+    if (K < 1 || nV < 1 || L < 1 || Mv < 1) return fail(h, APV_ERR_ARG, "apv_validation_span: K, nV, L and Mv must be at least 1");
+    if (nV > APV_VALSPAN_MAX_SLOTS || L > APV_MAX_SRCS) return fail(h, APV_ERR_ARG, "apv_validation_span: nV and L are at most 128");
+    for (int32_t k = 0; k < K; ++k)
+        if (!(h_phi[k] >= 0.0) || !std::isfinite(h_phi[k]))
+            return fail(h, APV_ERR_ARG, "apv_validation_span: a floor must be finite and >= 0 (0: no floor), not NaN");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    ApvOwned t;                                             // freed on every way out
+    // every device buffer of the call lies between two guard bands of GUARD bytes of 0xA5; h_guard counts the guard bytes that
+    // hold anything else after the launch
+    constexpr size_t GUARD = 512;
+    struct Band { unsigned char* base; size_t bytes; };
+    std::vector<Band> bands;
+    auto guarded = [&](auto** p, size_t bytes) -> hipError_t {
+        unsigned char* base = nullptr;
+        hipError_t e = t.device(&base, bytes + 2 * GUARD);
+        if (e != hipSuccess) return e;
+        e = hipMemsetAsync(base, 0xA5, bytes + 2 * GUARD, h->stream);
+        *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(base + GUARD);
+        bands.push_back({base, bytes});
+        return e;
+    };
+    const size_t nw = (size_t)K * nV * L, wbytes = nw * (c128 ? 16 : 8), gbytes = (size_t)K * Mv * L * 16, no = (size_t)K * nV;
+    char *dw = nullptr, *dgb = nullptr, *dgd = nullptr;
+    double *dphi = nullptr, *dbright = nullptr, *ddark = nullptr;
+    int32_t* dsrc = nullptr;
+    HIPCHK(h, guarded(&dw, wbytes));
+    HIPCHK(h, guarded(&dgb, gbytes));
+    HIPCHK(h, guarded(&dgd, gbytes));
+    HIPCHK(h, guarded(&dphi, sizeof(double) * K));
+    HIPCHK(h, guarded(&dbright, sizeof(double) * no));
+    HIPCHK(h, guarded(&ddark, sizeof(double) * no));
+    HIPCHK(h, guarded(&dsrc, sizeof(int32_t) * no));
+    HIPCHK(h, hipMemcpyAsync(dw, h_w, wbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dgb, h_G_bright, gbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dgd, h_G_dark, gbytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dphi, h_phi, sizeof(double) * K, hipMemcpyHostToDevice, h->stream));
+    ValSpanArgs a;
+    a.w[0] = dw; a.g_bright[0] = dgb; a.g_dark[0] = dgd; a.phi[0] = dphi; a.bright[0] = dbright; a.dark[0] = ddark; a.src[0] = dsrc;
+    std::string why;
+    if (h_ms) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    hipError_t e = apv_launch_validation_span(c128 != 0, K, nV, L, Mv, a, h->stream, &why);
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    if (h_ms) HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    std::vector<int32_t> src(no);
+    HIPCHK(h, hipMemcpyAsync(h_w, dw, wbytes, hipMemcpyDeviceToHost, h->stream));
+    if (h_bright) HIPCHK(h, hipMemcpyAsync(h_bright, dbright, sizeof(double) * no, hipMemcpyDeviceToHost, h->stream));
+    if (h_dark) HIPCHK(h, hipMemcpyAsync(h_dark, ddark, sizeof(double) * no, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(src.data(), dsrc, sizeof(int32_t) * no, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h_src) std::copy(src.begin(), src.end(), h_src);
+    if (h_rank)
+        for (int32_t k = 0; k < K; ++k) h_rank[k] = src[(size_t)k * nV + nV - 1] + 1;       // ranks 1 .. nV; 0: no source
+    if (h_ms) HIPCHK(h, hipEventElapsedTime(h_ms, h->ev0, h->ev1));
+    if (h_guard) {
+        std::vector<unsigned char> g(2 * GUARD);
+        int64_t bad = 0;
+        for (const Band& b : bands) {
+            HIPCHK(h, hipMemcpy(g.data(), b.base, GUARD, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(g.data() + GUARD, b.base + GUARD + b.bytes, GUARD, hipMemcpyDeviceToHost));
+            for (unsigned char v : g) bad += v != 0xA5;
+        }
+        *h_guard = bad;
+    }
     return APV_OK;
 }
 

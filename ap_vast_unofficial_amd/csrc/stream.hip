@@ -391,8 +391,8 @@ struct BackSchedule {
     hipStream_t tail_stream = nullptr;
     hipEvent_t copied = nullptr;
     void* lspill = nullptr;   // GevdParams::Lspill of this launch (nullptr: the handle's d_Lspill)
-    bool span_quiet = false;  // the launch does not write the span's outputs, nor the effort limit's (hops that run side by side on
-                              // several back streams)
+    bool span_quiet = false;  // the launch does not write the span's outputs, nor the validation span's, nor the effort limit's
+                              // (hops that run side by side on several back streams)
     BackSchedule(void* result_, void* ospec_) : result((char*)result_), ospec((char*)ospec_) {}
 };
 
@@ -503,6 +503,34 @@ static int back_limit_effort(apv_handle* h, hipStream_t st, void* const* wz, con
     return effort_launch(h, st, wz, 1, 0, sch.span_quiet ? EFFORT_EMIT_NONE : 0);
 }
 
+// The hop's filters `wz` put to the choice by validation contrast, in place, both zone programs in one launch (nothing in a stream
+// without apv_stream_set_validation_span): program A's bright bank is zone A's, its dark bank zone B's, and the reverse for B.
+// The effort limit, the projection, K3, the attributes and the states read the chosen filters.
+static int back_validation_span(apv_handle* h, hipStream_t st, void* const* wz, const BackSchedule& sch) {
+    const apv_handle::ValSpan& vs = h->valspan;
+    if (!vs.on) return APV_OK;
+    const apv_stream* s = h->st;
+    const size_t K = s->K, nV = s->nV;
+    ValSpanArgs a;
+    const LiveZones lz(s);
+    a.zones = lz.nz;
+    for (int i = 0; i < lz.nz; ++i) {
+        const size_t z = lz.z[i];
+        a.w[i] = wz[z];
+        a.g_bright[i] = vs.d_G[z];
+        a.g_dark[i] = vs.d_G[z ^ 1];
+        a.phi[i] = vs.d_phi + z * K;
+        a.bright[i] = vs.d_bright + z * K * nV;
+        a.dark[i] = vs.d_dark + z * K * nV;
+        a.src[i] = vs.d_src + z * K * nV;
+    }
+    a.emit = sch.span_quiet ? 0 : 1;
+    std::string why;
+    hipError_t e = apv_launch_validation_span(h->cfg.out_c128, s->K, s->nV, s->L, vs.Mv, a, st, &why);
+    if (e != hipSuccess) return launch_fail(h, e, why);
+    return APV_OK;
+}
+
 // FIR synthesis in place of K3 and K4: the hop's taps and the taps of the hop before it applied to the input signals in
 // one launch, the target paths (pure delays) included, written where K4 writes; a second, small launch then makes this
 // hop's taps and the newest J - 1 samples the next hop's.  Only the per-hop path reaches here (the chunked whole-signal
@@ -589,12 +617,14 @@ static int back_synthesis(apv_handle* h, hipStream_t st, void* pin_dst, const Ba
     return APV_OK;
 }
 
-// Back half of a hop on stream `st`: spectra `q` -> per-bin filters (K5'-K10), their projection in a constrained stream, then
+// Back half of a hop on stream `st`: spectra `q` -> per-bin filters (K5'-K10), the choice by validation contrast and the effort
+// limit where the handle has them, their projection in a constrained stream, then
 // output spectra (K3), synthesis and overlap-add (K4), or the FIR synthesis in their place; the emitted samples [n_out][H] and,
 // behind them, the status words [2][K] land in pinned `pin_dst`.
 static int enqueue_back(apv_handle* h, hipStream_t st, const HopSpectra& q, void* const* wz, void* const* lamz, void* pin_dst,
                         const BackSchedule& sch) {
     int rc = back_solve(h, st, q, wz, lamz, sch);
+    if (rc == APV_OK) rc = back_validation_span(h, st, wz, sch);
     if (rc == APV_OK) rc = back_limit_effort(h, st, wz, sch);
     if (rc == APV_OK) rc = back_constrain(h, st, wz);
     if (rc != APV_OK) return rc;
@@ -1532,6 +1562,9 @@ int apv_stream_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const
         if (h->eval_rv[0].size() != (size_t)h->eval_Pv * c.n_srcs * h->eval_Mv)
             return apv_fail(h, APV_ERR_ARG, "evaluation (apv_stream_set_evaluation): the responses were sized for another n_srcs");
     }
+    if (h->valspan.on && (h->eval_Pv <= 0 || h->eval_Mv != h->valspan.Mv))
+        return apv_fail(h, APV_ERR_ARG, "validation span (apv_stream_set_validation_span): the transfer functions were sized for the "
+                                        "validation microphones of another apv_stream_set_evaluation");
     if (h->eval_spectra) {
         if (h->eval_Pv <= 0)
             return apv_fail(h, APV_ERR_ARG, "evaluation spectra (apv_stream_set_evaluation_spectra) need the evaluation stage of apv_stream_set_evaluation");
@@ -2253,6 +2286,94 @@ int apv_get_effort(apv_handle* h, int32_t zone, double* h_effort, int32_t* h_ran
     // slot's rank
     if (h_rank)
         for (size_t k = 0; k < K; ++k) h_rank[k] = (h_rank[k] < 0 || (size_t)h_rank[k] >= nV) ? 0 : h->rank_list[(size_t)h_rank[k]];
+    return APV_OK;
+}
+
+// ---- the rank choice by the contrast at validation microphones (include/apvast_hip.h, kernels_valspan.hip) ----
+int apv_stream_set_validation_span(apv_handle* h, const void* h_G_A, const void* h_G_B, const double* h_floor) {
+    if (!h) return apv_fail(h, APV_ERR_ARG, "null handle");
+    if (!h_floor) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: null floor table");
+    apv_handle::ValSpan& vs = h->valspan;
+    const size_t K = (size_t)h->cfg.n_bins, L = (size_t)h->cfg.n_srcs, n = 2 * K;
+    // everything is checked before anything changes
+    if (h->bb) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: the validation span is a subband feature; this handle runs the broadband stream");
+    if (!vs.on) {
+        if (h->st) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: the stream is initialised (the first call comes before apv_stream_init)");
+        if (h->eval_Pv <= 0) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: the first call comes after apv_stream_set_evaluation (it sizes the transfer functions)");
+        if (!h_G_A || !h_G_B) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: the first call needs both transfer functions");
+        if (L > (size_t)APV_VALSPAN_MAX_SLOTS) return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: at most 128 loudspeakers");
+    } else if ((h_G_A != nullptr) != (h_G_B != nullptr)) {
+        return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: both transfer functions or neither");
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (!(h_floor[i] >= 0.0) || !std::isfinite(h_floor[i]))
+            return apv_fail(h, APV_ERR_ARG, "apv_stream_set_validation_span: a floor must be finite and >= 0 (0: no floor), not NaN");
+    SCHK(h, hipSetDevice(h->device));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    const size_t Mv = vs.on ? (size_t)vs.Mv : (size_t)h->eval_Mv, gbytes = 16 * K * Mv * L;
+    if (!vs.on) {
+        // the banks, the table and the outputs, all or none: a failure frees what the call had allocated.  The outputs have room
+        // for every rank list the handle can take (n_ranks <= n_srcs)
+        ApvOwned* own = new ApvOwned;
+        void *gA = nullptr, *gB = nullptr;
+        double *phi = nullptr, *bright = nullptr, *dark = nullptr;
+        int32_t* src = nullptr;
+        const size_t no = n * (L ? L : 1);
+        hipError_t e = own->device(&gA, gbytes ? gbytes : 1);
+        if (e == hipSuccess) e = own->device(&gB, gbytes ? gbytes : 1);
+        if (e == hipSuccess) e = own->device(&phi, sizeof(double) * (n ? n : 1));
+        if (e == hipSuccess) e = own->zeroed(&bright, no, sizeof(double), h->stream);
+        if (e == hipSuccess) e = own->zeroed(&dark, no, sizeof(double), h->stream);
+        if (e == hipSuccess) e = own->device(&src, sizeof(int32_t) * (no ? no : 1));
+        if (e == hipSuccess) e = hipMemsetAsync(src, 0xff, sizeof(int32_t) * (no ? no : 1), h->stream);     // -1: nothing yet
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->stream);
+            delete own;
+            return apv_fail(h, APV_ERR_HIP, std::string("apv_stream_set_validation_span: ") + hipGetErrorString(e));
+        }
+        vs.own = own; vs.d_G[0] = gA; vs.d_G[1] = gB; vs.d_phi = phi; vs.d_bright = bright; vs.d_dark = dark; vs.d_src = src;
+        vs.Mv = (int)Mv;
+        vs.on = true;
+    }
+    // the hop graphs hold the addresses of the banks and the table, not their values: no new capture
+    if (h_G_A) {
+        SCHK(h, hipMemcpyAsync(vs.d_G[0], h_G_A, gbytes, hipMemcpyHostToDevice, h->stream));
+        SCHK(h, hipMemcpyAsync(vs.d_G[1], h_G_B, gbytes, hipMemcpyHostToDevice, h->stream));
+    }
+    SCHK(h, hipMemcpyAsync(vs.d_phi, h_floor, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));               // the arrays are the caller's
+    return APV_OK;
+}
+
+int apv_get_validation_span(apv_handle* h, int32_t zone, int32_t what, void* h_dst) {
+    if (!h) return apv_fail(h, APV_ERR_ARG, "null handle");
+    const apv_handle::ValSpan& vs = h->valspan;
+    if (!vs.on) return apv_fail(h, APV_ERR_ARG, "apv_get_validation_span: the handle has no validation span (apv_stream_set_validation_span)");
+    if (zone != 0 && zone != 1) return apv_fail(h, APV_ERR_ARG, "apv_get_validation_span: zone must be 0 or 1");
+    if (what < APV_VALSPAN_BRIGHT || what > APV_VALSPAN_RANK) return apv_fail(h, APV_ERR_ARG, "apv_get_validation_span: what must be one of APV_VALSPAN_*");
+    if (!h_dst) return apv_fail(h, APV_ERR_ARG, "apv_get_validation_span: null destination");
+    const size_t K = (size_t)h->cfg.n_bins, nV = (size_t)h->cfg.n_ranks, o = (size_t)zone * K * nV;
+    SCHK(h, hipSetDevice(h->device));
+    if (what == APV_VALSPAN_BRIGHT || what == APV_VALSPAN_DARK) {
+        const double* src = (what == APV_VALSPAN_BRIGHT ? vs.d_bright : vs.d_dark) + o;
+        SCHK(h, hipMemcpyAsync(h_dst, src, sizeof(double) * K * nV, hipMemcpyDeviceToHost, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        return APV_OK;
+    }
+    if (what == APV_VALSPAN_SOURCE) {
+        SCHK(h, hipMemcpyAsync(h_dst, vs.d_src + o, sizeof(int32_t) * K * nV, hipMemcpyDeviceToHost, h->stream));
+        SCHK(h, hipStreamSynchronize(h->stream));
+        return APV_OK;
+    }
+    // the rank of the top slot's source: the top column of the sources, then the slot's entry of the rank list
+    int32_t* rank = static_cast<int32_t*>(h_dst);
+    std::vector<int32_t> src(K * nV);
+    SCHK(h, hipMemcpyAsync(src.data(), vs.d_src + o, sizeof(int32_t) * K * nV, hipMemcpyDeviceToHost, h->stream));
+    SCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < K; ++k) {
+        const int32_t t = src[k * nV + nV - 1];
+        rank[k] = (t < 0 || (size_t)t >= nV) ? 0 : h->rank_list[(size_t)t];
+    }
     return APV_OK;
 }
 

@@ -227,6 +227,7 @@ int apv_bb_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const dou
     if (!h || !h_rir_A || !h_rir_B) return apv_fail(h, APV_ERR_ARG, "null argument");
     if (h->span.on) return apv_fail(h, APV_ERR_ARG, "broadband mode: the handle has a span (apv_set_span), a subband feature");
     if (h->effort.on) return apv_fail(h, APV_ERR_ARG, "broadband mode: the handle has an effort limit (apv_stream_set_effort_limit), a subband feature");
+    if (h->valspan.on) return apv_fail(h, APV_ERR_ARG, "broadband mode: the handle has a validation span (apv_stream_set_validation_span), a subband feature");
     const apv_config& c = h->cfg;
     const int N = c.block_size, H = c.hop_size, J = filter_length, S = statistics_buffer_length;
     const int V = number_of_eigenvectors, L = c.n_srcs, M = c.n_mics;

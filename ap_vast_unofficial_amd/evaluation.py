@@ -3,6 +3,7 @@
   predict_pressure   Matlab/ControlMethods/predictPressure.m:1-17
   nmse, acoustic_contrast_db   Matlab/main.m:120-130
   metrics            the same two from the energies a subband stream's evaluation stage accumulates on the device
+  validation_contrast_db   the contrast the validation span (apvast(..., validation_floor_db=)) predicts per bin and filter
   spectral_metrics   contrast and NMSE per bin or band from the per-bin energies (apvast.evaluation_spectra())
   detectability_metrics   mean detectability and audible share of hops (apvast.evaluation_detectability())
   third_octave_bands the bin ranges of base-2 third-octave bands, for spectral_metrics
@@ -53,6 +54,16 @@ def metrics(totals):
     target = np.asarray(totals["target"], dtype=np.float64)
     return {"nmse": np.mean(error / target[..., None, :], axis=-1),
             "contrast_db": 10.0 * np.log10(np.sum(bright, axis=-1) / np.sum(dark, axis=-1))}
+
+
+def validation_contrast_db(bright, dark):
+    """10 log10(bright / dark) (main.m:129-130) of the energies a validation span reports (apvast.validation_bright_* /
+    validation_dark_*, any shape): +inf where dark = 0 < bright, NaN where both are 0 or either is not finite."""
+    b = np.asarray(bright, dtype=np.float64)
+    d = np.asarray(dark, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = 10.0 * np.log10(b / d)
+    return np.where(np.isfinite(b) & np.isfinite(d), c, np.nan)
 
 
 def detectability_metrics(totals):

@@ -200,6 +200,43 @@ int  apv_get_effort(apv_handle* h, int32_t zone, double* h_effort, int32_t* h_ra
 int  apv_limit_effort(apv_handle* h, int32_t c128, int32_t n_hops, int32_t K, int32_t nV, int32_t L, void* h_w, const double* h_limit,
                       double* h_effort, int32_t* h_rank, double* h_gain);
 
+/* Rank choice per bin by the contrast at validation microphones.  The contrast is that of Matlab/main.m:120-130,
+ * energy at the microphones of the program's own zone over energy at those of the other zone, predicted per bin from the static
+ * transfer functions of the validation responses, G_z[k][m][l] = sum_j rv_z[j][l][m] exp(-2 pi i j k / N).  Per zone program, bin k
+ * and output slot t (slots in ascending rank), in float64 whatever the filters' type:
+ *   bright_t = sum_m |sum_l G_own[k][m][l] W[k][t][l]|^2,  dark_t = sum_m |sum_l G_other[k][m][l] W[k][t][l]|^2
+ * (program A: own = zone A, other = zone B; program B the reverse).  With phi = h_floor[z][k] (linear, finite, >= 0) slot t' is
+ * admissible if both energies are finite and bright >= phi dark.  Every hop, behind the joint diagonalisation (span included) and
+ * ahead of the effort limit and the filter-length projection, one more kernel (csrc/kernels_valspan.hip) makes slot t a bit copy
+ * of slot src_t: the largest admissible t' <= t; where there is none, the first t' <= t with finite energies that maximises
+ * bright / dark (compared by cross-multiplication; dark = 0 < bright above every ratio, 0/0 lowest); where no slot t' <= t has
+ * finite energies the slot is left as it is (src_t = -1).  phi = 0 is "no floor in this bin": the energies are reported and the
+ * filters of the bin are not written.  Everything downstream sees the chosen filters; eigenvalues, eigenvectors, statistics and
+ * the span's outputs do not change, and the stage keeps no state from hop to hop.
+ * h_G_A / h_G_B are [n_bins][Mv][n_srcs] complex128 (Mv of apv_stream_set_evaluation), h_floor is [2][n_bins], row 0 = zone
+ * program A.  The first call allocates the banks, the table and the outputs and comes after apv_stream_set_evaluation and before
+ * apv_stream_init; later calls may pass NULL for both banks and then rewrite the floor alone.  New values hold from the next hop
+ * on (device memory: the captured hop graphs stay).  A handle that never had the call launches what it launched before.
+ * APV_ERR_ARG, nothing changed: a floor that is NaN, negative or infinite, a first call without the evaluation stage, without a
+ * bank or on an initialised stream, one bank without the other, a broadband handle.
+ *                                                         replaces: nothing in the reference */
+int  apv_stream_set_validation_span(apv_handle* h, const void* h_G_A, const void* h_G_B, const double* h_floor);
+/* Outputs of the stage of the last hop for zone program `zone` (0 / 1): what = APV_VALSPAN_BRIGHT / _DARK: [n_bins][n_ranks]
+ * float64, the energies BEFORE the choice; _SOURCE: [n_bins][n_ranks] int32, src_t (-1: left as it is, or no hop has run);
+ * _RANK: [n_bins] int32, the rank (entry of the rank list) of the top slot's source, 0 where it has none.  Synchronises the
+ * handle's stream.  APV_ERR_ARG on a handle without the stage. */
+enum { APV_VALSPAN_BRIGHT = 0, APV_VALSPAN_DARK = 1, APV_VALSPAN_SOURCE = 2, APV_VALSPAN_RANK = 3 };
+int  apv_get_validation_span(apv_handle* h, int32_t zone, int32_t what, void* h_dst);
+/* The stage alone for one program, on host arrays: h_w [K][nV][L] complex (c128 != 0: complex128, else complex64) replaced in
+ * place; h_G_bright, h_G_dark [K][Mv][L] complex128; h_phi [K]; nV, L <= 128.  h_bright, h_dark [K][nV], h_src [K][nV] as above,
+ * h_rank [K] = src of the top slot + 1 (the ranks being 1 .. nV; 0: none); any output may be NULL.  The call puts guard bands
+ * around each of its device buffers and leaves in h_guard (may be NULL) the number of guard bytes the launch changed, and in h_ms
+ * (may be NULL) the time of the launch alone between two events on the handle's stream, in milliseconds.  APV_ERR_ARG
+ * with nothing launched: a null input, a size below 1, nV or L above 128, a floor that is not finite and >= 0. */
+int  apv_validation_span(apv_handle* h, int32_t c128, int32_t K, int32_t nV, int32_t L, int32_t Mv, void* h_w, const void* h_G_bright,
+                         const void* h_G_dark, const double* h_phi, double* h_bright, double* h_dark, int32_t* h_src, int32_t* h_rank,
+                         int64_t* h_guard, float* h_ms);
+
 /* Synthesis of the subband stream.  APV_SYNTH_WOLA (the default) is the reference's: output spectra, inverse transform, sine
  * window, overlap-add; its output lags the input by block_size - hop_size samples.  APV_SYNTH_FIR applies the J taps of a
  * constrained stream (apv_stream_set_filter_taps) as time-domain FIR filters with no latency: with x_z[n] the input of zone
