@@ -906,6 +906,36 @@ __device__ __forceinline__ void cmm16(FA fa, FB fb, int lane, Cx<float> out[4]) 
     for (int t = 0; t < 4; ++t) out[t] = mk<float>(re[t], im[t]);
 }
 
+// Eight output columns of a complex float32 product as two real products per k-step on ONE real tile [re | im] (tile column c < 8
+// is the real part of output column c, tile column c + 8 its imaginary part):
+//   [Or | Oi] = Ar [Br | Bi] + Ai [-Bi | Br]   (NEG_LO)        [Or | Oi] = Ar [Br | Bi] + Ai [Bi | -Br]   (!NEG_LO: A stands for conj(A))
+// fa(i, k) is the complex element (Ar, Ai) of the A operand, fb(k, c) the REAL tile element.  The second B operand is the first
+// with its column XORed with 8 (the partner lane sits in the same row of sixteen: row_ror:8) and one fixed sign per lane.  Per
+// k-step the Ar product goes first, then the Ai one: every element has the summation cmm16<float> gives it ((-a) b and a (-b) are
+// the same bits), so a column of the packed product is bit for bit the column of the full one.  out[t] is tile element
+// (mfma_row<float>(lane, t), lane & 15).
+template <bool NEG_LO, typename FA, typename FB>
+__device__ __forceinline__ void pmm16(FA fa, FB fb, int lane, float out[4]) {
+    f4 acc = {0, 0, 0, 0};
+    const int rc = lane & 15, kq = lane >> 4;
+    const int sg = (((lane & 8) != 0) == NEG_LO) ? 0 : (int)0x80000000u;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const Cx<float> a = fa(rc, 4 * s + kq);
+        const float b1 = fb(4 * s + kq, rc);
+        const float b2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b1), 0x128, 0xf, 0xf, true) ^ sg);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b1, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b2, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) out[t] = acc[t];
+}
+// the value of lane ^ 8 (row_ror:8), for a double: two moves
+__device__ __forceinline__ double dpp_xor8(double v) {
+    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x128, 0xf, 0xf, true),
+                            __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x128, 0xf, 0xf, true));
+}
+
 // The same product with operand lambdas that also receive the k-step s: the accumulator layout of a product X,
 // out[t] = X[(lane >> 4) + 4 t][lane & 15], is at once the B operand X of the next product (fb = out[s]) and the A operand
 // X^T (fa = out[s]), so a result can feed a product without a round trip through LDS.

@@ -614,6 +614,16 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
         if constexpr (sizeof(T) == 8) normS2 = uniform_scalar((T)ldexp((double)normF2, 2 * sexp));
         else normS2 = uniform_scalar((T)ldexpf((float)normF2, 2 * sexp));
         bool v_in_lds = false, refined = false;
+        // float64, first refinement step: does the launch read eigenvector columns beyond the eight leading ones?  (Uniform over
+        // the launch but for the diagnostic stops.)  Ranks above 8, the eigenvalue or eigenvector outputs, a contrast floor (its
+        // c_v run over all sixteen terms; mu and the cap of a span only ever shorten the list), and the diagnostic stops that
+        // mark or time the whole step.  keep_a: the leading half passed its guard and the other did not -- its columns (qa: one
+        // component of four elements per lane) and eigenvalues wait for the guarded path to end.
+        const bool need_b = p.ranks[p.nV - 1] > 8 || p.lam != nullptr || p.lam1 != nullptr || p.U != nullptr ||
+                            (p.span.on && p.span.phi > 0.0) || (DBG && (dstop == 9 || dstop == 5 || dstop == 10));
+        bool keep_a = false;
+        T qa[4] = {0, 0, 0, 0};
+        T* const sLamA = sLam + N;                                            // [8] half A's eigenvalues meanwhile (free half of scol[0])
         // A one-sided solve is used only if it converged and its eigenvalues (the squared column norms) span less than 1e3: its
         // stop criterion is absolute, so columns of smaller norm (the null space of a rank-deficient C sits at the shift) may be
         // left askew.  Such a bin takes the two-sided sweeps on C, which is still intact in sA at that point.
@@ -678,9 +688,15 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 // sixteen column dot products.  A bin that misses the guard has lost nothing: T is still in accT, V in sB, and the
                 // float64 products below start from them as they always did.
                 if (refine_ok) {
+                    // The step runs in two halves of eight columns ("The leading half alone"): half A = columns
+                    // 8..15, the eight leading eigenvectors (the pre-solve delivers ascending eigenvalues), half B = columns 0..7,
+                    // only for a launch that reads them.  A half's Rs and Z are real 16 x 16 float tiles [re | im] and its two
+                    // products packed ones (pmm16): 8 MFMAs where the full complex product takes 16.
                     constexpr int LDR = 17;
-                    CF* const fR = reinterpret_cast<CF*>(&sA[0]);       // Rs; C is spent once T is in registers
-                    CF* const fZ = fR + N * LDR;                        // Z behind it: 2 x 16 x 17 x 8 B = all of sA
+                    float* const fT = reinterpret_cast<float*>(&sA[0]);   // tiles Rs, Z of half A, then of half B: 4 x 16 x 17 x 4 B
+                                                                          // = all of sA; C is spent once T is in registers
+                    T* const sG = reinterpret_cast<T*>(&scol[1][0]) + 8;  // [N] column norms g_j, behind sOrder's place
+                    const bool lo = (lane & 8) == 0;                      // this lane's tile column holds real parts
                     const T scl = (T)ldexp(1.0, sexp);                  // the pre-solve's scale: Rs 2^sexp is ~1e-6 whatever ||C|| is
                     C vv[4];
                     T num = (T)0, g = (T)0;
@@ -697,57 +713,95 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                     ginv = ginv * __builtin_fma(-g, ginv, (T)2);
                     T dj = num * ginv;
                     dj = __builtin_fma(__builtin_fma(-g, dj, num), ginv, dj);
-                    if (lane < N) sLam[mcol] = dj;
+                    if (lane < N) { sLam[mcol] = dj; sG[mcol] = g; }
                     wsync();                                            // every lane is past the product that read C
+                    // Rs of both halves in one pass: a lane's column belongs to one of them (without half B its lanes store nothing)
+                    if (need_b || !lo) {
+                        float* const tR = fT + (lo ? 2 * N * LDR : 0) + (mcol & 7);
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const T rx = __builtin_fma(-vv[t].x, dj, accT[t].x) * scl, ry = __builtin_fma(-vv[t].y, dj, accT[t].y) * scl;
-                        fR[mfma_row<T>(lane, t) * LDR + mcol] = mk<float>((float)rx, (float)ry);
+                        for (int t = 0; t < 4; ++t) {
+                            const T rx = __builtin_fma(-vv[t].x, dj, accT[t].x) * scl, ry = __builtin_fma(-vv[t].y, dj, accT[t].y) * scl;
+                            tR[mfma_row<T>(lane, t) * LDR] = (float)rx;
+                            tR[mfma_row<T>(lane, t) * LDR + 8] = (float)ry;
+                        }
                     }
                     wsync();
-                    CF accP[4];
-                    cmm16([&](int r, int kx) { const C v = sB[kx * LD + r]; return mk<float>((float)v.x, -(float)v.y); },
-                          [&](int kx, int c) { return fR[kx * LDR + c]; }, lane, accP);                                                  // V^H Rs
-                    bool bad = false;
-                    T l2 = (T)0;
+                    // One half up to its Z tile and eigenvalues (sLam2); true if it misses the guard.  The lane holds the real
+                    // (lo) or the imaginary parts of four entries of column j: the formulas are those of the full step, |Z_ij|^2
+                    // takes the other part's square from lane ^ 8 and is summed as zx zx + (zy zy) in the lanes of the real parts,
+                    // which alone judge the guard and sum the eigenvalue's second-order term.
+                    auto half_step = [&](const int h) -> bool {
+                        const float* const tR = fT + (h ? 0 : 2 * N * LDR);
+                        float* const tZ = fT + (h ? 1 : 3) * N * LDR;
+                        const int j = 8 * h + (lane & 7);
+                        float accP[4];
+                        pmm16<false>([&](int r, int kx) { const C v = sB[kx * LD + r]; return mk<float>((float)v.x, (float)v.y); },
+                                     [&](int kx, int c) { return tR[kx * LDR + c]; }, lane, accP);                                       // V^H Rs
+                        const T djh = sLam[j];
+                        const T zd = lo ? (T)0.5 * ((T)1 - sG[j]) : (T)0;
+                        bool bad = false;
+                        T l2 = (T)0;
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const int row = mfma_row<float>(lane, t);
-                        T zx = (T)0.5 * ((T)1 - g), zy = (T)0;
-                        if (row != mcol) {
-                            const T den = dj - sLam[row], dens = den * scl;
+                        for (int t = 0; t < 4; ++t) {
+                            const int row = mfma_row<float>(lane, t);
+                            const bool offd = row != j;
+                            const T den = djh - sLam[row], dens = den * scl;
                             T inv = __builtin_amdgcn_rcp(dens);
                             inv = inv * __builtin_fma(-dens, inv, (T)2);
-                            zx = (T)accP[t].x * inv;
-                            zy = (T)accP[t].y * inv;
-                            const T zz = zx * zx + zy * zy;
-                            bad = bad || !(zz <= (T)kRefineGuard2);                      // NaN / inf count as bad
-                            l2 = __builtin_fma(zz, den, l2);                             // the eigenvalue's second-order term, as below
+                            const T z = (T)accP[t] * inv;
+                            const T sq = z * z;
+                            const T zz = __builtin_fma(z, z, dpp_xor8(sq));
+                            bad = bad || (offd && lo && !(zz <= (T)kRefineGuard2));      // NaN / inf count as bad
+                            l2 = offd ? __builtin_fma(zz, den, l2) : l2;                 // the eigenvalue's second-order term, as below
+                            tZ[row * LDR + mcol] = (float)(offd ? z : zd);
                         }
-                        fZ[row * LDR + mcol] = mk<float>((float)zx, (float)zy);
+                        l2 += __shfl_xor(l2, 16, 64);
+                        l2 += __shfl_xor(l2, 32, 64);
+                        if (lane < 8) sLam2[j] = l2 + djh;
+                        return __any(bad) && dstop != 10;
+                    };
+                    bool miss = half_step(1), miss_b = false;
+                    if (need_b && !miss) miss_b = half_step(0);
+                    wsync();
+                    if (!miss && !need_b) {
+                        // the leading eight must come from half A: all 64 pairs (column of A, column of B), one per lane
+                        miss = __any(!(sLam2[8 + (lane & 7)] > sLam[lane >> 3]));
                     }
-                    l2 += __shfl_xor(l2, 16, 64);
-                    l2 += __shfl_xor(l2, 32, 64);
-                    if (!__any(bad) || dstop == 10) {
-                        if (lane < N) sLam2[mcol] = l2 + dj;
-                        wsync();
-                        CF accZ[4];
-                        cmm16([&](int r, int kx) { const C v = sB[r * LD + kx]; return mk<float>((float)v.x, (float)v.y); },
-                              [&](int kx, int c) { return fZ[kx * LDR + c]; }, lane, accZ);                                              // V Z
+                    if (!miss) {
+                        float accZ[4];
+                        auto vr = [&](int r, int kx) { const C v = sB[r * LD + kx]; return mk<float>((float)v.x, (float)v.y); };
+                        pmm16<true>(vr, [&](int kx, int c) { return fT[N * LDR + kx * LDR + c]; }, lane, accZ);                         // V Z
+                        T qb[4];
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
-                            const C v = sB[mfma_row<float>(lane, t) * LD + mcol];
-                            vv[t] = mk<T>(v.x + (T)accZ[t].x, v.y + (T)accZ[t].y);      // V'' = V + V Z, added in float64
+                            // this lane's component of V[row][lane & 7] and V[row][8 + (lane & 7)]
+                            const T* const v = reinterpret_cast<const T*>(&sB[mfma_row<float>(lane, t) * LD + (lane & 7)]) + (lo ? 0 : 1);
+                            qa[t] = v[2 * 8] + (T)accZ[t];                              // V'' = V + V Z, added in float64
+                            qb[t] = v[0];                                               // without half B: the V32 values
                         }
-                        if (lane < N) sLam[lane] = sLam2[lane];
-                        wsync();
+                        if (miss_b) {
+                            // the other half goes the guarded path below, which takes all sixteen columns as it always did;
+                            // this half's results wait and take their columns back afterwards
+                            if (lane < 8) sLamA[lane] = sLam2[8 + lane];
+                            keep_a = true;
+                        } else {
+                            if (need_b) {
+                                pmm16<true>(vr, [&](int kx, int c) { return fT[3 * N * LDR + kx * LDR + c]; }, lane, accZ);             // V Z
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            sA[mfma_row<float>(lane, t) * LD + mcol] = vv[t];           // Q for stage 5; sLam holds the eigenvalues
-                            sB[i * LD + jq + 4 * t] = wrow[t];                          // W back in place for stage 5
+                                for (int t = 0; t < 4; ++t) qb[t] += (T)accZ[t];
+                            }
+                            if (lane < N && (need_b || lane >= 8)) sLam[lane] = sLam2[lane];
+                            wsync();
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) {
+                                T* const q = reinterpret_cast<T*>(&sA[mfma_row<float>(lane, t) * LD + (lane & 7)]) + (lo ? 0 : 1);
+                                q[0] = qb[t];                                            // Q for stage 5; sLam holds the eigenvalues
+                                q[2 * 8] = qa[t];
+                                sB[i * LD + jq + 4 * t] = wrow[t];                      // W back in place for stage 5
+                            }
+                            wsync();
+                            refined = true;
                         }
-                        wsync();
-                        refined = true;
                     }
                 }
                 if (!refined) {
@@ -961,6 +1015,18 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
             wsync();
         }
 
+        if constexpr (sizeof(T) == 8) {
+            if (keep_a) {
+                // the leading half's columns and eigenvalues from the fast step (the guarded path, sweeps included, keeps every
+                // column at its index)
+                wsync();
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    reinterpret_cast<T*>(&sA[mfma_row<float>(lane, t) * LD + 8 + (lane & 7)])[(lane & 8) ? 1 : 0] = qa[t];
+                if (lane < 8) sLam[8 + lane] = sLamA[lane];
+                wsync();
+            }
+        }
         stamp(6);
         // ---------------- stage 4: descending order ----------------
         // all 64 lanes: lane (i = lane & 15, q = lane >> 4) compares eigenvalue i with four others, the counts meet over q
