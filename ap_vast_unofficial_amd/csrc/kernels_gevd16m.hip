@@ -151,8 +151,30 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
         q[t] = (f2v){(jq + 4 * t == i) ? 1.f : 0.f, 0.f};
     }
     // u and w are formed once per row (quad i: A[i][k] by a quad broadcast) and every lane fetches the entries of its own columns
-    // jq + 4 t from quad jq + 4 t (ds_bpermute: one crossbar trip each, no LDS storage, no barrier); ||x||^2 and u^H A u are summed
-    // over the quads on the VALU into a scalar register.
+    // jq + 4 t from quad jq + 4 t; ||x||^2 and u^H A u are summed over the quads on the VALU into a scalar register.
+    // The fetch goes through LDS (the scratch behind fX, free throughout): the quads write their element, element i to place
+    // 4 (i & 3) + (i >> 2), so that the elements jq + 4 t of a lane's slots lie side by side: one ds_write_b64 and one or two
+    // ds_read_b128 where the crossbar took up to eight ds_bpermute.  It is a move, so every bit of the result stays, and the
+    // kernel is 2 % faster for it (measured; DESIGN 4.1, "The reduction's crossbar trips through LDS", also has what is only
+    // inferred about why: the 16 waves of a CU share one LDS and crossbar).  One wave, whose LDS accesses execute in order: no barrier,
+    // and the next vector may take the same place.  The four lanes of a quad hold the same value; each writes a copy of its own
+    // (34 dwords apart: sixteen lanes, sixteen bank pairs) and everyone reads copy 0, lane 4 i's, as the crossbar did.
+    // the scratch (sB of the caller, N x LD elements of Cx<TS>) holds fQ, fX and the four copies: 3 x 136 + 128 bytes
+    constexpr size_t kVecOff = sizeof(CF) * N * LDQ + sizeof(float) * N * LDX;
+    static_assert(kVecOff + 3 * 136 + 128 <= sizeof(Cx<TS>) * N * LD, "the pre-solve's scratch no longer fits sB");
+    static_assert(kVecOff % 16 == 0, "ds_read_b128 wants 16-byte alignment (the caller declares sB alignas(16))");
+    char* const vbuf = reinterpret_cast<char*>(fX + N * LDX);
+    f2v* const vput = reinterpret_cast<f2v*>(vbuf + 136 * jq + 8 * (4 * (i & 3) + (i >> 2)));
+    const f4v* const vget = reinterpret_cast<const f4v*>(vbuf + 32 * jq);
+    auto by_column = [&](f2v v, f2v (&c)[4], int first) {                  // slots first .. 3 (first is a constant once unrolled)
+        *vput = v;
+        if (first < 2) {
+            const f4v lo = vget[0];
+            c[0] = (f2v){lo.x, lo.y}; c[1] = (f2v){lo.z, lo.w};
+        }
+        const f4v hi = vget[1];
+        c[2] = (f2v){hi.x, hi.y}; c[3] = (f2v){hi.z, hi.w};
+    };
     float e[N - 1], e2[N - 1];                                             // |sub-diagonal| and its square (wave-uniform)
     float dlr = 1.f, dli = 0.f;                                            // delta_k (the same in every lane)
 #pragma unroll
@@ -187,11 +209,7 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
         const float un = tp_keep(nrm, tp_lanes(15, 4 * k1));
         const CF vi = mk<float>(fmaf(phr, un, bx), fmaf(phi, un, by));
         f2v vj[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (t < t0) continue;
-            vj[t] = (f2v){tp_from(vi.x, 4 * (jq + 4 * t)), tp_from(vi.y, 4 * (jq + 4 * t))};
-        }
+        by_column((f2v){vi.x, vi.y}, vj, t0);
         // delta_{k+1} = -delta_k phi_k (off the chain: it fills the permutes' wait)
         {
             const float ndr = fmaf(dli, phi, -dlr * phr), ndi = -fmaf(dlr, phi, dli * phr);
@@ -220,11 +238,7 @@ __device__ __forceinline__ bool tridiag_presolve16(const Cx<TS>* sA, int sexp, f
         const CF wi = mk<float>(fmaf(gam, pr, kap * vi.x), fmaf(gam, pi, kap * vi.y));
         const f2v tu = {gam * ur, gam * ui};                                                // gamma (Q u)_i
         f2v wj[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (t < t0) continue;
-            wj[t] = (f2v){tp_from(wi.x, 4 * (jq + 4 * t)), tp_from(wi.y, 4 * (jq + 4 * t))};
-        }
+        by_column((f2v){wi.x, wi.y}, wj, t0);
         const f2v uv = {vi.x, vi.y}, wv = {wi.x, wi.y};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -445,7 +459,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
     int32_t* const pstatus = reinterpret_cast<int32_t*>(const_cast<char*>(at_hop(z1 ? p.status1 : p.status, p.hop_status)));
     using C = Cx<T>;
     __shared__ C sA[N * LD];       // R_B -> W R_B -> C -> Q (eigenvectors of C) (-> X for U)
-    __shared__ C sB[N * LD];       // R_D -> W = L^-1
+    __shared__ alignas(16) C sB[N * LD];   // R_D -> W = L^-1 (16 bytes: the pre-solve reads its scratch here by ds_read_b128)
     __shared__ C scol[2][N];       // (stage 1 keeps its columns in sB; the later stages' small arrays live here)
     __shared__ C swr[2][N];        // Cholesky: current row of W
     __shared__ C sr[N];

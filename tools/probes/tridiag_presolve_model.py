@@ -31,7 +31,12 @@ exact C, meets the kernel's one-step guard |Z| <= 3e-5 and its second-step limit
 
     python tools/probes/tridiag_presolve_model.py [K] [NSTEP] [NPTS] [SCHEME]
 
-SCHEME: "wide+best4" (the kernel's), "wide", "best4" or "quad".  The reciprocals of the L D L^T pivots carry 1-ulp noise too,
+SCHEME: "wide+best4" (the kernel's), "wide", "best4" or "quad".  The token "lanczos" (as in "wide+best4+lanczos") replaces step 1
+by a Lanczos reduction: the three-term recurrence from a fixed generic start vector with one full reorthogonalisation pass per
+step (`lanczos` below; T comes out real and the Lanczos vectors are Q, so there is nothing to accumulate and no phases), and a
+beta below LANCZOS_BETA_MIN ||C||_F fails the gate.  "+noreorth" drops the pass, "+no3term" the three-term step in front of it and
+"+ones" starts from ones / 4: the variants that do not work.  That reduction was built and measured in the kernel and is not what
+it runs ("The reduction's crossbar trips through LDS", has why); the scheme stays here for whoever takes it up.  The reciprocals of the L D L^T pivots carry 1-ulp noise too,
 as the bare v_rcp_f32 of the kernel does, whenever the reflector scalars do (ULP_NOISE, or `rng` of presolve); RCP_NOISE=0
 takes them correctly rounded (the kernel's earlier Newton step).
 """
@@ -137,6 +142,48 @@ def tridiag(A, rng=None):
     return a, e, e2, Q, delta
 
 
+# The start vector of the Lanczos reduction: sixteen entries of modulus 1/4 whose phases
+# 2 pi frac(m^2 phi + m sqrt 2) have no symmetry an array can share (a symmetric array has eigenvectors orthogonal to ones).
+_m = np.arange(N, dtype=np.float64)
+LANCZOS_START = (0.25 * np.exp(2j * np.pi * ((_m * _m * 0.6180339887498949 + _m * 1.4142135623730951) % 1.0))).astype(np.complex64)
+LANCZOS_BETA_MIN = 1e-6             # a beta below this (x ||C||_F) is a breakdown and fails the gate
+
+
+def lanczos(A, rng=None, start=None, reorth=True, three_term=True):
+    """A: [K,16,16] complex64, Hermitian.  Lanczos tridiagonalisation from the fixed start vector, in float32: w = A q_k,
+    alpha_k = Re q_k^H w, w -= alpha_k q_k + beta_{k-1} q_{k-1} (the three-term step), then ONE pass against all of q_0 .. q_k
+    (c = Q_k^H w, w -= Q_k c), n^2 = ||w||^2 + 16e-31, beta_k = n^2 rsq(n^2) and q_{k+1} = w rsq(n^2), the reciprocal root with
+    1-ulp noise (`rng`).  Returns a, e, e2, Q, delta as tridiag does: the Lanczos vectors are Q itself, T is real with a
+    positive sub-diagonal and delta is all ones.  `reorth`, `three_term`: the variants that do not work (see main)."""
+    K = A.shape[0]
+    q0 = LANCZOS_START if start is None else np.asarray(start, np.complex64)
+    Q = np.zeros((K, N, N), np.complex64)
+    Q[:, :, 0] = q0
+    a = np.zeros((K, N), f32)
+    e = np.zeros((K, N - 1), f32)
+    e2 = np.zeros((K, N - 1), f32)
+    for k in range(N):
+        qk = Q[:, :, k]
+        w = np.einsum("kij,kj->ki", A, qk).astype(np.complex64)
+        a[:, k] = (qk.real * w.real + qk.imag * w.imag).sum(1, dtype=f32)
+        if k == N - 1:
+            break
+        if three_term:
+            w = (w - a[:, k, None] * qk).astype(np.complex64)
+            if k > 0:
+                w = (w - e[:, k - 1, None] * Q[:, :, k - 1]).astype(np.complex64)
+        if reorth:
+            Qk = Q[:, :, :k + 1]
+            c = np.einsum("kij,ki->kj", Qk.conj(), w).astype(np.complex64)
+            w = (w - np.einsum("kij,kj->ki", Qk, c)).astype(np.complex64)
+        n2 = (f32(16e-31) + (w.real * w.real + w.imag * w.imag).sum(1, dtype=f32)).astype(f32)
+        r = ulp_noise(f32(1) / np.sqrt(n2), rng)
+        e[:, k] = (n2 * r).astype(f32)
+        e2[:, k] = n2
+        Q[:, :, k + 1] = (w * r[:, None]).astype(np.complex64)
+    return a, e, e2, Q, np.ones((K, N), np.complex64)
+
+
 def sturm_count(a, e2, x):
     """number of eigenvalues below x; a [K,16], e2 [K,15], x [K,...]"""
     q = (a[:, 0, None] - x).astype(f32)
@@ -239,7 +286,11 @@ def presolve(C, nstep, npts=4, rng=None, scheme=SCHEME_KERNEL, rcp_rng="as rng")
     sexp = -(np.frexp(nf2)[1] - 1) // 2
     A = (C * np.ldexp(1.0, sexp)[:, None, None]).astype(np.complex64)
     nrm = np.sqrt(np.ldexp(nf2, 2 * sexp)).astype(f32)
-    a, e, e2, Q, delta = tridiag(A, rng)
+    if "lanczos" in scheme:
+        a, e, e2, Q, delta = lanczos(A, rng, start=np.full(N, 0.25) if "ones" in scheme else None,
+                                     reorth="noreorth" not in scheme, three_term="no3term" not in scheme)
+    else:
+        a, e, e2, Q, delta = tridiag(A, rng)
     if "best4" in scheme:
         lo, hi = multisection(a, e2, nrm, nstep, npts, scheme, interval=True)
         X, lam, _ = best_of_four(a, e, lo, hi, nrm, rcp_rng)
@@ -254,6 +305,8 @@ def presolve(C, nstep, npts=4, rng=None, scheme=SCHEME_KERNEL, rcp_rng="as rng")
     with np.errstate(invalid="ignore"):
         apart = (np.diff(lam, axis=1) > f32(apart_threshold(nstep, scheme)) * nrm[:, None]).all(1)
         trust = (lam[:, 0] >= f32(1e-3) * lam[:, -1]) & apart & np.isfinite(X).all((1, 2)) & ~np.isnan(lam).any(1)
+        if "lanczos" in scheme:                                         # a breakdown of the recurrence fails the gate too
+            trust &= (e >= f32(LANCZOS_BETA_MIN) * nrm[:, None]).all(1)
     return V, lam, trust, (a, e, Q, A)
 
 
@@ -280,6 +333,8 @@ def main():
     noise = os.environ.get("ULP_NOISE", "1") != "0"
     V, lam, trust, (a, e, Q, A) = presolve(C, nstep, npts, np.random.default_rng(7) if noise else None, scheme,
                                            np.random.default_rng(11) if noise and os.environ.get("RCP_NOISE", "1") != "0" else None)
+    if "lanczos" in scheme:
+        print(f"lanczos: smallest beta / ||C||_F = {(e / np.sqrt((np.abs(A.astype(np.complex128)) ** 2).sum((1, 2)))[:, None]).min():.2e}")
     # the reduction itself: (Q diag(delta))^H A (Q diag(delta)) tridiagonal and real
     T = Q.conj().transpose(0, 2, 1).astype(np.complex128) @ A.astype(np.complex128) @ Q.astype(np.complex128)
     Tm = np.zeros_like(T)
