@@ -31,8 +31,8 @@ EXPORTS = (
     "apv_timer_start", "apv_timer_stop",
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev", "apv_analysis_dev", "apv_analysis_jobs_dev", "apv_synthesis_dev",
-    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_stream_set_validation_span", "apv_get_validation_span", "apv_validation_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
-    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state",
+    "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_eval_energies", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_stream_set_validation_span", "apv_get_validation_span", "apv_validation_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
+    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state", "apv_bb_set_evaluation", "apv_bb_reset_evaluation",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
     "apv_comm_unique_id", "apv_comm_init", "apv_allgather_filters_dev", "apv_comm_count", "apv_comm_last_gather", "apv_comm_barrier",
@@ -177,6 +177,9 @@ def load():
     lib.apv_host_alloc.argtypes = [C.POINTER(vp), sz]
     lib.apv_host_free.argtypes = [vp]
     lib.apv_bb_set_state.argtypes = [vp, C.c_char_p, vp, sz]
+    lib.apv_bb_set_evaluation.argtypes = [vp, i32, i32, vp, vp, i32, vp]
+    lib.apv_bb_reset_evaluation.argtypes = [vp]
+    lib.apv_eval_energies.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.apv_predict_pressure.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     lib.apv_vast_static.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp]
     lib.apv_comm_unique_id.argtypes = [C.c_char_p]
@@ -491,6 +494,45 @@ class Engine:
         finally:
             for b in (dy, dr, dp):
                 b.free()
+
+    def eval_energies(self, p, H, record=None, totals=None):
+        """The energy reduction of the broadband stream's evaluation stage alone (apv_eval_energies): p (Z, 2 E + 1, n H, Mv)
+        float64 pressures of n consecutive hops -> (record (n, Z, 3 E + 1, Mv), totals (Z, 3 E + 1, Mv)): per hop [bright of the E
+        ranks | dark | error | target], and totals = totals + record[i], i ascending, starting from `totals` (None: zeros).
+        `record`: what the record holds before the launch (None: zeros)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        if p.ndim != 4 or p.shape[1] % 2 != 1 or p.shape[1] < 3:
+            raise ValueError("p must be (Z, 2 E + 1, n H, Mv)")
+        Z, E, Mv, H = p.shape[0], (p.shape[1] - 1) // 2, p.shape[3], int(H)
+        if H < 1 or p.shape[2] % H or p.shape[2] < H:
+            raise ValueError("p must hold a whole number of hops of H samples")
+        n = p.shape[2] // H
+        rec = np.zeros((n, Z, 3 * E + 1, Mv)) if record is None else np.ascontiguousarray(record, dtype=np.float64)
+        tot = np.zeros((Z, 3 * E + 1, Mv)) if totals is None else np.ascontiguousarray(totals, dtype=np.float64)
+        if rec.shape != (n, Z, 3 * E + 1, Mv) or tot.shape != (Z, 3 * E + 1, Mv):
+            raise ValueError("record must be (n, Z, 3 E + 1, Mv) and totals (Z, 3 E + 1, Mv)")
+        dp, dr, dt = self.to_device(p), self.to_device(rec), self.to_device(tot)
+        try:
+            self._chk(self.lib.apv_eval_energies(self.h, dp.ptr, Z, E, H, Mv, n, dr.ptr, dt.ptr))
+            return dr.download(rec.shape, np.float64), dt.download(tot.shape, np.float64)
+        finally:
+            for b in (dp, dr, dt):
+                b.free()
+
+    def bb_set_evaluation(self, rv_A, rv_B, ranks):
+        """Evaluation stage of the broadband stream, after bb_init (apv_bb_set_evaluation): rv_A / rv_B (Pv, L, Mv) float64, the
+        responses to the validation microphones of zone A / B; ranks: the evaluated ranks, ascending, among the stream's."""
+        rv_A = np.ascontiguousarray(rv_A, dtype=np.float64)
+        rv_B = np.ascontiguousarray(rv_B, dtype=np.float64)
+        if rv_A.ndim != 3 or rv_A.shape != rv_B.shape or rv_A.shape[1] != self.L:
+            raise ValueError("rv_A and rv_B must both be (Pv, n_srcs, Mv)")
+        r = np.ascontiguousarray(ranks, dtype=np.int32).ravel()
+        Pv, _, Mv = rv_A.shape
+        self._chk(self.lib.apv_bb_set_evaluation(self.h, Pv, Mv, _ptr(rv_A), _ptr(rv_B), int(r.size), _ptr(r) if r.size else None))
+
+    def bb_reset_evaluation(self):
+        """Totals and output histories of the broadband stream's evaluation stage to zero (apv_bb_reset_evaluation)."""
+        self._chk(self.lib.apv_bb_reset_evaluation(self.h))
 
     def set_synthesis(self, mode):
         """Synthesis of the subband stream, before stream_init (apv_stream_set_synthesis): "wola" (the reference's overlap-add)

@@ -63,6 +63,8 @@ What is different (keyword-only, after ``perceptual``)
     totals and histories, ``evaluation.metrics(totals)`` gives NMSE and contrast in dB (main.m:120-130); get_state() gains
     ``evaluation_history`` (Z, E + 1, Pv - 1, L) and ``evaluation_totals`` (Z, 3 E + 1, Mv).  Outputs, filters and every other state
     are those of the same stream without the keywords, bit for bit; process_signal runs such a stream hop by hop.
+    In broadband mode the same stage is switched on by a method instead, ``ap.enable_evaluation(validation_rir_A,
+    validation_rir_B, ranks=None)``, once and at any hop boundary; there process_signal evaluates a whole group of hops per launch.
   * ``evaluation_spectra=True`` (a bool; needs the validation responses): the evaluation stage also keeps the last block_size
     pressure samples per set and microphone and, after every hop t, transforms the frame that ends with the hop under the analysis
     window, P_t = rfft(window * p[(t + 1) H - N : (t + 1) H]) (zero before sample 0, unnormalised), and accumulates per bin
@@ -397,6 +399,14 @@ class apvast:
             return None
         if mode == "broadband":
             raise ValueError("validation_rir_A / validation_rir_B are a subband keyword: broadband mode has no evaluation stage")
+        a, b = apvast._check_validation_rirs(rv_A, rv_B, L)
+        r = apvast._check_rank_subset(ranks, range(1, int(V) + 1), "evaluation_ranks must be None or a strictly ascending list of ranks "
+                                      "within 1..number_of_eigenvectors")
+        return a, b, r
+
+    @staticmethod
+    def _check_validation_rirs(rv_A, rv_B, L):
+        """Float64 copies of the responses to the validation microphones: both given, one shape (Pv, L, Mv), finite."""
         if rv_A is None or rv_B is None:
             raise ValueError("validation_rir_A and validation_rir_B go together: both or neither")
         a, b = np.array(rv_A, dtype=np.float64), np.array(rv_B, dtype=np.float64)
@@ -406,19 +416,22 @@ class apvast:
             raise ValueError(f"validation_rir_*: (Pv, L, Mv) with L = {L} loudspeakers (the constructor's) and Pv, Mv >= 1, got {a.shape}")
         if not (np.isfinite(a).all() and np.isfinite(b).all()):
             raise ValueError("validation_rir_A and validation_rir_B must be finite")
-        V = int(V)
+        return a, b
+
+    @staticmethod
+    def _check_rank_subset(ranks, emitted, message):
+        """The evaluated ranks as a list of ints: None -> every emitted rank, else a strictly ascending, non-empty subset of them."""
+        emitted = [int(v) for v in emitted]
         if ranks is None:
-            r = list(range(1, V + 1))
-        else:
-            try:
-                r = list(ranks)
-            except TypeError:
-                raise ValueError("evaluation_ranks must be None or a strictly ascending list of ranks within 1..number_of_eigenvectors")
-            ok = len(r) >= 1 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 1 <= int(v) <= V for v in r)
-            if not ok or any(int(r[i]) <= int(r[i - 1]) for i in range(1, len(r))):
-                raise ValueError("evaluation_ranks must be None or a strictly ascending list of ranks within 1..number_of_eigenvectors")
-            r = [int(v) for v in r]
-        return a, b, r
+            return emitted
+        try:
+            r = list(ranks)
+        except TypeError:
+            raise ValueError(message)
+        ok = len(r) >= 1 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and int(v) in emitted for v in r)
+        if not ok or any(int(r[i]) <= int(r[i - 1]) for i in range(1, len(r))):
+            raise ValueError(message)
+        return [int(v) for v in r]
 
     @staticmethod
     def _check_evaluation_spectra(value, evaluation, mode):
@@ -699,11 +712,42 @@ class apvast:
     validation_rank_B = property(lambda self: self._validation_output(1, 3))
 
     # ---- the evaluation stage (validation_rir_A / validation_rir_B): read from the device when asked for ------------------
+    def _eval_stage(self):
+        """(rv_A, rv_B, ranks) of the object's evaluation stage -- the constructor's in subband mode, enable_evaluation()'s in
+        broadband mode -- or None."""
+        d = self.__dict__
+        return d.get("_bb_evaluation") if d.get("mode") == "broadband" else d.get("_evaluation")
+
     def _eval_dims(self):
-        if self.__dict__.get("_evaluation") is None:
-            raise RuntimeError("this object has no evaluation stage: pass validation_rir_A and validation_rir_B")
-        a, _, r = self._evaluation
+        if self._eval_stage() is None:
+            raise RuntimeError("this object has no evaluation stage: pass validation_rir_A and validation_rir_B (subband mode) "
+                               "or call enable_evaluation() (broadband mode)")
+        a, _, r = self._eval_stage()
         return int(self.run_A) + int(self.run_B), len(r), a.shape[0], a.shape[2]
+
+    def enable_evaluation(self, validation_rir_A, validation_rir_B, ranks=None):
+        """Broadband mode: switch the evaluation stage on, once, at any hop boundary (before the first hop included).  From here
+        on the device filters every hop it emits through the responses to the validation microphones -- float64 (Pv, L, Mv), finite,
+        Pv <= 20465 -- and keeps pressures, energies per hop and totals as the subband keywords ``validation_rir_A`` /
+        ``validation_rir_B`` do: evaluation_hops(), evaluation_totals(), predicted_pressure(), reset_evaluation() and
+        evaluation.metrics() work the same, get_state() gains ``evaluation_history`` and ``evaluation_totals``.  ``ranks``: the
+        evaluated ranks, a strictly ascending subset of the ranks the object emits (1..number_of_eigenvectors; in the MATLAB dialect
+        the entries of number_of_eigenvectors); None: all of them.  Histories start from silence and totals from zero here.
+        process_signal evaluates a whole group of hops per launch.  Outputs, filters and every other state are untouched."""
+        if self.mode != "broadband":
+            raise RuntimeError("enable_evaluation() is the broadband mode's switch: in subband mode pass validation_rir_A and "
+                               "validation_rir_B (and evaluation_ranks) to the constructor")
+        if self.__dict__.get("_bb_evaluation") is not None:
+            raise RuntimeError("enable_evaluation(): this object has its evaluation stage already")
+        a, b = self._check_validation_rirs(validation_rir_A, validation_rir_B, self.number_of_srcs)
+        if a.shape[0] > 20465:
+            raise ValueError("validation_rir_*: Pv <= 20465 (one loudspeaker's window of Pv - 1 + 16 float64 samples has to fit "
+                             "160 KB of LDS)")
+        r = self._check_rank_subset(ranks, self._ranks, "ranks must be None or a strictly ascending list of ranks the object emits: "
+                                    f"{list(self._ranks)}")
+        self._eng.bb_set_evaluation(a, b, r)
+        self._bb_evaluation = (a, b, r)
+        self._bb_eval_hops = 0              # hops in the record of the last call
 
     @staticmethod
     def _eval_split(e, E):
@@ -717,6 +761,9 @@ class apvast:
         Z, E, _, Mv = self._eval_dims()
         if self._hops == 0:
             return None
+        if self.mode == "broadband":
+            n = self._bb_eval_hops
+            return self._eval_split(self._eng.bb_get_state("eval_hops", (n, Z, 3 * E + 1, Mv)), E) if n else None
         n = self._eng.state_bytes("eval_hops") // (8 * Z * (3 * E + 1) * Mv)
         if n == 0:
             return None
@@ -728,6 +775,8 @@ class apvast:
         Z, E, _, Mv = self._eval_dims()
         if self._hops == 0:
             return None
+        if self.mode == "broadband":
+            return self._eval_split(self._eng.bb_get_state("eval_totals", (Z, 3 * E + 1, Mv)), E)
         return self._eval_split(self._eng.get_state("eval_totals", (Z, 3 * E + 1, Mv), np.float64), E)
 
     def predicted_pressure(self):
@@ -736,7 +785,12 @@ class apvast:
         Z, E, _, Mv = self._eval_dims()
         if self._hops == 0:
             return None
-        p = self._eng.get_state("eval_pressure", (Z, 2 * E + 1, self.hop_size, Mv), np.float64)
+        if self.mode == "broadband":
+            if not self._bb_eval_hops:
+                return None                   # enabled or resumed, no hop since
+            p = self._eng.bb_get_state("eval_pressure", (Z, 2 * E + 1, self.hop_size, Mv))
+        else:
+            p = self._eng.get_state("eval_pressure", (Z, 2 * E + 1, self.hop_size, Mv), np.float64)
         return {"bright": np.ascontiguousarray(p[:, :E]), "dark": np.ascontiguousarray(p[:, E:2 * E]),
                 "target": np.ascontiguousarray(p[:, 2 * E])}
 
@@ -795,6 +849,9 @@ class apvast:
         """Totals to zero and the output histories to silence: the next hop's totals are its own energies.  With
         evaluation_spectra=True the per-bin energies and the pressure ring too, with evaluation_detectability=True its totals."""
         self._eval_dims()
+        if self.mode == "broadband":
+            self._eng.bb_reset_evaluation()
+            return
         self._eng.reset_evaluation()
         self._detect_hops = 0
 
@@ -912,6 +969,8 @@ class apvast:
             self.set_state({"response": np.stack(resp), "target_response": np.stack(tresp)})
         self._hops = 0
         self._bb_cache = None
+        self._bb_evaluation = None          # enable_evaluation() switches the stage on
+        self._bb_eval_hops = 0
 
     def _refresh_broadband(self):
         """A hop has run: what the attributes hold is stale.  Nothing is fetched here (see _bb_fetch)."""
@@ -961,6 +1020,7 @@ class apvast:
         if self.mode == "broadband":
             out = self._eng.bb_process_block(input_A, input_B, self._n_out)      # (groups, H, L), fresh for every hop
             res = self._split_groups(out)
+            self._bb_eval_hops = 1
             self._refresh_broadband()
             return res
         out = self._eng.process_block(input_A, input_B, self._n_out)         # (groups, H, L): one (H, L) array per zone and rank
@@ -993,6 +1053,7 @@ class apvast:
             # writes (groups, n_samples, L) -- every zone program's and rank's whole signal as the array handed out below
             out = self._eng.bb_process_signal(input_A, input_B, self._n_out, out=out)
             res = self._split_groups(out)
+            self._bb_eval_hops = input_A.size // self.hop_size
             self._hops += input_A.size // self.hop_size - 1
             self._refresh_broadband()
             return res
@@ -1292,7 +1353,9 @@ def _state_rows():
     bb = lambda self: self.mode == "broadband"
     sub = lambda on: (lambda self: self.mode == "subband" and bool(on(self)))         # a subband feature behind its keyword
     win, forget = sub(lambda self: self.statistics_hops > 1), sub(lambda self: self.statistics_forgetting is not None)
-    fir, ev = sub(lambda self: self.synthesis == "fir"), sub(lambda self: self._evaluation is not None)
+    fir, ev_sub = sub(lambda self: self.synthesis == "fir"), sub(lambda self: self._evaluation is not None)
+    # the evaluation stage: the constructor's in subband mode, enable_evaluation()'s in broadband mode
+    ev = lambda self: ev_sub(self) or (bb(self) and getattr(self, "_bb_evaluation", None) is not None)
     evs, evd = sub(lambda self: self._evaluation_spectra), sub(lambda self: self._evaluation_detectability)
     live = lambda self: self._live_applied
     N = lambda self: self.block_size
@@ -1319,11 +1382,23 @@ def _state_rows():
                          lambda self, v: self._put_zones(name, v, dtype(self._eng)))
 
     def whole(key, name, accepts, shape, dtype=lambda e: np.float64):
-        """one engine array of a subband feature, handed out as float64; neither fetched nor sent where it has no elements"""
-        return _StateRow(key, accepts, None, shape,
-                         lambda self: (self._eng.get_state(name, shape(self), dtype(self._eng)).astype(np.float64) if all(shape(self))
-                                       else np.zeros(shape(self))),
-                         lambda self, v: all(shape(self)) and self._eng.set_state(name, np.ascontiguousarray(v, dtype=dtype(self._eng))))
+        """one engine array of a feature, handed out as float64 (what the broadband stream keeps); neither fetched nor sent where
+        it has no elements"""
+        def get(self):
+            if not all(shape(self)):
+                return np.zeros(shape(self))
+            if bb(self):
+                return self._eng.bb_get_state(name, shape(self))
+            return self._eng.get_state(name, shape(self), dtype(self._eng)).astype(np.float64)
+
+        def put(self, v):
+            if not all(shape(self)):
+                return
+            if bb(self):
+                self._eng.bb_set_state(name, np.ascontiguousarray(v, dtype=np.float64))
+            else:
+                self._eng.set_state(name, np.ascontiguousarray(v, dtype=dtype(self._eng)))
+        return _StateRow(key, accepts, None, shape, get, put)
 
     return (
         banks("response", 4, N),

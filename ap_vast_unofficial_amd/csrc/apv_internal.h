@@ -439,6 +439,32 @@ struct EvalAdvanceArgs {
 };
 hipError_t apv_launch_eval_advance(int x_f64, const EvalAdvanceArgs& a, hipStream_t s);
 
+// kernels_bbeval.hip: the evaluation stage of the broadband stream behind a pressure launch over n hops (see the file header).
+// p [Z][2 E + 1][n H][Mv] -> the energies of hop i into slot slot0 + i of rec (slots of [Z][3 E + 1][Mv]); the order of a hop's sum
+// depends on H alone.
+struct BbEvalEnergyArgs {
+    const double* p;
+    double* rec;
+    int slot0, Z, E, H, Mv, n;
+};
+bool apv_bbeval_sizes_ok(int Z, int E, int H, int Mv, int n, std::string* why);
+hipError_t apv_launch_bbeval_energies(const BbEvalEnergyArgs& a, hipStream_t s, std::string* why);
+// behind it: totals <- totals + slot, for the slots slot0 .. slot0 + n - 1 in order; and with Pv > 1 and n_hist > 0, new_hist[g]
+// [Pv - 1][L] <- the newest Pv - 1 samples of [old_hist[g] | the n H samples of group hist_src[g]], sample (g, t, l) of the launch at
+// hop[g hop_stride + t sn + l sl].  Everything float64.
+struct BbEvalAdvanceArgs {
+    const double* rec;
+    double* totals;
+    const double* old_hist;
+    double* new_hist;
+    const double* hop;
+    size_t hop_stride;
+    long sn, sl;
+    const int32_t* hist_src;
+    int slot0, Z, E, H, Mv, n, Pv, L, n_hist;
+};
+hipError_t apv_launch_bbeval_advance(const BbEvalAdvanceArgs& a, hipStream_t s);
+
 // kernels_evalspec.hip: per-bin evaluation spectra (see the file header).  Three launches behind the two above: the hop's
 // pressures p [Z (2 E + 1)][H][Mv] into the ring [Z (2 E + 1) Mv][N] at the stream's ring offset (the offset AFTER the hop's
 // advance, as K1 and the analysis take it), the windowed float64 transform of every ring row into spec [N/2 + 1][Z (2 E + 1) Mv]

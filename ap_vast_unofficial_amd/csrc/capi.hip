@@ -1206,6 +1206,28 @@ int apv_eval_pressure(apv_handle* h, const void* d_y, const double* d_rv, int32_
     return APV_OK;
 }
 
+int apv_eval_energies(apv_handle* h, const double* d_p, int32_t Z, int32_t E, int32_t H, int32_t Mv, int32_t n_hops, double* d_record,
+                      double* d_totals) {
+    if (!h || !d_p || !d_record || !d_totals) return fail(h, APV_ERR_ARG, "apv_eval_energies: null device pointer");
+    std::string why;
+    if (!apv_bbeval_sizes_ok(Z, E, H, Mv, n_hops, &why)) return fail(h, APV_ERR_ARG, why);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    BbEvalEnergyArgs a{};
+    a.p = d_p; a.rec = d_record; a.slot0 = 0;
+    a.Z = Z; a.E = E; a.H = H; a.Mv = Mv; a.n = n_hops;
+    hipError_t e = apv_launch_bbeval_energies(a, h->stream, &why);
+    if (e == hipSuccess) {
+        BbEvalAdvanceArgs adv{};
+        adv.rec = d_record; adv.totals = d_totals;
+        adv.slot0 = 0; adv.Z = Z; adv.E = E; adv.H = H; adv.Mv = Mv; adv.n = n_hops; adv.Pv = 1; adv.L = 1; adv.n_hist = 0;
+        e = apv_launch_bbeval_advance(adv, h->stream);
+    }
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
 int apv_eval_spectrum_step(apv_handle* h, const double* d_pressure, double* d_ring, int32_t ring_off, int32_t N, int32_t H, int32_t Z,
                            int32_t E, int32_t Mv, double* d_totals) {
     if (!h || !d_pressure || !d_ring || !d_totals) return fail(h, APV_ERR_ARG, "null device pointer");

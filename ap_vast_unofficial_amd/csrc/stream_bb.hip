@@ -20,7 +20,9 @@
 #include "apv_owned.h"
 #include "state_layout.h"
 
+#include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 
@@ -104,6 +106,21 @@ struct apv_bb {
     hipEvent_t ev_front[2], ev_back[2];      // group set filled / group set read for the last time
     hipEvent_t ev_out[2];                    // a group's outputs have reached g_pin
     FirLive live;          // responses reassigned between hops (apv_bb_set_rirs): the correction tails still to be added to K1's output
+    // evaluation stage (apv_bb_set_evaluation, kernels_bbeval.hip); be_on = 0: off, nothing below exists
+    std::vector<int> rank_vals;   // the ranks of the V solutions, as d_ranks holds them
+    int be_on;
+    int be_Pv, be_Mv, be_E, be_Z; // response taps, validation microphones, evaluated ranks, zone programs that run
+    int be_sets, be_nhist;        // pressure sets be_Z (2 be_E + 1), evaluated groups be_Z (be_E + 1)
+    int be_cur;                   // the history buffer the next launch reads
+    double* be_rv[2];             // [Pv][L][Mv] responses to the validation microphones of zone A, zone B
+    int32_t* be_map;              // [sets][4] {group of the emitted hop, history slot, bank, -} of every pressure set
+    int32_t* be_hsrc;             // [nhist] the group behind every history slot
+    double* be_hist[2];           // [nhist][Pv - 1][L], alternating
+    double* be_p;                 // [sets][be_p_hops H][Mv]; a launch over c hops fills [sets][c H][Mv] of it
+    int be_p_hops, be_last;       // hops the pressure buffer holds per set; hops of the last launch (0: none yet)
+    double* be_tot;               // [Z][3 E + 1][Mv]
+    double* be_rec;               // [be_cap] slots of [Z][3 E + 1][Mv]: the energies of every hop of the last call
+    int be_cap, be_nrec;          // slots allocated; slots the last call filled
     ApvOwned own;          // every buffer, pinned block, event and stream above: made through it, freed by it
 };
 
@@ -274,6 +291,7 @@ int apv_bb_init(apv_handle* h, int32_t rir_len, const double* h_rir_A, const dou
     s->n_out = nz * nsol * L + 2 * L;
     s->out_group = c.out_layout == 1 ? L : 0;
     s->max_rank = ranks.back();
+    s->rank_vals = ranks;
     s->full_valid = 1;
     BCHK(h, s->own.device(&s->d_ranks, sizeof(int) * nsol));
     BCHK(h, hipMemcpyAsync(s->d_ranks, ranks.data(), sizeof(int) * nsol, hipMemcpyHostToDevice, h->stream));
@@ -579,6 +597,168 @@ static int bb_back(apv_handle* h, apv_bb* s, const BbHop& q, double* d_out, long
     return APV_OK;
 }
 
+static int bb_group_size(const apv_handle* h, const apv_bb* s, int n_hops);
+
+// ---- evaluation stage (apv_bb_set_evaluation) ---------------------------------------------------------------------------------------
+// The emitted samples of n consecutive hops filtered through the responses to the validation microphones, on the handle's stream:
+// ONE pressure launch over the n H samples (eval_pressure_kernel's bits depend on (Pv, L) and the data, not on the launch: a group
+// of hops is a long hop with the history in front), the energies of each of the n hops into the record's slots slot0 .. slot0 + n - 1,
+// and one launch that adds them to the totals in hop order and advances the histories.  d_out: the hops as bb_back emitted them --
+// sample-major (cfg.out_layout = 1) group q's n H samples start at d_out + q gstride (0: H L) and are consecutive in time;
+// channel-major [n_out][H], where only n = 1 is contiguous in time.     replaces: Matlab/main.m:64-76 with predictPressure.m:12-16
+static int bb_evaluate(apv_handle* h, apv_bb* s, const double* d_out, size_t gstride, int n, int slot0) {
+    hipStream_t st = h->stream;
+    const int H = s->H, L = s->L, c = s->be_cur;
+    const bool sample_major = s->out_group > 0;
+    if (!sample_major && n != 1) return apv_fail(h, APV_ERR_ARG, "evaluation: channel-major hops are evaluated one at a time");
+    if (n > s->be_p_hops || slot0 < 0 || slot0 + n > s->be_cap) return apv_fail(h, APV_ERR_STATE, "evaluation: buffers smaller than the launch");
+    const size_t hop_stride = sample_major ? (gstride ? gstride : (size_t)H * L) : (size_t)L * H;
+    const long sn = sample_major ? L : 1, sl = sample_major ? 1 : H;
+    EvalPressureArgs a{};
+    a.hist = s->be_hist[c]; a.hop = d_out;
+    a.hist_stride = (size_t)(s->be_Pv - 1) * L; a.hop_stride = hop_stride;
+    a.sn = sn; a.sl = sl;
+    a.rv[0] = s->be_rv[0]; a.rv[1] = s->be_rv[1];
+    a.map = s->be_map; a.p = s->be_p;
+    a.n_sets = s->be_sets; a.Pv = s->be_Pv; a.H = n * H; a.L = L; a.Mv = s->be_Mv;
+    std::string why;
+    hipError_t e = apv_launch_eval_pressure(1, a, st, &why);
+    if (e == hipSuccess) {
+        BbEvalEnergyArgs en{};
+        en.p = s->be_p; en.rec = s->be_rec; en.slot0 = slot0;
+        en.Z = s->be_Z; en.E = s->be_E; en.H = H; en.Mv = s->be_Mv; en.n = n;
+        e = apv_launch_bbeval_energies(en, st, &why);
+    }
+    if (e != hipSuccess) return apv_fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    BbEvalAdvanceArgs adv{};
+    adv.rec = s->be_rec; adv.totals = s->be_tot;
+    adv.old_hist = s->be_hist[c]; adv.new_hist = s->be_hist[c ^ 1];
+    adv.hop = d_out; adv.hop_stride = hop_stride; adv.sn = sn; adv.sl = sl;
+    adv.hist_src = s->be_hsrc;
+    adv.slot0 = slot0; adv.Z = s->be_Z; adv.E = s->be_E; adv.H = H; adv.Mv = s->be_Mv; adv.n = n; adv.Pv = s->be_Pv; adv.L = L;
+    adv.n_hist = s->be_nhist;
+    BCHK(h, apv_launch_bbeval_advance(adv, st));
+    if (s->be_Pv > 1) s->be_cur = c ^ 1;
+    s->be_last = n;
+    return APV_OK;
+}
+
+// the per-call record holds n_hops slots and the pressure buffer the launch of `group` hops; called before a call's first launch,
+// with nothing of an earlier call in flight
+static int bb_eval_reserve(apv_handle* h, apv_bb* s, int n_hops, int group) {
+    const size_t slot = (size_t)s->be_Z * (3 * s->be_E + 1) * s->be_Mv;
+    if (n_hops > s->be_cap) {
+        s->own.release(s->be_rec);
+        s->be_cap = 0;
+        BCHK(h, s->own.zeroed(&s->be_rec, slot * n_hops, sizeof(double), h->stream));
+        s->be_cap = n_hops;
+    }
+    if (group > s->be_p_hops) {
+        s->own.release(s->be_p);
+        s->be_p_hops = s->be_last = 0;
+        BCHK(h, s->own.zeroed(&s->be_p, (size_t)s->be_sets * group * s->H * s->be_Mv, sizeof(double), h->stream));
+        s->be_p_hops = group;
+        BCHK(h, apv_eval_pressure_prepare(1, s->be_Pv, group * s->H, s->L));
+    }
+    s->be_nrec = 0;
+    return APV_OK;
+}
+
+static void bb_eval_free(apv_bb* s) {
+    for (int z = 0; z < 2; ++z) {
+        s->own.release(s->be_rv[z]);
+        s->own.release(s->be_hist[z]);
+    }
+    s->own.release(s->be_map);
+    s->own.release(s->be_hsrc);
+    s->own.release(s->be_p);
+    s->own.release(s->be_tot);
+    s->own.release(s->be_rec);
+    s->be_on = s->be_cap = s->be_nrec = s->be_p_hops = s->be_last = s->be_cur = 0;
+}
+
+// Evaluation stage of the broadband stream: see include/apvast_hip.h.
+int apv_bb_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
+                          const int32_t* ranks) {
+    if (!h || !h->bb) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation: apv_bb_init has not been called");
+    apv_bb* s = h->bb;
+    if (s->be_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation: the stream has its evaluation stage already");
+    if (!h_rvA || !h_rvB || !ranks) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation: null argument");
+    if (Pv < 1 || Mv < 1) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation: Pv and Mv must be at least 1");
+    if (!apv_eval_pressure_fits(Pv))
+        return apv_fail(h, APV_ERR_ARG, "evaluation: one loudspeaker's window of Pv - 1 + 16 float64 samples does not fit 160 KB of LDS (Pv <= 20465)");
+    if ((Mv + 15) / 16 > 65535) return apv_fail(h, APV_ERR_ARG, "evaluation: at most 16 x 65535 validation microphones");
+    if (n_ranks < 1 || n_ranks > s->V) return apv_fail(h, APV_ERR_ARG, "evaluation: n_ranks must be within 1..the stream's ranks");
+    const BbZones zn(s->zones);
+    const int E = n_ranks, nz = zn.nz, V = s->V, L = s->L, H = s->H, nfilt = nz * V;
+    const int sets = nz * (2 * E + 1), nhist = nz * (E + 1);
+    // per zone program that runs, the pressure sets [bright of E ranks][dark of E ranks][target]; bright and target through the
+    // responses of the program's own zone, dark through the other zone's (as apv_stream_init lays them out)
+    std::vector<int32_t> map((size_t)4 * sets, 0), hsrc(nhist, 0);
+    int zi = 0;
+    for (int z = 0; z < 2; ++z) {
+        if (!zn.run[z]) continue;
+        for (int e = 0; e <= E; ++e) {
+            int grp = nfilt + z;                             // e = E: the program's target output A_t / B_t
+            if (e < E) {
+                if (e && ranks[e] <= ranks[e - 1]) return apv_fail(h, APV_ERR_ARG, "evaluation: ranks must be strictly ascending");
+                const auto it = std::find(s->rank_vals.begin(), s->rank_vals.end(), (int)ranks[e]);
+                if (it == s->rank_vals.end()) return apv_fail(h, APV_ERR_ARG, "evaluation: a rank that the stream does not emit");
+                grp = zi * V + (int)(it - s->rank_vals.begin());
+            }
+            const int hs = zi * (E + 1) + e;
+            hsrc[hs] = grp;
+            int32_t* mb = &map[(size_t)4 * (zi * (2 * E + 1) + (e < E ? e : 2 * E))];
+            mb[0] = grp; mb[1] = hs; mb[2] = z;
+            if (e < E) {
+                int32_t* md = mb + 4 * E;
+                md[0] = grp; md[1] = hs; md[2] = z ^ 1;
+            }
+        }
+        ++zi;
+    }
+    std::string why;
+    if (!apv_bbeval_sizes_ok(nz, E, H, Mv, 1, &why)) return apv_fail(h, APV_ERR_ARG, why);
+    BCHK(h, hipSetDevice(h->device));
+    BCHK(h, hipStreamSynchronize(h->stream));
+    s->be_Pv = Pv; s->be_Mv = Mv; s->be_E = E; s->be_Z = nz; s->be_sets = sets; s->be_nhist = nhist;
+    struct Guard { apv_bb* s; bool ok; ~Guard() { if (!ok) bb_eval_free(s); } } built{s, false};
+    hipStream_t st = h->stream;
+    const size_t bank = (size_t)Pv * L * Mv;
+    for (int z = 0; z < 2; ++z) {
+        BCHK(h, s->own.device(&s->be_rv[z], sizeof(double) * bank));
+        BCHK(h, hipMemcpyAsync(s->be_rv[z], z ? h_rvB : h_rvA, sizeof(double) * bank, hipMemcpyHostToDevice, st));
+    }
+    BCHK(h, s->own.device(&s->be_map, sizeof(int32_t) * map.size()));
+    BCHK(h, s->own.device(&s->be_hsrc, sizeof(int32_t) * hsrc.size()));
+    BCHK(h, hipMemcpyAsync(s->be_map, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, st));
+    BCHK(h, hipMemcpyAsync(s->be_hsrc, hsrc.data(), sizeof(int32_t) * hsrc.size(), hipMemcpyHostToDevice, st));
+    if (Pv > 1)
+        for (int b = 0; b < 2; ++b) BCHK(h, s->own.zeroed(&s->be_hist[b], (size_t)nhist * (Pv - 1) * L, sizeof(double), st));
+    BCHK(h, s->own.zeroed(&s->be_tot, (size_t)nz * (3 * E + 1) * Mv, sizeof(double), st));
+    // the kernels a hop and the largest group of apv_bb_process_signal select, outside any timed path
+    BCHK(h, apv_eval_pressure_prepare(1, Pv, H, L));
+    BCHK(h, apv_eval_pressure_prepare(1, Pv, bb_group_size(h, s, INT_MAX) * H, L));
+    const int rc = bb_eval_reserve(h, s, 1, 1);
+    if (rc != APV_OK) return rc;
+    BCHK(h, hipStreamSynchronize(st));                       // map, hsrc and the caller's responses may go
+    s->be_on = 1;
+    built.ok = true;
+    return APV_OK;
+}
+
+// "eval_totals" and both "eval_history" buffers to zero: the next hop's totals are its own energies
+int apv_bb_reset_evaluation(apv_handle* h) {
+    if (!h || !h->bb || !h->bb->be_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_reset_evaluation: no broadband stream with an evaluation stage");
+    apv_bb* s = h->bb;
+    BCHK(h, hipSetDevice(h->device));
+    BCHK(h, hipMemsetAsync(s->be_tot, 0, sizeof(double) * (size_t)s->be_Z * (3 * s->be_E + 1) * s->be_Mv, h->stream));
+    const size_t hb = sizeof(double) * (size_t)s->be_nhist * (s->be_Pv - 1) * s->L;
+    for (int b = 0; b < 2 && hb > 0; ++b) BCHK(h, hipMemsetAsync(s->be_hist[b], 0, hb, h->stream));
+    BCHK(h, hipStreamSynchronize(h->stream));
+    return APV_OK;
+}
+
 int apv_bb_process_block(apv_handle* h, const double* h_in_A, const double* h_in_B, double* h_out) {
     if (!h || !h_in_A || !h_in_B || !h_out) return apv_fail(h, APV_ERR_ARG, "null argument");
     apv_bb* s = h->bb;
@@ -606,8 +786,16 @@ int apv_bb_process_block(apv_handle* h, const double* h_in_A, const double* h_in
     // a result array from apv_host_alloc receives the hop by DMA; any other goes through the handle's page-locked buffer and a copy
     const size_t out_bytes = sizeof(double) * (size_t)s->n_out * H;
     const bool direct = host_is_pinned(h_out, out_bytes, false);
-    rc = bb_back(h, s, q, s->out, 0, direct ? h_out : s->pin_out, s->spec);
+    double* const dst = direct ? h_out : s->pin_out;
+    rc = bb_back(h, s, q, s->out, 0, s->be_on ? nullptr : dst, s->spec);
     if (rc != APV_OK) return rc;
+    if (s->be_on) {
+        // the evaluation stage behind the synthesis, in front of the copy back
+        s->be_nrec = 0;
+        if ((rc = bb_evaluate(h, s, s->out, 0, 1, 0)) != APV_OK) return rc;
+        s->be_nrec = 1;
+        BCHK(h, hipMemcpyAsync(dst, s->out, out_bytes, hipMemcpyDeviceToHost, st));
+    }
     BCHK(h, hipStreamSynchronize(st));
     BCHK(h, hipGetLastError());
     if (!direct) std::memcpy(h_out, s->pin_out, out_bytes);
@@ -748,6 +936,11 @@ static int bb_signal_prepare(BbSignalCall& c) {
         BCHK(h, s->own.pinned(&s->g_pin, sizeof(double) * 2 * c.z_out));
         s->g_pin_cap = c.z_out;
     }
+    if (s->be_on) {
+        const int rc = bb_eval_reserve(h, s, c.n_hops, s->out_group > 0 ? c.G : 1);
+        if (rc != APV_OK) return rc;
+        BCHK(h, hipStreamSynchronize(h->stream));            // the zero fills
+    }
     c.fs = s->front;
     c.cs = s->copy ? s->copy : h->stream;
     c.status.assign(gz, 0);
@@ -850,6 +1043,16 @@ static int signal_back(BbSignalCall& c, int g) {
         bool bad = false;
         for (int z = 0; z < nz; ++z) bad = bad || c.status[(size_t)i * nz + z] == 2;
         c.bad_hops += bad;
+    }
+    if (s->be_on) {
+        // the evaluation stage of the whole group: its samples are consecutive in time where the hops are emitted sample-major
+        // (group g + 2's wait for ev_out[set] orders the reuse of this output set behind these launches too: the same stream)
+        int rc = APV_OK;
+        if (s->out_group > 0) rc = bb_evaluate(c.h, s, c.gout(g), (size_t)gstride, c.count(g), c.hop0(g));
+        else
+            for (int i = 0; i < c.count(g) && rc == APV_OK; ++i) rc = bb_evaluate(c.h, s, c.gout(g) + (size_t)i * c.HL, 0, 1, c.hop0(g) + i);
+        if (rc != APV_OK) return rc;
+        s->be_nrec = c.hop0(g) + c.count(g);
     }
     return APV_OK;
 }
@@ -1083,6 +1286,26 @@ static int bb_lookup(apv_handle* h, const char* name, double** d, size_t* count,
     return apv_fail(h, APV_ERR_STATE, std::string("unknown broadband state name: ") + name);
 }
 
+// The names only a stream with the evaluation stage has, with the split of the subband stream's table (stream_state.hip):
+// "eval_pressure" [Z][2 E + 1][H][Mv], the last hop's, and "eval_hops" [hops of the last call][Z][3 E + 1][Mv] are read-only;
+// "eval_totals" [Z][3 E + 1][Mv] and "eval_history" [Z][E + 1][Pv - 1][L] (the buffer the next launch reads) can be set.
+struct BbEvalRef {
+    double* d;
+    size_t count;
+    bool read_only, last_rows;      // last_rows: H rows of each set behind a launch of be_last hops
+};
+static bool bb_eval_lookup(apv_bb* s, const char* name, BbEvalRef* r) {
+    if (!s->be_on) return false;
+    const size_t slot = (size_t)s->be_Z * (3 * s->be_E + 1) * s->be_Mv;
+    const auto is = [&](const char* n) { return std::strcmp(name, n) == 0; };
+    if (is("eval_pressure")) *r = BbEvalRef{s->be_p, (size_t)s->be_sets * s->H * s->be_Mv, true, true};
+    else if (is("eval_hops")) *r = BbEvalRef{s->be_rec, slot * s->be_nrec, true, false};
+    else if (is("eval_totals")) *r = BbEvalRef{s->be_tot, slot, false, false};
+    else if (is("eval_history")) *r = BbEvalRef{s->be_hist[s->be_cur], (size_t)s->be_nhist * (s->be_Pv - 1) * s->L, false, false};
+    else return false;
+    return true;
+}
+
 // The per-hop path solves for the eigenpairs the filters use (kernels_gevd_lead.hip).  lambda_* / U_* in full (apvast.py:380-387)
 // are attributes somebody may read afterwards: the first read after such a hop runs the complete joint diagonalisation on
 // the hop's matrices, which are still there (R is never modified by the solver).
@@ -1106,6 +1329,22 @@ int apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t coun
         BCHK(h, hipSetDevice(h->device));
         return apv_live_state(h, s->live, apv_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), h_dst, sizeof(double) * count,
                               true, h->stream);
+    }
+    BbEvalRef ev{};
+    if (bb_eval_lookup(h->bb, name, &ev)) {
+        apv_bb* s = h->bb;
+        if (count != ev.count) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+        if (ev.count == 0) return APV_OK;                    // "eval_history" with Pv = 1, "eval_hops" before the first hop
+        BCHK(h, hipSetDevice(h->device));
+        if (ev.last_rows) {
+            const size_t hop = sizeof(double) * (size_t)s->H * s->be_Mv, last = s->be_last > 0 ? s->be_last : 1;
+            BCHK(h, hipMemcpy2DAsync(h_dst, hop, ev.d + (last - 1) * (hop / sizeof(double)), last * hop, hop, s->be_sets,
+                                     hipMemcpyDeviceToHost, h->stream));
+        } else {
+            BCHK(h, hipMemcpyAsync(h_dst, ev.d, sizeof(double) * ev.count, hipMemcpyDeviceToHost, h->stream));
+        }
+        BCHK(h, hipStreamSynchronize(h->stream));
+        return APV_OK;
     }
     double* d; size_t need; int rows, len, off;
     int rc = bb_lookup(h, name, &d, &need, &rows, &len, &off);
@@ -1135,6 +1374,16 @@ int apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size_
         BCHK(h, hipStreamSynchronize(h->stream));
         return apv_live_state(h, s->live, apv_live_index(name), s->P, s->H, s->C, s->M, sizeof(double), const_cast<double*>(h_src),
                               sizeof(double) * count, false, h->stream);
+    }
+    BbEvalRef ev{};
+    if (bb_eval_lookup(h->bb, name, &ev)) {
+        if (ev.read_only) return apv_fail(h, APV_ERR_STATE, std::string(name) + " is read-only");
+        if (count != ev.count) return apv_fail(h, APV_ERR_STATE, "state size mismatch");
+        if (ev.count == 0) return APV_OK;
+        BCHK(h, hipSetDevice(h->device));
+        BCHK(h, hipMemcpyAsync(ev.d, h_src, sizeof(double) * ev.count, hipMemcpyHostToDevice, h->stream));
+        BCHK(h, hipStreamSynchronize(h->stream));
+        return APV_OK;
     }
     double* d; size_t need; int rows, len, off;
     int rc = bb_lookup(h, name, &d, &need, &rows, &len, &off);

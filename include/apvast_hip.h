@@ -358,6 +358,14 @@ int  apv_eval_detect_step(apv_handle* h, const void* d_spec, int32_t N, int32_t 
  * Pv > 20465.                                             replaces: Matlab/predictPressure.m:12-16 */
 int  apv_eval_pressure(apv_handle* h, const void* d_y, const double* d_rv, int32_t G, int32_t L, int32_t Pv, int32_t H, int32_t Mv,
                        double* d_p);
+/* The energy reduction of the broadband stream's evaluation stage alone, on the handle's stream: d_p [Z][2 E + 1][n_hops H][Mv]
+ * float64 pressures (per program: bright of the E ranks, dark of the E ranks, target) of n_hops consecutive hops -> d_record
+ * [n_hops][Z][3 E + 1][Mv], per hop bright = sum p_bright^2, dark = sum p_dark^2, error = sum (p_target - p_bright)^2 per rank and
+ * target = sum p_target^2 over the hop's H samples, summed in an order that depends on H alone; then d_totals [Z][3 E + 1][Mv]
+ * <- d_totals + d_record[i], i ascending.  No atomics.  APV_ERR_ARG for null pointers, Z outside 1..2, another size below 1, or
+ * n_hops x H of 2^31 and more.                            replaces: Matlab/main.m:120-130, the sums */
+int  apv_eval_energies(apv_handle* h, const double* d_p, int32_t Z, int32_t E, int32_t H, int32_t Mv, int32_t n_hops, double* d_record,
+                       double* d_totals);
 
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
@@ -611,6 +619,27 @@ int  apv_bb_set_rirs(apv_handle* h, int32_t rir_len, const double* h_rir_A, cons
 /* float64 state arrays by name (stream_bb.hip); `count` = number of doubles */
 int  apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t count);
 int  apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size_t count);
+/* Evaluation stage of the broadband stream (off unless this is called): behind the synthesis, and in front of the copy back, the
+ * device filters the samples it emits through the responses to validation microphones and reduces the pressures to energies per
+ * hop and microphone; definitions, pressure sets, group order and arguments as for apv_stream_set_evaluation, with the stream's own
+ * ranks (1..number_of_eigenvectors, or the list of apv_bb_set_rank_list) in place of the handle's rank list.  Called after
+ * apv_bb_init, once, at any hop boundary: the histories start from silence and the totals from zero there.
+ * apv_bb_process_block evaluates its hop in three launches (pressures; energies; totals and histories); apv_bb_process_signal with
+ * cfg.out_layout = 1 evaluates a whole group of hops in the same three -- a group's samples are consecutive in time, and the
+ * pressure kernel's bits do not depend on the launch -- and hop by hop with the channel-major layout.  The order in which a hop's
+ * energy is summed depends on the hop size alone (csrc/kernels_bbeval.hip), so both paths give the same bits for the same samples.
+ * States only such a stream has (apv_bb_get_state / apv_bb_set_state, counts in doubles):
+ *   "eval_pressure" [Z][2 E + 1][H][Mv], the last hop's; read-only
+ *   "eval_hops"     [n][Z][3 E + 1][Mv], the n hops of the last apv_bb_process_* call (the caller knows n); read-only
+ *   "eval_totals"   [Z][3 E + 1][Mv], total = total + hop, one addition per hop in hop order
+ *   "eval_history"  [Z][E + 1][Pv - 1][L], the newest Pv - 1 emitted samples of every evaluated group, oldest first
+ * APV_ERR_ARG (nothing changed) without apv_bb_init, on a second call, for null pointers, Pv < 1, Mv < 1, Pv > 20465, n_ranks
+ * outside 1..the stream's ranks, ranks not strictly ascending or not among the stream's.
+ *                                                         replaces: Matlab/main.m:64-76, 120-130 with predictPressure.m:12-16 */
+int  apv_bb_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
+                           const int32_t* ranks);
+/* "eval_totals" and both history buffers to zero: the next hop's totals equal its own energies.  APV_ERR_ARG without such a stream. */
+int  apv_bb_reset_evaluation(apv_handle* h);
 
 /* ---- evaluation and the static solver, float64 ------------------------- */
 /* p[t][m] = sum_s filter(rir[:, s, m], 1, x[:, s])[t].  h_x [T][L], h_rir [P][L][M], h_out [T][M].
