@@ -90,6 +90,8 @@ template <> struct Mfma16<float> {
     static __device__ __forceinline__ int row(int lane, int t) { return 4 * (lane >> 4) + t; }
 };
 
+__device__ __forceinline__ double rows_sum2(double x, double y);       // sums over the four rows of a wave: defined with the lane swaps below
+
 struct NoStamp { __device__ __forceinline__ void operator()(int) const {} };
 // `stamp(i)`: diagnostic hook (stage stamps of the diagnostic kernel instantiation; NoStamp in the product)
 // WITH_D: also r = X^H d (a compile-time flag: tested at run time, `dvec != nullptr` put every d load into a basic block of its own
@@ -213,9 +215,15 @@ __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* 
         for (int t = 0; t < 4; ++t) dst[MM::row(lane, t) * LD + col].y = im[t] - pt[t];
     }
     if constexpr (WITH_D) {
-        rx += __shfl_xor(rx, 16, 64); ry += __shfl_xor(ry, 16, 64);
-        rx += __shfl_xor(rx, 32, 64); ry += __shfl_xor(ry, 32, 64);
-        if (lane < N) sr[lane] = mk<T>(rx, ry);
+        if constexpr (TWO) {
+            // the four rows' partial sums meet on the VALU (rows_sum2); row 0 stores the real parts, row 1 the imaginary ones
+            const T s = rows_sum2(rx, ry);
+            if (lane < 2 * N) reinterpret_cast<T*>(&sr[col])[msub] = s;
+        } else {
+            rx += __shfl_xor(rx, 16, 64); ry += __shfl_xor(ry, 16, 64);
+            rx += __shfl_xor(rx, 32, 64); ry += __shfl_xor(ry, 32, 64);
+            if (lane < N) sr[lane] = mk<T>(rx, ry);
+        }
     }
 }
 
@@ -326,6 +334,57 @@ __device__ __forceinline__ void xswap_col4(double& t, double& b) {
     t = __hiloint2double(th, tl);
     b = __hiloint2double(bh, bl);
 }
+// ---- sums over the four 16-lane rows of a wave (lanes l, l ^ 16, l ^ 32, l ^ 48) by lane swaps on the VALU ----
+// The float64 kernel's matrix-vector stages leave four partial sums per element, one in each row.  As `v += __shfl_xor(v, 16)`,
+// `v += __shfl_xor(v, 32)` a double costs four ds_bpermute_b32; v_permlane16_swap and v_permlane32_swap deliver the same operands
+// to the same two additions, (r0 + r1) + (r2 + r3) up to the order inside an addition, so every sum keeps its bits.
+// With rows (a0, a1, a2, a3) of `a` and (b0, ...) of `b`: xswap_row<1> leaves a = (a0, b0, a2, b2), b = (a1, b1, a3, b3);
+// xswap_row<2> leaves a = (a0, a1, b0, b1), b = (a2, a3, b2, b3).
+// one value, the sum in every lane (T: int or double)
+template <typename T> __device__ __forceinline__ T rows_sum(T v) {
+    T c = v;
+    xswap_row<1>(v, c);                  // v = (v0, v0, v2, v2), c = (v1, v1, v3, v3)
+    v += c;
+    c = v;
+    xswap_row<2>(v, c);                  // v = (s0, s1, s0, s1), c = (s2, s3, s2, s3)
+    return v + c;
+}
+// two values at the price of one: the sum of x in rows 0 and 2, the sum of y in rows 1 and 3 (seven instructions for two doubles)
+__device__ __forceinline__ double rows_sum2(double x, double y) {
+    xswap_row<1>(x, y);                  // x = (x0, y0, x2, y2), y = (x1, y1, x3, y3)
+    double s = x + y, c = s;
+    xswap_row<2>(s, c);                  // s = (s0, s1, s0, s1), c = (s2, s3, s2, s3)
+    return s + c;
+}
+// the same with both sums in every lane: one more swap of the result with its copy
+__device__ __forceinline__ void rows_sum2_all(double& x, double& y) {
+    double s = rows_sum2(x, y), c = s;
+    xswap_row<1>(s, c);                  // s = (sum x) in every row, c = (sum y) in every row
+    x = s;
+    y = c;
+}
+// v of another lane of the row of sixteen or of the quad (DPP control CTRL), for a double: two moves
+template <int CTRL> __device__ __forceinline__ double dpp_move(double v) {
+    return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false),
+                            __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false));
+}
+// Sum over the 64 lanes in the butterfly order of wave_sum (lane ^ 32, 16, 8, 4, 2, 1), so that the sum keeps its bits: the
+// two row stages by swaps, lane ^ 8 by row_ror:8, lane ^ 4 by row_ror:4 (after the ^ 8 stage the row has period 8, so the lane
+// four places on holds what lane ^ 4 holds), lane ^ 2 and lane ^ 1 by quad_perm.  Every lane ends with the same value.
+__device__ __forceinline__ double wave_sum_valu(double v) {
+    double c = v;
+    xswap_row<2>(v, c);                  // v = (v0, v1, v0, v1), c = (v2, v3, v2, v3)
+    v += c;
+    c = v;
+    xswap_row<1>(v, c);                  // v = (s0, s0, s2, s2), c = (s1, s1, s3, s3): s2 = s0 and s3 = s1 by now
+    v += c;
+    v += dpp_move<0x128>(v);             // row_ror:8
+    v += dpp_move<0x124>(v);             // row_ror:4
+    v += dpp_move<0x4E>(v);              // quad_perm [2,3,0,1]
+    v += dpp_move<0xB1>(v);              // quad_perm [1,0,3,2]
+    return v;
+}
+
 template <int TB, typename T> __device__ __forceinline__ void cxswap_row(Cx<T>& t, Cx<T>& b) {
     xswap_row<TB>(t.x, b.x);
     xswap_row<TB>(t.y, b.y);

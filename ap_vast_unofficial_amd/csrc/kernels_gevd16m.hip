@@ -612,7 +612,10 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
         }
         // (wave-uniform: kept in scalar registers -- the vector registers of this kernel are all spoken for; as a vector value the
         // scaled norm was spilled on the common path, 8 bytes per lane = 17 MB of scratch written per launch)
-        const T normF2 = uniform_scalar(wave_sum(nrm));
+        // float64: the butterfly on the VALU (wave_sum_valu: the same additions in the same order, and every lane holds the total)
+        T normF2;
+        if constexpr (sizeof(T) == 8) normF2 = uniform_scalar(wave_sum_valu(nrm));
+        else normF2 = uniform_scalar(wave_sum(nrm));
         wsync();
         stamp(3);
         if (dstop == 3) return;
@@ -720,9 +723,8 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                         num = __builtin_fma(vv[t].y, accT[t].y, __builtin_fma(vv[t].x, accT[t].x, num));
                         g = __builtin_fma(vv[t].y, vv[t].y, __builtin_fma(vv[t].x, vv[t].x, g));
                     }
-                    // the column's sixteen rows sit in this lane's four slots and in lanes ^ 16, ^ 32
-                    num += __shfl_xor(num, 16, 64); g += __shfl_xor(g, 16, 64);
-                    num += __shfl_xor(num, 32, 64); g += __shfl_xor(g, 32, 64);
+                    // the column's sixteen rows sit in this lane's four slots and in lanes ^ 16, ^ 32; every lane divides
+                    rows_sum2_all(num, g);
                     T ginv = __builtin_amdgcn_rcp(g);
                     ginv = ginv * __builtin_fma(-g, ginv, (T)2);
                     T dj = num * ginv;
@@ -769,8 +771,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                             l2 = offd ? __builtin_fma(zz, den, l2) : l2;                 // the eigenvalue's second-order term, as below
                             tZ[row * LDR + mcol] = (float)(offd ? z : zd);
                         }
-                        l2 += __shfl_xor(l2, 16, 64);
-                        l2 += __shfl_xor(l2, 32, 64);
+                        l2 = rows_sum(l2);
                         if (lane < 8) sLam2[j] = l2 + djh;
                         return __any(bad) && dstop != 10;
                     };
@@ -877,8 +878,7 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                         sA[row * LD + mcol] = z;
                     }
                     // the column's sixteen rows sit in this lane's four slots and in lanes ^ 16, ^ 32; then add the quotient itself
-                    l2 += __shfl_xor(l2, 16, 64);
-                    l2 += __shfl_xor(l2, 32, 64);
+                    l2 = rows_sum(l2);
                     if (lane < N) sLam2[mcol] = l2 + dj;
                     const bool pass = !__any(bad) || dstop == 10;                 // 10: guard off (timing aid, results invalid)
                     if (dstop == 9 && !pass) status = 8 << step;                  // 9: mark the bins by the step they miss
@@ -1054,8 +1054,8 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 const T lj = sLam[j];
                 rank += (lj > li) || (lj == li && j < i16);
             }
-            rank += __shfl_xor(rank, 16, 64);
-            rank += __shfl_xor(rank, 32, 64);
+            if constexpr (sizeof(T) == 8) rank = rows_sum(rank);
+            else { rank += __shfl_xor(rank, 16, 64); rank += __shfl_xor(rank, 32, 64); }
             if (q4 == 0) sOrder[rank] = i16;
         }
 
@@ -1073,10 +1073,18 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 gx = fma_t(-w.y, rr.y, fma_t(w.x, rr.x, gx));
                 gy = fma_t(w.y, rr.x, fma_t(w.x, rr.y, gy));
             }
-            gx += __shfl_xor(gx, 16, 64); gy += __shfl_xor(gy, 16, 64);
-            gx += __shfl_xor(gx, 32, 64); gy += __shfl_xor(gy, 32, 64);
-            wsync();                                                        // every lane has read r
-            if (q4 == 0) sr[i16] = mk<T>(gx, gy);
+            if constexpr (sizeof(T) == 8) {
+                // the partial sums meet on the VALU (rows_sum2): row 0 holds the real part and row 1 the imaginary part, and each
+                // stores its own
+                const T s = rows_sum2(gx, gy);
+                wsync();                                                    // every lane has read r
+                if (q4 < 2) reinterpret_cast<T*>(&sr[i16])[q4] = s;
+            } else {
+                gx += __shfl_xor(gx, 16, 64); gy += __shfl_xor(gy, 16, 64);
+                gx += __shfl_xor(gx, 32, 64); gy += __shfl_xor(gy, 32, 64);
+                wsync();                                                    // every lane has read r
+                if (q4 == 0) sr[i16] = mk<T>(gx, gy);
+            }
         }
         wsync();
 
@@ -1092,11 +1100,19 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 sx = fma_t(v.y, rr.y, fma_t(v.x, rr.x, sx));
                 sy = fma_t(-v.y, rr.x, fma_t(v.x, rr.y, sy));
             }
-            sx += __shfl_xor(sx, 16, 64); sy += __shfl_xor(sy, 16, 64);
-            sx += __shfl_xor(sx, 32, 64); sy += __shfl_xor(sy, 32, 64);
-            if (q4 == 0) {
-                const T den = rcp_full(sLam[i16] + span_mu<true, T>(p.span, z1, k, p.mu));
-                scoef[i16] = mk<T>(sx * den, sy * den);
+            if constexpr (sizeof(T) == 8) {
+                const T s = rows_sum2(sx, sy);                              // as in stage 5: rows 0 and 1 scale and store a part each
+                if (q4 < 2) {
+                    const T den = rcp_full(sLam[i16] + span_mu<true, T>(p.span, z1, k, p.mu));
+                    reinterpret_cast<T*>(&scoef[i16])[q4] = s * den;
+                }
+            } else {
+                sx += __shfl_xor(sx, 16, 64); sy += __shfl_xor(sy, 16, 64);
+                sx += __shfl_xor(sx, 32, 64); sy += __shfl_xor(sy, 32, 64);
+                if (q4 == 0) {
+                    const T den = rcp_full(sLam[i16] + span_mu<true, T>(p.span, z1, k, p.mu));
+                    scoef[i16] = mk<T>(sx * den, sy * den);
+                }
             }
         }
         wsync();
@@ -1129,10 +1145,16 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                     ay = fma_t(cf.y, v.x, fma_t(cf.x, v.y, ay));
                 }
             }
-            T yx = ax + __shfl_xor(ax, 16, 64), yy = ay + __shfl_xor(ay, 16, 64);
-            yx += __shfl_xor(yx, 32, 64); yy += __shfl_xor(yy, 32, 64);
-            wsync();                                                        // the rank before has read its y
-            if (q4 == 0) sr[i16] = mk<T>(yx, yy);
+            if constexpr (sizeof(T) == 8) {
+                const T ys = rows_sum2(ax, ay);                             // (copies: the partials stay)
+                wsync();                                                    // the rank before has read its y
+                if (q4 < 2) reinterpret_cast<T*>(&sr[i16])[q4] = ys;
+            } else {
+                T yx = ax + __shfl_xor(ax, 16, 64), yy = ay + __shfl_xor(ay, 16, 64);
+                yx += __shfl_xor(yx, 32, 64); yy += __shfl_xor(yy, 32, 64);
+                wsync();                                                    // the rank before has read its y
+                if (q4 == 0) sr[i16] = mk<T>(yx, yy);
+            }
             wsync();
             T wx = 0, wy = 0;
 #pragma unroll
@@ -1141,12 +1163,22 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
                 wx = fma_t(wl[ll].y, y.y, fma_t(wl[ll].x, y.x, wx));       // conj(W[l][i]) y_l
                 wy = fma_t(-wl[ll].y, y.x, fma_t(wl[ll].x, y.y, wy));
             }
-            wx += __shfl_xor(wx, 16, 64); wy += __shfl_xor(wy, 16, 64);
-            wx += __shfl_xor(wx, 32, 64); wy += __shfl_xor(wy, 32, 64);
-            if (lane < N) {
-                const size_t o = ((size_t)k * p.nV + t) * N + lane;
-                if (p.out_c128) reinterpret_cast<double2*>(pw)[o] = make_double2((double)wx, (double)wy);
-                else reinterpret_cast<float2*>(pw)[o] = make_float2((float)wx, (float)wy);
+            if constexpr (sizeof(T) == 8) {
+                // rows 0 and 1 store a part each: the same bytes at the same addresses, from 32 lanes
+                const T ws = rows_sum2(wx, wy);
+                if (q4 < 2) {
+                    const size_t o = 2 * (((size_t)k * p.nV + t) * N + i16) + q4;
+                    if (p.out_c128) reinterpret_cast<double*>(pw)[o] = (double)ws;
+                    else reinterpret_cast<float*>(pw)[o] = (float)ws;
+                }
+            } else {
+                wx += __shfl_xor(wx, 16, 64); wy += __shfl_xor(wy, 16, 64);
+                wx += __shfl_xor(wx, 32, 64); wy += __shfl_xor(wy, 32, 64);
+                if (lane < N) {
+                    const size_t o = ((size_t)k * p.nV + t) * N + lane;
+                    if (p.out_c128) reinterpret_cast<double2*>(pw)[o] = make_double2((double)wx, (double)wy);
+                    else reinterpret_cast<float2*>(pw)[o] = make_float2((float)wx, (float)wy);
+                }
             }
         }
     }

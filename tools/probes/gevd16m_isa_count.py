@@ -7,6 +7,7 @@ table row in the form of DESIGN 4.1:
   VALU          every v_* but the MFMAs            SALU        every s_* but waits, nops, branches and barriers
   branches      s_branch and s_cbranch_*           LDS         every ds_* (ds_bpermute included)
   waits/nops    s_waitcnt* and s_nop               MFMA        v_mfma_*
+  ds_bpermute   the crossbar trips among the LDS instructions (ds_bpermute_b32; a __shfl_xor of a double is two)
 
 with the register count, spill stores and reloads, scratch and LDS bytes from the function's own footer.  Instructions are
 classed by the prefix of their mnemonic only.  (The regions of the float32 pre-solve: presolve_isa_count.py.)
@@ -100,6 +101,8 @@ def classify(ms):
             c["salu"] += 1
         elif m.startswith("ds_"):
             c["lds"] += 1
+            if m.startswith("ds_bpermute"):
+                c["bpermute"] += 1
         else:
             c["other"] += 1                     # global / scratch / buffer memory
     return c
@@ -123,9 +126,9 @@ def main():
     reloads = sum(1 for l in body if "Reload" in l)
     ms = [m for m in map(mnemonic, body) if m]
     c = classify(ms)
-    print("| build | VALU | SALU | branches | LDS | waits/nops | MFMA | memory | VGPRs | spill st / reloads | scratch | LDS bytes |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
-    print(f"| {args.label} | {c['valu']} | {c['salu']} | {c['branch']} | {c['lds']} | {c['wait']} | {c['mfma']} | {c['other']} | "
+    print("| build | VALU | SALU | branches | LDS | ds_bpermute | waits/nops | MFMA | memory | VGPRs | spill st / reloads | scratch | LDS bytes |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    print(f"| {args.label} | {c['valu']} | {c['salu']} | {c['branch']} | {c['lds']} | {c['bpermute']} | {c['wait']} | {c['mfma']} | {c['other']} | "
           f"{meta.get('NumVgprs')} | {spills} / {reloads} | {meta.get('ScratchSize')} B | {meta.get('LDSByteSize')} |")
     print()
     for head, ragged, loads, full, ahead in slab_loops(body):
