@@ -22,6 +22,13 @@
 //                            not yet covered has sum_k |<y, x_k>|^2 = 2 over the cluster's candidates, and every rejected
 //                            candidate carries less than 0.05 of it: the walk cannot end short for clusters of fewer than 39
 //                            complex dimensions (it reports status 3 if it does).
+//   6. gram_kernel,          Candidates of DIFFERENT eigenvalues are orthogonal as real vectors, and as complex ones only as far
+//      reorthonormalise_kernel  as the eigenspaces the real solver found are invariant under J.  The real Cholesky and whitening
+//                            round the embedding's structure away at ~eps cond(B) ||C||, so two eigenvalues a gap g apart (beyond
+//                            the cluster window) leave |x_j^H B x_k| ~ eps cond(B) ||C|| / g behind: 4.5e-10 at n = 97, cond(B) =
+//                            1e4 on a geometric spectrum (gaps of 1e-5 ||C||), where the oracle keeps 1e-13.  One step of the
+//                            symmetric orthonormalisation, U = Q (3/2 I - 1/2 Q^H B Q), squares that error; it moves a vector by
+//                            its overlaps, hence its residual by overlap x gap ~ eps cond(B) ||C||.
 #include <memory>
 #include <string>
 
@@ -94,10 +101,10 @@ __global__ void __launch_bounds__(256) loaded_product_kernel(int n, const C128* 
 }
 
 // one workgroup of 1024 threads per matrix; thread i owns element i of every vector (n <= 1024).
-// Q, BQ: [n][n] kept vectors and their products with the loaded B, one row each.  U[i][j] = Q[j][i] at the end.
+// Q, BQ: [n][n] kept vectors and their products with the loaded B, one row each; rows that were not filled are zero at the end.
 __global__ void __launch_bounds__(1024) select_kernel(int n, const C128* __restrict__ Xc, const C128* __restrict__ Yc,
                                                       const double* __restrict__ lam2, C128* __restrict__ Q, C128* __restrict__ BQ,
-                                                      C128* __restrict__ U, double* __restrict__ lam, int32_t* __restrict__ status) {
+                                                      double* __restrict__ lam, int32_t* __restrict__ status) {
     __shared__ C128 s_r[1024], s_c[1024];
     __shared__ double s_lam[1024], s_red[16];
     const size_t n2 = 2 * (size_t)n;
@@ -163,11 +170,69 @@ __global__ void __launch_bounds__(1024) select_kernel(int n, const C128* __restr
         __syncthreads();                                        // the kept rows are read through global memory by every wave
     }
     if (tid == 0 && status != nullptr && status[z] == 0 && m < n) status[z] = 3;
-    // outputs: U[i][j] = Q[j][i], eigenvalues of the kept candidates (descending already)
-    C128* Ub = U + (size_t)z * n * n;
-    for (int j = 0; j < n; ++j)
-        if (own) Ub[(size_t)tid * n + j] = j < m ? Qb[(size_t)j * n + tid] : mk<double>(0, 0);
+    // outputs: eigenvalues of the kept candidates (descending already); a walk that ended short leaves zero vectors
+    for (int j = m; j < n; ++j)
+        if (own) {
+            Qb[(size_t)j * n + tid] = mk<double>(0, 0);
+            BQb[(size_t)j * n + tid] = mk<double>(0, 0);
+        }
     if (own) lam[(size_t)z * n + tid] = tid < m ? s_lam[tid] : 0.0;
+}
+
+// G[j][k] = q_j^H (B q_k) = sum_i conj(Q[j][i]) BQ[k][i]: 16 x 16 entries a workgroup, the rows read in chunks of 16 through LDS
+__global__ void __launch_bounds__(256) gram_kernel(int n, const C128* __restrict__ Q, const C128* __restrict__ BQ, C128* __restrict__ G) {
+    __shared__ C128 sq[16][17], sb[16][17];
+    const size_t nn = (size_t)n * n;
+    const C128* Qb = Q + (size_t)blockIdx.z * nn;
+    const C128* BQb = BQ + (size_t)blockIdx.z * nn;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int j0 = blockIdx.y * 16, k0 = blockIdx.x * 16;
+    double gx = 0, gy = 0;
+    for (int i0 = 0; i0 < n; i0 += 16) {
+        const bool in_i = i0 + tx < n;
+        sq[ty][tx] = (in_i && j0 + ty < n) ? Qb[(size_t)(j0 + ty) * n + i0 + tx] : mk<double>(0, 0);
+        sb[ty][tx] = (in_i && k0 + ty < n) ? BQb[(size_t)(k0 + ty) * n + i0 + tx] : mk<double>(0, 0);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const C128 a = sq[ty][i], b = sb[tx][i];                 // conj(a) * b
+            gx = fma_t(a.y, b.y, fma_t(a.x, b.x, gx));
+            gy = fma_t(-a.y, b.x, fma_t(a.x, b.y, gy));
+        }
+        __syncthreads();
+    }
+    if (j0 + ty < n && k0 + tx < n) G[(size_t)blockIdx.z * nn + (size_t)(j0 + ty) * n + k0 + tx] = mk<double>(gx, gy);
+}
+
+// U[i][k] = sum_j Q[j][i] T[j][k] with T = 3/2 I - 1/2 G: 16 x 16 entries a workgroup
+__global__ void __launch_bounds__(256) reorthonormalise_kernel(int n, const C128* __restrict__ Q, const C128* __restrict__ G,
+                                                               C128* __restrict__ U) {
+    __shared__ C128 sq[16][17], st[16][17];
+    const size_t nn = (size_t)n * n;
+    const C128* Qb = Q + (size_t)blockIdx.z * nn;
+    const C128* Gb = G + (size_t)blockIdx.z * nn;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int i0 = blockIdx.y * 16, k0 = blockIdx.x * 16;
+    double ux = 0, uy = 0;
+    for (int j0 = 0; j0 < n; j0 += 16) {
+        const int j = j0 + ty;
+        sq[ty][tx] = (j < n && i0 + tx < n) ? Qb[(size_t)j * n + i0 + tx] : mk<double>(0, 0);
+        C128 t = mk<double>(0, 0);
+        if (j < n && k0 + tx < n) {
+            const C128 g = Gb[(size_t)j * n + k0 + tx];
+            t = mk<double>((j == k0 + tx ? 1.5 : 0.0) - 0.5 * g.x, -0.5 * g.y);
+        }
+        st[ty][tx] = t;
+        __syncthreads();
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) {
+            const C128 a = sq[jj][ty], b = st[jj][tx];               // a * b
+            ux = fma_t(-a.y, b.y, fma_t(a.x, b.x, ux));
+            uy = fma_t(a.y, b.x, fma_t(a.x, b.y, uy));
+        }
+        __syncthreads();
+    }
+    if (i0 + ty < n && k0 + tx < n) U[(size_t)blockIdx.z * nn + (size_t)(i0 + ty) * n + k0 + tx] = mk<double>(ux, uy);
 }
 
 struct DevBufs {
@@ -243,7 +308,11 @@ int apv_jdiag_large_c128(apv_handle* h, int32_t n, int32_t batch, const void* h_
         hipLaunchKernelGGL(candidates_kernel, dim3((unsigned)((n2 + 31) / 32), (n + 31) / 32, batch), dim3(32, 8), 0, st, n, dZ, dXc);
         hipLaunchKernelGGL(loaded_product_kernel, dim3((n + 63) / 64, (unsigned)((n2 + 3) / 4), batch), dim3(256), 0, st, n, dB, dXc,
                            h->cfg.reg_dark, dn, dYc);
-        hipLaunchKernelGGL(select_kernel, dim3(batch), dim3(1024), 0, st, n, dXc, dYc, dl2, dQ, dBQ, dU, dl, dst);
+        hipLaunchKernelGGL(select_kernel, dim3(batch), dim3(1024), 0, st, n, dXc, dYc, dl2, dQ, dBQ, dl, dst);
+        C128* const dG = dYc;                                   // the candidates' products are spent: [batch][n][n] of it holds the Gram matrix
+        const dim3 tg((n + 15) / 16, (n + 15) / 16, batch);
+        hipLaunchKernelGGL(gram_kernel, tg, dim3(256), 0, st, n, dQ, dBQ, dG);
+        hipLaunchKernelGGL(reorthonormalise_kernel, tg, dim3(256), 0, st, n, dQ, dG, dU);
         JCHK(hipGetLastError());
         JCHK(hipMemcpyAsync(h_U, dU, cmat, hipMemcpyDeviceToHost, st));
         JCHK(hipMemcpyAsync(h_lam, dl, (size_t)batch * n * sizeof(double), hipMemcpyDeviceToHost, st));
