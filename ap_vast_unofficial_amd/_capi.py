@@ -32,7 +32,7 @@ EXPORTS = (
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev", "apv_analysis_dev", "apv_analysis_jobs_dev", "apv_synthesis_dev",
     "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_eval_energies", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_stream_set_validation_span", "apv_get_validation_span", "apv_validation_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
-    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state", "apv_bb_set_evaluation", "apv_bb_reset_evaluation",
+    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state", "apv_bb_set_evaluation", "apv_bb_reset_evaluation", "apv_bb_set_evaluation_spectra", "apv_eval_spectra_hops",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static",
     "apv_comm_unique_id", "apv_comm_init", "apv_allgather_filters_dev", "apv_comm_count", "apv_comm_last_gather", "apv_comm_barrier",
@@ -180,6 +180,8 @@ def load():
     lib.apv_bb_set_evaluation.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     lib.apv_bb_reset_evaluation.argtypes = [vp]
     lib.apv_eval_energies.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.apv_bb_set_evaluation_spectra.argtypes = [vp, i32]
+    lib.apv_eval_spectra_hops.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.apv_predict_pressure.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     lib.apv_vast_static.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp]
     lib.apv_comm_unique_id.argtypes = [C.c_char_p]
@@ -533,6 +535,40 @@ class Engine:
     def bb_reset_evaluation(self):
         """Totals and output histories of the broadband stream's evaluation stage to zero (apv_bb_reset_evaluation)."""
         self._chk(self.lib.apv_bb_reset_evaluation(self.h))
+
+    def bb_set_evaluation_spectra(self):
+        """Per-bin spectra of the broadband stream's evaluation stage, after bb_set_evaluation, once, at any hop boundary
+        (apv_bb_set_evaluation_spectra): ring and spectra start from zero here."""
+        self._chk(self.lib.apv_bb_set_evaluation_spectra(self.h, 1))
+
+    def eval_spectra_hops(self, p, tail, N, H, totals=None, hops_per_launch=0):
+        """The three launches of the broadband stream's per-bin spectra alone (apv_eval_spectra_hops): p (Z, 2 E + 1, n H, Mv)
+        float64 pressures of n consecutive hops, tail (Z, 2 E + 1, Mv, N - H) the newest N - H samples in front of them, oldest
+        first (None: silence).  Every hop's frame of N samples is windowed and transformed and |P|^2 added to totals
+        (Z, 3 E + 1, N/2 + 1, Mv) (None: zeros) in hop order; hops_per_launch = 0: as many hops per sub-launch as the scratch budget
+        allows, otherwise at most that many.  Returns (totals, tail), the tail behind the last hop."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        N, H = int(N), int(H)
+        if p.ndim != 4 or p.shape[1] % 2 != 1 or p.shape[1] < 3:
+            raise ValueError("p must be (Z, 2 E + 1, n H, Mv)")
+        Z, E, Mv = p.shape[0], (p.shape[1] - 1) // 2, p.shape[3]
+        if H < 1 or H > N or p.shape[2] % H or p.shape[2] < H:
+            raise ValueError("p must hold a whole number of hops of H <= N samples")
+        n = p.shape[2] // H
+        tail = np.zeros((Z, 2 * E + 1, Mv, N - H)) if tail is None else np.ascontiguousarray(tail, dtype=np.float64)
+        tot = np.zeros((Z, 3 * E + 1, N // 2 + 1, Mv)) if totals is None else np.ascontiguousarray(totals, dtype=np.float64)
+        if tail.shape != (Z, 2 * E + 1, Mv, N - H) or tot.shape != (Z, 3 * E + 1, N // 2 + 1, Mv):
+            raise ValueError("tail must be (Z, 2 E + 1, Mv, N - H) and totals (Z, 3 E + 1, N/2 + 1, Mv)")
+        dp, dt = self.to_device(p), self.to_device(tot)
+        dl = self.to_device(tail) if tail.size else None
+        try:
+            self._chk(self.lib.apv_eval_spectra_hops(self.h, dp.ptr, dl.ptr if dl else None, N, H, Z, E, Mv, n, int(hops_per_launch),
+                                                     dt.ptr))
+            return dt.download(tot.shape, np.float64), dl.download(tail.shape, np.float64) if dl else tail
+        finally:
+            for b in (dp, dt, dl):
+                if b is not None:
+                    b.free()
 
     def set_synthesis(self, mode):
         """Synthesis of the subband stream, before stream_init (apv_stream_set_synthesis): "wola" (the reference's overlap-add)

@@ -73,6 +73,8 @@ What is different (keyword-only, after ``perceptual``)
     ``evaluation.spectral_metrics`` gives contrast and NMSE per bin or band, ``reset_evaluation()`` zeroes them too, and
     get_state() gains ``evaluation_spectra`` (Z, 3 E + 1, K, Mv) and ``evaluation_ring`` (Z, 2 E + 1, Mv, N).  Everything else the
     stream computes is unchanged, bit for bit.  Block sizes up to 4096.
+    In broadband mode the spectra are switched on by a method instead, ``ap.enable_evaluation_spectra()``, after
+    ``enable_evaluation()``, once and at any hop boundary; there process_signal transforms a whole group of hops per launch.
   * ``evaluation_detectability=True`` (a bool; needs ``evaluation_spectra=True``): behind the spectra of every hop the device
     evaluates the second half of the masking model, evaluateDetectability (perceptualModel.m:192-206): with w2_S the squared
     weighting curve of a masker spectrum S (perceptualModel.m:118-139, un-normalised) and f = 2 / N^2, per program z, evaluated
@@ -733,7 +735,8 @@ class apvast:
         evaluation.metrics() work the same, get_state() gains ``evaluation_history`` and ``evaluation_totals``.  ``ranks``: the
         evaluated ranks, a strictly ascending subset of the ranks the object emits (1..number_of_eigenvectors; in the MATLAB dialect
         the entries of number_of_eigenvectors); None: all of them.  Histories start from silence and totals from zero here.
-        process_signal evaluates a whole group of hops per launch.  Outputs, filters and every other state are untouched."""
+        process_signal evaluates a whole group of hops per launch.  Outputs, filters and every other state are untouched.
+        enable_evaluation_spectra(), after this call, adds the per-bin energies."""
         if self.mode != "broadband":
             raise RuntimeError("enable_evaluation() is the broadband mode's switch: in subband mode pass validation_rir_A and "
                                "validation_rir_B (and evaluation_ranks) to the constructor")
@@ -748,6 +751,25 @@ class apvast:
         self._eng.bb_set_evaluation(a, b, r)
         self._bb_evaluation = (a, b, r)
         self._bb_eval_hops = 0              # hops in the record of the last call
+
+    def enable_evaluation_spectra(self):
+        """Broadband mode: switch the per-bin spectra of the evaluation stage on, after enable_evaluation(), once, at any hop
+        boundary.  From here on the device keeps the last block_size pressure samples of every pressure set and microphone and,
+        after every hop, transforms them under the stream's sine window and accumulates |P|^2 per bin, as the subband keyword
+        ``evaluation_spectra=True`` does: evaluation_spectra() and evaluation.spectral_metrics() work the same, get_state() gains
+        ``evaluation_spectra`` (Z, 3 E + 1, K, Mv) and ``evaluation_ring`` (Z, 2 E + 1, Mv, N), reset_evaluation() zeroes both.
+        Ring and spectra start from zero here.  process_signal transforms a whole group of hops per launch; the bits are those
+        of the hop loop.  Everything else the object computes is untouched."""
+        if self.mode != "broadband":
+            raise RuntimeError("enable_evaluation_spectra() is the broadband mode's switch: in subband mode pass "
+                               "evaluation_spectra=True to the constructor")
+        if self.__dict__.get("_bb_evaluation") is None:
+            raise RuntimeError("enable_evaluation_spectra() comes after enable_evaluation()")
+        if self.__dict__.get("_bb_evaluation_spectra"):
+            raise RuntimeError("enable_evaluation_spectra(): this object keeps its evaluation spectra already")
+        self._eng.bb_set_evaluation_spectra()
+        self._bb_evaluation_spectra = True
+        self._bb_spec_hops = 0              # hops since the switch: evaluation_spectra() is None before the first
 
     @staticmethod
     def _eval_split(e, E):
@@ -799,12 +821,19 @@ class apvast:
         "error" (Z, E, Mv, K) and "target" (Z, Mv, K), K = block_size / 2 + 1; evaluation.spectral_metrics() turns them into
         contrast and NMSE per bin or band.  None before the first hop."""
         Z, E, _, Mv = self._eval_dims()
-        if not self.__dict__.get("_evaluation_spectra"):
-            raise RuntimeError("this object keeps no evaluation spectra: pass evaluation_spectra=True")
-        if self._hops == 0:
-            return None
+        if self.__dict__.get("mode") == "broadband":
+            if not self.__dict__.get("_bb_evaluation_spectra"):
+                raise RuntimeError("this object keeps no evaluation spectra: call enable_evaluation_spectra()")
+            if self._hops == 0 or not self._bb_spec_hops:
+                return None                   # switched on, no hop since
+            t = self._eng.bb_get_state("eval_spectra", (Z, 3 * E + 1, self._K, Mv))
+        else:
+            if not self.__dict__.get("_evaluation_spectra"):
+                raise RuntimeError("this object keeps no evaluation spectra: pass evaluation_spectra=True")
+            if self._hops == 0:
+                return None
+            t = self._eng.get_state("eval_spectra", (Z, 3 * E + 1, self._K, Mv), np.float64)
         # the device accumulates bins before microphones (neighbouring threads along the microphones)
-        t = self._eng.get_state("eval_spectra", (Z, 3 * E + 1, self._K, Mv), np.float64)
         t = t.transpose(0, 1, 3, 2)
         return {"bright": np.ascontiguousarray(t[:, :E]), "dark": np.ascontiguousarray(t[:, E:2 * E]),
                 "error": np.ascontiguousarray(t[:, 2 * E:3 * E]), "target": np.ascontiguousarray(t[:, 3 * E])}
@@ -847,7 +876,8 @@ class apvast:
 
     def reset_evaluation(self):
         """Totals to zero and the output histories to silence: the next hop's totals are its own energies.  With
-        evaluation_spectra=True the per-bin energies and the pressure ring too, with evaluation_detectability=True its totals."""
+        evaluation_spectra=True, or after enable_evaluation_spectra() in broadband mode, the per-bin energies and the pressure ring
+        too, with evaluation_detectability=True its totals."""
         self._eval_dims()
         if self.mode == "broadband":
             self._eng.bb_reset_evaluation()
@@ -971,6 +1001,8 @@ class apvast:
         self._bb_cache = None
         self._bb_evaluation = None          # enable_evaluation() switches the stage on
         self._bb_eval_hops = 0
+        self._bb_evaluation_spectra = False # enable_evaluation_spectra() switches the per-bin spectra on
+        self._bb_spec_hops = 0
 
     def _refresh_broadband(self):
         """A hop has run: what the attributes hold is stale.  Nothing is fetched here (see _bb_fetch)."""
@@ -1020,7 +1052,7 @@ class apvast:
         if self.mode == "broadband":
             out = self._eng.bb_process_block(input_A, input_B, self._n_out)      # (groups, H, L), fresh for every hop
             res = self._split_groups(out)
-            self._bb_eval_hops = 1
+            self._bb_eval_hops = self._bb_spec_hops = 1
             self._refresh_broadband()
             return res
         out = self._eng.process_block(input_A, input_B, self._n_out)         # (groups, H, L): one (H, L) array per zone and rank
@@ -1053,7 +1085,7 @@ class apvast:
             # writes (groups, n_samples, L) -- every zone program's and rank's whole signal as the array handed out below
             out = self._eng.bb_process_signal(input_A, input_B, self._n_out, out=out)
             res = self._split_groups(out)
-            self._bb_eval_hops = input_A.size // self.hop_size
+            self._bb_eval_hops = self._bb_spec_hops = input_A.size // self.hop_size
             self._hops += input_A.size // self.hop_size - 1
             self._refresh_broadband()
             return res
@@ -1356,7 +1388,10 @@ def _state_rows():
     fir, ev_sub = sub(lambda self: self.synthesis == "fir"), sub(lambda self: self._evaluation is not None)
     # the evaluation stage: the constructor's in subband mode, enable_evaluation()'s in broadband mode
     ev = lambda self: ev_sub(self) or (bb(self) and getattr(self, "_bb_evaluation", None) is not None)
-    evs, evd = sub(lambda self: self._evaluation_spectra), sub(lambda self: self._evaluation_detectability)
+    evs_sub, evd = sub(lambda self: self._evaluation_spectra), sub(lambda self: self._evaluation_detectability)
+    # the per-bin spectra: the constructor's keyword in subband mode, enable_evaluation_spectra()'s in broadband mode
+    evs = lambda self: evs_sub(self) or (bb(self) and getattr(self, "_bb_evaluation", None) is not None
+                                         and bool(getattr(self, "_bb_evaluation_spectra", False)))
     live = lambda self: self._live_applied
     N = lambda self: self.block_size
     S = lambda self: self.statistics_buffer_length

@@ -480,6 +480,28 @@ struct EvalSpectraArgs {
 bool apv_eval_spectra_size_ok(int N, int H, int Z, int E, int Mv, std::string* why);
 hipError_t apv_launch_eval_spectra(const EvalSpectraArgs& a, hipStream_t s, std::string* why);
 
+// kernels_bbevalspec.hip: the same spectra for the broadband stream, n consecutive hops per call (see the file header).  p: the
+// pressures [Z (2 E + 1)][.. n H ..][Mv] of the n hops, the sets p_set elements apart.  line[cur] holds the current line
+// [Z (2 E + 1) Mv][len], len >= N - H, whose last N - H samples are the newest from before the call; the call runs the n hops as
+// sub-launches of at most per_launch hops -- line [Z (2 E + 1) Mv][N - H + c H] into the other buffer, the windowed float64
+// transforms of its c frames into spec [c][N/2 + 1][Z (2 E + 1) Mv] complex128, |P|^2 added to totals [Z][3 E + 1][N/2 + 1][Mv]
+// in hop order -- and leaves cur and len at the last line.  Both line buffers hold N - H + min(n, per_launch) H samples per
+// channel, spec min(n, per_launch) hops.  The float64 tables of N must exist (apv_stft_prepare(N, 1)).
+constexpr size_t APV_BBSPEC_SCRATCH_BYTES = (size_t)64 << 20;       // budget of spec; one hop where a hop is larger
+struct BbSpecArgs {
+    const double* p;
+    size_t p_set;
+    double* line[2];
+    int cur;
+    long long len;
+    void* spec;
+    double* totals;
+    int N, H, Z, E, Mv, n, per_launch;
+};
+bool apv_bbspec_size_ok(int N, int H, int Z, int E, int Mv, std::string* why);
+int apv_bbspec_hops_fit(int N, int Z, int E, int Mv);         // hops per sub-launch the budget allows, at least 1
+hipError_t apv_launch_bbspec_hops(BbSpecArgs* a, hipStream_t s, std::string* why);
+
 // kernels_evaldetect.hip: perceptual detectability of the evaluated pressures (see the file header).  Three launches behind the
 // spectra above, on their bin-major scratch spec [N/2 + 1][Z (2 E + 1) Mv]: the squared weighting curves of the Z Mv target
 // spectra into curves [N/2 + 1][Z Mv], the weighted sums of every (program, rank, microphone) over the bins 1.. as `chunks`

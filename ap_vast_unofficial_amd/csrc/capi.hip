@@ -1254,6 +1254,43 @@ int apv_eval_spectrum_step(apv_handle* h, const double* d_pressure, double* d_ri
     return APV_OK;
 }
 
+int apv_eval_spectra_hops(apv_handle* h, const double* d_pressure, double* d_tail, int32_t N, int32_t H, int32_t Z, int32_t E, int32_t Mv,
+                          int32_t n_hops, int32_t hops_per_launch, double* d_totals) {
+    if (!h || !d_pressure || !d_totals) return fail(h, APV_ERR_ARG, "apv_eval_spectra_hops: null device pointer");
+    if (N < 1 || H < 1 || Z < 1 || E < 1 || Mv < 1 || n_hops < 1)
+        return fail(h, APV_ERR_ARG, "apv_eval_spectra_hops: N, H, Z, E, Mv and n_hops must be at least 1");
+    if ((N & 1) || N > 4096) return fail(h, APV_ERR_ARG, "apv_eval_spectra_hops: N must be even and at most 4096 (float64 transforms)");
+    if (hops_per_launch < 0) return fail(h, APV_ERR_ARG, "apv_eval_spectra_hops: hops_per_launch must not be negative");
+    if ((long long)n_hops * H > 0x7fffffffll) return fail(h, APV_ERR_ARG, "apv_eval_spectra_hops: n_hops x H must stay below 2^31");
+    std::string why;
+    if (!apv_bbspec_size_ok(N, H, Z, E, Mv, &why)) return fail(h, APV_ERR_ARG, why);
+    if (H < N && !d_tail) return fail(h, APV_ERR_ARG, "apv_eval_spectra_hops: null tail with H < N");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    HIPCHK(h, apv_stft_prepare(N, 1));
+    // lines and the transforms' scratch are this call's own: a test entry, not a per-hop path
+    const int fit = apv_bbspec_hops_fit(N, Z, E, Mv), tail = N - H;
+    const int c = std::min<int>(n_hops, hops_per_launch > 0 ? std::min<int>(hops_per_launch, fit) : fit);
+    const size_t ch = (size_t)Z * (2 * (size_t)E + 1) * Mv, row = (size_t)tail + (size_t)c * H;
+    ApvOwned t;
+    BbSpecArgs a{};
+    for (int b = 0; b < 2; ++b) HIPCHK(h, t.device(&a.line[b], sizeof(double) * ch * row));
+    HIPCHK(h, t.device(&a.spec, sizeof(double) * 2 * (size_t)c * ((size_t)N / 2 + 1) * ch));
+    // the tail alone is the line in front of the first hop
+    if (tail > 0) HIPCHK(h, hipMemcpyAsync(a.line[0], d_tail, sizeof(double) * ch * tail, hipMemcpyDeviceToDevice, h->stream));
+    a.p = d_pressure; a.p_set = (size_t)n_hops * H * Mv; a.cur = 0; a.len = tail; a.totals = d_totals;
+    a.N = N; a.H = H; a.Z = Z; a.E = E; a.Mv = Mv; a.n = n_hops; a.per_launch = c;
+    hipError_t e = apv_launch_bbspec_hops(&a, h->stream, &why);
+    if (e == hipSuccess && tail > 0)
+        e = hipMemcpy2DAsync(d_tail, sizeof(double) * tail, a.line[a.cur] + (a.len - tail), sizeof(double) * (size_t)a.len,
+                             sizeof(double) * tail, ch, hipMemcpyDeviceToDevice, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
 int apv_eval_detect_step(apv_handle* h, const void* d_spec, int32_t N, int32_t Z, int32_t E, int32_t Mv, int32_t n_channels,
                          const double* h_G2, double Cs, double Ca, double Leff, double* d_hop, double* d_totals) {
     if (!h || !d_spec || !h_G2 || !d_hop || !d_totals) return fail(h, APV_ERR_ARG, "null pointer");

@@ -121,6 +121,13 @@ struct apv_bb {
     double* be_tot;               // [Z][3 E + 1][Mv]
     double* be_rec;               // [be_cap] slots of [Z][3 E + 1][Mv]: the energies of every hop of the last call
     int be_cap, be_nrec;          // slots allocated; slots the last call filled
+    // per-bin spectra of that stage (apv_bb_set_evaluation_spectra, kernels_bbevalspec.hip); bs_on = 0: off, nothing below exists
+    int bs_on;
+    int bs_hops, bs_cur;          // hops of a sub-launch the line buffers and the scratch hold; the buffer with the current line
+    long long bs_len;             // samples per channel of the current line, at least N: its last N are "eval_ring"
+    double* bs_line[2];           // [sets Mv][N - H + bs_hops H], alternating
+    void* bs_spec;                // [bs_hops][K][sets Mv] complex128, the transforms' bin-major scratch
+    double* bs_tot;               // [Z][3 E + 1][K][Mv]
     ApvOwned own;          // every buffer, pinned block, event and stream above: made through it, freed by it
 };
 
@@ -640,6 +647,44 @@ static int bb_evaluate(apv_handle* h, apv_bb* s, const double* d_out, size_t gst
     BCHK(h, apv_launch_bbeval_advance(adv, st));
     if (s->be_Pv > 1) s->be_cur = c ^ 1;
     s->be_last = n;
+    if (s->bs_on) {
+        // the per-bin spectra of the same n hops: lines, transforms and |P|^2, in sub-launches of what the scratch holds
+        BbSpecArgs sp{};
+        sp.p = s->be_p; sp.p_set = (size_t)n * H * s->be_Mv;
+        sp.line[0] = s->bs_line[0]; sp.line[1] = s->bs_line[1]; sp.cur = s->bs_cur; sp.len = s->bs_len;
+        sp.spec = s->bs_spec; sp.totals = s->bs_tot;
+        sp.N = s->N; sp.H = H; sp.Z = s->be_Z; sp.E = s->be_E; sp.Mv = s->be_Mv; sp.n = n; sp.per_launch = s->bs_hops;
+        e = apv_launch_bbspec_hops(&sp, st, &why);
+        s->bs_cur = sp.cur; s->bs_len = sp.len;
+        if (e != hipSuccess) return apv_fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+    }
+    return APV_OK;
+}
+
+// line buffers and scratch of the spectra for launches of `group` hops: sub-launches of as many hops as the scratch budget holds.
+// The current line moves into the new buffers.  Called with nothing of the stage in flight.
+static int bb_spec_reserve(apv_handle* h, apv_bb* s, int group) {
+    const int c = std::min(group, apv_bbspec_hops_fit(s->N, s->be_Z, s->be_E, s->be_Mv));
+    if (c <= s->bs_hops) return APV_OK;
+    hipStream_t st = h->stream;
+    const size_t ch = (size_t)s->be_sets * s->be_Mv, row = (size_t)s->N - s->H + (size_t)c * s->H;
+    double* line[2] = {nullptr, nullptr};
+    void* spec = nullptr;
+    struct Guard {
+        ApvOwned& own; double** line; void** spec; bool ok;
+        ~Guard() { if (!ok) { own.release(line[0]); own.release(line[1]); own.release(*spec); } }
+    } made{s->own, line, &spec, false};
+    for (int b = 0; b < 2; ++b) BCHK(h, s->own.zeroed(&line[b], ch * row, sizeof(double), st));
+    BCHK(h, s->own.device(&spec, sizeof(double) * 2 * (size_t)c * s->K * ch));
+    if (s->bs_line[s->bs_cur])
+        BCHK(h, hipMemcpyAsync(line[0], s->bs_line[s->bs_cur], sizeof(double) * ch * (size_t)s->bs_len, hipMemcpyDeviceToDevice, st));
+    BCHK(h, hipStreamSynchronize(st));
+    for (int b = 0; b < 2; ++b) s->own.release(s->bs_line[b]);
+    s->own.release(s->bs_spec);
+    s->bs_line[0] = line[0]; s->bs_line[1] = line[1]; s->bs_spec = spec;
+    s->bs_cur = 0;
+    s->bs_hops = c;
+    made.ok = true;
     return APV_OK;
 }
 
@@ -661,7 +706,7 @@ static int bb_eval_reserve(apv_handle* h, apv_bb* s, int n_hops, int group) {
         BCHK(h, apv_eval_pressure_prepare(1, s->be_Pv, group * s->H, s->L));
     }
     s->be_nrec = 0;
-    return APV_OK;
+    return s->bs_on ? bb_spec_reserve(h, s, group) : APV_OK;
 }
 
 static void bb_eval_free(apv_bb* s) {
@@ -675,6 +720,14 @@ static void bb_eval_free(apv_bb* s) {
     s->own.release(s->be_tot);
     s->own.release(s->be_rec);
     s->be_on = s->be_cap = s->be_nrec = s->be_p_hops = s->be_last = s->be_cur = 0;
+}
+
+static void bb_spec_free(apv_bb* s) {
+    for (int b = 0; b < 2; ++b) s->own.release(s->bs_line[b]);
+    s->own.release(s->bs_spec);
+    s->own.release(s->bs_tot);
+    s->bs_on = s->bs_hops = s->bs_cur = 0;
+    s->bs_len = 0;
 }
 
 // Evaluation stage of the broadband stream: see include/apvast_hip.h.
@@ -747,7 +800,31 @@ int apv_bb_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h
     return APV_OK;
 }
 
-// "eval_totals" and both "eval_history" buffers to zero: the next hop's totals are its own energies
+// Per-bin spectra of the evaluation stage: see include/apvast_hip.h.
+int apv_bb_set_evaluation_spectra(apv_handle* h, int32_t on) {
+    if (!h || !h->bb) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation_spectra: apv_bb_init has not been called");
+    apv_bb* s = h->bb;
+    if (!s->be_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation_spectra: needs apv_bb_set_evaluation");
+    if (s->bs_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation_spectra: the stream keeps its evaluation spectra already");
+    if (on != 1) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation_spectra: on must be 1");
+    std::string why;
+    if (!apv_bbspec_size_ok(s->N, s->H, s->be_Z, s->be_E, s->be_Mv, &why)) return apv_fail(h, APV_ERR_ARG, why);
+    BCHK(h, hipSetDevice(h->device));
+    BCHK(h, hipStreamSynchronize(h->stream));
+    struct Guard { apv_bb* s; bool ok; ~Guard() { if (!ok) bb_spec_free(s); } } built{s, false};
+    BCHK(h, apv_stft_prepare(s->N, 1));                      // the float64 tables, outside any timed path
+    BCHK(h, s->own.zeroed(&s->bs_tot, (size_t)s->be_Z * (3 * s->be_E + 1) * s->K * s->be_Mv, sizeof(double), h->stream));
+    // lines for the launches the pressure buffer holds now; an empty line of N zeros per channel stands in front of the first hop
+    s->bs_len = s->N;
+    const int rc = bb_spec_reserve(h, s, std::max(s->be_p_hops, 1));
+    if (rc != APV_OK) return rc;
+    s->bs_on = 1;
+    built.ok = true;
+    return APV_OK;
+}
+
+// "eval_totals" and both "eval_history" buffers to zero: the next hop's totals are its own energies; with the spectra on,
+// "eval_spectra" and "eval_ring" too
 int apv_bb_reset_evaluation(apv_handle* h) {
     if (!h || !h->bb || !h->bb->be_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_reset_evaluation: no broadband stream with an evaluation stage");
     apv_bb* s = h->bb;
@@ -755,6 +832,10 @@ int apv_bb_reset_evaluation(apv_handle* h) {
     BCHK(h, hipMemsetAsync(s->be_tot, 0, sizeof(double) * (size_t)s->be_Z * (3 * s->be_E + 1) * s->be_Mv, h->stream));
     const size_t hb = sizeof(double) * (size_t)s->be_nhist * (s->be_Pv - 1) * s->L;
     for (int b = 0; b < 2 && hb > 0; ++b) BCHK(h, hipMemsetAsync(s->be_hist[b], 0, hb, h->stream));
+    if (s->bs_on) {
+        BCHK(h, hipMemsetAsync(s->bs_tot, 0, sizeof(double) * (size_t)s->be_Z * (3 * s->be_E + 1) * s->K * s->be_Mv, h->stream));
+        BCHK(h, hipMemsetAsync(s->bs_line[s->bs_cur], 0, sizeof(double) * (size_t)s->be_sets * s->be_Mv * (size_t)s->bs_len, h->stream));
+    }
     BCHK(h, hipStreamSynchronize(h->stream));
     return APV_OK;
 }
@@ -1288,11 +1369,14 @@ static int bb_lookup(apv_handle* h, const char* name, double** d, size_t* count,
 
 // The names only a stream with the evaluation stage has, with the split of the subband stream's table (stream_state.hip):
 // "eval_pressure" [Z][2 E + 1][H][Mv], the last hop's, and "eval_hops" [hops of the last call][Z][3 E + 1][Mv] are read-only;
-// "eval_totals" [Z][3 E + 1][Mv] and "eval_history" [Z][E + 1][Pv - 1][L] (the buffer the next launch reads) can be set.
+// "eval_totals" [Z][3 E + 1][Mv] and "eval_history" [Z][E + 1][Pv - 1][L] (the buffer the next launch reads) can be set.  With the
+// spectra on (apv_bb_set_evaluation_spectra) also "eval_spectra" [Z][3 E + 1][K][Mv] and "eval_ring" [Z (2 E + 1)][Mv][N], the
+// last N samples of every channel of the current line; both can be set, a set ring becoming the current line.
 struct BbEvalRef {
     double* d;
     size_t count;
     bool read_only, last_rows;      // last_rows: H rows of each set behind a launch of be_last hops
+    bool line_end;                  // the last N samples of every row of the current line
 };
 static bool bb_eval_lookup(apv_bb* s, const char* name, BbEvalRef* r) {
     if (!s->be_on) return false;
@@ -1302,6 +1386,8 @@ static bool bb_eval_lookup(apv_bb* s, const char* name, BbEvalRef* r) {
     else if (is("eval_hops")) *r = BbEvalRef{s->be_rec, slot * s->be_nrec, true, false};
     else if (is("eval_totals")) *r = BbEvalRef{s->be_tot, slot, false, false};
     else if (is("eval_history")) *r = BbEvalRef{s->be_hist[s->be_cur], (size_t)s->be_nhist * (s->be_Pv - 1) * s->L, false, false};
+    else if (s->bs_on && is("eval_spectra")) *r = BbEvalRef{s->bs_tot, slot * s->K, false, false};
+    else if (s->bs_on && is("eval_ring")) *r = BbEvalRef{s->bs_line[s->bs_cur], (size_t)s->be_sets * s->be_Mv * s->N, false, false, true};
     else return false;
     return true;
 }
@@ -1340,6 +1426,10 @@ int apv_bb_get_state(apv_handle* h, const char* name, double* h_dst, size_t coun
             const size_t hop = sizeof(double) * (size_t)s->H * s->be_Mv, last = s->be_last > 0 ? s->be_last : 1;
             BCHK(h, hipMemcpy2DAsync(h_dst, hop, ev.d + (last - 1) * (hop / sizeof(double)), last * hop, hop, s->be_sets,
                                      hipMemcpyDeviceToHost, h->stream));
+        } else if (ev.line_end) {
+            const size_t ring = sizeof(double) * (size_t)s->N;
+            BCHK(h, hipMemcpy2DAsync(h_dst, ring, ev.d + (s->bs_len - s->N), sizeof(double) * (size_t)s->bs_len, ring,
+                                     (size_t)s->be_sets * s->be_Mv, hipMemcpyDeviceToHost, h->stream));
         } else {
             BCHK(h, hipMemcpyAsync(h_dst, ev.d, sizeof(double) * ev.count, hipMemcpyDeviceToHost, h->stream));
         }
@@ -1383,6 +1473,7 @@ int apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size_
         BCHK(h, hipSetDevice(h->device));
         BCHK(h, hipMemcpyAsync(ev.d, h_src, sizeof(double) * ev.count, hipMemcpyHostToDevice, h->stream));
         BCHK(h, hipStreamSynchronize(h->stream));
+        if (ev.line_end) h->bb->bs_len = h->bb->N;           // the ring as given is the current line, N samples per channel
         return APV_OK;
     }
     double* d; size_t need; int rows, len, off;

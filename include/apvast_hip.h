@@ -366,6 +366,16 @@ int  apv_eval_pressure(apv_handle* h, const void* d_y, const double* d_rv, int32
  * n_hops x H of 2^31 and more.                            replaces: Matlab/main.m:120-130, the sums */
 int  apv_eval_energies(apv_handle* h, const double* d_p, int32_t Z, int32_t E, int32_t H, int32_t Mv, int32_t n_hops, double* d_record,
                        double* d_totals);
+/* The three launches of apv_bb_set_evaluation_spectra alone, on device pointers and the handle's stream: d_pressure
+ * [Z (2 E + 1)][n_hops H][Mv], the pressures of n_hops consecutive hops; d_tail [Z (2 E + 1)][Mv][N - H], in and out, the newest
+ * N - H samples in front of the first hop and behind the last, oldest first (may be null when H = N); |P|^2 of every hop's frame
+ * is added to d_totals [Z][3 E + 1][N/2 + 1][Mv] in hop order.  hops_per_launch = 0: sub-launches of as many hops as the scratch
+ * budget allows; otherwise of at most that many, through the same loop the stream runs -- the totals' bits do not depend on it.
+ * All float64.  The call allocates and frees its lines and scratch and synchronises.  APV_ERR_ARG for null pointers, sizes below
+ * 1, odd N, N > 4096, H > N, Z > 2, hops_per_launch < 0, or n_hops x H of 2^31 and more.
+ *                                                         replaces: nothing in the reference */
+int  apv_eval_spectra_hops(apv_handle* h, const double* d_pressure, double* d_tail, int32_t N, int32_t H, int32_t Z, int32_t E,
+                           int32_t Mv, int32_t n_hops, int32_t hops_per_launch, double* d_totals);
 
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
@@ -638,8 +648,26 @@ int  apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size
  *                                                         replaces: Matlab/main.m:64-76, 120-130 with predictPressure.m:12-16 */
 int  apv_bb_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
                            const int32_t* ranks);
-/* "eval_totals" and both history buffers to zero: the next hop's totals equal its own energies.  APV_ERR_ARG without such a stream. */
+/* "eval_totals" and both history buffers to zero: the next hop's totals equal its own energies; with
+ * apv_bb_set_evaluation_spectra also "eval_spectra" and "eval_ring".  APV_ERR_ARG without such a stream. */
 int  apv_bb_reset_evaluation(apv_handle* h);
+/* Per-bin spectra of the broadband stream's evaluation stage (off unless called with on = 1): the definition of
+ * apv_stream_set_evaluation_spectra -- frames of N = block_size pressure samples, H = hop_size apart, under the stream's sine
+ * window, unnormalised rfft, |P|^2 added per bin, one addition per element and hop in hop order, float64, no atomics -- with hop t
+ * counted from this call, a set "eval_ring" or apv_bb_reset_evaluation.  Behind the three launches of the evaluation stage three
+ * more per launch of n hops (csrc/kernels_bbevalspec.hip): per pressure set and microphone a line of the newest N - H samples from
+ * before and the launch's n H pressures; the stream's own windowed transform of its n frames; |P|^2 of the n hops added in hop order
+ * by one owner per element.  The bits of the totals depend on the data and the hop order alone, so apv_bb_process_block and a group
+ * of apv_bb_process_signal agree bit for bit.  The transforms' scratch has a budget of 64 MB (one hop where a hop is larger): a
+ * group whose spectra exceed it runs as consecutive sub-launches of as many hops as fit.  States only such a stream has:
+ *   "eval_spectra"  [Z][3 E + 1][K][Mv], K = N/2 + 1: per program [bright of the E ranks][dark ...][error ...][target]
+ *   "eval_ring"     [Z (2 E + 1)][Mv][N]: the last N pressure samples per set (the order of "eval_pressure") and microphone,
+ *                   oldest first
+ * both readable and settable.  Called after apv_bb_set_evaluation, once, at any hop boundary: ring and spectra start from zero
+ * there.  APV_ERR_ARG (nothing changed) without apv_bb_init, without apv_bb_set_evaluation, on a second call, for a value other
+ * than 1, and for block_size > 4096 or any other size the float64 transforms refuse.
+ *                                                         replaces: nothing in the reference (pwelch on the host) */
+int  apv_bb_set_evaluation_spectra(apv_handle* h, int32_t on);
 
 /* ---- evaluation and the static solver, float64 ------------------------- */
 /* p[t][m] = sum_s filter(rir[:, s, m], 1, x[:, s])[t].  h_x [T][L], h_rir [P][L][M], h_out [T][M].

@@ -13,7 +13,13 @@ largest rank evaluated:
   * NMSE and contrast (evaluation.metrics on the totals) of the signal the whole-signal leg ran: recorded, not gated.
 
 Writes profiles/broadband_evaluation.md (and one JSON line per leg on stdout).  A leg that fails or overruns its time limit ends
-the run."""
+the run.
+
+--spectra: the per-bin spectra on top of the stage (apvast.enable_evaluation_spectra, csrc/kernels_bbevalspec.hip) instead: the same
+two timings with the stage on against the stage on plus the spectra (on, spectra, on, spectra), at the reference's test
+parameters one more pair with all 50 ranks evaluated -- a hop's spectra are 20.7 MB there, so a group of 16 runs as sub-launches
+of three hops -- and contrast and NMSE per third-octave band at 48 kHz (recorded, not gated).  Replaces the section "Per-bin
+spectra" at the end of the same file."""
 import argparse
 import json
 import os
@@ -44,7 +50,8 @@ def validation(a0, b0):
     return tuple(r + 0.1 * np.sqrt(np.mean(r ** 2, axis=(1, 2), keepdims=True)) * rng.standard_normal(r.shape) for r in (a0, b0))
 
 
-def make(shape, stage):
+def make(shape, stage, all_ranks=False):
+    """stage 0: off; 1: the evaluation stage; 2: the stage and its per-bin spectra"""
     from ap_vast_unofficial_amd.apvast import apvast
     s = SHAPES[shape]
     a0, b0 = responses()
@@ -52,14 +59,16 @@ def make(shape, stage):
                 mode="broadband", seed=0)
     if stage:
         va, vb = validation(a0, b0)
-        ap.enable_evaluation(va, vb, [s["V"]])
+        ap.enable_evaluation(va, vb, None if all_ranks else [s["V"]])
+    if stage == 2:
+        ap.enable_evaluation_spectra()
     return ap
 
 
-def leg_stream(shape, stage):
+def leg_stream(shape, stage, all_ranks=False):
     s = SHAPES[shape]
     H, hops, nsig = s["H"], s["hops"], s["signal_hops"]
-    ap = make(shape, stage)
+    ap = make(shape, stage, all_ranks)
     x = np.random.default_rng(7).standard_normal((2, (hops + 2) * H))
     times = []
     for h in range(hops + 2):
@@ -74,13 +83,18 @@ def leg_stream(shape, stage):
     t0 = time.perf_counter()
     ap.process_signal(xs[0], xs[1], out=out)
     sig = (time.perf_counter() - t0) / nsig
-    r = {"shape": shape, "stage": bool(stage), "ms_per_hop": float(np.median(times[2:])) * 1e3, "ms_per_hop_process_signal": sig * 1e3,
+    r = {"shape": shape, "stage": int(stage), "all_ranks": bool(all_ranks), "ms_per_hop": float(np.median(times[2:])) * 1e3, "ms_per_hop_process_signal": sig * 1e3,
          "hops": hops, "signal_hops": nsig}
     if stage:
         from ap_vast_unofficial_amd.evaluation import metrics
         m = metrics(ap.evaluation_totals())
-        r.update(nmse=m["nmse"][:, 0].tolist(), contrast_db=m["contrast_db"][:, 0].tolist(), Pv=int(ap._eval_dims()[2]),
-                 Mv=int(ap._eval_dims()[3]))
+        r.update(nmse=m["nmse"][:, -1].tolist(), contrast_db=m["contrast_db"][:, -1].tolist(), Pv=int(ap._eval_dims()[2]),
+                 Mv=int(ap._eval_dims()[3]), E=int(ap._eval_dims()[1]))
+    if stage == 2:
+        from ap_vast_unofficial_amd.evaluation import spectral_metrics, third_octave_bands
+        centres, bands = third_octave_bands(48000, s["N"], f_min=100.0, f_max=16000.0)
+        b = spectral_metrics(ap.evaluation_spectra(), bands)
+        r.update(band_hz=centres.tolist(), band_contrast_db=b["contrast_db"][:, -1].tolist(), band_nmse=b["nmse"][:, -1].tolist())
     ap.close()
     return r
 
@@ -134,17 +148,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", choices=["stream", "kernels"])
     ap.add_argument("--shape", choices=list(SHAPES))
-    ap.add_argument("--stage", type=int, default=0)
+    ap.add_argument("--stage", type=int, default=0, help="0: off, 1: the evaluation stage, 2: the stage and its per-bin spectra")
+    ap.add_argument("--all-ranks", action="store_true", help="evaluate every rank instead of the largest")
+    ap.add_argument("--spectra", action="store_true", help="the legs of the per-bin spectra (see the module docstring)")
     ap.add_argument("--shapes", default="cfg1,reftest")
     ap.add_argument("--limit", type=int, default=240, help="seconds a leg may take")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "broadband_evaluation.md"))
     a = ap.parse_args()
     if a.leg == "stream":
-        print(json.dumps(leg_stream(a.shape, a.stage)))
+        print(json.dumps(leg_stream(a.shape, a.stage, a.all_ranks)))
         return
     if a.leg == "kernels":
         print(json.dumps(leg_kernels(a.shape)))
         return
+    if a.spectra:
+        return main_spectra(a)
     lines = ["# Broadband stream: evaluation stage (`apvast.enable_evaluation`)", "",
              "Written by `tools/bench_broadband_evaluation.py`; every leg a fresh process, two runs per leg, alternating (off, on, off, on).",
              "Validation responses: the control responses plus 10 % independent noise; the largest rank evaluated (E = 1, both zone",
@@ -184,6 +202,58 @@ def main():
     with open(path, "w") as f:
         f.write("\n".join(lines) + tail)
     print("wrote", path)
+
+
+SPECTRA_MARK = "\n# Per-bin spectra"
+
+
+def main_spectra(a):
+    lines = [SPECTRA_MARK.strip("\n") + " (`apvast.enable_evaluation_spectra`)", "",
+             "Written by `tools/bench_broadband_evaluation.py --spectra`; every leg a fresh process, two runs per leg, alternating (stage,",
+             "stage + spectra, stage, stage + spectra).  Same validation responses and calls as above.  Times in ms per hop.", ""]
+    for shape in a.shapes.split(","):
+        s = SHAPES[shape]
+        runs = {1: [], 2: []}
+        for _ in range(2):
+            for stage in (1, 2):
+                runs[stage].append(child(["--leg", "stream", "--shape", shape, "--stage", str(stage)], a.limit))
+        on, sp = runs[1], runs[2]
+        hop = [[r["ms_per_hop"] for r in q] for q in (on, sp)]
+        sig = [[r["ms_per_hop_process_signal"] for r in q] for q in (on, sp)]
+        lines += [f"## {s['label']}", "",
+                  f"The largest rank evaluated (6 pressure sets x {sp[0]['Mv']} microphones = {6 * sp[0]['Mv']} transforms of N = {s['N']} per hop); "
+                  f"{s['hops']} per-hop calls (median), `process_signal` over {s['signal_hops']} hops.", "",
+                  "| | stage on (two runs) | stage + spectra (two runs) | added, mean |", "|---|---|---|---|",
+                  f"| `process_input_buffers` | {rng_of(hop[0])} | {rng_of(hop[1])} | {np.mean(hop[1]) - np.mean(hop[0]):+.3f} |",
+                  f"| `process_signal` | {rng_of(sig[0])} | {rng_of(sig[1])} | {np.mean(sig[1]) - np.mean(sig[0]):+.3f} |", ""]
+        if shape == "reftest":
+            full = [child(["--leg", "stream", "--shape", shape, "--stage", str(stage), "--all-ranks"], a.limit) for stage in (1, 2)]
+            ch = 2 * (2 * full[1]["E"] + 1) * full[1]["Mv"]
+            mb = ch * (s["N"] // 2 + 1) * 16 / 1e6
+            lines += [f"All {full[1]['E']} ranks evaluated ({ch} transforms and {mb:.1f} MB of spectra per hop: sub-launches of "
+                      f"{max(int(64 * 2 ** 20 / (mb * 1e6)), 1)} hops under the 64 MB budget), one run each, stage / stage + spectra: "
+                      f"`process_input_buffers` {full[0]['ms_per_hop']:.3f} / {full[1]['ms_per_hop']:.3f}, `process_signal` "
+                      f"{full[0]['ms_per_hop_process_signal']:.3f} / {full[1]['ms_per_hop_process_signal']:.3f}.", ""]
+        r = sp[0]
+        lines += [f"Contrast and NMSE per third-octave band (`evaluation.third_octave_bands(48000, {s['N']}, 100, 16000)` into "
+                  f"`evaluation.spectral_metrics`), rank {s['V']}, totals over the {s['signal_hops']} hops of the `process_signal` leg; "
+                  "recorded, not gated.  Per zone program [A, B].", "", "| band (Hz) | contrast_db | nmse |", "|---|---|---|"]
+        for i, fc in enumerate(r["band_hz"]):
+            lines.append(f"| {fc:.0f} | " + ", ".join(f"{z[i]:.2f}" for z in r["band_contrast_db"]) + " | "
+                         + ", ".join(f"{z[i]:.4f}" for z in r["band_nmse"]) + " |")
+        lines += ["", f"Broadband, from the energies of the same leg: contrast {', '.join(f'{v:.2f}' for v in r['contrast_db'])} dB, NMSE "
+                  f"{', '.join(f'{v:.4f}' for v in r['nmse'])}.", ""]
+    old = open(a.out).read() if os.path.exists(a.out) else ""
+    notes = ""
+    if SPECTRA_MARK in old:
+        block = old[old.index(SPECTRA_MARK):]
+        old = old[:old.index(SPECTRA_MARK)]
+        mark = "\n## Notes on the spectra"
+        if mark in block:
+            notes = block[block.index(mark):]
+    with open(a.out, "w") as f:
+        f.write(old.rstrip("\n") + "\n\n" + "\n".join(lines) + notes)
+    print("wrote", a.out)
 
 
 if __name__ == "__main__":
