@@ -70,8 +70,9 @@ using d4 = __attribute__((ext_vector_type(4))) double;
 using f4 = __attribute__((ext_vector_type(4))) float;
 
 // R = X^H X for one [M][16] slab of c64 (XT = float2) or c128 (XT = double2) elements, result written to dst (LDS, row
-// stride LD); optional r = X^H d -> sr.  Lane l loads slab element 64 s + l: fully coalesced, and that one register is
-// both the A (X^H) and the B (X) operand of the 16x16x4 MFMA (float64: the B operands are xr + xi and xi - xr of it).
+// stride LD; float64 without d: the real tile G in dst's real parts, see below); optional r = X^H d -> sr.  Lane l loads slab
+// element 64 s + l: fully coalesced, and that one register is both the A (X^H) and the B (X) operand of the 16x16x4 MFMA
+// (float64: the B operands are xr + xi and xi - xr of it).
 template <typename T> struct Mfma16;
 // a b + c in one rounding, float or double (written a += p q + r s the compiler emits a product, an FMA and an addition)
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -193,6 +194,10 @@ __device__ __forceinline__ void correlate16(const XT* __restrict__ X, const XT* 
 #pragma unroll
         for (int t = 0; t < 4; ++t) dst[MM::row(lane, t) * LD + col].x = re[t];
         stamp(stamp_base + 1);                               // MFMAs retired (the stores above read the accumulator)
+        // The dark slab (the one without d) stops here, with G in the real parts of dst: the Cholesky's lanes take their rows of
+        // R_D from G_ij and G_ji themselves (stage 1 of gevd16m_body, the same two operations on the same operands), which saves the
+        // un-mixed tile's trip to LDS and back and its two waits.
+        if constexpr (!WITH_D) return;
         wsync();
         T gt[4];
 #pragma unroll
@@ -1012,6 +1017,24 @@ __device__ __forceinline__ void cmm16x(FA fa, FB fb, int lane, Cx<double> out[4]
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) out[t] = mk<double>(re[t], im[t]);
+}
+
+// The real tile G = Re P + Im P of the product P = A B^H, whose A operand is the transpose of a product's accumulator
+// (a[s] = A[lane & 15][4 s + (lane >> 4)], the layout cmm16x describes) and whose B is fetched as bw(j, k) = B[j][k]:
+//   G = Ar (Br - Bi)^T + Ai (Br + Bi)^T
+// two real MFMAs per k-step on one accumulator, nothing fetched twice.  For a Hermitian P, P_ij = ((G_ij + G_ji) / 2,
+// (G_ij - G_ji) / 2) as in correlate16.  out[t] is G[(lane >> 4) + 4 t][lane & 15].
+template <typename FB>
+__device__ __forceinline__ d4 hmm16_tile(const Cx<double> a[4], FB bw, int lane) {
+    d4 g = {0, 0, 0, 0};
+    const int rc = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const Cx<double> w = bw(rc, 4 * s + kq);
+        g = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s].x, w.x - w.y, g, 0, 0, 0);
+        g = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s].y, w.x + w.y, g, 0, 0, 0);
+    }
+    return g;
 }
 
 

@@ -4,7 +4,7 @@
 //   stage 0  R_B, R_D = X^H X, r = X_B^H d        MFMA 16x16x4 (f64 or f32), slab read once, coalesced
 //   stage 1  Cholesky of R_D + reg I TOGETHER WITH W = L^-1 (elimination applied to [B | I]); rows of B and W
 //            live in registers, one column / one row is broadcast through LDS per step      apvast.py:22-27
-//   stage 2  C = W R_B W^H                         two complex MFMA products                 apvast.py:28-29
+//   stage 2  C = W R_B W^H                         two MFMA products (f64: (W R_B)^T, then C's real tile from registers)   apvast.py:28-29
 //   stage 3  eigenvectors of C                                                                apvast.py:30
 //            float64: a float32 pre-solve -- Householder tridiagonal, Sturm multisection and inverse iteration
 //            (tridiag_presolve16) -- then one or two refinement steps of its eigenvector matrix on the f64 MFMA
@@ -117,6 +117,7 @@ constexpr float kTpLamErr = 0.125f * kTpFinal + 1e-6f;
 // the pair counts as apart.
 constexpr float kTpApart = 1e-5f + 2.f * kTpLamErr;
 constexpr int LDQ = 17, LDX = 17;       // row strides of the float Q and X in the pre-solve's LDS scratch
+constexpr int LDG = 17;                 // row stride, in reals, of stage 2's real tile G (odd: rows and columns both spread over the banks)
 
 // In: C (float64, LDS row stride LD) scaled by 2^sexp, normS2 = ||2^sexp C||_F^2.  Scratch: fQ (16 x LDQ complex), fX (16 x LDX
 // real).  Out: V32 (eigenvectors of C in float32, the f32 MFMA accumulator layout: v[t] is element
@@ -458,8 +459,8 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
     void* const plam = const_cast<char*>(at_hop(z1 ? p.lam1 : p.lam, p.hop_lam));
     int32_t* const pstatus = reinterpret_cast<int32_t*>(const_cast<char*>(at_hop(z1 ? p.status1 : p.status, p.hop_status)));
     using C = Cx<T>;
-    __shared__ C sA[N * LD];       // R_B -> W R_B -> C -> Q (eigenvectors of C) (-> X for U)
-    __shared__ alignas(16) C sB[N * LD];   // R_D -> W = L^-1 (16 bytes: the pre-solve reads its scratch here by ds_read_b128)
+    __shared__ C sA[N * LD];       // R_B -> W R_B (float32; float64: the real tile G of C) -> C -> Q (eigenvectors of C) (-> X for U)
+    __shared__ alignas(16) C sB[N * LD];   // R_D (float64 slabs: its real tile G) -> W = L^-1 (16 bytes: the pre-solve reads its scratch here by ds_read_b128)
     __shared__ C scol[2][N];       // (stage 1 keeps its columns in sB; the later stages' small arrays live here)
     __shared__ C swr[2][N];        // Cholesky: current row of W
     __shared__ C sr[N];
@@ -515,7 +516,14 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int j = jq + 4 * t;
-        brow[t] = sB[i * LD + j];
+        if constexpr (FUSED && sizeof(T) == 8) {
+            // float64 slabs: correlate16 left the real tile G of R_D in sB's real parts, and the row is un-mixed here, from G_ij and
+            // G_ji, by the operations correlate16 applies to R_B: R_D = R_D^H bit for bit and Im R_D_ii = 0 exactly
+            const T gij = sB[i * LD + j].x, gji = sB[j * LD + i].x;
+            brow[t] = mk<T>((T)0.5 * (gij + gji), (T)0.5 * (gij - gji));
+        } else {
+            brow[t] = sB[i * LD + j];
+        }
         if (j == i) brow[t] = mk<T>(brow[t].x + (T)p.reg_dark, 0);
         wrow[t] = mk<T>((j == i) ? (T)1 : (T)0, 0);
     }
@@ -594,19 +602,41 @@ __device__ __forceinline__ void gevd16m_body(const GevdParams& p, const int k, c
         // ---------------- stage 2: C = W A W^H ----------------
         C acc[4];
         const int col = lane & 15;
-        cmm16([&](int r, int kx) { return sB[r * LD + kx]; }, [&](int kx, int c) { return sA[kx * LD + c]; }, lane, acc);
-        wsync();
+        if constexpr (sizeof(T) == 8) {
+            // float64: T1 = W A never goes to LDS.  The first product is formed transposed, X = T1^T = A^T W^T (both operands
+            // read transposed: every real product multiplies the two numbers it always did, in the same k order, so X_ij has
+            // the bits of T1_ji), and its accumulator X[(lane >> 4) + 4 t][lane & 15] is, k-step by k-step, the A operand T1 of
+            // the second product.  That one is Hermitian, C = T1 W^H, and comes from its real tile G = Re C + Im C (hmm16_tile:
+            // 8 MFMAs for the 12 of a general product, W fetched once).  G passes through sA (R_B is spent: every read of it
+            // feeds the MFMAs G depends on) as a dense real tile of odd row stride, and C_ij = ((G_ij + G_ji) / 2,
+            // (G_ij - G_ji) / 2): C = C^H bit for bit, Im C_ii = 0 exactly.
+            cmm16([&](int r, int kx) { return sA[kx * LD + r]; }, [&](int kx, int c) { return sB[c * LD + kx]; }, lane, acc);
+            const d4 g = hmm16_tile(acc, [&](int c, int kx) { return sB[c * LD + kx]; }, lane);
+            T* const sG = reinterpret_cast<T*>(&sA[0]);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) sA[mfma_row<T>(lane, t) * LD + col] = acc[t];          // T1 = W A
-        wsync();
-        cmm16([&](int r, int kx) { return sA[r * LD + kx]; },
-              [&](int kx, int c) { const C w = sB[c * LD + kx]; return mk<T>(w.x, -w.y); }, lane, acc);
-        wsync();
+            for (int t = 0; t < 4; ++t) sG[mfma_row<T>(lane, t) * LDG + col] = g[t];
+            wsync();
+            T gt[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) gt[t] = sG[col * LDG + mfma_row<T>(lane, t)];
+            wsync();
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = mk<T>((T)0.5 * (g[t] + gt[t]), (T)0.5 * (g[t] - gt[t]));
+        } else {
+            cmm16([&](int r, int kx) { return sB[r * LD + kx]; }, [&](int kx, int c) { return sA[kx * LD + c]; }, lane, acc);
+            wsync();
+#pragma unroll
+            for (int t = 0; t < 4; ++t) sA[mfma_row<T>(lane, t) * LD + col] = acc[t];          // T1 = W A
+            wsync();
+            cmm16([&](int r, int kx) { return sA[r * LD + kx]; },
+                  [&](int kx, int c) { const C w = sB[c * LD + kx]; return mk<T>(w.x, -w.y); }, lane, acc);
+            wsync();
+        }
         T nrm = 0;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int row = mfma_row<T>(lane, t);
-            if (row == col) acc[t].y = 0;
+            if (sizeof(T) != 8 && row == col) acc[t].y = 0;                                // (float64: zero already, from the tile)
             sA[row * LD + col] = acc[t];                                                    // C
             nrm += acc[t].x * acc[t].x + acc[t].y * acc[t].y;
         }
