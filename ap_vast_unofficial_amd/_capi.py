@@ -17,6 +17,7 @@ MAX_SRCS = 128        # largest n_srcs of a handle (orders 65..128: csrc/kernels
 F32, F64 = 0, 1
 REG_ABS, REG_REL = 0, 1
 NORM2_METHODS = {"auto": 0, "one_wg": 1, "grid": 2}    # APV_NORM2_AUTO / _ONE_WG / _GRID
+HANKEL_FORMS = {"auto": 0, "displacement": 1, "dense": 2}    # APV_HANKEL_AUTO / _DISPLACEMENT / _DENSE
 
 OK = 0
 ERR_ARG, ERR_HIP, ERR_NOT_PD, ERR_NO_CONVERGE, ERR_RCCL, ERR_STATE = -1, -2, -3, -4, -5, -6
@@ -34,7 +35,7 @@ EXPORTS = (
     "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_eval_energies", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_stream_set_validation_span", "apv_get_validation_span", "apv_validation_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
     "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state", "apv_bb_set_evaluation", "apv_bb_reset_evaluation", "apv_bb_set_evaluation_spectra", "apv_eval_spectra_hops",
     "apv_host_alloc", "apv_host_free",
-    "apv_predict_pressure", "apv_vast_static",
+    "apv_predict_pressure", "apv_vast_static", "apv_hankel_statistics",
     "apv_comm_unique_id", "apv_comm_init", "apv_allgather_filters_dev", "apv_comm_count", "apv_comm_last_gather", "apv_comm_barrier",
     "apv_debug_set_stamps", "apv_debug_live_resources", "apv_device_sync", "apv_device_info",
 )
@@ -184,6 +185,7 @@ def load():
     lib.apv_eval_spectra_hops.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.apv_predict_pressure.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     lib.apv_vast_static.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp]
+    lib.apv_hankel_statistics.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
     lib.apv_comm_unique_id.argtypes = [C.c_char_p]
     lib.apv_comm_init.argtypes = [vp, C.c_char_p, i32, i32]
     lib.apv_allgather_filters_dev.argtypes = [vp, vp, vp]
@@ -1362,6 +1364,38 @@ class Engine:
                                            int(reference_index), int(number_of_eigenvectors), float(mu),
                                            _ptr(gB), _ptr(gD), _ptr(w)))
         return w
+
+    def hankel_statistics(self, stats, tstats=None, *, J, L, M, off=0, skip=1, ncols=None, toff=None, form="auto"):
+        """The broadband Hankel statistics alone (apvast.py:329-364, unscaled), as a hop and vast_static launch them.
+        stats (njobs, M*L, S) or (M*L, S) float64 rings, row m*L + s, read from ring offset `off`; tstats (M, S) pairs with
+        job 0.  skip=1 drops sample J (the python dialect), skip=0 is the contiguous matrix (MATLAB dialect, static solver).
+        ncols and toff default to the python dialect's S - J + (0 if skip else 1) and J if skip else J - 1.
+        form: "auto" (what a hop runs), "displacement" or "dense".  Returns (R (njobs, n, n), r (n,) or None, form_taken)."""
+        st = np.ascontiguousarray(stats, dtype=np.float64)
+        if st.ndim == 2:
+            st = st[None]
+        if st.ndim != 3 or st.shape[1] != M * L:
+            raise ValueError("stats must be (njobs, M*L, S)")
+        if form not in HANKEL_FORMS:
+            raise ValueError(f"form must be one of {sorted(HANKEL_FORMS)}")
+        njobs, _, S = st.shape
+        skip = 1 if skip else 0
+        if ncols is None:
+            ncols = S - J + (0 if skip else 1)
+        if toff is None:
+            toff = J if skip else J - 1
+        ts = None
+        if tstats is not None:
+            ts = np.ascontiguousarray(tstats, dtype=np.float64)
+            if ts.shape != (M, S):
+                raise ValueError("tstats must be (M, S)")
+        n = J * L
+        R = np.empty((njobs, n, n))
+        r = np.empty(n) if ts is not None else None
+        taken = C.c_int32(0)
+        self._chk(self.lib.apv_hankel_statistics(self.h, int(J), int(L), int(M), S, int(off), skip, int(ncols), int(toff), njobs,
+                                                 _ptr(st), _ptr(ts), HANKEL_FORMS[form], _ptr(R), _ptr(r), C.byref(taken)))
+        return R, r, {v: k for k, v in HANKEL_FORMS.items()}[taken.value]
 
     # -- multi-GPU --------------------------------------------------------------
     @staticmethod

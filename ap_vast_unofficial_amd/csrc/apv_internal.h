@@ -573,9 +573,11 @@ hipError_t apv_launch_hist2_f64(int P, int H, int pad, const double* old0, const
                                 double* new1, hipStream_t s);
 // ring[c][(len - H + n + off) % len] = src[c][n], n < H, c < n_ch
 hipError_t apv_launch_ring_append_f64(int len, int H, int off, const double* src, long src_ld, double* ring, int n_ch, hipStream_t s);
-// R = sum_m Y_m Y_m^T of njobs Hankel data matrices (displacement form where it fits, else dense products on the matrix cores)
+// R = sum_m Y_m Y_m^T of njobs Hankel data matrices (displacement form where it fits, else dense products on the matrix cores).
+// form: APV_HANKEL_AUTO is that choice; APV_HANKEL_DISPLACEMENT / APV_HANKEL_DENSE force one (the displacement form where it
+// does not fit: hipErrorInvalidValue, nothing launched).  *form_taken: the form that was launched.
 hipError_t apv_launch_syrk_hankel(hipStream_t s, int n, int J, int L, int M, int S, int off, int skip, int ncols, int njobs,
-                                  const SyrkJobs& jobs);
+                                  const SyrkJobs& jobs, int form = APV_HANKEL_AUTO, int* form_taken = nullptr);
 // r = sum_m Y_m d_m[toff:]
 hipError_t apv_launch_xcorr_hankel(int n, int J, int L, int M, int S, int off, int skip, int ncols, int toff, const double* stats,
                                    const double* tstats, double* r, hipStream_t s);

@@ -931,6 +931,53 @@ int apv_vast_static(apv_handle* h, int32_t Nb, int32_t Nd, int32_t P, int32_t L,
     return rc;
 }
 
+// The Hankel statistics of the broadband stream and of the static solver on host buffers, either form on request
+// (kernels_bb.hip: hankel_corr_kernel / syrk_hankel_kernel, xcorr_hankel_kernel); sizes checked as apv_bb_init checks them.
+int apv_hankel_statistics(apv_handle* h, int32_t J, int32_t L, int32_t M, int32_t S, int32_t off, int32_t skip, int32_t ncols,
+                          int32_t toff, int32_t njobs, const double* h_stats, const double* h_tstats, int32_t form,
+                          double* h_R, double* h_r, int32_t* form_taken) {
+    if (!h || !h_stats || !h_R) return fail(h, APV_ERR_ARG, "null argument");
+    if (h_tstats && !h_r) return fail(h, APV_ERR_ARG, "apv_hankel_statistics: h_tstats without h_r");
+    if (njobs < 1 || njobs > 4) return fail(h, APV_ERR_ARG, "apv_hankel_statistics: njobs must be in 1..4");
+    if (form != APV_HANKEL_AUTO && form != APV_HANKEL_DISPLACEMENT && form != APV_HANKEL_DENSE)
+        return fail(h, APV_ERR_ARG, "apv_hankel_statistics: unknown form");
+    if (J < 1 || L < 1 || M < 1 || S < 1 || (long long)J * L > 4096)
+        return fail(h, APV_ERR_ARG, "apv_hankel_statistics: bad sizes (1 <= J, J L <= 4096)");
+    if (off < 0 || off >= S || (skip != 0 && skip != 1) || ncols < 1 || (long long)ncols + J - 1 + skip > S || toff < 0 ||
+        (long long)toff + ncols > S)
+        return fail(h, APV_ERR_ARG, "apv_hankel_statistics: off, skip, ncols or toff out of range for the ring length");
+    const int n = J * L;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const size_t per = (size_t)M * L * S, nn = (size_t)n * n;
+    ApvOwned tmp;                                           // freed on every way out
+    double *ds = nullptr, *dt = nullptr, *dR = nullptr, *dr = nullptr;
+    HIPCHK(h, tmp.device(&ds, sizeof(double) * per * njobs));
+    HIPCHK(h, tmp.device(&dR, sizeof(double) * nn * njobs));
+    HIPCHK(h, hipMemcpyAsync(ds, h_stats, sizeof(double) * per * njobs, hipMemcpyHostToDevice, st));
+    if (h_tstats) {
+        HIPCHK(h, tmp.device(&dt, sizeof(double) * (size_t)M * S));
+        HIPCHK(h, tmp.device(&dr, sizeof(double) * n));
+        HIPCHK(h, hipMemcpyAsync(dt, h_tstats, sizeof(double) * (size_t)M * S, hipMemcpyHostToDevice, st));
+    }
+    SyrkJobs jobs{};
+    for (int q = 0; q < njobs; ++q) {
+        jobs.stats[q] = ds + q * per;
+        jobs.R[q] = dR + q * nn;
+    }
+    int taken = 0;
+    const hipError_t e = apv_launch_syrk_hankel(st, n, J, L, M, S, off, skip, ncols, njobs, jobs, form, &taken);
+    if (e == hipErrorInvalidValue && form == APV_HANKEL_DISPLACEMENT && !taken)
+        return fail(h, APV_ERR_ARG, "apv_hankel_statistics: the displacement form does not fit these sizes (2 J - 1 <= 1024, LDS <= 158 KiB)");
+    HIPCHK(h, e);
+    if (h_tstats) HIPCHK(h, apv_launch_xcorr_hankel(n, J, L, M, S, off, skip, ncols, toff, ds, dt, dr, st));
+    HIPCHK(h, hipMemcpyAsync(h_R, dR, sizeof(double) * nn * njobs, hipMemcpyDeviceToHost, st));
+    if (h_tstats) HIPCHK(h, hipMemcpyAsync(h_r, dr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (form_taken) *form_taken = taken;
+    return APV_OK;
+}
+
 int apv_stft_analysis_dev(apv_handle* h, int32_t n_ch, const float* d_x, void* d_spec) {
     if (!h || !d_x || !d_spec) return fail(h, APV_ERR_ARG, "null device pointer");
     if (h->cfg.block_size <= 0) return fail(h, APV_ERR_ARG, "handle was created without an STFT geometry");

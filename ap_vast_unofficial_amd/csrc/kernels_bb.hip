@@ -363,12 +363,16 @@ hipError_t apv_launch_ring_append_f64(int len, int H, int off, const double* src
 }
 
 hipError_t apv_launch_syrk_hankel(hipStream_t st, int n, int J, int L, int M, int S, int off, int skip, int ncols, int njobs,
-                                  const SyrkJobs& jobs) {
+                                  const SyrkJobs& jobs, int form, int* form_taken) {
     // the displacement form where its LDS fits (both loudspeakers' sequences of all microphones) and a thread has a lag block,
-    // else the dense products on the matrix cores
+    // else the dense products on the matrix cores; `form` forces one of the two (apv_hankel_statistics)
     const int Sg = S + 8;
     const size_t lds = sizeof(double) * ((size_t)2 * M * Sg + (size_t)hc_red_len(J) + 2 * (size_t)J);
-    if (2 * J - 1 <= HC_TPB && lds <= 158 * 1024 && ncols + J + 2 <= Sg) {
+    const bool fits = 2 * J - 1 <= HC_TPB && lds <= 158 * 1024 && ncols + J + 2 <= Sg;
+    if (form == APV_HANKEL_DISPLACEMENT && !fits) return hipErrorInvalidValue;
+    const bool displacement = fits && form != APV_HANKEL_DENSE;
+    if (form_taken) *form_taken = displacement ? APV_HANKEL_DISPLACEMENT : APV_HANKEL_DENSE;
+    if (displacement) {
         static std::atomic<unsigned long long> attr_set{0};
         const hipError_t e = apv_set_max_dynamic_lds(reinterpret_cast<const void*>(&hankel_corr_kernel), 158 * 1024, attr_set);
         if (e != hipSuccess) return e;

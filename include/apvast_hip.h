@@ -21,7 +21,7 @@
  *     and apv_bb_process_block use buffers sized by apv_create / apv_*_init (apv_process_signal sets up its second
  *     spectra set and pinned staging at its first call); the on-demand readers (apv_stream_get_statistics) allocate their
  *     work space once and keep it; the host-buffer conveniences (apv_update, apv_jdiag_*, apv_predict_pressure,
- *     apv_vast_static) stage through device memory of their own.
+ *     apv_vast_static, apv_hankel_statistics) stage through device memory of their own.
  *
  * Data layout (HBM), subband mode -- bin-major so that one bin's control-point
  * matrix is one contiguous, coalesced slab:
@@ -679,6 +679,23 @@ int  apv_predict_pressure(apv_handle* h, int32_t T, int32_t L, int32_t M, int32_
  *                                                         replaces Matlab/ControlMethods/vast.m:1-97 */
 int  apv_vast_static(apv_handle* h, int32_t Nb, int32_t Nd, int32_t P, int32_t L, int32_t J, int32_t modeling_delay,
                      int32_t reference_index, int32_t V, double mu, const double* h_gB, const double* h_gD, double* h_w);
+/* The broadband Hankel statistics alone, as a hop and apv_vast_static launch them (kernel-level entry for tests):
+ * R_j = sum_m Y_m Y_m^T for njobs (1..4) sets of rings and, with h_tstats, r = sum_m Y_m d_m for job 0, where
+ * Y_m[(s, i)][c] = g_{s,m}[J - 1 - i + c], c < ncols, g = the ring unwrapped from `off` (sample J dropped when skip = 1) and
+ * d_m[c] = the unwrapped target ring's sample toff + c.  h_stats [njobs][M*L][S] (row m*L + s), h_tstats [M][S] or NULL,
+ * h_R [njobs][n][n], n = J L, h_r [n] or NULL (written only with h_tstats), all float64 on the host; *form_taken (may be NULL)
+ * receives the form that ran.  No dialect scaling.  form: APV_HANKEL_AUTO is the launcher's own choice -- the displacement
+ * form (one full sum per lag, then a walk down each diagonal) where 2 J - 1 <= 1024, its LDS (2 M (S + 8) doubles and the
+ * work arrays) stays within 158 KiB and ncols + J + 2 <= S + 8, else the dense products on the matrix cores;
+ * APV_HANKEL_DISPLACEMENT / APV_HANKEL_DENSE force one.  APV_ERR_ARG (nothing launched) unless 1 <= J, 1 <= L, 1 <= M,
+ * n <= 4096, 0 <= off < S, skip in {0, 1}, ncols >= 1, ncols + J - 1 + skip <= S, 0 <= toff, toff + ncols <= S, and for
+ * APV_HANKEL_DISPLACEMENT where that form does not fit.          replaces apvast.py:329-364 / apVast.m:410-447 (unscaled) */
+#define APV_HANKEL_AUTO         0
+#define APV_HANKEL_DISPLACEMENT 1
+#define APV_HANKEL_DENSE        2
+int  apv_hankel_statistics(apv_handle* h, int32_t J, int32_t L, int32_t M, int32_t S, int32_t off, int32_t skip, int32_t ncols,
+                           int32_t toff, int32_t njobs, const double* h_stats, const double* h_tstats, int32_t form,
+                           double* h_R, double* h_r, int32_t* form_taken);
 
 /* ---- multi-GPU: bins sharded across ranks, one RCCL all-gather ---------- */
 int  apv_comm_unique_id(char id_out[128]);                                /* rank 0 calls, then broadcasts */

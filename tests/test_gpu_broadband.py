@@ -202,6 +202,65 @@ def test_broadband_statistics_shapes(golden, J, S, L, M):
     ap.close()
 
 
+def test_broadband_statistics_single_zone_two_jobs(golden):
+    """One zone program: the statistics launch carries two jobs (R_AA, R_AB), not four.  (J, S, L, M) = (5, 703, 4, 3), 698
+    columns, the displacement form; four hops against the oracle at the bound of test_broadband_statistics_shapes."""
+    from ap_vast_unofficial_amd.apvast import apvast
+    from oracle.broadband import BroadbandOracle
+    J, S, L, M = 5, 703, 4, 3
+    rirs = golden("rirs_cfg1")
+    rA, rB = rirs["rirA"][:200, :L, :M], rirs["rirB"][:200, :L, :M]
+    N, H, V = 128, 64, 2
+    ap = apvast(N, rA, rB, J, 3, 0, 1, V, 1.0, S, hop_size=H, run_B=False, perceptual=False, mode="broadband", seed=11)
+    np.random.seed(11)
+    orc = BroadbandOracle(N, rA, rB, J, 3, 0, 1, V, 1.0, S, hop_size=H, run_B=False)
+    x = np.random.default_rng(3).standard_normal((2, 4 * H))
+    try:
+        for h in range(4):
+            ap.process_input_buffers(x[0, h * H:(h + 1) * H], x[1, h * H:(h + 1) * H])
+            orc.process_input_buffers(x[0, h * H:(h + 1) * H], x[1, h * H:(h + 1) * H])
+    except np.linalg.LinAlgError:
+        pass        # as in test_broadband_statistics_shapes: the statistics stand
+    for got, exp in ((ap.R_A_to_A, orc.R_AA), (ap.R_A_to_B, orc.R_AB)):
+        assert np.abs(got - exp).max() <= 1e-12 * np.abs(exp).max()
+    assert np.abs(ap.r_A[:, 0] - orc.r_A).max() <= 1e-12 * np.abs(orc.r_A).max()
+    assert ap.R_B_to_B is None and ap.R_B_to_A is None
+    ap.close()
+
+
+def test_broadband_matlab_dialect_dense_statistics(golden):
+    """dialect='matlab' where the statistics take the dense fall-back, (J, S, L, M) = (24, 1664, 3, 8) as in
+    test_broadband_statistics_shapes: the contiguous matrix has 1641 columns, one more than a multiple of four, so the dense
+    kernel's guarded last step runs with one live column.  Two hops against the oracle at the bounds of
+    test_broadband_matlab_dialect_vs_oracle."""
+    from ap_vast_unofficial_amd.apvast import apvast
+    from oracle.broadband_matlab import MatlabBroadbandOracle
+    J, S, L, M = 24, 1664, 3, 8
+    rirs = golden("rirs_cfg1")
+    rA, rB = rirs["rirA"][:200, :L, :M], rirs["rirB"][:200, :L, :M]
+    N, H, ranks = 128, 64, [1, 3, 8, 20]
+    ap = apvast(N, rA, rB, J, 3, 0, 1, ranks, 1.0, S, perceptual=False, mode="broadband", dialect="matlab")
+    orc = MatlabBroadbandOracle(N, rA, rB, J, 3, 0, 1, ranks, 1.0, S)
+    rng = np.random.default_rng(21)               # both sides from the same small noise, as in that test
+    orc.response[:] = 1e-3 * rng.standard_normal(orc.response.shape)
+    orc.target_response[:] = 1e-3 * rng.standard_normal(orc.target_response.shape)
+    ap.set_state({"response": orc.response, "target_response": orc.target_response})
+    x = np.random.default_rng(8).standard_normal((2, 2 * H))
+    for h in range(2):
+        got = ap.process_input_buffers(x[0, h * H:(h + 1) * H], x[1, h * H:(h + 1) * H])
+        exp = orc.process_input_buffers(x[0, h * H:(h + 1) * H], x[1, h * H:(h + 1) * H])
+        for q in range(4):
+            e = exp[q]
+            assert np.abs(np.stack(got[q]) - e).max() <= 1e-6 * max(np.abs(e).max(), 1e-30), (h, q)
+    for gotR, expR in ((ap.R_A_to_A, orc.R_AA), (ap.R_A_to_B, orc.R_AB), (ap.R_B_to_B, orc.R_BB), (ap.R_B_to_A, orc.R_BA)):
+        assert np.abs(gotR - expR).max() <= 1e-7 * np.abs(expR).max()
+    assert np.abs(ap.r_A[:, 0] - orc.r_A).max() <= 1e-12 * np.abs(orc.r_A).max()
+    assert np.abs(ap.lambda_A[:20] / orc.lambda_A[:20] - 1).max() < 1e-6
+    for i in range(len(ranks)):
+        assert np.linalg.norm(ap.w_A[i, :, 0] - orc.w_A[i]) <= 1e-6 * np.linalg.norm(orc.w_A[i])
+    ap.close()
+
+
 @pytest.mark.parametrize("perceptual", [False, True])
 def test_broadband_matlab_dialect_vs_oracle(golden, perceptual):
     """dialect='matlab' in broadband mode against the restatement of apVast.m (unpinned): contiguous data
