@@ -33,7 +33,7 @@ EXPORTS = (
     "apv_set_rank_list", "apv_update_dev", "apv_set_update_streams", "apv_update", "apv_corr_dev", "apv_corr_bf16_dev", "apv_to_bf16_dev", "apv_gevd_vast_dev", "apv_jdiag_batched", "apv_jdiag_large", "apv_jdiag_leading", "apv_jdiag_large_c128", "apv_norm2",
     "apv_stft_analysis_dev", "apv_istft_ola_dev", "apv_analysis_dev", "apv_analysis_jobs_dev", "apv_synthesis_dev",
     "apv_stream_set_stat_hops", "apv_stream_set_stat_forgetting", "apv_stream_set_filter_taps", "apv_constrain_filters", "apv_stream_set_synthesis", "apv_fir_synthesis", "apv_stream_set_evaluation", "apv_stream_set_evaluation_spectra", "apv_eval_spectrum_step", "apv_stream_set_evaluation_detectability", "apv_eval_detect_step", "apv_stream_reset_evaluation", "apv_eval_pressure", "apv_eval_energies", "apv_stream_init", "apv_stream_set_perceptual", "apv_process_block", "apv_process_block_f64", "apv_process_signal", "apv_process_signal_f64", "apv_stream_is_f64", "apv_stream_get_statistics", "apv_stream_not_converged", "apv_stream_set_rirs", "apv_set_mu", "apv_set_span", "apv_get_span", "apv_stream_set_effort_limit", "apv_get_effort", "apv_limit_effort", "apv_stream_set_validation_span", "apv_get_validation_span", "apv_validation_span", "apv_state_bytes", "apv_get_state", "apv_set_state",
-    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state", "apv_bb_set_evaluation", "apv_bb_reset_evaluation", "apv_bb_set_evaluation_spectra", "apv_eval_spectra_hops",
+    "apv_bb_set_rank_list", "apv_bb_init", "apv_bb_set_perceptual", "apv_bb_process_block", "apv_bb_process_signal", "apv_bb_set_rirs", "apv_bb_get_state", "apv_bb_set_state", "apv_bb_set_evaluation", "apv_bb_reset_evaluation", "apv_bb_set_evaluation_spectra", "apv_eval_spectra_hops", "apv_bb_set_evaluation_detectability", "apv_eval_detect_hops",
     "apv_host_alloc", "apv_host_free",
     "apv_predict_pressure", "apv_vast_static", "apv_hankel_statistics",
     "apv_comm_unique_id", "apv_comm_init", "apv_allgather_filters_dev", "apv_comm_count", "apv_comm_last_gather", "apv_comm_barrier",
@@ -183,6 +183,8 @@ def load():
     lib.apv_eval_energies.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.apv_bb_set_evaluation_spectra.argtypes = [vp, i32]
     lib.apv_eval_spectra_hops.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.apv_bb_set_evaluation_detectability.argtypes = [vp, i32, vp, C.c_double, C.c_double, C.c_double]
+    lib.apv_eval_detect_hops.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp]
     lib.apv_predict_pressure.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     lib.apv_vast_static.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_double, vp, vp, vp]
     lib.apv_hankel_statistics.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
@@ -542,6 +544,42 @@ class Engine:
         """Per-bin spectra of the broadband stream's evaluation stage, after bb_set_evaluation, once, at any hop boundary
         (apv_bb_set_evaluation_spectra): ring and spectra start from zero here."""
         self._chk(self.lib.apv_bb_set_evaluation_spectra(self.h, 1))
+
+    def bb_set_evaluation_detectability(self, tables):
+        """Perceptual detectability of the broadband stream's evaluated pressures, after bb_set_evaluation_spectra, once, at any
+        hop boundary (apv_bb_set_evaluation_detectability): the totals start from zero here.  tables:
+        ap_vast_unofficial_amd.perceptual.PerceptualTables of the block size."""
+        G2 = np.ascontiguousarray(tables.G2, dtype=np.float64)
+        if G2.ndim != 2 or G2.shape[0] != self.K:
+            raise ValueError("the tables' G2 must be (n_bins, n_channels)")
+        self._chk(self.lib.apv_bb_set_evaluation_detectability(self.h, G2.shape[1], _ptr(G2), float(tables.Cs), float(tables.Ca),
+                                                               float(tables.Leff)))
+
+    def eval_detect_hops(self, spec, tables, Z, E, totals=None, hops_per_launch=None):
+        """The three hop-batched launches of the broadband stream's detectability stage alone (apv_eval_detect_hops): spec
+        (n, N/2 + 1, Z (2 E + 1), Mv) complex128, the bin-major spectra of n consecutive hops (per program: bright of the E ranks,
+        dark of the E ranks, target); tables: PerceptualTables of N (or any object with G2 (N/2 + 1, C), Cs, Ca, Leff); totals
+        (Z, 6 E, Mv) float64 (None: zeros); hops_per_launch: at most that many hops per sub-launch (None: all n in one).  Returns
+        the hops' values (n, Z, 2 E, Mv) -- per program the error of the E ranks, then the leak -- and the new totals."""
+        spec = np.ascontiguousarray(spec, dtype=np.complex128)
+        G2 = np.ascontiguousarray(tables.G2, dtype=np.float64)
+        Z, E = int(Z), int(E)
+        if spec.ndim != 4 or G2.ndim != 2 or spec.shape[0] < 1:
+            raise ValueError("spec must be (n, N/2 + 1, Z (2 E + 1), Mv) and the tables' G2 (N/2 + 1, C)")
+        n, K, sets, Mv = spec.shape
+        totals = np.zeros((Z, 6 * E, Mv)) if totals is None else np.ascontiguousarray(totals, dtype=np.float64)
+        if sets != Z * (2 * E + 1) or G2.shape[0] != K or totals.shape != (Z, 6 * E, Mv):
+            raise ValueError("spec (n, N/2 + 1, Z (2 E + 1), Mv), G2 (N/2 + 1, C) and totals (Z, 6 E, Mv) do not agree")
+        per = n if hops_per_launch is None else int(hops_per_launch)
+        ds, dt = self.to_device(spec), self.to_device(totals)
+        dh = DeviceBuffer(self, 8 * n * Z * 2 * E * Mv)
+        try:
+            self._chk(self.lib.apv_eval_detect_hops(self.h, ds.ptr, n, per, 2 * (K - 1), Z, E, Mv, G2.shape[1], _ptr(G2),
+                                                    float(tables.Cs), float(tables.Ca), float(tables.Leff), dh.ptr, dt.ptr))
+            return dh.download((n, Z, 2 * E, Mv), np.float64), dt.download(totals.shape, np.float64)
+        finally:
+            for b in (ds, dt, dh):
+                b.free()
 
     def eval_spectra_hops(self, p, tail, N, H, totals=None, hops_per_launch=0):
         """The three launches of the broadband stream's per-bin spectra alone (apv_eval_spectra_hops): p (Z, 2 E + 1, n H, Mv)

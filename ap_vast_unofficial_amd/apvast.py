@@ -85,6 +85,9 @@ What is different (keyword-only, after ``perceptual``)
     and audible-hop counts, ``evaluation_detectability_hops()`` the last call's hops, ``evaluation.detectability_metrics`` means
     and audible shares; get_state() gains ``evaluation_detectability`` (Z, 6 E + 1, Mv): the device's totals and, in a last row,
     the hops they cover.  Everything else the stream computes is unchanged, bit for bit.
+    In broadband mode the detectability is switched on by a method instead, ``ap.enable_evaluation_detectability()``, after
+    ``enable_evaluation_spectra()``, once and at any hop boundary; the totals and the hop count start there, and process_signal
+    evaluates a whole group of hops in three launches whose bits are those of the hop loop.
   * ``effort_limit_db`` (subband mode; a float, (K,) or (2, K) array of dB values, row 0 = zone program A, ``+inf`` = no limit in
     that bin): the array effort e = sum_l |W[k, v, l]|^2 of every filter of a hop -- relative to the reference loudspeaker alone,
     whose effort is 0 dB -- is held to E = 10^(dB / 10) between the joint diagonalisation and the filter-length projection.  A
@@ -759,7 +762,8 @@ class apvast:
         ``evaluation_spectra=True`` does: evaluation_spectra() and evaluation.spectral_metrics() work the same, get_state() gains
         ``evaluation_spectra`` (Z, 3 E + 1, K, Mv) and ``evaluation_ring`` (Z, 2 E + 1, Mv, N), reset_evaluation() zeroes both.
         Ring and spectra start from zero here.  process_signal transforms a whole group of hops per launch; the bits are those
-        of the hop loop.  Everything else the object computes is untouched."""
+        of the hop loop.  Everything else the object computes is untouched.  enable_evaluation_detectability(), after this call,
+        adds the masking model's detectability of error and leakage on the same spectra."""
         if self.mode != "broadband":
             raise RuntimeError("enable_evaluation_spectra() is the broadband mode's switch: in subband mode pass "
                                "evaluation_spectra=True to the constructor")
@@ -770,6 +774,35 @@ class apvast:
         self._eng.bb_set_evaluation_spectra()
         self._bb_evaluation_spectra = True
         self._bb_spec_hops = 0              # hops since the switch: evaluation_spectra() is None before the first
+
+    def enable_evaluation_detectability(self):
+        """Broadband mode: switch the perceptual detectability of the evaluated pressures on, after
+        enable_evaluation_spectra(), once, at any hop boundary.  From here on the device evaluates, behind the spectra of every
+        hop, the second half of the masking model as the subband keyword ``evaluation_detectability=True`` does -- "error", the
+        reproduction error masked by the program the listener wants, and "leak", the other program's leakage masked by this
+        zone's own target (the threshold in quiet with one program), D = 1 just audible: evaluation_detectability(),
+        evaluation_detectability_hops() and evaluation.detectability_metrics() work the same, get_state() gains
+        ``evaluation_detectability`` (Z, 6 E + 1, Mv), reset_evaluation() zeroes it.  The tables are
+        PerceptualTables(block_size, sampling_rate, fullscale_db_spl) -- ``self.model`` with perceptual=True -- and are kept as
+        ``detectability_model``; a block they cannot be calibrated for raises what they raise and leaves the object as it was.
+        Totals start from zero here.  process_signal evaluates a whole group of hops in three launches; the bits are those of the
+        hop loop.  Everything else the object computes is untouched."""
+        if self.mode != "broadband":
+            raise RuntimeError("enable_evaluation_detectability() is the broadband mode's switch: in subband mode pass "
+                               "evaluation_detectability=True to the constructor")
+        if self.__dict__.get("_bb_evaluation") is None or not self.__dict__.get("_bb_evaluation_spectra"):
+            raise RuntimeError("enable_evaluation_detectability() comes after enable_evaluation_spectra()")
+        if self.__dict__.get("_bb_evaluation_detectability"):
+            raise RuntimeError("enable_evaluation_detectability(): this object keeps its detectabilities already")
+        tables = self.__dict__.get("model") if self.__dict__.get("perceptual") else None
+        if tables is None:
+            from .perceptual import PerceptualTables
+            tables = PerceptualTables(self.block_size, self.sampling_rate, self._fullscale_db_spl)
+        self._eng.bb_set_evaluation_detectability(tables)
+        self.detectability_model = tables
+        self._bb_evaluation_detectability = True
+        self._detect_hops = 0               # hops the totals cover: since the switch, reset_evaluation() or a restored state
+        self._bb_detect_rec = 0             # hops in the record of the last call; None from the accessors before the first
 
     @staticmethod
     def _eval_split(e, E):
@@ -840,9 +873,20 @@ class apvast:
 
     def _detect_dims(self):
         Z, E, _, Mv = self._eval_dims()
-        if not self.__dict__.get("_evaluation_detectability"):
+        if self.__dict__.get("mode") == "broadband":
+            if not self.__dict__.get("_bb_evaluation_detectability"):
+                raise RuntimeError("this object keeps no detectabilities: call enable_evaluation_detectability()")
+        elif not self.__dict__.get("_evaluation_detectability"):
             raise RuntimeError("this object keeps no detectabilities: pass evaluation_detectability=True")
         return Z, E, Mv
+
+    def _detect_state(self, name, shape):
+        """a state array of the detectability stage; in broadband mode None while no hop has run since the switch"""
+        if self._hops == 0:
+            return None
+        if self.mode == "broadband":
+            return self._eng.bb_get_state(name, shape) if self._bb_detect_rec else None
+        return self._eng.get_state(name, shape, np.float64)
 
     def evaluation_detectability(self):
         """Perceptual detectability D of the evaluated pressures (D = 1: just audible) over every hop since construction, set_state
@@ -852,9 +896,9 @@ class apvast:
         "hops", the hops counted; evaluation.detectability_metrics() turns them into means and audible shares.  None before the
         first hop."""
         Z, E, Mv = self._detect_dims()
-        if self._hops == 0:
+        t = self._detect_state("eval_detect", (Z, 2, 3, E, Mv))
+        if t is None:
             return None
-        t = self._eng.get_state("eval_detect", (Z, 2, 3, E, Mv), np.float64)
         out = {"hops": int(self._detect_hops)}
         for i, name in enumerate(("error", "leak")):
             out[name] = np.ascontiguousarray(t[:, i, 0])
@@ -868,19 +912,24 @@ class apvast:
         Z, E, Mv = self._detect_dims()
         if self._hops == 0:
             return None
-        n = self._eng.state_bytes("eval_detect_hops") // (8 * Z * 2 * E * Mv)
+        if self.mode == "broadband":
+            n = self._bb_detect_rec         # the host knows the hops of the last call
+        else:
+            n = self._eng.state_bytes("eval_detect_hops") // (8 * Z * 2 * E * Mv)
         if n == 0:
             return None
-        r = self._eng.get_state("eval_detect_hops", (n, Z, 2, E, Mv), np.float64)
+        r = self._detect_state("eval_detect_hops", (n, Z, 2, E, Mv))
         return {"error": np.ascontiguousarray(r[:, :, 0]), "leak": np.ascontiguousarray(r[:, :, 1])}
 
     def reset_evaluation(self):
         """Totals to zero and the output histories to silence: the next hop's totals are its own energies.  With
         evaluation_spectra=True, or after enable_evaluation_spectra() in broadband mode, the per-bin energies and the pressure ring
-        too, with evaluation_detectability=True its totals."""
+        too, with evaluation_detectability=True its totals.  After enable_evaluation_detectability() in broadband mode the
+        detectability totals and their hop count go to zero as well."""
         self._eval_dims()
         if self.mode == "broadband":
             self._eng.bb_reset_evaluation()
+            self._detect_hops = 0
             return
         self._eng.reset_evaluation()
         self._detect_hops = 0
@@ -1003,6 +1052,9 @@ class apvast:
         self._bb_eval_hops = 0
         self._bb_evaluation_spectra = False # enable_evaluation_spectra() switches the per-bin spectra on
         self._bb_spec_hops = 0
+        self._bb_evaluation_detectability = False   # enable_evaluation_detectability() switches the detectability on
+        self.detectability_model = None     # the tables the device received there
+        self._detect_hops = self._bb_detect_rec = 0
 
     def _refresh_broadband(self):
         """A hop has run: what the attributes hold is stale.  Nothing is fetched here (see _bb_fetch)."""
@@ -1053,6 +1105,9 @@ class apvast:
             out = self._eng.bb_process_block(input_A, input_B, self._n_out)      # (groups, H, L), fresh for every hop
             res = self._split_groups(out)
             self._bb_eval_hops = self._bb_spec_hops = 1
+            if self._bb_evaluation_detectability:
+                self._bb_detect_rec = 1
+                self._detect_hops += 1
             self._refresh_broadband()
             return res
         out = self._eng.process_block(input_A, input_B, self._n_out)         # (groups, H, L): one (H, L) array per zone and rank
@@ -1086,6 +1141,9 @@ class apvast:
             out = self._eng.bb_process_signal(input_A, input_B, self._n_out, out=out)
             res = self._split_groups(out)
             self._bb_eval_hops = self._bb_spec_hops = input_A.size // self.hop_size
+            if self._bb_evaluation_detectability:
+                self._bb_detect_rec = input_A.size // self.hop_size
+                self._detect_hops += input_A.size // self.hop_size
             self._hops += input_A.size // self.hop_size - 1
             self._refresh_broadband()
             return res
@@ -1358,7 +1416,9 @@ class apvast:
         # the totals as the device keeps them -- per program sum, max and audible count of the error, then of the leak -- and
         # in a last row the hops they cover, which only the host counts
         Z, E, _, Mv = self._eval_dims()
-        return np.concatenate([self._eng.get_state("eval_detect", (Z, 6 * E, Mv), np.float64),
+        tot = (self._eng.bb_get_state("eval_detect", (Z, 6 * E, Mv)) if self.mode == "broadband"
+               else self._eng.get_state("eval_detect", (Z, 6 * E, Mv), np.float64))
+        return np.concatenate([tot,
                                np.full((Z, 1, Mv), float(self._detect_hops))], axis=1)
 
     def _put_detectability(self, value):
@@ -1366,7 +1426,10 @@ class apvast:
         hops = a[0, 6 * E, 0]
         if not (hops >= 0 and hops == np.floor(hops) and np.all(a[:, 6 * E] == hops)):
             raise ValueError("evaluation_detectability: the last row must hold one hop count, a non-negative integer")
-        self._eng.set_state("eval_detect", np.ascontiguousarray(a[:, :6 * E]))
+        if self.mode == "broadband":
+            self._eng.bb_set_state("eval_detect", np.ascontiguousarray(a[:, :6 * E]))
+        else:
+            self._eng.set_state("eval_detect", np.ascontiguousarray(a[:, :6 * E]))
         self._detect_hops = int(hops)
 
     def close(self):
@@ -1388,10 +1451,12 @@ def _state_rows():
     fir, ev_sub = sub(lambda self: self.synthesis == "fir"), sub(lambda self: self._evaluation is not None)
     # the evaluation stage: the constructor's in subband mode, enable_evaluation()'s in broadband mode
     ev = lambda self: ev_sub(self) or (bb(self) and getattr(self, "_bb_evaluation", None) is not None)
-    evs_sub, evd = sub(lambda self: self._evaluation_spectra), sub(lambda self: self._evaluation_detectability)
+    evs_sub, evd_sub = sub(lambda self: self._evaluation_spectra), sub(lambda self: self._evaluation_detectability)
     # the per-bin spectra: the constructor's keyword in subband mode, enable_evaluation_spectra()'s in broadband mode
     evs = lambda self: evs_sub(self) or (bb(self) and getattr(self, "_bb_evaluation", None) is not None
                                          and bool(getattr(self, "_bb_evaluation_spectra", False)))
+    # the detectability: the constructor's keyword in subband mode, enable_evaluation_detectability()'s in broadband mode
+    evd = lambda self: evd_sub(self) or (bb(self) and bool(getattr(self, "_bb_evaluation_detectability", False)) and bool(evs(self)))
     live = lambda self: self._live_applied
     N = lambda self: self.block_size
     S = lambda self: self.statistics_buffer_length

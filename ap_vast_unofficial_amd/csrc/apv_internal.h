@@ -488,6 +488,19 @@ hipError_t apv_launch_eval_spectra(const EvalSpectraArgs& a, hipStream_t s, std:
 // in hop order -- and leaves cur and len at the last line.  Both line buffers hold N - H + min(n, per_launch) H samples per
 // channel, spec min(n, per_launch) hops.  The float64 tables of N must exist (apv_stft_prepare(N, 1)).
 constexpr size_t APV_BBSPEC_SCRATCH_BYTES = (size_t)64 << 20;       // budget of spec; one hop where a hop is larger
+// the optional detectability part (kernels_evaldetect.hip, hop-batched): behind every sub-launch's transforms, on its scratch,
+// before the next sub-launch overwrites it.  curves and part hold min(n, per_launch) hops; hop i of the call goes to slot
+// slot0 + i of rec.
+struct BbSpecDetectArgs {
+    const double* G2T;
+    const double* quiet;
+    double* curves;
+    double* part;
+    double* rec;
+    double* totals;
+    int slot0, C;
+    double Cs, Ca, Leff;
+};
 struct BbSpecArgs {
     const double* p;
     size_t p_set;
@@ -497,10 +510,15 @@ struct BbSpecArgs {
     void* spec;
     double* totals;
     int N, H, Z, E, Mv, n, per_launch;
+    const BbSpecDetectArgs* detect;  // null: off
 };
 bool apv_bbspec_size_ok(int N, int H, int Z, int E, int Mv, std::string* why);
 int apv_bbspec_hops_fit(int N, int Z, int E, int Mv);         // hops per sub-launch the budget allows, at least 1
 hipError_t apv_launch_bbspec_hops(BbSpecArgs* a, hipStream_t s, std::string* why);
+// the detectability part alone on a caller's spectra [n][N/2 + 1][Z (2 E + 1) Mv], in sub-launches of at most per_launch hops as
+// above (d.slot0 the slot of the first hop; d.curves and d.part hold min(n, per_launch) hops)
+hipError_t apv_launch_bbspec_detect_hops(const BbSpecDetectArgs& d, const void* spec, int n, int per_launch, int N, int Z, int E, int Mv,
+                                         hipStream_t s, std::string* why);
 
 // kernels_evaldetect.hip: perceptual detectability of the evaluated pressures (see the file header).  Three launches behind the
 // spectra above, on their bin-major scratch spec [N/2 + 1][Z (2 E + 1) Mv]: the squared weighting curves of the Z Mv target
@@ -526,6 +544,20 @@ bool apv_eval_detect_size_ok(int N, int Z, int E, int Mv, int C, std::string* wh
 int apv_eval_detect_chunks(int N, int Z, int E, int Mv);      // partial sums per element: a function of the sizes alone
 hipError_t apv_launch_eval_detect_quiet(int N, int C, const double* G2T, double Cs, double Ca, double Leff, double* quiet, hipStream_t s);
 hipError_t apv_launch_eval_detect(const EvalDetectArgs& a, hipStream_t s, std::string* why);
+// the hop-batched form, on the spectra of n consecutive hops spec [n][N/2 + 1][Z (2 E + 1) Mv]: curves [n][N/2 + 1][Z Mv], part
+// [n][chunks][Z][2 E][Mv], hop i into slot slot0 + i of rec (slots of [Z][2 E][Mv]) and, in hop order, into the totals.  n <= 65535.
+struct EvalDetectHopsArgs {
+    const void* spec;
+    const double* G2T;
+    const double* quiet;
+    double* curves;
+    double* part;
+    double* rec;
+    double* totals;
+    int slot0, n, N, Z, E, Mv, C;
+    double Cs, Ca, Leff;
+};
+hipError_t apv_launch_eval_detect_hops(const EvalDetectHopsArgs& a, hipStream_t s, std::string* why);
 
 // whole-signal path, a chunk of hops per launch (kernels_stft.hip / kernels_stream.hip; see process_signal_chunked_t in stream.hip)
 hipError_t apv_launch_stft_analysis_chunk(int f64, int N, int n_jobs, const void* const* x, const int* n_ch, void* const* spec,

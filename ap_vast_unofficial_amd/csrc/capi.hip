@@ -1378,6 +1378,45 @@ int apv_eval_detect_step(apv_handle* h, const void* d_spec, int32_t N, int32_t Z
     return APV_OK;
 }
 
+int apv_eval_detect_hops(apv_handle* h, const void* d_spec, int32_t n_hops, int32_t hops_per_launch, int32_t N, int32_t Z, int32_t E,
+                         int32_t Mv, int32_t n_channels, const double* h_G2, double Cs, double Ca, double Leff, double* d_hops,
+                         double* d_totals) {
+    if (!h || !d_spec || !h_G2 || !d_hops || !d_totals) return fail(h, APV_ERR_ARG, "null pointer");
+    if (N < 1 || Z < 1 || E < 1 || Mv < 1 || n_channels < 1 || n_hops < 1 || hops_per_launch < 1)
+        return fail(h, APV_ERR_ARG, "apv_eval_detect_hops: N, Z, E, Mv, n_channels, n_hops and hops_per_launch must be at least 1");
+    if (N & 1) return fail(h, APV_ERR_ARG, "apv_eval_detect_hops: N must be even");
+    if (!std::isfinite(Cs) || !std::isfinite(Ca) || !std::isfinite(Leff) || !(Ca > 0.0))
+        return fail(h, APV_ERR_ARG, "apv_eval_detect_hops: Cs, Ca and Leff must be finite, Ca positive");
+    std::string why;
+    if (!apv_eval_detect_size_ok(N, Z, E, Mv, n_channels, &why)) return fail(h, APV_ERR_ARG, why);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc = lanes_join(h, true)) return rc;
+    // the table, the curves and the partial sums are this call's own: a test entry, not a per-hop path
+    const int K = N / 2 + 1, chunks = apv_eval_detect_chunks(N, Z, E, Mv), c = std::min<int>(std::min<int>(n_hops, hops_per_launch), 65535);
+    std::vector<double> gt((size_t)n_channels * K);
+    for (int k = 0; k < K; ++k)
+        for (int i = 0; i < n_channels; ++i) gt[(size_t)i * K + k] = h_G2[(size_t)k * n_channels + i];
+    ApvOwned t;
+    double *G2T = nullptr, *quiet = nullptr, *curves = nullptr, *part = nullptr;
+    HIPCHK(h, t.device(&G2T, sizeof(double) * gt.size()));
+    HIPCHK(h, t.device(&quiet, sizeof(double) * K));
+    HIPCHK(h, t.device(&curves, sizeof(double) * (size_t)c * K * Z * Mv));
+    HIPCHK(h, t.device(&part, sizeof(double) * (size_t)c * chunks * Z * 2 * E * Mv));
+    HIPCHK(h, hipMemcpyAsync(G2T, gt.data(), sizeof(double) * gt.size(), hipMemcpyHostToDevice, h->stream));
+    hipError_t e = apv_launch_eval_detect_quiet(N, n_channels, G2T, Cs, Ca, Leff, quiet, h->stream);
+    if (e == hipSuccess) {
+        BbSpecDetectArgs d{};
+        d.G2T = G2T; d.quiet = quiet; d.curves = curves; d.part = part; d.rec = d_hops; d.totals = d_totals;
+        d.slot0 = 0; d.C = n_channels; d.Cs = Cs; d.Ca = Ca; d.Leff = Leff;
+        e = apv_launch_bbspec_detect_hops(d, d_spec, n_hops, c, N, Z, E, Mv, h->stream, &why);
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);  // gt and the scratch go out of scope
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP,
+                                     why.empty() ? hipGetErrorString(e) : why);
+    return APV_OK;
+}
+
 int apv_comm_unique_id(char id_out[128]) {
     if (!id_out) return APV_ERR_ARG;
     ncclUniqueId id;

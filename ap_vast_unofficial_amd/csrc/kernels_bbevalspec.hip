@@ -28,6 +28,9 @@
 // The scratch has a fixed byte budget (APV_BBSPEC_SCRATCH_BYTES, at least one hop): a group of hops runs as consecutive
 // sub-launches of as many hops as fit, which by the property of 3 changes no bit.
 //
+// With the detectability switch (apv_bb_set_evaluation_detectability) the three hop-batched launches of kernels_evaldetect.hip
+// follow 3 inside every sub-launch, on the scratch the next sub-launch overwrites; their bits do not depend on c either.
+//
 // Bounds: every access of 1 and 3 is predicated; H, Mv, N and c need not be multiples of anything.  Nothing is read past
 // [sets][n H][Mv] pressures, the old line's [sets Mv][old length] and [c][K][sets Mv] spectra; nothing is written past
 // [sets Mv][N - H + c H] line samples and the totals.
@@ -105,6 +108,31 @@ int apv_bbspec_hops_fit(int N, int Z, int E, int Mv) {
     return (int)std::min<size_t>(std::max<size_t>(APV_BBSPEC_SCRATCH_BYTES / hop, 1), 65535);
 }
 
+// the detectability of the c hops whose spectra stand at `spec`, hops i0 .. i0 + c - 1 of the call
+static hipError_t bbspec_detect(const BbSpecDetectArgs& d, const void* spec, int i0, int c, int N, int Z, int E, int Mv, hipStream_t s,
+                                std::string* why) {
+    EvalDetectHopsArgs a{};
+    a.spec = spec; a.G2T = d.G2T; a.quiet = d.quiet; a.curves = d.curves; a.part = d.part; a.rec = d.rec; a.totals = d.totals;
+    a.slot0 = d.slot0 + i0; a.n = c; a.N = N; a.Z = Z; a.E = E; a.Mv = Mv; a.C = d.C;
+    a.Cs = d.Cs; a.Ca = d.Ca; a.Leff = d.Leff;
+    return apv_launch_eval_detect_hops(a, s, why);
+}
+
+hipError_t apv_launch_bbspec_detect_hops(const BbSpecDetectArgs& d, const void* spec, int n, int per_launch, int N, int Z, int E, int Mv,
+                                         hipStream_t s, std::string* why) {
+    if (!spec || n < 1 || per_launch < 1 || per_launch > 65535) {
+        if (why) *why = "evaluation detectability: null spectra, no hops, or 0 hops per launch";
+        return hipErrorInvalidValue;
+    }
+    const size_t hop = sizeof(double) * 2 * ((size_t)N / 2 + 1) * Z * (2 * (size_t)E + 1) * Mv;
+    for (int i0 = 0; i0 < n; i0 += per_launch) {
+        const hipError_t e = bbspec_detect(d, static_cast<const char*>(spec) + (size_t)i0 * hop, i0, std::min(per_launch, n - i0), N, Z, E,
+                                           Mv, s, why);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t apv_launch_bbspec_hops(BbSpecArgs* a, hipStream_t s, std::string* why) {
     if (!apv_bbspec_size_ok(a->N, a->H, a->Z, a->E, a->Mv, why)) return hipErrorInvalidValue;
     const int tail = a->N - a->H;
@@ -135,6 +163,11 @@ hipError_t apv_launch_bbspec_hops(BbSpecArgs* a, hipStream_t s, std::string* why
                            static_cast<const double2*>(a->spec), a->totals, a->Z, a->E, K, a->Mv, c);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
+        if (a->detect) {
+            // on this sub-launch's spectra, before the next one overwrites them
+            e = bbspec_detect(*a->detect, a->spec, i0, c, a->N, a->Z, a->E, a->Mv, s, why);
+            if (e != hipSuccess) return e;
+        }
     }
     return hipSuccess;
 }

@@ -31,6 +31,14 @@
 // No atomics, every combination order fixed: the bits depend on the sizes and the data alone.  Bounds: every access is predicated;
 // K, Mv, E, C need not be multiples of anything.  Nothing is read past [K][Z (2 E + 1) Mv] spectra, [C][K] table entries and
 // [K][Z Mv] curves, nothing written past the curves, [chunks][Z][2 E][Mv] partial sums, the record's slots and the totals.
+//
+// The hop-batched forms (apv_launch_eval_detect_hops; the broadband stream, whose scratch holds the spectra of c consecutive hops
+// [c][K][Z (2 E + 1) Mv]) are the same three bodies with the hop as one more grid coordinate: c Z Mv curve workgroups into curves
+// [c][K][Z Mv], the reduction's workgroups c times over into part [c][chunks][Z][2 E][Mv] -- chunks and the slice walk are those of
+// one hop, so a hop's partial sums do not know the launch they are in --, and ONE update launch whose threads walk the c hops in
+// order: chunks ascending, the record's slot slot0 + i (a launch argument), then sum, max and count carried in registers.  The bits
+// of a hop and of the totals therefore depend on the sizes, the data and the hop order alone, and at c = 1 they are those of the
+// per-hop launches: both forms compile the same device functions.
 #include "apv_internal.h"
 
 #include <algorithm>
@@ -41,16 +49,15 @@ constexpr int ED_T = 16;                       // microphones of a workgroup of 
 constexpr int ED_FILL = 256;                   // workgroups the reduction aims for: one per CU
 constexpr int ED_CT = 1024;                    // threads of a workgroup of the curve kernel
 
-__global__ void __launch_bounds__(ED_CT) eval_detect_curve_kernel(const double2* __restrict__ spec, int Z, int E, int K, int Mv, int C,
-                                                                const double* __restrict__ G2T, double Cs, double Ca, double Leff,
-                                                                double f, double* __restrict__ curves, long c_k,
-                                                                unsigned long long* __restrict__ ctl) {
+// the curve of target column `col` = (z, m) of one hop's spectra (null: silence) into curves[k c_k + col]
+__device__ __forceinline__ void curve_column(const double2* __restrict__ spec, int Z, int E, int K, int Mv, int C,
+                                             const double* __restrict__ G2T, double Cs, double Ca, double Leff, double f,
+                                             double* __restrict__ curves, long c_k, int col) {
     extern __shared__ double ed_sm[];
     double* P2 = ed_sm;                        // [K]
     double* inv = ed_sm + K;                   // [C]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int z = blockIdx.x / Mv, m = blockIdx.x - z * Mv;
-    if (ctl && blockIdx.x == 0 && tid == 0) ctl[2] = ctl[2] + 1;     // no other thread of this launch reads it
+    const int z = col / Mv, m = col - z * Mv;
     if (spec) {
         const size_t row = (size_t)Z * (2 * E + 1) * Mv;
         const double2* __restrict__ t = spec + ((size_t)z * (2 * E + 1) + 2 * E) * Mv + m;
@@ -83,17 +90,36 @@ __global__ void __launch_bounds__(ED_CT) eval_detect_curve_kernel(const double2*
         double a = 0.0;
 #pragma unroll 4
         for (int c = 0; c < C; ++c) a += G2T[(size_t)c * K + k] * inv[c];
-        curves[(size_t)k * c_k + blockIdx.x] = a * scale;
+        curves[(size_t)k * c_k + col] = a * scale;
     }
 }
 
-__global__ void __launch_bounds__(256) eval_detect_reduce_kernel(const double2* __restrict__ spec, const double* __restrict__ curves,
-                                                                 const double* __restrict__ quiet, double* __restrict__ part, int Z,
-                                                                 int E, int K, int Mv, int kc, double f) {
+__global__ void __launch_bounds__(ED_CT) eval_detect_curve_kernel(const double2* __restrict__ spec, int Z, int E, int K, int Mv, int C,
+                                                                const double* __restrict__ G2T, double Cs, double Ca, double Leff,
+                                                                double f, double* __restrict__ curves, long c_k,
+                                                                unsigned long long* __restrict__ ctl) {
+    if (ctl && blockIdx.x == 0 && threadIdx.x == 0) ctl[2] = ctl[2] + 1;     // no other thread of this launch reads it
+    curve_column(spec, Z, E, K, Mv, C, G2T, Cs, Ca, Leff, f, curves, c_k, (int)blockIdx.x);
+}
+
+// the hop-batched form: workgroup (column, hop) of spec [c][K][Z (2 E + 1) Mv] into curves [c][K][Z Mv]
+__global__ void __launch_bounds__(ED_CT) eval_detect_curve_hops_kernel(const double2* __restrict__ spec, int Z, int E, int K, int Mv, int C,
+                                                                     const double* __restrict__ G2T, double Cs, double Ca, double Leff,
+                                                                     double f, double* __restrict__ curves) {
+    const size_t c_k = (size_t)Z * Mv, hop = blockIdx.y;
+    curve_column(spec + hop * K * ((size_t)Z * (2 * E + 1) * Mv), Z, E, K, Mv, C, G2T, Cs, Ca, Leff, f, curves + hop * K * c_k,
+                 (long)c_k, (int)blockIdx.x);
+}
+
+// the partial sums of microphone group mg of (program, rank) zy over the bins of chunk ch of one hop: spec, curves and part are
+// the hop's own
+__device__ __forceinline__ void reduce_chunk(const double2* __restrict__ spec, const double* __restrict__ curves,
+                                             const double* __restrict__ quiet, double* __restrict__ part, int Z, int E, int K, int Mv,
+                                             int kc, double f, int mg, int zy, int ch) {
     __shared__ double red[2][ED_T][ED_T + 1];
     const int tid = threadIdx.x, ml = tid & 15, sl = tid >> 4;
-    const int z = blockIdx.y / E, e = blockIdx.y - z * E, m = blockIdx.x * ED_T + ml;
-    const int k0 = 1 + (int)blockIdx.z * kc, k1 = min(K, k0 + kc);
+    const int z = zy / E, e = zy - z * E, m = mg * ED_T + ml;
+    const int k0 = 1 + ch * kc, k1 = min(K, k0 + kc);
     double err = 0.0, leak = 0.0;
     if (m < Mv) {
         const size_t row = (size_t)Z * (2 * E + 1) * Mv, cw = (size_t)Z * Mv;
@@ -122,8 +148,32 @@ __global__ void __launch_bounds__(256) eval_detect_reduce_kernel(const double2* 
     }
     if (sl < 2 && m < Mv) {
         const size_t items = (size_t)Z * 2 * E * Mv;
-        part[(size_t)blockIdx.z * items + ((size_t)z * 2 * E + (size_t)sl * E + e) * Mv + m] = red[sl][0][ml];
+        part[(size_t)ch * items + ((size_t)z * 2 * E + (size_t)sl * E + e) * Mv + m] = red[sl][0][ml];
     }
+}
+
+__global__ void __launch_bounds__(256) eval_detect_reduce_kernel(const double2* __restrict__ spec, const double* __restrict__ curves,
+                                                                 const double* __restrict__ quiet, double* __restrict__ part, int Z,
+                                                                 int E, int K, int Mv, int kc, double f) {
+    reduce_chunk(spec, curves, quiet, part, Z, E, K, Mv, kc, f, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+}
+
+// the hop-batched form: blockIdx.x = hop x microphone groups + group, so that the hops are bounded by 2^31 and not by 65535;
+// spec [c][K][Z (2 E + 1) Mv], curves [c][K][Z Mv], part [c][chunks][Z][2 E][Mv]
+__global__ void __launch_bounds__(256) eval_detect_reduce_hops_kernel(const double2* __restrict__ spec, const double* __restrict__ curves,
+                                                                      const double* __restrict__ quiet, double* __restrict__ part, int Z,
+                                                                      int E, int K, int Mv, int kc, double f, int groups) {
+    const size_t hop = blockIdx.x / (unsigned)groups;
+    const int mg = (int)(blockIdx.x - hop * groups);
+    reduce_chunk(spec + hop * K * ((size_t)Z * (2 * E + 1) * Mv), curves + hop * K * ((size_t)Z * Mv), quiet,
+                 part + hop * gridDim.z * ((size_t)Z * 2 * E * Mv), Z, E, K, Mv, kc, f, mg, (int)blockIdx.y, (int)blockIdx.z);
+}
+
+// sum, max and count of D > 1 of element `it` of a hop, one hop later
+__device__ __forceinline__ void fold_hop(double d, double& sum, double& mx, double& cnt) {
+    sum = sum + d;
+    mx = d > mx ? d : mx;
+    cnt = cnt + (d > 1.0 ? 1.0 : 0.0);
 }
 
 __global__ void __launch_bounds__(256) eval_detect_update_kernel(const double* __restrict__ part, int chunks, double* __restrict__ hop,
@@ -142,9 +192,34 @@ __global__ void __launch_bounds__(256) eval_detect_update_kernel(const double* _
     const int kind = j / E, e = j - kind * E;
     double* __restrict__ tz = totals + (((size_t)z * 6 + 3 * kind) * E + e) * Mv + m;
     const size_t plane = (size_t)E * Mv;
-    tz[0] = tz[0] + d;
-    tz[plane] = d > tz[plane] ? d : tz[plane];
-    tz[2 * plane] = tz[2 * plane] + (d > 1.0 ? 1.0 : 0.0);
+    double sum = tz[0], mx = tz[plane], cnt = tz[2 * plane];
+    fold_hop(d, sum, mx, cnt);
+    tz[0] = sum;
+    tz[plane] = mx;
+    tz[2 * plane] = cnt;
+}
+
+// the hop-batched form: the n hops of part [n][chunks][Z][2 E][Mv] in order, hop i into slot slot0 + i of rec
+__global__ void __launch_bounds__(256) eval_detect_update_hops_kernel(const double* __restrict__ part, int chunks, double* __restrict__ rec,
+                                                                      long long slot0, double* __restrict__ totals, int Z, int E,
+                                                                      int Mv, int n) {
+    const size_t items = (size_t)Z * 2 * E * Mv, it = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (it >= items) return;
+    const int m = (int)(it % Mv), j = (int)((it / Mv) % (2 * E)), z = (int)(it / ((size_t)Mv * 2 * E));
+    const int kind = j / E, e = j - kind * E;
+    double* __restrict__ tz = totals + (((size_t)z * 6 + 3 * kind) * E + e) * Mv + m;
+    const size_t plane = (size_t)E * Mv;
+    double sum = tz[0], mx = tz[plane], cnt = tz[2 * plane];
+    for (int i = 0; i < n; ++i) {
+        const double* __restrict__ ph = part + (size_t)i * chunks * items + it;
+        double d = 0.0;
+        for (int c = 0; c < chunks; ++c) d += ph[(size_t)c * items];
+        rec[((size_t)slot0 + i) * items + it] = d;
+        fold_hop(d, sum, mx, cnt);
+    }
+    tz[0] = sum;
+    tz[plane] = mx;
+    tz[2 * plane] = cnt;
 }
 
 size_t curve_lds(int K, int C) { return sizeof(double) * ((size_t)K + C); }
@@ -201,5 +276,33 @@ hipError_t apv_launch_eval_detect(const EvalDetectArgs& a, hipStream_t s, std::s
     const size_t items = (size_t)a.Z * 2 * a.E * a.Mv;
     hipLaunchKernelGGL(eval_detect_update_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a.part, chunks, a.hop, a.ctl,
                        a.totals, a.Z, a.E, a.Mv);
+    return hipGetLastError();
+}
+
+hipError_t apv_launch_eval_detect_hops(const EvalDetectHopsArgs& a, hipStream_t s, std::string* why) {
+    if (!apv_eval_detect_size_ok(a.N, a.Z, a.E, a.Mv, a.C, why)) return hipErrorInvalidValue;
+    if (!a.spec || !a.G2T || !a.curves || !a.part || !a.totals || !a.rec || (a.Z == 1 && !a.quiet) || a.slot0 < 0) {
+        if (why) *why = "evaluation detectability: null device pointer or a negative slot";
+        return hipErrorInvalidValue;
+    }
+    const long long groups = (a.Mv + ED_T - 1) / ED_T;
+    if (a.n < 1 || a.n > 65535 || groups * a.n > 0x7fffffffll) {
+        if (why) *why = "evaluation detectability: 1..65535 hops per launch, hops x ceil(Mv / 16) below 2^31";
+        return hipErrorInvalidValue;
+    }
+    const int K = a.N / 2 + 1, chunks = apv_eval_detect_chunks(a.N, a.Z, a.E, a.Mv), kc = (K - 1 + chunks - 1) / chunks;
+    const double f = 2.0 / ((double)a.N * (double)a.N);
+    const double2* spec = static_cast<const double2*>(a.spec);
+    hipLaunchKernelGGL(eval_detect_curve_hops_kernel, dim3((unsigned)(a.Z * a.Mv), (unsigned)a.n), dim3(ED_CT), curve_lds(K, a.C), s, spec,
+                       a.Z, a.E, K, a.Mv, a.C, a.G2T, a.Cs, a.Ca, a.Leff, f, a.curves);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(eval_detect_reduce_hops_kernel, dim3((unsigned)(groups * a.n), (unsigned)(a.Z * a.E), (unsigned)chunks), dim3(256),
+                       0, s, spec, a.curves, a.quiet, a.part, a.Z, a.E, K, a.Mv, kc, f, (int)groups);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const size_t items = (size_t)a.Z * 2 * a.E * a.Mv;
+    hipLaunchKernelGGL(eval_detect_update_hops_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a.part, chunks, a.rec,
+                       (long long)a.slot0, a.totals, a.Z, a.E, a.Mv, a.n);
     return hipGetLastError();
 }

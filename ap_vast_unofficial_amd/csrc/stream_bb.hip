@@ -128,7 +128,19 @@ struct apv_bb {
     double* bs_line[2];           // [sets Mv][N - H + bs_hops H], alternating
     void* bs_spec;                // [bs_hops][K][sets Mv] complex128, the transforms' bin-major scratch
     double* bs_tot;               // [Z][3 E + 1][K][Mv]
-    ApvOwned own;          // every buffer, pinned block, event and stream above: made through it, freed by it
+    // perceptual detectability behind those spectra (apv_bb_set_evaluation_detectability, kernels_evaldetect.hip, hop-batched);
+    // bd_on = 0: off, nothing below exists
+    int bd_on;
+    int bd_C;                     // channels of the model
+    double bd_Cs, bd_Ca, bd_Leff;
+    double* bd_G2T;               // [bd_C][K]: the squared channel responses, channel-major
+    double* bd_quiet;             // [K]: the curve of a silent masker (read with one zone program), formed once
+    double* bd_curves;            // [bs_hops][K][Z Mv]: the squared weighting curves of a sub-launch's hops
+    double* bd_part;              // [bs_hops][chunks][Z][2 E][Mv]: their partial sums
+    double* bd_tot;               // [Z][6 E][Mv]: per program sum, max and count of D > 1 of the error, then of the leak
+    double* bd_rec;               // [bd_cap] slots of [Z][2 E][Mv]: the values of every hop of the last call
+    int bd_cap, bd_nrec;          // slots allocated; slots the last call filled
+    ApvOwned own;         // every buffer, pinned block, event and stream above: made through it, freed by it
 };
 
 namespace {
@@ -654,10 +666,36 @@ static int bb_evaluate(apv_handle* h, apv_bb* s, const double* d_out, size_t gst
         sp.line[0] = s->bs_line[0]; sp.line[1] = s->bs_line[1]; sp.cur = s->bs_cur; sp.len = s->bs_len;
         sp.spec = s->bs_spec; sp.totals = s->bs_tot;
         sp.N = s->N; sp.H = H; sp.Z = s->be_Z; sp.E = s->be_E; sp.Mv = s->be_Mv; sp.n = n; sp.per_launch = s->bs_hops;
+        BbSpecDetectArgs det{};
+        if (s->bd_on) {
+            // and their detectability, inside every sub-launch: the record's slots are those of the energies
+            if (slot0 + n > s->bd_cap) return apv_fail(h, APV_ERR_STATE, "evaluation detectability: record smaller than the launch");
+            det.G2T = s->bd_G2T; det.quiet = s->bd_quiet; det.curves = s->bd_curves; det.part = s->bd_part;
+            det.rec = s->bd_rec; det.totals = s->bd_tot; det.slot0 = slot0; det.C = s->bd_C;
+            det.Cs = s->bd_Cs; det.Ca = s->bd_Ca; det.Leff = s->bd_Leff;
+            sp.detect = &det;
+        }
         e = apv_launch_bbspec_hops(&sp, st, &why);
         s->bs_cur = sp.cur; s->bs_len = sp.len;
         if (e != hipSuccess) return apv_fail(h, e == hipErrorInvalidValue ? APV_ERR_ARG : APV_ERR_HIP, why.empty() ? hipGetErrorString(e) : why);
+        if (s->bd_on) s->bd_nrec = slot0 + n;
     }
+    return APV_OK;
+}
+
+// curves and partial sums of the detectability for sub-launches of c hops: scratch, nothing of it outlives a sub-launch.  Called
+// with nothing of the stage in flight.
+static int bb_detect_scratch(apv_handle* h, apv_bb* s, int c) {
+    const size_t cols = (size_t)s->be_Z * s->be_Mv, items = cols * 2 * s->be_E;
+    double *curves = nullptr, *part = nullptr;
+    if (s->own.device(&curves, sizeof(double) * (size_t)c * s->K * cols) != hipSuccess ||
+        s->own.device(&part, sizeof(double) * (size_t)c * apv_eval_detect_chunks(s->N, s->be_Z, s->be_E, s->be_Mv) * items) != hipSuccess) {
+        s->own.release(curves);
+        return apv_fail(h, APV_ERR_HIP, "evaluation detectability: out of device memory for the curves of a sub-launch");
+    }
+    s->own.release(s->bd_curves);
+    s->own.release(s->bd_part);
+    s->bd_curves = curves; s->bd_part = part;
     return APV_OK;
 }
 
@@ -666,6 +704,10 @@ static int bb_evaluate(apv_handle* h, apv_bb* s, const double* d_out, size_t gst
 static int bb_spec_reserve(apv_handle* h, apv_bb* s, int group) {
     const int c = std::min(group, apv_bbspec_hops_fit(s->N, s->be_Z, s->be_E, s->be_Mv));
     if (c <= s->bs_hops) return APV_OK;
+    if (s->bd_on) {
+        const int rc = bb_detect_scratch(h, s, c);           // first: on failure the spectra keep their sub-launch
+        if (rc != APV_OK) return rc;
+    }
     hipStream_t st = h->stream;
     const size_t ch = (size_t)s->be_sets * s->be_Mv, row = (size_t)s->N - s->H + (size_t)c * s->H;
     double* line[2] = {nullptr, nullptr};
@@ -706,6 +748,15 @@ static int bb_eval_reserve(apv_handle* h, apv_bb* s, int n_hops, int group) {
         BCHK(h, apv_eval_pressure_prepare(1, s->be_Pv, group * s->H, s->L));
     }
     s->be_nrec = 0;
+    if (s->bd_on) {
+        if (n_hops > s->bd_cap) {
+            s->own.release(s->bd_rec);
+            s->bd_cap = 0;
+            BCHK(h, s->own.zeroed(&s->bd_rec, (size_t)s->be_Z * 2 * s->be_E * s->be_Mv * n_hops, sizeof(double), h->stream));
+            s->bd_cap = n_hops;
+        }
+        s->bd_nrec = 0;
+    }
     return s->bs_on ? bb_spec_reserve(h, s, group) : APV_OK;
 }
 
@@ -728,6 +779,16 @@ static void bb_spec_free(apv_bb* s) {
     s->own.release(s->bs_tot);
     s->bs_on = s->bs_hops = s->bs_cur = 0;
     s->bs_len = 0;
+}
+
+static void bb_detect_free(apv_bb* s) {
+    s->own.release(s->bd_G2T);
+    s->own.release(s->bd_quiet);
+    s->own.release(s->bd_curves);
+    s->own.release(s->bd_part);
+    s->own.release(s->bd_tot);
+    s->own.release(s->bd_rec);
+    s->bd_on = s->bd_C = s->bd_cap = s->bd_nrec = 0;
 }
 
 // Evaluation stage of the broadband stream: see include/apvast_hip.h.
@@ -823,8 +884,49 @@ int apv_bb_set_evaluation_spectra(apv_handle* h, int32_t on) {
     return APV_OK;
 }
 
+// Perceptual detectability behind the per-bin spectra: see include/apvast_hip.h.
+int apv_bb_set_evaluation_detectability(apv_handle* h, int32_t n_channels, const double* h_G2, double Cs, double Ca, double Leff) {
+    if (!h || !h->bb) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation_detectability: apv_bb_init has not been called");
+    apv_bb* s = h->bb;
+    if (!s->bs_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation_detectability: needs apv_bb_set_evaluation_spectra");
+    if (s->bd_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_set_evaluation_detectability: the stream keeps its detectabilities already");
+    if (n_channels < 1 || n_channels > 512 || !h_G2) return apv_fail(h, APV_ERR_ARG, "evaluation detectability: a table of 1..512 channels");
+    if (!std::isfinite(Cs) || !std::isfinite(Ca) || !std::isfinite(Leff) || !(Ca > 0.0))
+        return apv_fail(h, APV_ERR_ARG, "evaluation detectability: Cs, Ca and Leff must be finite, Ca positive");
+    const int K = s->K, Cn = n_channels;
+    for (size_t i = 0; i < (size_t)K * Cn; ++i)
+        if (!std::isfinite(h_G2[i])) return apv_fail(h, APV_ERR_ARG, "evaluation detectability: the table must be finite");
+    std::string why;
+    if (!apv_eval_detect_size_ok(s->N, s->be_Z, s->be_E, s->be_Mv, Cn, &why)) return apv_fail(h, APV_ERR_ARG, why);
+    BCHK(h, hipSetDevice(h->device));
+    BCHK(h, hipStreamSynchronize(h->stream));
+    struct Guard { apv_bb* s; bool ok; ~Guard() { if (!ok) bb_detect_free(s); } } built{s, false};
+    hipStream_t st = h->stream;
+    std::vector<double> gt((size_t)Cn * K);                  // channel-major, as the curve kernel streams it
+    for (int k = 0; k < K; ++k)
+        for (int i = 0; i < Cn; ++i) gt[(size_t)i * K + k] = h_G2[(size_t)k * Cn + i];
+    s->bd_C = Cn; s->bd_Cs = Cs; s->bd_Ca = Ca; s->bd_Leff = Leff;
+    BCHK(h, s->own.device(&s->bd_G2T, sizeof(double) * gt.size()));
+    BCHK(h, hipMemcpyAsync(s->bd_G2T, gt.data(), sizeof(double) * gt.size(), hipMemcpyHostToDevice, st));
+    BCHK(h, s->own.device(&s->bd_quiet, sizeof(double) * K));
+    const size_t items = (size_t)s->be_Z * 2 * s->be_E * s->be_Mv;
+    BCHK(h, s->own.zeroed(&s->bd_tot, 3 * items, sizeof(double), st));
+    // the record as large as the energies', curves and partial sums for the sub-launches the scratch holds now
+    const int cap = std::max(s->be_cap, 1);
+    BCHK(h, s->own.zeroed(&s->bd_rec, items * cap, sizeof(double), st));
+    s->bd_cap = cap;
+    const int rc = bb_detect_scratch(h, s, std::max(s->bs_hops, 1));
+    if (rc != APV_OK) return rc;
+    BCHK(h, apv_launch_eval_detect_quiet(s->N, Cn, s->bd_G2T, Cs, Ca, Leff, s->bd_quiet, st));
+    BCHK(h, hipStreamSynchronize(st));                       // gt may go
+    s->bd_nrec = 0;
+    s->bd_on = 1;
+    built.ok = true;
+    return APV_OK;
+}
+
 // "eval_totals" and both "eval_history" buffers to zero: the next hop's totals are its own energies; with the spectra on,
-// "eval_spectra" and "eval_ring" too
+// "eval_spectra" and "eval_ring" too, with the detectability on "eval_detect"
 int apv_bb_reset_evaluation(apv_handle* h) {
     if (!h || !h->bb || !h->bb->be_on) return apv_fail(h, APV_ERR_ARG, "apv_bb_reset_evaluation: no broadband stream with an evaluation stage");
     apv_bb* s = h->bb;
@@ -836,6 +938,7 @@ int apv_bb_reset_evaluation(apv_handle* h) {
         BCHK(h, hipMemsetAsync(s->bs_tot, 0, sizeof(double) * (size_t)s->be_Z * (3 * s->be_E + 1) * s->K * s->be_Mv, h->stream));
         BCHK(h, hipMemsetAsync(s->bs_line[s->bs_cur], 0, sizeof(double) * (size_t)s->be_sets * s->be_Mv * (size_t)s->bs_len, h->stream));
     }
+    if (s->bd_on) BCHK(h, hipMemsetAsync(s->bd_tot, 0, sizeof(double) * (size_t)s->be_Z * 6 * s->be_E * s->be_Mv, h->stream));
     BCHK(h, hipStreamSynchronize(h->stream));
     return APV_OK;
 }
@@ -1371,7 +1474,9 @@ static int bb_lookup(apv_handle* h, const char* name, double** d, size_t* count,
 // "eval_pressure" [Z][2 E + 1][H][Mv], the last hop's, and "eval_hops" [hops of the last call][Z][3 E + 1][Mv] are read-only;
 // "eval_totals" [Z][3 E + 1][Mv] and "eval_history" [Z][E + 1][Pv - 1][L] (the buffer the next launch reads) can be set.  With the
 // spectra on (apv_bb_set_evaluation_spectra) also "eval_spectra" [Z][3 E + 1][K][Mv] and "eval_ring" [Z (2 E + 1)][Mv][N], the
-// last N samples of every channel of the current line; both can be set, a set ring becoming the current line.
+// last N samples of every channel of the current line; both can be set, a set ring becoming the current line.  With the
+// detectability on (apv_bb_set_evaluation_detectability) also "eval_detect" [Z][6 E][Mv], which can be set, and "eval_detect_hops"
+// [hops of the last call][Z][2 E][Mv], read-only.
 struct BbEvalRef {
     double* d;
     size_t count;
@@ -1388,6 +1493,8 @@ static bool bb_eval_lookup(apv_bb* s, const char* name, BbEvalRef* r) {
     else if (is("eval_history")) *r = BbEvalRef{s->be_hist[s->be_cur], (size_t)s->be_nhist * (s->be_Pv - 1) * s->L, false, false};
     else if (s->bs_on && is("eval_spectra")) *r = BbEvalRef{s->bs_tot, slot * s->K, false, false};
     else if (s->bs_on && is("eval_ring")) *r = BbEvalRef{s->bs_line[s->bs_cur], (size_t)s->be_sets * s->be_Mv * s->N, false, false, true};
+    else if (s->bd_on && is("eval_detect")) *r = BbEvalRef{s->bd_tot, (size_t)s->be_Z * 6 * s->be_E * s->be_Mv, false, false};
+    else if (s->bd_on && is("eval_detect_hops")) *r = BbEvalRef{s->bd_rec, (size_t)s->be_Z * 2 * s->be_E * s->be_Mv * s->bd_nrec, true, false};
     else return false;
     return true;
 }

@@ -376,6 +376,17 @@ int  apv_eval_energies(apv_handle* h, const double* d_p, int32_t Z, int32_t E, i
  *                                                         replaces: nothing in the reference */
 int  apv_eval_spectra_hops(apv_handle* h, const double* d_pressure, double* d_tail, int32_t N, int32_t H, int32_t Z, int32_t E,
                            int32_t Mv, int32_t n_hops, int32_t hops_per_launch, double* d_totals);
+/* The three hop-batched launches of apv_bb_set_evaluation_detectability alone, on device pointers and the handle's stream: d_spec
+ * [n_hops][N/2 + 1][Z (2 E + 1) Mv] complex128, the bin-major spectra of n_hops consecutive hops (per program: bright of the E
+ * ranks, dark of the E ranks, target); h_G2 [N/2 + 1][n_channels] on the host.  Hop i's values go to d_hops [n_hops][Z][2 E][Mv]
+ * and, in hop order, into d_totals [Z][6 E][Mv] as for apv_eval_detect_step, whose bits a call with one hop reproduces.  The hops
+ * run as sub-launches of at most hops_per_launch, through the same loop the stream runs -- no bit depends on it.  The call uploads
+ * the tables, allocates and frees its scratch and synchronises.  APV_ERR_ARG (outputs untouched) for null pointers, sizes below 1,
+ * hops_per_launch < 1, odd N, Z > 2, n_channels > 512, non-finite constants, Ca <= 0 or N/2 + 1 + n_channels > 8192.
+ *                                                         replaces: nothing in the reference */
+int  apv_eval_detect_hops(apv_handle* h, const void* d_spec, int32_t n_hops, int32_t hops_per_launch, int32_t N, int32_t Z, int32_t E,
+                          int32_t Mv, int32_t n_channels, const double* h_G2, double Cs, double Ca, double Leff, double* d_hops,
+                          double* d_totals);
 
 /* ---- device memory / stream plumbing ----------------------------------- */
 int  apv_dev_alloc(apv_handle* h, size_t bytes, void** d_ptr);
@@ -649,7 +660,8 @@ int  apv_bb_set_state(apv_handle* h, const char* name, const double* h_src, size
 int  apv_bb_set_evaluation(apv_handle* h, int32_t Pv, int32_t Mv, const double* h_rvA, const double* h_rvB, int32_t n_ranks,
                            const int32_t* ranks);
 /* "eval_totals" and both history buffers to zero: the next hop's totals equal its own energies; with
- * apv_bb_set_evaluation_spectra also "eval_spectra" and "eval_ring".  APV_ERR_ARG without such a stream. */
+ * apv_bb_set_evaluation_spectra also "eval_spectra" and "eval_ring", with apv_bb_set_evaluation_detectability "eval_detect".
+ * APV_ERR_ARG without such a stream. */
 int  apv_bb_reset_evaluation(apv_handle* h);
 /* Per-bin spectra of the broadband stream's evaluation stage (off unless called with on = 1): the definition of
  * apv_stream_set_evaluation_spectra -- frames of N = block_size pressure samples, H = hop_size apart, under the stream's sine
@@ -668,6 +680,23 @@ int  apv_bb_reset_evaluation(apv_handle* h);
  * than 1, and for block_size > 4096 or any other size the float64 transforms refuse.
  *                                                         replaces: nothing in the reference (pwelch on the host) */
 int  apv_bb_set_evaluation_spectra(apv_handle* h, int32_t on);
+/* Perceptual detectability of the broadband stream's evaluated pressures: the definition of
+ * apv_stream_set_evaluation_detectability -- error and leak per hop, program, evaluated rank and validation microphone from the
+ * hop's spectra, f = 2 / N^2, the masker including bin 0, the sums over the bins 1.., the threshold in quiet as the leak's masker
+ * with one program, float64, no atomics -- behind the transforms of every (sub-)launch of the spectra stage, on their scratch,
+ * as three launches over all its hops (csrc/kernels_evaldetect.hip, the hop-batched forms).  The bits of a hop's values and of the
+ * totals depend on the sizes, the data and the hop order alone, so apv_bb_process_block and a group of apv_bb_process_signal agree
+ * bit for bit.  States only such a stream has:
+ *   "eval_detect"       [Z][6 E][Mv]: per program [sum | max | number of hops with D > 1] of the error of the E ranks, then the
+ *                       same three of the leak, since this call or the last reset (total = total + hop per hop); settable
+ *   "eval_detect_hops"  [n][Z][2 E][Mv], the n hops of the last apv_bb_process_* call since this one (the caller knows n): per
+ *                       program the error of the E ranks, then the leak; read-only
+ * apv_bb_reset_evaluation zeroes "eval_detect".  h_G2 [N/2 + 1][n_channels], Cs, Ca, Leff: the tables of the model
+ * (perceptual.PerceptualTables).  Called after apv_bb_set_evaluation_spectra, once, at any hop boundary: the totals start from zero
+ * there; ring, spectra and everything else go on untouched.  APV_ERR_ARG (nothing changed) without apv_bb_init, without
+ * apv_bb_set_evaluation_spectra, on a second call, for n_channels outside 1..512, a null table, a non-finite table entry or
+ * constant, Ca <= 0, or N/2 + 1 + n_channels > 8192.     replaces: Matlab/ControlMethods/perceptualModel.m:192-206, on the device */
+int  apv_bb_set_evaluation_detectability(apv_handle* h, int32_t n_channels, const double* h_G2, double Cs, double Ca, double Leff);
 
 /* ---- evaluation and the static solver, float64 ------------------------- */
 /* p[t][m] = sum_s filter(rir[:, s, m], 1, x[:, s])[t].  h_x [T][L], h_rir [P][L][M], h_out [T][M].

@@ -19,7 +19,13 @@ the run.
 two timings with the stage on against the stage on plus the spectra (on, spectra, on, spectra), at the reference's test
 parameters one more pair with all 50 ranks evaluated -- a hop's spectra are 20.7 MB there, so a group of 16 runs as sub-launches
 of three hops -- and contrast and NMSE per third-octave band at 48 kHz (recorded, not gated).  Replaces the section "Per-bin
-spectra" at the end of the same file."""
+spectra" of the same file.
+
+--detectability: the perceptual detectability on top of the spectra (apvast.enable_evaluation_detectability, the hop-batched
+launches of csrc/kernels_evaldetect.hip): the same two timings with stage + spectra against stage + spectra + detectability
+(spectra, detectability, spectra, detectability), and the mean detectability per hop and the audible share of hops of error and
+leak (evaluation.detectability_metrics; recorded, not gated).  Replaces the section "Detectability" at the end of the same
+file."""
 import argparse
 import json
 import os
@@ -51,7 +57,7 @@ def validation(a0, b0):
 
 
 def make(shape, stage, all_ranks=False):
-    """stage 0: off; 1: the evaluation stage; 2: the stage and its per-bin spectra"""
+    """stage 0: off; 1: the evaluation stage; 2: the stage and its per-bin spectra; 3: those and the detectability"""
     from ap_vast_unofficial_amd.apvast import apvast
     s = SHAPES[shape]
     a0, b0 = responses()
@@ -60,8 +66,10 @@ def make(shape, stage, all_ranks=False):
     if stage:
         va, vb = validation(a0, b0)
         ap.enable_evaluation(va, vb, None if all_ranks else [s["V"]])
-    if stage == 2:
+    if stage >= 2:
         ap.enable_evaluation_spectra()
+    if stage == 3:
+        ap.enable_evaluation_detectability()
     return ap
 
 
@@ -90,6 +98,11 @@ def leg_stream(shape, stage, all_ranks=False):
         m = metrics(ap.evaluation_totals())
         r.update(nmse=m["nmse"][:, -1].tolist(), contrast_db=m["contrast_db"][:, -1].tolist(), Pv=int(ap._eval_dims()[2]),
                  Mv=int(ap._eval_dims()[3]), E=int(ap._eval_dims()[1]))
+    if stage == 3:
+        from ap_vast_unofficial_amd.evaluation import detectability_metrics
+        d = detectability_metrics(ap.evaluation_detectability())
+        r.update(detect_hops=int(ap.evaluation_detectability()["hops"]), n_channels=int(ap.detectability_model.n_channels),
+                 **{k: v[:, -1].tolist() for k, v in d.items()})
     if stage == 2:
         from ap_vast_unofficial_amd.evaluation import spectral_metrics, third_octave_bands
         centres, bands = third_octave_bands(48000, s["N"], f_min=100.0, f_max=16000.0)
@@ -148,9 +161,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", choices=["stream", "kernels"])
     ap.add_argument("--shape", choices=list(SHAPES))
-    ap.add_argument("--stage", type=int, default=0, help="0: off, 1: the evaluation stage, 2: the stage and its per-bin spectra")
+    ap.add_argument("--stage", type=int, default=0,
+                    help="0: off, 1: the evaluation stage, 2: the stage and its per-bin spectra, 3: those and the detectability")
     ap.add_argument("--all-ranks", action="store_true", help="evaluate every rank instead of the largest")
     ap.add_argument("--spectra", action="store_true", help="the legs of the per-bin spectra (see the module docstring)")
+    ap.add_argument("--detectability", action="store_true", help="the legs of the detectability (see the module docstring)")
     ap.add_argument("--shapes", default="cfg1,reftest")
     ap.add_argument("--limit", type=int, default=240, help="seconds a leg may take")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "broadband_evaluation.md"))
@@ -163,6 +178,8 @@ def main():
         return
     if a.spectra:
         return main_spectra(a)
+    if a.detectability:
+        return main_detectability(a)
     lines = ["# Broadband stream: evaluation stage (`apvast.enable_evaluation`)", "",
              "Written by `tools/bench_broadband_evaluation.py`; every leg a fresh process, two runs per leg, alternating (off, on, off, on).",
              "Validation responses: the control responses plus 10 % independent noise; the largest rank evaluated (E = 1, both zone",
@@ -244,11 +261,57 @@ def main_spectra(a):
         lines += ["", f"Broadband, from the energies of the same leg: contrast {', '.join(f'{v:.2f}' for v in r['contrast_db'])} dB, NMSE "
                   f"{', '.join(f'{v:.4f}' for v in r['nmse'])}.", ""]
     old = open(a.out).read() if os.path.exists(a.out) else ""
-    notes = ""
+    notes = after = ""
+    if DETECT_MARK in old:                                   # the section behind this one stays
+        after = "\n" + old[old.index(DETECT_MARK):]
+        old = old[:old.index(DETECT_MARK)]
     if SPECTRA_MARK in old:
         block = old[old.index(SPECTRA_MARK):]
         old = old[:old.index(SPECTRA_MARK)]
         mark = "\n## Notes on the spectra"
+        if mark in block:
+            notes = block[block.index(mark):]
+    with open(a.out, "w") as f:
+        f.write(old.rstrip("\n") + "\n\n" + "\n".join(lines) + notes.rstrip("\n") + "\n" + after)
+    print("wrote", a.out)
+
+
+DETECT_MARK = "\n# Detectability"
+
+
+def main_detectability(a):
+    lines = [DETECT_MARK.strip("\n") + " (`apvast.enable_evaluation_detectability`)", "",
+             "Written by `tools/bench_broadband_evaluation.py --detectability`; every leg a fresh process, two runs per leg, alternating",
+             "(stage + spectra, stage + spectra + detectability, and again).  Same validation responses and calls as above; the model's",
+             "tables are `PerceptualTables(N, 48000, 94)`.  Times in ms per hop.", ""]
+    for shape in a.shapes.split(","):
+        s = SHAPES[shape]
+        runs = {2: [], 3: []}
+        for _ in range(2):
+            for stage in (2, 3):
+                runs[stage].append(child(["--leg", "stream", "--shape", shape, "--stage", str(stage)], a.limit))
+        sp, de = runs[2], runs[3]
+        hop = [[r["ms_per_hop"] for r in q] for q in (sp, de)]
+        sig = [[r["ms_per_hop_process_signal"] for r in q] for q in (sp, de)]
+        r = de[0]
+        fmt = lambda v, f: ", ".join(format(x, f) for x in v)
+        lines += [f"## {s['label']}", "",
+                  f"The largest rank evaluated (2 programs x {r['Mv']} microphones = {2 * r['Mv']} curves of K = {s['N'] // 2 + 1} bins and "
+                  f"{r['n_channels']} channels per hop, {4 * r['Mv']} weighted sums); {s['hops']} per-hop calls (median), `process_signal` "
+                  f"over {s['signal_hops']} hops.", "",
+                  "| | stage + spectra (two runs) | + detectability (two runs) | added, mean |", "|---|---|---|---|",
+                  f"| `process_input_buffers` | {rng_of(hop[0])} | {rng_of(hop[1])} | {np.mean(hop[1]) - np.mean(hop[0]):+.3f} |",
+                  f"| `process_signal` | {rng_of(sig[0])} | {rng_of(sig[1])} | {np.mean(sig[1]) - np.mean(sig[0]):+.3f} |", "",
+                  f"Detectability at rank {s['V']} over the {r['detect_hops']} hops of the `process_signal` leg, per zone program [A, B], mean "
+                  f"over the microphones (D = 1: just audible; recorded, not gated): `error_mean` {fmt(r['error_mean'], '.4g')}, `leak_mean` "
+                  f"{fmt(r['leak_mean'], '.4g')}; audible share of hops: error {fmt(r['error_audible_share'], '.3f')}, leak "
+                  f"{fmt(r['leak_audible_share'], '.3f')}.", ""]
+    old = open(a.out).read() if os.path.exists(a.out) else ""
+    notes = ""
+    if DETECT_MARK in old:
+        block = old[old.index(DETECT_MARK):]
+        old = old[:old.index(DETECT_MARK)]
+        mark = "\n## Notes on the detectability"
         if mark in block:
             notes = block[block.index(mark):]
     with open(a.out, "w") as f:
